@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the batched Truss.Solve() hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]     (N > 1: launched by torch.distributed.run)
+
+A plain run measures the headline only: set-up, the config-5 leg untimed (`--dataset-samples`), the W warm-up steps,
+the K timed steps, the outputs of the last timed step (`--dump-outputs DIR`), and a line with the headline's fields
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and how the run was set up).  `--full` runs
+everything described below as well: the other configurations' legs, the CPU baselines and the oracle check, the repeats, the
+per-stage and roofline figures and the informational legs; the options that size or switch those apply with it only
+(`--dataset-samples` sizes the untimed config-5 leg of a plain run as well).
 
 Workload (BASELINE.json configs[1]): the 942-bar truss (tests/golden/data/bar-942_input_0.json,
 n_free = 696) packed once and replicated to `--batch` (default 4096) INDEPENDENT problems per GPU,
@@ -10,11 +17,11 @@ the batch: joint order (found, applied and priced per truss, on the device) -> d
 recover (six calls through the C ABI); nothing is shared between the copies or carried over between steps.
 Weak scaling: every rank solves its own batch; no collective on the data path.
 
-Order of a run: the legs of configs 3 and 5 (each with a barrier-bracketed region of its own), then the headline - W
+Order of a `--full` run: the legs of configs 3 and 5 (each with a barrier-bracketed region of its own), then the headline - W
 warm-up steps in the form of the timed ones, the K timed steps between barriers (`value`), `--repeats` further repeats of
 that region (`repeats`: min / median / max) -, then the informational legs (`leg_order` in the line).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with these extra objects:
+Prints ONE JSON line on rank 0; with `--full` it carries these extra objects:
   roofline      dominant kernel (the factorisation with the fused substitution): algorithmic bytes or executed
                 tile FLOP / measured average launch duration (events recorded on the launch stream inside the
                 timed steps), the roof picked by arithmetic intensity; `frac_dense_8d` = SURVEY 8d's dense figure
@@ -48,6 +55,25 @@ if ROOT not in sys.path:
 PEAK_FP64_TFLOPS = 78.6
 PEAK_HBM_GBS = 8000.0
 STAGES = ("dofmap", "assemble", "potrf", "potrs", "recover")
+#: `--dump-outputs`: at most this many bytes in all; a larger batch is written as a fixed, seeded sample of its trusses
+DUMP_BYTES_MAX = 64 << 20
+DUMP_SEED = 0
+
+
+def dump_outputs(res, out_dir):
+    """`--dump-outputs DIR`: what the timed path hands its caller after its last step (`batch.BatchResult`: displace,
+    external [B, nJ_max, 3], internal [B, nM_max], info [B]) as DIR/<name>.npy in float64, and `truss_index.npy` = the
+    trusses written (all of them, or a sorted sample drawn with `DUMP_SEED` when they exceed `DUMP_BYTES_MAX`)."""
+    import numpy as np
+    arrays = {"displace": res.displace, "external": res.external, "internal": res.internal, "info": res.info}
+    B = int(res.info.shape[0])
+    per_truss = 8 * (1 + sum(int(np.prod(a.shape[1:], dtype=np.int64)) for a in arrays.values()))
+    keep = min(B, DUMP_BYTES_MAX // per_truss)
+    index = np.arange(B) if keep == B else np.sort(np.random.default_rng(DUMP_SEED).choice(B, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "truss_index.npy"), index.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a[index], dtype=np.float64))
 
 
 #: the sources that determine the factorisation kernel and what it reads (the PMC traffic record is about it)
@@ -1006,6 +1032,12 @@ def main():
     ap.add_argument("--oversubscribe", action="store_true",
                     help="allow more ranks than visible GPUs (ranks share devices round-robin; for testing "
                          "the multi-rank path on a 1-GPU box - the line then reports the devices really used)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the other configurations' legs, CPU baselines and oracle check, repeats, "
+                         "per-stage and roofline figures, informational legs (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step as DIR/<name>.npy (float64; at most 64 MB in all, a "
+                         "fixed seeded sample of the trusses beyond that)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))
@@ -1024,13 +1056,13 @@ def main():
     distributed = world > 1
     data = load_case(args.case)
     cpu_all = None
-    if world == 1 and not args.no_cpu_baseline and args.cpu_pool_seconds > 0:
+    if args.full and world == 1 and not args.no_cpu_baseline and args.cpu_pool_seconds > 0:
         try:  # forked workers: only safe while this process has not initialised the GPU
             cpu_all = cpu_baseline_all_cores(data, args.cpu_pool_seconds)
         except Exception as exc:  # informational only
             cpu_all = {"error": repr(exc)}
     cube_cpu = None
-    if world == 1 and not args.no_cpu_baseline and args.cube_batch > 0 and args.cube_cpu_seconds > 0:
+    if args.full and world == 1 and not args.no_cpu_baseline and args.cube_batch > 0 and args.cube_cpu_seconds > 0:
         try:  # (its all-cores part forks: before the GPU is initialised)
             cube_cpu = cube_cpu_baseline(args.cube_batch, args.cube_cpu_seconds, pool_too=args.cpu_pool_seconds > 0)
         except Exception as exc:
@@ -1081,7 +1113,7 @@ def main():
     # the median of its own 25 repeats; `leg_order` in the line says which way round it was).
     # the ragged workload of north_star (BASELINE config 3), on EVERY rank, with its own barrier-bracketed region
     cube = None
-    if args.cube_batch > 0:
+    if args.full and args.cube_batch > 0:
         torch.cuda.empty_cache()
         try:
             cube = cube_batch_leg(args, device, torch, batch, barrier, reduce_max, rank, world, cpu=cube_cpu)
@@ -1090,11 +1122,11 @@ def main():
             if distributed:
                 raise
     cube_strong = None
-    if args.cube_total > 0 and not (world == 1 and args.cube_total == args.cube_batch and isinstance(cube, dict)
-                                    and "value" in cube):
+    if args.full and args.cube_total > 0 and not (world == 1 and args.cube_total == args.cube_batch
+                                                  and isinstance(cube, dict) and "value" in cube):
         cube_strong = config3_strong_leg(args, device, torch, batch, barrier, reduce_max, gather, rank, world)
     dataset = None
-    if args.dataset_samples > 0:
+    if args.full and args.dataset_samples > 0:
         try:
             dataset = dataset_leg(args, device, torch, barrier, reduce_max, rank, world)
         except Exception as exc:
@@ -1102,8 +1134,13 @@ def main():
             if distributed:
                 raise
     data_strong = None
-    if args.dataset_total > 0 and world > 1:   # (N = 1: a late leg under the watchdog, like the other multi-stream legs)
+    if args.full and args.dataset_total > 0 and world > 1:   # (N = 1: a late leg under the watchdog, like the others)
         data_strong = config5_strong_leg(args, device, torch, barrier, reduce_max, gather, rank, world)
+    if not args.full and args.dataset_samples > 0:
+        # A plain run times the headline in the state a --full run times it in: behind the config-5 leg, run here untimed
+        # and its result dropped.  Without it the factorisation mostly ran ~4 % slower on some boxes (1.59-1.61 against
+        # 1.53-1.55 ms per step); five seconds of headline steps in its place did not help (clocks are not the cause).
+        dataset_leg(args, device, torch, barrier, reduce_max, rank, world)
     batch.release_workspaces()   # (the legs' slabs go back to the driver: the headline batch allocates on a clean device)
 
     packed = batch.pack_json([data]).replicate(args.batch)
@@ -1170,6 +1207,53 @@ def main():
         step(potrf_events=potrf_events[k])
     barrier()
     elapsed = time.perf_counter() - t0
+    res = dev.result()   # (what the last timed step computed: `--dump-outputs`, `info_nonzero`, the oracle check)
+    elapsed_min = reduce_max(elapsed, "min")   # (the fastest rank: imbalance between the ranks shows in the line)
+    elapsed = reduce_max(elapsed)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(res, args.dump_outputs)
+
+    def headline():
+        """The fields of the headline: the whole line of a plain run, the start of a `--full` one."""
+        return {
+            "metric": "truss solves/sec (batched Solve)",
+            "value": world * args.batch * args.steps / elapsed,
+            "unit": "solves/s",
+            "n_gpus": n_devices_used,
+            "ranks": world,
+            "timing_group": timing_group,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "rank_ms_per_step": {"min": elapsed_min / args.steps * 1e3, "max": elapsed / args.steps * 1e3},
+            "host_threads_per_rank": host_threads,
+            "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),   # (set to 8 by the package unless the caller chose)
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic: bundled bar-942 truss replicated as independent problems",
+            "config": {"workload": f"{args.case} x {args.batch} independent copies per GPU "
+                                   f"(nJ {nJ}, nM {nM}, n_free {n})",
+                       "batch_per_gpu": args.batch, "parallelism": f"batch-sharded x{world}, no collective",
+                       "joint_order": ("profile: trs_joint_order on the device INSIDE the timed step, for every truss "
+                                       "of every step (all coordinate sweeps, priced by the tile envelope); tile masks "
+                                       "formed every step, no launch hints; results in the given numbering"
+                                       if order_in_step else
+                                       (order or "given") + (" (found once per topology, before the timed region; results "
+                                                             "in the given numbering)" if order else ""))},
+            "info_nonzero": int((res.info != 0).sum()),
+            "envelope": not args.dense,
+        }
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     potrf_ms_timed = float(np.mean([e0.elapsed_time(e1) for e0, e1 in potrf_events]))
     # the spread of the headline: the same K-step region again and again (same calls, same brackets; the events of
     # the first region are recorded over - their times are taken already), max over the ranks per repeat
@@ -1187,12 +1271,8 @@ def main():
         step(all_events[k])
     torch.cuda.synchronize(device)
 
-    elapsed_min = reduce_max(elapsed, "min")   # (the fastest rank: imbalance between the ranks shows in the line)
-    elapsed = reduce_max(elapsed)
-
     stage_ms = {s: float(np.mean([all_events[k][i][0].elapsed_time(all_events[k][i][1])
                                   for k in range(args.steps)])) for i, s in enumerate(stages)}
-    res = dev.result()
 
     # reference point outside the timed region (rank 0): the same kernels with the envelope switched
     # off, i.e. the dense factorisation that SURVEY section 8d's FLOP figure describes
@@ -1283,7 +1363,6 @@ def main():
             pcie = {"error": repr(exc)}
 
     if rank == 0:
-        total_trusses = world * args.batch * args.steps
         potrf_s = potrf_ms_timed * 1e-3   # the dominant kernel, measured inside the timed region
         potrf_kernel = "trs_potrf_kernel"
         if dev.env is not None:
@@ -1371,35 +1450,10 @@ def main():
             return {"bound": "hbm", "achieved": gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s",
                     "frac": gbs / PEAK_HBM_GBS, "bytes_per_truss": bytes_per_truss}
 
-        line = {
-            "metric": "truss solves/sec (batched Solve)",
-            "value": total_trusses / elapsed,
-            "unit": "solves/s",
-            "n_gpus": n_devices_used,
-            "ranks": world,
-            "timing_group": timing_group,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "rank_ms_per_step": {"min": elapsed_min / args.steps * 1e3, "max": elapsed / args.steps * 1e3},
+        line = headline()
+        line.update({
             "repeats": repeat_stats(repeat_s, repeat_potrf_ms, args.steps, world * args.batch),
-            "host_threads_per_rank": host_threads,
             "leg_order": "cube_batch, dataset, then the headline (config 2) and the informational legs",
-            "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),   # (set to 8 by the package unless the caller chose)
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic: bundled bar-942 truss replicated as independent problems",
-            "config": {"workload": f"{args.case} x {args.batch} independent copies per GPU "
-                                   f"(nJ {nJ}, nM {nM}, n_free {n})",
-                       "batch_per_gpu": args.batch, "parallelism": f"batch-sharded x{world}, no collective",
-                       "joint_order": ("profile: trs_joint_order on the device INSIDE the timed step, for every truss "
-                                       "of every step (all coordinate sweeps, priced by the tile envelope); tile masks "
-                                       "formed every step, no launch hints; results in the given numbering"
-                                       if order_in_step else
-                                       (order or "given") + (" (found once per topology, before the timed region; results "
-                                                             "in the given numbering)" if order else ""))},
             "roofline": roofline,
             "stages_ms": stage_ms,
             "stages_ms_note": "event pairs around every stage, measured over an equal number of instrumented steps "
@@ -1416,9 +1470,7 @@ def main():
                                 "avg_launch_ms": stage_ms["potrs"]} if substituted
                                else hbm_stage("potrs", counts["potrs_bytes"])),
             "recover_roofline": hbm_stage("recover", counts["recover_bytes"]),
-            "info_nonzero": int((res.info != 0).sum()),
-            "envelope": not args.dense,
-        }
+        })
         # north_star's last sentence in ONE record: config 2 weak-scaled (the headline), config 3 and config 5
         # strong-scaled, each with the spread over the ranks - what a driver that runs this command at N = 1, 2, 4, 8
         # tabulates

@@ -135,3 +135,30 @@ def test_late_leg_watchdog_leaves_a_finished_leg_alone():
     guard.put(lambda: line.__setitem__("edge", {"ok": True}))
     time.sleep(0.5)                                          # (the watchdog thread has woken up and left by now)
     assert line == {"value": 1.0, "edge": {"ok": True}} and not guard._thread.is_alive()
+
+
+def test_dump_outputs_writes_float64_within_the_cap(tmp_path):
+    """`bench.dump_outputs` (`--dump-outputs DIR`): the arrays of a `BatchResult` as float64 .npy files; a batch above
+    `DUMP_BYTES_MAX` is written as a sorted sample of its trusses that is the same from run to run, a small one whole."""
+    import numpy as np
+    from python_stable_3d_truss_analysis_amd.batch import BatchResult
+    B, nJ, nM = 4096, 244, 942   # (the headline batch: bar-942 x 4096)
+    u = np.arange(B * nJ * 3, dtype=np.float64).reshape(B, nJ, 3)
+    res = BatchResult(u, -u, np.arange(B * nM, dtype=np.float64).reshape(B, nM), np.arange(B, dtype=np.int32) % 3)
+    outs = []
+    for k in range(2):
+        bench.dump_outputs(res, str(tmp_path / str(k)))
+        outs.append({n: np.load(tmp_path / str(k) / (n + ".npy"))
+                     for n in ("truss_index", "displace", "external", "internal", "info")})
+    a, b = outs
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_BYTES_MAX
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert all(np.array_equal(a[n], b[n]) for n in a)
+    idx = a["truss_index"].astype(np.int64)
+    assert 0 < len(idx) < B and np.all(np.diff(idx) > 0) and idx[-1] < B
+    assert np.array_equal(a["displace"], u[idx]) and np.array_equal(a["external"], -u[idx])
+    assert np.array_equal(a["internal"], res.internal[idx]) and np.array_equal(a["info"], res.info[idx])
+    small = BatchResult(u[:8], u[:8], res.internal[:8], res.info[:8])
+    bench.dump_outputs(small, str(tmp_path / "small"))
+    assert np.array_equal(np.load(tmp_path / "small" / "truss_index.npy"), np.arange(8.0))
+    assert np.array_equal(np.load(tmp_path / "small" / "internal.npy"), res.internal[:8])

@@ -94,7 +94,7 @@ def test_bench_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--batch", "256", "--no-cpu-baseline", "--no-pcie", "--cube-batch", "384", "--cube-steps", "2",
-           "--dataset-samples", "512", "--no-dense-ref", "--cube-total", "600", "--dataset-total", "700"]
+           "--dataset-samples", "512", "--no-dense-ref", "--cube-total", "600", "--dataset-total", "700", "--full"]
     if ndev < 2:
         cmd.append("--oversubscribe")
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
@@ -151,7 +151,7 @@ def test_bench_eight_ranks_smoke():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
            "--batch", "128", "--no-cpu-baseline", "--no-pcie", "--cube-batch", "256", "--cube-steps", "1",
-           "--dataset-samples", "256", "--no-dense-ref", "--cube-total", "2000", "--dataset-total", "3000"]
+           "--dataset-samples", "256", "--no-dense-ref", "--cube-total", "2000", "--dataset-total", "3000", "--full"]
     if ndev < 8:
         cmd.append("--oversubscribe")
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
@@ -162,8 +162,13 @@ def test_bench_eight_ranks_smoke():
     assert line["ranks"] == 8 and line["n_gpus"] == min(8, ndev)
     assert line["info_nonzero"] == 0 and line["value"] > 0
     assert line["rank_ms_per_step"]["min"] <= line["rank_ms_per_step"]["max"]
-    # (its share of the CPUs at most; torchrun's OMP_NUM_THREADS=1 for multi-process jobs wins where it is set)
-    assert 1 <= line["host_threads_per_rank"] <= max(1, available_cpus() // 8)
+    # (its share of the CPUs at most; torchrun's OMP_NUM_THREADS=1 for multi-process jobs wins where it is set, and an
+    # OMP_NUM_THREADS of the caller's environment wins over both in every rank: generate.set_host_thread_share)
+    omp = os.environ.get("OMP_NUM_THREADS")
+    if omp:
+        assert line["host_threads_per_rank"] == int(omp)
+    else:
+        assert 1 <= line["host_threads_per_rank"] <= max(1, available_cpus() // 8)
     cube = line["cube_batch"]
     assert "error" not in cube and cube["info_nonzero"] == 0 and cube["batch_per_gpu"] == 256
     assert cube["value"] > 0 and cube["rank_ms_per_step"]["min"] <= cube["rank_ms_per_step"]["max"]

@@ -1,11 +1,15 @@
-mkdir -p gpurun_out/r6
+#!/bin/bash
+# Three default-shaped `bench.py --full` runs back to back on one box, and their headline figures side by side.
+#   tools/bench_repeat.sh [OUT_DIR]      -> OUT_DIR/rep_{1,2,3}.json, .err   (default bench_out/repeat, git-ignored)
+OUT=${1:-bench_out/repeat}
+mkdir -p "$OUT"
 for k in 1 2 3; do
-  timeout 400 python bench.py --no-pcie --no-dense-ref --large-trusses 0 --dataset-total 0 > gpurun_out/r6/rep_$k.json 2> gpurun_out/r6/rep_$k.err
+  timeout 400 python bench.py --full --no-pcie --no-dense-ref --large-trusses 0 --dataset-total 0 > "$OUT/rep_$k.json" 2> "$OUT/rep_$k.err"
 done
-python - <<'PY'
-import json
+python - "$OUT" <<'PY'
+import json, sys
 for k in (1, 2, 3):
-    l = [x for x in open(f"gpurun_out/r6/rep_{k}.json") if x.startswith("{")]
+    l = [x for x in open(f"{sys.argv[1]}/rep_{k}.json") if x.startswith("{")]
     b = json.loads(l[0])
     r = b["repeats"]
     print(f"run {k}: value {b['value'] / 1e6:.3f} M (first region, {b['steps']} steps, {b['ms_per_step']:.4f} ms/step); repeats min/median/max "

@@ -31,5 +31,5 @@ timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_
 find $OUT/${TAG}_cube_stats -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/${TAG}_cube_kernel_stats.csv
 timeout 600 tools/cube_pmc.sh ${TAG}_cubepmc > /dev/null 2>&1
 cp $OUT/${TAG}_cubepmc/cube_pmc.txt $OUT/${TAG}_cube_pmc.txt
-timeout 900 python3 bench.py > $OUT/${TAG}_bench.json.log 2> $OUT/${TAG}_bench.err
+timeout 900 python3 bench.py --full > $OUT/${TAG}_bench.json.log 2> $OUT/${TAG}_bench.err
 ls -la $OUT/${TAG}_*.csv $OUT/${TAG}_*.json $OUT/${TAG}_*.txt $OUT/${TAG}_*.log 2>/dev/null | awk '{print $5, $9}'
