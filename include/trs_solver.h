@@ -469,6 +469,51 @@ int trs_solve_rows_tab(int B, int nJ_max, int nM_max, int n_max_bound, const dou
                        int32_t *info, void *work, int32_t *env, const int32_t *joint_out, const int64_t *out_rows,
                        int nJ_out_max, int nM_out_max, int32_t *info_out, int hints, void *stream);
 
+/* ---- Load cases: several right-hand sides per truss from ONE factorisation (csrc/cases.hip).  A truss is checked
+ * against several load cases that share its joints, members and supports (the reference's examples bar-47 and bar-72
+ * ship that way); only the loads differ.  The stages after trs_dofmap -> trs_assemble -> trs_potrf_batched (any
+ * load vector: the factor does not depend on it) are:
+ *
+ *   trs_gather_cases   the reduced right-hand sides of every case
+ *   trs_potrs_cases    L y = f, then U x = y, for every case against the factored slab
+ *   trs_recover_cases  u, f_ext and N of every case (trs_recover_tab_cases: its twin in the table member form -
+ *                      named with the form first, so that the set of `_tab` twins of the ABI 10 entry points stays as it is)
+ *
+ * Layout of the right-hand sides F (device, double): CASE-MAJOR [B][L][ld_f], ld_f >= slab_rows.  Row (b, k) holds
+ * the reduced vector of case k of truss b: entries c < n_free[b] the free DOFs in the order of free_index, entries
+ * n_free[b] <= c < n_pad zero (trs_gather_cases writes them; n_pad = round_up(n_free, 64)).  trs_potrs_cases
+ * overwrites the rows with the reduced displacements, so case k of the result is a valid `uf` of trs_recover:
+ * F + k * ld_f with ld_uf = L * ld_f - and trs_recover_cases gives bit for bit what trs_recover gives on that slice.
+ *
+ * loads [B][L][nJ_max][3] are in the CALLER's joint numbering; joint_in / joint_out (or NULL) is the joint order the
+ * batch was assembled in (trs_joint_order's perm: the old id of the joint that became joint j), the same array
+ * trs_recover takes as joint_out.  No load array has to be permuted by the caller, and results come back in the
+ * caller's numbering: u, f_ext [B][L][nJ_max][3], N [B][L][nM_max].
+ *
+ * trs_potrs_cases reads every stored tile of the factor once per direction per group of 16 cases (one wave per truss
+ * and group, v_mfma_f64_16x16x4_f64), inside the envelope only (env as from trs_assemble, or NULL for the dense mode),
+ * and works for every routing (narrow, wide, compact).  The result of case k does not depend on L or on the other
+ * cases, bit for bit.  The factorisation's status stays in its `info`: a truss with info[b] != 0 gets meaningless
+ * numbers, the others are unaffected.
+ * trs_recover_cases needs the tables of one truss in a CU's LDS: trs_recover_cases_fits(nJ_max, nM_max) says whether
+ * a batch shape qualifies (about 3000 joints with 4 members per joint); otherwise it returns hipErrorInvalidValue. */
+int trs_gather_cases(int B, int L, int nJ_max, const double *loads /* [B][L][nJ_max][3] */,
+                     const int32_t *free_index, const int32_t *n_free, const int32_t *nJ,
+                     const int32_t *joint_in /* [B][nJ_max] or NULL */, double *F /* out [B][L][ld_f] */, int ld_f,
+                     void *stream);
+int trs_potrs_cases(int B, int L, const int32_t *n_free, int ld, int slab_rows, const double *S /* factored */,
+                    double *F /* inout [B][L][ld_f] */, int ld_f, const int32_t *env /* or NULL */, void *stream);
+int trs_recover_cases_fits(int nJ_max, int nM_max);
+int trs_recover_cases(int B, int L, int nJ_max, int nM_max, const double *xyz, const int32_t *conn, const double *E,
+                      const double *A, const double *loads /* [B][L][nJ_max][3], caller's numbering */,
+                      const int32_t *free_index, const int32_t *nJ, const int32_t *nM, const double *F, int ld_f,
+                      double *u /* [B][L][nJ_max][3] */, double *f_ext /* [B][L][nJ_max][3] */,
+                      double *N /* [B][L][nM_max] */, const int32_t *joint_out /* [B][nJ_max] or NULL */, void *stream);
+int trs_recover_tab_cases(int B, int L, int nJ_max, int nM_max, const double *xyz, const uint16_t *conn16,
+                          const uint8_t *type_idx, const double *types, const double *loads, const int32_t *free_index,
+                          const int32_t *nJ, const int32_t *nM, const double *F, int ld_f, double *u, double *f_ext,
+                          double *N, const int32_t *joint_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,18 +28,20 @@ if "GPU_MAX_HW_QUEUES" not in _os.environ:
         _os.environ["GPU_MAX_HW_QUEUES"] = "8"
 
 from .type import GenerateMethod, LinkType, MemberType, MetapathType, SupportType, TaskType
-from .truss import Member, Truss
+from .truss import Member, Truss, load_cases_from_json
 from .utils import HipExtensionError, TrussNotStableError
 
 __all__ = ["Truss", "Member", "MemberType", "SupportType", "MetapathType", "TaskType",
            "LinkType", "GenerateMethod", "HipExtensionError", "TrussNotStableError",
            "solve_batch", "pack_trusses", "PackedBatch", "BatchResult", "RaggedSolver", "DeviceBatch",
-           "ShardedSolver", "solve_batch_sharded", "solve_batch_distributed"]
+           "ShardedSolver", "solve_batch_sharded", "solve_batch_distributed",
+           "solve_load_cases", "LoadCaseResult", "load_cases_from_json"]
 
 
 def __getattr__(name):
     # torch-dependent names are resolved lazily so that the model imports without torch
-    if name in ("solve_batch", "pack_trusses", "PackedBatch", "BatchResult", "RaggedSolver", "DeviceBatch"):
+    if name in ("solve_batch", "pack_trusses", "PackedBatch", "BatchResult", "RaggedSolver", "DeviceBatch",
+                "solve_load_cases", "LoadCaseResult"):
         from . import batch
         return getattr(batch, name)
     if name in ("ShardedSolver", "solve_batch_sharded", "solve_batch_distributed"):

@@ -65,6 +65,12 @@ SIGNATURES = {
                            _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "trs_solve_rows_tab": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _I,
                                 _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _P]),
+    # load cases (several right-hand sides per factorisation)
+    "trs_gather_cases": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "trs_potrs_cases": (_I, [_I, _I, _P, _I, _I, _P, _P, _I, _P, _P]),
+    "trs_recover_cases_fits": (_I, [_I, _I]),
+    "trs_recover_cases": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "trs_recover_tab_cases": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
 }
 
 #: must equal TRS_ABI_VERSION of include/trs_solver.h

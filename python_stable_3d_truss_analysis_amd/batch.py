@@ -753,6 +753,62 @@ class DeviceBatch:
                 (HINT_ALL_TILES if self.all_tiles and self.env is not None else 0) | self._wide_hint(),
                 self._stream()), what)
 
+    # -- several load cases from one factorisation (include/trs_solver.h "Load cases") ------------------
+    def factor(self):
+        """dofmap, assembly and Cholesky factorisation of the resident batch, asynchronous on the current stream: the
+        factor stays in the slab for any number of `solve_cases` calls (the batch's own `loads` ride along and are not
+        needed by them).  A batch on the fused small-system path keeps no factor: build it with `use_small=False`."""
+        if self.small:
+            raise ValueError("factor(): this batch takes the fused small-system kernel, which keeps no factor - "
+                             "build the DeviceBatch with use_small=False")
+        with self.torch.cuda.device(self.device):
+            self.dofmap()
+            self.assemble()
+            self.potrf()
+        self._factored = True
+
+    def solve_cases(self, loads, out=None):
+        """Gather, multi-case substitution and recovery on the resident factor (`factor()` first).  `loads`: float64
+        device tensor [B, L, nJ_max, 3] in the CALLER's joint numbering (a joint order applied to the batch is undone
+        on the device).  Returns a dict of device tensors u, f_ext [B, L, nJ_max, 3] and N [B, L, nM_max] (`out`: such
+        a dict to write into); `self.info` holds the factorisation's status per truss."""
+        t = self.torch
+        if not getattr(self, "_factored", False):
+            raise ValueError("solve_cases(): no factor - call factor() first")
+        if loads.dim() != 4 or tuple(loads.shape[:1]) + tuple(loads.shape[2:]) != (self.B, self.nJ_max, 3) \
+                or loads.dtype != t.float64 or loads.device != self.device:
+            raise ValueError(f"solve_cases(): loads must be float64 [B={self.B}, L, nJ_max={self.nJ_max}, 3] on {self.device}")
+        loads = loads.contiguous()
+        L = int(loads.shape[1])
+        if out is None:
+            out = {"u": t.zeros([self.B, L, self.nJ_max, 3], dtype=t.float64, device=self.device),
+                   "f_ext": t.zeros([self.B, L, self.nJ_max, 3], dtype=t.float64, device=self.device),
+                   "N": t.zeros([self.B, L, self.nM_max], dtype=t.float64, device=self.device)}
+        if self.B == 0 or L == 0:
+            return out
+        if not self.lib.trs_recover_cases_fits(self.nJ_max, self.nM_max):
+            raise HipExtensionError(f"solve_cases(): a truss of {self.nJ_max} joints / {self.nM_max} members exceeds the "
+                                    "LDS of the multi-case recovery (trs_recover_cases_fits)")
+        F = getattr(self, "cases_F", None)   # right-hand sides, case-major [B][L][ld_f], ld_f = self.rows
+        if F is None or int(F.shape[1]) != L:
+            F = t.empty([self.B, L, self.rows], dtype=t.float64, device=self.device)
+        jo = self.joint_out.data_ptr() if self.joint_out is not None else None
+        stream = self._stream()
+        with t.cuda.device(self.device):
+            _capi.check(self.lib.trs_gather_cases(self.B, L, self.nJ_max, loads.data_ptr(), self.free_index.data_ptr(),
+                                                  self.n_free.data_ptr(), self.nJ.data_ptr(), jo, F.data_ptr(),
+                                                  self.rows, stream), "trs_gather_cases")
+            _capi.check(self.lib.trs_potrs_cases(self.B, L, self.n_free.data_ptr(), self.ld, self.rows,
+                                                 self.S.data_ptr(), F.data_ptr(), self.rows, self._env_ptr(), stream),
+                        "trs_potrs_cases")
+            fn, what = (self.lib.trs_recover_tab_cases, "trs_recover_tab_cases") if self.table \
+                else (self.lib.trs_recover_cases, "trs_recover_cases")
+            _capi.check(fn(self.B, L, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *self._members(), loads.data_ptr(),
+                           self.free_index.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), F.data_ptr(), self.rows,
+                           out["u"].data_ptr(), out["f_ext"].data_ptr(), out["N"].data_ptr(), jo, stream), what)
+        self.cases_F = F   # (kept: the reduced displacements of the last call, and the buffer of the next)
+        return out
+
     def fitness(self, allow_stress, allow_displace, out=None):
         """(weight, stress_violation, displacement_violation) per truss, on device."""
         t = self.torch
@@ -2042,6 +2098,62 @@ def solve_batch_streamed(packed: PackedBatch, device=None, reorder=True, pool=No
                           lanes=lanes)
     solver.step()
     return solver.result()
+
+
+@dataclass
+class LoadCaseResult:
+    """Dense host results of `solve_load_cases`: displace/external [B, L, nJ_max, 3], internal [B, L, nM_max],
+    info [B] (0 ok, k>0: pivot k of the reduced stiffness matrix is not positive - the cases of that truss are
+    meaningless, the other trusses are unaffected)."""
+    displace: np.ndarray
+    external: np.ndarray
+    internal: np.ndarray
+    info: np.ndarray
+
+
+def solve_load_cases(trusses_or_packed, loads, device=None, reorder=False, options=None, max_slab_bytes=64 << 30,
+                     on_device=False, sections=None, use_envelope=True):
+    """Solve every truss of a batch under L load cases, factoring each truss ONCE: `loads` is [B, L, nJ_max, dim]
+    (numpy or torch; dim 2 or 3, a 2D load gets z = 0) in the caller's joint numbering; the packed batch's own `loads`
+    field is ignored.  Per size bucket (`size_buckets`, as `solve_batch`'s generic route) the trusses are uploaded,
+    ordered (`reorder`, any `order_plan`), assembled and factored once (`DeviceBatch.factor`), then all L cases are
+    gathered, substituted against the factor and recovered (`DeviceBatch.solve_cases`).  Returns a `LoadCaseResult`
+    (host arrays, or torch tensors on the device with `on_device=True`).  Either member form.  Batches of small
+    trusses go through the staged pipeline too (the fused small-system kernel keeps no factor).  `sections=` variants
+    are not combined with load cases (ValueError).  `use_envelope=False`: the dense mode (`DeviceBatch`)."""
+    if sections is not None:
+        raise ValueError("solve_load_cases: sections= variants cannot be combined with load cases")
+    packed = trusses_or_packed if isinstance(trusses_or_packed, PackedBatch) else pack_trusses(list(trusses_or_packed))
+    torch, dev = _require_gpu(device)
+    B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
+    if isinstance(loads, np.ndarray):
+        loads = torch.from_numpy(np.ascontiguousarray(loads, dtype=np.float64))
+    if loads.dim() != 4 or int(loads.shape[0]) != B or int(loads.shape[2]) != nJ_max or int(loads.shape[3]) not in (2, 3):
+        raise ValueError(f"solve_load_cases: loads must be [B={B}, L, nJ_max={nJ_max}, 2 or 3], got {tuple(loads.shape)}")
+    L = int(loads.shape[1])
+    loads = loads.to(device=dev, dtype=torch.float64)
+    if int(loads.shape[3]) == 2:
+        loads = torch.nn.functional.pad(loads, (0, 1))
+    loads = loads.contiguous()
+    u = torch.zeros([B, L, nJ_max, 3], dtype=torch.float64, device=dev)
+    f = torch.zeros([B, L, nJ_max, 3], dtype=torch.float64, device=dev)
+    N = torch.zeros([B, L, nM_max], dtype=torch.float64, device=dev)
+    info = torch.zeros([B], dtype=torch.int32, device=dev)
+    if B and L:
+        for idx in size_buckets(packed, max_slab_bytes):
+            sub = packed.take(idx).trimmed()
+            rows = torch.from_numpy(np.asarray(idx, dtype=np.int64)).to(dev)
+            db = DeviceBatch(sub, dev, use_envelope=use_envelope, use_small=False, reorder=reorder, options=options)
+            db.factor()
+            res = db.solve_cases(loads.index_select(0, rows)[:, :, :sub.nJ_max].contiguous())
+            u[rows, :, :sub.nJ_max] = res["u"]
+            f[rows, :, :sub.nJ_max] = res["f_ext"]
+            N[rows, :, :sub.nM_max] = res["N"]
+            info[rows] = db.info
+    if on_device:
+        return LoadCaseResult(u, f, N, info)
+    torch.cuda.synchronize(dev)
+    return LoadCaseResult(u.cpu().numpy(), f.cpu().numpy(), N.cpu().numpy(), info.cpu().numpy())
 
 
 def _is_pinned(packed):

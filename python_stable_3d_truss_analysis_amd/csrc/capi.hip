@@ -404,3 +404,50 @@ int trs_solve_rows_tab(int B, int nJ_max, int nM_max, int n_max_bound, const dou
 }
 
 }  // extern "C"
+
+// ---- load cases (include/trs_solver.h "Load cases"; csrc/cases.hip) ----
+extern "C" {
+int trs_gather_cases_launch(int, int, int, const double*, const int*, const int*, const int*, const int*, double*, int,
+                            hipStream_t);
+int trs_potrs_cases_launch(int, int, const int*, int, size_t, int, const double*, double*, int, const int*, hipStream_t);
+int trs_recover_cases_launch(int, int, int, int, const double*, const TrsMembers*, const double*, const int*, const int*,
+                             const int*, const double*, int, double*, double*, double*, const int*, hipStream_t);
+size_t trs_recover_cases_lds(int, int);
+
+int trs_gather_cases(int B, int L, int nJ_max, const double* loads, const int32_t* free_index, const int32_t* n_free,
+                     const int32_t* nJ, const int32_t* joint_in, double* F, int ld_f, void* stream) {
+    if (B < 0 || L < 0 || nJ_max < 0 || ld_f < 0) return (int)hipErrorInvalidValue;
+    return trs_gather_cases_launch(B, L, nJ_max, loads, free_index, n_free, nJ, joint_in, F, ld_f, (hipStream_t)stream);
+}
+
+int trs_potrs_cases(int B, int L, const int32_t* n_free, int ld, int slab_rows, const double* S, double* F, int ld_f,
+                    const int32_t* env, void* stream) {
+    if (B < 0 || L < 0 || bad_slab(ld, slab_rows) || ld_f < slab_rows) return (int)hipErrorInvalidValue;
+    return trs_potrs_cases_launch(B, L, n_free, ld, (size_t)slab_rows * ld, slab_rows, S, F, ld_f, env,
+                                  (hipStream_t)stream);
+}
+
+int trs_recover_cases_fits(int nJ_max, int nM_max) {
+    return nJ_max >= 0 && nM_max >= 0 && trs_recover_cases_lds(nJ_max, nM_max) <= 160 * 1024;
+}
+
+int trs_recover_cases(int B, int L, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* E,
+                      const double* A, const double* loads, const int32_t* free_index, const int32_t* nJ,
+                      const int32_t* nM, const double* F, int ld_f, double* u, double* f_ext, double* N,
+                      const int32_t* joint_out, void* stream) {
+    if (B < 0 || L < 0) return (int)hipErrorInvalidValue;
+    const TrsMembers mem = trs_members_general(conn, E, A);
+    return trs_recover_cases_launch(B, L, nJ_max, nM_max, xyz, &mem, loads, free_index, nJ, nM, F, ld_f, u, f_ext, N,
+                                    joint_out, (hipStream_t)stream);
+}
+
+int trs_recover_tab_cases(int B, int L, int nJ_max, int nM_max, const double* xyz, const uint16_t* conn16,
+                          const uint8_t* type_idx, const double* types, const double* loads, const int32_t* free_index,
+                          const int32_t* nJ, const int32_t* nM, const double* F, int ld_f, double* u, double* f_ext,
+                          double* N, const int32_t* joint_out, void* stream) {
+    if (B < 0 || L < 0 || (B > 0 && (!conn16 || !type_idx || !types))) return (int)hipErrorInvalidValue;
+    const TrsMembers mem = trs_members_table(conn16, type_idx, types);
+    return trs_recover_cases_launch(B, L, nJ_max, nM_max, xyz, &mem, loads, free_index, nJ, nM, F, ld_f, u, f_ext, N,
+                                    joint_out, (hipStream_t)stream);
+}
+}  // extern "C"

@@ -7,69 +7,11 @@
 // Also the constraint reductions the GA fitness needs (truss.py:166-168,429-462; ga.py:139-149).
 #include "trs_common.h"
 #include "../../include/trs_solver.h"
+#include "trs_recover.h"
 
 namespace {
 
-struct MemberGeom {
-    double len, c[3];
-};
-
-__device__ __forceinline__ MemberGeom member_geom(const double* X, int j0, int j1) {
-    MemberGeom g;
-    double d[3], len2 = 0.0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        d[a] = X[3 * j1 + a] - X[3 * j0 + a];
-        len2 += d[a] * d[a];
-    }
-    g.len = sqrt(len2);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) g.c[a] = d[a] / g.len;
-    return g;
-}
-
-// axial force of a member from the displacements of its end joints: N = (E A / L) c . (u1 - u0)
-__device__ __forceinline__ double member_axial(const MemberGeom& g, double EA, const double* u, int j0, int j1) {
-    const double k = EA / g.len;
-    double proj = 0.0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) proj += g.c[a] * (u[3 * j1 + a] - u[3 * j0 + a]);
-    return k * proj;
-}
-
-// The end force of member (g, axial) on its joint `end` (1: +N c on joint1, 0: -N c on joint0), added to a
-// running reaction sum.  ONE function with explicit fused multiply-adds for every path of the kernel: the paths
-// then round alike and their reactions are equal bit for bit.
-__device__ __forceinline__ void add_end_force(double (&r)[3], const double (&c)[3], double axial, int end) {
-    const double s = end ? axial : -axial;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) r[a] = fma(s, c[a], r[a]);
-}
-
-// Reaction at one constrained joint from its list of member ends ((member << 1) | end): the list is sorted by
-// member id in place (insertion sort: the lists are short) and summed in that order.
-template <class ListPtr>
-__device__ __forceinline__ void joint_reaction(ListPtr list, const int deg, const TrsMembers& mem,
-                                               const double* __restrict__ X, const size_t mbase, const double* u,
-                                               const int* jo, double (&r)[3]) {
-    for (int i = 1; i < deg; ++i) {
-        const int key = list[i];
-        int p = i - 1;
-        while (p >= 0 && list[p] > key) {
-            list[p + 1] = list[p];
-            --p;
-        }
-        list[p + 1] = key;
-    }
-    r[0] = r[1] = r[2] = 0.0;
-    for (int i = 0; i < deg; ++i) {
-        const int m = list[i] >> 1, end = list[i] & 1;
-        const int2 c = mem.ends(mbase + m);
-        const MemberGeom g = member_geom(X, c.x, c.y);
-        const double axial = member_axial(g, mem.EA(mbase + m), u, jo ? jo[c.x] : c.x, jo ? jo[c.y] : c.y);
-        add_end_force(r, g.c, axial, end);
-    }
-}
+using namespace trs_rec;
 
 // entries of the member-end lists the path without LDS staging keeps in LDS (128 KB)
 #define TRS_RECOVER_LIST_CAP 32768

@@ -350,6 +350,36 @@ class Truss:
             raise np.linalg.LinAlgError("Singular matrix")
         self.AdoptDenseResults(result.displace[0], result.external[0], result.internal[0])
 
+    def SolveLoadCases(self, cases):
+        """Solve this truss under several load cases with ONE factorisation of its stiffness matrix: `cases` is a list
+        of `{jointID: vector}` dicts.  Returns one solved copy of the truss per case, carrying that case's forces and
+        results (its `Serialize()` has the shape of the reference's output files); this truss stays as it is.
+        Raises `TrussNotStableError` before any arithmetic when the counting test fails and
+        `numpy.linalg.LinAlgError` when the reduced stiffness matrix is not positive definite."""
+        if not self.isStable:
+            raise TrussNotStableError("The truss is not stable !")
+        from .batch import pack_trusses, solve_load_cases  # late import: keeps the model importable without torch
+        packed = pack_trusses([self])
+        copies = []
+        for case in cases:
+            t = Truss(self._dim).LoadFromJSON(data=self.Serialize())
+            t._loads = {}
+            for jointID, vector in case.items():
+                t.AddExternalForce(jointID, vector)
+            copies.append(t)
+        loads = np.zeros([1, len(copies), packed.nJ_max, 3])
+        for k, t in enumerate(copies):
+            for j, v in t._loads.items():
+                loads[0, k, j, :self._dim] = v
+        if not copies:
+            return []
+        result = solve_load_cases(packed, loads)
+        if int(result.info[0]) != 0:
+            raise np.linalg.LinAlgError("Singular matrix")
+        for k, t in enumerate(copies):
+            t.AdoptDenseResults(result.displace[0, k], result.external[0, k], result.internal[0, k])
+        return copies
+
     def AdoptDenseResults(self, displace, external, internal):
         """Install dense results (`[nJoint, dim]`, `[nJoint, dim]`, `[nMember]`) as the
         sparse result dicts of the reference: entries below 1e-10 in every component are
@@ -434,3 +464,27 @@ class Truss:
             raise TrussNotSolvedError("Haven't done structural analysis yet.")
         lengths = ((j, GetLength(d)) for j, d in self._displace.items())
         return self._excess(lengths, limit, isGetSumViolation, isGetSumNonViolation)
+
+
+def load_cases_from_json(paths):
+    """Several input files of ONE structure (the reference ships its examples so: `bar-47_input_{0,1,2}.json`) as
+    `(Truss, cases)`: the truss of the first file (with that file's forces) and one `{jointID: vector}` dict of forces
+    per file, for `Truss.SolveLoadCases`.  Raises ValueError naming the first file whose `joint` or `member` block
+    differs from the first file's."""
+    paths = list(paths)
+    if not paths:
+        raise ValueError("load_cases_from_json: no files")
+    datas = []
+    for path in paths:
+        with open(path, "r", encoding="utf-8") as fh:
+            datas.append(json.load(fh))
+    first = datas[0]
+    for path, data in zip(paths[1:], datas[1:]):
+        for block in ("joint", "member"):
+            if data[block] != first[block]:
+                raise ValueError(f"load_cases_from_json: the {block!r} block of {path} differs from {paths[0]}'s: "
+                                 "load cases must share one structure")
+    dim = len(first["joint"][0][0]) if first["joint"] else 3
+    truss = Truss(dim).LoadFromJSON(data={k: first[k] for k in ("joint", "force", "member")})
+    cases = [{int(j): tuple(float(x) for x in v) for j, v in data["force"]} for data in datas]
+    return truss, cases
