@@ -514,6 +514,56 @@ int trs_recover_tab_cases(int B, int L, int nJ_max, int nM_max, const double *xy
                           const int32_t *nJ, const int32_t *nM, const double *F, int ld_f, double *u, double *f_ext,
                           double *N, const int32_t *joint_out, void *stream);
 
+/* ---- Adjoint gradients: the derivative of the results with respect to the design from ONE more substitution against
+ * the resident factor (csrc/adjoint.hip).  After trs_potrf_batched and the load-case stages above (the forward reduced
+ * displacements still in their F), the caller supplies cotangents - the derivative of some scalar J with respect to
+ * the results - grad_u, grad_f_ext [B][L][nJ_max][3] and grad_N [B][L][nM_max] in the CALLER's joint numbering (any of
+ * them NULL = zero) and receives dJ/dA, dJ/dE [B][nM_max], dJ/dxyz [B][nJ_max][3] (summed over the L cases, in the
+ * order k = 0 .. L - 1) and dJ/dloads [B][L][nJ_max][3] (per case; zero at constrained DOFs), again in the caller's
+ * numbering, padding written as zero.  Three stages:
+ *
+ *   trs_adjoint_rhs    the reduced right-hand sides r_f of the adjoint systems, in the layout of F above, into a
+ *                      buffer of its own (the forward solutions must survive):  with g^ = grad_f_ext at constrained
+ *                      DOFs, k = E A / len and c the direction cosines of a member,
+ *                      s_m = k (grad_N_m + c . (g^_j1 - g^_j0)),  r_f = grad_u_f + sum over member ends (+- s_m c_m)
+ *   trs_potrs_cases    K_ff lambda = r_f on that buffer, unchanged
+ *   trs_adjoint_grad   mu = lambda at free, -g^ at constrained DOFs;  t_m = grad_N_m - c . (mu_j1 - mu_j0);
+ *                      dJ/dA_m = N_m t_m / A_m,  dJ/dE_m = N_m t_m / E_m,  dJ/dloads = mu + grad_f_ext at free DOFs,
+ *                      dJ/dxyz_j = sum over member ends (+- g_m), g_m the derivative of the member's terms with respect
+ *                      to its end-to-end vector.  Any output pointer may be NULL (not wanted, not computed).
+ *
+ * (the `_tab` twins carry the form in the middle of their names, as trs_recover_tab_cases does; in the table form dJ/dA
+ * and dJ/dE are still per MEMBER.)  Every sum runs in one fixed order (member ends by member id, cases by index) and
+ * no floating-point atomic is used: the gradients are bit-reproducible from run to run, from stream to stream and
+ * between the two member forms, and dJ/dloads of case k does not depend on L or on the other cases.  A truss with
+ * info[b] != 0 gets meaningless numbers, the others are unaffected.  The slab and the forward F are only read.
+ * Both kernels hold the tables of one truss in a CU's LDS (two DOF vectors, the member-end lists of all joints, one
+ * double per member): trs_adjoint_fits(nJ_max, nM_max) says whether a batch shape qualifies; otherwise the entry
+ * points return hipErrorInvalidValue. */
+int trs_adjoint_fits(int nJ_max, int nM_max);
+int trs_adjoint_rhs(int B, int L, int nJ_max, int nM_max, const double *xyz, const int32_t *conn, const double *E,
+                    const double *A, const double *grad_u /* [B][L][nJ_max][3] or NULL */,
+                    const double *grad_f_ext /* [B][L][nJ_max][3] or NULL */,
+                    const double *grad_N /* [B][L][nM_max] or NULL */, const int32_t *free_index,
+                    const int32_t *n_free, const int32_t *nJ, const int32_t *nM,
+                    const int32_t *joint_in /* [B][nJ_max] or NULL */, double *F /* out [B][L][ld_f] */, int ld_f,
+                    void *stream);
+int trs_adjoint_tab_rhs(int B, int L, int nJ_max, int nM_max, const double *xyz, const uint16_t *conn16,
+                        const uint8_t *type_idx, const double *types, const double *grad_u, const double *grad_f_ext,
+                        const double *grad_N, const int32_t *free_index, const int32_t *n_free, const int32_t *nJ,
+                        const int32_t *nM, const int32_t *joint_in, double *F, int ld_f, void *stream);
+int trs_adjoint_grad(int B, int L, int nJ_max, int nM_max, const double *xyz, const int32_t *conn, const double *E,
+                     const double *A, const double *grad_f_ext, const double *grad_N, const int32_t *free_index,
+                     const int32_t *nJ, const int32_t *nM, const double *F /* forward, [B][L][ld_f] */,
+                     const double *Lam /* adjoint, [B][L][ld_f] */, int ld_f, double *gA /* [B][nM_max] or NULL */,
+                     double *gE /* [B][nM_max] or NULL */, double *gxyz /* [B][nJ_max][3] or NULL */,
+                     double *gloads /* [B][L][nJ_max][3] or NULL */, const int32_t *joint_out, void *stream);
+int trs_adjoint_tab_grad(int B, int L, int nJ_max, int nM_max, const double *xyz, const uint16_t *conn16,
+                         const uint8_t *type_idx, const double *types, const double *grad_f_ext, const double *grad_N,
+                         const int32_t *free_index, const int32_t *nJ, const int32_t *nM, const double *F,
+                         const double *Lam, int ld_f, double *gA, double *gE, double *gxyz, double *gloads,
+                         const int32_t *joint_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,15 +35,19 @@ __all__ = ["Truss", "Member", "MemberType", "SupportType", "MetapathType", "Task
            "LinkType", "GenerateMethod", "HipExtensionError", "TrussNotStableError",
            "solve_batch", "pack_trusses", "PackedBatch", "BatchResult", "RaggedSolver", "DeviceBatch",
            "ShardedSolver", "solve_batch_sharded", "solve_batch_distributed",
-           "solve_load_cases", "LoadCaseResult", "load_cases_from_json"]
+           "solve_load_cases", "LoadCaseResult", "load_cases_from_json",
+           "solve_gradients", "GradientResult", "DifferentiableTruss"]
 
 
 def __getattr__(name):
     # torch-dependent names are resolved lazily so that the model imports without torch
     if name in ("solve_batch", "pack_trusses", "PackedBatch", "BatchResult", "RaggedSolver", "DeviceBatch",
-                "solve_load_cases", "LoadCaseResult"):
+                "solve_load_cases", "LoadCaseResult", "solve_gradients", "GradientResult"):
         from . import batch
         return getattr(batch, name)
+    if name == "DifferentiableTruss":
+        from . import autograd
+        return autograd.DifferentiableTruss
     if name in ("ShardedSolver", "solve_batch_sharded", "solve_batch_distributed"):
         from . import shard
         return getattr(shard, name)

@@ -71,6 +71,12 @@ SIGNATURES = {
     "trs_recover_cases_fits": (_I, [_I, _I]),
     "trs_recover_cases": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "trs_recover_tab_cases": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    # adjoint gradients (one more substitution against the factor; csrc/adjoint.hip)
+    "trs_adjoint_fits": (_I, [_I, _I]),
+    "trs_adjoint_rhs": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "trs_adjoint_tab_rhs": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "trs_adjoint_grad": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "trs_adjoint_tab_grad": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
 }
 
 #: must equal TRS_ABI_VERSION of include/trs_solver.h

@@ -766,6 +766,7 @@ class DeviceBatch:
             self.assemble()
             self.potrf()
         self._factored = True
+        self._bump_generation()
 
     def solve_cases(self, loads, out=None):
         """Gather, multi-case substitution and recovery on the resident factor (`factor()` first).  `loads`: float64
@@ -807,7 +808,97 @@ class DeviceBatch:
                            self.free_index.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), F.data_ptr(), self.rows,
                            out["u"].data_ptr(), out["f_ext"].data_ptr(), out["N"].data_ptr(), jo, stream), what)
         self.cases_F = F   # (kept: the reduced displacements of the last call, and the buffer of the next)
+        self._bump_generation()
+        self._forward = (self.generation, L)   # what `adjoint_cases` may differentiate
         return out
+
+    # -- adjoint gradients of the solved cases (include/trs_solver.h "Adjoint gradients") ------------------
+    #: the gradients `adjoint_cases` can give, and their shapes' trailing dimensions
+    GRADIENTS = ("A", "E", "xyz", "loads")
+
+    @property
+    def generation(self):
+        """Counts the `factor()` and `solve_cases()` calls of this batch: a forward state is identified by the value
+        after its `solve_cases()`, and `adjoint_cases` refuses any other."""
+        return getattr(self, "_generation", 0)
+
+    def _bump_generation(self):
+        self._generation = self.generation + 1
+
+    def _gradient_shape(self, key, L):
+        return {"A": [self.B, self.nM_max], "E": [self.B, self.nM_max], "xyz": [self.B, self.nJ_max, 3],
+                "loads": [self.B, L, self.nJ_max, 3]}[key]
+
+    def adjoint_cases(self, grad_u=None, grad_f_ext=None, grad_N=None, want=GRADIENTS, out=None, generation=None):
+        """The vector-Jacobian product of the last `solve_cases(loads)`: for cotangents `grad_u`, `grad_f_ext`
+        [B, L, nJ_max, 3] and `grad_N` [B, L, nM_max] (float64 device tensors in the CALLER's joint numbering, the
+        derivative of some scalar J with respect to the results; None = zero) the gradients dJ/dA, dJ/dE [B, nM_max],
+        dJ/dxyz [B, nJ_max, 3] (summed over the L cases) and dJ/dloads [B, L, nJ_max, 3], as a dict of device tensors
+        with the keys named in `want` (`out`: such a dict to write into).  Three launches on the current stream,
+        asynchronous: the reduced right-hand sides, one substitution against the resident factor (no factorisation;
+        the forward solutions in `cases_F` are only read), and the contraction with the forward field.  In the table
+        member form dA / dE are per member too.
+        The forward state must be current: `factor()` and `solve_cases()` bump `generation`, and a gradient of anything
+        but the last `solve_cases()` of the last `factor()` raises ValueError (`generation`: the value the caller saw
+        after ITS `solve_cases()`, checked as well)."""
+        t = self.torch
+        forward = getattr(self, "_forward", None)
+        if not getattr(self, "_factored", False) or forward is None:
+            raise ValueError("adjoint_cases(): no forward solution - call factor() and solve_cases(loads) first")
+        if forward[0] != self.generation or (generation is not None and generation != self.generation):
+            raise ValueError("adjoint_cases(): the forward solution is stale - factor() or solve_cases() ran since "
+                             "the solve these gradients belong to")
+        L = forward[1]
+        want = tuple(want)
+        if any(k not in self.GRADIENTS for k in want):
+            raise ValueError(f"adjoint_cases(): want must name some of {self.GRADIENTS}, got {want}")
+        shapes = {"grad_u": (self.B, L, self.nJ_max, 3), "grad_f_ext": (self.B, L, self.nJ_max, 3),
+                  "grad_N": (self.B, L, self.nM_max)}
+        cot = {"grad_u": grad_u, "grad_f_ext": grad_f_ext, "grad_N": grad_N}
+        for name, g in cot.items():
+            if g is None:
+                continue
+            if tuple(g.shape) != shapes[name] or g.dtype != t.float64 or g.device != self.device:
+                raise ValueError(f"adjoint_cases(): {name} must be float64 {list(shapes[name])} on {self.device} "
+                                 f"(the last solve_cases() had L = {L}), got {g.dtype} {list(g.shape)} on {g.device}")
+            cot[name] = g.contiguous()
+        if out is None:
+            out = {}
+        for k in want:
+            if k not in out:
+                out[k] = t.zeros(self._gradient_shape(k, L), dtype=t.float64, device=self.device)
+            elif list(out[k].shape) != self._gradient_shape(k, L) or out[k].dtype != t.float64 \
+                    or out[k].device != self.device or not out[k].is_contiguous():
+                raise ValueError(f"adjoint_cases(): out[{k!r}] must be a contiguous float64 "
+                                 f"{self._gradient_shape(k, L)} tensor on {self.device}")
+        if self.B == 0 or L == 0:
+            return {k: out[k] for k in want}
+        if not self.lib.trs_adjoint_fits(self.nJ_max, self.nM_max):
+            raise HipExtensionError(f"adjoint_cases(): a truss of {self.nJ_max} joints / {self.nM_max} members exceeds "
+                                    "the LDS of the adjoint kernels (trs_adjoint_fits)")
+        Lam = getattr(self, "cases_Lam", None)   # the adjoint systems: a buffer of their own, the forward F survives
+        if Lam is None or int(Lam.shape[1]) != L:
+            Lam = t.empty([self.B, L, self.rows], dtype=t.float64, device=self.device)
+        ptr = lambda x: None if x is None else x.data_ptr()
+        jo = ptr(self.joint_out)
+        stream = self._stream()
+        tab = "_tab" if self.table else ""
+        with t.cuda.device(self.device):
+            _capi.check(getattr(self.lib, f"trs_adjoint{tab}_rhs")(
+                self.B, L, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *self._members(), ptr(cot["grad_u"]),
+                ptr(cot["grad_f_ext"]), ptr(cot["grad_N"]), self.free_index.data_ptr(), self.n_free.data_ptr(),
+                self.nJ.data_ptr(), self.nM.data_ptr(), jo, Lam.data_ptr(), self.rows, stream), f"trs_adjoint{tab}_rhs")
+            _capi.check(self.lib.trs_potrs_cases(self.B, L, self.n_free.data_ptr(), self.ld, self.rows,
+                                                 self.S.data_ptr(), Lam.data_ptr(), self.rows, self._env_ptr(), stream),
+                        "trs_potrs_cases")
+            _capi.check(getattr(self.lib, f"trs_adjoint{tab}_grad")(
+                self.B, L, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *self._members(), ptr(cot["grad_f_ext"]),
+                ptr(cot["grad_N"]), self.free_index.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(),
+                self.cases_F.data_ptr(), Lam.data_ptr(), self.rows, ptr(out.get("A") if "A" in want else None),
+                ptr(out.get("E") if "E" in want else None), ptr(out.get("xyz") if "xyz" in want else None),
+                ptr(out.get("loads") if "loads" in want else None), jo, stream), f"trs_adjoint{tab}_grad")
+        self.cases_Lam = Lam
+        return {k: out[k] for k in want}
 
     def fitness(self, allow_stress, allow_displace, out=None):
         """(weight, stress_violation, displacement_violation) per truss, on device."""
@@ -2154,6 +2245,115 @@ def solve_load_cases(trusses_or_packed, loads, device=None, reorder=False, optio
         return LoadCaseResult(u, f, N, info)
     torch.cuda.synchronize(dev)
     return LoadCaseResult(u.cpu().numpy(), f.cpu().numpy(), N.cpu().numpy(), info.cpu().numpy())
+
+
+@dataclass
+class GradientResult:
+    """Gradients of `solve_gradients`: dA, dE [B, nM_max] (per member, also in the table member form), dxyz
+    [B, nJ_max, 3] (summed over the load cases; z = 0 for a 2D truss), dloads [B, L, nJ_max, 3] (per case, zero at
+    constrained DOFs), info [B] (the factorisation's status: the gradients of a truss with info != 0 are meaningless)."""
+    dA: np.ndarray
+    dE: np.ndarray
+    dxyz: np.ndarray
+    dloads: np.ndarray
+    info: np.ndarray
+
+
+def _cotangent(torch, name, g, shape, dev):
+    """A cotangent of `solve_gradients` as a contiguous float64 device tensor of `shape` (2D vectors get z = 0)."""
+    if g is None:
+        return None
+    if isinstance(g, np.ndarray):
+        g = torch.from_numpy(np.ascontiguousarray(g, dtype=np.float64))
+    g = g.to(device=dev, dtype=torch.float64)
+    if len(shape) == 4 and g.dim() == 4 and int(g.shape[3]) == 2:
+        g = torch.nn.functional.pad(g, (0, 1))
+    return g.contiguous()
+
+
+def _check_gradient_args(B, nJ_max, nM_max, loads, cotangents, loss, sections):
+    """The argument errors of `solve_gradients` that need no device.  Returns L."""
+    if sections is not None:
+        raise ValueError("solve_gradients: sections= variants cannot be combined with gradients")
+    shape = tuple(int(x) for x in loads.shape)
+    if len(shape) != 4 or shape[0] != B or shape[2] != nJ_max or shape[3] not in (2, 3):
+        raise ValueError(f"solve_gradients: loads must be [B={B}, L, nJ_max={nJ_max}, 2 or 3], got {shape}")
+    L = shape[1]
+    given = {k: g for k, g in cotangents.items() if g is not None}
+    if loss is not None and given:
+        raise ValueError("solve_gradients: give either loss= or fixed cotangents (grad_u / grad_f_ext / grad_N), not both")
+    if loss is None and not given:
+        raise ValueError("solve_gradients: nothing to differentiate - give grad_u, grad_f_ext, grad_N or loss=")
+    for name, g in given.items():
+        got = tuple(int(x) for x in g.shape)
+        ok = got == (B, L, nM_max) if name == "grad_N" else \
+            (len(got) == 4 and got[:3] == (B, L, nJ_max) and got[3] in (2, 3))
+        if not ok:
+            want = f"[B={B}, L={L}, nM_max={nM_max}]" if name == "grad_N" else f"[B={B}, L={L}, nJ_max={nJ_max}, 2 or 3]"
+            raise ValueError(f"solve_gradients: {name} must be {want}, got {got}")
+    return L
+
+
+def solve_gradients(trusses_or_packed, loads, grad_u=None, grad_f_ext=None, grad_N=None, loss=None,
+                    want=DeviceBatch.GRADIENTS, device=None, reorder=False, options=None, max_slab_bytes=64 << 30,
+                    on_device=False, sections=None, use_envelope=True):
+    """`solve_load_cases` plus the adjoint gradients of its results: every truss is factored ONCE, its L load cases
+    are solved, and one more substitution against the same factor gives the derivative of a scalar J with respect to
+    the member areas and moduli, the joint coordinates and the loads (`DeviceBatch.adjoint_cases`; no finite
+    differences, no second factorisation).  J enters either as fixed cotangents `grad_u`, `grad_f_ext`
+    [B, L, nJ_max, dim] and `grad_N` [B, L, nM_max] (numpy or torch, caller's joint numbering; a missing one is zero),
+    or as `loss=`, a callable `(u, f_ext, N) -> (grad_u, grad_f_ext, grad_N)` on device tensors (entries may be None),
+    called once per size bucket between the forward and the adjoint pass with that bucket's results
+    [b, L, nJ_bucket, 3] / [b, L, nM_bucket] - for objectives that depend on the results (stress limits, displacement
+    norms).  Buckets, member forms, `reorder` plans, `on_device` and `use_envelope` as `solve_load_cases`.
+    Returns (`LoadCaseResult`, `GradientResult`); gradients not named in `want` come back as zeros."""
+    packed = trusses_or_packed if isinstance(trusses_or_packed, PackedBatch) else pack_trusses(list(trusses_or_packed))
+    B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
+    cots = {"grad_u": grad_u, "grad_f_ext": grad_f_ext, "grad_N": grad_N}
+    L = _check_gradient_args(B, nJ_max, nM_max, loads, cots, loss, sections)
+    want = tuple(want)
+    if any(k not in DeviceBatch.GRADIENTS for k in want):
+        raise ValueError(f"solve_gradients: want must name some of {DeviceBatch.GRADIENTS}, got {want}")
+    torch, dev = _require_gpu(device)
+    loads = _cotangent(torch, "loads", loads, (B, L, nJ_max, 3), dev)
+    cots = {k: _cotangent(torch, k, g, (B, L, nM_max) if k == "grad_N" else (B, L, nJ_max, 3), dev)
+            for k, g in cots.items()}
+    zeros = lambda *shape: torch.zeros(list(shape), dtype=torch.float64, device=dev)
+    u, f, N = zeros(B, L, nJ_max, 3), zeros(B, L, nJ_max, 3), zeros(B, L, nM_max)
+    grads = {"A": zeros(B, nM_max), "E": zeros(B, nM_max), "xyz": zeros(B, nJ_max, 3), "loads": zeros(B, L, nJ_max, 3)}
+    info = torch.zeros([B], dtype=torch.int32, device=dev)
+    if B and L:
+        for idx in size_buckets(packed, max_slab_bytes):
+            sub = packed.take(idx).trimmed()
+            rows = torch.from_numpy(np.asarray(idx, dtype=np.int64)).to(dev)
+            db = DeviceBatch(sub, dev, use_envelope=use_envelope, use_small=False, reorder=reorder, options=options)
+            db.factor()
+            res = db.solve_cases(loads.index_select(0, rows)[:, :, :sub.nJ_max].contiguous())
+            if loss is not None:
+                gu_b, gf_b, gN_b = loss(res["u"], res["f_ext"], res["N"])
+            else:
+                cut = lambda g, n: None if g is None else g.index_select(0, rows)[:, :, :n].contiguous()
+                gu_b, gf_b = cut(cots["grad_u"], sub.nJ_max), cut(cots["grad_f_ext"], sub.nJ_max)
+                gN_b = cut(cots["grad_N"], sub.nM_max)
+            g = db.adjoint_cases(gu_b, gf_b, gN_b, want=want)
+            u[rows, :, :sub.nJ_max] = res["u"]
+            f[rows, :, :sub.nJ_max] = res["f_ext"]
+            N[rows, :, :sub.nM_max] = res["N"]
+            info[rows] = db.info
+            for key, val in g.items():
+                if key == "loads":
+                    grads[key][rows, :, :sub.nJ_max] = val
+                elif key == "xyz":
+                    grads[key][rows, :sub.nJ_max] = val
+                else:
+                    grads[key][rows, :sub.nM_max] = val
+    if not on_device:
+        torch.cuda.synchronize(dev)
+        host = lambda x: x.cpu().numpy()
+        u, f, N, info = host(u), host(f), host(N), host(info)
+        grads = {k: host(v) for k, v in grads.items()}
+    return (LoadCaseResult(u, f, N, info),
+            GradientResult(grads["A"], grads["E"], grads["xyz"], grads["loads"], info))
 
 
 def _is_pinned(packed):

@@ -1,0 +1,301 @@
+// Adjoint gradients of a factored, solved batch (include/trs_solver.h "Adjoint gradients"): the vector-Jacobian
+// product of the results (u, f_ext, N of every load case) with respect to the design (A, E, xyz, loads), from ONE
+// more substitution against the resident factor - no factorisation, no finite differences.
+//
+//   trs_adjoint_rhs    cotangents gu, gf [B][L][nJ_max][3], gN [B][L][nM_max] (caller's numbering) -> reduced
+//                      right-hand sides r_f, F [B][L][ld_f] in the layout trs_potrs_cases reads
+//   trs_potrs_cases    K_ff lambda = r_f (cases.hip, unchanged, on a buffer of its own)
+//   trs_adjoint_grad   forward field u (reduced, as trs_potrs_cases left it) x adjoint field mu -> gA, gE [B][nM_max],
+//                      gxyz [B][nJ_max][3] (summed over the cases), gloads [B][L][nJ_max][3]
+//
+// With g^ = gf at the constrained DOFs (zero elsewhere), k = E A / len, c the direction cosines, D. = (.)_j1 - (.)_j0:
+//   s_m  = k (gN_m + c . D g^)                     member pseudo-force
+//   r_f  = gu_f + sum_ends (+- s_m c_m)            free DOFs
+//   mu_f = lambda, mu_c = -g^_c
+//   t_m  = gN_m - c . D mu,   gA_m = N_m t_m / A_m,   gE_m = N_m t_m / E_m,   gloads_f = mu_f + gf_f
+//   g_m  = (k / len) { t_m D u - (c . D u) D mu + (c . D u) (3 c . D mu - 2 gN_m) c },   gxyz_j = sum_ends (+- g_m)
+//
+// One work-group per truss, as trs_recover_cases: the member-end lists of EVERY joint are built in LDS once
+// (integer atomics, then sorted by member id), every joint's sum runs over its list in member-id order, the cases
+// are accumulated in the order k = 0 .. L - 1, and no floating-point atomic is used anywhere: the results are
+// bit-reproducible from run to run, from stream to stream and between the two member forms.
+#include "../../include/trs_solver.h"
+#include "trs_common.h"
+#include "trs_recover.h"
+
+namespace {
+
+using namespace trs_rec;
+
+__device__ __forceinline__ double member_modulus(const TrsMembers& mem, size_t mm) {
+    return mem.table() ? mem.types[3 * (int)mem.tidx[mm] + 1] : mem.E[mm];
+}
+
+// LDS tables of one truss (both kernels; the right-hand-side kernel uses one of the two DOF vectors)
+struct AdjTables {
+    double* v0;   // [3 nJ_max]
+    double* v1;   // [3 nJ_max]
+    double* pm;   // [nM_max]    one double per member
+    int* cnt;     // [nJ_max]
+    int* start;   // [nJ_max + 1]
+    int* ends;    // [2 nM_max]  (member << 1) | end, per joint, sorted by member id
+};
+
+__device__ __forceinline__ AdjTables adj_tables(double* sh, int nJ_max, int nM_max) {
+    AdjTables t;
+    t.v0 = sh;
+    t.v1 = sh + 3 * nJ_max;
+    t.pm = t.v1 + 3 * nJ_max;
+    t.cnt = reinterpret_cast<int*>(t.pm + nM_max);
+    t.start = t.cnt + nJ_max;
+    t.ends = t.start + nJ_max + 1;
+    return t;
+}
+
+// The member-end lists of every joint of truss b, sorted by member id (trs_recover_cases builds the same lists
+// for the constrained joints only).  Ends with a barrier.
+__device__ __forceinline__ void build_end_lists(const AdjTables& t, const TrsMembers& mem, const size_t mbase,
+                                                const int joints, const int members, const int nJ_max,
+                                                const int tid) {
+    for (int j = tid; j < nJ_max; j += 256) t.cnt[j] = 0;
+    __syncthreads();
+    for (int m = tid; m < members; m += 256) {
+        const int2 c = mem.ends(mbase + m);
+        atomicAdd(&t.cnt[c.x], 1);
+        atomicAdd(&t.cnt[c.y], 1);
+    }
+    __syncthreads();
+    if (tid < 64) {  // exclusive scan of cnt by one wave
+        int base = 0;
+        for (int j0 = 0; j0 < joints; j0 += 64) {
+            const int j = j0 + tid;
+            const int v = j < joints ? t.cnt[j] : 0;
+            int incl = v;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const int up = __shfl_up(incl, off);
+                if (tid >= off) incl += up;
+            }
+            if (j < joints) t.start[j] = base + incl - v;
+            base += __shfl(incl, 63);
+        }
+    }
+    __syncthreads();
+    for (int j = tid; j < joints; j += 256) t.cnt[j] = 0;  // the fill cursor
+    __syncthreads();
+    for (int m = tid; m < members; m += 256) {
+        const int2 c = mem.ends(mbase + m);
+        t.ends[t.start[c.x] + atomicAdd(&t.cnt[c.x], 1)] = m << 1;
+        t.ends[t.start[c.y] + atomicAdd(&t.cnt[c.y], 1)] = (m << 1) | 1;
+    }
+    __syncthreads();
+    for (int j = tid; j < joints; j += 256) {
+        int* list = t.ends + t.start[j];
+        const int deg = t.cnt[j];
+        for (int i = 1; i < deg; ++i) {
+            const int key = list[i];
+            int p = i - 1;
+            while (p >= 0 && list[p] > key) {
+                list[p + 1] = list[p];
+                --p;
+            }
+            list[p + 1] = key;
+        }
+    }
+    __syncthreads();
+}
+
+// ---- step 1: the reduced right-hand side of the adjoint system ------------------------------------------------------
+__global__ __launch_bounds__(256) void trs_adjoint_rhs_kernel(
+    const int L, const double* __restrict__ xyz, const TrsMembers mem, const double* __restrict__ gu,
+    const double* __restrict__ gf, const double* __restrict__ gN, const int* __restrict__ free_index,
+    const int* __restrict__ n_free, const int* __restrict__ nJ, const int* __restrict__ nM, const int nJ_max,
+    const int nM_max, const int* __restrict__ joint_in, double* __restrict__ F, const int ld_f) {
+    extern __shared__ double sh[];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int joints = nJ[b], members = nM[b];
+    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
+    const AdjTables t = adj_tables(sh, nJ_max, nM_max);
+    double* gh = t.v0;  // g^: gf at the constrained DOFs, device numbering
+    double* s = t.pm;   // member pseudo-force
+    const int* fi = free_index + (size_t)b * ndof_max;
+    const double* X = xyz + (size_t)b * ndof_max;
+    const size_t mbase = (size_t)b * nM_max;
+    const int* ji = joint_in != nullptr ? joint_in + (size_t)b * nJ_max : nullptr;
+    const int n = n_free[b], npad = trs_round_up(n, TRS_NB);
+    build_end_lists(t, mem, mbase, joints, members, nJ_max, tid);
+    for (int k = 0; k < L; ++k) {
+        const size_t bk = (size_t)b * L + k;
+        const double* guk = gu != nullptr ? gu + bk * ndof_max : nullptr;  // caller's numbering
+        const double* gfk = gf != nullptr ? gf + bk * ndof_max : nullptr;
+        const double* gNk = gN != nullptr ? gN + bk * nM_max : nullptr;
+        double* f = F + bk * ld_f;
+        __syncthreads();  // (the previous case's readers of gh and s are done)
+        for (int d = tid; d < ndof; d += 256) {
+            const int o = ji != nullptr ? 3 * ji[d / 3] + d % 3 : d;
+            gh[d] = (gfk != nullptr && fi[d] < 0) ? gfk[o] : 0.0;
+        }
+        __syncthreads();
+        for (int m = tid; m < members; m += 256) {
+            const int2 c = mem.ends(mbase + m);
+            const MemberGeom g = member_geom(X, c.x, c.y);
+            // k c . (g^_j1 - g^_j0): the axial "force" of the field g^
+            const double proj = member_axial(g, mem.EA(mbase + m), gh, c.x, c.y);
+            s[m] = gNk != nullptr ? fma(mem.EA(mbase + m) / g.len, gNk[m], proj) : proj;
+        }
+        __syncthreads();
+        for (int j = tid; j < joints; j += 256) {
+            if ((fi[3 * j] < 0) & (fi[3 * j + 1] < 0) & (fi[3 * j + 2] < 0)) continue;  // no free DOF here
+            double r[3] = {0.0, 0.0, 0.0};
+            const int* list = t.ends + t.start[j];
+            const int deg = t.cnt[j];
+            for (int i = 0; i < deg; ++i) {
+                const int m = list[i] >> 1, end = list[i] & 1;
+                const int2 c = mem.ends(mbase + m);
+                const MemberGeom g = member_geom(X, c.x, c.y);
+                add_end_force(r, g.c, s[m], end);
+            }
+            const int o = ji != nullptr ? 3 * ji[j] : 3 * j;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const int row = fi[3 * j + a];
+                if (row >= 0) f[row] = guk != nullptr ? r[a] + guk[o + a] : r[a];
+            }
+        }
+        for (int c = n + tid; c < npad; c += 256) f[c] = 0.0;
+    }
+}
+
+// ---- step 3: contraction of the adjoint field with the forward field ------------------------------------------------
+__global__ __launch_bounds__(256) void trs_adjoint_grad_kernel(
+    const int L, const double* __restrict__ xyz, const TrsMembers mem, const double* __restrict__ gf,
+    const double* __restrict__ gN, const int* __restrict__ free_index, const int* __restrict__ nJ,
+    const int* __restrict__ nM, const int nJ_max, const int nM_max, const double* __restrict__ Fu,
+    const double* __restrict__ Lam, const int ld_f, double* __restrict__ gA, double* __restrict__ gE,
+    double* __restrict__ gxyz, double* __restrict__ gloads, const int* __restrict__ joint_out) {
+    extern __shared__ double sh[];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int joints = nJ[b], members = nM[b];
+    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
+    const AdjTables t = adj_tables(sh, nJ_max, nM_max);
+    double* u = t.v0;    // forward displacements of one case, device numbering
+    double* mu = t.v1;   // adjoint field of that case
+    double* acc = t.pm;  // sum over the cases of N_m t_m
+    const int* fi = free_index + (size_t)b * ndof_max;
+    const double* X = xyz + (size_t)b * ndof_max;
+    const size_t mbase = (size_t)b * nM_max;
+    const int* jo = joint_out != nullptr ? joint_out + (size_t)b * nJ_max : nullptr;
+    const bool want_sections = (gA != nullptr) | (gE != nullptr);
+    double* gx = gxyz != nullptr ? gxyz + (size_t)b * ndof_max : nullptr;
+    if (gx != nullptr) build_end_lists(t, mem, mbase, joints, members, nJ_max, tid);
+    for (int k = 0; k < L; ++k) {
+        const size_t bk = (size_t)b * L + k;
+        const double* uk = Fu + bk * ld_f;
+        const double* lk = Lam + bk * ld_f;
+        const double* gfk = gf != nullptr ? gf + bk * ndof_max : nullptr;  // caller's numbering
+        const double* gNk = gN != nullptr ? gN + bk * nM_max : nullptr;
+        double* glk = gloads != nullptr ? gloads + bk * ndof_max : nullptr;
+        __syncthreads();  // (the previous case's readers of u and mu are done)
+        for (int d = tid; d < ndof_max; d += 256) {
+            const int r = d < ndof ? fi[d] : -1;
+            const int o = jo != nullptr ? 3 * jo[d / 3] + d % 3 : d;
+            const double gfo = (gfk != nullptr && d < ndof) ? gfk[o] : 0.0;
+            const double lam = r >= 0 ? lk[r] : 0.0;
+            u[d] = r >= 0 ? uk[r] : 0.0;
+            mu[d] = r >= 0 ? lam : -gfo;
+            if (glk != nullptr) glk[o] = r >= 0 ? lam + gfo : 0.0;
+        }
+        __syncthreads();
+        if (want_sections)
+            for (int m = tid; m < members; m += 256) {
+                const int2 c = mem.ends(mbase + m);
+                const MemberGeom g = member_geom(X, c.x, c.y);
+                const double EA = mem.EA(mbase + m);
+                const double axial = member_axial(g, EA, u, c.x, c.y);  // the bits of the recovery's N
+                double cm = 0.0;
+#pragma unroll
+                for (int a = 0; a < 3; ++a) cm += g.c[a] * (mu[3 * c.y + a] - mu[3 * c.x + a]);
+                const double tm = (gNk != nullptr ? gNk[m] : 0.0) - cm;
+                acc[m] = k == 0 ? axial * tm : fma(axial, tm, acc[m]);
+            }
+        if (gx != nullptr)
+            for (int j = tid; j < joints; j += 256) {
+                double r[3] = {0.0, 0.0, 0.0};
+                const int* list = t.ends + t.start[j];
+                const int deg = t.cnt[j];
+                for (int i = 0; i < deg; ++i) {
+                    const int m = list[i] >> 1, end = list[i] & 1;
+                    const int2 c = mem.ends(mbase + m);
+                    const MemberGeom g = member_geom(X, c.x, c.y);
+                    const double kl = mem.EA(mbase + m) / g.len / g.len;
+                    double du[3], dm[3], cu = 0.0, cm = 0.0;
+#pragma unroll
+                    for (int a = 0; a < 3; ++a) {
+                        du[a] = u[3 * c.y + a] - u[3 * c.x + a];
+                        dm[a] = mu[3 * c.y + a] - mu[3 * c.x + a];
+                        cu += g.c[a] * du[a];
+                        cm += g.c[a] * dm[a];
+                    }
+                    const double gn = gNk != nullptr ? gNk[m] : 0.0;
+                    const double tm = gn - cm, along = cu * (3.0 * cm - 2.0 * gn);
+                    double gm[3];
+#pragma unroll
+                    for (int a = 0; a < 3; ++a) gm[a] = tm * du[a] - cu * dm[a] + along * g.c[a];
+                    add_end_force(r, gm, kl, end);
+                }
+                // accumulated over the cases in the output itself: joint j is this thread's in every case
+                const int o = jo != nullptr ? 3 * jo[j] : 3 * j;
+#pragma unroll
+                for (int a = 0; a < 3; ++a) gx[o + a] = k == 0 ? r[a] : gx[o + a] + r[a];
+            }
+    }
+    __syncthreads();
+    for (int m = tid; m < nM_max; m += 256) {
+        const bool live = m < members;
+        if (gA != nullptr) gA[mbase + m] = live ? acc[m] / mem.area(mbase + m) : 0.0;
+        if (gE != nullptr) gE[mbase + m] = live ? acc[m] / member_modulus(mem, mbase + m) : 0.0;
+    }
+    if (gx != nullptr)
+        for (int j = joints + tid; j < nJ_max; j += 256) {
+            const int o = jo != nullptr ? 3 * jo[j] : 3 * j;
+            gx[o] = gx[o + 1] = gx[o + 2] = 0.0;
+        }
+}
+
+}  // namespace
+
+extern "C" size_t trs_adjoint_lds(int nJ_max, int nM_max) {
+    return (((size_t)6 * nJ_max + (size_t)nM_max) * sizeof(double) +
+            ((size_t)2 * nJ_max + 1 + 2 * (size_t)nM_max) * sizeof(int) + 15) / 16 * 16;
+}
+
+extern "C" int trs_adjoint_rhs_launch(int B, int L, int nJ_max, int nM_max, const double* xyz, const TrsMembers* members,
+                                      const double* gu, const double* gf, const double* gN, const int* free_index,
+                                      const int* n_free, const int* nJ, const int* nM, const int* joint_in, double* F,
+                                      int ld_f, hipStream_t stream) {
+    if (B <= 0 || L <= 0) return 0;
+    const size_t lds = trs_adjoint_lds(nJ_max, nM_max);
+    if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
+    static const int lds_limit_set = (int)hipFuncSetAttribute(   // once per process, not per launch
+        reinterpret_cast<const void*>(trs_adjoint_rhs_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)lds_limit_set;
+    hipLaunchKernelGGL(trs_adjoint_rhs_kernel, dim3(B), dim3(256), lds, stream, L, xyz, *members, gu, gf, gN, free_index,
+                       n_free, nJ, nM, nJ_max, nM_max, joint_in, F, ld_f);
+    return (int)hipGetLastError();
+}
+
+extern "C" int trs_adjoint_grad_launch(int B, int L, int nJ_max, int nM_max, const double* xyz, const TrsMembers* members,
+                                       const double* gf, const double* gN, const int* free_index, const int* nJ,
+                                       const int* nM, const double* Fu, const double* Lam, int ld_f, double* gA,
+                                       double* gE, double* gxyz, double* gloads, const int* joint_out,
+                                       hipStream_t stream) {
+    if (B <= 0 || L <= 0) return 0;
+    const size_t lds = trs_adjoint_lds(nJ_max, nM_max);
+    if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
+    static const int lds_limit_set = (int)hipFuncSetAttribute(   // once per process, not per launch
+        reinterpret_cast<const void*>(trs_adjoint_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)lds_limit_set;
+    hipLaunchKernelGGL(trs_adjoint_grad_kernel, dim3(B), dim3(256), lds, stream, L, xyz, *members, gf, gN, free_index, nJ,
+                       nM, nJ_max, nM_max, Fu, Lam, ld_f, gA, gE, gxyz, gloads, joint_out);
+    return (int)hipGetLastError();
+}

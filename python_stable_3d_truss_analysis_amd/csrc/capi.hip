@@ -451,3 +451,61 @@ int trs_recover_tab_cases(int B, int L, int nJ_max, int nM_max, const double* xy
                                     joint_out, (hipStream_t)stream);
 }
 }  // extern "C"
+
+// ---- adjoint gradients (include/trs_solver.h "Adjoint gradients"; csrc/adjoint.hip) ----
+extern "C" {
+int trs_adjoint_rhs_launch(int, int, int, int, const double*, const TrsMembers*, const double*, const double*,
+                           const double*, const int*, const int*, const int*, const int*, const int*, double*, int,
+                           hipStream_t);
+int trs_adjoint_grad_launch(int, int, int, int, const double*, const TrsMembers*, const double*, const double*, const int*,
+                            const int*, const int*, const double*, const double*, int, double*, double*, double*, double*,
+                            const int*, hipStream_t);
+size_t trs_adjoint_lds(int, int);
+
+int trs_adjoint_fits(int nJ_max, int nM_max) {
+    return nJ_max >= 0 && nM_max >= 0 && trs_adjoint_lds(nJ_max, nM_max) <= 160 * 1024;
+}
+
+int trs_adjoint_rhs(int B, int L, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* E,
+                    const double* A, const double* grad_u, const double* grad_f_ext, const double* grad_N,
+                    const int32_t* free_index, const int32_t* n_free, const int32_t* nJ, const int32_t* nM,
+                    const int32_t* joint_in, double* F, int ld_f, void* stream) {
+    if (B < 0 || L < 0 || nJ_max < 0 || nM_max < 0 || ld_f < 0) return (int)hipErrorInvalidValue;
+    const TrsMembers mem = trs_members_general(conn, E, A);
+    return trs_adjoint_rhs_launch(B, L, nJ_max, nM_max, xyz, &mem, grad_u, grad_f_ext, grad_N, free_index, n_free, nJ, nM,
+                                  joint_in, F, ld_f, (hipStream_t)stream);
+}
+
+int trs_adjoint_tab_rhs(int B, int L, int nJ_max, int nM_max, const double* xyz, const uint16_t* conn16,
+                        const uint8_t* type_idx, const double* types, const double* grad_u, const double* grad_f_ext,
+                        const double* grad_N, const int32_t* free_index, const int32_t* n_free, const int32_t* nJ,
+                        const int32_t* nM, const int32_t* joint_in, double* F, int ld_f, void* stream) {
+    if (B < 0 || L < 0 || nJ_max < 0 || nM_max < 0 || ld_f < 0 || (B > 0 && (!conn16 || !type_idx || !types)))
+        return (int)hipErrorInvalidValue;
+    const TrsMembers mem = trs_members_table(conn16, type_idx, types);
+    return trs_adjoint_rhs_launch(B, L, nJ_max, nM_max, xyz, &mem, grad_u, grad_f_ext, grad_N, free_index, n_free, nJ, nM,
+                                  joint_in, F, ld_f, (hipStream_t)stream);
+}
+
+int trs_adjoint_grad(int B, int L, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* E,
+                     const double* A, const double* grad_f_ext, const double* grad_N, const int32_t* free_index,
+                     const int32_t* nJ, const int32_t* nM, const double* F, const double* Lam, int ld_f, double* gA,
+                     double* gE, double* gxyz, double* gloads, const int32_t* joint_out, void* stream) {
+    if (B < 0 || L < 0 || nJ_max < 0 || nM_max < 0 || ld_f < 0) return (int)hipErrorInvalidValue;
+    const TrsMembers mem = trs_members_general(conn, E, A);
+    return trs_adjoint_grad_launch(B, L, nJ_max, nM_max, xyz, &mem, grad_f_ext, grad_N, free_index, nJ, nM, F, Lam, ld_f,
+                                   gA, gE, gxyz, gloads, joint_out, (hipStream_t)stream);
+}
+
+int trs_adjoint_tab_grad(int B, int L, int nJ_max, int nM_max, const double* xyz, const uint16_t* conn16,
+                         const uint8_t* type_idx, const double* types, const double* grad_f_ext, const double* grad_N,
+                         const int32_t* free_index, const int32_t* nJ, const int32_t* nM, const double* F,
+                         const double* Lam, int ld_f, double* gA, double* gE, double* gxyz, double* gloads,
+                         const int32_t* joint_out, void* stream) {
+    if (B < 0 || L < 0 || nJ_max < 0 || nM_max < 0 || ld_f < 0 || (B > 0 && (!conn16 || !type_idx || !types)))
+        return (int)hipErrorInvalidValue;
+    const TrsMembers mem = trs_members_table(conn16, type_idx, types);
+    return trs_adjoint_grad_launch(B, L, nJ_max, nM_max, xyz, &mem, grad_f_ext, grad_N, free_index, nJ, nM, F, Lam, ld_f,
+                                   gA, gE, gxyz, gloads, joint_out, (hipStream_t)stream);
+}
+}  // extern "C"
