@@ -82,6 +82,16 @@ SIGNATURES = {
 #: must equal TRS_ABI_VERSION of include/trs_solver.h
 ABI_VERSION = 10
 
+# The flag words of the ABI (tests/test_capi_symbols.py compares every one with its define).
+# TRS_ASM_* of include/trs_solver.h: `flags` of trs_assemble
+ASM_FULL_SYMMETRIC, ASM_COMPACT, ASM_ALL_NARROW, ASM_ALL_TILES, ASM_ALL_WIDE = 1, 2, 4, 8, 16
+# TRS_HINT_* of include/trs_solver.h: `hints` of the factorisation, substitution, recovery and whole-pipeline calls
+HINT_NO_WIDE, HINT_SUBSTITUTED, HINT_COMPACT, HINT_SEPARATE_STAGES, HINT_NO_SMALL, HINT_RECOVER_UNSTAGED = 1, 2, 4, 8, 16, 32
+HINT_ALL_TILES, HINT_RECOVER_SCAN, HINT_ALL_WIDE = 64, 128, 256
+NARROW_MAX_BELOW = 24   # csrc/trs_common.h TRS_NARROW_MAX_BELOW: reach up to which a matrix goes to a wave of its own
+ORDER_RCM_BELOW = 128   # csrc/reorder.c TRS_ORDER_RCM_BELOW, csrc/order.hip RCM_BELOW: effort 3 prices Cuthill-McKee
+#                         below this many free joints
+
 _lib = None
 
 

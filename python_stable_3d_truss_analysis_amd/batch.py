@@ -13,7 +13,10 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _capi
+from . import _capi, _hostapi
+from ._capi import (ASM_ALL_NARROW, ASM_ALL_TILES, ASM_ALL_WIDE, ASM_COMPACT, ASM_FULL_SYMMETRIC,   # noqa: F401
+                    HINT_ALL_TILES, HINT_ALL_WIDE, HINT_COMPACT, HINT_NO_SMALL, HINT_NO_WIDE, HINT_RECOVER_SCAN,
+                    HINT_RECOVER_UNSTAGED, HINT_SEPARATE_STAGES, HINT_SUBSTITUTED, NARROW_MAX_BELOW, ORDER_RCM_BELOW)
 from .type import SupportType
 from .utils import HipExtensionError
 
@@ -279,10 +282,9 @@ _JSON_ERRORS = {1: "JSON syntax", 2: "inconsistent coordinate / load dimension",
 
 def _pack_json_native(count, call):
     """Two passes through the native reader (`csrc/jsonpack.c`): sizes, then the padded arrays."""
-    import ctypes
     nJ = np.zeros([count], dtype=np.int32); nM = np.zeros([count], dtype=np.int32)
     dim = np.full([count], 3, dtype=np.int32)
-    ptr = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    ptr = _hostapi.ptr
 
     def run(nJ_max, nM_max, arrays):
         rc = call(nJ_max, nM_max, *(ptr(a) for a in arrays), ptr(nJ), ptr(nM), ptr(dim))
@@ -305,39 +307,33 @@ def pack_json_texts(texts, members="general"):
     native bulk reader (`csrc/jsonpack.c`, OpenMP over the documents): no Python objects per joint or
     member.  Same arrays as `pack_json([json.loads(t) for t in texts])`; `members` as there."""
     import ctypes
-    from .generate import _load
-    lib = _load()
+    lib = _hostapi.load()
     raw = [t.encode("utf-8") if isinstance(t, str) else bytes(t) for t in texts]
     B = len(raw)
     arr = (ctypes.c_char_p * B)(*raw)
     lens = np.array([len(r) for r in raw], dtype=np.int64)
-    lib.trs_json_pack.restype = ctypes.c_int
     return _member_form(_pack_json_native(B, lambda jm, mm, *rest: lib.trs_json_pack(
-        ctypes.c_int(B), arr, lens.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(jm), ctypes.c_int(mm), *rest)), members)
+        B, arr, _hostapi.ptr(lens), jm, mm, *rest)), members)
 
 
 def pack_json_files(paths, members="general"):
     """Truss JSON FILES -> `PackedBatch`; the files are read (once) and parsed natively, in parallel
     (the bulk form of `Truss.LoadFromJSON`, reference `truss.py:401-421`)."""
     import ctypes
-    from .generate import _load
-    lib = _load()
+    lib = _hostapi.load()
     raw = [os.fsencode(p) for p in paths]
     B = len(raw)
     arr = (ctypes.c_char_p * B)(*raw)
     bufs = (ctypes.c_void_p * B)()
     lens = np.zeros([B], dtype=np.int64)
-    lib.trs_json_read_files.restype = ctypes.c_int
-    lib.trs_json_pack.restype = ctypes.c_int
-    rc = lib.trs_json_read_files(ctypes.c_int(B), arr, bufs, lens.ctypes.data_as(ctypes.c_void_p))
+    rc = lib.trs_json_read_files(B, arr, bufs, _hostapi.ptr(lens))
     try:
         if rc != 0:
             raise ValueError(f"truss JSON #{(-rc) // 1000 - 1}: {_JSON_ERRORS[6]}")
         return _member_form(_pack_json_native(B, lambda jm, mm, *rest: lib.trs_json_pack(
-            ctypes.c_int(B), bufs, lens.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(jm), ctypes.c_int(mm), *rest)),
-                            members)
+            B, bufs, _hostapi.ptr(lens), jm, mm, *rest)), members)
     finally:
-        lib.trs_json_free_files(ctypes.c_int(B), bufs)
+        lib.trs_json_free_files(B, bufs)
 
 
 @dataclass
@@ -601,29 +597,49 @@ class DeviceBatch:
                                         self.free_index.data_ptr(), self.n_free.data_ptr(),
                                         self._stream()), "trs_dofmap")
 
-    def _hints(self, substituted=False):
-        if not self.all_narrow or self.env is None or self.options["all_wide"]:
+    # -- the flag words of the C calls: one method per kind of call, composed nowhere else -------------
+    def _enveloped(self):
+        """There is envelope metadata and `all_wide` does not overrule it: what the narrow routing and the compact
+        form need."""
+        return self.env is not None and not self.options["all_wide"]
+
+    def _assemble_flags(self):
+        has_env = self.env is not None
+        return (ASM_ALL_NARROW if self.all_narrow and self._enveloped() else 0) | \
+               (ASM_COMPACT if self.options["compact"] and self._enveloped() else 0) | \
+               (ASM_ALL_WIDE if self.options["all_wide"] and has_env else 0) | \
+               (ASM_ALL_TILES if self.all_tiles and has_env else 0)
+
+    def _form_hints(self):
+        """How the matrices are stored and whether the factorising wave goes on to the substitution."""
+        return (HINT_COMPACT if self.options["compact"] and self._enveloped() else 0) | \
+               (0 if self.options["fused_substitution"] else HINT_SEPARATE_STAGES)
+
+    def _potrf_hints(self):
+        return (HINT_NO_WIDE if self.all_narrow and self._enveloped() else 0) | self._form_hints()
+
+    def _potrs_hints(self):
+        if not (self.all_narrow and self._enveloped()):
             return 0
         # (whether THIS batch's last factorisation ran with the substitution fused in, not the option's value now)
-        fused = substituted and self.rows <= 1024 and self._potrf_fused
+        fused = self.rows <= 1024 and self._potrf_fused
         return HINT_NO_WIDE | (HINT_SUBSTITUTED if fused else 0)
 
-    def _stage_hints(self):
-        return (HINT_COMPACT if self.options["compact"] and self.env is not None and not self.options["all_wide"] else 0) | \
-               (0 if self.options["fused_substitution"] else HINT_SEPARATE_STAGES) | \
-               (HINT_RECOVER_UNSTAGED if self.options["recover_unstaged"] else 0) | \
+    def _recover_hints(self):
+        return (HINT_RECOVER_UNSTAGED if self.options["recover_unstaged"] else 0) | \
                (HINT_RECOVER_SCAN if self.options["recover_scan"] else 0)
 
+    def _solve_hints(self, rows=False):
+        """`trs_solve` (never the fused small-system kernel: `solve` takes that path itself, by shape or by request), or
+        `trs_solve_rows`.  TRS_HINT_NO_WIDE goes out whatever `all_wide` says: TRS_HINT_ALL_WIDE overrides it in C."""
+        has_env = self.env is not None
+        return (0 if rows else HINT_NO_SMALL) | self._form_hints() | self._recover_hints() | \
+               (HINT_NO_WIDE if self.all_narrow and has_env else 0) | \
+               (HINT_ALL_TILES if self.all_tiles and has_env else 0) | \
+               (HINT_ALL_WIDE if self.options["all_wide"] and has_env else 0)
+
     def assemble(self, flags=0):
-        wide = self.options["all_wide"] and self.env is not None
-        if self.all_narrow and self.env is not None and not wide:
-            flags |= ASM_ALL_NARROW
-        if self.options["compact"] and self.env is not None and not wide:
-            flags |= ASM_COMPACT
-        if wide:
-            flags |= ASM_ALL_WIDE
-        if self.all_tiles and self.env is not None:
-            flags |= ASM_ALL_TILES
+        flags |= self._assemble_flags()
         fn, what = self._fn("trs_assemble")
         _capi.check(fn(
             self.B, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *self._members(),
@@ -637,13 +653,12 @@ class DeviceBatch:
         _capi.check(self.lib.trs_potrf_batched(self.B, self.n_free.data_ptr(), self.ld, self.rows,
                                                self.S.data_ptr(), self.info.data_ptr(), self._env_ptr(),
                                                self.work.data_ptr(), self.uf.data_ptr(), self.rows,
-                                               self._hints() | (self._stage_hints() & (HINT_COMPACT | HINT_SEPARATE_STAGES)),
-                                               self._stream()), "trs_potrf_batched")
+                                               self._potrf_hints(), self._stream()), "trs_potrf_batched")
 
     def potrs(self):
         _capi.check(self.lib.trs_potrs_batched(self.B, self.n_free.data_ptr(), self.ld, self.rows,
                                                self.S.data_ptr(), self.uf.data_ptr(), self.rows,
-                                               self._env_ptr(), self._hints(substituted=True), self._stream()),
+                                               self._env_ptr(), self._potrs_hints(), self._stream()),
                     "trs_potrs_batched")
 
     def recover(self):
@@ -654,7 +669,7 @@ class DeviceBatch:
             self.nJ.data_ptr(), self.nM.data_ptr(), self.uf.data_ptr(), self.rows, self.u.data_ptr(),
             self.f_ext.data_ptr(), self.N.data_ptr(),
             self.joint_out.data_ptr() if self.joint_out is not None else None,
-            self._stage_hints() & (HINT_RECOVER_UNSTAGED | HINT_RECOVER_SCAN), self._stream()), what)
+            self._recover_hints(), self._stream()), what)
 
     def recover_rows(self, rows, out, nJ_out_max, nM_out_max):
         """`trs_recover_rows`: the recovery with a ragged batch's bucket scatter folded in - the results of truss b go
@@ -667,8 +682,7 @@ class DeviceBatch:
             self.nJ.data_ptr(), self.nM.data_ptr(), self.uf.data_ptr(), self.rows,
             self.joint_out.data_ptr() if self.joint_out is not None else None, self.info.data_ptr(),
             rows.data_ptr(), int(nJ_out_max), int(nM_out_max), out["u"].data_ptr(), out["f_ext"].data_ptr(),
-            out["N"].data_ptr(), out["info"].data_ptr(), self._stage_hints() & (HINT_RECOVER_UNSTAGED | HINT_RECOVER_SCAN), self._stream()),
-            what)
+            out["N"].data_ptr(), out["info"].data_ptr(), self._recover_hints(), self._stream()), what)
 
     def solve_rows(self, rows, out, nJ_out_max, nM_out_max, types=None):
         """`trs_solve_rows`: the staged pipeline in one C call with `recover_rows` as its last stage.  `types` (table
@@ -684,9 +698,7 @@ class DeviceBatch:
                 self.info.data_ptr(), self.work.data_ptr(), self._env_ptr(),
                 self.joint_out.data_ptr() if self.joint_out is not None else None, rows.data_ptr(),
                 int(nJ_out_max), int(nM_out_max), out["info"].data_ptr(),
-                (HINT_NO_WIDE if self.all_narrow and self.env is not None else 0) | self._stage_hints() |
-                (HINT_ALL_TILES if self.all_tiles and self.env is not None else 0) | self._wide_hint(),
-                self._stream()), what)
+                self._solve_hints(rows=True), self._stream()), what)
 
     def _solve_small(self, fitness=None, out=None, types=None):
         """`trs_solve_small`: the whole of `Truss.Solve()` in one kernel (optionally with the GA
@@ -729,9 +741,6 @@ class DeviceBatch:
                                              genes.data_ptr(), type_table.data_ptr(), self.A.data_ptr(),
                                              self.E.data_ptr(), self.rho.data_ptr(), self._stream()), "trs_ga_sections")
 
-    def _wide_hint(self):
-        return HINT_ALL_WIDE if self.options["all_wide"] and self.env is not None else 0
-
     def solve(self, types=None):
         """The whole pipeline, asynchronous on the current stream: one kernel for a batch of small
         trusses (`trs_solve_small`), otherwise one C call that enqueues the five stages.  `types` as `solve_rows`."""
@@ -748,10 +757,7 @@ class DeviceBatch:
                 self.rows, self.u.data_ptr(), self.f_ext.data_ptr(), self.N.data_ptr(),
                 self.info.data_ptr(), self.work.data_ptr(), self._env_ptr(),
                 self.joint_out.data_ptr() if self.joint_out is not None else None,
-                # (not on the fused small path here, by shape or by request: the staged pipeline in any case)
-                (HINT_NO_WIDE if self.all_narrow and self.env is not None else 0) | self._stage_hints() | HINT_NO_SMALL |
-                (HINT_ALL_TILES if self.all_tiles and self.env is not None else 0) | self._wide_hint(),
-                self._stream()), what)
+                self._solve_hints(), self._stream()), what)
 
     # -- several load cases from one factorisation (include/trs_solver.h "Load cases") ------------------
     def factor(self):
@@ -1093,17 +1099,11 @@ def rcm_permutation(packed: PackedBatch):
     """Reverse Cuthill-McKee joint order of every truss (native, `csrc/reorder.c`):
     perm[b, k] = old id of the joint that becomes joint k.  Shrinks the envelope of the reduced
     stiffness matrix of trusses that are not numbered along their long axis (cube trusses)."""
-    import ctypes
-    from .generate import _load
-    lib = _load()
-    lib.trs_rcm_order.restype = ctypes.c_int
     perm = np.empty([packed.B, packed.nJ_max], dtype=np.int32)
-    ptr = lambda a: np.ascontiguousarray(a).ctypes.data_as(ctypes.c_void_p)
+    ptr = _hostapi.ptr
     conn, cbits, nJ, nM = (np.ascontiguousarray(a) for a in (packed.conn, packed.cbits, packed.nJ, packed.nM))
-    rc = lib.trs_rcm_order(ctypes.c_int(packed.B), ctypes.c_int(packed.nJ_max), ctypes.c_int(packed.nM_max),
-                           ptr(conn), ptr(cbits), ptr(nJ), ptr(nM), perm.ctypes.data_as(ctypes.c_void_p))
-    if rc != 0:
-        raise RuntimeError(f"trs_rcm_order failed ({rc})")
+    _hostapi.check(_hostapi.load().trs_rcm_order(packed.B, packed.nJ_max, packed.nM_max,
+                                                 ptr(conn), ptr(cbits), ptr(nJ), ptr(nM), ptr(perm)), "trs_rcm_order")
     return perm
 
 
@@ -1114,32 +1114,16 @@ def profile_permutation(packed: PackedBatch, return_choice=False, effort=2):
     the reference's cube trusses 25-35 % less factorisation work.  perm[b, k] = old id of the joint that
     becomes joint k; `return_choice` adds the winning candidate's id per truss (0 = RCM).  `effort`: 0 RCM and
     its reverse, 1 + one sweep, 2 everything, 3 every sweep and the RCM pair only for trusses below 128 free joints."""
-    import ctypes
-    from .generate import _load
-    lib = _load()
-    lib.trs_profile_order.restype = ctypes.c_int
     perm = np.empty([packed.B, packed.nJ_max], dtype=np.int32)
     choice = np.empty([packed.B], dtype=np.int32)
-    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    ptr = _hostapi.ptr
     xyz = np.ascontiguousarray(packed.xyz, dtype=np.float64)
     conn, nJ, nM = (np.ascontiguousarray(a, dtype=np.int32) for a in (packed.conn, packed.nJ, packed.nM))
     cbits = np.ascontiguousarray(packed.cbits, dtype=np.uint8)
-    rc = lib.trs_profile_order(ctypes.c_int(packed.B), ctypes.c_int(packed.nJ_max), ctypes.c_int(packed.nM_max),
-                               ptr(xyz), ptr(conn), ptr(cbits), ptr(nJ), ptr(nM), ptr(perm), ptr(choice),
-                               ctypes.c_int(effort))
-    if rc != 0:
-        raise RuntimeError(f"trs_profile_order failed ({rc})")
+    _hostapi.check(_hostapi.load().trs_profile_order(
+        packed.B, packed.nJ_max, packed.nM_max, ptr(xyz), ptr(conn), ptr(cbits), ptr(nJ), ptr(nM), ptr(perm), ptr(choice),
+        effort), "trs_profile_order")
     return (perm, choice) if return_choice else perm
-
-
-NARROW_MAX_BELOW = 24   # csrc/trs_common.h TRS_NARROW_MAX_BELOW: reach up to which a matrix goes to a wave of its own
-# include/trs_solver.h
-HINT_NO_WIDE, HINT_SUBSTITUTED, HINT_COMPACT, HINT_SEPARATE_STAGES, HINT_NO_SMALL, HINT_RECOVER_UNSTAGED = 1, 2, 4, 8, 16, 32
-HINT_RECOVER_SCAN = 128
-HINT_ALL_WIDE = 256
-HINT_ALL_TILES = 64
-ORDER_RCM_BELOW = 128           # csrc/order.hip RCM_BELOW: effort 3 prices Cuthill-McKee below this many free joints
-ASM_FULL_SYMMETRIC, ASM_COMPACT, ASM_ALL_NARROW, ASM_ALL_TILES, ASM_ALL_WIDE = 1, 2, 4, 8, 16
 
 
 def envelope_reach(packed: PackedBatch, perm=None):
@@ -1147,19 +1131,14 @@ def envelope_reach(packed: PackedBatch, perm=None):
     the numbering given, or after the renumbering `perm` (native, `csrc/reorder.c`; the metadata `trs_assemble`
     derives on the device).  A batch that stays at or below `NARROW_MAX_BELOW` holds no matrix for the
     work-group kernels."""
-    import ctypes
-    from .generate import _load
-    lib = _load()
-    lib.trs_envelope_reach.restype = ctypes.c_int
     reach = np.empty([packed.B], dtype=np.int32)
-    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    ptr = _hostapi.ptr
     conn, nJ, nM = (np.ascontiguousarray(a, dtype=np.int32) for a in (packed.conn, packed.nJ, packed.nM))
     cbits = np.ascontiguousarray(packed.cbits, dtype=np.uint8)
     pm = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32)
-    rc = lib.trs_envelope_reach(ctypes.c_int(packed.B), ctypes.c_int(packed.nJ_max), ctypes.c_int(packed.nM_max),
-                                ptr(conn), ptr(cbits), ptr(nJ), ptr(nM), None if pm is None else ptr(pm), ptr(reach))
-    if rc != 0:
-        raise RuntimeError(f"trs_envelope_reach failed ({rc})")
+    _hostapi.check(_hostapi.load().trs_envelope_reach(
+        packed.B, packed.nJ_max, packed.nM_max, ptr(conn), ptr(cbits), ptr(nJ), ptr(nM), ptr(pm), ptr(reach)),
+        "trs_envelope_reach")
     return reach
 
 
@@ -1188,21 +1167,15 @@ def joint_order(packed: PackedBatch, reorder):
 def permute_joints(packed: PackedBatch, perm):
     """The same trusses with joint k := old joint perm[b, k] (members keep their order).
     Native (`csrc/reorder.c`, OpenMP over the batch)."""
-    import ctypes
-    from .generate import _load
-    lib = _load()
-    lib.trs_apply_joint_order.restype = ctypes.c_int
     B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
     src = [np.ascontiguousarray(a, dtype=t) for a, t in (
         (perm, np.int32), (packed.nM, np.int32), (packed.xyz, np.float64), (packed.conn, np.int32),
         (packed.cbits, np.uint8), (packed.loads, np.float64))]
     xyz, conn = np.empty_like(src[2]), np.empty_like(src[3])
     cbits, loads = np.empty_like(src[4]), np.empty_like(src[5])
-    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-    rc = lib.trs_apply_joint_order(ctypes.c_int(B), ctypes.c_int(nJ_max), ctypes.c_int(nM_max),
-                                   *(ptr(a) for a in src), ptr(xyz), ptr(conn), ptr(cbits), ptr(loads))
-    if rc != 0:
-        raise RuntimeError(f"trs_apply_joint_order failed ({rc})")
+    ptr = _hostapi.ptr
+    _hostapi.check(_hostapi.load().trs_apply_joint_order(
+        B, nJ_max, nM_max, *(ptr(a) for a in src), ptr(xyz), ptr(conn), ptr(cbits), ptr(loads)), "trs_apply_joint_order")
     return PackedBatch(xyz, conn, packed.E, packed.A, packed.rho, cbits, loads, packed.nJ, packed.nM,
                        packed.dim, packed.n_free)
 

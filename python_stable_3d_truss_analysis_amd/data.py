@@ -20,6 +20,7 @@ import os
 
 import numpy as np
 
+from . import _hostapi
 from .batch import BatchResult, PackedBatch, pack_trusses
 from .truss import Truss
 from .type import MemberType, MetapathType, SupportType, TaskType
@@ -163,9 +164,7 @@ def feature_tensors_host(packed: PackedBatch, actual: BatchResult, prior: BatchR
     """float32 feature tensors of a solved batch, formed natively on the HOST (`csrc/graphfeat.c`,
     OpenMP over the batch; same formulas as `graph_arrays`, which stays the single-truss path):
     dict joint_x [B,nJ,FJ], member_x [B,nM,FM], joint_y / member_y (regression), weight [B] (numpy)."""
-    import ctypes
     import torch
-    from .generate import _load
     B, nJm, nMm = packed.B, packed.nJ_max, packed.nM_max
     regression = taskType == TaskType.REGRESSION
     FJ, FM = _feature_shapes(B, nJm, nMm, prior is not None, regression)
@@ -179,17 +178,12 @@ def feature_tensors_host(packed: PackedBatch, actual: BatchResult, prior: BatchR
             c(packed.cbits, np.uint8), c(packed.loads, np.float64), c(packed.nJ, np.int32), c(packed.nM, np.int32)]
     res = [c(actual.displace, np.float64), c(actual.internal, np.float64)] if regression else [None, None]
     res += [c(prior.displace, np.float64), c(prior.internal, np.float64)] if prior is not None else [None, None]
-    ptr = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-    tptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-    lib = _load()
-    lib.trs_graph_features.restype = ctypes.c_int
-    rc = lib.trs_graph_features(
-        ctypes.c_int(B), ctypes.c_int(nJm), ctypes.c_int(nMm), *(ptr(a) for a in keep), *(ptr(a) for a in res),
-        ctypes.c_double(fixedArea if prior is not None else 1.0), ctypes.c_double(forceScale),
-        ctypes.c_double(displaceScale), ctypes.c_double(positionScale), ctypes.c_int(int(regression)),
-        tptr(joint_x), tptr(member_x), tptr(joint_y), tptr(member_y), ptr(weight))
-    if rc != 0:
-        raise RuntimeError(f"trs_graph_features failed ({rc})")
+    ptr = _hostapi.ptr
+    tptr = lambda t: None if t is None else t.data_ptr()
+    _hostapi.check(_hostapi.load().trs_graph_features(
+        B, nJm, nMm, *(ptr(a) for a in keep), *(ptr(a) for a in res), fixedArea if prior is not None else 1.0,
+        forceScale, displaceScale, positionScale, int(regression), tptr(joint_x), tptr(member_x), tptr(joint_y),
+        tptr(member_y), ptr(weight)), "trs_graph_features")
     return {"joint_x": joint_x, "member_x": member_x, "joint_y": joint_y, "member_y": member_y,
             "weight": weight, "conn": torch.from_numpy(keep[1].astype(np.int64))}
 

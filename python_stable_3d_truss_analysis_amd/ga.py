@@ -17,6 +17,7 @@ import random
 
 import numpy as np
 
+from . import _hostapi
 from .truss import Truss
 from .type import MemberType
 from .utils import (INF, ZERO_EPS, EliteNumberTooMuchError, MinDisplaceTooLargeError,
@@ -314,28 +315,21 @@ class GA:
         if not (state[0] == 3 and len(state[1]) == 625 and type(random._inst) is random.Random):
             return False
         try:
-            from .generate import _load
-            return hasattr(_load(), "trs_ga_update_pop")
+            return hasattr(_hostapi.load(), "trs_ga_update_pop")
         except Exception:
             return False
 
     def _update_pop_native(self, pop, elite, out):
         """`UpdatePop` on uint8 gene matrices (`trs_ga_update_pop`): the draws come out of Python's global generator
         - state handed over and put back -, in the reference's order (ga.py:173-190)."""
-        import ctypes
-        from .generate import _load
         version, words, gauss = random.getstate()
         state = np.array(words, dtype=np.uint32)
         toCross = self.pCrossover
         toMutate = toCross + self.pMutate
         toKeep = toMutate + self.pOrigin
-        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-        lib = _load()
-        lib.trs_ga_update_pop.restype = ctypes.c_int
-        rc = lib.trs_ga_update_pop(ptr(state), ctypes.c_int(self.nPop), ctypes.c_int(self.nElite),
-                                   ctypes.c_int(self.nMember), ctypes.c_int(self.nType), ctypes.c_double(toCross),
-                                   ctypes.c_double(toMutate), ctypes.c_double(toKeep), ptr(elite), ptr(pop), ptr(out),
-                                   None)
+        ptr = _hostapi.ptr
+        rc = _hostapi.load().trs_ga_update_pop(ptr(state), self.nPop, self.nElite, self.nMember, self.nType, toCross,
+                                               toMutate, toKeep, ptr(elite), ptr(pop), ptr(out), None)
         if rc != 0:
             raise RuntimeError(f"trs_ga_update_pop refused the population ({rc})")
         random.setstate((version, tuple(state.tolist()), gauss))

@@ -13,92 +13,13 @@ import os
 
 import numpy as np
 
+from . import _hostapi
+# (the loader and the thread budget live with the binding; these names stay importable from here)
+from ._hostapi import LIB_PATH as GENLIB_PATH, load as _load   # noqa: F401
+from ._hostapi import available_cpus, host_thread_budget, host_threads, set_host_thread_share   # noqa: F401
 from .batch import PackedBatch, count_free
 from .truss import Truss
 from .type import GenerateMethod, LinkType, MemberType
-from .utils import HipExtensionError
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-GENLIB_PATH = os.path.join(_HERE, "libtrs_host.so")
-_gen = None
-
-
-def available_cpus():
-    """CPUs this process may actually use: the affinity mask, cut down to the cgroup CPU quota (v2
-    `cpu.max`, v1 `cpu.cfs_quota_us`) when the container has one."""
-    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
-    quota = None
-    try:
-        with open("/sys/fs/cgroup/cpu.max") as fh:
-            q, period = fh.read().split()[:2]
-            if q != "max":
-                quota = int(q) / int(period)
-    except (OSError, ValueError):
-        try:
-            with open("/sys/fs/cgroup/cpu/cpu.cfs_quota_us") as fq, open("/sys/fs/cgroup/cpu/cpu.cfs_period_us") as fp:
-                q, period = int(fq.read()), int(fp.read())
-                if q > 0 and period > 0:
-                    quota = q / period
-        except (OSError, ValueError):
-            pass
-    if quota is not None:
-        n = min(n, max(1, int(quota + 0.5)))
-    return max(1, n)
-
-
-_thread_share = None   # number of processes that share this host's CPUs with this one (set_host_thread_share)
-
-
-def host_thread_budget(sharers=None):
-    """Threads the native host helpers of THIS process may use: the CPUs the container really has
-    (`available_cpus`) divided by the number of processes that work side by side on this host - the ranks of a
-    `torchrun` launch (`LOCAL_WORLD_SIZE`) or the workers of a `shard.ShardedSolver`.  Eight ranks that each
-    start a team of every CPU oversubscribe the host eight times exactly where the ragged workloads are
-    host-bound (the joint order, the generator)."""
-    if sharers is None:
-        sharers = _thread_share
-    if sharers is None:
-        try:
-            sharers = int(os.environ.get("LOCAL_WORLD_SIZE", "1"))
-        except ValueError:
-            sharers = 1
-    return max(1, available_cpus() // max(1, int(sharers)))
-
-
-def set_host_thread_share(sharers):
-    """Declare that `sharers` processes share this host (a rank of an N-process job, a worker of a pool of
-    N): the OpenMP teams of the native helpers are sized to `host_thread_budget()` from now on
-    (`OMP_NUM_THREADS` in the environment still wins).  Returns the budget."""
-    global _thread_share
-    _thread_share = max(1, int(sharers))
-    if _gen is not None and "OMP_NUM_THREADS" not in os.environ:
-        _gen.trs_host_threads(host_thread_budget())
-    return host_thread_budget()
-
-
-def host_threads():
-    """Size of the OpenMP team the native helpers use right now."""
-    return int(_load().trs_host_threads(0))
-
-
-def _load():
-    global _gen
-    if _gen is None:
-        if not os.path.exists(GENLIB_PATH):
-            raise HipExtensionError(f"{GENLIB_PATH} is missing: run __graft_entry__.build()")
-        lib = ctypes.CDLL(GENLIB_PATH)
-        P, I, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
-        lib.trs_cubegen.restype = I
-        lib.trs_cubegen.argtypes = [I, ctypes.c_uint64, I, I, I, P, I, I, I, D, D, P, I, I, P, I, I, I,
-                                    P, P, P, P, P, P, P, P, P, P, ctypes.c_int64]
-        lib.trs_cubegen_bounds.restype = I
-        lib.trs_cubegen_bounds.argtypes = [I, I, I, I, I, P, P]
-        lib.trs_host_threads.restype = I
-        lib.trs_host_threads.argtypes = [I]
-        if "OMP_NUM_THREADS" not in os.environ:   # a team of every logical CPU is throttled under a CPU quota
-            lib.trs_host_threads(host_thread_budget())
-        _gen = lib
-    return _gen
 
 
 def _fresh_seed():
@@ -126,7 +47,7 @@ def generate_cube_batch(num_cubes, gridRange=(5, 5, 5), lengthRange=(50, 150),
     `isAddPinSupport=False` no joint is supported (an augmenter is expected to add supports).
     Truss b draws from a stream keyed by (seed, first_index + b): generating a dataset in chunks or
     shards (`first_index` = global index of the chunk's first truss) gives the same trusses."""
-    lib = _load()
+    lib = _hostapi.load()
     num_cubes = np.ascontiguousarray(num_cubes, dtype=np.int32).ravel()
     B = len(num_cubes)
     gx, gy, gz = (int(v) for v in gridRange)
@@ -139,18 +60,14 @@ def generate_cube_batch(num_cubes, gridRange=(5, 5, 5), lengthRange=(50, 150),
     frange = np.ascontiguousarray(forceRange, dtype=np.float64).reshape(3, 2)
     lo, hi = (-1, -1) if nForceRange is None else tuple(-1 if v is None else int(v) for v in nForceRange)
     retries = ctypes.c_int64(0)
-    ptr = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    ptr = _hostapi.ptr
 
     def run(nJ_max, nM_max, xyz, conn, E, A, rho, cbits, loads):
-        rc = lib.trs_cubegen(B, int(seed) & (2 ** 64 - 1), gx, gy, gz, ptr(num_cubes), int(method),
-                             int(linkType), int(bool(isAllowParallel)) | (0 if isAddPinSupport else 2),
-                             float(lengthRange[0]),
-                             float(lengthRange[1]), ptr(frange), lo, hi, ptr(table), len(table), nJ_max,
-                             nM_max, ptr(xyz), ptr(conn), ptr(E), ptr(A), ptr(rho), ptr(cbits), ptr(loads),
-                             ptr(nJ), ptr(nM), ctypes.cast(ctypes.byref(retries), ctypes.c_void_p),
-                             int(first_index))
-        if rc != 0:
-            raise RuntimeError(f"trs_cubegen failed ({rc})")
+        _hostapi.check(lib.trs_cubegen(
+            B, int(seed) & (2 ** 64 - 1), gx, gy, gz, ptr(num_cubes), int(method), int(linkType),
+            int(bool(isAllowParallel)) | (0 if isAddPinSupport else 2), float(lengthRange[0]), float(lengthRange[1]),
+            ptr(frange), lo, hi, ptr(table), len(table), nJ_max, nM_max, ptr(xyz), ptr(conn), ptr(E), ptr(A), ptr(rho),
+            ptr(cbits), ptr(loads), ptr(nJ), ptr(nM), ctypes.byref(retries), int(first_index)), "trs_cubegen")
 
     # pass 1: sizes only (same per-truss RNG streams) -> exact padding; pass 2: the batch itself
     run(nJ_bound, nM_bound, None, None, None, None, None, None, None)
@@ -192,8 +109,8 @@ def generate_cube_batch_device(num_cubes, gridRange=(5, 5, 5), lengthRange=(50, 
     B = len(num_cubes)
     gx, gy, gz = (int(v) for v in gridRange)
     nJ_b, nM_b = ctypes.c_int(), ctypes.c_int()
-    _load().trs_cubegen_bounds(gx, gy, gz, int(num_cubes.max(initial=1)), int(isAllowParallel),
-                               ctypes.byref(nJ_b), ctypes.byref(nM_b))
+    _hostapi.load().trs_cubegen_bounds(gx, gy, gz, int(num_cubes.max(initial=1)), int(isAllowParallel),
+                                       ctypes.byref(nJ_b), ctypes.byref(nM_b))
     frange = np.ascontiguousarray(forceRange, dtype=np.float64).reshape(3, 2)
     lo, hi = (-1, -1) if nForceRange is None else tuple(-1 if v is None else int(v) for v in nForceRange)
     d_cubes = torch.from_numpy(num_cubes).to(dev)
@@ -207,7 +124,7 @@ def generate_cube_batch_device(num_cubes, gridRange=(5, 5, 5), lengthRange=(50, 
         with torch.cuda.device(dev):
             _capi.check(lib.trs_cubegen_dev(
                 B, int(seed) & (2 ** 64 - 1), gx, gy, gz, d_cubes.data_ptr(), int(method), int(linkType), flags,
-                float(lengthRange[0]), float(lengthRange[1]), frange.ctypes.data_as(ctypes.c_void_p), lo, hi,
+                float(lengthRange[0]), float(lengthRange[1]), _hostapi.ptr(frange), lo, hi,
                 d_types.data_ptr(), int(d_types.shape[0]), nJ_max, nM_max, ptr("xyz"), ptr("conn"), ptr("E"), ptr("A"),
                 ptr("rho"), ptr("cbits"), ptr("loads"), nJ.data_ptr(), nM.data_ptr(), n_free.data_ptr(),
                 status.data_ptr(), int(first_index), torch.cuda.current_stream(dev).cuda_stream), "trs_cubegen_dev")

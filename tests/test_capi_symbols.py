@@ -1,10 +1,11 @@
 """The C-ABI shared library loads on a CPU-only box and exports every symbol that
-include/trs_solver.h declares (no compute calls here)."""
+include/trs_solver.h declares (no compute calls here); the two ctypes tables (`_capi`, `_hostapi`), the flag constants
+and the flag words `DeviceBatch` composes, against the headers."""
 import ctypes
 import os
 import re
 
-from python_stable_3d_truss_analysis_amd import _capi
+from python_stable_3d_truss_analysis_amd import _capi, _hostapi
 from tests.helpers import ROOT
 
 
@@ -51,6 +52,142 @@ def test_host_library_exports_every_symbol_of_its_header():
                      "trs_json_free_files", "trs_json_pack", "trs_json_read_files", "trs_profile_order", "trs_rcm_order"]
     for name in names:
         assert hasattr(lib, name), f"{name} declared in trs_host.h but not exported"
+    assert sorted(_hostapi.SIGNATURES) == names     # the ctypes table covers the whole header
+    assert generate._load is _hostapi.load and lib is _hostapi.load()
+
+
+def declared_prototypes(header):
+    """name -> (returns void, number of parameters) of every function a header declares: comments and preprocessor
+    lines stripped, `name ( ... ) ;` matched, top-level commas counted (`void` / nothing = no parameter)."""
+    text = open(os.path.join(ROOT, "include", header)).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    text = re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*$", "", text, flags=re.M)
+    out = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(trs_[a-z_0-9]+)\s*\(([^;]*)\)\s*;", text):
+        depth, commas = 0, 0
+        for ch in params:
+            depth += (ch == "(") - (ch == ")")
+            commas += ch == "," and depth == 0
+        assert name not in out, name
+        out[name] = (ret.split()[-1] == "void", 0 if params.strip() in ("", "void") else commas + 1)
+    return out
+
+
+def test_signature_tables_have_the_headers_parameter_counts():
+    """Both bindings: every declared function has as many parameters as its table entry has argtypes, and a `void`
+    return is restype None (and nothing else is)."""
+    for header, table, count in (("trs_solver.h", _capi.SIGNATURES, 44), ("trs_host.h", _hostapi.SIGNATURES, 12)):
+        protos = declared_prototypes(header)
+        assert sorted(protos) == declared_symbols(header) == sorted(table) and len(protos) == count, header
+        for name, (is_void, n_params) in protos.items():
+            restype, argtypes = table[name]
+            assert len(argtypes) == n_params, f"{name}: {header} declares {n_params} parameters, the table {len(argtypes)}"
+            assert (restype is None) == is_void, f"{name}: restype {restype} against the header's return type"
+    host = declared_prototypes("trs_host.h")
+    assert [host[name][1] for name in sorted(host)] == [13, 29, 7, 9, 12, 25, 1, 2, 15, 4, 11, 8]
+    assert [name for name in host if host[name][0]] == ["trs_json_free_files"]
+
+
+def _define(path, name):
+    (value,) = re.findall(r"^[ \t]*#define[ \t]+%s[ \t]+(\d+)\b" % name, open(path).read(), flags=re.M)
+    return int(value)
+
+
+def test_flag_constants_equal_the_defines_of_the_headers():
+    """`_capi.ASM_*` / `_capi.HINT_*` are exactly the `TRS_ASM_*` / `TRS_HINT_*` of include/trs_solver.h (both ways), the
+    two routing thresholds equal their defines in csrc/, and `batch` hands the same names on."""
+    from python_stable_3d_truss_analysis_amd import batch
+    header = os.path.join(ROOT, "include", "trs_solver.h")
+    defines = {name: int(value) for name, value in
+               re.findall(r"^[ \t]*#define[ \t]+TRS_((?:ASM|HINT)_\w+)[ \t]+(\d+)\b", open(header).read(), flags=re.M)}
+    assert len(defines) == 14
+    ours = {name: value for name, value in vars(_capi).items() if name.startswith(("ASM_", "HINT_"))}
+    assert ours == defines
+    assert _capi.ABI_VERSION == _define(header, "TRS_ABI_VERSION")
+    assert _capi.NARROW_MAX_BELOW == _define(os.path.join(_capi.CSRC_DIR, "trs_common.h"), "TRS_NARROW_MAX_BELOW")
+    assert _capi.ORDER_RCM_BELOW == _define(os.path.join(_capi.CSRC_DIR, "reorder.c"), "TRS_ORDER_RCM_BELOW")
+    (device_rcm_below,) = re.findall(r"\bconstexpr\s+int\s+RCM_BELOW\s*=\s*(\d+)\s*;",
+                                     open(os.path.join(_capi.CSRC_DIR, "order.hip")).read())
+    assert _capi.ORDER_RCM_BELOW == int(device_rcm_below)
+    for name in list(ours) + ["NARROW_MAX_BELOW", "ORDER_RCM_BELOW"]:
+        assert getattr(batch, name) == getattr(_capi, name), name
+
+
+def test_device_batch_flag_words_for_every_setting():
+    """The words `DeviceBatch` hands to C, for all 2^5 option settings x `all_narrow` x `all_tiles` x envelope metadata
+    present / absent (x the two facts the substitution's word looks at): equal to the expressions each call site
+    spelled out before the words were composed in one place (written out below, not taken from the code under test)."""
+    import itertools
+    from python_stable_3d_truss_analysis_amd import batch
+    from python_stable_3d_truss_analysis_amd.batch import (
+        ASM_ALL_NARROW, ASM_ALL_TILES, ASM_ALL_WIDE, ASM_COMPACT, HINT_ALL_TILES, HINT_ALL_WIDE, HINT_COMPACT, HINT_NO_SMALL,
+        HINT_NO_WIDE, HINT_RECOVER_SCAN, HINT_RECOVER_UNSTAGED, HINT_SEPARATE_STAGES, HINT_SUBSTITUTED)
+    names = sorted(batch.DEFAULT_OPTIONS)
+    assert names == ["all_wide", "compact", "fused_substitution", "recover_scan", "recover_unstaged"]
+    seen = 0
+    for values in itertools.product((False, True), repeat=5):
+        options = dict(zip(names, values))
+        for all_narrow, all_tiles, env, rows, potrf_fused in itertools.product(
+                (False, True), (False, True), (None, object()), (1024, 1088), (False, True)):
+            db = batch.DeviceBatch.__new__(batch.DeviceBatch)     # no device: only what the words are made of
+            db.options, db.all_narrow, db.all_tiles, db.rows, db._potrf_fused = dict(options), all_narrow, all_tiles, rows, potrf_fused
+            db._slab = (None, None, None, env)
+            assert db.env is env
+
+            def hints(substituted=False):
+                if not all_narrow or env is None or options["all_wide"]:
+                    return 0
+                fused = substituted and rows <= 1024 and potrf_fused
+                return HINT_NO_WIDE | (HINT_SUBSTITUTED if fused else 0)
+
+            stage_hints = (HINT_COMPACT if options["compact"] and env is not None and not options["all_wide"] else 0) | \
+                          (0 if options["fused_substitution"] else HINT_SEPARATE_STAGES) | \
+                          (HINT_RECOVER_UNSTAGED if options["recover_unstaged"] else 0) | \
+                          (HINT_RECOVER_SCAN if options["recover_scan"] else 0)
+            wide_hint = HINT_ALL_WIDE if options["all_wide"] and env is not None else 0
+            flags = 0
+            wide = options["all_wide"] and env is not None
+            if all_narrow and env is not None and not wide:
+                flags |= ASM_ALL_NARROW
+            if options["compact"] and env is not None and not wide:
+                flags |= ASM_COMPACT
+            if wide:
+                flags |= ASM_ALL_WIDE
+            if all_tiles and env is not None:
+                flags |= ASM_ALL_TILES
+            solve_rows = (HINT_NO_WIDE if all_narrow and env is not None else 0) | stage_hints | \
+                         (HINT_ALL_TILES if all_tiles and env is not None else 0) | wide_hint
+            solve = (HINT_NO_WIDE if all_narrow and env is not None else 0) | stage_hints | HINT_NO_SMALL | \
+                    (HINT_ALL_TILES if all_tiles and env is not None else 0) | wide_hint
+            what = (options, all_narrow, all_tiles, env is not None, rows, potrf_fused)
+            words = {"assemble": (db._assemble_flags(), flags),
+                     "potrf": (db._potrf_hints(), hints() | (stage_hints & (HINT_COMPACT | HINT_SEPARATE_STAGES))),
+                     "potrs": (db._potrs_hints(), hints(substituted=True)),
+                     "recover": (db._recover_hints(), stage_hints & (HINT_RECOVER_UNSTAGED | HINT_RECOVER_SCAN)),
+                     "solve_rows": (db._solve_hints(rows=True), solve_rows),
+                     "solve": (db._solve_hints(), solve)}
+            for call, (got, want) in words.items():
+                assert type(got) is int and got == want, (call, got, want, what)
+            seen += 1
+    assert seen == 32 * 2 * 2 * 2 * 4
+
+
+def test_ctypes_prototypes_are_attached_in_the_two_binding_modules_only():
+    """The plumbing the bindings replaced does not grow back: no module of the package but `_capi` and `_hostapi` sets a
+    `.restype` / `.argtypes`, and none imports the host library's loader from `generate` inside a function."""
+    package = os.path.dirname(_capi.__file__)
+    attaches = re.compile(r"\.(restype|argtypes)\s*=[^=]")
+    checked = 0
+    for folder, _, files in os.walk(package):
+        for name in files:
+            if not name.endswith(".py"):
+                continue
+            text = open(os.path.join(folder, name)).read()
+            checked += 1
+            assert "from .generate import _load" not in text, name
+            assert bool(attaches.search(text)) == (name in ("_capi.py", "_hostapi.py")), name
+    assert checked >= 10
 
 
 def test_table_member_form_twins_mirror_their_general_entry_points():

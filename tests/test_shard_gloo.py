@@ -106,8 +106,8 @@ def test_eight_workers_share_the_host_cpus():
 
 def test_rank_of_a_launch_takes_its_share(monkeypatch):
     """Under `torchrun` (LOCAL_WORLD_SIZE ranks on this host) a rank's default budget is its share."""
-    from python_stable_3d_truss_analysis_amd import generate as gen
-    monkeypatch.setattr(gen, "_thread_share", None)
+    from python_stable_3d_truss_analysis_amd import _hostapi, generate as gen
+    monkeypatch.setattr(_hostapi, "_thread_share", None)   # (the budget's state lives with the host library's loader)
     monkeypatch.setenv("LOCAL_WORLD_SIZE", "4")
     assert gen.host_thread_budget() == max(1, gen.available_cpus() // 4)
     monkeypatch.delenv("LOCAL_WORLD_SIZE")
