@@ -24,7 +24,8 @@
 //                         the free-DOF counts, a neighbour minimum per joint, integer atomic minima per row
 //                         chunk and a suffix minimum with shuffles;
 //   phase C (work-group)  the cheapest (cost, evaluation order) wins; permutation, envelope reach (the launch hint
-//                         of trs_solver.h) and, if asked, the renumbered inputs go to HBM.
+//                         of trs_solver.h; kept by the wave that priced the winner) and, if asked, the renumbered
+//                         inputs go to HBM.
 #include "trs_common.h"
 #include "../../include/trs_solver.h"
 #include <type_traits>
@@ -34,6 +35,12 @@ namespace {
 #ifndef TRS_ORDER_THREADS
 #define TRS_ORDER_THREADS 256   // (512 = eight waves, one candidate task per wave instead of two on half of the waves, was
 #endif                          // measured: 1.35-2.1 x SLOWER - the kernel's rate follows the work-groups per CU: R5.7)
+#ifndef TRS_ORDER_MIN_WG
+#define TRS_ORDER_MIN_WG 6      // work-groups per CU the register allocation leaves room for (__launch_bounds__): see the kernel
+#endif
+#ifndef TRS_ORDER_MR
+#define TRS_ORDER_MR (2048 / TRS_ORDER_THREADS)   // members per thread kept in registers across phase A
+#endif
 constexpr int NT = TRS_ORDER_THREADS;
 constexpr int NWAVE = NT / 64;
 static_assert(NT == 128 || NT == 256 || NT == 512, "two, four or eight waves");
@@ -86,7 +93,7 @@ __host__ __device__ inline OrdLds ord_layout(int nJ_max, int nM_max) {
     l.c01 = take(2 * n * NWAVE);            // u16 [4][n] (first row chunk of a joint << 1) | its rows straddle two chunks
     p = p > lists_end ? p : lists_end;
     l.cmin = take(4 * (size_t)l.nch_max * NWAVE);  // int [4][nch]
-    l.ctrl = take(4 * 32);
+    l.ctrl = take(4 * 32);                  // int [32]   0..2 level counters; per wave from 8: rank, 16: choice, 24: reach
     l.red = take(8 * 64);
     l.total = p;
     return l;
@@ -223,11 +230,21 @@ __device__ int bfs_sweep(const Tables& t, int nj, int root, int stamp, int* last
     return tail;
 }
 
+// Envelope reach of an order below the 64 x 64 diagonal blocks (reorder.c trs_envelope_reach; what trs_assemble will
+// derive), from the values a pricing has in registers anyway: with ft[q] = first coupled chunk of row chunk q, made
+// non-decreasing from the bottom, the reach is the largest q - tcol over the block columns' last chunks tcol = 4 j + 3
+// and the chunks q > tcol with ft[q] <= tcol.  For a given q the nearest such column is j = ft[q] / 4, so
+//   reach = max(0, max_q (q - 4 (ft[q] / 4) - 3));
+// the padding chunks up to the next multiple of four couple to themselves and contribute nothing.  A lane keeps the
+// maximum over its own chunks; the wave maximum is taken only for an order that wins (consider()).
+__device__ __forceinline__ int reach_term(int q, int ft) { return q - (ft & ~3) - 3; }
+
 // Cost of an order of the nf free joints (reorder.c envelope_cost), by ONE wave on its own scratch.
-// ord(k) = old id of the joint at position k.  Returns sum_q w_q (w_q + 12); *n_out = free DOFs.
+// ord(k) = old id of the joint at position k.  Returns sum_q w_q (w_q + 12); *n_out = free DOFs; *reach_lane = this
+// lane's part of the order's envelope reach (reach_term).
 template <typename Ord>
 __device__ unsigned long long price_order(const Tables& t, int nf, Ord ord, unsigned short* newidx,
-                                          unsigned short* c01, int* cmin, int lane, int* n_out) {
+                                          unsigned short* c01, int* cmin, int lane, int* n_out, int* reach_lane) {
     int carry = 0;
     for (int base = 0; base < nf; base += 64) {
         const int k = base + lane;
@@ -260,7 +277,7 @@ __device__ unsigned long long price_order(const Tables& t, int nf, Ord ord, unsi
     }
     __builtin_amdgcn_wave_barrier();
     unsigned long long cost = 0;
-    int run = nch;
+    int run = nch, reach = 0;
     for (int base = (nch - 1) / 64 * 64; base >= 0; base -= 64) {
         const int q = base + lane;
         int v = q < nch ? cmin[q] : 0x7fffffff;
@@ -273,6 +290,7 @@ __device__ unsigned long long price_order(const Tables& t, int nf, Ord ord, unsi
         if (q < nch) {
             const unsigned long long w = (unsigned long long)(q - v + 1);
             cost += w * (w + 12ull);
+            reach = max(reach, reach_term(q, v));
         }
         run = __shfl(v, 0);
     }
@@ -280,6 +298,7 @@ __device__ unsigned long long price_order(const Tables& t, int nf, Ord ord, unsi
     for (int off = 32; off > 0; off >>= 1) cost += __shfl_xor(cost, off);
     __builtin_amdgcn_wave_barrier();
     *n_out = n;
+    *reach_lane = reach;
     return cost;
 }
 
@@ -287,11 +306,12 @@ __device__ unsigned long long price_order(const Tables& t, int nf, Ord ord, unsi
 // is most of a pricing): in the reversed order a joint's first coupled position is its neighbours' LAST position of
 // the forward order, and its rows start at n - (rows before it) - (its own rows).  fwd(k) = old id of the joint at
 // position k; c01r / cminr: a second scratch pair (the wave's slice of the sort keys, dead once the sort is done).
-// Same two values as price_order(fwd) and price_order(reversed).
+// Same two values, and the same two reach parts, as price_order(fwd) and price_order(reversed).
 template <typename Fwd>
 __device__ void price_order_pair(const Tables& t, int nf, Fwd fwd, unsigned short* newidx, unsigned short* c01,
                                  int* cmin, unsigned short* c01r, int* cminr, int lane, int* n_out,
-                                 unsigned long long* cost_fwd, unsigned long long* cost_rev) {
+                                 unsigned long long* cost_fwd, unsigned long long* cost_rev, int* reach_fwd,
+                                 int* reach_rev) {
     auto pack = [](int ds, int v) { return (unsigned short)(((ds >> 4) << 1) | ((((ds + v - 1) >> 4) != (ds >> 4)) ? 1 : 0)); };
     int carry = 0;
     for (int base = 0; base < nf; base += 64) {
@@ -338,7 +358,7 @@ __device__ void price_order_pair(const Tables& t, int nf, Fwd fwd, unsigned shor
     }
     __builtin_amdgcn_wave_barrier();
     unsigned long long cf = 0, cr = 0;
-    int runf = nch, runr = nch;
+    int runf = nch, runr = nch, rf = 0, rr = 0;
     for (int base = (nch - 1) / 64 * 64; base >= 0; base -= 64) {
         const int q = base + lane;
         int vf = q < nch ? cmin[q] : 0x7fffffff, vr = q < nch ? cminr[q] : 0x7fffffff;
@@ -356,6 +376,8 @@ __device__ void price_order_pair(const Tables& t, int nf, Fwd fwd, unsigned shor
             const unsigned long long wf = (unsigned long long)(q - vf + 1), wr = (unsigned long long)(q - vr + 1);
             cf += wf * (wf + 12ull);
             cr += wr * (wr + 12ull);
+            rf = max(rf, reach_term(q, vf));
+            rr = max(rr, reach_term(q, vr));
         }
         runf = __shfl(vf, 0);
         runr = __shfl(vr, 0);
@@ -369,9 +391,15 @@ __device__ void price_order_pair(const Tables& t, int nf, Fwd fwd, unsigned shor
     *n_out = n;
     *cost_fwd = cf;
     *cost_rev = cr;
+    *reach_fwd = rf;
+    *reach_rev = rr;
 }
 
-__global__ __launch_bounds__(NT, 4) void trs_joint_order_kernel(
+// Registers, not LDS, decided the work-groups per CU of the mid-sized shapes: 94 VGPRs are five waves per SIMD = five
+// work-groups per CU, where bar-942's 26 KB of tables leave room for six.  A bound of six work-groups (80 VGPRs, a
+// handful of spilled values) puts 4096 trusses through 2.67 instead of 3.2 rounds of the chip (EXPERIMENTS R10); eight
+// (64 VGPRs) spills three times as much.  Shapes whose tables allow four or fewer work-groups keep their occupancy.
+__global__ __launch_bounds__(NT, TRS_ORDER_MIN_WG) void trs_joint_order_kernel(
     const double* __restrict__ xyz, const void* __restrict__ conn, const unsigned char* __restrict__ cbits,
     const double* __restrict__ loads, const int* __restrict__ nJ_arr, const int* __restrict__ nM_arr,
     const int nJ_max, const int nM_max, int* __restrict__ perm_out, int* __restrict__ choice_out,
@@ -426,7 +454,7 @@ __global__ __launch_bounds__(NT, 4) void trs_joint_order_kernel(
     // stage (in the space the adjacency fill will take over later), the members' end joints are kept in
     // registers for the two passes that need them.
     double* Xs = reinterpret_cast<double*>(lds + lay.keys);  // [3 nJ_max] staged coordinates, in the shared region (dead before the fill)
-    constexpr int MR = 2048 / NT;   // a thread's first members stay in registers (2048 members without a second read)
+    constexpr int MR = TRS_ORDER_MR;   // a thread's first members stay in registers (no second read of them)
     int2 cr[MR];
     const size_t mrow = src * (size_t)nM_src;   // first member of the truss in the input arrays
     auto CNI = [&](int m) {
@@ -699,12 +727,15 @@ __global__ __launch_bounds__(NT, 4) void trs_joint_order_kernel(
     unsigned* k32 = reinterpret_cast<unsigned*>(t.keys) + (size_t)wave * lay.n4;
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(k32);
     unsigned long long my_cost = NO_COST;
-    int my_rank = 0x7fffffff, my_choice = 0, ndof = 0;
-    auto consider = [&](unsigned long long cost, int eval_rank, int choice, auto ord) {
-        if (cost < my_cost || (cost == my_cost && eval_rank < my_rank)) {
+    int my_rank = 0x7fffffff, my_choice = 0, my_reach = 0, ndof = 0, rl = 0;
+    auto consider = [&](unsigned long long cost, int eval_rank, int choice, auto ord, int reach_lane) {
+        if (cost < my_cost || (cost == my_cost && eval_rank < my_rank)) {   // (the same on every lane of the wave)
             my_cost = cost;
             my_rank = eval_rank;
             my_choice = choice;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) reach_lane = max(reach_lane, __shfl_xor(reach_lane, off));
+            my_reach = __builtin_amdgcn_readfirstlane(reach_lane);
             for (int k = lane; k < nf; k += 64) wbest[k] = (unsigned short)ord(k);
             __builtin_amdgcn_wave_barrier();
         }
@@ -712,15 +743,18 @@ __global__ __launch_bounds__(NT, 4) void trs_joint_order_kernel(
     if (nf > 0) {
         if (!use_rcm && !sweeps && wave == 0) {  // nothing to choose from: the free joints by ascending id
             auto ord = [&](int k) { return (int)t.ids[k]; };
-            consider(price_order(t, nf, ord, newidx, c01, cmin, lane, &ndof), 0, 14, ord);
+            const unsigned long long cost = price_order(t, nf, ord, newidx, c01, cmin, lane, &ndof, &rl);
+            consider(cost, 0, 14, ord, rl);
         }
         if (use_rcm && wave == (n_sweep > 1 ? NWAVE - 2 : 0)) {  // reverse Cuthill-McKee
             auto ord = [&](int k) { return t.order[nf - 1 - k]; };
-            consider(price_order(t, nf, ord, newidx, c01, cmin, lane, &ndof), 0, 0, ord);
+            const unsigned long long cost = price_order(t, nf, ord, newidx, c01, cmin, lane, &ndof, &rl);
+            consider(cost, 0, 0, ord, rl);
         }
         if (use_rcm && wave == (n_sweep > 1 ? NWAVE - 1 : 1)) {  // plain Cuthill-McKee
             auto ord = [&](int k) { return t.order[k]; };
-            consider(price_order(t, nf, ord, newidx, c01, cmin, lane, &ndof), 1, 1, ord);
+            const unsigned long long cost = price_order(t, nf, ord, newidx, c01, cmin, lane, &ndof, &rl);
+            consider(cost, 1, 1, ord, rl);
         }
         const bool wide_keys = key_bits > 32;
         for (int i = wide_keys ? ((wave & 1) ? n_sweep : wave / 2) : wave; i < n_sweep; i += wide_keys ? NWAVE / 2 : NWAVE) {
@@ -798,9 +832,10 @@ __global__ __launch_bounds__(NT, 4) void trs_joint_order_kernel(
             unsigned short* c01r = reinterpret_cast<unsigned short*>(k32);
             int* cminr = reinterpret_cast<int*>(k32 + ((nf + 3) >> 2 << 1));
             unsigned long long cost_fwd, cost_rev;
-            price_order_pair(t, nf, fwd, newidx, c01, cmin, c01r, cminr, lane, &ndof, &cost_fwd, &cost_rev);
-            consider(cost_fwd, 2 + 2 * i, 2 + 2 * ax, fwd);
-            consider(cost_rev, 3 + 2 * i, 3 + 2 * ax, rev);
+            int rl_rev = 0;
+            price_order_pair(t, nf, fwd, newidx, c01, cmin, c01r, cminr, lane, &ndof, &cost_fwd, &cost_rev, &rl, &rl_rev);
+            consider(cost_fwd, 2 + 2 * i, 2 + 2 * ax, fwd, rl);
+            consider(cost_rev, 3 + 2 * i, 3 + 2 * ax, rev, rl_rev);
             st.mark(4);
         }
     }
@@ -810,6 +845,7 @@ __global__ __launch_bounds__(NT, 4) void trs_joint_order_kernel(
         t.red[wave] = my_cost;
         t.ctrl[8 + wave] = my_rank;
         t.ctrl[16 + wave] = my_choice;
+        t.ctrl[24 + wave] = my_reach;
     }
     __syncthreads();
     st.mark(6);
@@ -837,43 +873,8 @@ __global__ __launch_bounds__(NT, 4) void trs_joint_order_kernel(
     if (tid == 0 && choice_out != nullptr) choice_out[b] = nf > 0 ? t.ctrl[16 + win] : 0;
     __syncthreads();
     for (int k = tid; k < nJ_max; k += NT) P[k] = fullperm[k];
-    // envelope reach of the chosen order below the 64 x 64 diagonal blocks (reorder.c trs_envelope_reach; what
-    // trs_assemble will derive): by wave 0 on its scratch
-    if (reach_out != nullptr && wave == 0) {
-        int widest = 0;
-        if (nf > 0) {
-            auto ord = [&](int k) { return (int)wperm[k]; };
-            int n = 0;
-            price_order(t, nf, ord, newidx, c01, cmin, lane, &n);
-            const int nch = (n + 15) >> 4, nchp = (n + 63) / 64 * 4;
-            int* ft = cmin;  // cmin -> ft: running minimum from the end (padding chunks couple to themselves)
-            for (int q = nch + lane; q < nchp; q += 64) ft[q] = q;
-            __builtin_amdgcn_wave_barrier();
-            int run = nchp;
-            for (int base = (nchp - 1) / 64 * 64; base >= 0; base -= 64) {
-                const int q = base + lane;
-                int v = q < nchp ? ft[q] : 0x7fffffff;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const int o = __shfl_down(v, off);
-                    if (lane + off < 64) v = min(v, o);
-                }
-                v = min(v, run);
-                if (q < nchp) ft[q] = v;
-                run = __shfl(v, 0);
-            }
-            __builtin_amdgcn_wave_barrier();
-            for (int j = lane; j < nchp / 4; j += 64) {  // last chunk q with ft[q] <= 4 j + 3 (ft is non-decreasing)
-                const int tcol = 4 * j + 3;
-                int q = tcol;
-                while (q + 1 < nchp && ft[q + 1] <= tcol) ++q;
-                widest = max(widest, q - tcol);
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) widest = max(widest, __shfl_xor(widest, off));
-        }
-        if (lane == 0) reach_out[b] = widest;
-    }
+    // envelope reach of the chosen order (the launch hint of trs_solver.h): the wave that priced the winner kept it
+    if (reach_out != nullptr && tid == 0) reach_out[b] = nf > 0 ? t.ctrl[24 + win] : 0;
     st.mark(7);
     // the renumbered inputs (reorder.c trs_apply_joint_order): joint k := old joint perm[k], members keep their
     // order with renumbered ends, padding members stay (0, 0)

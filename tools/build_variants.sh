@@ -23,7 +23,7 @@ fi
 for spec in "$@"; do
   tag=${spec%%:*}; flags=${spec#*:}
   objs=""
-  for f in dofmap assemble potrf potrs recover small graphfeat order rows cubegen capi; do
+  for f in dofmap assemble potrf potrs recover cases adjoint small graphfeat order rows cubegen capi; do
     if [ -n "${ONLY:-}" ] && ! echo " $ONLY " | grep -q " $f "; then objs="$objs $f.o"; continue; fi
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-value $flags -c $f.hip -o /tmp/var_${tag}_$f.o &
     objs="$objs /tmp/var_${tag}_$f.o"
