@@ -36,13 +36,14 @@ __all__ = ["Truss", "Member", "MemberType", "SupportType", "MetapathType", "Task
            "solve_batch", "pack_trusses", "PackedBatch", "BatchResult", "RaggedSolver", "DeviceBatch",
            "ShardedSolver", "solve_batch_sharded", "solve_batch_distributed",
            "solve_load_cases", "LoadCaseResult", "load_cases_from_json",
-           "solve_gradients", "GradientResult", "DifferentiableTruss"]
+           "solve_gradients", "GradientResult", "DifferentiableTruss",
+           "solve_modes", "ModeResult"]
 
 
 def __getattr__(name):
     # torch-dependent names are resolved lazily so that the model imports without torch
     if name in ("solve_batch", "pack_trusses", "PackedBatch", "BatchResult", "RaggedSolver", "DeviceBatch",
-                "solve_load_cases", "LoadCaseResult", "solve_gradients", "GradientResult"):
+                "solve_load_cases", "LoadCaseResult", "solve_gradients", "GradientResult", "solve_modes", "ModeResult"):
         from . import batch
         return getattr(batch, name)
     if name == "DifferentiableTruss":

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in `include/trs_solver.h` (library: `libtrs_hip.so`, in-tree).
+"""ctypes binding of the C ABI in `include/trs_solver.h` and `include/trs_modes.h` (library: `libtrs_hip.so`, in-tree).
 
 There is no fallback: if the library is missing, `load()` raises `HipExtensionError`.
 """
@@ -79,8 +79,22 @@ SIGNATURES = {
     "trs_adjoint_tab_grad": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
 }
 
+#: every symbol `include/trs_modes.h` declares (natural frequencies; csrc/modes.hip, the same library)
+MODES_SIGNATURES = {
+    "trs_modes_abi_version": (_I, []),
+    "trs_modes_fits": (_I, [_I, _I]),
+    "trs_modes_mass": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P, _P, _I, _P, _P]),
+    "trs_modes_tab_mass": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P, _P, _I, _P, _P]),
+    "trs_modes_step": (_I, [_I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _D, _P]),
+    "trs_modes_shapes": (_I, [_I, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
+}
+
 #: must equal TRS_ABI_VERSION of include/trs_solver.h
 ABI_VERSION = 10
+#: must equal TRS_MODES_ABI_VERSION of include/trs_modes.h
+MODES_ABI_VERSION = 1
+#: TRS_MODES_BLOCK of include/trs_modes.h: vectors per truss of the block iteration (one case group)
+MODES_BLOCK = 16
 
 # The flag words of the ABI (tests/test_capi_symbols.py compares every one with its define).
 # TRS_ASM_* of include/trs_solver.h: `flags` of trs_assemble
@@ -120,11 +134,12 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as exc:
         raise HipExtensionError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (restype, argtypes) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = restype
-        fn.argtypes = argtypes
-    if lib.trs_abi_version() != ABI_VERSION:
+    for table in (SIGNATURES, MODES_SIGNATURES):
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(lib, name)
+            fn.restype = restype
+            fn.argtypes = argtypes
+    if lib.trs_abi_version() != ABI_VERSION or lib.trs_modes_abi_version() != MODES_ABI_VERSION:
         raise HipExtensionError("libtrs_hip.so ABI version mismatch")
     _lib = lib
     return lib

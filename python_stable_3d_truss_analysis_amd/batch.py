@@ -16,7 +16,7 @@ import numpy as np
 from . import _capi, _hostapi
 from ._capi import (ASM_ALL_NARROW, ASM_ALL_TILES, ASM_ALL_WIDE, ASM_COMPACT, ASM_FULL_SYMMETRIC,   # noqa: F401
                     HINT_ALL_TILES, HINT_ALL_WIDE, HINT_COMPACT, HINT_NO_SMALL, HINT_NO_WIDE, HINT_RECOVER_SCAN,
-                    HINT_RECOVER_UNSTAGED, HINT_SEPARATE_STAGES, HINT_SUBSTITUTED, NARROW_MAX_BELOW, ORDER_RCM_BELOW)
+                    HINT_RECOVER_UNSTAGED, HINT_SEPARATE_STAGES, HINT_SUBSTITUTED, MODES_BLOCK, NARROW_MAX_BELOW, ORDER_RCM_BELOW)
 from .type import SupportType
 from .utils import HipExtensionError
 
@@ -824,7 +824,7 @@ class DeviceBatch:
 
     @property
     def generation(self):
-        """Counts the `factor()` and `solve_cases()` calls of this batch: a forward state is identified by the value
+        """Counts the `factor()`, `solve_cases()` and `modes()` calls of this batch: a forward state is identified by the value
         after its `solve_cases()`, and `adjoint_cases` refuses any other."""
         return getattr(self, "_generation", 0)
 
@@ -905,6 +905,96 @@ class DeviceBatch:
                 ptr(out.get("loads") if "loads" in want else None), jo, stream), f"trs_adjoint{tab}_grad")
         self.cases_Lam = Lam
         return {k: out[k] for k in want}
+
+    # -- natural frequencies and mode shapes from the resident factor (include/trs_modes.h) ------------------
+    def modes(self, p, tol=1e-10, max_iters=256, check_every=8, joint_mass=None, mass_scale=1.0, out=None):
+        """The `p` lowest pairs of K_ff phi = lambda M phi of every truss (M: lumped mass, include/trs_modes.h) by block
+        inverse iteration against the resident factor (`factor()` first): per iteration one `trs_potrs_cases` launch
+        on a block of 16 vectors and one `trs_modes_step` launch; every `check_every` iterations the residuals are
+        formed, the trusses whose first n_modes pairs are below `tol` freeze, and ONE small read-back (is any truss still
+        iterating?) decides whether to go on, up to `max_iters`.  `joint_mass`: float64 device tensor [B, nJ_max] in the
+        CALLER's joint numbering (non-structural mass), or None; `mass_scale` multiplies the members' mass.
+        Returns a dict of device tensors lam [B, p] (NaN beyond n_modes), phi [B, p, nJ_max, 3] (caller's numbering,
+        M-orthonormal, largest component positive), resid [B, p], n_modes [B] = min(p, DOFs with mass) and iters [B]
+        (0: not converged within `max_iters` - the last iterate and its residual are returned all the same).
+        The block shares the buffer of `solve_cases`' right-hand sides, so a forward solution kept for
+        `adjoint_cases` is invalidated (`generation` is bumped); the factor is only read."""
+        t = self.torch
+        if not getattr(self, "_factored", False):
+            raise ValueError("modes(): no factor - call factor() first")
+        _check_mode_args(self.B, self.nJ_max, p, None if joint_mass is None else tuple(joint_mass.shape), mass_scale, tol,
+                         max_iters, check_every)
+        p, max_iters, check_every = int(p), int(max_iters), int(check_every)
+        if joint_mass is not None:
+            if joint_mass.dtype != t.float64 or joint_mass.device != self.device:
+                raise ValueError(f"modes(): joint_mass must be float64 [B={self.B}, nJ_max={self.nJ_max}] on {self.device}")
+            joint_mass = joint_mass.contiguous()
+        shapes = {"lam": ([self.B, p], t.float64), "phi": ([self.B, p, self.nJ_max, 3], t.float64),
+                  "resid": ([self.B, p], t.float64), "n_modes": ([self.B], t.int32), "iters": ([self.B], t.int32)}
+        if out is None:
+            out = {}
+        for k, (shape, dtype) in shapes.items():
+            if k not in out:
+                out[k] = t.zeros(shape, dtype=dtype, device=self.device)
+            elif list(out[k].shape) != shape or out[k].dtype != dtype or out[k].device != self.device \
+                    or not out[k].is_contiguous():
+                raise ValueError(f"modes(): out[{k!r}] must be a contiguous {dtype} {shape} tensor on {self.device}")
+        out = {k: out[k] for k in shapes}
+        if self.B == 0:
+            return out
+        if not self.lib.trs_modes_fits(self.nJ_max, self.nM_max):
+            raise HipExtensionError(f"modes(): a truss of {self.nJ_max} joints / {self.nM_max} members exceeds the LDS "
+                                    "of the mass kernel (trs_modes_fits)")
+        Q = MODES_BLOCK
+        F = getattr(self, "cases_F", None)   # the block's right-hand sides / solutions: the load cases' buffer
+        if F is None or int(F.shape[1]) != Q:
+            F = t.empty([self.B, Q, self.rows], dtype=t.float64, device=self.device)
+        self.cases_F = F
+        self._bump_generation()              # (whatever `solve_cases` left there is gone: `adjoint_cases` refuses it)
+        ws = getattr(self, "_modes_ws", None)
+        if ws is None:
+            f64 = lambda *shape: t.empty(list(shape), dtype=t.float64, device=self.device)
+            i32 = lambda *shape: t.empty(list(shape), dtype=t.int32, device=self.device)
+            ws = self._modes_ws = {"X": f64(self.B, Q, self.rows), "Mf": f64(self.B, self.rows), "lam": f64(self.B, Q),
+                                   "resid": f64(self.B, Q), "n_mass": i32(self.B), "state": i32(self.B)}
+        ptr = lambda x: None if x is None else x.data_ptr()
+        jo = ptr(self.joint_out)
+        stream = self._stream()
+        if self.table:
+            mass_fn, what = self.lib.trs_modes_tab_mass, "trs_modes_tab_mass"
+            members = (self.conn.data_ptr(), self.type_idx.data_ptr(), self.types.data_ptr())
+        else:
+            mass_fn, what = self.lib.trs_modes_mass, "trs_modes_mass"
+            members = (self.conn.data_ptr(), self.A.data_ptr(), self.rho.data_ptr())
+
+        def step(first, check, it):
+            _capi.check(self.lib.trs_modes_step(
+                self.B, p, self.n_free.data_ptr(), ws["n_mass"].data_ptr(), ws["Mf"].data_ptr(), F.data_ptr(),
+                ws["X"].data_ptr(), self.rows, ws["lam"].data_ptr(), ws["resid"].data_ptr(), ws["state"].data_ptr(),
+                first, check, it, float(tol), stream), "trs_modes_step")
+
+        with t.cuda.device(self.device):
+            _capi.check(mass_fn(self.B, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *members, ptr(joint_mass), jo,
+                                float(mass_scale), self.free_index.data_ptr(), self.n_free.data_ptr(),
+                                self.nJ.data_ptr(), self.nM.data_ptr(), ws["Mf"].data_ptr(), self.rows,
+                                ws["n_mass"].data_ptr(), stream), what)
+            step(1, 0, 0)
+            for it in range(1, max_iters + 1):
+                check = it % check_every == 0 or it == max_iters
+                _capi.check(self.lib.trs_potrs_cases(self.B, Q, self.n_free.data_ptr(), self.ld, self.rows,
+                                                     self.S.data_ptr(), F.data_ptr(), self.rows, self._env_ptr(), stream),
+                            "trs_potrs_cases")
+                step(0, int(check), it)
+                if check and not bool((ws["state"] == 0).any().item()):   # the one read-back per check point
+                    break
+            _capi.check(self.lib.trs_modes_shapes(self.B, p, self.nJ_max, ws["X"].data_ptr(), self.rows,
+                                                  self.free_index.data_ptr(), self.nJ.data_ptr(), jo,
+                                                  out["phi"].data_ptr(), stream), "trs_modes_shapes")
+        out["lam"].copy_(ws["lam"][:, :p])
+        out["resid"].copy_(ws["resid"][:, :p])
+        out["n_modes"].copy_(ws["n_mass"].clamp(max=p))
+        out["iters"].copy_(ws["state"])
+        return out
 
     def fitness(self, allow_stress, allow_displace, out=None):
         """(weight, stress_violation, displacement_violation) per truss, on device."""
@@ -2327,6 +2417,96 @@ def solve_gradients(trusses_or_packed, loads, grad_u=None, grad_f_ext=None, grad
         grads = {k: host(v) for k, v in grads.items()}
     return (LoadCaseResult(u, f, N, info),
             GradientResult(grads["A"], grads["E"], grads["xyz"], grads["loads"], info))
+
+
+@dataclass
+class ModeResult:
+    """Results of `solve_modes`: eigenvalue [B, p] (lambda = omega^2 of K phi = lambda M phi, ascending; NaN beyond
+    n_modes), omega [B, p] = sqrt(eigenvalue), shape [B, p, nJ_max, 3] (caller's joint numbering, M-orthonormal, zero at
+    constrained DOFs, largest component positive; z = 0 for a 2D truss), residual [B, p] (relative, in the M-norm),
+    n_modes [B] = min(p, free DOFs with mass), iters [B] (the iteration at which the truss's pairs were all below the
+    tolerance; 0 = not within max_iters), info [B] (the factorisation's status: a truss with info != 0 has meaningless
+    modes, the others are unaffected)."""
+    eigenvalue: np.ndarray
+    omega: np.ndarray
+    shape: np.ndarray
+    residual: np.ndarray
+    n_modes: np.ndarray
+    iters: np.ndarray
+    info: np.ndarray
+
+
+def _check_mode_args(B, nJ_max, p, joint_mass_shape, mass_scale, tol, max_iters, check_every=8, joint_mass_min=None):
+    """The argument errors of `solve_modes` / `DeviceBatch.modes` that need no device."""
+    if isinstance(p, bool) or int(p) != p or not 1 <= int(p) <= 8:
+        raise ValueError(f"modes: p must be an integer in 1 .. 8 (one block of {MODES_BLOCK} vectors delivers at most 8 "
+                         f"pairs), got {p!r}")
+    if joint_mass_shape is not None and tuple(int(x) for x in joint_mass_shape) != (B, nJ_max):
+        raise ValueError(f"modes: joint_mass must be [B={B}, nJ_max={nJ_max}], got {tuple(joint_mass_shape)}")
+    if joint_mass_min is not None and not joint_mass_min >= 0:
+        raise ValueError("modes: joint_mass must be non-negative and finite")
+    if not (np.isfinite(mass_scale) and mass_scale >= 0):
+        raise ValueError(f"modes: mass_scale must be non-negative and finite, got {mass_scale!r}")
+    if not tol > 0:
+        raise ValueError(f"modes: tol must be positive, got {tol!r}")
+    if int(max_iters) < 1 or int(check_every) < 1:
+        raise ValueError("modes: max_iters and check_every must be at least 1")
+
+
+def solve_modes(trusses_or_packed, p=6, joint_mass=None, mass_scale=1.0, tol=1e-10, max_iters=256, device=None,
+                reorder=False, options=None, max_slab_bytes=64 << 30, on_device=False, use_envelope=True):
+    """The `p` (1 .. 8) lowest natural frequencies and mode shapes of every truss of a batch, from ONE factorisation per
+    truss: lumped mass m_j = mass_scale * (half the mass a * length * density of every member at joint j) +
+    joint_mass[b, j] on the three DOFs of a joint, block inverse iteration against the resident Cholesky factor
+    (`DeviceBatch.factor` / `DeviceBatch.modes`, include/trs_modes.h).  `joint_mass`: [B, nJ_max] (numpy or torch,
+    caller's joint numbering, non-negative) or None; `mass_scale`: 1 / g for densities given as weight densities.
+    Buckets, member forms, `reorder` plans, `on_device` and `use_envelope` as `solve_load_cases`.  Returns a
+    `ModeResult`."""
+    packed = trusses_or_packed if isinstance(trusses_or_packed, PackedBatch) else pack_trusses(list(trusses_or_packed))
+    B, nJ_max = packed.B, packed.nJ_max
+    jm_shape = jm_min = None
+    if joint_mass is not None:
+        jm_shape = tuple(int(x) for x in joint_mass.shape)
+        if isinstance(joint_mass, np.ndarray):
+            joint_mass = np.ascontiguousarray(joint_mass, dtype=np.float64)
+            jm_min = float(joint_mass.min()) if joint_mass.size else 0.0
+            jm_min = jm_min if np.isfinite(joint_mass).all() else float("nan")
+        else:
+            jm_min = float(joint_mass.min()) if joint_mass.numel() else 0.0
+            jm_min = jm_min if bool(joint_mass.isfinite().all()) else float("nan")
+    _check_mode_args(B, nJ_max, p, jm_shape, mass_scale, tol, max_iters, joint_mass_min=jm_min)
+    p = int(p)
+    torch, dev = _require_gpu(device)
+    if isinstance(joint_mass, np.ndarray):
+        joint_mass = torch.from_numpy(joint_mass)
+    if joint_mass is not None:
+        joint_mass = joint_mass.to(device=dev, dtype=torch.float64)
+    lam = torch.full([B, p], float("nan"), dtype=torch.float64, device=dev)
+    phi = torch.zeros([B, p, nJ_max, 3], dtype=torch.float64, device=dev)
+    resid = torch.full([B, p], float("nan"), dtype=torch.float64, device=dev)
+    n_modes = torch.zeros([B], dtype=torch.int32, device=dev)
+    iters = torch.zeros([B], dtype=torch.int32, device=dev)
+    info = torch.zeros([B], dtype=torch.int32, device=dev)
+    if B:
+        for idx in size_buckets(packed, max_slab_bytes):
+            sub = packed.take(idx).trimmed()
+            rows = torch.from_numpy(np.asarray(idx, dtype=np.int64)).to(dev)
+            db = DeviceBatch(sub, dev, use_envelope=use_envelope, use_small=False, reorder=reorder, options=options)
+            db.factor()
+            jm = None if joint_mass is None else joint_mass.index_select(0, rows)[:, :sub.nJ_max].contiguous()
+            res = db.modes(p, tol=tol, max_iters=max_iters, joint_mass=jm, mass_scale=mass_scale)
+            lam[rows] = res["lam"]
+            phi[rows, :, :sub.nJ_max] = res["phi"]
+            resid[rows] = res["resid"]
+            n_modes[rows] = res["n_modes"]
+            iters[rows] = res["iters"]
+            info[rows] = db.info
+    omega = lam.sqrt()
+    if on_device:
+        return ModeResult(lam, omega, phi, resid, n_modes, iters, info)
+    torch.cuda.synchronize(dev)
+    host = lambda x: x.cpu().numpy()
+    return ModeResult(host(lam), host(omega), host(phi), host(resid), host(n_modes), host(iters), host(info))
 
 
 def _is_pinned(packed):

@@ -380,6 +380,35 @@ class Truss:
             t.AdoptDenseResults(result.displace[0, k], result.external[0, k], result.internal[0, k])
         return copies
 
+    def NaturalFrequencies(self, nModes=6, jointMasses=None, massScale=1.0, returnShapes=False):
+        """The `nModes` (1 .. 8) lowest natural circular frequencies omega of this truss, ascending, with a lumped mass
+        matrix: every member gives half of `a * length * density` (times `massScale`: 1 / g for weight densities) to
+        each end joint, `jointMasses` ({jointID: mass}) adds non-structural mass.  A truss with fewer than `nModes` free
+        DOFs of positive mass returns as many values as it has.  `returnShapes=True`: also a list of
+        `{jointID: vector}` dicts, one per frequency (mass-orthonormal, largest component positive).
+        One factorisation on the GPU and inverse iteration against it (`batch.solve_modes`); the truss's loads, its
+        solved state and its results stay as they are.  Raises `TrussNotStableError` when the counting test fails and
+        `numpy.linalg.LinAlgError` when the reduced stiffness matrix is not positive definite, as `Solve()` does."""
+        if not self.isStable:
+            raise TrussNotStableError("The truss is not stable !")
+        from .batch import pack_trusses, solve_modes  # late import: keeps the model importable without torch
+        packed = pack_trusses([self])
+        masses = None
+        if jointMasses:
+            masses = np.zeros([1, packed.nJ_max])
+            for jointID, mass in jointMasses.items():
+                masses[0, jointID] = mass
+        result = solve_modes(packed, p=nModes, joint_mass=masses, mass_scale=massScale)
+        if int(result.info[0]) != 0:
+            raise np.linalg.LinAlgError("Singular matrix")
+        count = int(result.n_modes[0])
+        omega = result.omega[0, :count].copy()
+        if not returnShapes:
+            return omega
+        nJ, dim = len(self._pos), self._dim
+        shapes = [dict(zip(range(nJ), result.shape[0, k, :nJ, :dim].copy())) for k in range(count)]
+        return omega, shapes
+
     def AdoptDenseResults(self, displace, external, internal):
         """Install dense results (`[nJoint, dim]`, `[nJoint, dim]`, `[nMember]`) as the
         sparse result dicts of the reference: entries below 1e-10 in every component are
