@@ -28,7 +28,7 @@ if "GPU_MAX_HW_QUEUES" not in _os.environ:
         _os.environ["GPU_MAX_HW_QUEUES"] = "8"
 
 from .type import GenerateMethod, LinkType, MemberType, MetapathType, SupportType, TaskType
-from .truss import Member, Truss, load_cases_from_json
+from .truss import LoadCase, Member, Truss, load_cases_from_json
 from .utils import HipExtensionError, TrussNotStableError
 
 __all__ = ["Truss", "Member", "MemberType", "SupportType", "MetapathType", "TaskType",
@@ -37,13 +37,14 @@ __all__ = ["Truss", "Member", "MemberType", "SupportType", "MetapathType", "Task
            "ShardedSolver", "solve_batch_sharded", "solve_batch_distributed",
            "solve_load_cases", "LoadCaseResult", "load_cases_from_json",
            "solve_gradients", "GradientResult", "DifferentiableTruss",
-           "solve_modes", "ModeResult"]
+           "solve_modes", "ModeResult", "solve_effect_cases", "EffectCaseResult", "LoadCase"]
 
 
 def __getattr__(name):
     # torch-dependent names are resolved lazily so that the model imports without torch
     if name in ("solve_batch", "pack_trusses", "PackedBatch", "BatchResult", "RaggedSolver", "DeviceBatch",
-                "solve_load_cases", "LoadCaseResult", "solve_gradients", "GradientResult", "solve_modes", "ModeResult"):
+                "solve_load_cases", "LoadCaseResult", "solve_gradients", "GradientResult", "solve_modes", "ModeResult",
+                "solve_effect_cases", "EffectCaseResult"):
         from . import batch
         return getattr(batch, name)
     if name == "DifferentiableTruss":

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in `include/trs_solver.h` and `include/trs_modes.h` (library: `libtrs_hip.so`, in-tree).
+"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h` and `include/trs_effects.h` (library: `libtrs_hip.so`, in-tree).
 
 There is no fallback: if the library is missing, `load()` raises `HipExtensionError`.
 """
@@ -89,10 +89,24 @@ MODES_SIGNATURES = {
     "trs_modes_shapes": (_I, [_I, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
 }
 
+#: every symbol `include/trs_effects.h` declares (settlements, pre-strain, self-weight; csrc/effects.hip, the same library)
+EFFECTS_SIGNATURES = {
+    "trs_effects_abi_version": (_I, []),
+    "trs_effects_fits": (_I, [_I, _I]),
+    "trs_effects_rhs": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "trs_effects_tab_rhs": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "trs_effects_recover": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P,
+                                 _P, _P]),
+    "trs_effects_tab_recover": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P,
+                                     _P, _P]),
+}
+
 #: must equal TRS_ABI_VERSION of include/trs_solver.h
 ABI_VERSION = 10
 #: must equal TRS_MODES_ABI_VERSION of include/trs_modes.h
 MODES_ABI_VERSION = 1
+#: must equal TRS_EFFECTS_ABI_VERSION of include/trs_effects.h
+EFFECTS_ABI_VERSION = 1
 #: TRS_MODES_BLOCK of include/trs_modes.h: vectors per truss of the block iteration (one case group)
 MODES_BLOCK = 16
 
@@ -134,12 +148,13 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as exc:
         raise HipExtensionError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for table in (SIGNATURES, MODES_SIGNATURES):
+    for table in (SIGNATURES, MODES_SIGNATURES, EFFECTS_SIGNATURES):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype = restype
             fn.argtypes = argtypes
-    if lib.trs_abi_version() != ABI_VERSION or lib.trs_modes_abi_version() != MODES_ABI_VERSION:
+    if lib.trs_abi_version() != ABI_VERSION or lib.trs_modes_abi_version() != MODES_ABI_VERSION \
+            or lib.trs_effects_abi_version() != EFFECTS_ABI_VERSION:
         raise HipExtensionError("libtrs_hip.so ABI version mismatch")
     _lib = lib
     return lib

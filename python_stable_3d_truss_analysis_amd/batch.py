@@ -71,6 +71,12 @@ class PackedBatch:
     def is_table(self):
         return self.type_idx is not None
 
+    def constrained(self):
+        """bool [B, nJ_max, 3]: the DOF is held by a support (the bits of `cbits`; False on padding joints)."""
+        bits = np.asarray(self.cbits, dtype=np.uint8)
+        live = np.arange(self.nJ_max)[None, :] < np.asarray(self.nJ)[:, None]
+        return (((bits[:, :, None] >> np.arange(3, dtype=np.uint8)) & 1) != 0) & live[:, :, None]
+
     def _map(self, fn):
         """A batch whose per-truss arrays are `fn(field name, array)` (absent fields stay absent, the type table is shared)."""
         vals = {}
@@ -818,13 +824,94 @@ class DeviceBatch:
         self._forward = (self.generation, L)   # what `adjoint_cases` may differentiate
         return out
 
+    # -- load cases with settlements, pre-strain and self-weight (include/trs_effects.h) ------------------
+    def solve_effect_cases(self, loads=None, prestrain=None, settlement=None, accel=None, want_body=False, out=None):
+        """`solve_cases` for cases that carry more than joint forces, on the resident factor (`factor()` first): `loads`
+        [B, L, nJ_max, 3] joint forces, `prestrain` [B, L, nM_max] member initial strains (alpha dT, dL / L),
+        `settlement` [B, L, nJ_max, 3] prescribed displacements (read at constrained DOFs only) and `accel` [B, L, 3]
+        body-force vectors per unit weight (a member loads each end joint with half of a * length * density times it) -
+        float64 device tensors, joint arrays in the CALLER's numbering; any may be None, at least one must be given, and
+        all agree on L.  The effects change the right-hand side only (`trs_effects_rhs`), the substitution is
+        `trs_potrs_cases` as it is, and the recovery (`trs_effects_recover`) gives u with the settlements at the
+        supports, N = k c . (u1 - u0) - E A eps0 and f_ext without the self-weight (include/trs_effects.h).  Returns a
+        dict of device tensors u, f_ext [B, L, nJ_max, 3], N [B, L, nM_max] and - `want_body` - body [B, L, nJ_max, 3],
+        the self-weight load of every joint (`out`: such a dict to write into).  With only `loads` given the results are
+        those of `solve_cases(loads)` bit for bit.
+        `generation` is bumped and the forward state of `adjoint_cases` is dropped: the equivalent loads depend on A, E
+        and xyz, which the adjoint of `solve_cases` does not know, so gradients of these cases are refused."""
+        t = self.torch
+        if not getattr(self, "_factored", False):
+            raise ValueError("solve_effect_cases(): no factor - call factor() first")
+        given = {"loads": loads, "prestrain": prestrain, "settlement": settlement, "accel": accel}
+        tails = {"loads": (self.nJ_max, 3), "prestrain": (self.nM_max,), "settlement": (self.nJ_max, 3), "accel": (3,)}
+        names = {"loads": "nJ_max, 3", "prestrain": "nM_max", "settlement": "nJ_max, 3", "accel": "3"}
+        L = None
+        for name, x in given.items():
+            if x is None:
+                continue
+            shape = tuple(int(v) for v in x.shape)
+            if len(shape) != 2 + len(tails[name]) or shape[:1] + shape[2:] != (self.B,) + tails[name] \
+                    or x.dtype != t.float64 or x.device != self.device:
+                raise ValueError(f"solve_effect_cases(): {name} must be float64 [B={self.B}, L, {names[name]}] "
+                                 f"(nJ_max={self.nJ_max}, nM_max={self.nM_max}) on {self.device}")
+            if L is not None and shape[1] != L:
+                raise ValueError(f"solve_effect_cases(): {name} has L = {shape[1]}, the arguments before it L = {L}")
+            L = shape[1]
+            given[name] = x.contiguous()
+        if L is None:
+            raise ValueError("solve_effect_cases(): give at least one of loads, prestrain, settlement, accel")
+        shapes = {"u": [self.B, L, self.nJ_max, 3], "f_ext": [self.B, L, self.nJ_max, 3], "N": [self.B, L, self.nM_max]}
+        if want_body:
+            shapes["body"] = [self.B, L, self.nJ_max, 3]
+        if out is None:
+            out = {}
+        for k, shape in shapes.items():
+            if k not in out:
+                out[k] = t.zeros(shape, dtype=t.float64, device=self.device)
+            elif list(out[k].shape) != shape or out[k].dtype != t.float64 or out[k].device != self.device \
+                    or not out[k].is_contiguous():
+                raise ValueError(f"solve_effect_cases(): out[{k!r}] must be a contiguous float64 {shape} tensor on "
+                                 f"{self.device}")
+        out = {k: out[k] for k in shapes}
+        if self.B == 0 or L == 0:
+            return out
+        if not self.lib.trs_effects_fits(self.nJ_max, self.nM_max):
+            raise HipExtensionError(f"solve_effect_cases(): a truss of {self.nJ_max} joints / {self.nM_max} members "
+                                    "exceeds the LDS of the effect kernels (trs_effects_fits)")
+        F = getattr(self, "cases_F", None)   # right-hand sides, case-major [B][L][ld_f], ld_f = self.rows
+        if F is None or int(F.shape[1]) != L:
+            F = t.empty([self.B, L, self.rows], dtype=t.float64, device=self.device)
+        ptr = lambda x: None if x is None else x.data_ptr()
+        jo = ptr(self.joint_out)
+        stream = self._stream()
+        tab = "_tab" if self.table else ""
+        members = self._members() if self.table else self._members() + (ptr(self.rho),)
+        effects = tuple(ptr(given[k]) for k in ("loads", "prestrain", "settlement", "accel"))
+        self._forward = None                 # (F is about to be overwritten; see the docstring)
+        self._bump_generation()
+        with t.cuda.device(self.device):
+            _capi.check(getattr(self.lib, f"trs_effects{tab}_rhs")(
+                self.B, L, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *members, *effects,
+                self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), jo,
+                F.data_ptr(), self.rows, stream), f"trs_effects{tab}_rhs")
+            _capi.check(self.lib.trs_potrs_cases(self.B, L, self.n_free.data_ptr(), self.ld, self.rows,
+                                                 self.S.data_ptr(), F.data_ptr(), self.rows, self._env_ptr(), stream),
+                        "trs_potrs_cases")
+            _capi.check(getattr(self.lib, f"trs_effects{tab}_recover")(
+                self.B, L, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *members, *effects,
+                self.free_index.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), F.data_ptr(), self.rows,
+                out["u"].data_ptr(), out["f_ext"].data_ptr(), out["N"].data_ptr(), ptr(out.get("body")), jo, stream),
+                f"trs_effects{tab}_recover")
+        self.cases_F = F
+        return out
+
     # -- adjoint gradients of the solved cases (include/trs_solver.h "Adjoint gradients") ------------------
     #: the gradients `adjoint_cases` can give, and their shapes' trailing dimensions
     GRADIENTS = ("A", "E", "xyz", "loads")
 
     @property
     def generation(self):
-        """Counts the `factor()`, `solve_cases()` and `modes()` calls of this batch: a forward state is identified by the value
+        """Counts the `factor()`, `solve_cases()`, `solve_effect_cases()` and `modes()` calls of this batch: a forward state is identified by the value
         after its `solve_cases()`, and `adjoint_cases` refuses any other."""
         return getattr(self, "_generation", 0)
 
@@ -2308,6 +2395,120 @@ def solve_load_cases(trusses_or_packed, loads, device=None, reorder=False, optio
         return LoadCaseResult(u, f, N, info)
     torch.cuda.synchronize(dev)
     return LoadCaseResult(u.cpu().numpy(), f.cpu().numpy(), N.cpu().numpy(), info.cpu().numpy())
+
+
+@dataclass
+class EffectCaseResult:
+    """Dense results of `solve_effect_cases`: displace/external/body [B, L, nJ_max, 3], internal [B, L, nM_max], info [B]
+    (as `LoadCaseResult`).  `displace` holds the settlements at the constrained DOFs, `internal` is
+    k c . (u1 - u0) - E A eps0, `external` never contains the self-weight - that is `body`, and over all DOFs of a truss
+    `external + body` sums to zero."""
+    displace: np.ndarray
+    external: np.ndarray
+    internal: np.ndarray
+    body: np.ndarray
+    info: np.ndarray
+
+
+def _check_effect_args(packed, loads, prestrain, settlement, accel, sections):
+    """The argument errors of `solve_effect_cases` that need no device.  Returns (L, arrays): the given arguments as
+    contiguous float64 host arrays, vectors padded to three components."""
+    if sections is not None:
+        raise ValueError("solve_effect_cases: sections= variants cannot be combined with load cases")
+    B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
+    # every argument is [B, L] + inner + last: the dimensions after L, and the allowed sizes of the vector axis (if any)
+    inner = {"loads": (nJ_max,), "prestrain": (nM_max,), "settlement": (nJ_max,), "accel": ()}
+    arrays, L = {}, None
+    for name, x in (("loads", loads), ("prestrain", prestrain), ("settlement", settlement), ("accel", accel)):
+        if x is None:
+            continue
+        if not isinstance(x, np.ndarray) and hasattr(x, "detach"):
+            x = x.detach().cpu().numpy()
+        x = np.asarray(x, dtype=np.float64)
+        vector = name != "prestrain"
+        shape = tuple(x.shape)
+        if vector:
+            ok = len(shape) >= 3 and shape[-1] in (2, 3)
+            shape = shape[:-1]
+        else:
+            ok = True
+        ok = ok and len(shape) == 2 + len(inner[name]) and shape[0] == B and shape[2:] == inner[name]
+        if not ok:
+            tail = "".join(f", {v}" for v in inner[name]) + (", 2 or 3" if vector else "")
+            raise ValueError(f"solve_effect_cases: {name} must be [B={B}, L{tail}], got {tuple(x.shape)}")
+        if L is not None and x.shape[1] != L:
+            raise ValueError(f"solve_effect_cases: {name} has L = {x.shape[1]}, the arguments before it L = {L}")
+        L = int(x.shape[1])
+        if not np.isfinite(x).all():
+            raise ValueError(f"solve_effect_cases: {name} has a non-finite entry")
+        if vector and x.shape[-1] == 2:
+            x = np.concatenate([x, np.zeros(x.shape[:-1] + (1,))], axis=-1)
+        arrays[name] = np.ascontiguousarray(x)
+    if L is None:
+        raise ValueError("solve_effect_cases: give at least one of loads, prestrain, settlement, accel")
+    flat = np.asarray(packed.dim).reshape(-1) == 2
+    if "accel" in arrays and arrays["accel"][flat][..., 2].any():
+        raise ValueError("solve_effect_cases: accel has a z component on a 2D truss")
+    if "settlement" in arrays:
+        ubar = arrays["settlement"]
+        if ubar[flat][..., 2].any():
+            raise ValueError("solve_effect_cases: settlement has a z component on a 2D truss")
+        held = packed.constrained()
+        if (ubar != 0)[np.broadcast_to(~held[:, None], ubar.shape)].any():
+            raise ValueError("solve_effect_cases: settlement is non-zero at a free DOF (a displacement can be "
+                             "prescribed at constrained DOFs only)")
+    return L, arrays
+
+
+def solve_effect_cases(trusses_or_packed, loads=None, prestrain=None, settlement=None, accel=None, device=None,
+                       reorder=False, options=None, max_slab_bytes=64 << 30, on_device=False, sections=None,
+                       use_envelope=True):
+    """`solve_load_cases` for cases that carry support settlements, member pre-strain and self-weight beside (or in
+    place of) joint forces - every truss is still factored ONCE, because all three only change the right-hand side.
+    Per case k of truss b (numpy or torch, caller's joint numbering; any may be None, at least one is given, all agree
+    on L; vectors of a 2D truss may have two components):
+      `loads`      [B, L, nJ_max, dim]  joint forces;
+      `prestrain`  [B, L, nM_max]       member initial strain eps0: alpha * dT for a temperature change, dL / L for a
+                                        member fabricated too long; N = k c . (u1 - u0) - E A eps0;
+      `settlement` [B, L, nJ_max, dim]  prescribed displacements of the CONSTRAINED DOFs (zero elsewhere - a non-zero
+                                        entry at a free DOF is a ValueError);
+      `accel`      [B, L, dim]          body-force vector per unit weight, e.g. (0, 0, -1) for densities that are weight
+                                        densities: a member loads each end joint with half of a * length * density
+                                        times it.
+    Returns an `EffectCaseResult` (host arrays, or torch tensors on the device with `on_device=True`): `displace` shows
+    the settlements at the supports, `external` is the applied load at free DOFs and the support's force at constrained
+    DOFs - never the self-weight, which is `body`.  Buckets, member forms, `reorder` plans, `options` and `use_envelope`
+    as `solve_load_cases`; `sections=` variants, non-finite entries and z components on a 2D truss raise ValueError
+    before any device work."""
+    packed = trusses_or_packed if isinstance(trusses_or_packed, PackedBatch) else pack_trusses(list(trusses_or_packed))
+    L, arrays = _check_effect_args(packed, loads, prestrain, settlement, accel, sections)
+    torch, dev = _require_gpu(device)
+    B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
+    given = {k: torch.from_numpy(v).to(dev) for k, v in arrays.items()}
+    zeros = lambda *shape: torch.zeros(list(shape), dtype=torch.float64, device=dev)
+    u, f, N, body = zeros(B, L, nJ_max, 3), zeros(B, L, nJ_max, 3), zeros(B, L, nM_max), zeros(B, L, nJ_max, 3)
+    info = torch.zeros([B], dtype=torch.int32, device=dev)
+    if B and L:
+        for idx in size_buckets(packed, max_slab_bytes):
+            sub = packed.take(idx).trimmed()
+            rows = torch.from_numpy(np.asarray(idx, dtype=np.int64)).to(dev)
+            db = DeviceBatch(sub, dev, use_envelope=use_envelope, use_small=False, reorder=reorder, options=options)
+            db.factor()
+            cut = {"loads": sub.nJ_max, "prestrain": sub.nM_max, "settlement": sub.nJ_max}
+            part = {k: (v.index_select(0, rows)[:, :, :cut[k]] if k in cut else v.index_select(0, rows)).contiguous()
+                    for k, v in given.items()}
+            res = db.solve_effect_cases(part.get("loads"), part.get("prestrain"), part.get("settlement"),
+                                        part.get("accel"), want_body=True)
+            u[rows, :, :sub.nJ_max] = res["u"]
+            f[rows, :, :sub.nJ_max] = res["f_ext"]
+            N[rows, :, :sub.nM_max] = res["N"]
+            body[rows, :, :sub.nJ_max] = res["body"]
+            info[rows] = db.info
+    if on_device:
+        return EffectCaseResult(u, f, N, body, info)
+    torch.cuda.synchronize(dev)
+    host = lambda x: x.cpu().numpy()
+    return EffectCaseResult(host(u), host(f), host(N), host(body), host(info))
 
 
 @dataclass

@@ -1,0 +1,352 @@
+// Load cases with support settlements, member pre-strain and self-weight (include/trs_effects.h): equivalent joint
+// loads on the way in, a correction of N and of the support forces on the way out - the factor in the slab and
+// trs_potrs_cases (cases.hip) are used as they are.
+//
+//   trs_effects_rhs      loads, eps0 [B][L][nM_max], ubar, accel [B][L][3] -> reduced right-hand sides F [B][L][ld_f]
+//   trs_potrs_cases      K_ff x = f (cases.hip, unchanged)
+//   trs_effects_recover  u (ubar at the constrained DOFs), f_ext, N = k c . D u - E A eps0, body
+//
+// With k = E A / len, c the direction cosines, D. = (.)_j1 - (.)_j0 and g the case's body-force vector:
+//   s_m    = E A eps0_m - k c . D ubar                   member term of the right-hand side
+//   body_j = sum_ends 1/2 (a len density) g              the same vector on every axis' DOF, per axis
+//   rhs_f  = loads_f + body_f + sum_ends (+- s_m c)      free DOFs
+//   f_c    = sum_ends (+- N_m c) - body_c                constrained DOFs; f_f = loads_f
+//
+// One work-group per truss, the shape of trs_adjoint_rhs / trs_recover_cases: the member-end lists of EVERY joint are
+// built in LDS once (integer atomics, then sorted by member id), every joint's sums run over its list in member-id
+// order, and no floating-point atomic is used anywhere.  N and the support sums are formed by the functions of
+// trs_recover.h in trs_recover_cases' order and an effect's term is added only where its pointer is non-null: without
+// effects the bits are those of the plain load cases.
+// build_end_lists is a second copy of adjoint.hip's (that file is left as it is: its kernels' code objects, and so the
+// bits and the timings of the adjoint path, stay what they were); the tables here differ - one DOF vector, not two.
+#include "../../include/trs_effects.h"
+#include "trs_common.h"
+#include "trs_recover.h"
+
+namespace {
+
+using namespace trs_rec;
+
+// LDS tables of one truss (both kernels)
+struct EffTables {
+    double* v;    // [3 nJ_max]  ubar (right-hand side) or u (recovery) of one case, device numbering
+    double* pm;   // [nM_max]    one double per member: s_m or N_m of that case
+    int* cnt;     // [nJ_max]
+    int* start;   // [nJ_max + 1]
+    int* ends;    // [2 nM_max]  (member << 1) | end, per joint, sorted by member id
+};
+
+__device__ __forceinline__ EffTables eff_tables(double* sh, int nJ_max, int nM_max) {
+    EffTables t;
+    t.v = sh;
+    t.pm = sh + 3 * nJ_max;
+    t.cnt = reinterpret_cast<int*>(t.pm + nM_max);
+    t.start = t.cnt + nJ_max;
+    t.ends = t.start + nJ_max + 1;
+    return t;
+}
+
+size_t effects_lds(int nJ_max, int nM_max) {
+    return (((size_t)3 * nJ_max + (size_t)nM_max) * sizeof(double) +
+            ((size_t)2 * nJ_max + 1 + 2 * (size_t)nM_max) * sizeof(int) + 15) / 16 * 16;
+}
+
+// The member-end lists of every joint of truss b, sorted by member id.  Ends with a barrier.
+__device__ __forceinline__ void build_end_lists(const EffTables& t, const TrsMembers& mem, const size_t mbase,
+                                                const int joints, const int members, const int nJ_max,
+                                                const int tid) {
+    for (int j = tid; j < nJ_max; j += 256) t.cnt[j] = 0;
+    __syncthreads();
+    for (int m = tid; m < members; m += 256) {
+        const int2 c = mem.ends(mbase + m);
+        atomicAdd(&t.cnt[c.x], 1);
+        atomicAdd(&t.cnt[c.y], 1);
+    }
+    __syncthreads();
+    if (tid < 64) {  // exclusive scan of cnt by one wave
+        int base = 0;
+        for (int j0 = 0; j0 < joints; j0 += 64) {
+            const int j = j0 + tid;
+            const int v = j < joints ? t.cnt[j] : 0;
+            int incl = v;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const int up = __shfl_up(incl, off);
+                if (tid >= off) incl += up;
+            }
+            if (j < joints) t.start[j] = base + incl - v;
+            base += __shfl(incl, 63);
+        }
+    }
+    __syncthreads();
+    for (int j = tid; j < joints; j += 256) t.cnt[j] = 0;  // the fill cursor
+    __syncthreads();
+    for (int m = tid; m < members; m += 256) {
+        const int2 c = mem.ends(mbase + m);
+        t.ends[t.start[c.x] + atomicAdd(&t.cnt[c.x], 1)] = m << 1;
+        t.ends[t.start[c.y] + atomicAdd(&t.cnt[c.y], 1)] = (m << 1) | 1;
+    }
+    __syncthreads();
+    for (int j = tid; j < joints; j += 256) {
+        int* list = t.ends + t.start[j];
+        const int deg = t.cnt[j];
+        for (int i = 1; i < deg; ++i) {
+            const int key = list[i];
+            int p = i - 1;
+            while (p >= 0 && list[p] > key) {
+                list[p + 1] = list[p];
+                --p;
+            }
+            list[p + 1] = key;
+        }
+    }
+    __syncthreads();
+}
+
+// Half the weight of member mm on one of its end joints, added to the joint's running body load: the product in
+// Member.weight's order (trs_modes_mass forms the same half), ONE function with explicit fused multiply-adds for both
+// kernels - the body load in the right-hand side and the one taken out of the support forces are the same bits.
+__device__ __forceinline__ void add_end_weight(double (&bd)[3], const TrsMembers& mem, const size_t mm, const double len,
+                                               const double* g) {
+    const double half = 0.5 * (mem.area(mm) * len * mem.density(mm));
+#pragma unroll
+    for (int a = 0; a < 3; ++a) bd[a] = fma(half, g[a], bd[a]);
+}
+
+// ---- the reduced right-hand side ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void trs_effects_rhs_kernel(
+    const int L, const double* __restrict__ xyz, const TrsMembers mem, const double* __restrict__ loads,
+    const double* __restrict__ eps0, const double* __restrict__ ubar, const double* __restrict__ accel,
+    const int* __restrict__ free_index, const int* __restrict__ n_free, const int* __restrict__ nJ,
+    const int* __restrict__ nM, const int nJ_max, const int nM_max, const int* __restrict__ joint_in,
+    double* __restrict__ F, const int ld_f) {
+    extern __shared__ double sh[];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int joints = nJ[b], members = nM[b];
+    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
+    const EffTables t = eff_tables(sh, nJ_max, nM_max);
+    double* ub = t.v;   // ubar at the constrained DOFs, zero elsewhere, device numbering
+    double* s = t.pm;   // member term
+    const int* fi = free_index + (size_t)b * ndof_max;
+    const double* X = xyz + (size_t)b * ndof_max;
+    const size_t mbase = (size_t)b * nM_max;
+    const int* ji = joint_in != nullptr ? joint_in + (size_t)b * nJ_max : nullptr;
+    const int n = n_free[b], npad = trs_round_up(n, TRS_NB);
+    const bool member_terms = (eps0 != nullptr) | (ubar != nullptr);
+    const bool lists = member_terms | (accel != nullptr);
+    if (lists) build_end_lists(t, mem, mbase, joints, members, nJ_max, tid);
+    for (int k = 0; k < L; ++k) {
+        const size_t bk = (size_t)b * L + k;
+        const double* lk = loads != nullptr ? loads + bk * ndof_max : nullptr;  // caller's numbering
+        const double* ubk = ubar != nullptr ? ubar + bk * ndof_max : nullptr;
+        const double* ek = eps0 != nullptr ? eps0 + bk * nM_max : nullptr;
+        const double* gk = accel != nullptr ? accel + bk * 3 : nullptr;
+        double* f = F + bk * ld_f;
+        if (member_terms) {
+            __syncthreads();  // (the previous case's readers of ub and s are done)
+            if (ubk != nullptr)
+                for (int d = tid; d < ndof; d += 256) {
+                    const int o = ji != nullptr ? 3 * ji[d / 3] + d % 3 : d;
+                    ub[d] = fi[d] < 0 ? ubk[o] : 0.0;
+                }
+            __syncthreads();
+            for (int m = tid; m < members; m += 256) {
+                const int2 c = mem.ends(mbase + m);
+                const MemberGeom g = member_geom(X, c.x, c.y);
+                const double EA = mem.EA(mbase + m);
+                // - k c . (ubar_j1 - ubar_j0): what the settled supports push into the free DOFs (-K_fc ubar_c)
+                double sm = ubk != nullptr ? -member_axial(g, EA, ub, c.x, c.y) : 0.0;
+                if (ek != nullptr) sm = fma(EA, ek[m], sm);
+                s[m] = sm;
+            }
+            __syncthreads();
+        }
+        for (int j = tid; j < joints; j += 256) {
+            if ((fi[3 * j] < 0) & (fi[3 * j + 1] < 0) & (fi[3 * j + 2] < 0)) continue;  // no free DOF here
+            double r[3] = {0.0, 0.0, 0.0}, bd[3] = {0.0, 0.0, 0.0};
+            if (lists) {
+                const int* list = t.ends + t.start[j];
+                const int deg = t.cnt[j];
+                for (int i = 0; i < deg; ++i) {
+                    const int m = list[i] >> 1, end = list[i] & 1;
+                    const int2 c = mem.ends(mbase + m);
+                    const MemberGeom g = member_geom(X, c.x, c.y);
+                    if (member_terms) add_end_force(r, g.c, s[m], end);
+                    if (gk != nullptr) add_end_weight(bd, mem, mbase + m, g.len, gk);
+                }
+            }
+            const int o = ji != nullptr ? 3 * ji[j] : 3 * j;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const int row = fi[3 * j + a];
+                if (row < 0) continue;
+                double v = lk != nullptr ? lk[o + a] : 0.0;
+                if (gk != nullptr) v += bd[a];
+                if (member_terms) v += r[a];
+                f[row] = v;
+            }
+        }
+        for (int c = n + tid; c < npad; c += 256) f[c] = 0.0;
+    }
+}
+
+// ---- the recovery ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void trs_effects_recover_kernel(
+    const int L, const double* __restrict__ xyz, const TrsMembers mem, const double* __restrict__ loads,
+    const double* __restrict__ eps0, const double* __restrict__ ubar, const double* __restrict__ accel,
+    const int* __restrict__ free_index, const int* __restrict__ nJ, const int* __restrict__ nM, const int nJ_max,
+    const int nM_max, const double* __restrict__ F, const int ld_f, double* __restrict__ u_out,
+    double* __restrict__ f_out, double* __restrict__ N_out, double* __restrict__ body_out,
+    const int* __restrict__ joint_out) {
+    extern __shared__ double sh[];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int joints = nJ[b], members = nM[b];
+    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
+    const EffTables t = eff_tables(sh, nJ_max, nM_max);
+    double* u = t.v;    // displacements of one case, device numbering: solved at the free DOFs, ubar at the others
+    double* Nm = t.pm;  // axial forces of that case
+    const int* fi = free_index + (size_t)b * ndof_max;
+    const double* X = xyz + (size_t)b * ndof_max;
+    const size_t mbase = (size_t)b * nM_max;
+    const int* jo = joint_out != nullptr ? joint_out + (size_t)b * nJ_max : nullptr;
+    build_end_lists(t, mem, mbase, joints, members, nJ_max, tid);
+    for (int k = 0; k < L; ++k) {
+        const size_t bk = (size_t)b * L + k;
+        const double* fk = F + bk * ld_f;
+        const double* lk = loads != nullptr ? loads + bk * ndof_max : nullptr;  // caller's numbering
+        const double* ubk = ubar != nullptr ? ubar + bk * ndof_max : nullptr;
+        const double* ek = eps0 != nullptr ? eps0 + bk * nM_max : nullptr;
+        const double* gk = accel != nullptr ? accel + bk * 3 : nullptr;
+        double* uo = u_out + bk * ndof_max;
+        double* fo = f_out + bk * ndof_max;
+        double* bo = body_out != nullptr ? body_out + bk * ndof_max : nullptr;
+        __syncthreads();  // (the previous case's readers of u and Nm are done)
+        for (int d = tid; d < ndof_max; d += 256) {
+            const int r = d < ndof ? fi[d] : -1;
+            const int o = jo != nullptr ? 3 * jo[d / 3] + d % 3 : d;
+            const double v = r >= 0 ? fk[r] : ((ubk != nullptr && d < ndof) ? ubk[o] : 0.0);
+            u[d] = v;
+            uo[o] = v;
+            if (r >= 0) fo[o] = lk != nullptr ? lk[o] : 0.0;  // free DOF: the applied load
+            else if (d >= ndof) fo[o] = 0.0;                  // padding
+            if (bo != nullptr && d >= ndof) bo[o] = 0.0;
+        }
+        __syncthreads();
+        for (int m = tid; m < nM_max; m += 256) {
+            double axial = 0.0;
+            if (m < members) {
+                const int2 c = mem.ends(mbase + m);
+                const MemberGeom g = member_geom(X, c.x, c.y);
+                const double EA = mem.EA(mbase + m);
+                axial = member_axial(g, EA, u, c.x, c.y);
+                if (ek != nullptr) axial = fma(-EA, ek[m], axial);
+                Nm[m] = axial;
+            }
+            N_out[bk * nM_max + m] = axial;
+        }
+        __syncthreads();
+        for (int j = tid; j < joints; j += 256) {
+            const bool held = (fi[3 * j] < 0) | (fi[3 * j + 1] < 0) | (fi[3 * j + 2] < 0);
+            if (!held && bo == nullptr) continue;  // nothing of this joint is written here
+            double r[3] = {0.0, 0.0, 0.0}, bd[3] = {0.0, 0.0, 0.0};
+            const int* list = t.ends + t.start[j];
+            const int deg = t.cnt[j];
+            for (int i = 0; i < deg; ++i) {
+                const int m = list[i] >> 1, end = list[i] & 1;
+                const int2 c = mem.ends(mbase + m);
+                const MemberGeom g = member_geom(X, c.x, c.y);
+                if (held) add_end_force(r, g.c, Nm[m], end);
+                if (gk != nullptr) add_end_weight(bd, mem, mbase + m, g.len, gk);
+            }
+            const int o = jo != nullptr ? 3 * jo[j] : 3 * j;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                if (fi[3 * j + a] < 0) fo[o + a] = gk != nullptr ? r[a] - bd[a] : r[a];
+                if (bo != nullptr) bo[o + a] = bd[a];
+            }
+        }
+    }
+}
+
+int effects_rhs_launch(int B, int L, int nJ_max, int nM_max, const double* xyz, const TrsMembers& mem,
+                       const double* loads, const double* eps0, const double* ubar, const double* accel,
+                       const int* free_index, const int* n_free, const int* nJ, const int* nM, const int* joint_in,
+                       double* F, int ld_f, hipStream_t stream) {
+    if (B < 0 || L < 0 || nJ_max < 0 || nM_max < 0 || ld_f < 0) return (int)hipErrorInvalidValue;
+    if (B == 0 || L == 0) return 0;
+    if (!trs_effects_fits(nJ_max, nM_max)) return (int)hipErrorInvalidValue;
+    if (accel != nullptr && mem.tidx == nullptr && mem.rho == nullptr) return (int)hipErrorInvalidValue;
+    static const int lds_limit_set = (int)hipFuncSetAttribute(   // once per process, not per launch
+        reinterpret_cast<const void*>(trs_effects_rhs_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)lds_limit_set;
+    hipLaunchKernelGGL(trs_effects_rhs_kernel, dim3(B), dim3(256), effects_lds(nJ_max, nM_max), stream, L, xyz, mem,
+                       loads, eps0, ubar, accel, free_index, n_free, nJ, nM, nJ_max, nM_max, joint_in, F, ld_f);
+    return (int)hipGetLastError();
+}
+
+int effects_recover_launch(int B, int L, int nJ_max, int nM_max, const double* xyz, const TrsMembers& mem,
+                           const double* loads, const double* eps0, const double* ubar, const double* accel,
+                           const int* free_index, const int* nJ, const int* nM, const double* F, int ld_f, double* u,
+                           double* f_ext, double* N, double* body, const int* joint_out, hipStream_t stream) {
+    if (B < 0 || L < 0 || nJ_max < 0 || nM_max < 0 || ld_f < 0) return (int)hipErrorInvalidValue;
+    if (B == 0 || L == 0) return 0;
+    if (!trs_effects_fits(nJ_max, nM_max)) return (int)hipErrorInvalidValue;
+    if (accel != nullptr && mem.tidx == nullptr && mem.rho == nullptr) return (int)hipErrorInvalidValue;
+    static const int lds_limit_set = (int)hipFuncSetAttribute(   // once per process, not per launch
+        reinterpret_cast<const void*>(trs_effects_recover_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+        160 * 1024);
+    (void)lds_limit_set;
+    hipLaunchKernelGGL(trs_effects_recover_kernel, dim3(B), dim3(256), effects_lds(nJ_max, nM_max), stream, L, xyz, mem,
+                       loads, eps0, ubar, accel, free_index, nJ, nM, nJ_max, nM_max, F, ld_f, u, f_ext, N, body,
+                       joint_out);
+    return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+int trs_effects_abi_version(void) { return TRS_EFFECTS_ABI_VERSION; }
+
+int trs_effects_fits(int nJ_max, int nM_max) {
+    return nJ_max >= 0 && nM_max >= 0 && effects_lds(nJ_max, nM_max) <= 160 * 1024;
+}
+
+int trs_effects_rhs(int B, int L, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* E,
+                    const double* A, const double* rho, const double* loads, const double* eps0, const double* ubar,
+                    const double* accel, const int32_t* free_index, const int32_t* n_free, const int32_t* nJ,
+                    const int32_t* nM, const int32_t* joint_in, double* F, int ld_f, void* stream) {
+    return effects_rhs_launch(B, L, nJ_max, nM_max, xyz, trs_members_general(conn, E, A, rho), loads, eps0, ubar, accel,
+                              free_index, n_free, nJ, nM, joint_in, F, ld_f, (hipStream_t)stream);
+}
+
+int trs_effects_tab_rhs(int B, int L, int nJ_max, int nM_max, const double* xyz, const uint16_t* conn16,
+                        const uint8_t* type_idx, const double* types, const double* loads, const double* eps0,
+                        const double* ubar, const double* accel, const int32_t* free_index, const int32_t* n_free,
+                        const int32_t* nJ, const int32_t* nM, const int32_t* joint_in, double* F, int ld_f,
+                        void* stream) {
+    if (B > 0 && (!conn16 || !type_idx || !types)) return (int)hipErrorInvalidValue;
+    return effects_rhs_launch(B, L, nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), loads, eps0, ubar,
+                              accel, free_index, n_free, nJ, nM, joint_in, F, ld_f, (hipStream_t)stream);
+}
+
+int trs_effects_recover(int B, int L, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* E,
+                        const double* A, const double* rho, const double* loads, const double* eps0, const double* ubar,
+                        const double* accel, const int32_t* free_index, const int32_t* nJ, const int32_t* nM,
+                        const double* F, int ld_f, double* u, double* f_ext, double* N, double* body,
+                        const int32_t* joint_out, void* stream) {
+    return effects_recover_launch(B, L, nJ_max, nM_max, xyz, trs_members_general(conn, E, A, rho), loads, eps0, ubar,
+                                  accel, free_index, nJ, nM, F, ld_f, u, f_ext, N, body, joint_out, (hipStream_t)stream);
+}
+
+int trs_effects_tab_recover(int B, int L, int nJ_max, int nM_max, const double* xyz, const uint16_t* conn16,
+                            const uint8_t* type_idx, const double* types, const double* loads, const double* eps0,
+                            const double* ubar, const double* accel, const int32_t* free_index, const int32_t* nJ,
+                            const int32_t* nM, const double* F, int ld_f, double* u, double* f_ext, double* N,
+                            double* body, const int32_t* joint_out, void* stream) {
+    if (B > 0 && (!conn16 || !type_idx || !types)) return (int)hipErrorInvalidValue;
+    return effects_recover_launch(B, L, nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), loads, eps0, ubar,
+                                  accel, free_index, nJ, nM, F, ld_f, u, f_ext, N, body, joint_out, (hipStream_t)stream);
+}
+
+}  // extern "C"

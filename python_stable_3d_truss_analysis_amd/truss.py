@@ -380,6 +380,42 @@ class Truss:
             t.AdoptDenseResults(result.displace[0, k], result.external[0, k], result.internal[0, k])
         return copies
 
+    def SolveEffectCases(self, cases):
+        """Solve this truss under several `LoadCase`s - joint forces, support settlements, member pre-strains
+        (temperature, lack of fit) and self-weight, in any mix - with ONE factorisation of its stiffness matrix: all of
+        them change the right-hand side only (`batch.solve_effect_cases`).  Returns one solved copy of the truss per
+        case, carrying that case's forces and results: `GetDisplacements` shows the settlements at the supports,
+        `GetInternalForces` is k c . (u1 - u0) - E A eps0, and `GetExternalForces` / `GetResistances` hold what the
+        supports and the applied forces supply - the self-weight is in neither (it is `copy.bodyForces`,
+        {jointID: vector}).  This truss stays as it is.  Raises `TrussNotStableError` before any arithmetic when the
+        counting test fails, ValueError for a settlement along a free axis, and `numpy.linalg.LinAlgError` when the
+        reduced stiffness matrix is not positive definite."""
+        if not self.isStable:
+            raise TrussNotStableError("The truss is not stable !")
+        from .batch import pack_trusses, solve_effect_cases  # late import: keeps the model importable without torch
+        cases = list(cases)
+        if not cases:
+            return []
+        nJ, nM, dim = len(self._pos), len(self._bars), self._dim
+        dense = pack_load_cases(cases, nJ, nM, dim)
+        if dense["loads"] is None:
+            dense["loads"] = np.zeros([1, len(cases), nJ, 3])
+        copies = []
+        for case in cases:
+            t = Truss(dim).LoadFromJSON(data=self.Serialize())
+            t._loads = {}
+            for jointID, vector in case.forces.items():
+                t.AddExternalForce(jointID, vector)
+            copies.append(t)
+        result = solve_effect_cases(pack_trusses([self]), **dense)
+        if int(result.info[0]) != 0:
+            raise np.linalg.LinAlgError("Singular matrix")
+        for k, t in enumerate(copies):
+            t.AdoptDenseResults(result.displace[0, k], result.external[0, k], result.internal[0, k])
+            body = result.body[0, k, :nJ, :dim]
+            t.bodyForces = {j: body[j].copy() for j in np.flatnonzero((np.abs(body) >= ZERO_EPS).any(axis=1)).tolist()}
+        return copies
+
     def NaturalFrequencies(self, nModes=6, jointMasses=None, massScale=1.0, returnShapes=False):
         """The `nModes` (1 .. 8) lowest natural circular frequencies omega of this truss, ascending, with a lumped mass
         matrix: every member gives half of `a * length * density` (times `massScale`: 1 / g for weight densities) to
@@ -493,6 +529,69 @@ class Truss:
             raise TrussNotSolvedError("Haven't done structural analysis yet.")
         lengths = ((j, GetLength(d)) for j, d in self._displace.items())
         return self._excess(lengths, limit, isGetSumViolation, isGetSumNonViolation)
+
+
+class LoadCase:
+    """One load case of `Truss.SolveEffectCases`: what acts on the structure beside (or in place of) joint forces.
+
+    `forces`      {jointID: vector}   joint forces, as `AddExternalForce` takes them;
+    `settlements` {jointID: vector}   prescribed displacements of a SUPPORTED joint - the components along its free
+                                      axes must be zero;
+    `prestrains`  {memberID: eps0}    member initial strain: alpha * dT for a temperature change, dL / L for a member
+                                      fabricated too long (positive: the member wants to be longer);
+    `gravity`     vector or None      body-force vector per unit weight: every member loads each of its end joints with
+                                      half of a * length * density times it, e.g. (0, 0, -1) for weight densities."""
+
+    def __init__(self, forces=None, settlements=None, prestrains=None, gravity=None):
+        self.forces = dict(forces or {})
+        self.settlements = dict(settlements or {})
+        self.prestrains = dict(prestrains or {})
+        self.gravity = None if gravity is None else tuple(float(x) for x in gravity)
+
+    def __repr__(self):
+        return (f"LoadCase(forces={self.forces!r}, settlements={self.settlements!r}, prestrains={self.prestrains!r}, "
+                f"gravity={self.gravity!r})")
+
+
+def pack_load_cases(cases, nJoint, nMember, dim):
+    """A list of `LoadCase` as the dense arrays of `batch.solve_effect_cases` for ONE truss: a dict with `loads`,
+    `settlement` [1, L, nJoint, 3], `prestrain` [1, L, nMember] and `accel` [1, L, 3]; an effect that no case carries is
+    None (the cases that lack one the others carry get zeros).  Raises `InvaildJointError` / KeyError for an id the
+    truss does not have and `DimensionError` for a vector that is not `dim` long."""
+    cases = list(cases)
+    L = len(cases)
+
+    def vector(v):
+        if len(v) != dim:
+            raise DimensionError(f"Dimension of each vector of a load case must be {dim}, but got {len(v)}.")
+        return [float(x) for x in v]
+
+    def joints(field):
+        if not any(getattr(c, field) for c in cases):
+            return None
+        out = np.zeros([1, L, nJoint, 3])
+        for k, c in enumerate(cases):
+            for jointID, v in getattr(c, field).items():
+                if not (isinstance(jointID, (int, np.integer)) and 0 <= jointID < nJoint):
+                    raise InvaildJointError(f"No such joint [{jointID}] in load case {k}.")
+                out[0, k, jointID, :dim] = vector(v)
+        return out
+
+    prestrain = None
+    if any(c.prestrains for c in cases):
+        prestrain = np.zeros([1, L, nMember])
+        for k, c in enumerate(cases):
+            for memberID, eps0 in c.prestrains.items():
+                if not (isinstance(memberID, (int, np.integer)) and 0 <= memberID < nMember):
+                    raise KeyError(f"No such member [{memberID}] in load case {k}.")
+                prestrain[0, k, memberID] = float(eps0)
+    accel = None
+    if any(c.gravity is not None for c in cases):
+        accel = np.zeros([1, L, 3])
+        for k, c in enumerate(cases):
+            if c.gravity is not None:
+                accel[0, k, :dim] = vector(c.gravity)
+    return {"loads": joints("forces"), "settlement": joints("settlements"), "prestrain": prestrain, "accel": accel}
 
 
 def load_cases_from_json(paths):
