@@ -449,6 +449,11 @@ def joint_order_device(torch, tensors, effort=2, apply=True, want_choice=False, 
     return out
 
 
+def _ptr(x):
+    """The device address of an optional tensor argument of a C call."""
+    return None if x is None else x.data_ptr()
+
+
 class DeviceBatch:
     """A packed batch resident in HBM plus the workspace of the pipeline.
 
@@ -780,45 +785,76 @@ class DeviceBatch:
         self._factored = True
         self._bump_generation()
 
+    # what the analyses on the resident factor share (solve_cases, solve_effect_cases, adjoint_cases, modes)
+    def _need_factor(self, what):
+        if not getattr(self, "_factored", False):
+            raise ValueError(f"{what}(): no factor - call factor() first")
+
+    def _out_tensors(self, what, shapes, out):
+        """The result dict of `what`: exactly the keys of `shapes` (key -> shape for float64, or (shape, dtype)), taken
+        from `out` where it has them - they must be contiguous device tensors of that shape and type - and allocated
+        (into `out` too, if one was given) where it has not."""
+        t = self.torch
+        out = {} if out is None else out
+        for k, spec in shapes.items():
+            shape, dtype = spec if isinstance(spec, tuple) else (spec, t.float64)
+            if k not in out:
+                out[k] = t.zeros(shape, dtype=dtype, device=self.device)
+            elif list(out[k].shape) != shape or out[k].dtype != dtype or out[k].device != self.device \
+                    or not out[k].is_contiguous():
+                raise ValueError(f"{what}(): out[{k!r}] must be a contiguous {'float64' if spec is shape else dtype} "
+                                 f"{shape} tensor on {self.device}")
+        return {k: out[k] for k in shapes}
+
+    def _case_block(self, attr, L):
+        """The buffer `attr` (cases_F, cases_Lam) if it holds L cases, else a new one: right-hand sides and solutions,
+        case-major [B][L][ld_f], ld_f = self.rows.  The caller keeps it in `attr`."""
+        X = getattr(self, attr, None)
+        if X is None or int(X.shape[1]) != L:
+            X = self.torch.empty([self.B, L, self.rows], dtype=self.torch.float64, device=self.device)
+        return X
+
+    def _case_launch(self):
+        """What every launch of these methods is given: joint_out's pointer (or None), the current stream, and the infix
+        of the entry points of this batch's member form."""
+        return _ptr(self.joint_out), self._stream(), "_tab" if self.table else ""
+
+    def _potrs_cases(self, X, L):
+        """L y = f, U x = y for the L columns of X against the resident factor, in place."""
+        _capi.check(self.lib.trs_potrs_cases(self.B, L, self.n_free.data_ptr(), self.ld, self.rows, self.S.data_ptr(),
+                                             X.data_ptr(), self.rows, self._env_ptr(), self._stream()), "trs_potrs_cases")
+
     def solve_cases(self, loads, out=None):
         """Gather, multi-case substitution and recovery on the resident factor (`factor()` first).  `loads`: float64
         device tensor [B, L, nJ_max, 3] in the CALLER's joint numbering (a joint order applied to the batch is undone
         on the device).  Returns a dict of device tensors u, f_ext [B, L, nJ_max, 3] and N [B, L, nM_max] (`out`: such
-        a dict to write into); `self.info` holds the factorisation's status per truss."""
+        a dict to write into - its tensors are checked as the other analyses check theirs, and the dict returned holds
+        exactly u, f_ext and N, not the caller's dict object); `self.info` holds the factorisation's status per truss."""
         t = self.torch
-        if not getattr(self, "_factored", False):
-            raise ValueError("solve_cases(): no factor - call factor() first")
+        self._need_factor("solve_cases")
         if loads.dim() != 4 or tuple(loads.shape[:1]) + tuple(loads.shape[2:]) != (self.B, self.nJ_max, 3) \
                 or loads.dtype != t.float64 or loads.device != self.device:
             raise ValueError(f"solve_cases(): loads must be float64 [B={self.B}, L, nJ_max={self.nJ_max}, 3] on {self.device}")
         loads = loads.contiguous()
         L = int(loads.shape[1])
-        if out is None:
-            out = {"u": t.zeros([self.B, L, self.nJ_max, 3], dtype=t.float64, device=self.device),
-                   "f_ext": t.zeros([self.B, L, self.nJ_max, 3], dtype=t.float64, device=self.device),
-                   "N": t.zeros([self.B, L, self.nM_max], dtype=t.float64, device=self.device)}
+        out = self._out_tensors("solve_cases", {"u": [self.B, L, self.nJ_max, 3], "f_ext": [self.B, L, self.nJ_max, 3],
+                                                "N": [self.B, L, self.nM_max]}, out)
         if self.B == 0 or L == 0:
             return out
         if not self.lib.trs_recover_cases_fits(self.nJ_max, self.nM_max):
             raise HipExtensionError(f"solve_cases(): a truss of {self.nJ_max} joints / {self.nM_max} members exceeds the "
                                     "LDS of the multi-case recovery (trs_recover_cases_fits)")
-        F = getattr(self, "cases_F", None)   # right-hand sides, case-major [B][L][ld_f], ld_f = self.rows
-        if F is None or int(F.shape[1]) != L:
-            F = t.empty([self.B, L, self.rows], dtype=t.float64, device=self.device)
-        jo = self.joint_out.data_ptr() if self.joint_out is not None else None
-        stream = self._stream()
+        F = self._case_block("cases_F", L)
+        jo, stream, tab = self._case_launch()
         with t.cuda.device(self.device):
             _capi.check(self.lib.trs_gather_cases(self.B, L, self.nJ_max, loads.data_ptr(), self.free_index.data_ptr(),
                                                   self.n_free.data_ptr(), self.nJ.data_ptr(), jo, F.data_ptr(),
                                                   self.rows, stream), "trs_gather_cases")
-            _capi.check(self.lib.trs_potrs_cases(self.B, L, self.n_free.data_ptr(), self.ld, self.rows,
-                                                 self.S.data_ptr(), F.data_ptr(), self.rows, self._env_ptr(), stream),
-                        "trs_potrs_cases")
-            fn, what = (self.lib.trs_recover_tab_cases, "trs_recover_tab_cases") if self.table \
-                else (self.lib.trs_recover_cases, "trs_recover_cases")
-            _capi.check(fn(self.B, L, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *self._members(), loads.data_ptr(),
-                           self.free_index.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), F.data_ptr(), self.rows,
-                           out["u"].data_ptr(), out["f_ext"].data_ptr(), out["N"].data_ptr(), jo, stream), what)
+            self._potrs_cases(F, L)
+            _capi.check(getattr(self.lib, f"trs_recover{tab}_cases")(
+                self.B, L, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *self._members(), loads.data_ptr(),
+                self.free_index.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), F.data_ptr(), self.rows,
+                out["u"].data_ptr(), out["f_ext"].data_ptr(), out["N"].data_ptr(), jo, stream), f"trs_recover{tab}_cases")
         self.cases_F = F   # (kept: the reduced displacements of the last call, and the buffer of the next)
         self._bump_generation()
         self._forward = (self.generation, L)   # what `adjoint_cases` may differentiate
@@ -840,8 +876,7 @@ class DeviceBatch:
         `generation` is bumped and the forward state of `adjoint_cases` is dropped: the equivalent loads depend on A, E
         and xyz, which the adjoint of `solve_cases` does not know, so gradients of these cases are refused."""
         t = self.torch
-        if not getattr(self, "_factored", False):
-            raise ValueError("solve_effect_cases(): no factor - call factor() first")
+        self._need_factor("solve_effect_cases")
         given = {"loads": loads, "prestrain": prestrain, "settlement": settlement, "accel": accel}
         tails = {"loads": (self.nJ_max, 3), "prestrain": (self.nM_max,), "settlement": (self.nJ_max, 3), "accel": (3,)}
         names = {"loads": "nJ_max, 3", "prestrain": "nM_max", "settlement": "nJ_max, 3", "accel": "3"}
@@ -863,30 +898,16 @@ class DeviceBatch:
         shapes = {"u": [self.B, L, self.nJ_max, 3], "f_ext": [self.B, L, self.nJ_max, 3], "N": [self.B, L, self.nM_max]}
         if want_body:
             shapes["body"] = [self.B, L, self.nJ_max, 3]
-        if out is None:
-            out = {}
-        for k, shape in shapes.items():
-            if k not in out:
-                out[k] = t.zeros(shape, dtype=t.float64, device=self.device)
-            elif list(out[k].shape) != shape or out[k].dtype != t.float64 or out[k].device != self.device \
-                    or not out[k].is_contiguous():
-                raise ValueError(f"solve_effect_cases(): out[{k!r}] must be a contiguous float64 {shape} tensor on "
-                                 f"{self.device}")
-        out = {k: out[k] for k in shapes}
+        out = self._out_tensors("solve_effect_cases", shapes, out)
         if self.B == 0 or L == 0:
             return out
         if not self.lib.trs_effects_fits(self.nJ_max, self.nM_max):
             raise HipExtensionError(f"solve_effect_cases(): a truss of {self.nJ_max} joints / {self.nM_max} members "
                                     "exceeds the LDS of the effect kernels (trs_effects_fits)")
-        F = getattr(self, "cases_F", None)   # right-hand sides, case-major [B][L][ld_f], ld_f = self.rows
-        if F is None or int(F.shape[1]) != L:
-            F = t.empty([self.B, L, self.rows], dtype=t.float64, device=self.device)
-        ptr = lambda x: None if x is None else x.data_ptr()
-        jo = ptr(self.joint_out)
-        stream = self._stream()
-        tab = "_tab" if self.table else ""
-        members = self._members() if self.table else self._members() + (ptr(self.rho),)
-        effects = tuple(ptr(given[k]) for k in ("loads", "prestrain", "settlement", "accel"))
+        F = self._case_block("cases_F", L)
+        jo, stream, tab = self._case_launch()
+        members = self._members() if self.table else self._members() + (_ptr(self.rho),)
+        effects = tuple(_ptr(given[k]) for k in ("loads", "prestrain", "settlement", "accel"))
         self._forward = None                 # (F is about to be overwritten; see the docstring)
         self._bump_generation()
         with t.cuda.device(self.device):
@@ -894,13 +915,11 @@ class DeviceBatch:
                 self.B, L, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *members, *effects,
                 self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), jo,
                 F.data_ptr(), self.rows, stream), f"trs_effects{tab}_rhs")
-            _capi.check(self.lib.trs_potrs_cases(self.B, L, self.n_free.data_ptr(), self.ld, self.rows,
-                                                 self.S.data_ptr(), F.data_ptr(), self.rows, self._env_ptr(), stream),
-                        "trs_potrs_cases")
+            self._potrs_cases(F, L)
             _capi.check(getattr(self.lib, f"trs_effects{tab}_recover")(
                 self.B, L, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *members, *effects,
                 self.free_index.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), F.data_ptr(), self.rows,
-                out["u"].data_ptr(), out["f_ext"].data_ptr(), out["N"].data_ptr(), ptr(out.get("body")), jo, stream),
+                out["u"].data_ptr(), out["f_ext"].data_ptr(), out["N"].data_ptr(), _ptr(out.get("body")), jo, stream),
                 f"trs_effects{tab}_recover")
         self.cases_F = F
         return out
@@ -955,43 +974,27 @@ class DeviceBatch:
                 raise ValueError(f"adjoint_cases(): {name} must be float64 {list(shapes[name])} on {self.device} "
                                  f"(the last solve_cases() had L = {L}), got {g.dtype} {list(g.shape)} on {g.device}")
             cot[name] = g.contiguous()
-        if out is None:
-            out = {}
-        for k in want:
-            if k not in out:
-                out[k] = t.zeros(self._gradient_shape(k, L), dtype=t.float64, device=self.device)
-            elif list(out[k].shape) != self._gradient_shape(k, L) or out[k].dtype != t.float64 \
-                    or out[k].device != self.device or not out[k].is_contiguous():
-                raise ValueError(f"adjoint_cases(): out[{k!r}] must be a contiguous float64 "
-                                 f"{self._gradient_shape(k, L)} tensor on {self.device}")
+        out = self._out_tensors("adjoint_cases", {k: self._gradient_shape(k, L) for k in want}, out)
         if self.B == 0 or L == 0:
-            return {k: out[k] for k in want}
+            return out
         if not self.lib.trs_adjoint_fits(self.nJ_max, self.nM_max):
             raise HipExtensionError(f"adjoint_cases(): a truss of {self.nJ_max} joints / {self.nM_max} members exceeds "
                                     "the LDS of the adjoint kernels (trs_adjoint_fits)")
-        Lam = getattr(self, "cases_Lam", None)   # the adjoint systems: a buffer of their own, the forward F survives
-        if Lam is None or int(Lam.shape[1]) != L:
-            Lam = t.empty([self.B, L, self.rows], dtype=t.float64, device=self.device)
-        ptr = lambda x: None if x is None else x.data_ptr()
-        jo = ptr(self.joint_out)
-        stream = self._stream()
-        tab = "_tab" if self.table else ""
+        Lam = self._case_block("cases_Lam", L)   # the adjoint systems: a buffer of their own, the forward F survives
+        jo, stream, tab = self._case_launch()
         with t.cuda.device(self.device):
             _capi.check(getattr(self.lib, f"trs_adjoint{tab}_rhs")(
-                self.B, L, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *self._members(), ptr(cot["grad_u"]),
-                ptr(cot["grad_f_ext"]), ptr(cot["grad_N"]), self.free_index.data_ptr(), self.n_free.data_ptr(),
+                self.B, L, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *self._members(), _ptr(cot["grad_u"]),
+                _ptr(cot["grad_f_ext"]), _ptr(cot["grad_N"]), self.free_index.data_ptr(), self.n_free.data_ptr(),
                 self.nJ.data_ptr(), self.nM.data_ptr(), jo, Lam.data_ptr(), self.rows, stream), f"trs_adjoint{tab}_rhs")
-            _capi.check(self.lib.trs_potrs_cases(self.B, L, self.n_free.data_ptr(), self.ld, self.rows,
-                                                 self.S.data_ptr(), Lam.data_ptr(), self.rows, self._env_ptr(), stream),
-                        "trs_potrs_cases")
+            self._potrs_cases(Lam, L)
             _capi.check(getattr(self.lib, f"trs_adjoint{tab}_grad")(
-                self.B, L, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *self._members(), ptr(cot["grad_f_ext"]),
-                ptr(cot["grad_N"]), self.free_index.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(),
-                self.cases_F.data_ptr(), Lam.data_ptr(), self.rows, ptr(out.get("A") if "A" in want else None),
-                ptr(out.get("E") if "E" in want else None), ptr(out.get("xyz") if "xyz" in want else None),
-                ptr(out.get("loads") if "loads" in want else None), jo, stream), f"trs_adjoint{tab}_grad")
+                self.B, L, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *self._members(), _ptr(cot["grad_f_ext"]),
+                _ptr(cot["grad_N"]), self.free_index.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(),
+                self.cases_F.data_ptr(), Lam.data_ptr(), self.rows, _ptr(out.get("A")), _ptr(out.get("E")),
+                _ptr(out.get("xyz")), _ptr(out.get("loads")), jo, stream), f"trs_adjoint{tab}_grad")
         self.cases_Lam = Lam
-        return {k: out[k] for k in want}
+        return out
 
     # -- natural frequencies and mode shapes from the resident factor (include/trs_modes.h) ------------------
     def modes(self, p, tol=1e-10, max_iters=256, check_every=8, joint_mass=None, mass_scale=1.0, out=None):
@@ -1007,8 +1010,7 @@ class DeviceBatch:
         The block shares the buffer of `solve_cases`' right-hand sides, so a forward solution kept for
         `adjoint_cases` is invalidated (`generation` is bumped); the factor is only read."""
         t = self.torch
-        if not getattr(self, "_factored", False):
-            raise ValueError("modes(): no factor - call factor() first")
+        self._need_factor("modes")
         _check_mode_args(self.B, self.nJ_max, p, None if joint_mass is None else tuple(joint_mass.shape), mass_scale, tol,
                          max_iters, check_every)
         p, max_iters, check_every = int(p), int(max_iters), int(check_every)
@@ -1018,25 +1020,14 @@ class DeviceBatch:
             joint_mass = joint_mass.contiguous()
         shapes = {"lam": ([self.B, p], t.float64), "phi": ([self.B, p, self.nJ_max, 3], t.float64),
                   "resid": ([self.B, p], t.float64), "n_modes": ([self.B], t.int32), "iters": ([self.B], t.int32)}
-        if out is None:
-            out = {}
-        for k, (shape, dtype) in shapes.items():
-            if k not in out:
-                out[k] = t.zeros(shape, dtype=dtype, device=self.device)
-            elif list(out[k].shape) != shape or out[k].dtype != dtype or out[k].device != self.device \
-                    or not out[k].is_contiguous():
-                raise ValueError(f"modes(): out[{k!r}] must be a contiguous {dtype} {shape} tensor on {self.device}")
-        out = {k: out[k] for k in shapes}
+        out = self._out_tensors("modes", shapes, out)
         if self.B == 0:
             return out
         if not self.lib.trs_modes_fits(self.nJ_max, self.nM_max):
             raise HipExtensionError(f"modes(): a truss of {self.nJ_max} joints / {self.nM_max} members exceeds the LDS "
                                     "of the mass kernel (trs_modes_fits)")
         Q = MODES_BLOCK
-        F = getattr(self, "cases_F", None)   # the block's right-hand sides / solutions: the load cases' buffer
-        if F is None or int(F.shape[1]) != Q:
-            F = t.empty([self.B, Q, self.rows], dtype=t.float64, device=self.device)
-        self.cases_F = F
+        F = self.cases_F = self._case_block("cases_F", Q)   # the block's right-hand sides / solutions
         self._bump_generation()              # (whatever `solve_cases` left there is gone: `adjoint_cases` refuses it)
         ws = getattr(self, "_modes_ws", None)
         if ws is None:
@@ -1044,15 +1035,8 @@ class DeviceBatch:
             i32 = lambda *shape: t.empty(list(shape), dtype=t.int32, device=self.device)
             ws = self._modes_ws = {"X": f64(self.B, Q, self.rows), "Mf": f64(self.B, self.rows), "lam": f64(self.B, Q),
                                    "resid": f64(self.B, Q), "n_mass": i32(self.B), "state": i32(self.B)}
-        ptr = lambda x: None if x is None else x.data_ptr()
-        jo = ptr(self.joint_out)
-        stream = self._stream()
-        if self.table:
-            mass_fn, what = self.lib.trs_modes_tab_mass, "trs_modes_tab_mass"
-            members = (self.conn.data_ptr(), self.type_idx.data_ptr(), self.types.data_ptr())
-        else:
-            mass_fn, what = self.lib.trs_modes_mass, "trs_modes_mass"
-            members = (self.conn.data_ptr(), self.A.data_ptr(), self.rho.data_ptr())
+        jo, stream, tab = self._case_launch()
+        members = self._members() if self.table else (self.conn.data_ptr(), self.A.data_ptr(), self.rho.data_ptr())
 
         def step(first, check, it):
             _capi.check(self.lib.trs_modes_step(
@@ -1061,16 +1045,15 @@ class DeviceBatch:
                 first, check, it, float(tol), stream), "trs_modes_step")
 
         with t.cuda.device(self.device):
-            _capi.check(mass_fn(self.B, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *members, ptr(joint_mass), jo,
-                                float(mass_scale), self.free_index.data_ptr(), self.n_free.data_ptr(),
-                                self.nJ.data_ptr(), self.nM.data_ptr(), ws["Mf"].data_ptr(), self.rows,
-                                ws["n_mass"].data_ptr(), stream), what)
+            _capi.check(getattr(self.lib, f"trs_modes{tab}_mass")(
+                self.B, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *members, _ptr(joint_mass), jo,
+                float(mass_scale), self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(),
+                self.nM.data_ptr(), ws["Mf"].data_ptr(), self.rows, ws["n_mass"].data_ptr(), stream),
+                f"trs_modes{tab}_mass")
             step(1, 0, 0)
             for it in range(1, max_iters + 1):
                 check = it % check_every == 0 or it == max_iters
-                _capi.check(self.lib.trs_potrs_cases(self.B, Q, self.n_free.data_ptr(), self.ld, self.rows,
-                                                     self.S.data_ptr(), F.data_ptr(), self.rows, self._env_ptr(), stream),
-                            "trs_potrs_cases")
+                self._potrs_cases(F, Q)
                 step(0, int(check), it)
                 if check and not bool((ws["state"] == 0).any().item()):   # the one read-back per check point
                     break
@@ -2341,6 +2324,74 @@ def solve_batch_streamed(packed: PackedBatch, device=None, reorder=True, pool=No
     return solver.result()
 
 
+def _as_packed(trusses_or_packed):
+    return trusses_or_packed if isinstance(trusses_or_packed, PackedBatch) else pack_trusses(list(trusses_or_packed))
+
+
+def _device_f64(torch, dev, x, vectors=False):
+    """An array argument (numpy or torch; None stays None) as a contiguous float64 tensor on `dev`; `vectors`: the last
+    axis holds 2 or 3 components, and two get z = 0."""
+    if x is None:
+        return None
+    if isinstance(x, np.ndarray):
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))
+    x = x.to(device=dev, dtype=torch.float64)
+    if vectors and int(x.shape[-1]) == 2:
+        x = torch.nn.functional.pad(x, (0, 1))
+    return x.contiguous()
+
+
+def _host_result(torch, dev, res):
+    """A result dataclass of device tensors as the same dataclass of numpy arrays."""
+    torch.cuda.synchronize(dev)
+    return type(res)(**{k: v.cpu().numpy() for k, v in vars(res).items()})
+
+
+class _Bucket:
+    """One size bucket of `_factored_buckets`: `rows`, its trusses' places in the full batch, and the bucket's own padded
+    sizes.  `cut` and `put` name the axis that runs over joints (`nJ=`) or members (`nM=`), if the tensor has one."""
+
+    def __init__(self, rows, nJ_max, nM_max):
+        self.rows, self.nJ_max, self.nM_max = rows, nJ_max, nM_max
+
+    def cut(self, x, nJ=None, nM=None):
+        """The bucket's part of a full-batch device tensor, contiguous (None stays None)."""
+        if x is None:
+            return None
+        x = x.index_select(0, self.rows)
+        if nJ is not None:
+            x = x.narrow(nJ, 0, self.nJ_max)
+        if nM is not None:
+            x = x.narrow(nM, 0, self.nM_max)
+        return x.contiguous()
+
+    def put(self, dst, src, nJ=None, nM=None):
+        """Write a result of the bucket into the full-batch tensor `dst`."""
+        index = [self.rows] + [slice(None)] * (src.dim() - 1)
+        if nJ is not None:
+            index[nJ] = slice(0, self.nJ_max)
+        if nM is not None:
+            index[nM] = slice(0, self.nM_max)
+        dst[tuple(index)] = src
+
+
+def _factored_buckets(packed, dev, info, max_slab_bytes, reorder, options, use_envelope, cases=1):
+    """The loop that the analyses on a resident factor share: per size bucket (`size_buckets`) the trusses are uploaded,
+    ordered and factored on the staged pipeline, and (DeviceBatch, _Bucket) is yielded for the analysis; afterwards the
+    factorisation's status goes to the bucket's rows of `info`.  Nothing is factored for an empty batch or for
+    `cases` = 0 load cases."""
+    import torch
+    if not packed.B or not cases:
+        return
+    for idx in size_buckets(packed, max_slab_bytes):
+        sub = packed.take(idx).trimmed()
+        part = _Bucket(torch.from_numpy(np.asarray(idx, dtype=np.int64)).to(dev), sub.nJ_max, sub.nM_max)
+        db = DeviceBatch(sub, dev, use_envelope=use_envelope, use_small=False, reorder=reorder, options=options)
+        db.factor()
+        yield db, part
+        info[part.rows] = db.info
+
+
 @dataclass
 class LoadCaseResult:
     """Dense host results of `solve_load_cases`: displace/external [B, L, nJ_max, 3], internal [B, L, nM_max],
@@ -2350,6 +2401,24 @@ class LoadCaseResult:
     external: np.ndarray
     internal: np.ndarray
     info: np.ndarray
+
+
+def _load_cases_on_device(torch, dev, packed, loads, max_slab_bytes, reorder, options, use_envelope, after=None):
+    """The forward pass of `solve_load_cases` and `solve_gradients`: `loads` float64 [B, L, nJ_max, 3] on `dev`, the
+    buckets as `_factored_buckets` makes them; `after(db, part, res)` runs per bucket on the solved cases.  Returns a
+    `LoadCaseResult` of device tensors."""
+    B, L, nJ_max, nM_max = packed.B, int(loads.shape[1]), packed.nJ_max, packed.nM_max
+    zeros = lambda *shape: torch.zeros(list(shape), dtype=torch.float64, device=dev)
+    out = LoadCaseResult(zeros(B, L, nJ_max, 3), zeros(B, L, nJ_max, 3), zeros(B, L, nM_max),
+                         torch.zeros([B], dtype=torch.int32, device=dev))
+    for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope, cases=L):
+        res = db.solve_cases(part.cut(loads, nJ=2))
+        part.put(out.displace, res["u"], nJ=2)
+        part.put(out.external, res["f_ext"], nJ=2)
+        part.put(out.internal, res["N"], nM=2)
+        if after is not None:
+            after(db, part, res)
+    return out
 
 
 def solve_load_cases(trusses_or_packed, loads, device=None, reorder=False, options=None, max_slab_bytes=64 << 30,
@@ -2364,37 +2433,15 @@ def solve_load_cases(trusses_or_packed, loads, device=None, reorder=False, optio
     are not combined with load cases (ValueError).  `use_envelope=False`: the dense mode (`DeviceBatch`)."""
     if sections is not None:
         raise ValueError("solve_load_cases: sections= variants cannot be combined with load cases")
-    packed = trusses_or_packed if isinstance(trusses_or_packed, PackedBatch) else pack_trusses(list(trusses_or_packed))
+    packed = _as_packed(trusses_or_packed)
     torch, dev = _require_gpu(device)
-    B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
-    if isinstance(loads, np.ndarray):
-        loads = torch.from_numpy(np.ascontiguousarray(loads, dtype=np.float64))
-    if loads.dim() != 4 or int(loads.shape[0]) != B or int(loads.shape[2]) != nJ_max or int(loads.shape[3]) not in (2, 3):
-        raise ValueError(f"solve_load_cases: loads must be [B={B}, L, nJ_max={nJ_max}, 2 or 3], got {tuple(loads.shape)}")
-    L = int(loads.shape[1])
-    loads = loads.to(device=dev, dtype=torch.float64)
-    if int(loads.shape[3]) == 2:
-        loads = torch.nn.functional.pad(loads, (0, 1))
-    loads = loads.contiguous()
-    u = torch.zeros([B, L, nJ_max, 3], dtype=torch.float64, device=dev)
-    f = torch.zeros([B, L, nJ_max, 3], dtype=torch.float64, device=dev)
-    N = torch.zeros([B, L, nM_max], dtype=torch.float64, device=dev)
-    info = torch.zeros([B], dtype=torch.int32, device=dev)
-    if B and L:
-        for idx in size_buckets(packed, max_slab_bytes):
-            sub = packed.take(idx).trimmed()
-            rows = torch.from_numpy(np.asarray(idx, dtype=np.int64)).to(dev)
-            db = DeviceBatch(sub, dev, use_envelope=use_envelope, use_small=False, reorder=reorder, options=options)
-            db.factor()
-            res = db.solve_cases(loads.index_select(0, rows)[:, :, :sub.nJ_max].contiguous())
-            u[rows, :, :sub.nJ_max] = res["u"]
-            f[rows, :, :sub.nJ_max] = res["f_ext"]
-            N[rows, :, :sub.nM_max] = res["N"]
-            info[rows] = db.info
-    if on_device:
-        return LoadCaseResult(u, f, N, info)
-    torch.cuda.synchronize(dev)
-    return LoadCaseResult(u.cpu().numpy(), f.cpu().numpy(), N.cpu().numpy(), info.cpu().numpy())
+    B, nJ_max = packed.B, packed.nJ_max
+    shape = tuple(int(x) for x in loads.shape)
+    if len(shape) != 4 or shape[0] != B or shape[2] != nJ_max or shape[3] not in (2, 3):
+        raise ValueError(f"solve_load_cases: loads must be [B={B}, L, nJ_max={nJ_max}, 2 or 3], got {shape}")
+    out = _load_cases_on_device(torch, dev, packed, _device_f64(torch, dev, loads, vectors=True), max_slab_bytes,
+                                reorder, options, use_envelope)
+    return out if on_device else _host_result(torch, dev, out)
 
 
 @dataclass
@@ -2480,35 +2527,22 @@ def solve_effect_cases(trusses_or_packed, loads=None, prestrain=None, settlement
     DOFs - never the self-weight, which is `body`.  Buckets, member forms, `reorder` plans, `options` and `use_envelope`
     as `solve_load_cases`; `sections=` variants, non-finite entries and z components on a 2D truss raise ValueError
     before any device work."""
-    packed = trusses_or_packed if isinstance(trusses_or_packed, PackedBatch) else pack_trusses(list(trusses_or_packed))
+    packed = _as_packed(trusses_or_packed)
     L, arrays = _check_effect_args(packed, loads, prestrain, settlement, accel, sections)
     torch, dev = _require_gpu(device)
     B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
-    given = {k: torch.from_numpy(v).to(dev) for k, v in arrays.items()}
+    given = {k: _device_f64(torch, dev, v) for k, v in arrays.items()}
     zeros = lambda *shape: torch.zeros(list(shape), dtype=torch.float64, device=dev)
-    u, f, N, body = zeros(B, L, nJ_max, 3), zeros(B, L, nJ_max, 3), zeros(B, L, nM_max), zeros(B, L, nJ_max, 3)
-    info = torch.zeros([B], dtype=torch.int32, device=dev)
-    if B and L:
-        for idx in size_buckets(packed, max_slab_bytes):
-            sub = packed.take(idx).trimmed()
-            rows = torch.from_numpy(np.asarray(idx, dtype=np.int64)).to(dev)
-            db = DeviceBatch(sub, dev, use_envelope=use_envelope, use_small=False, reorder=reorder, options=options)
-            db.factor()
-            cut = {"loads": sub.nJ_max, "prestrain": sub.nM_max, "settlement": sub.nJ_max}
-            part = {k: (v.index_select(0, rows)[:, :, :cut[k]] if k in cut else v.index_select(0, rows)).contiguous()
-                    for k, v in given.items()}
-            res = db.solve_effect_cases(part.get("loads"), part.get("prestrain"), part.get("settlement"),
-                                        part.get("accel"), want_body=True)
-            u[rows, :, :sub.nJ_max] = res["u"]
-            f[rows, :, :sub.nJ_max] = res["f_ext"]
-            N[rows, :, :sub.nM_max] = res["N"]
-            body[rows, :, :sub.nJ_max] = res["body"]
-            info[rows] = db.info
-    if on_device:
-        return EffectCaseResult(u, f, N, body, info)
-    torch.cuda.synchronize(dev)
-    host = lambda x: x.cpu().numpy()
-    return EffectCaseResult(host(u), host(f), host(N), host(body), host(info))
+    out = EffectCaseResult(zeros(B, L, nJ_max, 3), zeros(B, L, nJ_max, 3), zeros(B, L, nM_max), zeros(B, L, nJ_max, 3),
+                           torch.zeros([B], dtype=torch.int32, device=dev))
+    axis = {"loads": dict(nJ=2), "prestrain": dict(nM=2), "settlement": dict(nJ=2), "accel": {}}
+    for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope, cases=L):
+        res = db.solve_effect_cases(**{k: part.cut(given.get(k), **axis[k]) for k in axis}, want_body=True)
+        part.put(out.displace, res["u"], nJ=2)
+        part.put(out.external, res["f_ext"], nJ=2)
+        part.put(out.internal, res["N"], nM=2)
+        part.put(out.body, res["body"], nJ=2)
+    return out if on_device else _host_result(torch, dev, out)
 
 
 @dataclass
@@ -2521,18 +2555,6 @@ class GradientResult:
     dxyz: np.ndarray
     dloads: np.ndarray
     info: np.ndarray
-
-
-def _cotangent(torch, name, g, shape, dev):
-    """A cotangent of `solve_gradients` as a contiguous float64 device tensor of `shape` (2D vectors get z = 0)."""
-    if g is None:
-        return None
-    if isinstance(g, np.ndarray):
-        g = torch.from_numpy(np.ascontiguousarray(g, dtype=np.float64))
-    g = g.to(device=dev, dtype=torch.float64)
-    if len(shape) == 4 and g.dim() == 4 and int(g.shape[3]) == 2:
-        g = torch.nn.functional.pad(g, (0, 1))
-    return g.contiguous()
 
 
 def _check_gradient_args(B, nJ_max, nM_max, loads, cotangents, loss, sections):
@@ -2571,7 +2593,7 @@ def solve_gradients(trusses_or_packed, loads, grad_u=None, grad_f_ext=None, grad
     [b, L, nJ_bucket, 3] / [b, L, nM_bucket] - for objectives that depend on the results (stress limits, displacement
     norms).  Buckets, member forms, `reorder` plans, `on_device` and `use_envelope` as `solve_load_cases`.
     Returns (`LoadCaseResult`, `GradientResult`); gradients not named in `want` come back as zeros."""
-    packed = trusses_or_packed if isinstance(trusses_or_packed, PackedBatch) else pack_trusses(list(trusses_or_packed))
+    packed = _as_packed(trusses_or_packed)
     B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
     cots = {"grad_u": grad_u, "grad_f_ext": grad_f_ext, "grad_N": grad_N}
     L = _check_gradient_args(B, nJ_max, nM_max, loads, cots, loss, sections)
@@ -2579,45 +2601,25 @@ def solve_gradients(trusses_or_packed, loads, grad_u=None, grad_f_ext=None, grad
     if any(k not in DeviceBatch.GRADIENTS for k in want):
         raise ValueError(f"solve_gradients: want must name some of {DeviceBatch.GRADIENTS}, got {want}")
     torch, dev = _require_gpu(device)
-    loads = _cotangent(torch, "loads", loads, (B, L, nJ_max, 3), dev)
-    cots = {k: _cotangent(torch, k, g, (B, L, nM_max) if k == "grad_N" else (B, L, nJ_max, 3), dev)
-            for k, g in cots.items()}
+    cots = {k: _device_f64(torch, dev, g, vectors=k != "grad_N") for k, g in cots.items()}
     zeros = lambda *shape: torch.zeros(list(shape), dtype=torch.float64, device=dev)
-    u, f, N = zeros(B, L, nJ_max, 3), zeros(B, L, nJ_max, 3), zeros(B, L, nM_max)
-    grads = {"A": zeros(B, nM_max), "E": zeros(B, nM_max), "xyz": zeros(B, nJ_max, 3), "loads": zeros(B, L, nJ_max, 3)}
-    info = torch.zeros([B], dtype=torch.int32, device=dev)
-    if B and L:
-        for idx in size_buckets(packed, max_slab_bytes):
-            sub = packed.take(idx).trimmed()
-            rows = torch.from_numpy(np.asarray(idx, dtype=np.int64)).to(dev)
-            db = DeviceBatch(sub, dev, use_envelope=use_envelope, use_small=False, reorder=reorder, options=options)
-            db.factor()
-            res = db.solve_cases(loads.index_select(0, rows)[:, :, :sub.nJ_max].contiguous())
-            if loss is not None:
-                gu_b, gf_b, gN_b = loss(res["u"], res["f_ext"], res["N"])
-            else:
-                cut = lambda g, n: None if g is None else g.index_select(0, rows)[:, :, :n].contiguous()
-                gu_b, gf_b = cut(cots["grad_u"], sub.nJ_max), cut(cots["grad_f_ext"], sub.nJ_max)
-                gN_b = cut(cots["grad_N"], sub.nM_max)
-            g = db.adjoint_cases(gu_b, gf_b, gN_b, want=want)
-            u[rows, :, :sub.nJ_max] = res["u"]
-            f[rows, :, :sub.nJ_max] = res["f_ext"]
-            N[rows, :, :sub.nM_max] = res["N"]
-            info[rows] = db.info
-            for key, val in g.items():
-                if key == "loads":
-                    grads[key][rows, :, :sub.nJ_max] = val
-                elif key == "xyz":
-                    grads[key][rows, :sub.nJ_max] = val
-                else:
-                    grads[key][rows, :sub.nM_max] = val
-    if not on_device:
-        torch.cuda.synchronize(dev)
-        host = lambda x: x.cpu().numpy()
-        u, f, N, info = host(u), host(f), host(N), host(info)
-        grads = {k: host(v) for k, v in grads.items()}
-    return (LoadCaseResult(u, f, N, info),
-            GradientResult(grads["A"], grads["E"], grads["xyz"], grads["loads"], info))
+    grads = GradientResult(zeros(B, nM_max), zeros(B, nM_max), zeros(B, nJ_max, 3), zeros(B, L, nJ_max, 3), None)
+    dst = {"A": (grads.dA, dict(nM=1)), "E": (grads.dE, dict(nM=1)), "xyz": (grads.dxyz, dict(nJ=1)),
+           "loads": (grads.dloads, dict(nJ=2))}
+
+    def adjoint(db, part, res):
+        if loss is not None:
+            gu, gf, gN = loss(res["u"], res["f_ext"], res["N"])
+        else:
+            gu, gf = part.cut(cots["grad_u"], nJ=2), part.cut(cots["grad_f_ext"], nJ=2)
+            gN = part.cut(cots["grad_N"], nM=2)
+        for key, val in db.adjoint_cases(gu, gf, gN, want=want).items():
+            part.put(dst[key][0], val, **dst[key][1])
+
+    out = _load_cases_on_device(torch, dev, packed, _device_f64(torch, dev, loads, vectors=True), max_slab_bytes,
+                                reorder, options, use_envelope, after=adjoint)
+    grads.info = out.info
+    return (out, grads) if on_device else (_host_result(torch, dev, out), _host_result(torch, dev, grads))
 
 
 @dataclass
@@ -2663,13 +2665,12 @@ def solve_modes(trusses_or_packed, p=6, joint_mass=None, mass_scale=1.0, tol=1e-
     caller's joint numbering, non-negative) or None; `mass_scale`: 1 / g for densities given as weight densities.
     Buckets, member forms, `reorder` plans, `on_device` and `use_envelope` as `solve_load_cases`.  Returns a
     `ModeResult`."""
-    packed = trusses_or_packed if isinstance(trusses_or_packed, PackedBatch) else pack_trusses(list(trusses_or_packed))
+    packed = _as_packed(trusses_or_packed)
     B, nJ_max = packed.B, packed.nJ_max
     jm_shape = jm_min = None
     if joint_mass is not None:
         jm_shape = tuple(int(x) for x in joint_mass.shape)
         if isinstance(joint_mass, np.ndarray):
-            joint_mass = np.ascontiguousarray(joint_mass, dtype=np.float64)
             jm_min = float(joint_mass.min()) if joint_mass.size else 0.0
             jm_min = jm_min if np.isfinite(joint_mass).all() else float("nan")
         else:
@@ -2678,36 +2679,17 @@ def solve_modes(trusses_or_packed, p=6, joint_mass=None, mass_scale=1.0, tol=1e-
     _check_mode_args(B, nJ_max, p, jm_shape, mass_scale, tol, max_iters, joint_mass_min=jm_min)
     p = int(p)
     torch, dev = _require_gpu(device)
-    if isinstance(joint_mass, np.ndarray):
-        joint_mass = torch.from_numpy(joint_mass)
-    if joint_mass is not None:
-        joint_mass = joint_mass.to(device=dev, dtype=torch.float64)
-    lam = torch.full([B, p], float("nan"), dtype=torch.float64, device=dev)
-    phi = torch.zeros([B, p, nJ_max, 3], dtype=torch.float64, device=dev)
-    resid = torch.full([B, p], float("nan"), dtype=torch.float64, device=dev)
-    n_modes = torch.zeros([B], dtype=torch.int32, device=dev)
-    iters = torch.zeros([B], dtype=torch.int32, device=dev)
-    info = torch.zeros([B], dtype=torch.int32, device=dev)
-    if B:
-        for idx in size_buckets(packed, max_slab_bytes):
-            sub = packed.take(idx).trimmed()
-            rows = torch.from_numpy(np.asarray(idx, dtype=np.int64)).to(dev)
-            db = DeviceBatch(sub, dev, use_envelope=use_envelope, use_small=False, reorder=reorder, options=options)
-            db.factor()
-            jm = None if joint_mass is None else joint_mass.index_select(0, rows)[:, :sub.nJ_max].contiguous()
-            res = db.modes(p, tol=tol, max_iters=max_iters, joint_mass=jm, mass_scale=mass_scale)
-            lam[rows] = res["lam"]
-            phi[rows, :, :sub.nJ_max] = res["phi"]
-            resid[rows] = res["resid"]
-            n_modes[rows] = res["n_modes"]
-            iters[rows] = res["iters"]
-            info[rows] = db.info
-    omega = lam.sqrt()
-    if on_device:
-        return ModeResult(lam, omega, phi, resid, n_modes, iters, info)
-    torch.cuda.synchronize(dev)
-    host = lambda x: x.cpu().numpy()
-    return ModeResult(host(lam), host(omega), host(phi), host(resid), host(n_modes), host(iters), host(info))
+    joint_mass = _device_f64(torch, dev, joint_mass)
+    full = lambda shape, value, dtype=torch.float64: torch.full(shape, value, dtype=dtype, device=dev)
+    out = ModeResult(full([B, p], float("nan")), None, full([B, p, nJ_max, 3], 0.0), full([B, p], float("nan")),
+                     full([B], 0, torch.int32), full([B], 0, torch.int32), full([B], 0, torch.int32))
+    for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope):
+        res = db.modes(p, tol=tol, max_iters=max_iters, joint_mass=part.cut(joint_mass, nJ=1), mass_scale=mass_scale)
+        part.put(out.shape, res["phi"], nJ=2)
+        for field, key in (("eigenvalue", "lam"), ("residual", "resid"), ("n_modes", "n_modes"), ("iters", "iters")):
+            part.put(getattr(out, field), res[key])
+    out.omega = out.eigenvalue.sqrt()
+    return out if on_device else _host_result(torch, dev, out)
 
 
 def _is_pinned(packed):

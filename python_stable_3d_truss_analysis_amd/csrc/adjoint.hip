@@ -16,9 +16,10 @@
 //   g_m  = (k / len) { t_m D u - (c . D u) D mu + (c . D u) (3 c . D mu - 2 gN_m) c },   gxyz_j = sum_ends (+- g_m)
 //
 // One work-group per truss, as trs_recover_cases: the member-end lists of EVERY joint are built in LDS once
-// (integer atomics, then sorted by member id), every joint's sum runs over its list in member-id order, the cases
-// are accumulated in the order k = 0 .. L - 1, and no floating-point atomic is used anywhere: the results are
-// bit-reproducible from run to run, from stream to stream and between the two member forms.
+// (trs_rec::build_end_lists in trs_recover.h: integer atomics, then sorted by member id), every joint's sum runs over
+// its list in member-id order, the cases are accumulated in the order k = 0 .. L - 1, and no floating-point atomic is
+// used anywhere: the results are bit-reproducible from run to run, from stream to stream and between the two member
+// forms.
 #include "../../include/trs_solver.h"
 #include "trs_common.h"
 #include "trs_recover.h"
@@ -32,13 +33,10 @@ __device__ __forceinline__ double member_modulus(const TrsMembers& mem, size_t m
 }
 
 // LDS tables of one truss (both kernels; the right-hand-side kernel uses one of the two DOF vectors)
-struct AdjTables {
+struct AdjTables : EndLists {  // (the member-end lists of EVERY joint: trs_recover.h)
     double* v0;   // [3 nJ_max]
     double* v1;   // [3 nJ_max]
     double* pm;   // [nM_max]    one double per member
-    int* cnt;     // [nJ_max]
-    int* start;   // [nJ_max + 1]
-    int* ends;    // [2 nM_max]  (member << 1) | end, per joint, sorted by member id
 };
 
 __device__ __forceinline__ AdjTables adj_tables(double* sh, int nJ_max, int nM_max) {
@@ -50,59 +48,6 @@ __device__ __forceinline__ AdjTables adj_tables(double* sh, int nJ_max, int nM_m
     t.start = t.cnt + nJ_max;
     t.ends = t.start + nJ_max + 1;
     return t;
-}
-
-// The member-end lists of every joint of truss b, sorted by member id (trs_recover_cases builds the same lists
-// for the constrained joints only).  Ends with a barrier.
-__device__ __forceinline__ void build_end_lists(const AdjTables& t, const TrsMembers& mem, const size_t mbase,
-                                                const int joints, const int members, const int nJ_max,
-                                                const int tid) {
-    for (int j = tid; j < nJ_max; j += 256) t.cnt[j] = 0;
-    __syncthreads();
-    for (int m = tid; m < members; m += 256) {
-        const int2 c = mem.ends(mbase + m);
-        atomicAdd(&t.cnt[c.x], 1);
-        atomicAdd(&t.cnt[c.y], 1);
-    }
-    __syncthreads();
-    if (tid < 64) {  // exclusive scan of cnt by one wave
-        int base = 0;
-        for (int j0 = 0; j0 < joints; j0 += 64) {
-            const int j = j0 + tid;
-            const int v = j < joints ? t.cnt[j] : 0;
-            int incl = v;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const int up = __shfl_up(incl, off);
-                if (tid >= off) incl += up;
-            }
-            if (j < joints) t.start[j] = base + incl - v;
-            base += __shfl(incl, 63);
-        }
-    }
-    __syncthreads();
-    for (int j = tid; j < joints; j += 256) t.cnt[j] = 0;  // the fill cursor
-    __syncthreads();
-    for (int m = tid; m < members; m += 256) {
-        const int2 c = mem.ends(mbase + m);
-        t.ends[t.start[c.x] + atomicAdd(&t.cnt[c.x], 1)] = m << 1;
-        t.ends[t.start[c.y] + atomicAdd(&t.cnt[c.y], 1)] = (m << 1) | 1;
-    }
-    __syncthreads();
-    for (int j = tid; j < joints; j += 256) {
-        int* list = t.ends + t.start[j];
-        const int deg = t.cnt[j];
-        for (int i = 1; i < deg; ++i) {
-            const int key = list[i];
-            int p = i - 1;
-            while (p >= 0 && list[p] > key) {
-                list[p + 1] = list[p];
-                --p;
-            }
-            list[p + 1] = key;
-        }
-    }
-    __syncthreads();
 }
 
 // ---- step 1: the reduced right-hand side of the adjoint system ------------------------------------------------------
@@ -124,6 +69,7 @@ __global__ __launch_bounds__(256) void trs_adjoint_rhs_kernel(
     const int* ji = joint_in != nullptr ? joint_in + (size_t)b * nJ_max : nullptr;
     const int n = n_free[b], npad = trs_round_up(n, TRS_NB);
     build_end_lists(t, mem, mbase, joints, members, nJ_max, tid);
+    __syncthreads();
     for (int k = 0; k < L; ++k) {
         const size_t bk = (size_t)b * L + k;
         const double* guk = gu != nullptr ? gu + bk * ndof_max : nullptr;  // caller's numbering
@@ -187,7 +133,10 @@ __global__ __launch_bounds__(256) void trs_adjoint_grad_kernel(
     const int* jo = joint_out != nullptr ? joint_out + (size_t)b * nJ_max : nullptr;
     const bool want_sections = (gA != nullptr) | (gE != nullptr);
     double* gx = gxyz != nullptr ? gxyz + (size_t)b * ndof_max : nullptr;
-    if (gx != nullptr) build_end_lists(t, mem, mbase, joints, members, nJ_max, tid);
+    if (gx != nullptr) {
+        build_end_lists(t, mem, mbase, joints, members, nJ_max, tid);
+        __syncthreads();
+    }
     for (int k = 0; k < L; ++k) {
         const size_t bk = (size_t)b * L + k;
         const double* uk = Fu + bk * ld_f;

@@ -279,60 +279,18 @@ __global__ __launch_bounds__(256) void trs_recover_cases_kernel(
     const int joints = nJ[b], members = nM[b];
     const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
     double* u = sh;                                              // [ndof_max]
-    int* cnt = reinterpret_cast<int*>(sh + ndof_max);            // [nJ_max]
-    int* start = cnt + nJ_max;                                   // [nJ_max + 1]
-    int* ends = start + nJ_max + 1;                              // [2 nM_max]
+    EndLists t;
+    t.cnt = reinterpret_cast<int*>(sh + ndof_max);               // [nJ_max]
+    t.start = t.cnt + nJ_max;                                    // [nJ_max + 1]
+    t.ends = t.start + nJ_max + 1;                               // [2 nM_max]
     const int* fi = free_index + (size_t)b * ndof_max;
     const double* X = xyz + (size_t)b * ndof_max;
     const size_t mbase = (size_t)b * nM_max;
     const int* jo = joint_out != nullptr ? joint_out + (size_t)b * nJ_max : nullptr;
     auto constrained = [&](int j) { return (fi[3 * j] < 0) | (fi[3 * j + 1] < 0) | (fi[3 * j + 2] < 0); };
-    for (int j = tid; j < nJ_max; j += 256) cnt[j] = 0;
-    __syncthreads();
-    for (int m = tid; m < members; m += 256) {
-        const int2 c = mem.ends(mbase + m);
-        if (constrained(c.x)) atomicAdd(&cnt[c.x], 1);
-        if (constrained(c.y)) atomicAdd(&cnt[c.y], 1);
-    }
-    __syncthreads();
-    if (tid < 64) {  // exclusive scan of cnt by one wave
-        int base = 0;
-        for (int j0 = 0; j0 < joints; j0 += 64) {
-            const int j = j0 + tid;
-            const int v = j < joints ? cnt[j] : 0;
-            int incl = v;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const int up = __shfl_up(incl, off);
-                if (tid >= off) incl += up;
-            }
-            if (j < joints) start[j] = base + incl - v;
-            base += __shfl(incl, 63);
-        }
-    }
-    __syncthreads();
-    for (int j = tid; j < joints; j += 256) cnt[j] = 0;  // the fill cursor
-    __syncthreads();
-    for (int m = tid; m < members; m += 256) {
-        const int2 c = mem.ends(mbase + m);
-        if (constrained(c.x)) ends[start[c.x] + atomicAdd(&cnt[c.x], 1)] = m << 1;
-        if (constrained(c.y)) ends[start[c.y] + atomicAdd(&cnt[c.y], 1)] = (m << 1) | 1;
-    }
-    __syncthreads();
-    // sorted by member id once (joint_reaction sorts in place; later cases find the lists sorted)
-    for (int j = tid; j < joints; j += 256) {
-        int* list = ends + start[j];
-        const int deg = cnt[j];
-        for (int i = 1; i < deg; ++i) {
-            const int key = list[i];
-            int p = i - 1;
-            while (p >= 0 && list[p] > key) {
-                list[p + 1] = list[p];
-                --p;
-            }
-            list[p + 1] = key;
-        }
-    }
+    // sorted by member id once (joint_reaction sorts in place; later cases find the lists sorted); the case loop opens
+    // with the barrier that the builder leaves to its caller
+    build_end_lists(t, mem, mbase, joints, members, nJ_max, tid, constrained);
     for (int k = 0; k < L; ++k) {
         const size_t bk = (size_t)b * L + k;
         const double* fk = F + bk * ld_f;
@@ -360,7 +318,7 @@ __global__ __launch_bounds__(256) void trs_recover_cases_kernel(
             N_out[bk * nM_max + m] = axial;
         }
         for (int j = tid; j < joints; j += 256) {
-            const int deg = cnt[j];
+            const int deg = t.cnt[j];
             if (deg == 0) {
                 // a constrained joint without members: zero reaction
                 if (constrained(j)) {
@@ -372,7 +330,7 @@ __global__ __launch_bounds__(256) void trs_recover_cases_kernel(
                 continue;
             }
             double r[3];
-            joint_reaction(ends + start[j], deg, mem, X, mbase, u, nullptr, r);
+            joint_reaction(t.ends + t.start[j], deg, mem, X, mbase, u, nullptr, r);
             const int o = jo != nullptr ? 3 * jo[j] : 3 * j;
 #pragma unroll
             for (int a = 0; a < 3; ++a)

@@ -16,9 +16,8 @@
 // built in LDS once (integer atomics, then sorted by member id), every joint's sums run over its list in member-id
 // order, and no floating-point atomic is used anywhere.  N and the support sums are formed by the functions of
 // trs_recover.h in trs_recover_cases' order and an effect's term is added only where its pointer is non-null: without
-// effects the bits are those of the plain load cases.
-// build_end_lists is a second copy of adjoint.hip's (that file is left as it is: its kernels' code objects, and so the
-// bits and the timings of the adjoint path, stay what they were); the tables here differ - one DOF vector, not two.
+// effects the bits are those of the plain load cases.  The list builder is trs_rec::build_end_lists (trs_recover.h),
+// the one that trs_recover_cases and the adjoint kernels use.
 #include "../../include/trs_effects.h"
 #include "trs_common.h"
 #include "trs_recover.h"
@@ -28,12 +27,9 @@ namespace {
 using namespace trs_rec;
 
 // LDS tables of one truss (both kernels)
-struct EffTables {
+struct EffTables : EndLists {  // (the member-end lists of EVERY joint: trs_recover.h)
     double* v;    // [3 nJ_max]  ubar (right-hand side) or u (recovery) of one case, device numbering
     double* pm;   // [nM_max]    one double per member: s_m or N_m of that case
-    int* cnt;     // [nJ_max]
-    int* start;   // [nJ_max + 1]
-    int* ends;    // [2 nM_max]  (member << 1) | end, per joint, sorted by member id
 };
 
 __device__ __forceinline__ EffTables eff_tables(double* sh, int nJ_max, int nM_max) {
@@ -49,58 +45,6 @@ __device__ __forceinline__ EffTables eff_tables(double* sh, int nJ_max, int nM_m
 size_t effects_lds(int nJ_max, int nM_max) {
     return (((size_t)3 * nJ_max + (size_t)nM_max) * sizeof(double) +
             ((size_t)2 * nJ_max + 1 + 2 * (size_t)nM_max) * sizeof(int) + 15) / 16 * 16;
-}
-
-// The member-end lists of every joint of truss b, sorted by member id.  Ends with a barrier.
-__device__ __forceinline__ void build_end_lists(const EffTables& t, const TrsMembers& mem, const size_t mbase,
-                                                const int joints, const int members, const int nJ_max,
-                                                const int tid) {
-    for (int j = tid; j < nJ_max; j += 256) t.cnt[j] = 0;
-    __syncthreads();
-    for (int m = tid; m < members; m += 256) {
-        const int2 c = mem.ends(mbase + m);
-        atomicAdd(&t.cnt[c.x], 1);
-        atomicAdd(&t.cnt[c.y], 1);
-    }
-    __syncthreads();
-    if (tid < 64) {  // exclusive scan of cnt by one wave
-        int base = 0;
-        for (int j0 = 0; j0 < joints; j0 += 64) {
-            const int j = j0 + tid;
-            const int v = j < joints ? t.cnt[j] : 0;
-            int incl = v;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const int up = __shfl_up(incl, off);
-                if (tid >= off) incl += up;
-            }
-            if (j < joints) t.start[j] = base + incl - v;
-            base += __shfl(incl, 63);
-        }
-    }
-    __syncthreads();
-    for (int j = tid; j < joints; j += 256) t.cnt[j] = 0;  // the fill cursor
-    __syncthreads();
-    for (int m = tid; m < members; m += 256) {
-        const int2 c = mem.ends(mbase + m);
-        t.ends[t.start[c.x] + atomicAdd(&t.cnt[c.x], 1)] = m << 1;
-        t.ends[t.start[c.y] + atomicAdd(&t.cnt[c.y], 1)] = (m << 1) | 1;
-    }
-    __syncthreads();
-    for (int j = tid; j < joints; j += 256) {
-        int* list = t.ends + t.start[j];
-        const int deg = t.cnt[j];
-        for (int i = 1; i < deg; ++i) {
-            const int key = list[i];
-            int p = i - 1;
-            while (p >= 0 && list[p] > key) {
-                list[p + 1] = list[p];
-                --p;
-            }
-            list[p + 1] = key;
-        }
-    }
-    __syncthreads();
 }
 
 // Half the weight of member mm on one of its end joints, added to the joint's running body load: the product in
@@ -134,7 +78,10 @@ __global__ __launch_bounds__(256) void trs_effects_rhs_kernel(
     const int n = n_free[b], npad = trs_round_up(n, TRS_NB);
     const bool member_terms = (eps0 != nullptr) | (ubar != nullptr);
     const bool lists = member_terms | (accel != nullptr);
-    if (lists) build_end_lists(t, mem, mbase, joints, members, nJ_max, tid);
+    if (lists) {
+        build_end_lists(t, mem, mbase, joints, members, nJ_max, tid);
+        __syncthreads();
+    }
     for (int k = 0; k < L; ++k) {
         const size_t bk = (size_t)b * L + k;
         const double* lk = loads != nullptr ? loads + bk * ndof_max : nullptr;  // caller's numbering
@@ -210,6 +157,7 @@ __global__ __launch_bounds__(256) void trs_effects_recover_kernel(
     const size_t mbase = (size_t)b * nM_max;
     const int* jo = joint_out != nullptr ? joint_out + (size_t)b * nJ_max : nullptr;
     build_end_lists(t, mem, mbase, joints, members, nJ_max, tid);
+    __syncthreads();
     for (int k = 0; k < L; ++k) {
         const size_t bk = (size_t)b * L + k;
         const double* fk = F + bk * ld_f;

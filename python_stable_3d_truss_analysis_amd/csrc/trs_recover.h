@@ -1,6 +1,7 @@
 // trs_recover.h - the per-member and per-joint arithmetic of the result recovery, shared by trs_recover
 // (recover.hip) and the multi-case recovery trs_recover_cases (cases.hip): both paths call the same functions,
-// so case k of a multi-case recovery rounds exactly like a single recovery of case k.
+// so case k of a multi-case recovery rounds exactly like a single recovery of case k.  Also the builder of the
+// per-joint member-end lists in LDS that cases.hip, adjoint.hip and effects.hip sum over (build_end_lists).
 #pragma once
 #include "trs_common.h"
 
@@ -64,6 +65,74 @@ __device__ __forceinline__ void joint_reaction(ListPtr list, const int deg, cons
         const MemberGeom g = member_geom(X, c.x, c.y);
         const double axial = member_axial(g, mem.EA(mbase + m), u, jo ? jo[c.x] : c.x, jo ? jo[c.y] : c.y);
         add_end_force(r, g.c, axial, end);
+    }
+}
+
+// The member-end lists of one truss in LDS: joint j's ends are ends[start[j] .. start[j] + cnt[j]), each
+// (member << 1) | end, sorted by member id.
+struct EndLists {
+    int* cnt;     // [nJ_max]
+    int* start;   // [nJ_max + 1]
+    int* ends;    // [2 nM_max]
+};
+
+struct EveryJoint {
+    __device__ __forceinline__ bool operator()(int) const { return true; }
+};
+
+// Builds the lists of the joints that `keep(j)` admits (the others get empty lists), by a work-group of 256 threads:
+// count with integer atomics, scan, fill, then every list is sorted by member id - the order in which every kernel
+// sums over a list, whatever order the atomics filled it in.  The ONE builder of trs_recover_cases (cases.hip: the
+// constrained joints), the adjoint kernels (adjoint.hip) and the effect kernels (effects.hip).  There is no barrier
+// after the sort: the caller places one before a thread reads a list that it did not sort itself.
+template <class Keep = EveryJoint>
+__device__ __forceinline__ void build_end_lists(const EndLists& t, const TrsMembers& mem, const size_t mbase,
+                                                const int joints, const int members, const int nJ_max, const int tid,
+                                                Keep keep = Keep()) {
+    for (int j = tid; j < nJ_max; j += 256) t.cnt[j] = 0;
+    __syncthreads();
+    for (int m = tid; m < members; m += 256) {
+        const int2 c = mem.ends(mbase + m);
+        if (keep(c.x)) atomicAdd(&t.cnt[c.x], 1);
+        if (keep(c.y)) atomicAdd(&t.cnt[c.y], 1);
+    }
+    __syncthreads();
+    if (tid < 64) {  // exclusive scan of cnt by one wave
+        int base = 0;
+        for (int j0 = 0; j0 < joints; j0 += 64) {
+            const int j = j0 + tid;
+            const int v = j < joints ? t.cnt[j] : 0;
+            int incl = v;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const int up = __shfl_up(incl, off);
+                if (tid >= off) incl += up;
+            }
+            if (j < joints) t.start[j] = base + incl - v;
+            base += __shfl(incl, 63);
+        }
+    }
+    __syncthreads();
+    for (int j = tid; j < joints; j += 256) t.cnt[j] = 0;  // the fill cursor
+    __syncthreads();
+    for (int m = tid; m < members; m += 256) {
+        const int2 c = mem.ends(mbase + m);
+        if (keep(c.x)) t.ends[t.start[c.x] + atomicAdd(&t.cnt[c.x], 1)] = m << 1;
+        if (keep(c.y)) t.ends[t.start[c.y] + atomicAdd(&t.cnt[c.y], 1)] = (m << 1) | 1;
+    }
+    __syncthreads();
+    for (int j = tid; j < joints; j += 256) {
+        int* list = t.ends + t.start[j];
+        const int deg = t.cnt[j];
+        for (int i = 1; i < deg; ++i) {
+            const int key = list[i];
+            int p = i - 1;
+            while (p >= 0 && list[p] > key) {
+                list[p + 1] = list[p];
+                --p;
+            }
+            list[p + 1] = key;
+        }
     }
 }
 
