@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h` and `include/trs_effects.h` (library: `libtrs_hip.so`, in-tree).
+"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h` and `include/trs_loss.h` (library: `libtrs_hip.so`, in-tree).
 
 There is no fallback: if the library is missing, `load()` raises `HipExtensionError`.
 """
@@ -101,12 +101,26 @@ EFFECTS_SIGNATURES = {
                                      _P, _P]),
 }
 
+#: every symbol `include/trs_loss.h` declares (member-loss analysis; csrc/loss.hip, the same library)
+LOSS_SIGNATURES = {
+    "trs_loss_abi_version": (_I, []),
+    "trs_loss_fits": (_I, [_I, _I, _I]),
+    "trs_loss_rhs": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "trs_loss_tab_rhs": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "trs_loss_apply": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _D, _P, _P, _P, _P, _P, _P,
+                            _P, _P, _P]),
+    "trs_loss_tab_apply": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _D, _P, _P, _P, _P, _P,
+                                _P, _P, _P, _P]),
+}
+
 #: must equal TRS_ABI_VERSION of include/trs_solver.h
 ABI_VERSION = 10
 #: must equal TRS_MODES_ABI_VERSION of include/trs_modes.h
 MODES_ABI_VERSION = 1
 #: must equal TRS_EFFECTS_ABI_VERSION of include/trs_effects.h
 EFFECTS_ABI_VERSION = 1
+#: must equal TRS_LOSS_ABI_VERSION of include/trs_loss.h
+LOSS_ABI_VERSION = 1
 #: TRS_MODES_BLOCK of include/trs_modes.h: vectors per truss of the block iteration (one case group)
 MODES_BLOCK = 16
 
@@ -148,13 +162,13 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as exc:
         raise HipExtensionError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for table in (SIGNATURES, MODES_SIGNATURES, EFFECTS_SIGNATURES):
+    for table in (SIGNATURES, MODES_SIGNATURES, EFFECTS_SIGNATURES, LOSS_SIGNATURES):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype = restype
             fn.argtypes = argtypes
     if lib.trs_abi_version() != ABI_VERSION or lib.trs_modes_abi_version() != MODES_ABI_VERSION \
-            or lib.trs_effects_abi_version() != EFFECTS_ABI_VERSION:
+            or lib.trs_effects_abi_version() != EFFECTS_ABI_VERSION or lib.trs_loss_abi_version() != LOSS_ABI_VERSION:
         raise HipExtensionError("libtrs_hip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -449,6 +449,11 @@ def joint_order_device(torch, tensors, effort=2, apply=True, want_choice=False, 
     return out
 
 
+#: `r_tol` of the member-loss analysis: a member whose redundancy r_e is at most this is critical.  Over the shipped
+#: fixtures the critical members have |r| <= a few 1e-15 and the others r >= 3.8e-4 (EXPERIMENTS R14).
+MEMBER_LOSS_R_TOL = 1e-8
+
+
 def _ptr(x):
     """The device address of an optional tensor argument of a C call."""
     return None if x is None else x.data_ptr()
@@ -930,7 +935,7 @@ class DeviceBatch:
 
     @property
     def generation(self):
-        """Counts the `factor()`, `solve_cases()`, `solve_effect_cases()` and `modes()` calls of this batch: a forward state is identified by the value
+        """Counts the `factor()`, `solve_cases()` (also the one inside `member_loss()`), `solve_effect_cases()` and `modes()` calls of this batch: a forward state is identified by the value
         after its `solve_cases()`, and `adjoint_cases` refuses any other."""
         return getattr(self, "_generation", 0)
 
@@ -994,6 +999,71 @@ class DeviceBatch:
                 self.cases_F.data_ptr(), Lam.data_ptr(), self.rows, _ptr(out.get("A")), _ptr(out.get("E")),
                 _ptr(out.get("xyz")), _ptr(out.get("loads")), jo, stream), f"trs_adjoint{tab}_grad")
         self.cases_Lam = Lam
+        return out
+
+    # -- member-loss analysis: every single-member removal from the resident factor (include/trs_loss.h) ------------------
+    def member_loss(self, loads, r_tol=MEMBER_LOSS_R_TOL, want_forces=False, chunk=64, out=None,
+                    max_result_bytes=4 << 30):
+        """What the loss of any ONE member does to every truss, for every member, on the resident factor (`factor()`
+        first): a removal is a rank-one change of K_ff, so per member one substitution column against the factor and
+        one pass of `trs_loss_apply` replace a factorisation (include/trs_loss.h).  `loads`: float64 device tensor
+        [B, L, nJ_max, 3] in the CALLER's joint numbering, as `solve_cases` takes it.  The intact state comes from
+        `solve_cases(loads)`; then the members are taken `chunk` at a time (rounded up to a multiple of 16, one case
+        group of the substitution): `trs_loss_rhs`, `trs_potrs_cases`, `trs_loss_apply`, on a buffer [B, chunk, rows] of
+        this method's own (allocated per call, beside the slab) - `cases_F` keeps the intact displacements.  Returns a dict of device tensors: u, f_ext
+        [B, L, nJ_max, 3] and N [B, L, nM_max] of the intact truss, r [B, nM_max] (the redundancy 1 - k_e b_e . z_e; the
+        r of a truss sum to nM - n_free), critical [B, nM_max] (int32: r <= `r_tol`, the truss is a mechanism without
+        that member), peak_stress, peak_displace [B, L, nM_max] (max |N'| / A over the surviving members, max |u'| over
+        the joints; +inf for a critical member) with peak_member, peak_joint (int32; caller's joint numbering, the
+        lowest id on a tie, -1 where there is none) and - `want_forces` - N_after [B, L, nM_max, nM_max], row e the
+        member forces without member e (NaN for a critical member); refused with ValueError when it would exceed
+        `max_result_bytes`.  `out`: such a dict to write into.  `generation` is bumped by the `solve_cases` inside and
+        the forward state is that call's: `adjoint_cases` differentiates the intact state afterwards."""
+        t = self.torch
+        self._need_factor("member_loss")
+        if loads.dim() != 4 or tuple(loads.shape[:1]) + tuple(loads.shape[2:]) != (self.B, self.nJ_max, 3) \
+                or loads.dtype != t.float64 or loads.device != self.device:
+            raise ValueError(f"member_loss(): loads must be float64 [B={self.B}, L, nJ_max={self.nJ_max}, 3] on {self.device}")
+        if not 0.0 < float(r_tol) < 1.0:
+            raise ValueError(f"member_loss(): r_tol must lie in (0, 1), got {r_tol!r}")
+        if int(chunk) < 1:
+            raise ValueError(f"member_loss(): chunk must be at least 1, got {chunk!r}")
+        B, L, nJ_max, nM_max = self.B, int(loads.shape[1]), self.nJ_max, self.nM_max
+        if want_forces and B * L * nM_max * nM_max * 8 > max_result_bytes:
+            raise ValueError(f"member_loss(): N_after [B={B}, L={L}, {nM_max}, {nM_max}] takes {B * L * nM_max * nM_max * 8} "
+                             f"bytes, more than max_result_bytes = {max_result_bytes}")
+        i32 = t.int32
+        shapes = {"u": [B, L, nJ_max, 3], "f_ext": [B, L, nJ_max, 3], "N": [B, L, nM_max], "r": [B, nM_max],
+                  "critical": ([B, nM_max], i32), "peak_stress": [B, L, nM_max], "peak_member": ([B, L, nM_max], i32),
+                  "peak_displace": [B, L, nM_max], "peak_joint": ([B, L, nM_max], i32)}
+        if want_forces:
+            shapes["N_after"] = [B, L, nM_max, nM_max]
+        out = self._out_tensors("member_loss", shapes, out)
+        if B and L and not self.lib.trs_loss_fits(nJ_max, nM_max, L):
+            raise HipExtensionError(f"member_loss(): a truss of {nJ_max} joints / {nM_max} members exceeds the LDS of "
+                                    "the apply kernel (trs_loss_fits)")
+        self.solve_cases(loads, out={k: out[k] for k in ("u", "f_ext", "N")})
+        if B == 0 or L == 0 or nM_max == 0:
+            return out
+        C = min(-(-int(chunk) // 16) * 16, -(-nM_max // 16) * 16)
+        # the chunk's columns: B * C * rows doubles (1.5 GB for bar-942 x 4096 at chunk 64) beside the slab, not counted
+        # in `max_slab_bytes`, and released when this call returns
+        Z = t.empty([B, C, self.rows], dtype=t.float64, device=self.device)
+        jo, stream, tab = self._case_launch()
+        rhs, apply = getattr(self.lib, f"trs_loss{tab}_rhs"), getattr(self.lib, f"trs_loss{tab}_apply")
+        with t.cuda.device(self.device):
+            for e0 in range(0, nM_max, C):
+                _capi.check(rhs(B, e0, C, nJ_max, nM_max, self.xyz.data_ptr(), *self._members(),
+                                self.free_index.data_ptr(), self.n_free.data_ptr(), self.nM.data_ptr(), Z.data_ptr(),
+                                self.rows, stream), f"trs_loss{tab}_rhs")
+                self._potrs_cases(Z, C)
+                _capi.check(apply(B, L, e0, C, nJ_max, nM_max, self.xyz.data_ptr(), *self._members(),
+                                  self.free_index.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), Z.data_ptr(),
+                                  self.cases_F.data_ptr(), self.rows, float(r_tol), out["r"].data_ptr(),
+                                  out["critical"].data_ptr(), out["peak_stress"].data_ptr(),
+                                  out["peak_member"].data_ptr(), out["peak_displace"].data_ptr(),
+                                  out["peak_joint"].data_ptr(), _ptr(out.get("N_after")), jo, stream),
+                            f"trs_loss{tab}_apply")
         return out
 
     # -- natural frequencies and mode shapes from the resident factor (include/trs_modes.h) ------------------
@@ -2349,7 +2419,8 @@ def _host_result(torch, dev, res):
 
 class _Bucket:
     """One size bucket of `_factored_buckets`: `rows`, its trusses' places in the full batch, and the bucket's own padded
-    sizes.  `cut` and `put` name the axis that runs over joints (`nJ=`) or members (`nM=`), if the tensor has one."""
+    sizes.  `cut` and `put` name the axis that runs over joints (`nJ=`) or members (`nM=`; `put` takes a tuple of them
+    too), if the tensor has one."""
 
     def __init__(self, rows, nJ_max, nM_max):
         self.rows, self.nJ_max, self.nM_max = rows, nJ_max, nM_max
@@ -2370,8 +2441,8 @@ class _Bucket:
         index = [self.rows] + [slice(None)] * (src.dim() - 1)
         if nJ is not None:
             index[nJ] = slice(0, self.nJ_max)
-        if nM is not None:
-            index[nM] = slice(0, self.nM_max)
+        for axis in (() if nM is None else nM if isinstance(nM, tuple) else (nM,)):
+            index[axis] = slice(0, self.nM_max)
         dst[tuple(index)] = src
 
 
@@ -2690,6 +2761,102 @@ def solve_modes(trusses_or_packed, p=6, joint_mass=None, mass_scale=1.0, tol=1e-
             part.put(getattr(out, field), res[key])
     out.omega = out.eigenvalue.sqrt()
     return out if on_device else _host_result(torch, dev, out)
+
+
+@dataclass
+class MemberLossResult:
+    """Results of `solve_member_loss`.  The intact truss: displace/external [B, L, nJ_max, 3], internal [B, L, nM_max] (as
+    `LoadCaseResult`).  Per removed member e: redundancy [B, nM_max] (r_e in [0, 1]; the r of a truss sum to its degree
+    of statical indeterminacy nM - n_free), critical [B, nM_max] (bool: r_e <= r_tol - without e the truss is a
+    mechanism), and per load case peak_stress, peak_displace [B, L, nM_max] (the largest |N'| / A among the surviving
+    members and the largest joint displacement after the removal; +inf for a critical member) with peak_member,
+    peak_joint [B, L, nM_max] (where: member id, caller's joint id; -1 where there is none), internal_after
+    [B, L, nM_max, nM_max] (`want_forces`, else None: row e the member forces without e, NaN for a critical member).
+    Padding members: zeros, ids -1.  info [B]: the factorisation's status - a truss with info != 0 has meaningless
+    numbers, the others are unaffected."""
+    displace: np.ndarray
+    external: np.ndarray
+    internal: np.ndarray
+    redundancy: np.ndarray
+    critical: np.ndarray
+    peak_stress: np.ndarray
+    peak_member: np.ndarray
+    peak_displace: np.ndarray
+    peak_joint: np.ndarray
+    internal_after: np.ndarray
+    info: np.ndarray
+
+
+def _check_member_loss_args(packed, loads, r_tol, sections, want_forces=False, max_result_bytes=4 << 30, chunk=64):
+    """The argument errors of `solve_member_loss` that need no device.  Returns the loads as a contiguous float64 host
+    array [B, L, nJ_max, 3] (`loads=None`: the batch's own loads as one case)."""
+    if sections is not None:
+        raise ValueError("solve_member_loss: sections= variants cannot be combined with the member-loss analysis")
+    if isinstance(r_tol, bool) or not isinstance(r_tol, (int, float, np.floating)) or not 0.0 < float(r_tol) < 1.0:
+        raise ValueError(f"solve_member_loss: r_tol must lie in (0, 1), got {r_tol!r}")
+    if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
+        raise ValueError(f"solve_member_loss: chunk must be an integer of at least 1, got {chunk!r}")
+    B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
+    if loads is None:
+        x = np.asarray(packed.loads, dtype=np.float64)[:, None]
+    else:
+        if not isinstance(loads, np.ndarray) and hasattr(loads, "detach"):
+            loads = loads.detach().cpu().numpy()
+        x = np.asarray(loads, dtype=np.float64)
+    shape = tuple(x.shape)
+    if len(shape) != 4 or shape[0] != B or shape[2] != nJ_max or shape[3] not in (2, 3):
+        raise ValueError(f"solve_member_loss: loads must be [B={B}, L, nJ_max={nJ_max}, 2 or 3], got {shape}")
+    if not np.isfinite(x).all():
+        raise ValueError("solve_member_loss: loads has a non-finite entry")
+    if shape[3] == 2:
+        x = np.concatenate([x, np.zeros(shape[:3] + (1,))], axis=-1)
+    if want_forces and B * shape[1] * nM_max * nM_max * 8 > max_result_bytes:
+        raise ValueError(f"solve_member_loss: internal_after [B={B}, L={shape[1]}, {nM_max}, {nM_max}] takes "
+                         f"{B * shape[1] * nM_max * nM_max * 8} bytes, more than max_result_bytes = {max_result_bytes}")
+    return np.ascontiguousarray(x)
+
+
+def solve_member_loss(trusses_or_packed, loads=None, r_tol=MEMBER_LOSS_R_TOL, want_forces=False, device=None,
+                      reorder=False, options=None, max_slab_bytes=64 << 30, on_device=False, sections=None,
+                      use_envelope=True, chunk=64, max_result_bytes=4 << 30):
+    """Robustness screening: what the loss of any ONE member does to every truss of a batch - whether it is still stable,
+    and the worst member stress and joint displacement afterwards under each of L load cases - from ONE factorisation
+    per truss.  Removing member e changes K_ff by the rank-one term k_e b_e b_e^T, so one more substitution column
+    z_e = inv(K_ff) b_e per member gives everything exactly: the redundancy r_e = 1 - k_e b_e . z_e (r_e <= `r_tol`: the
+    member is critical), and with alpha = N_e / r_e the state u + alpha z_e, N_m + alpha k_m b_m . z_e after the removal
+    (`DeviceBatch.member_loss`, include/trs_loss.h).  `loads`: [B, L, nJ_max, dim] (numpy or torch, caller's joint
+    numbering; dim 2 or 3), or None for the batch's own loads as one case.  `want_forces`: also the member forces after
+    every removal, [B, L, nM_max, nM_max] - refused above `max_result_bytes`.  Buckets, member forms, `reorder` plans,
+    `options`, `on_device` and `use_envelope` as `solve_load_cases`; `chunk`: members per substitution (`member_loss`; its
+    buffer of B * chunk * rows doubles per bucket comes on top of `max_slab_bytes`).  `sections=` variants, non-finite
+    loads, an `r_tol` outside (0, 1) and a `chunk` below 1 raise ValueError before any device work.  Returns a `MemberLossResult`."""
+    packed = _as_packed(trusses_or_packed)
+    loads = _check_member_loss_args(packed, loads, r_tol, sections, want_forces, max_result_bytes, chunk)
+    torch, dev = _require_gpu(device)
+    B, L, nJ_max, nM_max = packed.B, int(loads.shape[1]), packed.nJ_max, packed.nM_max
+    loads = _device_f64(torch, dev, loads)
+    full = lambda shape, value=0.0, dtype=torch.float64: torch.full(shape, value, dtype=dtype, device=dev)
+    i32 = torch.int32
+    out = MemberLossResult(full([B, L, nJ_max, 3]), full([B, L, nJ_max, 3]), full([B, L, nM_max]), full([B, nM_max]),
+                           full([B, nM_max], 0, i32), full([B, L, nM_max]), full([B, L, nM_max], -1, i32),
+                           full([B, L, nM_max]), full([B, L, nM_max], -1, i32),
+                           full([B, L, nM_max, nM_max]) if want_forces else None, full([B], 0, i32))
+    fields = (("displace", "u", dict(nJ=2)), ("external", "f_ext", dict(nJ=2)), ("internal", "N", dict(nM=2)),
+              ("redundancy", "r", dict(nM=1)), ("critical", "critical", dict(nM=1)),
+              ("peak_stress", "peak_stress", dict(nM=2)), ("peak_member", "peak_member", dict(nM=2)),
+              ("peak_displace", "peak_displace", dict(nM=2)), ("peak_joint", "peak_joint", dict(nM=2)))
+    for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope, cases=L):
+        res = db.member_loss(part.cut(loads, nJ=2), r_tol=r_tol, want_forces=want_forces, chunk=chunk,
+                             max_result_bytes=max_result_bytes)
+        for field, key, axes in fields:
+            part.put(getattr(out, field), res[key], **axes)
+        if want_forces:
+            part.put(out.internal_after, res["N_after"], nM=(2, 3))
+    out.critical = out.critical != 0
+    if on_device:
+        return out
+    torch.cuda.synchronize(dev)
+    return MemberLossResult(**{k: None if v is None else v.cpu().numpy() for k, v in vars(out).items()})
 
 
 def _is_pinned(packed):

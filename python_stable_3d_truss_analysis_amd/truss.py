@@ -445,6 +445,60 @@ class Truss:
         shapes = [dict(zip(range(nJ), result.shape[0, k, :nJ, :dim].copy())) for k in range(count)]
         return omega, shapes
 
+    def MemberLoss(self, cases=None, rTol=None, returnForces=False):
+        """What the loss of any ONE member does to this truss, for every member and every load case, from ONE
+        factorisation (`batch.solve_member_loss`): `cases` is a list of `{jointID: vector}` dicts as `SolveLoadCases`
+        takes them (None: the truss's own forces as one case).  Returns a list, one entry per case, of
+        `{memberID: record}`; a record holds
+          "redundancy"   r_e in [0, 1] (the same in every case; over the truss they sum to its degree of indeterminacy),
+          "critical"     True when r_e <= `rTol` (default `batch.MEMBER_LOSS_R_TOL`): without the member the truss is a
+                         mechanism - the peaks are then inf and their ids None,
+          "peakStress", "peakStressMember"           the largest |N| / a among the surviving members, and where,
+          "peakDisplacement", "peakDisplacementJoint"  the largest joint displacement, and where,
+          "forces"       (`returnForces`) {memberID: N} after the removal, entries below 1e-10 dropped like the other
+                         results (None for a critical member).
+        The truss's loads, its solved state and its results stay as they are.  Raises `TrussNotStableError` when the
+        counting test fails and `numpy.linalg.LinAlgError` when the reduced stiffness matrix is not positive definite,
+        as `Solve()` does."""
+        if not self.isStable:
+            raise TrussNotStableError("The truss is not stable !")
+        from .batch import MEMBER_LOSS_R_TOL, pack_trusses, solve_member_loss  # late import, as the other solvers
+        packed = pack_trusses([self])
+        nM = len(self._bars)
+        loads = None
+        if cases is not None:
+            cases = list(cases)
+            if not cases:
+                return []
+            loads = np.zeros([1, len(cases), packed.nJ_max, 3])
+            for k, case in enumerate(cases):
+                probe = Truss(self._dim).LoadFromJSON(data=dict(self.Serialize(), force=[]))
+                for jointID, vector in case.items():
+                    probe.AddExternalForce(jointID, vector)
+                for j, v in probe._loads.items():
+                    loads[0, k, j, :self._dim] = v
+        result = solve_member_loss(packed, loads, r_tol=MEMBER_LOSS_R_TOL if rTol is None else rTol,
+                                   want_forces=returnForces)
+        if int(result.info[0]) != 0:
+            raise np.linalg.LinAlgError("Singular matrix")
+        out = []
+        for k in range(result.peak_stress.shape[1]):
+            records = {}
+            for e in range(nM):
+                critical = bool(result.critical[0, e])
+                rec = {"redundancy": float(result.redundancy[0, e]), "critical": critical,
+                       "peakStress": float(result.peak_stress[0, k, e]),
+                       "peakStressMember": None if result.peak_member[0, k, e] < 0 else int(result.peak_member[0, k, e]),
+                       "peakDisplacement": float(result.peak_displace[0, k, e]),
+                       "peakDisplacementJoint": None if result.peak_joint[0, k, e] < 0 else int(result.peak_joint[0, k, e])}
+                if returnForces:
+                    n = result.internal_after[0, k, e, :nM]
+                    rec["forces"] = None if critical else \
+                        {int(m): float(n[m]) for m in np.flatnonzero(np.abs(n) >= ZERO_EPS)}
+                records[e] = rec
+            out.append(records)
+        return out
+
     def AdoptDenseResults(self, displace, external, internal):
         """Install dense results (`[nJoint, dim]`, `[nJoint, dim]`, `[nMember]`) as the
         sparse result dicts of the reference: entries below 1e-10 in every component are
