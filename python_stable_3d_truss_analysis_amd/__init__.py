@@ -38,14 +38,15 @@ __all__ = ["Truss", "Member", "MemberType", "SupportType", "MetapathType", "Task
            "solve_load_cases", "LoadCaseResult", "load_cases_from_json",
            "solve_gradients", "GradientResult", "DifferentiableTruss",
            "solve_modes", "ModeResult", "solve_effect_cases", "EffectCaseResult", "LoadCase",
-           "solve_member_loss", "MemberLossResult"]
+           "solve_member_loss", "MemberLossResult", "solve_influence", "InfluenceResult"]
 
 
 def __getattr__(name):
     # torch-dependent names are resolved lazily so that the model imports without torch
     if name in ("solve_batch", "pack_trusses", "PackedBatch", "BatchResult", "RaggedSolver", "DeviceBatch",
                 "solve_load_cases", "LoadCaseResult", "solve_gradients", "GradientResult", "solve_modes", "ModeResult",
-                "solve_effect_cases", "EffectCaseResult", "solve_member_loss", "MemberLossResult"):
+                "solve_effect_cases", "EffectCaseResult", "solve_member_loss", "MemberLossResult", "solve_influence",
+                "InfluenceResult"):
         from . import batch
         return getattr(batch, name)
     if name == "DifferentiableTruss":

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h` and `include/trs_loss.h` (library: `libtrs_hip.so`, in-tree).
+"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h` and `include/trs_influence.h` (library: `libtrs_hip.so`, in-tree).
 
 There is no fallback: if the library is missing, `load()` raises `HipExtensionError`.
 """
@@ -113,6 +113,17 @@ LOSS_SIGNATURES = {
                                 _P, _P, _P, _P]),
 }
 
+#: every symbol `include/trs_influence.h` declares (influence lines and moving-load envelopes; csrc/influence.hip, the
+#: same library)
+INFLUENCE_SIGNATURES = {
+    "trs_influence_abi_version": (_I, []),
+    "trs_influence_fits": (_I, [_I, _I, _I]),
+    "trs_influence_apply": (_I, [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P,
+                                 _P, _P, _P, _P, _P, _P, _P, _P]),
+    "trs_influence_tab_apply": (_I, [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I,
+                                     _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+}
+
 #: must equal TRS_ABI_VERSION of include/trs_solver.h
 ABI_VERSION = 10
 #: must equal TRS_MODES_ABI_VERSION of include/trs_modes.h
@@ -121,6 +132,8 @@ MODES_ABI_VERSION = 1
 EFFECTS_ABI_VERSION = 1
 #: must equal TRS_LOSS_ABI_VERSION of include/trs_loss.h
 LOSS_ABI_VERSION = 1
+#: must equal TRS_INFLUENCE_ABI_VERSION of include/trs_influence.h
+INFLUENCE_ABI_VERSION = 1
 #: TRS_MODES_BLOCK of include/trs_modes.h: vectors per truss of the block iteration (one case group)
 MODES_BLOCK = 16
 
@@ -162,13 +175,14 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as exc:
         raise HipExtensionError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for table in (SIGNATURES, MODES_SIGNATURES, EFFECTS_SIGNATURES, LOSS_SIGNATURES):
+    for table in (SIGNATURES, MODES_SIGNATURES, EFFECTS_SIGNATURES, LOSS_SIGNATURES, INFLUENCE_SIGNATURES):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype = restype
             fn.argtypes = argtypes
     if lib.trs_abi_version() != ABI_VERSION or lib.trs_modes_abi_version() != MODES_ABI_VERSION \
-            or lib.trs_effects_abi_version() != EFFECTS_ABI_VERSION or lib.trs_loss_abi_version() != LOSS_ABI_VERSION:
+            or lib.trs_effects_abi_version() != EFFECTS_ABI_VERSION or lib.trs_loss_abi_version() != LOSS_ABI_VERSION \
+            or lib.trs_influence_abi_version() != INFLUENCE_ABI_VERSION:
         raise HipExtensionError("libtrs_hip.so ABI version mismatch")
     _lib = lib
     return lib

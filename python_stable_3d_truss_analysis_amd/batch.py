@@ -1066,6 +1066,72 @@ class DeviceBatch:
                             f"trs_loss{tab}_apply")
         return out
 
+    # -- influence lines and moving-load envelopes from the resident factor (include/trs_influence.h) ------------------
+    def influence(self, path, path_len, direction, train_w, train_o, want_lines=False, chunk=64, out=None):
+        """The influence lines of every member force along a path of joints, and the envelope of a load train that
+        crosses it, on the resident factor (`factor()` first): k_m inv(K_ff) b_m,f - the column the member-loss analysis
+        forms - is the influence line of N_m for a unit load at every joint at once (include/trs_influence.h).  `path`:
+        int32 device tensor [B, P_max] of joint ids in the CALLER's numbering, `path_len` int32 [B] (entries of `path`
+        at or beyond it are ignored), `direction` float64 [B, 3] (the load vector per unit axle weight), `train_w`,
+        `train_o` float64 [A] (axle weights, and offsets behind the lead axle ascending from 0) - the caller validates
+        them (`solve_influence` does).  The members are taken `chunk` at a time (rounded up to a multiple of 16, one case
+        group of the substitution): `trs_loss_rhs`, `trs_potrs_cases`, `trs_influence_apply`, on a buffer
+        [B, chunk, rows] of this method's own (allocated per call, beside the slab).  Returns a dict of device tensors
+        [B, nM_max]: N_max, N_min (the extremes of the train's response), x_max, x_min (the lead axle's arc positions
+        that attain them; NaN for a padding member or an empty path), area_pos, area_neg (the integrals of the positive
+        and the negative part of the line) and - `want_lines` - eta [B, nM_max, P_max], the ordinates at the path joints.
+        `out`: such a dict to write into.  Nothing else of the batch changes: `cases_F`, `generation` and the forward
+        state that `adjoint_cases` differentiates stay as they are."""
+        t = self.torch
+        self._need_factor("influence")
+        B, nJ_max, nM_max = self.B, self.nJ_max, self.nM_max
+
+        def need(x, name, shape, dtype):
+            if x.dim() != len(shape) or any(s is not None and int(x.shape[i]) != s for i, s in enumerate(shape)) \
+                    or x.dtype != dtype or x.device != self.device:
+                raise ValueError(f"influence(): {name} must be {dtype} {['any' if s is None else s for s in shape]} "
+                                 f"on {self.device}")
+            return x.contiguous()
+
+        path = need(path, "path", [B, None], t.int32)
+        path_len = need(path_len, "path_len", [B], t.int32)
+        direction = need(direction, "direction", [B, 3], t.float64)
+        train_w = need(train_w, "train_w", [None], t.float64)
+        train_o = need(train_o, "train_o", [int(train_w.shape[0])], t.float64)
+        P_max, A = int(path.shape[1]), int(train_w.shape[0])
+        if A < 1:
+            raise ValueError("influence(): the train has no axle")
+        if int(chunk) < 1:
+            raise ValueError(f"influence(): chunk must be at least 1, got {chunk!r}")
+        shapes = {k: [B, nM_max] for k in ("N_max", "N_min", "x_max", "x_min", "area_pos", "area_neg")}
+        if want_lines:
+            shapes["eta"] = [B, nM_max, P_max]
+        out = self._out_tensors("influence", shapes, out)
+        if not self.lib.trs_influence_fits(nJ_max, P_max, A):
+            raise HipExtensionError(f"influence(): a path of {P_max} joints with {A} axles on a truss of {nJ_max} joints "
+                                    "exceeds the LDS of the apply kernel (trs_influence_fits)")
+        if B == 0 or nM_max == 0:
+            return out
+        C = min(-(-int(chunk) // 16) * 16, -(-nM_max // 16) * 16)
+        # the chunk's columns: B * C * rows doubles beside the slab, as `member_loss` takes them
+        Z = t.empty([B, C, self.rows], dtype=t.float64, device=self.device)
+        jo, stream, tab = self._case_launch()
+        rhs, apply = getattr(self.lib, f"trs_loss{tab}_rhs"), getattr(self.lib, f"trs_influence{tab}_apply")
+        with t.cuda.device(self.device):
+            for e0 in range(0, nM_max, C):
+                _capi.check(rhs(B, e0, C, nJ_max, nM_max, self.xyz.data_ptr(), *self._members(),
+                                self.free_index.data_ptr(), self.n_free.data_ptr(), self.nM.data_ptr(), Z.data_ptr(),
+                                self.rows, stream), f"trs_loss{tab}_rhs")
+                self._potrs_cases(Z, C)
+                _capi.check(apply(B, e0, C, nJ_max, nM_max, P_max, A, self.xyz.data_ptr(), *self._members(),
+                                  self.free_index.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), path.data_ptr(),
+                                  path_len.data_ptr(), direction.data_ptr(), train_w.data_ptr(), train_o.data_ptr(),
+                                  Z.data_ptr(), self.rows, _ptr(out.get("eta")), out["N_max"].data_ptr(),
+                                  out["N_min"].data_ptr(), out["x_max"].data_ptr(), out["x_min"].data_ptr(),
+                                  out["area_pos"].data_ptr(), out["area_neg"].data_ptr(), jo, stream),
+                            f"trs_influence{tab}_apply")
+        return out
+
     # -- natural frequencies and mode shapes from the resident factor (include/trs_modes.h) ------------------
     def modes(self, p, tol=1e-10, max_iters=256, check_every=8, joint_mass=None, mass_scale=1.0, out=None):
         """The `p` lowest pairs of K_ff phi = lambda M phi of every truss (M: lumped mass, include/trs_modes.h) by block
@@ -2857,6 +2923,136 @@ def solve_member_loss(trusses_or_packed, loads=None, r_tol=MEMBER_LOSS_R_TOL, wa
         return out
     torch.cuda.synchronize(dev)
     return MemberLossResult(**{k: None if v is None else v.cpu().numpy() for k, v in vars(out).items()})
+
+
+@dataclass
+class InfluenceResult:
+    """Results of `solve_influence`, per member [B, nM_max]: N_max, N_min (the largest and the smallest force the load
+    train puts into the member as it crosses the path), x_max, x_min (the arc positions of the lead axle that attain
+    them; NaN for a padding member or an empty path), area_pos, area_neg (the integrals of the positive and the negative
+    part of the influence line over the path: times a line load, the extremes under a uniform live load); lines
+    [B, nM_max, P_max] (`want_lines`, else None: the influence ordinates at the path joints, zero past a truss's path).
+    Padding members: zeros.  info [B]: the factorisation's status - a truss with info != 0 has meaningless numbers, the
+    others are unaffected."""
+    N_max: np.ndarray
+    N_min: np.ndarray
+    x_max: np.ndarray
+    x_min: np.ndarray
+    area_pos: np.ndarray
+    area_neg: np.ndarray
+    lines: np.ndarray
+    info: np.ndarray
+
+
+def _host_array(x, dtype):
+    if not isinstance(x, np.ndarray) and hasattr(x, "detach"):
+        x = x.detach().cpu().numpy()
+    return np.asarray(x, dtype=dtype)
+
+
+def _check_influence_args(packed, path, direction, train, sections, want_lines=False, max_result_bytes=4 << 30, chunk=64):
+    """The argument errors of `solve_influence` that need no device (the last one needs the library).  Returns host
+    arrays: path int32 [B, P_max] (-1 padding), path_len int32 [B], direction float64 [B, 3], train_w, train_o [A]."""
+    if sections is not None:
+        raise ValueError("solve_influence: sections= variants cannot be combined with the influence analysis")
+    if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
+        raise ValueError(f"solve_influence: chunk must be an integer of at least 1, got {chunk!r}")
+    B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
+    # the path: a list of joint-id lists, or [B, P_max] with -1 padding
+    if isinstance(path, (list, tuple)) and all(isinstance(row, (list, tuple)) for row in path):
+        rows = [[int(j) for j in row] for row in path]
+        if len(rows) != B:
+            raise ValueError(f"solve_influence: path must hold one list of joints per truss (B={B}), got {len(rows)}")
+        dense = np.full([B, max([len(r) for r in rows], default=0)], -1, dtype=np.int64)
+        for b, row in enumerate(rows):
+            if any(j < 0 for j in row):
+                raise ValueError(f"solve_influence: path of truss {b} names a joint out of range")
+            dense[b, :len(row)] = row
+    else:
+        raw = _host_array(path, None)
+        if raw.ndim != 2 or raw.shape[0] != B or raw.dtype.kind not in "iu":
+            raise ValueError(f"solve_influence: path must be a list of joint-id lists or an integer array [B={B}, P_max]")
+        dense = raw.astype(np.int64)
+    P_max = int(dense.shape[1])
+    path_len = (dense >= 0).sum(axis=1).astype(np.int32)
+    nJ = np.asarray(packed.nJ, dtype=np.int64)
+    for b in range(B):
+        row = dense[b, :path_len[b]]
+        if (dense[b, path_len[b]:] != -1).any() or (row < 0).any() or (row >= nJ[b]).any():
+            raise ValueError(f"solve_influence: path of truss {b} names a joint out of range (joints 0 .. {int(nJ[b]) - 1}, "
+                             "-1 padding at the end only)")
+        pos = np.asarray(packed.xyz, dtype=np.float64)[b, row]
+        if len(row) > 1 and (pos[1:] == pos[:-1]).all(axis=1).any():
+            raise ValueError(f"solve_influence: two consecutive path joints of truss {b} lie at the same position")
+    # the load vector
+    d = _host_array(direction, np.float64)
+    if d.shape not in ((2,), (3,), (B, 2), (B, 3)):
+        raise ValueError(f"solve_influence: direction must be [3], [2], [B={B}, 3] or [B, 2], got {d.shape}")
+    if not np.isfinite(d).all():
+        raise ValueError("solve_influence: direction has a non-finite entry")
+    d = np.broadcast_to(d, (B, d.shape[-1]))
+    d = np.ascontiguousarray(np.concatenate([d, np.zeros([B, 3 - d.shape[-1]])], axis=1))
+    # the train
+    pairs = [(1.0, 0.0)] if train is None else [tuple(ax) for ax in train]
+    if not pairs:
+        raise ValueError("solve_influence: the train has no axle")
+    if any(len(ax) != 2 for ax in pairs):
+        raise ValueError("solve_influence: train must be a list of (weight, offset) pairs")
+    w = np.array([float(ax[0]) for ax in pairs])
+    o = np.array([float(ax[1]) for ax in pairs])
+    if not (np.isfinite(w).all() and np.isfinite(o).all()):
+        raise ValueError("solve_influence: train has a non-finite entry")
+    if o[0] != 0.0 or (np.diff(o) < 0.0).any():
+        raise ValueError("solve_influence: the axle offsets must ascend from 0 (the lead axle first)")
+    if want_lines and B * nM_max * P_max * 8 > max_result_bytes:
+        raise ValueError(f"solve_influence: lines [B={B}, {nM_max}, {P_max}] takes {B * nM_max * P_max * 8} bytes, more "
+                         f"than max_result_bytes = {max_result_bytes}")
+    if not _capi.load().trs_influence_fits(nJ_max, P_max, len(w)):
+        raise ValueError(f"solve_influence: a path of {P_max} joints with {len(w)} axles on trusses of up to {nJ_max} "
+                         "joints exceeds the LDS of the apply kernel (trs_influence_fits)")
+    return np.ascontiguousarray(dense, dtype=np.int32), path_len, d, w, o
+
+
+def solve_influence(trusses_or_packed, path, direction, train=None, want_lines=False, device=None, reorder=False,
+                    options=None, max_slab_bytes=64 << 30, on_device=False, sections=None, use_envelope=True, chunk=64,
+                    max_result_bytes=4 << 30):
+    """Moving loads: the worst force a load train can put into every member of every truss of a batch as it crosses a
+    path of joints - a vehicle on a bridge deck, a crane on a runway girder - from ONE factorisation per truss.  For
+    member m the column z_m = inv(K_ff) b_m,f (the one the member-loss analysis forms) gives N_m = k_m z_m . f for ANY
+    load f, so k_m z_m read along the path IS the influence line of N_m; the train is swept over it exactly - the
+    extremes of a piecewise linear response lie where some axle stands on a path joint (`DeviceBatch.influence`,
+    include/trs_influence.h).  `path`: a list of joint-id lists, one per truss, or [B, P_max] with -1 padding
+    (caller's numbering; consecutive joints at distinct positions, a joint may recur); `direction`: the load vector per
+    unit axle weight, [3], [2], [B, 3] or [B, 2]; `train`: a list of (weight, offset) pairs, the offsets behind the lead
+    axle ascending from 0 (None: one unit axle - the envelope is then the extreme ordinate).  An axle between two path
+    joints is shared between them by the lever rule; an axle off the path loads nothing.  `want_lines`: also the
+    ordinates at the path joints, [B, nM_max, P_max] - refused above `max_result_bytes`.  Buckets, member forms,
+    `reorder` plans, `options`, `on_device`, `use_envelope` and `chunk` as `solve_member_loss`.  `sections=` variants, a
+    path joint out of range, two consecutive path joints at one position, a non-finite value, offsets that do not ascend
+    from 0, an empty train and a shape `trs_influence_fits` refuses raise ValueError before any device work.  Returns an
+    `InfluenceResult`."""
+    packed = _as_packed(trusses_or_packed)
+    path, path_len, d, w, o = _check_influence_args(packed, path, direction, train, sections, want_lines,
+                                                    max_result_bytes, chunk)
+    torch, dev = _require_gpu(device)
+    B, nM_max, P_max = packed.B, packed.nM_max, int(path.shape[1])
+    up = lambda a: torch.from_numpy(a).to(dev)
+    path, path_len, d, w, o = up(path), up(path_len), up(d), up(w), up(o)
+    full = lambda shape, value=0.0, dtype=torch.float64: torch.full(shape, value, dtype=dtype, device=dev)
+    nan = float("nan")
+    out = InfluenceResult(full([B, nM_max]), full([B, nM_max]), full([B, nM_max], nan), full([B, nM_max], nan),
+                          full([B, nM_max]), full([B, nM_max]), full([B, nM_max, P_max]) if want_lines else None,
+                          full([B], 0, torch.int32))
+    for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope, cases=1):
+        res = db.influence(part.cut(path), part.cut(path_len), part.cut(d), w, o, want_lines=want_lines, chunk=chunk)
+        for key in ("N_max", "N_min", "x_max", "x_min", "area_pos", "area_neg"):
+            part.put(getattr(out, key), res[key], nM=1)
+        if want_lines:
+            part.put(out.lines, res["eta"], nM=1)
+    if on_device:
+        return out
+    torch.cuda.synchronize(dev)
+    return InfluenceResult(**{k: None if v is None else v.cpu().numpy() for k, v in vars(out).items()})
 
 
 def _is_pinned(packed):

@@ -499,6 +499,40 @@ class Truss:
             out.append(records)
         return out
 
+    def InfluenceLines(self, path, direction, train=None, returnLines=False):
+        """Moving loads: the influence lines of every member force along `path` (a list of joint IDs, consecutive ones at
+        distinct positions) for a load `direction` (a vector per unit axle weight), and the envelope of a load `train`
+        - a list of (weight, offset) pairs, the offsets behind the lead axle ascending from 0; None: one unit axle -
+        that crosses the path, from ONE factorisation (`batch.solve_influence`).  Returns `{memberID: record}`; a record
+        holds
+          "max", "maxAt"   the largest member force any position of the train gives, and the arc position of the lead
+                           axle (measured along the path from its first joint) that gives it,
+          "min", "minAt"   the smallest, and where (the positions are None for an empty path),
+          "areaPositive", "areaNegative"   the integrals of the positive and of the negative part of the influence line
+                           along the path (times a line load: the extremes under a uniform live load),
+          "ordinates"      (`returnLines`) the influence ordinates at the path joints, a list over `path`.
+        The truss's loads, its solved state and its results stay as they are.  Raises `TrussNotStableError` when the
+        counting test fails and `numpy.linalg.LinAlgError` when the reduced stiffness matrix is not positive definite,
+        as `Solve()` does."""
+        if not self.isStable:
+            raise TrussNotStableError("The truss is not stable !")
+        from .batch import pack_trusses, solve_influence  # late import, as the other solvers
+        path = [int(j) for j in path]
+        result = solve_influence(pack_trusses([self]), [path], np.asarray(direction, dtype=float), train=train,
+                                 want_lines=returnLines)
+        if int(result.info[0]) != 0:
+            raise np.linalg.LinAlgError("Singular matrix")
+        at = lambda x: None if math.isnan(x) else float(x)
+        records = {}
+        for m in range(len(self._bars)):
+            rec = {"max": float(result.N_max[0, m]), "maxAt": at(result.x_max[0, m]),
+                   "min": float(result.N_min[0, m]), "minAt": at(result.x_min[0, m]),
+                   "areaPositive": float(result.area_pos[0, m]), "areaNegative": float(result.area_neg[0, m])}
+            if returnLines:
+                rec["ordinates"] = [float(v) for v in result.lines[0, m, :len(path)]]
+            records[m] = rec
+        return records
+
     def AdoptDenseResults(self, displace, external, internal):
         """Install dense results (`[nJoint, dim]`, `[nJoint, dim]`, `[nMember]`) as the
         sparse result dicts of the reference: entries below 1e-10 in every component are
