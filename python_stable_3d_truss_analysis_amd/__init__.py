@@ -38,7 +38,8 @@ __all__ = ["Truss", "Member", "MemberType", "SupportType", "MetapathType", "Task
            "solve_load_cases", "LoadCaseResult", "load_cases_from_json",
            "solve_gradients", "GradientResult", "DifferentiableTruss",
            "solve_modes", "ModeResult", "solve_effect_cases", "EffectCaseResult", "LoadCase",
-           "solve_member_loss", "MemberLossResult", "solve_influence", "InfluenceResult"]
+           "solve_member_loss", "MemberLossResult", "solve_influence", "InfluenceResult",
+           "solve_member_sets", "MemberSetResult"]
 
 
 def __getattr__(name):
@@ -46,7 +47,7 @@ def __getattr__(name):
     if name in ("solve_batch", "pack_trusses", "PackedBatch", "BatchResult", "RaggedSolver", "DeviceBatch",
                 "solve_load_cases", "LoadCaseResult", "solve_gradients", "GradientResult", "solve_modes", "ModeResult",
                 "solve_effect_cases", "EffectCaseResult", "solve_member_loss", "MemberLossResult", "solve_influence",
-                "InfluenceResult"):
+                "InfluenceResult", "solve_member_sets", "MemberSetResult"):
         from . import batch
         return getattr(batch, name)
     if name == "DifferentiableTruss":

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h` and `include/trs_influence.h` (library: `libtrs_hip.so`, in-tree).
+"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h`, `include/trs_influence.h` and `include/trs_sets.h` (library: `libtrs_hip.so`, in-tree).
 
 There is no fallback: if the library is missing, `load()` raises `HipExtensionError`.
 """
@@ -124,6 +124,19 @@ INFLUENCE_SIGNATURES = {
                                      _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
+#: every symbol `include/trs_sets.h` declares (member-set scenarios: up to eight members removed or resized at once;
+#: csrc/sets.hip, the same library)
+SETS_SIGNATURES = {
+    "trs_sets_abi_version": (_I, []),
+    "trs_sets_fits": (_I, [_I, _I, _I]),
+    "trs_sets_rhs": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "trs_sets_tab_rhs": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "trs_sets_apply": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _D, _P, _P,
+                            _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "trs_sets_tab_apply": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _D, _P,
+                                _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+}
+
 #: must equal TRS_ABI_VERSION of include/trs_solver.h
 ABI_VERSION = 10
 #: must equal TRS_MODES_ABI_VERSION of include/trs_modes.h
@@ -134,6 +147,10 @@ EFFECTS_ABI_VERSION = 1
 LOSS_ABI_VERSION = 1
 #: must equal TRS_INFLUENCE_ABI_VERSION of include/trs_influence.h
 INFLUENCE_ABI_VERSION = 1
+#: must equal TRS_SETS_ABI_VERSION of include/trs_sets.h
+SETS_ABI_VERSION = 1
+#: TRS_SETS_MAX of include/trs_sets.h: members per scenario at most
+SETS_MAX = 8
 #: TRS_MODES_BLOCK of include/trs_modes.h: vectors per truss of the block iteration (one case group)
 MODES_BLOCK = 16
 
@@ -175,14 +192,16 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as exc:
         raise HipExtensionError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for table in (SIGNATURES, MODES_SIGNATURES, EFFECTS_SIGNATURES, LOSS_SIGNATURES, INFLUENCE_SIGNATURES):
+    for table in (SIGNATURES, MODES_SIGNATURES, EFFECTS_SIGNATURES, LOSS_SIGNATURES, INFLUENCE_SIGNATURES,
+                  SETS_SIGNATURES):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype = restype
             fn.argtypes = argtypes
     if lib.trs_abi_version() != ABI_VERSION or lib.trs_modes_abi_version() != MODES_ABI_VERSION \
             or lib.trs_effects_abi_version() != EFFECTS_ABI_VERSION or lib.trs_loss_abi_version() != LOSS_ABI_VERSION \
-            or lib.trs_influence_abi_version() != INFLUENCE_ABI_VERSION:
+            or lib.trs_influence_abi_version() != INFLUENCE_ABI_VERSION \
+            or lib.trs_sets_abi_version() != SETS_ABI_VERSION:
         raise HipExtensionError("libtrs_hip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -452,6 +452,120 @@ def joint_order_device(torch, tensors, effort=2, apply=True, want_choice=False, 
 #: `r_tol` of the member-loss analysis: a member whose redundancy r_e is at most this is critical.  Over the shipped
 #: fixtures the critical members have |r| <= a few 1e-15 and the others r >= 3.8e-4 (EXPERIMENTS R14).
 MEMBER_LOSS_R_TOL = 1e-8
+#: members per scenario of `member_sets` at most (TRS_SETS_MAX of include/trs_sets.h)
+MEMBER_SETS_MAX = _capi.SETS_MAX
+
+
+def _round_up16(x):
+    return -(-int(x) // 16) * 16
+
+
+def plan_member_sets(sets, chunk, nM_max=None):
+    """The ranges `DeviceBatch.member_sets` takes the scenario axis in.  `sets`: int array [B, S, K] of member ids, -1
+    padding at the end of a set; `chunk`: columns per substitution, rounded up to C, a multiple of 16 (and no more than
+    `nM_max` rounded up, when given).  The scenarios are taken in order into consecutive ranges [s0, s1), each as long
+    as every truss's DISTINCT members of the range number at most C - a member that several scenarios of a range share
+    costs one column - and a scenario is never split (it has at most C members: K <= C is required).  Returns a list of
+    (s0, s1, cols, slot): cols int32 [B, C], the members of the range in order of first appearance, -1 beyond them;
+    slot int32 [B, s1 - s0, K], the place in cols[b] of every member of every scenario, -1 where `sets` has -1.  Pure
+    numpy: no device is needed."""
+    sets = np.asarray(sets)
+    B, S, K = sets.shape
+    C = _round_up16(chunk)
+    if nM_max is not None:
+        C = max(16, min(C, _round_up16(nM_max)))
+    if K > C:
+        raise ValueError(f"plan_member_sets: a set of {K} members does not fit {C} columns")
+    width = int(sets.max(initial=-1)) + 1 if nM_max is None else int(nM_max)
+    rows = np.arange(B)[:, None]
+    valid = sets >= 0
+    safe = np.where(valid, sets, 0)
+    place = np.full([B, max(width, 1)], -1, dtype=np.int32)   # member -> its column in the open range
+    count = np.zeros([B], dtype=np.int64)
+    cols = np.full([B, C], -1, dtype=np.int32)
+    slot = np.full([B, S, K], -1, dtype=np.int32)
+    out, s0 = [], 0
+    for s in range(S):
+        fresh = valid[:, s] & (place[rows, safe[:, s]] < 0)
+        if s > s0 and (count + fresh.sum(axis=1) > C).any():
+            out.append((s0, s, cols, slot[:, s0:s]))
+            place[:], count[:], s0 = -1, 0, s
+            cols = np.full([B, C], -1, dtype=np.int32)
+            fresh = valid[:, s].copy()
+        where = (count[:, None] + np.cumsum(fresh, axis=1) - 1).astype(np.int32)
+        b_new, k_new = np.nonzero(fresh)
+        place[b_new, safe[b_new, s, k_new]] = where[b_new, k_new]
+        cols[b_new, where[b_new, k_new]] = safe[b_new, s, k_new]
+        count += fresh.sum(axis=1)
+        slot[:, s] = np.where(valid[:, s], place[rows, safe[:, s]], -1)
+    if S:
+        out.append((s0, S, cols, slot[:, s0:S]))
+    return out
+
+
+def _member_set_arrays(who, sets, gamma, B, nM, nM_max):
+    """`sets` and `gamma` of a member-set analysis as host arrays int32 / float64 [B, S, 8] (gamma None stays None), or
+    ValueError.  `sets`: an integer array [B, S, K <= 8] with -1 padding at the end of every set, or a list (per truss)
+    of lists (per scenario) of member ids - trusses with fewer scenarios get empty sets; `gamma` in the same form as
+    `sets`, entry for entry (its entries at the padding are ignored).  `nM` [B]: the member counts the ids are checked
+    against (None: `nM_max` for every truss)."""
+    nested = isinstance(sets, (list, tuple))
+    if nested:
+        if len(sets) != B or not all(isinstance(row, (list, tuple)) and all(isinstance(x, (list, tuple, np.ndarray))
+                                                                             for x in row) for row in sets):
+            raise ValueError(f"{who}: sets must hold one list of scenarios (lists of member ids) per truss (B={B})")
+        S = max([len(row) for row in sets], default=0)
+        if any(len(x) > MEMBER_SETS_MAX for row in sets for x in row):
+            raise ValueError(f"{who}: a set holds more than {MEMBER_SETS_MAX} members")
+        dense = np.full([B, S, MEMBER_SETS_MAX], -1, dtype=np.int64)
+        for b, row in enumerate(sets):
+            for i, x in enumerate(row):
+                x = np.asarray(x)
+                if x.size and x.dtype.kind not in "iu":
+                    raise ValueError(f"{who}: member ids must be integers")
+                if (x.astype(np.int64) < 0).any():
+                    raise ValueError(f"{who}: scenario {i} of truss {b} names a member out of range")
+                dense[b, i, :x.size] = x
+    else:
+        raw = _host_array(sets, None)
+        if raw.ndim != 3 or raw.shape[0] != B or raw.dtype.kind not in "iu":
+            raise ValueError(f"{who}: sets must be a list of lists of member-id lists or an integer array [B={B}, S, K]")
+        if raw.shape[2] > MEMBER_SETS_MAX:
+            raise ValueError(f"{who}: a set holds more than {MEMBER_SETS_MAX} members (K = {raw.shape[2]})")
+        dense = np.full(raw.shape[:2] + (MEMBER_SETS_MAX,), -1, dtype=np.int64)
+        dense[:, :, :raw.shape[2]] = raw
+    S = dense.shape[1]
+    valid = dense >= 0
+    limit = np.full([B], nM_max, dtype=np.int64) if nM is None else np.asarray(nM, dtype=np.int64)
+    if (dense < -1).any() or (dense >= limit[:, None, None]).any():
+        b, i = [int(v[0]) for v in np.nonzero((dense < -1) | (dense >= limit[:, None, None]))[:2]]
+        raise ValueError(f"{who}: scenario {i} of truss {b} names a member out of range (members 0 .. {int(limit[b]) - 1})")
+    if (valid[:, :, 1:] & ~valid[:, :, :-1]).any():
+        raise ValueError(f"{who}: -1 pads the END of a set only")
+    ordered = np.sort(dense, axis=2)
+    if ((ordered[:, :, 1:] == ordered[:, :, :-1]) & (ordered[:, :, 1:] >= 0)).any():
+        b, i = [int(v[0]) for v in np.nonzero((ordered[:, :, 1:] == ordered[:, :, :-1]) & (ordered[:, :, 1:] >= 0))[:2]]
+        raise ValueError(f"{who}: scenario {i} of truss {b} names a member twice")
+    if gamma is None:
+        return dense.astype(np.int32), None
+    g = np.zeros([B, S, MEMBER_SETS_MAX])
+    if isinstance(gamma, (list, tuple)) and nested:
+        if len(gamma) != B or any(len(grow) != len(row) or any(len(gx) != len(x) for gx, x in zip(grow, row))
+                                  for grow, row in zip(gamma, sets)):
+            raise ValueError(f"{who}: the factors must match the sets entry for entry")
+        for b, grow in enumerate(gamma):
+            for i, gx in enumerate(grow):
+                g[b, i, :len(gx)] = np.asarray(gx, dtype=np.float64)
+    else:
+        raw = _host_array(gamma, np.float64)
+        if nested or raw.ndim != 3 or raw.shape[:2] != (B, S) or raw.shape[2] > MEMBER_SETS_MAX \
+                or raw.shape[2] < int(valid.sum(axis=2).max(initial=0)):
+            raise ValueError(f"{who}: the factors must match the sets entry for entry ([B={B}, S={S}, K])")
+        g[:, :, :raw.shape[2]] = raw
+    g = np.where(valid, g, 0.0)
+    if not np.isfinite(g).all() or (g < 0.0).any():
+        raise ValueError(f"{who}: a factor is negative or not finite")
+    return dense.astype(np.int32), np.ascontiguousarray(g)
 
 
 def _ptr(x):
@@ -1064,6 +1178,88 @@ class DeviceBatch:
                                   out["peak_member"].data_ptr(), out["peak_displace"].data_ptr(),
                                   out["peak_joint"].data_ptr(), _ptr(out.get("N_after")), jo, stream),
                             f"trs_loss{tab}_apply")
+        return out
+
+    # -- member-set scenarios: up to eight members removed or resized at once (include/trs_sets.h) ------------------
+    def member_sets(self, loads, sets, gamma=None, r_tol=MEMBER_LOSS_R_TOL, want_forces=False, want_displace=False,
+                    chunk=64, out=None, max_result_bytes=4 << 30):
+        """What removing, damaging or strengthening up to eight members AT ONCE does to every truss, for S scenarios per
+        truss, on the resident factor (`factor()` first): a scenario changes K_ff by a term of rank k <= 8, so one
+        substitution column per DISTINCT member of a range of scenarios and one k x k elimination per scenario replace a
+        factorisation per scenario (include/trs_sets.h).  `loads`: float64 device tensor [B, L, nJ_max, 3] in the
+        CALLER's joint numbering, as `solve_cases` takes it.  `sets`: HOST integer array [B, S, K <= 8] of member ids,
+        -1 padding at the end of a set (an empty set gives the intact state), or the nested lists `solve_member_sets`
+        takes; `gamma`: HOST array of the same shape, the area factor of every named member (0 removed, below 1
+        damaged, above 1 strengthened, 1 unchanged), or None - every member removed.  They are host arrays because the
+        plan is made on the host (`plan_member_sets`): the scenario axis is cut into ranges whose distinct members per
+        truss fit `chunk` columns (rounded up to a multiple of 16, one case group of the substitution), and per range
+        `trs_sets_rhs`, `trs_potrs_cases` and `trs_sets_apply` run on a buffer [B, chunk, rows] of this method's own
+        (allocated per call, beside the slab).  The intact state comes from `solve_cases(loads)`.  Returns a dict of
+        device tensors: u, f_ext [B, L, nJ_max, 3] and N [B, L, nM_max] of the intact truss; pivot [B, S, 8] (the pivots
+        of the elimination in the set's order - for removals the redundancy of member j once the members before it are
+        gone; NaN beyond the set and after a failing position), unstable, first_unstable [B, S] (int32: some pivot
+        <= `r_tol` - the truss is a mechanism from that member of the set on - and its position, else -1); peak_stress,
+        peak_displace [B, L, S] (max |N'| / (gamma A) over the members that are not removed, max |u'| over the joints;
+        +inf for an unstable scenario) with peak_member, peak_joint (int32; caller's joint numbering, the lowest id on
+        a tie, -1 where there is none) and - `want_forces`, `want_displace` - N_after [B, L, S, nM_max] and u_after
+        [B, L, S, nJ_max, 3] (caller's joint numbering; NaN for an unstable scenario), together refused with ValueError
+        above `max_result_bytes`.  `out`: such a dict to write into.  `generation` is bumped by the `solve_cases`
+        inside and the forward state is that call's, exactly as after `member_loss`."""
+        t = self.torch
+        self._need_factor("member_sets")
+        if loads.dim() != 4 or tuple(loads.shape[:1]) + tuple(loads.shape[2:]) != (self.B, self.nJ_max, 3) \
+                or loads.dtype != t.float64 or loads.device != self.device:
+            raise ValueError(f"member_sets(): loads must be float64 [B={self.B}, L, nJ_max={self.nJ_max}, 3] on {self.device}")
+        if not 0.0 < float(r_tol) < 1.0:
+            raise ValueError(f"member_sets(): r_tol must lie in (0, 1), got {r_tol!r}")
+        if int(chunk) < 1:
+            raise ValueError(f"member_sets(): chunk must be at least 1, got {chunk!r}")
+        B, L, nJ_max, nM_max = self.B, int(loads.shape[1]), self.nJ_max, self.nM_max
+        sets, gamma = _member_set_arrays("member_sets()", sets, gamma, B, None, nM_max)
+        S = int(sets.shape[1])
+        extra = 8 * B * L * S * (nM_max * bool(want_forces) + 3 * nJ_max * bool(want_displace))
+        if extra > max_result_bytes:
+            raise ValueError(f"member_sets(): N_after / u_after of [B={B}, L={L}, S={S}] scenarios take {extra} bytes, "
+                             f"more than max_result_bytes = {max_result_bytes}")
+        i32 = t.int32
+        shapes = {"u": [B, L, nJ_max, 3], "f_ext": [B, L, nJ_max, 3], "N": [B, L, nM_max],
+                  "pivot": [B, S, MEMBER_SETS_MAX], "unstable": ([B, S], i32), "first_unstable": ([B, S], i32),
+                  "peak_stress": [B, L, S], "peak_member": ([B, L, S], i32), "peak_displace": [B, L, S],
+                  "peak_joint": ([B, L, S], i32)}
+        if want_forces:
+            shapes["N_after"] = [B, L, S, nM_max]
+        if want_displace:
+            shapes["u_after"] = [B, L, S, nJ_max, 3]
+        out = self._out_tensors("member_sets", shapes, out)
+        if B and L and not self.lib.trs_sets_fits(nJ_max, nM_max, L):
+            raise HipExtensionError(f"member_sets(): a truss of {nJ_max} joints / {nM_max} members exceeds the LDS of "
+                                    "the apply kernel (trs_sets_fits)")
+        self.solve_cases(loads, out={k: out[k] for k in ("u", "f_ext", "N")})
+        if B == 0 or L == 0 or S == 0:
+            return out
+        plan = plan_member_sets(sets, chunk, nM_max)
+        C = int(plan[0][2].shape[1])
+        # the range's columns: B * C * rows doubles beside the slab, as `member_loss` takes them
+        Z = t.empty([B, C, self.rows], dtype=t.float64, device=self.device)
+        jo, stream, tab = self._case_launch()
+        rhs, apply = getattr(self.lib, f"trs_sets{tab}_rhs"), getattr(self.lib, f"trs_sets{tab}_apply")
+        up = lambda a: t.from_numpy(np.ascontiguousarray(a)).to(self.device)
+        with t.cuda.device(self.device):
+            for s0, s1, cols, slot in plan:
+                cols, slot = up(cols), up(slot)
+                factors = None if gamma is None else up(gamma[:, s0:s1])
+                _capi.check(rhs(B, C, nJ_max, nM_max, self.xyz.data_ptr(), *self._members(), self.free_index.data_ptr(),
+                                self.n_free.data_ptr(), self.nM.data_ptr(), cols.data_ptr(), Z.data_ptr(), self.rows,
+                                stream), f"trs_sets{tab}_rhs")
+                self._potrs_cases(Z, C)
+                _capi.check(apply(B, L, S, s0, s1 - s0, C, nJ_max, nM_max, self.xyz.data_ptr(), *self._members(),
+                                  self.free_index.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), cols.data_ptr(),
+                                  slot.data_ptr(), _ptr(factors), Z.data_ptr(), self.cases_F.data_ptr(), self.rows,
+                                  float(r_tol), out["pivot"].data_ptr(), out["unstable"].data_ptr(),
+                                  out["first_unstable"].data_ptr(), out["peak_stress"].data_ptr(),
+                                  out["peak_member"].data_ptr(), out["peak_displace"].data_ptr(),
+                                  out["peak_joint"].data_ptr(), _ptr(out.get("N_after")), _ptr(out.get("u_after")), jo,
+                                  stream), f"trs_sets{tab}_apply")
         return out
 
     # -- influence lines and moving-load envelopes from the resident factor (include/trs_influence.h) ------------------
@@ -2523,6 +2719,7 @@ def _factored_buckets(packed, dev, info, max_slab_bytes, reorder, options, use_e
     for idx in size_buckets(packed, max_slab_bytes):
         sub = packed.take(idx).trimmed()
         part = _Bucket(torch.from_numpy(np.asarray(idx, dtype=np.int64)).to(dev), sub.nJ_max, sub.nM_max)
+        part.index = np.asarray(idx, dtype=np.int64)   # (the same places on the host: `solve_member_sets` plans there)
         db = DeviceBatch(sub, dev, use_envelope=use_envelope, use_small=False, reorder=reorder, options=options)
         db.factor()
         yield db, part
@@ -2923,6 +3120,105 @@ def solve_member_loss(trusses_or_packed, loads=None, r_tol=MEMBER_LOSS_R_TOL, wa
         return out
     torch.cuda.synchronize(dev)
     return MemberLossResult(**{k: None if v is None else v.cpu().numpy() for k, v in vars(out).items()})
+
+
+@dataclass
+class MemberSetResult:
+    """Results of `solve_member_sets`.  The intact truss: displace/external [B, L, nJ_max, 3], internal [B, L, nM_max] (as
+    `LoadCaseResult`).  Per scenario s: pivot [B, S, 8] (the pivots of the elimination in the set's order - for removals
+    the redundancy of member j once the members before it are gone; NaN beyond the set and after a failing position),
+    unstable [B, S] (bool: some pivot <= r_tol), first_unstable [B, S] (the position in the set from which the truss is a
+    mechanism, else -1), and per load case peak_stress, peak_displace [B, L, S] (the largest |N'| / (gamma A) among the
+    members that are not removed and the largest joint displacement; +inf for an unstable scenario) with peak_member,
+    peak_joint [B, L, S] (member id, caller's joint id; -1 where there is none), internal_after [B, L, S, nM_max]
+    (`want_forces`, else None) and displace_after [B, L, S, nJ_max, 3] (`want_displace`, else None; NaN for an unstable
+    scenario).  info [B]: the factorisation's status - a truss with info != 0 has meaningless numbers, the others are
+    unaffected."""
+    displace: np.ndarray
+    external: np.ndarray
+    internal: np.ndarray
+    pivot: np.ndarray
+    unstable: np.ndarray
+    first_unstable: np.ndarray
+    peak_stress: np.ndarray
+    peak_member: np.ndarray
+    peak_displace: np.ndarray
+    peak_joint: np.ndarray
+    internal_after: np.ndarray
+    displace_after: np.ndarray
+    info: np.ndarray
+
+
+def _check_member_sets_args(packed, sets, factors, loads, r_tol, sections, want_forces=False, want_displace=False,
+                            max_result_bytes=4 << 30, chunk=64):
+    """The argument errors of `solve_member_sets` that need no device.  Returns host arrays: sets int32 [B, S, 8],
+    factors float64 [B, S, 8] or None, loads float64 [B, L, nJ_max, 3]."""
+    if sections is not None:
+        raise ValueError("solve_member_sets: sections= variants cannot be combined with the member-set analysis")
+    try:
+        loads = _check_member_loss_args(packed, loads, r_tol, None, chunk=chunk)
+    except ValueError as exc:
+        raise ValueError(str(exc).replace("solve_member_loss", "solve_member_sets")) from None
+    B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
+    sets, factors = _member_set_arrays("solve_member_sets", sets, factors, B, packed.nM, nM_max)
+    extra = 8 * B * int(loads.shape[1]) * int(sets.shape[1]) * (nM_max * bool(want_forces) + 3 * nJ_max * bool(want_displace))
+    if extra > max_result_bytes:
+        raise ValueError(f"solve_member_sets: internal_after / displace_after of [B={B}, L={loads.shape[1]}, "
+                         f"S={sets.shape[1]}] scenarios take {extra} bytes, more than max_result_bytes = {max_result_bytes}")
+    return sets, factors, loads
+
+
+def solve_member_sets(trusses_or_packed, sets, factors=None, loads=None, r_tol=MEMBER_LOSS_R_TOL, want_forces=False,
+                      want_displace=False, device=None, reorder=False, options=None, max_slab_bytes=64 << 30,
+                      on_device=False, sections=None, use_envelope=True, chunk=64, max_result_bytes=4 << 30):
+    """Scenario screening: what happens to every truss of a batch when up to eight of its members are removed, damaged
+    or strengthened AT ONCE - "these two diagonals and that chord go together", "this bay corrodes to half its section",
+    "double those four members" - for S scenarios per truss, from ONE factorisation per truss.  A scenario changes K_ff
+    by sum_j (gamma_j - 1) k_j b_j b_j^T, of rank k <= 8: the columns z_j = inv(K_ff) b_j of its members and one k x k
+    elimination in the set's order give the state exactly (`DeviceBatch.member_sets`, include/trs_sets.h); the pivots of
+    that elimination tell whether - and from which member of the set on - the truss is a mechanism.  `sets`: a list (per
+    truss) of lists (per scenario) of member-id lists, or an integer array [B, S, K <= 8] with -1 padding at the end of
+    a set; an empty set gives the intact state (trusses with fewer scenarios are padded with it).  `factors`: the area
+    factor gamma of every named member in the same form (0 removed, below 1 damaged, above 1 strengthened, 1 unchanged),
+    or None: every member removed.  `loads`: [B, L, nJ_max, dim] (numpy or torch, caller's joint numbering; dim 2 or 3),
+    or None for the batch's own loads as one case.  `want_forces`, `want_displace`: also the member forces and the
+    joint displacements of every scenario - together refused above `max_result_bytes`.  Buckets, member forms, `reorder`
+    plans, `options`, `on_device`, `use_envelope` and `chunk` as `solve_member_loss`.  An id outside [0, nM[b]), an id
+    twice in a set, more than 8 members in a set, a negative or non-finite factor, `sections=` variants, non-finite
+    loads, an `r_tol` outside (0, 1) and a `chunk` below 1 raise ValueError before any device work.  Returns a
+    `MemberSetResult`."""
+    packed = _as_packed(trusses_or_packed)
+    sets, factors, loads = _check_member_sets_args(packed, sets, factors, loads, r_tol, sections, want_forces,
+                                                   want_displace, max_result_bytes, chunk)
+    torch, dev = _require_gpu(device)
+    B, L, S, nJ_max, nM_max = packed.B, int(loads.shape[1]), int(sets.shape[1]), packed.nJ_max, packed.nM_max
+    loads = _device_f64(torch, dev, loads)
+    full = lambda shape, value=0.0, dtype=torch.float64: torch.full(shape, value, dtype=dtype, device=dev)
+    i32, nan = torch.int32, float("nan")
+    out = MemberSetResult(full([B, L, nJ_max, 3]), full([B, L, nJ_max, 3]), full([B, L, nM_max]),
+                          full([B, S, MEMBER_SETS_MAX], nan), full([B, S], 0, i32), full([B, S], -1, i32),
+                          full([B, L, S]), full([B, L, S], -1, i32), full([B, L, S]), full([B, L, S], -1, i32),
+                          full([B, L, S, nM_max]) if want_forces else None,
+                          full([B, L, S, nJ_max, 3]) if want_displace else None, full([B], 0, i32))
+    fields = (("displace", "u", dict(nJ=2)), ("external", "f_ext", dict(nJ=2)), ("internal", "N", dict(nM=2)),
+              ("pivot", "pivot", {}), ("unstable", "unstable", {}), ("first_unstable", "first_unstable", {}),
+              ("peak_stress", "peak_stress", {}), ("peak_member", "peak_member", {}),
+              ("peak_displace", "peak_displace", {}), ("peak_joint", "peak_joint", {}))
+    for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope, cases=L):
+        res = db.member_sets(part.cut(loads, nJ=2), sets[part.index], None if factors is None else factors[part.index],
+                             r_tol=r_tol, want_forces=want_forces, want_displace=want_displace, chunk=chunk,
+                             max_result_bytes=max_result_bytes)
+        for field, key, axes in fields:
+            part.put(getattr(out, field), res[key], **axes)
+        if want_forces:
+            part.put(out.internal_after, res["N_after"], nM=3)
+        if want_displace:
+            part.put(out.displace_after, res["u_after"], nJ=3)
+    out.unstable = out.unstable != 0
+    if on_device:
+        return out
+    torch.cuda.synchronize(dev)
+    return MemberSetResult(**{k: None if v is None else v.cpu().numpy() for k, v in vars(out).items()})
 
 
 @dataclass

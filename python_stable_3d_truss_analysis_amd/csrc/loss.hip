@@ -17,6 +17,7 @@
 // slice, the pass, L, B or the member form.
 #include "../../include/trs_loss.h"
 #include "trs_common.h"
+#include "trs_loss_row.h"
 #include "trs_recover.h"
 
 #include <limits.h>
@@ -25,6 +26,7 @@
 namespace {
 
 using namespace trs_rec;
+using trs_loss_row::wave_max_index;
 
 #ifndef TRS_LOSS_WAVES
 #define TRS_LOSS_WAVES 4          // waves per work-group (EXPERIMENTS R14); trs_loss_fits' rule counts their z vectors
@@ -79,19 +81,6 @@ __device__ __forceinline__ LossTables loss_tables(double* sh, int nJ_max, int nM
     return t;
 }
 
-// (value, index) maximum over the wave: the larger value, the lower index on a tie
-__device__ __forceinline__ void wave_max_index(double& v, int& i) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ov = __shfl_xor(v, off);
-        const int oi = __shfl_xor(i, off);
-        if (ov > v || (ov == v && oi < i)) {
-            v = ov;
-            i = oi;
-        }
-    }
-}
-
 // ---- the right-hand sides: one wave per row --------------------------------------------------------------------------
 __global__ __launch_bounds__(64 * WAVES) void trs_loss_rhs_kernel(const int e0, const int C, const double* __restrict__ xyz,
                                                            const TrsMembers mem, const int* __restrict__ free_index,
@@ -105,27 +94,8 @@ __global__ __launch_bounds__(64 * WAVES) void trs_loss_rhs_kernel(const int e0, 
     const int e = e0 + i;
     const int npad = trs_round_up(n_free[b], TRS_NB);
     double* row = Z + ((size_t)b * C + i) * ld_f;
-    int at[6] = {-1, -1, -1, -1, -1, -1};
-    double val[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (e < nM[b]) {
-        const int* fi = free_index + (size_t)b * 3 * nJ_max;
-        const int2 c = mem.ends((size_t)b * nM_max + e);
-        const MemberGeom g = member_geom(xyz + (size_t)b * 3 * nJ_max, c.x, c.y);
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            at[a] = fi[3 * c.y + a];
-            val[a] = g.c[a];
-            at[3 + a] = fi[3 * c.x + a];
-            val[3 + a] = -g.c[a];
-        }
-    }
-    for (int col = lane; col < npad; col += 64) {
-        double v = 0.0;
-#pragma unroll
-        for (int t = 0; t < 6; ++t)
-            if (at[t] == col) v = val[t];
-        row[col] = v;
-    }
+    trs_loss_row::write_row(row, npad, lane, e < nM[b], (size_t)b * nM_max + e, mem, xyz + (size_t)b * 3 * nJ_max,
+                            free_index + (size_t)b * 3 * nJ_max);
 }
 
 // ---- the apply kernel ------------------------------------------------------------------------------------------------

@@ -1,0 +1,472 @@
+// Member-set scenarios (include/trs_sets.h): what removing, damaging or strengthening up to eight members AT ONCE does
+// to a truss, from the factor in the slab - the change K_ff + sum_j theta_j k_j b_j b_j^T has rank k, so one substitution
+// column per DISTINCT member of a range of scenarios (trs_potrs_cases, cases.hip, as it is) and one k x k elimination
+// per scenario replace one factorisation per scenario.
+//
+//   trs_sets_rhs      Z [B][C][ld_f]: row i = b_e,f of e = cols[b][i] (trs_loss_row.h: the row of trs_loss_rhs)
+//   trs_potrs_cases   z_e = inv(K_ff) b_e,f
+//   trs_sets_apply    P_ij = c_i . D z_j,  A = I + diag(k) P diag(theta) = L U in the set's order,  a = theta inv(A) n,
+//                     u' = u - sum_j a_j z_j,  N'_m = gamma_m k_m c_m . D u', and the maxima of |k_m c_m . D u'| / A_m over
+//                     the members with gamma != 0 and of |u'_j| over the joints
+//
+// The apply kernel has the shape of trs_loss_apply (loss.hip): one work-group of four waves per (truss, slice of the
+// range's scenarios), the member table, the DOF map, joint_out and u and N of a pass of cases staged in LDS once.  Every
+// wave takes one scenario at a time.  Lane 8 i + j gathers P_ij from Z through free_index - the expression that forms
+// r_e in trs_loss_apply, so a single removal's pivot has r_e's bits - and holds A_ij during the elimination, which runs
+// in lockstep with wave shuffles; L and U go to 64 doubles of LDS of the wave's own.  Lane 8 l + i then substitutes case
+// l of the pass (forward, backward, ascending) and leaves a_i = theta_i x_i in 64 more.  Per case the wave forms
+// u' = u - sum_j a_j z_j in its ONE joint-layout LDS vector (ascending j, one fma per term, the k rows of Z streamed
+// through free_index) and runs its lanes over the members and the joints.  Max is exact and every other number is one
+// fixed expression of staged values: the result of (s, l) does not depend on the range, the slice, the pass, L, B, the
+// place of the columns in Z or the member form.
+#include "../../include/trs_sets.h"
+#include "trs_common.h"
+#include "trs_loss_row.h"
+#include "trs_recover.h"
+
+#include <limits.h>
+#include <math.h>
+
+namespace {
+
+using namespace trs_rec;
+using trs_loss_row::wave_max_index;
+
+constexpr int WAVES = 4;          // waves per work-group; trs_sets_fits' rule counts their u' vectors
+constexpr int KMAX = TRS_SETS_MAX;
+constexpr int MAX_PASS = 8;       // load cases per pass at most: lane 8 l + i substitutes case l
+constexpr size_t LDS_BUDGET = 160 * 1024;   // a CU's LDS: the ONE number behind trs_sets_fits, the passes and the launch
+#ifndef TRS_SETS_SLICE
+#define TRS_SETS_SLICE 32         // scenarios per work-group
+#endif
+static_assert(KMAX * KMAX == 64 && MAX_PASS * KMAX == 64, "one lane per entry of the k x k system / per (case, member)");
+
+// LDS of the apply kernel with g cases per pass (the rule of trs_sets_fits)
+size_t sets_lds(int nJ_max, int nM_max, int g) {
+    const size_t doubles = (size_t)5 * nM_max + (size_t)3 * nJ_max * WAVES + (size_t)128 * WAVES +
+                           (size_t)g * ((size_t)3 * nJ_max + nM_max);
+    const size_t ints = (size_t)2 * nM_max + (size_t)4 * nJ_max;
+    return (doubles * sizeof(double) + ints * sizeof(int) + 15) / 16 * 16;
+}
+
+// cases per pass: the largest g <= min(L, MAX_PASS) that fits, evened out over the passes it makes necessary; 0 = none
+int sets_pass(int nJ_max, int nM_max, int L) {
+    int g = L < MAX_PASS ? L : MAX_PASS;
+    while (g > 0 && sets_lds(nJ_max, nM_max, g) > LDS_BUDGET) --g;
+    if (g <= 0) return 0;
+    const int passes = (L + g - 1) / g;
+    return (L + passes - 1) / passes;
+}
+
+struct SetsTables {
+    double *cx, *cy, *cz, *k, *ia;   // [nM_max] each
+    double* z;                       // [WAVES][3 nJ_max]  u' of the wave's current (scenario, case)
+    double* lu;                      // [WAVES][64]        L (below the diagonal) and U of the wave's scenario
+    double* a;                       // [WAVES][64]        a_i of case l of the pass at 8 l + i
+    double* u;                       // [g][3 nJ_max]
+    double* N;                       // [g][nM_max]
+    int2* ends;                      // [nM_max]
+    int* fi;                         // [3 nJ_max]
+    int* jo;                         // [nJ_max]
+};
+
+__device__ __forceinline__ SetsTables sets_tables(double* sh, int nJ_max, int nM_max, int g) {
+    SetsTables t;
+    t.cx = sh;
+    t.cy = t.cx + nM_max;
+    t.cz = t.cy + nM_max;
+    t.k = t.cz + nM_max;
+    t.ia = t.k + nM_max;
+    t.z = t.ia + nM_max;
+    t.lu = t.z + (size_t)WAVES * 3 * nJ_max;
+    t.a = t.lu + 64 * WAVES;
+    t.u = t.a + 64 * WAVES;
+    t.N = t.u + (size_t)g * 3 * nJ_max;
+    t.ends = reinterpret_cast<int2*>(t.N + (size_t)g * nM_max);
+    t.fi = reinterpret_cast<int*>(t.ends + nM_max);
+    t.jo = t.fi + 3 * nJ_max;
+    return t;
+}
+
+// ---- the right-hand sides: one wave per row --------------------------------------------------------------------------
+__global__ __launch_bounds__(64 * WAVES) void trs_sets_rhs_kernel(const int C, const double* __restrict__ xyz,
+                                                                  const TrsMembers mem, const int* __restrict__ free_index,
+                                                                  const int* __restrict__ n_free, const int* __restrict__ nM,
+                                                                  const int* __restrict__ cols, const int nJ_max,
+                                                                  const int nM_max, double* __restrict__ Z, const int ld_f) {
+    const int per_truss = (C + WAVES - 1) / WAVES;   // work-groups per truss
+    const int b = blockIdx.x / per_truss, lane = threadIdx.x & 63;
+    const int i = (blockIdx.x - b * per_truss) * WAVES + (threadIdx.x >> 6);
+    if (i >= C) return;
+    const int e = cols[(size_t)b * C + i];
+    const bool real = e >= 0 && e < nM[b];
+    const int npad = min(trs_round_up(n_free[b], TRS_NB), ld_f);
+    trs_loss_row::write_row(Z + ((size_t)b * C + i) * ld_f, npad, lane, real, (size_t)b * nM_max + (real ? e : 0), mem,
+                            xyz + (size_t)b * 3 * nJ_max, free_index + (size_t)b * 3 * nJ_max);
+}
+
+// ---- the apply kernel ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64 * WAVES) void trs_sets_apply_kernel(
+    const int L, const int g, const int S, const int s0, const int Sc, const int C, const int slice,
+    const double* __restrict__ xyz, const TrsMembers mem, const int* __restrict__ free_index, const int* __restrict__ nJ,
+    const int* __restrict__ nM, const int nJ_max, const int nM_max, const int* __restrict__ cols,
+    const int* __restrict__ slot, const double* __restrict__ gamma, const double* __restrict__ Z,
+    const double* __restrict__ U, const int ld_f, const double r_tol, double* __restrict__ piv_out,
+    int* __restrict__ unst_out, int* __restrict__ first_out, double* __restrict__ ps_out, int* __restrict__ pm_out,
+    double* __restrict__ pd_out, int* __restrict__ pj_out, double* __restrict__ NA, double* __restrict__ UA,
+    const int* __restrict__ joint_out) {
+    extern __shared__ double sh[];
+    const int slices = (Sc + slice - 1) / slice;   // work-groups per truss
+    const int b = blockIdx.x / slices, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // the scenarios of this work-group, counted within the range: first <= sl < last
+    const int first = (blockIdx.x - b * slices) * slice;
+    const int last = min(first + slice, Sc);
+    if (first >= last) return;
+    // trimmed to the arrays, so that no table entry and no output lies outside them whatever nJ[b] and nM[b] hold
+    const int joints = min(max(nJ[b], 0), nJ_max), members = min(max(nM[b], 0), nM_max);
+    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
+    const SetsTables t = sets_tables(sh, nJ_max, nM_max, g);
+    const size_t mbase = (size_t)b * nM_max;
+    const double* X = xyz + (size_t)b * ndof_max;
+    double* zw = t.z + (size_t)wave * ndof_max;
+    double* luw = t.lu + 64 * wave;
+    double* aw = t.a + 64 * wave;
+    const double inf = __builtin_huge_val(), nan = __builtin_nan("");
+    const int hi = lane >> 3, lo = lane & 7;   // lane = 8 hi + lo
+
+    // once per work-group: the member table, the DOF map, the joint order
+    for (int m = tid; m < members; m += 64 * WAVES) {
+        int2 c = mem.ends(mbase + m);
+        c.x = min(max(c.x, 0), nJ_max - 1);   // (a joint id outside the arrays would index LDS outside them)
+        c.y = min(max(c.y, 0), nJ_max - 1);
+        const MemberGeom mg = member_geom(X, c.x, c.y);
+        t.ends[m] = c;
+        t.cx[m] = mg.c[0];
+        t.cy[m] = mg.c[1];
+        t.cz[m] = mg.c[2];
+        t.k[m] = mem.EA(mbase + m) / mg.len;
+        t.ia[m] = 1.0 / mem.area(mbase + m);
+    }
+    // staged for every joint of the arrays, -1 (held) past the truss's own: an end joint trimmed to there reads zeros
+    for (int d = tid; d < ndof_max; d += 64 * WAVES) {
+        const int row = free_index[(size_t)b * ndof_max + d];
+        t.fi[d] = d < ndof && row < ld_f ? row : -1;
+    }
+    for (int j = tid; j < nJ_max; j += 64 * WAVES) {
+        const int id = joint_out != nullptr ? joint_out[(size_t)b * nJ_max + j] : j;
+        t.jo[j] = id >= 0 && id < nJ_max ? id : j;
+    }
+    for (int d = tid; d < WAVES * ndof_max; d += 64 * WAVES) t.z[d] = 0.0;   // (entries past ndof stay zero)
+
+    for (int l0 = 0; l0 < L; l0 += g) {
+        const int lg = min(g, L - l0);   // the cases of this pass: l0 .. l0 + lg - 1
+        __syncthreads();                 // (the tables above are written; the previous pass's readers of u and N are done)
+        for (int x = tid; x < lg * ndof_max; x += 64 * WAVES) {
+            const int l = x / ndof_max, d = x - l * ndof_max;
+            const int row = t.fi[d];
+            t.u[(size_t)l * ndof_max + d] = row >= 0 ? U[((size_t)b * L + l0 + l) * ld_f + row] : 0.0;
+        }
+        __syncthreads();
+        for (int x = tid; x < lg * members; x += 64 * WAVES) {   // N = k c . (u_j1 - u_j0), as trs_loss_apply stages it
+            const int l = x / members, m = x - l * members;
+            const double* ul = t.u + (size_t)l * ndof_max;
+            const int2 c = t.ends[m];
+            double p = t.cx[m] * (ul[3 * c.y] - ul[3 * c.x]);
+            p = fma(t.cy[m], ul[3 * c.y + 1] - ul[3 * c.x + 1], p);
+            p = fma(t.cz[m], ul[3 * c.y + 2] - ul[3 * c.x + 2], p);
+            t.N[(size_t)l * nM_max + m] = t.k[m] * p;
+        }
+        __syncthreads();
+
+        for (int sl = first + wave; sl < last; sl += WAVES) {
+            const size_t sb = (size_t)b * S + s0 + sl;            // (b, s) of the per-scenario outputs
+            const size_t out0 = ((size_t)b * L + l0) * S + s0 + sl;   // (b, l0, s); the next case lies S further
+            // the set: lane j < 8 holds its j-th member, column and factor; it ends at the first entry that names none
+            const size_t in0 = ((size_t)b * Sc + sl) * KMAX;
+            int my_col = -1, my_e = -1;
+            double my_gamma = 0.0;
+            if (lane < KMAX) {
+                my_col = slot[in0 + lane];
+                if (my_col >= 0 && my_col < C) {
+                    const int e = cols[(size_t)b * C + my_col];
+                    if (e >= 0 && e < members) my_e = e;
+                }
+                if (gamma != nullptr) my_gamma = gamma[in0 + lane];
+            }
+            const unsigned ends_at = (unsigned)(__ballot(lane < KMAX && my_e < 0) & 0xffu);
+            const int k = ends_at != 0 ? __builtin_ctz(ends_at) : KMAX;
+            int e_of[KMAX], col_of[KMAX];
+            double gam[KMAX];
+#pragma unroll
+            for (int j = 0; j < KMAX; ++j) {
+                e_of[j] = __builtin_amdgcn_readfirstlane(__shfl(my_e, j));
+                col_of[j] = __builtin_amdgcn_readfirstlane(__shfl(my_col, j));
+                gam[j] = __shfl(my_gamma, j);
+            }
+            // A_ij = delta_ij + theta_j k_i c_i . (z_j at i's j1 - z_j at i's j0) in lane 8 i + j
+            const int e_hi = __shfl(my_e, hi), e_lo = __shfl(my_e, lo), cj = __shfl(my_col, lo);
+            const double theta = __shfl(my_gamma, lo) - 1.0;   // of member lo: column lo of A, and a_lo below
+            double Aij = hi == lo ? 1.0 : 0.0;
+            if (hi < k && lo < k) {
+                const int ei = e_hi;
+                const double* zj = Z + ((size_t)b * C + cj) * ld_f;
+                const int2 ce = t.ends[ei];
+                double v[6];
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    const int r1 = t.fi[3 * ce.y + a], r0 = t.fi[3 * ce.x + a];
+                    v[a] = r1 >= 0 ? zj[r1] : 0.0;
+                    v[3 + a] = r0 >= 0 ? zj[r0] : 0.0;
+                }
+                double pe = t.cx[ei] * (v[0] - v[3]);
+                pe = fma(t.cy[ei], v[1] - v[4], pe);
+                pe = fma(t.cz[ei], v[2] - v[5], pe);
+                Aij = fma(theta * t.k[ei], pe, Aij);
+            }
+            // Gauss without pivoting, in the set's order
+            int fail = -1;
+            double my_pivot = nan;   // lane j < 8: p_j
+#pragma unroll
+            for (int p = 0; p < KMAX; ++p) {
+                if (p >= k || fail >= 0) break;
+                const double piv = __shfl(Aij, 9 * p);
+                if (lane == p) my_pivot = piv;
+                if (!(piv > r_tol)) {
+                    fail = p;
+                    break;
+                }
+                const double aip = __shfl(Aij, 8 * hi + p), apj = __shfl(Aij, 8 * p + lo);
+                if (hi > p) {
+                    const double f = aip / piv;
+                    if (lo == p) Aij = f;
+                    else if (lo > p) Aij = fma(-f, apj, Aij);
+                }
+            }
+            if (l0 == 0) {
+                if (lane < KMAX) piv_out[sb * KMAX + lane] = my_pivot;
+                if (lane == 0) {
+                    unst_out[sb] = fail >= 0 ? 1 : 0;
+                    first_out[sb] = fail;
+                }
+            }
+            if (fail >= 0) {
+                if (lane < lg) {
+                    const size_t o = out0 + (size_t)lane * S;
+                    ps_out[o] = inf;
+                    pd_out[o] = inf;
+                    pm_out[o] = -1;
+                    pj_out[o] = -1;
+                }
+                for (int l = 0; l < lg; ++l) {
+                    const size_t o = out0 + (size_t)l * S;
+                    if (NA != nullptr)
+                        for (int m = lane; m < nM_max; m += 64) NA[o * nM_max + m] = m < members ? nan : 0.0;
+                    if (UA != nullptr)
+                        for (int j = lane; j < nJ_max; j += 64) {
+                            double* dst = UA + (o * nJ_max + t.jo[j]) * 3;
+                            dst[0] = dst[1] = dst[2] = j < joints ? nan : 0.0;
+                        }
+                }
+                continue;
+            }
+            // a = theta inv(A) n of the cases of the pass: lane 8 l + i
+            luw[lane] = Aij;
+            __builtin_amdgcn_wave_barrier();
+            {
+                const bool mine = hi < lg && lo < k;
+                double y = 0.0;
+                if (mine) y = t.N[(size_t)hi * nM_max + e_lo];
+#pragma unroll
+                for (int j = 0; j < KMAX; ++j) {   // L y = n (unit diagonal)
+                    if (j >= k) break;
+                    const double yj = __shfl(y, 8 * hi + j);
+                    if (mine && lo > j) y = fma(-luw[8 * lo + j], yj, y);
+                }
+#pragma unroll
+                for (int j = KMAX - 1; j >= 0; --j) {   // U x = y
+                    if (j >= k) continue;
+                    if (mine && lo == j) y = y / luw[9 * j];
+                    const double xj = __shfl(y, 8 * hi + j);
+                    if (mine && lo < j) y = fma(-luw[8 * lo + j], xj, y);
+                }
+                aw[lane] = mine ? theta * y : 0.0;
+            }
+            __builtin_amdgcn_wave_barrier();
+
+            for (int l = 0; l < lg; ++l) {
+                const size_t o = out0 + (size_t)l * S;
+                // u' = u - sum_j a_j z_j in joint layout (this wave's own vector: written and read by this wave only)
+                {
+                    const double* ul = t.u + (size_t)l * ndof_max;
+                    double al[KMAX];
+#pragma unroll
+                    for (int j = 0; j < KMAX; ++j) al[j] = aw[8 * l + j];
+                    for (int d = lane; d < ndof; d += 64) {
+                        double v = ul[d];
+                        const int row = t.fi[d];
+                        if (row >= 0) {
+#pragma unroll
+                            for (int j = 0; j < KMAX; ++j) {
+                                if (j >= k) break;
+                                v = fma(-al[j], Z[((size_t)b * C + col_of[j]) * ld_f + row], v);
+                            }
+                        }
+                        zw[d] = v;
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();
+                // the members
+                double best = -1.0;
+                int where = INT_MAX;
+                for (int m0 = 0; m0 < nM_max; m0 += 64) {
+                    const int m = m0 + lane;
+                    const bool real = m < members;
+                    double after = 0.0;
+                    if (real) {
+                        const int2 c = t.ends[m];
+                        double p = t.cx[m] * (zw[3 * c.y] - zw[3 * c.x]);
+                        p = fma(t.cy[m], zw[3 * c.y + 1] - zw[3 * c.x + 1], p);
+                        p = fma(t.cz[m], zw[3 * c.y + 2] - zw[3 * c.x + 2], p);
+                        const double n = t.k[m] * p;
+                        double gm = 1.0;
+                        bool changed = false;
+#pragma unroll
+                        for (int j = 0; j < KMAX; ++j)
+                            if (j < k && m == e_of[j]) {
+                                gm = gam[j];
+                                changed = true;
+                            }
+                        after = !changed ? n : gm == 0.0 ? 0.0 : gm * n;
+                        const double s = fabs(n) * t.ia[m];
+                        if (gm != 0.0 && s > best) {   // (ascending m per lane: the first of equals stays)
+                            best = s;
+                            where = m;
+                        }
+                    }
+                    if (NA != nullptr && m < nM_max) NA[o * nM_max + m] = after;
+                }
+                wave_max_index(best, where);
+                if (lane == 0) {
+                    ps_out[o] = where == INT_MAX ? 0.0 : best;
+                    pm_out[o] = where == INT_MAX ? -1 : where;
+                }
+                // the joints
+                best = -1.0;
+                where = INT_MAX;
+                for (int j = lane; j < nJ_max; j += 64) {
+                    const int id = t.jo[j];
+                    const double a0 = zw[3 * j], a1 = zw[3 * j + 1], a2 = zw[3 * j + 2];   // (zero past the truss's joints)
+                    if (j < joints) {
+                        const double d = sqrt(fma(a2, a2, fma(a1, a1, a0 * a0)));
+                        if (d > best || (d == best && id < where)) {
+                            best = d;
+                            where = id;
+                        }
+                    }
+                    if (UA != nullptr) {
+                        double* dst = UA + (o * nJ_max + id) * 3;
+                        dst[0] = a0;
+                        dst[1] = a1;
+                        dst[2] = a2;
+                    }
+                }
+                wave_max_index(best, where);
+                if (lane == 0) {
+                    pd_out[o] = where == INT_MAX ? 0.0 : best;
+                    pj_out[o] = where == INT_MAX ? -1 : where;
+                }
+                __builtin_amdgcn_wave_barrier();   // (the next case's u' overwrites zw)
+            }
+        }
+    }
+}
+
+int sets_rhs_launch(int B, int C, int nJ_max, int nM_max, const double* xyz, const TrsMembers& mem, const int* free_index,
+                    const int* n_free, const int* nM, const int* cols, double* Z, int ld_f, hipStream_t stream) {
+    if (B < 0 || C < 0 || nJ_max < 0 || nM_max < 0 || ld_f < 0) return (int)hipErrorInvalidValue;
+    if (B == 0 || C == 0) return 0;
+    if (!mem.conn || !xyz || !free_index || !n_free || !nM || !cols || !Z) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(trs_sets_rhs_kernel, dim3((unsigned)((C + WAVES - 1) / WAVES) * (unsigned)B), dim3(64 * WAVES), 0,
+                       stream, C, xyz, mem, free_index, n_free, nM, cols, nJ_max, nM_max, Z, ld_f);
+    return (int)hipGetLastError();
+}
+
+int sets_apply_launch(int B, int L, int S, int s0, int Sc, int C, int nJ_max, int nM_max, const double* xyz,
+                      const TrsMembers& mem, const int* free_index, const int* nJ, const int* nM, const int* cols,
+                      const int* slot, const double* gamma, const double* Z, const double* U, int ld_f, double r_tol,
+                      double* pivot, int* unstable, int* first_unstable, double* peak_stress, int* peak_member,
+                      double* peak_displace, int* peak_joint, double* N_after, double* u_after, const int* joint_out,
+                      hipStream_t stream) {
+    if (B < 0 || L < 0 || S < 0 || s0 < 0 || Sc < 0 || C < 0 || nJ_max < 0 || nM_max < 0 || ld_f < 0)
+        return (int)hipErrorInvalidValue;
+    if ((long long)s0 + Sc > S) return (int)hipErrorInvalidValue;   // (the outputs hold S scenarios)
+    if (B == 0 || L == 0 || Sc == 0) return 0;
+    if (nJ_max == 0 && nM_max > 0) return (int)hipErrorInvalidValue;   // (members without joints to end at)
+    if (!trs_sets_fits(nJ_max, nM_max, L)) return (int)hipErrorInvalidValue;
+    if (!mem.conn || (mem.tidx == nullptr && (!mem.E || !mem.A)) || !xyz || !free_index || !nJ || !nM || !slot || !U || !pivot || !unstable || !first_unstable || !peak_stress ||
+        !peak_member || !peak_displace || !peak_joint || (C > 0 && (!cols || !Z)))
+        return (int)hipErrorInvalidValue;
+    const int g = sets_pass(nJ_max, nM_max, L);
+    if (g <= 0) return (int)hipErrorInvalidValue;   // (the kernel's pass loop steps by g)
+    static const int lds_limit_set = (int)hipFuncSetAttribute(   // once per process, not per launch
+        reinterpret_cast<const void*>(trs_sets_apply_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET);
+    (void)lds_limit_set;
+    const int slices = (Sc + TRS_SETS_SLICE - 1) / TRS_SETS_SLICE;
+    hipLaunchKernelGGL(trs_sets_apply_kernel, dim3((unsigned)slices * (unsigned)B), dim3(64 * WAVES),
+                       sets_lds(nJ_max, nM_max, g), stream, L, g, S, s0, Sc, C, TRS_SETS_SLICE, xyz, mem, free_index, nJ,
+                       nM, nJ_max, nM_max, cols, slot, gamma, Z, U, ld_f, r_tol, pivot, unstable, first_unstable,
+                       peak_stress, peak_member, peak_displace, peak_joint, N_after, u_after, joint_out);
+    return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+int trs_sets_abi_version(void) { return TRS_SETS_ABI_VERSION; }
+
+int trs_sets_fits(int nJ_max, int nM_max, int L) {
+    return nJ_max >= 0 && nM_max >= 0 && L >= 0 && sets_lds(nJ_max, nM_max, 1) <= LDS_BUDGET;
+}
+
+int trs_sets_rhs(int B, int C, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* E,
+                 const double* A, const int32_t* free_index, const int32_t* n_free, const int32_t* nM,
+                 const int32_t* cols, double* Z, int ld_f, void* stream) {
+    return sets_rhs_launch(B, C, nJ_max, nM_max, xyz, trs_members_general(conn, E, A), free_index, n_free, nM, cols, Z,
+                           ld_f, (hipStream_t)stream);
+}
+
+int trs_sets_tab_rhs(int B, int C, int nJ_max, int nM_max, const double* xyz, const uint16_t* conn16,
+                     const uint8_t* type_idx, const double* types, const int32_t* free_index, const int32_t* n_free,
+                     const int32_t* nM, const int32_t* cols, double* Z, int ld_f, void* stream) {
+    if (B > 0 && (!conn16 || !type_idx || !types)) return (int)hipErrorInvalidValue;
+    return sets_rhs_launch(B, C, nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), free_index, n_free, nM,
+                           cols, Z, ld_f, (hipStream_t)stream);
+}
+
+int trs_sets_apply(int B, int L, int S, int s0, int Sc, int C, int nJ_max, int nM_max, const double* xyz,
+                   const int32_t* conn, const double* E, const double* A, const int32_t* free_index, const int32_t* nJ,
+                   const int32_t* nM, const int32_t* cols, const int32_t* slot, const double* gamma, const double* Z,
+                   const double* U, int ld_f, double r_tol, double* pivot, int32_t* unstable, int32_t* first_unstable,
+                   double* peak_stress, int32_t* peak_member, double* peak_displace, int32_t* peak_joint,
+                   double* N_after, double* u_after, const int32_t* joint_out, void* stream) {
+    return sets_apply_launch(B, L, S, s0, Sc, C, nJ_max, nM_max, xyz, trs_members_general(conn, E, A), free_index, nJ, nM,
+                             cols, slot, gamma, Z, U, ld_f, r_tol, pivot, unstable, first_unstable, peak_stress,
+                             peak_member, peak_displace, peak_joint, N_after, u_after, joint_out, (hipStream_t)stream);
+}
+
+int trs_sets_tab_apply(int B, int L, int S, int s0, int Sc, int C, int nJ_max, int nM_max, const double* xyz,
+                       const uint16_t* conn16, const uint8_t* type_idx, const double* types, const int32_t* free_index,
+                       const int32_t* nJ, const int32_t* nM, const int32_t* cols, const int32_t* slot,
+                       const double* gamma, const double* Z, const double* U, int ld_f, double r_tol, double* pivot,
+                       int32_t* unstable, int32_t* first_unstable, double* peak_stress, int32_t* peak_member,
+                       double* peak_displace, int32_t* peak_joint, double* N_after, double* u_after,
+                       const int32_t* joint_out, void* stream) {
+    if (B > 0 && (!conn16 || !type_idx || !types)) return (int)hipErrorInvalidValue;
+    return sets_apply_launch(B, L, S, s0, Sc, C, nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types),
+                             free_index, nJ, nM, cols, slot, gamma, Z, U, ld_f, r_tol, pivot, unstable, first_unstable,
+                             peak_stress, peak_member, peak_displace, peak_joint, N_after, u_after, joint_out,
+                             (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -470,13 +470,7 @@ class Truss:
             cases = list(cases)
             if not cases:
                 return []
-            loads = np.zeros([1, len(cases), packed.nJ_max, 3])
-            for k, case in enumerate(cases):
-                probe = Truss(self._dim).LoadFromJSON(data=dict(self.Serialize(), force=[]))
-                for jointID, vector in case.items():
-                    probe.AddExternalForce(jointID, vector)
-                for j, v in probe._loads.items():
-                    loads[0, k, j, :self._dim] = v
+            loads = self._case_loads(cases, packed.nJ_max)
         result = solve_member_loss(packed, loads, r_tol=MEMBER_LOSS_R_TOL if rTol is None else rTol,
                                    want_forces=returnForces)
         if int(result.info[0]) != 0:
@@ -496,6 +490,78 @@ class Truss:
                     rec["forces"] = None if critical else \
                         {int(m): float(n[m]) for m in np.flatnonzero(np.abs(n) >= ZERO_EPS)}
                 records[e] = rec
+            out.append(records)
+        return out
+
+    def _case_loads(self, cases, nJ_max):
+        """[1, L, nJ_max, 3]: `{jointID: vector}` load cases as the dense array the batched analyses take, every vector
+        checked as `AddExternalForce` checks it."""
+        loads = np.zeros([1, len(cases), nJ_max, 3])
+        for k, case in enumerate(cases):
+            probe = Truss(self._dim).LoadFromJSON(data=dict(self.Serialize(), force=[]))
+            for jointID, vector in case.items():
+                probe.AddExternalForce(jointID, vector)
+            for j, v in probe._loads.items():
+                loads[0, k, j, :self._dim] = v
+        return loads
+
+    def MemberSets(self, sets, factors=None, cases=None, rTol=None, returnForces=False):
+        """What removing, damaging or strengthening SEVERAL members at once does to this truss, for every scenario and
+        every load case, from ONE factorisation (`batch.solve_member_sets`): `sets` is a list of scenarios, each a list
+        of up to 8 distinct member IDs; `factors` a list of the same shape with the area factor of every named member
+        (0 removed, below 1 damaged, above 1 strengthened; None: every member removed); `cases` a list of
+        `{jointID: vector}` dicts as `SolveLoadCases` takes them (None: the truss's own forces as one case).  Returns a
+        list, one entry per case, of lists with one record per scenario; a record holds
+          "members", "factors"   the scenario as given,
+          "pivots"        one per member, in the set's order: for removals the redundancy of the member once the members
+                          before it are gone (None after a failing position),
+          "unstable"      True when a pivot is <= `rTol` (default `batch.MEMBER_LOSS_R_TOL`): the truss is a mechanism -
+                          the peaks are then inf and their ids None,
+          "firstUnstable" the member ID at which the set makes the truss a mechanism (None: it stays stable),
+          "peakStress", "peakStressMember"           the largest |N| / a among the members that are not removed, and where,
+          "peakDisplacement", "peakDisplacementJoint"  the largest joint displacement, and where,
+          "forces"        (`returnForces`) {memberID: N} in the scenario, entries below 1e-10 dropped like the other
+                          results (None for an unstable scenario).
+        The truss's loads, its solved state and its results stay as they are.  Raises ValueError for a bad scenario (as
+        `batch.solve_member_sets`), `TrussNotStableError` when the counting test fails and `numpy.linalg.LinAlgError`
+        when the reduced stiffness matrix is not positive definite, as `Solve()` does."""
+        if not self.isStable:
+            raise TrussNotStableError("The truss is not stable !")
+        from .batch import MEMBER_LOSS_R_TOL, pack_trusses, solve_member_sets  # late import, as the other solvers
+        packed = pack_trusses([self])
+        nM = len(self._bars)
+        sets = [list(x) for x in sets]
+        if factors is not None:
+            factors = [[list(g) for g in factors]]
+        loads = None
+        if cases is not None:
+            cases = list(cases)
+            if not cases:
+                return []
+            loads = self._case_loads(cases, packed.nJ_max)
+        result = solve_member_sets(packed, [sets], factors, loads, r_tol=MEMBER_LOSS_R_TOL if rTol is None else rTol,
+                                   want_forces=returnForces)
+        if int(result.info[0]) != 0:
+            raise np.linalg.LinAlgError("Singular matrix")
+        out = []
+        for k in range(result.peak_stress.shape[1]):
+            records = []
+            for s, members in enumerate(sets):
+                unstable, first = bool(result.unstable[0, s]), int(result.first_unstable[0, s])
+                pivots = [float(p) for p in result.pivot[0, s, :len(members)]]
+                rec = {"members": [int(m) for m in members],
+                       "factors": [0.0] * len(members) if factors is None else [float(g) for g in factors[0][s]],
+                       "pivots": [None if p != p else p for p in pivots], "unstable": unstable,
+                       "firstUnstable": int(members[first]) if unstable else None,
+                       "peakStress": float(result.peak_stress[0, k, s]),
+                       "peakStressMember": None if result.peak_member[0, k, s] < 0 else int(result.peak_member[0, k, s]),
+                       "peakDisplacement": float(result.peak_displace[0, k, s]),
+                       "peakDisplacementJoint": None if result.peak_joint[0, k, s] < 0 else int(result.peak_joint[0, k, s])}
+                if returnForces:
+                    n = result.internal_after[0, k, s, :nM]
+                    rec["forces"] = None if unstable else \
+                        {int(m): float(n[m]) for m in np.flatnonzero(np.abs(n) >= ZERO_EPS)}
+                records.append(rec)
             out.append(records)
         return out
 
