@@ -184,6 +184,10 @@ def load():
     global _lib
     if _lib is not None:
         return _lib
+    # torch first: it brings a HIP runtime of its own, and in a process that loads the system's runtime (through this
+    # library) before torch's, every later call finds no device (hipError 100) - `solve_influence` asks
+    # trs_influence_fits before it touches torch
+    import torch  # noqa: F401
     if not os.path.exists(LIB_PATH):
         raise HipExtensionError(
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "

@@ -460,6 +460,13 @@ def _round_up16(x):
     return -(-int(x) // 16) * 16
 
 
+def _chunk_columns(chunk, nM_max=None):
+    """The columns C of one substitution of the column analyses: `chunk` rounded up to a multiple of 16 (one case group),
+    and no more than `nM_max` rounded up, when given."""
+    C = _round_up16(chunk)
+    return C if nM_max is None else max(16, min(C, _round_up16(nM_max)))
+
+
 def plan_member_sets(sets, chunk, nM_max=None):
     """The ranges `DeviceBatch.member_sets` takes the scenario axis in.  `sets`: int array [B, S, K] of member ids, -1
     padding at the end of a set; `chunk`: columns per substitution, rounded up to C, a multiple of 16 (and no more than
@@ -471,9 +478,7 @@ def plan_member_sets(sets, chunk, nM_max=None):
     numpy: no device is needed."""
     sets = np.asarray(sets)
     B, S, K = sets.shape
-    C = _round_up16(chunk)
-    if nM_max is not None:
-        C = max(16, min(C, _round_up16(nM_max)))
+    C = _chunk_columns(chunk, nM_max)
     if K > C:
         raise ValueError(f"plan_member_sets: a set of {K} members does not fit {C} columns")
     width = int(sets.max(initial=-1)) + 1 if nM_max is None else int(nM_max)
@@ -933,6 +938,16 @@ class DeviceBatch:
             X = self.torch.empty([self.B, L, self.rows], dtype=self.torch.float64, device=self.device)
         return X
 
+    def _check_loads(self, what, loads):
+        """`loads` of `what`(), contiguous: a float64 tensor [B, L, nJ_max, 3] on this batch's device, or ValueError."""
+        if loads.dim() != 4 or tuple(loads.shape[:1]) + tuple(loads.shape[2:]) != (self.B, self.nJ_max, 3) \
+                or loads.dtype != self.torch.float64 or loads.device != self.device:
+            raise ValueError(f"{what}(): loads must be float64 [B={self.B}, L, nJ_max={self.nJ_max}, 3] on {self.device}")
+        return loads.contiguous()
+
+    def _case_shapes(self, L):
+        return {"u": [self.B, L, self.nJ_max, 3], "f_ext": [self.B, L, self.nJ_max, 3], "N": [self.B, L, self.nM_max]}
+
     def _case_launch(self):
         """What every launch of these methods is given: joint_out's pointer (or None), the current stream, and the infix
         of the entry points of this batch's member form."""
@@ -951,13 +966,9 @@ class DeviceBatch:
         exactly u, f_ext and N, not the caller's dict object); `self.info` holds the factorisation's status per truss."""
         t = self.torch
         self._need_factor("solve_cases")
-        if loads.dim() != 4 or tuple(loads.shape[:1]) + tuple(loads.shape[2:]) != (self.B, self.nJ_max, 3) \
-                or loads.dtype != t.float64 or loads.device != self.device:
-            raise ValueError(f"solve_cases(): loads must be float64 [B={self.B}, L, nJ_max={self.nJ_max}, 3] on {self.device}")
-        loads = loads.contiguous()
+        loads = self._check_loads("solve_cases", loads)
         L = int(loads.shape[1])
-        out = self._out_tensors("solve_cases", {"u": [self.B, L, self.nJ_max, 3], "f_ext": [self.B, L, self.nJ_max, 3],
-                                                "N": [self.B, L, self.nM_max]}, out)
+        out = self._out_tensors("solve_cases", self._case_shapes(L), out)
         if self.B == 0 or L == 0:
             return out
         if not self.lib.trs_recover_cases_fits(self.nJ_max, self.nM_max):
@@ -1014,7 +1025,7 @@ class DeviceBatch:
             given[name] = x.contiguous()
         if L is None:
             raise ValueError("solve_effect_cases(): give at least one of loads, prestrain, settlement, accel")
-        shapes = {"u": [self.B, L, self.nJ_max, 3], "f_ext": [self.B, L, self.nJ_max, 3], "N": [self.B, L, self.nM_max]}
+        shapes = self._case_shapes(L)
         if want_body:
             shapes["body"] = [self.B, L, self.nJ_max, 3]
         out = self._out_tensors("solve_effect_cases", shapes, out)
@@ -1115,6 +1126,36 @@ class DeviceBatch:
         self.cases_Lam = Lam
         return out
 
+    # -- the analyses on the columns z_e = inv(K_ff) b_e,f: member_loss, member_sets, influence ------------------
+    def _check_columns(self, what, chunk, r_tol=None):
+        """The `chunk` (and `r_tol`) errors of a column analysis, under the calling method's name."""
+        if r_tol is not None and not 0.0 < float(r_tol) < 1.0:
+            raise ValueError(f"{what}(): r_tol must lie in (0, 1), got {r_tol!r}")
+        if int(chunk) < 1:
+            raise ValueError(f"{what}(): chunk must be at least 1, got {chunk!r}")
+
+    def _columns(self, C, ranges, cols=None):
+        """The loop of the column analyses, as a generator.  For every range of `ranges` the rows b_e,f of up to C members
+        go into Z [B, C, rows] - the members range .. range + C - 1 (`trs_loss_rhs`), or with `cols` those that the device
+        id list `cols(range)` [B, C] names (`trs_sets_rhs`) -, one `trs_potrs_cases` turns them into the columns
+        z_e = inv(K_ff) b_e,f, and (Z, range) is yielded to the analysis's own kernel.  The caller iterates with this batch's
+        device current (`torch.cuda.device`): the launches here run inside its loop."""
+        t = self.torch
+        # the range's columns: B * C * rows doubles (1.5 GB for bar-942 x 4096 at chunk 64) beside the slab, not counted
+        # in `max_slab_bytes`, and released when the analysis returns
+        Z = t.empty([self.B, C, self.rows], dtype=t.float64, device=self.device)
+        stream, tab = self._case_launch()[1:]
+        for rng in ranges:
+            if cols is None:
+                name, first, last = f"trs_loss{tab}_rhs", (rng, C), ()
+            else:
+                name, first, last = f"trs_sets{tab}_rhs", (C,), (cols(rng).data_ptr(),)
+            _capi.check(getattr(self.lib, name)(
+                self.B, *first, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *self._members(), self.free_index.data_ptr(),
+                self.n_free.data_ptr(), self.nM.data_ptr(), *last, Z.data_ptr(), self.rows, stream), name)
+            self._potrs_cases(Z, C)
+            yield Z, rng
+
     # -- member-loss analysis: every single-member removal from the resident factor (include/trs_loss.h) ------------------
     def member_loss(self, loads, r_tol=MEMBER_LOSS_R_TOL, want_forces=False, chunk=64, out=None,
                     max_result_bytes=4 << 30):
@@ -1133,23 +1174,16 @@ class DeviceBatch:
         member forces without member e (NaN for a critical member); refused with ValueError when it would exceed
         `max_result_bytes`.  `out`: such a dict to write into.  `generation` is bumped by the `solve_cases` inside and
         the forward state is that call's: `adjoint_cases` differentiates the intact state afterwards."""
-        t = self.torch
         self._need_factor("member_loss")
-        if loads.dim() != 4 or tuple(loads.shape[:1]) + tuple(loads.shape[2:]) != (self.B, self.nJ_max, 3) \
-                or loads.dtype != t.float64 or loads.device != self.device:
-            raise ValueError(f"member_loss(): loads must be float64 [B={self.B}, L, nJ_max={self.nJ_max}, 3] on {self.device}")
-        if not 0.0 < float(r_tol) < 1.0:
-            raise ValueError(f"member_loss(): r_tol must lie in (0, 1), got {r_tol!r}")
-        if int(chunk) < 1:
-            raise ValueError(f"member_loss(): chunk must be at least 1, got {chunk!r}")
+        loads = self._check_loads("member_loss", loads)
+        self._check_columns("member_loss", chunk, r_tol)
         B, L, nJ_max, nM_max = self.B, int(loads.shape[1]), self.nJ_max, self.nM_max
         if want_forces and B * L * nM_max * nM_max * 8 > max_result_bytes:
             raise ValueError(f"member_loss(): N_after [B={B}, L={L}, {nM_max}, {nM_max}] takes {B * L * nM_max * nM_max * 8} "
                              f"bytes, more than max_result_bytes = {max_result_bytes}")
-        i32 = t.int32
-        shapes = {"u": [B, L, nJ_max, 3], "f_ext": [B, L, nJ_max, 3], "N": [B, L, nM_max], "r": [B, nM_max],
-                  "critical": ([B, nM_max], i32), "peak_stress": [B, L, nM_max], "peak_member": ([B, L, nM_max], i32),
-                  "peak_displace": [B, L, nM_max], "peak_joint": ([B, L, nM_max], i32)}
+        i32 = self.torch.int32
+        shapes = dict(self._case_shapes(L), r=[B, nM_max], critical=([B, nM_max], i32), peak_stress=[B, L, nM_max],
+                      peak_member=([B, L, nM_max], i32), peak_displace=[B, L, nM_max], peak_joint=([B, L, nM_max], i32))
         if want_forces:
             shapes["N_after"] = [B, L, nM_max, nM_max]
         out = self._out_tensors("member_loss", shapes, out)
@@ -1159,25 +1193,15 @@ class DeviceBatch:
         self.solve_cases(loads, out={k: out[k] for k in ("u", "f_ext", "N")})
         if B == 0 or L == 0 or nM_max == 0:
             return out
-        C = min(-(-int(chunk) // 16) * 16, -(-nM_max // 16) * 16)
-        # the chunk's columns: B * C * rows doubles (1.5 GB for bar-942 x 4096 at chunk 64) beside the slab, not counted
-        # in `max_slab_bytes`, and released when this call returns
-        Z = t.empty([B, C, self.rows], dtype=t.float64, device=self.device)
+        C = _chunk_columns(chunk, nM_max)
         jo, stream, tab = self._case_launch()
-        rhs, apply = getattr(self.lib, f"trs_loss{tab}_rhs"), getattr(self.lib, f"trs_loss{tab}_apply")
-        with t.cuda.device(self.device):
-            for e0 in range(0, nM_max, C):
-                _capi.check(rhs(B, e0, C, nJ_max, nM_max, self.xyz.data_ptr(), *self._members(),
-                                self.free_index.data_ptr(), self.n_free.data_ptr(), self.nM.data_ptr(), Z.data_ptr(),
-                                self.rows, stream), f"trs_loss{tab}_rhs")
-                self._potrs_cases(Z, C)
-                _capi.check(apply(B, L, e0, C, nJ_max, nM_max, self.xyz.data_ptr(), *self._members(),
-                                  self.free_index.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), Z.data_ptr(),
-                                  self.cases_F.data_ptr(), self.rows, float(r_tol), out["r"].data_ptr(),
-                                  out["critical"].data_ptr(), out["peak_stress"].data_ptr(),
-                                  out["peak_member"].data_ptr(), out["peak_displace"].data_ptr(),
-                                  out["peak_joint"].data_ptr(), _ptr(out.get("N_after")), jo, stream),
-                            f"trs_loss{tab}_apply")
+        results = [out[k].data_ptr() for k in ("r", "critical", "peak_stress", "peak_member", "peak_displace", "peak_joint")]
+        with self.torch.cuda.device(self.device):
+            for Z, e0 in self._columns(C, range(0, nM_max, C)):
+                _capi.check(getattr(self.lib, f"trs_loss{tab}_apply")(
+                    B, L, e0, C, nJ_max, nM_max, self.xyz.data_ptr(), *self._members(), self.free_index.data_ptr(),
+                    self.nJ.data_ptr(), self.nM.data_ptr(), Z.data_ptr(), self.cases_F.data_ptr(), self.rows, float(r_tol),
+                    *results, _ptr(out.get("N_after")), jo, stream), f"trs_loss{tab}_apply")
         return out
 
     # -- member-set scenarios: up to eight members removed or resized at once (include/trs_sets.h) ------------------
@@ -1205,15 +1229,9 @@ class DeviceBatch:
         [B, L, S, nJ_max, 3] (caller's joint numbering; NaN for an unstable scenario), together refused with ValueError
         above `max_result_bytes`.  `out`: such a dict to write into.  `generation` is bumped by the `solve_cases`
         inside and the forward state is that call's, exactly as after `member_loss`."""
-        t = self.torch
         self._need_factor("member_sets")
-        if loads.dim() != 4 or tuple(loads.shape[:1]) + tuple(loads.shape[2:]) != (self.B, self.nJ_max, 3) \
-                or loads.dtype != t.float64 or loads.device != self.device:
-            raise ValueError(f"member_sets(): loads must be float64 [B={self.B}, L, nJ_max={self.nJ_max}, 3] on {self.device}")
-        if not 0.0 < float(r_tol) < 1.0:
-            raise ValueError(f"member_sets(): r_tol must lie in (0, 1), got {r_tol!r}")
-        if int(chunk) < 1:
-            raise ValueError(f"member_sets(): chunk must be at least 1, got {chunk!r}")
+        loads = self._check_loads("member_sets", loads)
+        self._check_columns("member_sets", chunk, r_tol)
         B, L, nJ_max, nM_max = self.B, int(loads.shape[1]), self.nJ_max, self.nM_max
         sets, gamma = _member_set_arrays("member_sets()", sets, gamma, B, None, nM_max)
         S = int(sets.shape[1])
@@ -1221,11 +1239,10 @@ class DeviceBatch:
         if extra > max_result_bytes:
             raise ValueError(f"member_sets(): N_after / u_after of [B={B}, L={L}, S={S}] scenarios take {extra} bytes, "
                              f"more than max_result_bytes = {max_result_bytes}")
-        i32 = t.int32
-        shapes = {"u": [B, L, nJ_max, 3], "f_ext": [B, L, nJ_max, 3], "N": [B, L, nM_max],
-                  "pivot": [B, S, MEMBER_SETS_MAX], "unstable": ([B, S], i32), "first_unstable": ([B, S], i32),
-                  "peak_stress": [B, L, S], "peak_member": ([B, L, S], i32), "peak_displace": [B, L, S],
-                  "peak_joint": ([B, L, S], i32)}
+        i32 = self.torch.int32
+        shapes = dict(self._case_shapes(L), pivot=[B, S, MEMBER_SETS_MAX], unstable=([B, S], i32),
+                      first_unstable=([B, S], i32), peak_stress=[B, L, S], peak_member=([B, L, S], i32),
+                      peak_displace=[B, L, S], peak_joint=([B, L, S], i32))
         if want_forces:
             shapes["N_after"] = [B, L, S, nM_max]
         if want_displace:
@@ -1239,27 +1256,19 @@ class DeviceBatch:
             return out
         plan = plan_member_sets(sets, chunk, nM_max)
         C = int(plan[0][2].shape[1])
-        # the range's columns: B * C * rows doubles beside the slab, as `member_loss` takes them
-        Z = t.empty([B, C, self.rows], dtype=t.float64, device=self.device)
         jo, stream, tab = self._case_launch()
-        rhs, apply = getattr(self.lib, f"trs_sets{tab}_rhs"), getattr(self.lib, f"trs_sets{tab}_apply")
-        up = lambda a: t.from_numpy(np.ascontiguousarray(a)).to(self.device)
-        with t.cuda.device(self.device):
-            for s0, s1, cols, slot in plan:
-                cols, slot = up(cols), up(slot)
-                factors = None if gamma is None else up(gamma[:, s0:s1])
-                _capi.check(rhs(B, C, nJ_max, nM_max, self.xyz.data_ptr(), *self._members(), self.free_index.data_ptr(),
-                                self.n_free.data_ptr(), self.nM.data_ptr(), cols.data_ptr(), Z.data_ptr(), self.rows,
-                                stream), f"trs_sets{tab}_rhs")
-                self._potrs_cases(Z, C)
-                _capi.check(apply(B, L, S, s0, s1 - s0, C, nJ_max, nM_max, self.xyz.data_ptr(), *self._members(),
-                                  self.free_index.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), cols.data_ptr(),
-                                  slot.data_ptr(), _ptr(factors), Z.data_ptr(), self.cases_F.data_ptr(), self.rows,
-                                  float(r_tol), out["pivot"].data_ptr(), out["unstable"].data_ptr(),
-                                  out["first_unstable"].data_ptr(), out["peak_stress"].data_ptr(),
-                                  out["peak_member"].data_ptr(), out["peak_displace"].data_ptr(),
-                                  out["peak_joint"].data_ptr(), _ptr(out.get("N_after")), _ptr(out.get("u_after")), jo,
-                                  stream), f"trs_sets{tab}_apply")
+        results = [out[k].data_ptr() for k in ("pivot", "unstable", "first_unstable", "peak_stress", "peak_member",
+                                               "peak_displace", "peak_joint")]
+        up = lambda a: None if a is None else self.torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+        uploaded = ((s0, s1, up(cols), up(slot), up(None if gamma is None else gamma[:, s0:s1]))
+                    for s0, s1, cols, slot in plan)   # (a generator: one range at a time, as the loop comes to it)
+        with self.torch.cuda.device(self.device):
+            for Z, (s0, s1, cols, slot, factors) in self._columns(C, uploaded, cols=lambda rng: rng[2]):
+                _capi.check(getattr(self.lib, f"trs_sets{tab}_apply")(
+                    B, L, S, s0, s1 - s0, C, nJ_max, nM_max, self.xyz.data_ptr(), *self._members(),
+                    self.free_index.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), cols.data_ptr(), slot.data_ptr(),
+                    _ptr(factors), Z.data_ptr(), self.cases_F.data_ptr(), self.rows, float(r_tol), *results,
+                    _ptr(out.get("N_after")), _ptr(out.get("u_after")), jo, stream), f"trs_sets{tab}_apply")
         return out
 
     # -- influence lines and moving-load envelopes from the resident factor (include/trs_influence.h) ------------------
@@ -1297,8 +1306,7 @@ class DeviceBatch:
         P_max, A = int(path.shape[1]), int(train_w.shape[0])
         if A < 1:
             raise ValueError("influence(): the train has no axle")
-        if int(chunk) < 1:
-            raise ValueError(f"influence(): chunk must be at least 1, got {chunk!r}")
+        self._check_columns("influence", chunk)
         shapes = {k: [B, nM_max] for k in ("N_max", "N_min", "x_max", "x_min", "area_pos", "area_neg")}
         if want_lines:
             shapes["eta"] = [B, nM_max, P_max]
@@ -1308,24 +1316,16 @@ class DeviceBatch:
                                     "exceeds the LDS of the apply kernel (trs_influence_fits)")
         if B == 0 or nM_max == 0:
             return out
-        C = min(-(-int(chunk) // 16) * 16, -(-nM_max // 16) * 16)
-        # the chunk's columns: B * C * rows doubles beside the slab, as `member_loss` takes them
-        Z = t.empty([B, C, self.rows], dtype=t.float64, device=self.device)
+        C = _chunk_columns(chunk, nM_max)
         jo, stream, tab = self._case_launch()
-        rhs, apply = getattr(self.lib, f"trs_loss{tab}_rhs"), getattr(self.lib, f"trs_influence{tab}_apply")
-        with t.cuda.device(self.device):
-            for e0 in range(0, nM_max, C):
-                _capi.check(rhs(B, e0, C, nJ_max, nM_max, self.xyz.data_ptr(), *self._members(),
-                                self.free_index.data_ptr(), self.n_free.data_ptr(), self.nM.data_ptr(), Z.data_ptr(),
-                                self.rows, stream), f"trs_loss{tab}_rhs")
-                self._potrs_cases(Z, C)
-                _capi.check(apply(B, e0, C, nJ_max, nM_max, P_max, A, self.xyz.data_ptr(), *self._members(),
-                                  self.free_index.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), path.data_ptr(),
-                                  path_len.data_ptr(), direction.data_ptr(), train_w.data_ptr(), train_o.data_ptr(),
-                                  Z.data_ptr(), self.rows, _ptr(out.get("eta")), out["N_max"].data_ptr(),
-                                  out["N_min"].data_ptr(), out["x_max"].data_ptr(), out["x_min"].data_ptr(),
-                                  out["area_pos"].data_ptr(), out["area_neg"].data_ptr(), jo, stream),
-                            f"trs_influence{tab}_apply")
+        results = [out[k].data_ptr() for k in ("N_max", "N_min", "x_max", "x_min", "area_pos", "area_neg")]
+        with self.torch.cuda.device(self.device):
+            for Z, e0 in self._columns(C, range(0, nM_max, C)):
+                _capi.check(getattr(self.lib, f"trs_influence{tab}_apply")(
+                    B, e0, C, nJ_max, nM_max, P_max, A, self.xyz.data_ptr(), *self._members(), self.free_index.data_ptr(),
+                    self.nJ.data_ptr(), self.nM.data_ptr(), path.data_ptr(), path_len.data_ptr(), direction.data_ptr(),
+                    train_w.data_ptr(), train_o.data_ptr(), Z.data_ptr(), self.rows, _ptr(out.get("eta")), *results, jo,
+                    stream), f"trs_influence{tab}_apply")
         return out
 
     # -- natural frequencies and mode shapes from the resident factor (include/trs_modes.h) ------------------
@@ -2674,9 +2674,51 @@ def _device_f64(torch, dev, x, vectors=False):
 
 
 def _host_result(torch, dev, res):
-    """A result dataclass of device tensors as the same dataclass of numpy arrays."""
+    """A result dataclass of device tensors as the same dataclass of numpy arrays (None stays None)."""
     torch.cuda.synchronize(dev)
-    return type(res)(**{k: v.cpu().numpy() for k, v in vars(res).items()})
+    return type(res)(**{k: None if v is None else v.cpu().numpy() for k, v in vars(res).items()})
+
+
+def _host_array(x, dtype):
+    """An array argument (numpy, torch or nested lists) as a host array of `dtype` (None: its own)."""
+    if not isinstance(x, np.ndarray) and hasattr(x, "detach"):
+        x = x.detach().cpu().numpy()
+    return np.asarray(x, dtype=dtype)
+
+
+def _peak_fields(*shape):
+    """The `FIELDS` entries that `MemberLossResult` and `MemberSetResult` share: the two peaks and where they occur."""
+    return {"peak_stress": ("peak_stress", 0.0, "float64", shape), "peak_member": ("peak_member", -1, "int32", shape),
+            "peak_displace": ("peak_displace", 0.0, "float64", shape), "peak_joint": ("peak_joint", -1, "int32", shape)}
+
+
+def _new_result(torch, dev, cls, B, sizes, without=()):
+    """A result dataclass of an analysis on the resident factor on `dev`, from its table `cls.FIELDS`: field -> (key of the
+    `DeviceBatch` method's dict, fill value, dtype, shape after B).  The shape names its sizes ("L", "S", "P", "nJ",
+    "nM": looked up in `sizes`); "bool" is kept as int32 until `_finish_result`.  Fields named in `without` (optional
+    results that were not asked for) are None; `info` [B] is int32 zeros."""
+    made = {field: None if field in without else
+            torch.full([B] + [sizes.get(n, n) for n in shape], fill, device=dev,
+                       dtype=torch.int32 if dtype == "bool" else getattr(torch, dtype))
+            for field, (key, fill, dtype, shape) in cls.FIELDS.items()}
+    return cls(**made, info=torch.zeros([B], dtype=torch.int32, device=dev))
+
+
+def _put_result(part, out, res):
+    """A bucket's results `res` (the dict of the `DeviceBatch` method) into the full-batch dataclass `out`: the "nJ" and
+    "nM" places of a field's shape are the axes `_Bucket.put` narrows; a key that `res` lacks keeps its fill value."""
+    for field, (key, fill, dtype, shape) in type(out).FIELDS.items():
+        if getattr(out, field) is not None and key in res:
+            part.put(getattr(out, field), res[key], nJ=shape.index("nJ") + 1 if "nJ" in shape else None,
+                     nM=tuple(i + 1 for i, n in enumerate(shape) if n == "nM"))
+
+
+def _finish_result(torch, dev, out, on_device):
+    """The flags of `out` as bool, and the whole on the host unless `on_device`."""
+    for field, (key, fill, dtype, shape) in type(out).FIELDS.items():
+        if dtype == "bool":
+            setattr(out, field, getattr(out, field) != 0)
+    return out if on_device else _host_result(torch, dev, out)
 
 
 class _Bucket:
@@ -2736,20 +2778,19 @@ class LoadCaseResult:
     internal: np.ndarray
     info: np.ndarray
 
+    FIELDS = {"displace": ("u", 0.0, "float64", ("L", "nJ", 3)), "external": ("f_ext", 0.0, "float64", ("L", "nJ", 3)),
+              "internal": ("N", 0.0, "float64", ("L", "nM"))}
+
 
 def _load_cases_on_device(torch, dev, packed, loads, max_slab_bytes, reorder, options, use_envelope, after=None):
     """The forward pass of `solve_load_cases` and `solve_gradients`: `loads` float64 [B, L, nJ_max, 3] on `dev`, the
     buckets as `_factored_buckets` makes them; `after(db, part, res)` runs per bucket on the solved cases.  Returns a
     `LoadCaseResult` of device tensors."""
-    B, L, nJ_max, nM_max = packed.B, int(loads.shape[1]), packed.nJ_max, packed.nM_max
-    zeros = lambda *shape: torch.zeros(list(shape), dtype=torch.float64, device=dev)
-    out = LoadCaseResult(zeros(B, L, nJ_max, 3), zeros(B, L, nJ_max, 3), zeros(B, L, nM_max),
-                         torch.zeros([B], dtype=torch.int32, device=dev))
+    L = int(loads.shape[1])
+    out = _new_result(torch, dev, LoadCaseResult, packed.B, {"L": L, "nJ": packed.nJ_max, "nM": packed.nM_max})
     for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope, cases=L):
         res = db.solve_cases(part.cut(loads, nJ=2))
-        part.put(out.displace, res["u"], nJ=2)
-        part.put(out.external, res["f_ext"], nJ=2)
-        part.put(out.internal, res["N"], nM=2)
+        _put_result(part, out, res)
         if after is not None:
             after(db, part, res)
     return out
@@ -2790,6 +2831,8 @@ class EffectCaseResult:
     body: np.ndarray
     info: np.ndarray
 
+    FIELDS = dict(LoadCaseResult.FIELDS, body=("body", 0.0, "float64", ("L", "nJ", 3)))
+
 
 def _check_effect_args(packed, loads, prestrain, settlement, accel, sections):
     """The argument errors of `solve_effect_cases` that need no device.  Returns (L, arrays): the given arguments as
@@ -2803,9 +2846,7 @@ def _check_effect_args(packed, loads, prestrain, settlement, accel, sections):
     for name, x in (("loads", loads), ("prestrain", prestrain), ("settlement", settlement), ("accel", accel)):
         if x is None:
             continue
-        if not isinstance(x, np.ndarray) and hasattr(x, "detach"):
-            x = x.detach().cpu().numpy()
-        x = np.asarray(x, dtype=np.float64)
+        x = _host_array(x, np.float64)
         vector = name != "prestrain"
         shape = tuple(x.shape)
         if vector:
@@ -2864,18 +2905,12 @@ def solve_effect_cases(trusses_or_packed, loads=None, prestrain=None, settlement
     packed = _as_packed(trusses_or_packed)
     L, arrays = _check_effect_args(packed, loads, prestrain, settlement, accel, sections)
     torch, dev = _require_gpu(device)
-    B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
     given = {k: _device_f64(torch, dev, v) for k, v in arrays.items()}
-    zeros = lambda *shape: torch.zeros(list(shape), dtype=torch.float64, device=dev)
-    out = EffectCaseResult(zeros(B, L, nJ_max, 3), zeros(B, L, nJ_max, 3), zeros(B, L, nM_max), zeros(B, L, nJ_max, 3),
-                           torch.zeros([B], dtype=torch.int32, device=dev))
+    out = _new_result(torch, dev, EffectCaseResult, packed.B, {"L": L, "nJ": packed.nJ_max, "nM": packed.nM_max})
     axis = {"loads": dict(nJ=2), "prestrain": dict(nM=2), "settlement": dict(nJ=2), "accel": {}}
     for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope, cases=L):
-        res = db.solve_effect_cases(**{k: part.cut(given.get(k), **axis[k]) for k in axis}, want_body=True)
-        part.put(out.displace, res["u"], nJ=2)
-        part.put(out.external, res["f_ext"], nJ=2)
-        part.put(out.internal, res["N"], nM=2)
-        part.put(out.body, res["body"], nJ=2)
+        _put_result(part, out, db.solve_effect_cases(**{k: part.cut(given.get(k), **axis[k]) for k in axis},
+                                                     want_body=True))
     return out if on_device else _host_result(torch, dev, out)
 
 
@@ -2889,6 +2924,9 @@ class GradientResult:
     dxyz: np.ndarray
     dloads: np.ndarray
     info: np.ndarray
+
+    FIELDS = {"dA": ("A", 0.0, "float64", ("nM",)), "dE": ("E", 0.0, "float64", ("nM",)),
+              "dxyz": ("xyz", 0.0, "float64", ("nJ", 3)), "dloads": ("loads", 0.0, "float64", ("L", "nJ", 3))}
 
 
 def _check_gradient_args(B, nJ_max, nM_max, loads, cotangents, loss, sections):
@@ -2936,10 +2974,7 @@ def solve_gradients(trusses_or_packed, loads, grad_u=None, grad_f_ext=None, grad
         raise ValueError(f"solve_gradients: want must name some of {DeviceBatch.GRADIENTS}, got {want}")
     torch, dev = _require_gpu(device)
     cots = {k: _device_f64(torch, dev, g, vectors=k != "grad_N") for k, g in cots.items()}
-    zeros = lambda *shape: torch.zeros(list(shape), dtype=torch.float64, device=dev)
-    grads = GradientResult(zeros(B, nM_max), zeros(B, nM_max), zeros(B, nJ_max, 3), zeros(B, L, nJ_max, 3), None)
-    dst = {"A": (grads.dA, dict(nM=1)), "E": (grads.dE, dict(nM=1)), "xyz": (grads.dxyz, dict(nJ=1)),
-           "loads": (grads.dloads, dict(nJ=2))}
+    grads = _new_result(torch, dev, GradientResult, B, {"L": L, "nJ": nJ_max, "nM": nM_max})
 
     def adjoint(db, part, res):
         if loss is not None:
@@ -2947,8 +2982,7 @@ def solve_gradients(trusses_or_packed, loads, grad_u=None, grad_f_ext=None, grad
         else:
             gu, gf = part.cut(cots["grad_u"], nJ=2), part.cut(cots["grad_f_ext"], nJ=2)
             gN = part.cut(cots["grad_N"], nM=2)
-        for key, val in db.adjoint_cases(gu, gf, gN, want=want).items():
-            part.put(dst[key][0], val, **dst[key][1])
+        _put_result(part, grads, db.adjoint_cases(gu, gf, gN, want=want))   # (the gradients named in `want`)
 
     out = _load_cases_on_device(torch, dev, packed, _device_f64(torch, dev, loads, vectors=True), max_slab_bytes,
                                 reorder, options, use_envelope, after=adjoint)
@@ -3049,34 +3083,45 @@ class MemberLossResult:
     internal_after: np.ndarray
     info: np.ndarray
 
+    FIELDS = dict(LoadCaseResult.FIELDS, redundancy=("r", 0.0, "float64", ("nM",)), critical=("critical", 0, "bool", ("nM",)),
+                  **_peak_fields("L", "nM"), internal_after=("N_after", 0.0, "float64", ("L", "nM", "nM")))
+
+
+def _check_chunk(who, chunk):
+    """`chunk` of a `solve_*` wrapper of the column analyses: an integer of at least 1, or ValueError in `who`'s name."""
+    if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
+        raise ValueError(f"{who}: chunk must be an integer of at least 1, got {chunk!r}")
+
+
+def _check_column_args(who, what, packed, loads, r_tol, sections, chunk):
+    """The argument errors that `solve_member_loss` and `solve_member_sets` (`who`) share.  Returns the loads as a
+    contiguous float64 host array [B, L, nJ_max, 3] (`loads=None`: the batch's own loads as one case)."""
+    if sections is not None:
+        raise ValueError(f"{who}: sections= variants cannot be combined with the {what} analysis")
+    if isinstance(r_tol, bool) or not isinstance(r_tol, (int, float, np.floating)) or not 0.0 < float(r_tol) < 1.0:
+        raise ValueError(f"{who}: r_tol must lie in (0, 1), got {r_tol!r}")
+    _check_chunk(who, chunk)
+    B, nJ_max = packed.B, packed.nJ_max
+    x = np.asarray(packed.loads, dtype=np.float64)[:, None] if loads is None else _host_array(loads, np.float64)
+    shape = tuple(x.shape)
+    if len(shape) != 4 or shape[0] != B or shape[2] != nJ_max or shape[3] not in (2, 3):
+        raise ValueError(f"{who}: loads must be [B={B}, L, nJ_max={nJ_max}, 2 or 3], got {shape}")
+    if not np.isfinite(x).all():
+        raise ValueError(f"{who}: loads has a non-finite entry")
+    if shape[3] == 2:
+        x = np.concatenate([x, np.zeros(shape[:3] + (1,))], axis=-1)
+    return np.ascontiguousarray(x)
+
 
 def _check_member_loss_args(packed, loads, r_tol, sections, want_forces=False, max_result_bytes=4 << 30, chunk=64):
     """The argument errors of `solve_member_loss` that need no device.  Returns the loads as a contiguous float64 host
     array [B, L, nJ_max, 3] (`loads=None`: the batch's own loads as one case)."""
-    if sections is not None:
-        raise ValueError("solve_member_loss: sections= variants cannot be combined with the member-loss analysis")
-    if isinstance(r_tol, bool) or not isinstance(r_tol, (int, float, np.floating)) or not 0.0 < float(r_tol) < 1.0:
-        raise ValueError(f"solve_member_loss: r_tol must lie in (0, 1), got {r_tol!r}")
-    if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
-        raise ValueError(f"solve_member_loss: chunk must be an integer of at least 1, got {chunk!r}")
-    B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
-    if loads is None:
-        x = np.asarray(packed.loads, dtype=np.float64)[:, None]
-    else:
-        if not isinstance(loads, np.ndarray) and hasattr(loads, "detach"):
-            loads = loads.detach().cpu().numpy()
-        x = np.asarray(loads, dtype=np.float64)
-    shape = tuple(x.shape)
-    if len(shape) != 4 or shape[0] != B or shape[2] != nJ_max or shape[3] not in (2, 3):
-        raise ValueError(f"solve_member_loss: loads must be [B={B}, L, nJ_max={nJ_max}, 2 or 3], got {shape}")
-    if not np.isfinite(x).all():
-        raise ValueError("solve_member_loss: loads has a non-finite entry")
-    if shape[3] == 2:
-        x = np.concatenate([x, np.zeros(shape[:3] + (1,))], axis=-1)
+    x = _check_column_args("solve_member_loss", "member-loss", packed, loads, r_tol, sections, chunk)
+    B, nM_max, shape = packed.B, packed.nM_max, x.shape
     if want_forces and B * shape[1] * nM_max * nM_max * 8 > max_result_bytes:
         raise ValueError(f"solve_member_loss: internal_after [B={B}, L={shape[1]}, {nM_max}, {nM_max}] takes "
                          f"{B * shape[1] * nM_max * nM_max * 8} bytes, more than max_result_bytes = {max_result_bytes}")
-    return np.ascontiguousarray(x)
+    return x
 
 
 def solve_member_loss(trusses_or_packed, loads=None, r_tol=MEMBER_LOSS_R_TOL, want_forces=False, device=None,
@@ -3096,30 +3141,14 @@ def solve_member_loss(trusses_or_packed, loads=None, r_tol=MEMBER_LOSS_R_TOL, wa
     packed = _as_packed(trusses_or_packed)
     loads = _check_member_loss_args(packed, loads, r_tol, sections, want_forces, max_result_bytes, chunk)
     torch, dev = _require_gpu(device)
-    B, L, nJ_max, nM_max = packed.B, int(loads.shape[1]), packed.nJ_max, packed.nM_max
+    L = int(loads.shape[1])
     loads = _device_f64(torch, dev, loads)
-    full = lambda shape, value=0.0, dtype=torch.float64: torch.full(shape, value, dtype=dtype, device=dev)
-    i32 = torch.int32
-    out = MemberLossResult(full([B, L, nJ_max, 3]), full([B, L, nJ_max, 3]), full([B, L, nM_max]), full([B, nM_max]),
-                           full([B, nM_max], 0, i32), full([B, L, nM_max]), full([B, L, nM_max], -1, i32),
-                           full([B, L, nM_max]), full([B, L, nM_max], -1, i32),
-                           full([B, L, nM_max, nM_max]) if want_forces else None, full([B], 0, i32))
-    fields = (("displace", "u", dict(nJ=2)), ("external", "f_ext", dict(nJ=2)), ("internal", "N", dict(nM=2)),
-              ("redundancy", "r", dict(nM=1)), ("critical", "critical", dict(nM=1)),
-              ("peak_stress", "peak_stress", dict(nM=2)), ("peak_member", "peak_member", dict(nM=2)),
-              ("peak_displace", "peak_displace", dict(nM=2)), ("peak_joint", "peak_joint", dict(nM=2)))
+    out = _new_result(torch, dev, MemberLossResult, packed.B, {"L": L, "nJ": packed.nJ_max, "nM": packed.nM_max},
+                      without=() if want_forces else ("internal_after",))
     for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope, cases=L):
-        res = db.member_loss(part.cut(loads, nJ=2), r_tol=r_tol, want_forces=want_forces, chunk=chunk,
-                             max_result_bytes=max_result_bytes)
-        for field, key, axes in fields:
-            part.put(getattr(out, field), res[key], **axes)
-        if want_forces:
-            part.put(out.internal_after, res["N_after"], nM=(2, 3))
-    out.critical = out.critical != 0
-    if on_device:
-        return out
-    torch.cuda.synchronize(dev)
-    return MemberLossResult(**{k: None if v is None else v.cpu().numpy() for k, v in vars(out).items()})
+        _put_result(part, out, db.member_loss(part.cut(loads, nJ=2), r_tol=r_tol, want_forces=want_forces, chunk=chunk,
+                                              max_result_bytes=max_result_bytes))
+    return _finish_result(torch, dev, out, on_device)
 
 
 @dataclass
@@ -3148,17 +3177,17 @@ class MemberSetResult:
     displace_after: np.ndarray
     info: np.ndarray
 
+    FIELDS = dict(LoadCaseResult.FIELDS, pivot=("pivot", float("nan"), "float64", ("S", MEMBER_SETS_MAX)),
+                  unstable=("unstable", 0, "bool", ("S",)), first_unstable=("first_unstable", -1, "int32", ("S",)),
+                  **_peak_fields("L", "S"), internal_after=("N_after", 0.0, "float64", ("L", "S", "nM")),
+                  displace_after=("u_after", 0.0, "float64", ("L", "S", "nJ", 3)))
+
 
 def _check_member_sets_args(packed, sets, factors, loads, r_tol, sections, want_forces=False, want_displace=False,
                             max_result_bytes=4 << 30, chunk=64):
     """The argument errors of `solve_member_sets` that need no device.  Returns host arrays: sets int32 [B, S, 8],
     factors float64 [B, S, 8] or None, loads float64 [B, L, nJ_max, 3]."""
-    if sections is not None:
-        raise ValueError("solve_member_sets: sections= variants cannot be combined with the member-set analysis")
-    try:
-        loads = _check_member_loss_args(packed, loads, r_tol, None, chunk=chunk)
-    except ValueError as exc:
-        raise ValueError(str(exc).replace("solve_member_loss", "solve_member_sets")) from None
+    loads = _check_column_args("solve_member_sets", "member-set", packed, loads, r_tol, sections, chunk)
     B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
     sets, factors = _member_set_arrays("solve_member_sets", sets, factors, B, packed.nM, nM_max)
     extra = 8 * B * int(loads.shape[1]) * int(sets.shape[1]) * (nM_max * bool(want_forces) + 3 * nJ_max * bool(want_displace))
@@ -3191,34 +3220,16 @@ def solve_member_sets(trusses_or_packed, sets, factors=None, loads=None, r_tol=M
     sets, factors, loads = _check_member_sets_args(packed, sets, factors, loads, r_tol, sections, want_forces,
                                                    want_displace, max_result_bytes, chunk)
     torch, dev = _require_gpu(device)
-    B, L, S, nJ_max, nM_max = packed.B, int(loads.shape[1]), int(sets.shape[1]), packed.nJ_max, packed.nM_max
+    L = int(loads.shape[1])
     loads = _device_f64(torch, dev, loads)
-    full = lambda shape, value=0.0, dtype=torch.float64: torch.full(shape, value, dtype=dtype, device=dev)
-    i32, nan = torch.int32, float("nan")
-    out = MemberSetResult(full([B, L, nJ_max, 3]), full([B, L, nJ_max, 3]), full([B, L, nM_max]),
-                          full([B, S, MEMBER_SETS_MAX], nan), full([B, S], 0, i32), full([B, S], -1, i32),
-                          full([B, L, S]), full([B, L, S], -1, i32), full([B, L, S]), full([B, L, S], -1, i32),
-                          full([B, L, S, nM_max]) if want_forces else None,
-                          full([B, L, S, nJ_max, 3]) if want_displace else None, full([B], 0, i32))
-    fields = (("displace", "u", dict(nJ=2)), ("external", "f_ext", dict(nJ=2)), ("internal", "N", dict(nM=2)),
-              ("pivot", "pivot", {}), ("unstable", "unstable", {}), ("first_unstable", "first_unstable", {}),
-              ("peak_stress", "peak_stress", {}), ("peak_member", "peak_member", {}),
-              ("peak_displace", "peak_displace", {}), ("peak_joint", "peak_joint", {}))
+    out = _new_result(torch, dev, MemberSetResult, packed.B,
+                      {"L": L, "S": int(sets.shape[1]), "nJ": packed.nJ_max, "nM": packed.nM_max},
+                      without=(() if want_forces else ("internal_after",)) + (() if want_displace else ("displace_after",)))
     for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope, cases=L):
-        res = db.member_sets(part.cut(loads, nJ=2), sets[part.index], None if factors is None else factors[part.index],
-                             r_tol=r_tol, want_forces=want_forces, want_displace=want_displace, chunk=chunk,
-                             max_result_bytes=max_result_bytes)
-        for field, key, axes in fields:
-            part.put(getattr(out, field), res[key], **axes)
-        if want_forces:
-            part.put(out.internal_after, res["N_after"], nM=3)
-        if want_displace:
-            part.put(out.displace_after, res["u_after"], nJ=3)
-    out.unstable = out.unstable != 0
-    if on_device:
-        return out
-    torch.cuda.synchronize(dev)
-    return MemberSetResult(**{k: None if v is None else v.cpu().numpy() for k, v in vars(out).items()})
+        _put_result(part, out, db.member_sets(
+            part.cut(loads, nJ=2), sets[part.index], None if factors is None else factors[part.index], r_tol=r_tol,
+            want_forces=want_forces, want_displace=want_displace, chunk=chunk, max_result_bytes=max_result_bytes))
+    return _finish_result(torch, dev, out, on_device)
 
 
 @dataclass
@@ -3239,11 +3250,10 @@ class InfluenceResult:
     lines: np.ndarray
     info: np.ndarray
 
-
-def _host_array(x, dtype):
-    if not isinstance(x, np.ndarray) and hasattr(x, "detach"):
-        x = x.detach().cpu().numpy()
-    return np.asarray(x, dtype=dtype)
+    FIELDS = {"N_max": ("N_max", 0.0, "float64", ("nM",)), "N_min": ("N_min", 0.0, "float64", ("nM",)),
+              "x_max": ("x_max", float("nan"), "float64", ("nM",)), "x_min": ("x_min", float("nan"), "float64", ("nM",)),
+              "area_pos": ("area_pos", 0.0, "float64", ("nM",)), "area_neg": ("area_neg", 0.0, "float64", ("nM",)),
+              "lines": ("eta", 0.0, "float64", ("nM", "P"))}
 
 
 def _check_influence_args(packed, path, direction, train, sections, want_lines=False, max_result_bytes=4 << 30, chunk=64):
@@ -3251,8 +3261,7 @@ def _check_influence_args(packed, path, direction, train, sections, want_lines=F
     arrays: path int32 [B, P_max] (-1 padding), path_len int32 [B], direction float64 [B, 3], train_w, train_o [A]."""
     if sections is not None:
         raise ValueError("solve_influence: sections= variants cannot be combined with the influence analysis")
-    if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
-        raise ValueError(f"solve_influence: chunk must be an integer of at least 1, got {chunk!r}")
+    _check_chunk("solve_influence", chunk)
     B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
     # the path: a list of joint-id lists, or [B, P_max] with -1 padding
     if isinstance(path, (list, tuple)) and all(isinstance(row, (list, tuple)) for row in path):
@@ -3331,24 +3340,14 @@ def solve_influence(trusses_or_packed, path, direction, train=None, want_lines=F
     path, path_len, d, w, o = _check_influence_args(packed, path, direction, train, sections, want_lines,
                                                     max_result_bytes, chunk)
     torch, dev = _require_gpu(device)
-    B, nM_max, P_max = packed.B, packed.nM_max, int(path.shape[1])
     up = lambda a: torch.from_numpy(a).to(dev)
     path, path_len, d, w, o = up(path), up(path_len), up(d), up(w), up(o)
-    full = lambda shape, value=0.0, dtype=torch.float64: torch.full(shape, value, dtype=dtype, device=dev)
-    nan = float("nan")
-    out = InfluenceResult(full([B, nM_max]), full([B, nM_max]), full([B, nM_max], nan), full([B, nM_max], nan),
-                          full([B, nM_max]), full([B, nM_max]), full([B, nM_max, P_max]) if want_lines else None,
-                          full([B], 0, torch.int32))
+    out = _new_result(torch, dev, InfluenceResult, packed.B, {"nM": packed.nM_max, "P": int(path.shape[1])},
+                      without=() if want_lines else ("lines",))
     for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope, cases=1):
-        res = db.influence(part.cut(path), part.cut(path_len), part.cut(d), w, o, want_lines=want_lines, chunk=chunk)
-        for key in ("N_max", "N_min", "x_max", "x_min", "area_pos", "area_neg"):
-            part.put(getattr(out, key), res[key], nM=1)
-        if want_lines:
-            part.put(out.lines, res["eta"], nM=1)
-    if on_device:
-        return out
-    torch.cuda.synchronize(dev)
-    return InfluenceResult(**{k: None if v is None else v.cpu().numpy() for k, v in vars(out).items()})
+        _put_result(part, out, db.influence(part.cut(path), part.cut(path_len), part.cut(d), w, o,
+                                            want_lines=want_lines, chunk=chunk))
+    return _finish_result(torch, dev, out, on_device)
 
 
 def _is_pinned(packed):

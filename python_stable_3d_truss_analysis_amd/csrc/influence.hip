@@ -1,5 +1,5 @@
 // Influence lines and moving-load envelopes (include/trs_influence.h): the column z_m = inv(K_ff) b_m,f that the
-// member-loss analysis already forms (trs_loss_rhs, trs_potrs_cases, as they are) is, times k_m, the influence line of
+// member-loss analysis forms (trs_loss_rhs, trs_potrs_cases, as they are) is, times k_m, the influence line of
 // N_m for a unit load at every joint in every direction (Maxwell / Mueller-Breslau).  The one kernel here reads those
 // columns along a path, sweeps a load train over it and keeps the extremes.
 //
@@ -16,6 +16,7 @@
 // areas are summed segment by segment in ascending p.  Max and min are exact and every other number is one fixed
 // expression of staged values: the result of (b, m) does not depend on the chunk, the slice, B or the member form.
 #include "../../include/trs_influence.h"
+#include "trs_columns.h"
 #include "trs_common.h"
 #include "trs_recover.h"
 
@@ -25,9 +26,10 @@
 namespace {
 
 using namespace trs_rec;
+using trs_col::wave_extreme_index;
 
 constexpr int WAVES = 4;                    // waves per work-group; trs_influence_fits' rule counts their eta vectors
-constexpr size_t LDS_BUDGET = 160 * 1024;   // a CU's LDS: the ONE number behind trs_influence_fits and the launch
+using trs_col::LDS_BUDGET;                  // (behind trs_influence_fits and the launch too)
 #ifndef TRS_INFLUENCE_SLICE
 #define TRS_INFLUENCE_SLICE 16              // members per work-group
 #endif
@@ -60,20 +62,6 @@ __device__ __forceinline__ InfluenceTables influence_tables(double* sh, int nJ_m
     t.di = t.pj + P_max;
     t.inv = t.di + (size_t)3 * P_max;
     return t;
-}
-
-// (value, index) extreme over the wave: the larger (MAX) or the smaller value, the lower index among equal values
-template <bool MAX>
-__device__ __forceinline__ void wave_extreme_index(double& v, int& i) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ov = __shfl_xor(v, off);
-        const int oi = __shfl_xor(i, off);
-        if ((MAX ? ov > v : ov < v) || (ov == v && oi < i)) {
-            v = ov;
-            i = oi;
-        }
-    }
 }
 
 // eta_m at arc position t of a path of P >= 1 joints (s: its arc lengths, S = s[P - 1], eps = 1e-12 S), 0 off the path

@@ -3,107 +3,40 @@
 // column per DISTINCT member of a range of scenarios (trs_potrs_cases, cases.hip, as it is) and one k x k elimination
 // per scenario replace one factorisation per scenario.
 //
-//   trs_sets_rhs      Z [B][C][ld_f]: row i = b_e,f of e = cols[b][i] (trs_loss_row.h: the row of trs_loss_rhs)
+//   trs_sets_rhs      Z [B][C][ld_f]: row i = b_e,f of e = cols[b][i] (the rhs kernel of loss.hip)
 //   trs_potrs_cases   z_e = inv(K_ff) b_e,f
 //   trs_sets_apply    P_ij = c_i . D z_j,  A = I + diag(k) P diag(theta) = L U in the set's order,  a = theta inv(A) n,
 //                     u' = u - sum_j a_j z_j,  N'_m = gamma_m k_m c_m . D u', and the maxima of |k_m c_m . D u'| / A_m over
 //                     the members with gamma != 0 and of |u'_j| over the joints
 //
-// The apply kernel has the shape of trs_loss_apply (loss.hip): one work-group of four waves per (truss, slice of the
-// range's scenarios), the member table, the DOF map, joint_out and u and N of a pass of cases staged in LDS once.  Every
-// wave takes one scenario at a time.  Lane 8 i + j gathers P_ij from Z through free_index - the expression that forms
-// r_e in trs_loss_apply, so a single removal's pivot has r_e's bits - and holds A_ij during the elimination, which runs
-// in lockstep with wave shuffles; L and U go to 64 doubles of LDS of the wave's own.  Lane 8 l + i then substitutes case
-// l of the pass (forward, backward, ascending) and leaves a_i = theta_i x_i in 64 more.  Per case the wave forms
-// u' = u - sum_j a_j z_j in its ONE joint-layout LDS vector (ascending j, one fma per term, the k rows of Z streamed
-// through free_index) and runs its lanes over the members and the joints.  Max is exact and every other number is one
-// fixed expression of staged values: the result of (s, l) does not depend on the range, the slice, the pass, L, B, the
-// place of the columns in Z or the member form.
+// The apply kernel is one work-group of four waves per (truss, slice of the range's scenarios) on the staged tables of
+// trs_columns.h.  Every wave takes one scenario at a time.  Lane 8 i + j gathers P_ij from Z through free_index - the
+// expression that forms r_e in trs_loss_apply, so a single removal's pivot has r_e's bits - and holds A_ij during the
+// elimination, which runs in lockstep with wave shuffles; L and U go to 64 doubles of LDS of the wave's own.  Lane
+// 8 l + i then substitutes case l of the pass (forward, backward, ascending) and leaves a_i = theta_i x_i in 64 more.
+// Per case the wave forms u' = u - sum_j a_j z_j in its ONE joint-layout LDS vector (ascending j, one fma per term, the
+// k rows of Z streamed through free_index) and runs its lanes over the members and the joints.  Max is exact and every
+// other number is one fixed expression of staged values: the result of (s, l) does not depend on the range, the slice,
+// the pass, L, B, the place of the columns in Z or the member form.
 #include "../../include/trs_sets.h"
 #include "trs_common.h"
-#include "trs_loss_row.h"
+#include "trs_columns.h"
 #include "trs_recover.h"
 
-#include <limits.h>
 #include <math.h>
 
 namespace {
 
 using namespace trs_rec;
-using trs_loss_row::wave_max_index;
+using namespace trs_col;
 
 constexpr int WAVES = 4;          // waves per work-group; trs_sets_fits' rule counts their u' vectors
 constexpr int KMAX = TRS_SETS_MAX;
-constexpr int MAX_PASS = 8;       // load cases per pass at most: lane 8 l + i substitutes case l
-constexpr size_t LDS_BUDGET = 160 * 1024;   // a CU's LDS: the ONE number behind trs_sets_fits, the passes and the launch
+constexpr int OWN = 128;          // doubles of a wave's own: L and U of its scenario, then a_i of case l at 8 l + i
 #ifndef TRS_SETS_SLICE
 #define TRS_SETS_SLICE 32         // scenarios per work-group
 #endif
 static_assert(KMAX * KMAX == 64 && MAX_PASS * KMAX == 64, "one lane per entry of the k x k system / per (case, member)");
-
-// LDS of the apply kernel with g cases per pass (the rule of trs_sets_fits)
-size_t sets_lds(int nJ_max, int nM_max, int g) {
-    const size_t doubles = (size_t)5 * nM_max + (size_t)3 * nJ_max * WAVES + (size_t)128 * WAVES +
-                           (size_t)g * ((size_t)3 * nJ_max + nM_max);
-    const size_t ints = (size_t)2 * nM_max + (size_t)4 * nJ_max;
-    return (doubles * sizeof(double) + ints * sizeof(int) + 15) / 16 * 16;
-}
-
-// cases per pass: the largest g <= min(L, MAX_PASS) that fits, evened out over the passes it makes necessary; 0 = none
-int sets_pass(int nJ_max, int nM_max, int L) {
-    int g = L < MAX_PASS ? L : MAX_PASS;
-    while (g > 0 && sets_lds(nJ_max, nM_max, g) > LDS_BUDGET) --g;
-    if (g <= 0) return 0;
-    const int passes = (L + g - 1) / g;
-    return (L + passes - 1) / passes;
-}
-
-struct SetsTables {
-    double *cx, *cy, *cz, *k, *ia;   // [nM_max] each
-    double* z;                       // [WAVES][3 nJ_max]  u' of the wave's current (scenario, case)
-    double* lu;                      // [WAVES][64]        L (below the diagonal) and U of the wave's scenario
-    double* a;                       // [WAVES][64]        a_i of case l of the pass at 8 l + i
-    double* u;                       // [g][3 nJ_max]
-    double* N;                       // [g][nM_max]
-    int2* ends;                      // [nM_max]
-    int* fi;                         // [3 nJ_max]
-    int* jo;                         // [nJ_max]
-};
-
-__device__ __forceinline__ SetsTables sets_tables(double* sh, int nJ_max, int nM_max, int g) {
-    SetsTables t;
-    t.cx = sh;
-    t.cy = t.cx + nM_max;
-    t.cz = t.cy + nM_max;
-    t.k = t.cz + nM_max;
-    t.ia = t.k + nM_max;
-    t.z = t.ia + nM_max;
-    t.lu = t.z + (size_t)WAVES * 3 * nJ_max;
-    t.a = t.lu + 64 * WAVES;
-    t.u = t.a + 64 * WAVES;
-    t.N = t.u + (size_t)g * 3 * nJ_max;
-    t.ends = reinterpret_cast<int2*>(t.N + (size_t)g * nM_max);
-    t.fi = reinterpret_cast<int*>(t.ends + nM_max);
-    t.jo = t.fi + 3 * nJ_max;
-    return t;
-}
-
-// ---- the right-hand sides: one wave per row --------------------------------------------------------------------------
-__global__ __launch_bounds__(64 * WAVES) void trs_sets_rhs_kernel(const int C, const double* __restrict__ xyz,
-                                                                  const TrsMembers mem, const int* __restrict__ free_index,
-                                                                  const int* __restrict__ n_free, const int* __restrict__ nM,
-                                                                  const int* __restrict__ cols, const int nJ_max,
-                                                                  const int nM_max, double* __restrict__ Z, const int ld_f) {
-    const int per_truss = (C + WAVES - 1) / WAVES;   // work-groups per truss
-    const int b = blockIdx.x / per_truss, lane = threadIdx.x & 63;
-    const int i = (blockIdx.x - b * per_truss) * WAVES + (threadIdx.x >> 6);
-    if (i >= C) return;
-    const int e = cols[(size_t)b * C + i];
-    const bool real = e >= 0 && e < nM[b];
-    const int npad = min(trs_round_up(n_free[b], TRS_NB), ld_f);
-    trs_loss_row::write_row(Z + ((size_t)b * C + i) * ld_f, npad, lane, real, (size_t)b * nM_max + (real ? e : 0), mem,
-                            xyz + (size_t)b * 3 * nJ_max, free_index + (size_t)b * 3 * nJ_max);
-}
 
 // ---- the apply kernel ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64 * WAVES) void trs_sets_apply_kernel(
@@ -125,58 +58,17 @@ __global__ __launch_bounds__(64 * WAVES) void trs_sets_apply_kernel(
     // trimmed to the arrays, so that no table entry and no output lies outside them whatever nJ[b] and nM[b] hold
     const int joints = min(max(nJ[b], 0), nJ_max), members = min(max(nM[b], 0), nM_max);
     const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
-    const SetsTables t = sets_tables(sh, nJ_max, nM_max, g);
-    const size_t mbase = (size_t)b * nM_max;
-    const double* X = xyz + (size_t)b * ndof_max;
+    const Tables t = tables(sh, nJ_max, nM_max, g, WAVES, OWN);
     double* zw = t.z + (size_t)wave * ndof_max;
-    double* luw = t.lu + 64 * wave;
-    double* aw = t.a + 64 * wave;
+    double* luw = t.own + OWN * wave;
+    double* aw = luw + 64;
     const double inf = __builtin_huge_val(), nan = __builtin_nan("");
     const int hi = lane >> 3, lo = lane & 7;   // lane = 8 hi + lo
 
-    // once per work-group: the member table, the DOF map, the joint order
-    for (int m = tid; m < members; m += 64 * WAVES) {
-        int2 c = mem.ends(mbase + m);
-        c.x = min(max(c.x, 0), nJ_max - 1);   // (a joint id outside the arrays would index LDS outside them)
-        c.y = min(max(c.y, 0), nJ_max - 1);
-        const MemberGeom mg = member_geom(X, c.x, c.y);
-        t.ends[m] = c;
-        t.cx[m] = mg.c[0];
-        t.cy[m] = mg.c[1];
-        t.cz[m] = mg.c[2];
-        t.k[m] = mem.EA(mbase + m) / mg.len;
-        t.ia[m] = 1.0 / mem.area(mbase + m);
-    }
-    // staged for every joint of the arrays, -1 (held) past the truss's own: an end joint trimmed to there reads zeros
-    for (int d = tid; d < ndof_max; d += 64 * WAVES) {
-        const int row = free_index[(size_t)b * ndof_max + d];
-        t.fi[d] = d < ndof && row < ld_f ? row : -1;
-    }
-    for (int j = tid; j < nJ_max; j += 64 * WAVES) {
-        const int id = joint_out != nullptr ? joint_out[(size_t)b * nJ_max + j] : j;
-        t.jo[j] = id >= 0 && id < nJ_max ? id : j;
-    }
-    for (int d = tid; d < WAVES * ndof_max; d += 64 * WAVES) t.z[d] = 0.0;   // (entries past ndof stay zero)
-
+    stage(t, tid, 64 * WAVES, b, joints, members, nJ_max, nM_max, xyz, mem, free_index, joint_out, ld_f);
     for (int l0 = 0; l0 < L; l0 += g) {
         const int lg = min(g, L - l0);   // the cases of this pass: l0 .. l0 + lg - 1
-        __syncthreads();                 // (the tables above are written; the previous pass's readers of u and N are done)
-        for (int x = tid; x < lg * ndof_max; x += 64 * WAVES) {
-            const int l = x / ndof_max, d = x - l * ndof_max;
-            const int row = t.fi[d];
-            t.u[(size_t)l * ndof_max + d] = row >= 0 ? U[((size_t)b * L + l0 + l) * ld_f + row] : 0.0;
-        }
-        __syncthreads();
-        for (int x = tid; x < lg * members; x += 64 * WAVES) {   // N = k c . (u_j1 - u_j0), as trs_loss_apply stages it
-            const int l = x / members, m = x - l * members;
-            const double* ul = t.u + (size_t)l * ndof_max;
-            const int2 c = t.ends[m];
-            double p = t.cx[m] * (ul[3 * c.y] - ul[3 * c.x]);
-            p = fma(t.cy[m], ul[3 * c.y + 1] - ul[3 * c.x + 1], p);
-            p = fma(t.cz[m], ul[3 * c.y + 2] - ul[3 * c.x + 2], p);
-            t.N[(size_t)l * nM_max + m] = t.k[m] * p;
-        }
-        __syncthreads();
+        stage_pass(t, tid, 64 * WAVES, lg, members, nJ_max, nM_max, U + ((size_t)b * L + l0) * ld_f, ld_f);
 
         for (int sl = first + wave; sl < last; sl += WAVES) {
             const size_t sb = (size_t)b * S + s0 + sl;            // (b, s) of the per-scenario outputs
@@ -218,10 +110,7 @@ __global__ __launch_bounds__(64 * WAVES) void trs_sets_apply_kernel(
                     v[a] = r1 >= 0 ? zj[r1] : 0.0;
                     v[3 + a] = r0 >= 0 ? zj[r0] : 0.0;
                 }
-                double pe = t.cx[ei] * (v[0] - v[3]);
-                pe = fma(t.cy[ei], v[1] - v[4], pe);
-                pe = fma(t.cz[ei], v[2] - v[5], pe);
-                Aij = fma(theta * t.k[ei], pe, Aij);
+                Aij = fma(theta * t.k[ei], along(t, ei, v[0] - v[3], v[1] - v[4], v[2] - v[5]), Aij);
             }
             // Gauss without pivoting, in the set's order
             int fail = -1;
@@ -323,11 +212,7 @@ __global__ __launch_bounds__(64 * WAVES) void trs_sets_apply_kernel(
                     const bool real = m < members;
                     double after = 0.0;
                     if (real) {
-                        const int2 c = t.ends[m];
-                        double p = t.cx[m] * (zw[3 * c.y] - zw[3 * c.x]);
-                        p = fma(t.cy[m], zw[3 * c.y + 1] - zw[3 * c.x + 1], p);
-                        p = fma(t.cz[m], zw[3 * c.y + 2] - zw[3 * c.x + 2], p);
-                        const double n = t.k[m] * p;
+                        const double n = t.k[m] * along(t, m, zw);
                         double gm = 1.0;
                         bool changed = false;
 #pragma unroll
@@ -345,11 +230,7 @@ __global__ __launch_bounds__(64 * WAVES) void trs_sets_apply_kernel(
                     }
                     if (NA != nullptr && m < nM_max) NA[o * nM_max + m] = after;
                 }
-                wave_max_index(best, where);
-                if (lane == 0) {
-                    ps_out[o] = where == INT_MAX ? 0.0 : best;
-                    pm_out[o] = where == INT_MAX ? -1 : where;
-                }
+                close_peak(best, where, lane, ps_out + o, pm_out + o);
                 // the joints
                 best = -1.0;
                 where = INT_MAX;
@@ -370,11 +251,7 @@ __global__ __launch_bounds__(64 * WAVES) void trs_sets_apply_kernel(
                         dst[2] = a2;
                     }
                 }
-                wave_max_index(best, where);
-                if (lane == 0) {
-                    pd_out[o] = where == INT_MAX ? 0.0 : best;
-                    pj_out[o] = where == INT_MAX ? -1 : where;
-                }
+                close_peak(best, where, lane, pd_out + o, pj_out + o);
                 __builtin_amdgcn_wave_barrier();   // (the next case's u' overwrites zw)
             }
         }
@@ -383,12 +260,9 @@ __global__ __launch_bounds__(64 * WAVES) void trs_sets_apply_kernel(
 
 int sets_rhs_launch(int B, int C, int nJ_max, int nM_max, const double* xyz, const TrsMembers& mem, const int* free_index,
                     const int* n_free, const int* nM, const int* cols, double* Z, int ld_f, hipStream_t stream) {
-    if (B < 0 || C < 0 || nJ_max < 0 || nM_max < 0 || ld_f < 0) return (int)hipErrorInvalidValue;
-    if (B == 0 || C == 0) return 0;
-    if (!mem.conn || !xyz || !free_index || !n_free || !nM || !cols || !Z) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(trs_sets_rhs_kernel, dim3((unsigned)((C + WAVES - 1) / WAVES) * (unsigned)B), dim3(64 * WAVES), 0,
-                       stream, C, xyz, mem, free_index, n_free, nM, cols, nJ_max, nM_max, Z, ld_f);
-    return (int)hipGetLastError();
+    if (B > 0 && C > 0 && (!mem.conn || !xyz || !free_index || !n_free || !nM || !cols || !Z))
+        return (int)hipErrorInvalidValue;   // (without `cols` the kernel would take the members 0 .. C - 1)
+    return rhs_launch(B, 0, cols, C, nJ_max, nM_max, xyz, mem, free_index, n_free, nM, Z, ld_f, stream);
 }
 
 int sets_apply_launch(int B, int L, int S, int s0, int Sc, int C, int nJ_max, int nM_max, const double* xyz,
@@ -406,14 +280,14 @@ int sets_apply_launch(int B, int L, int S, int s0, int Sc, int C, int nJ_max, in
     if (!mem.conn || (mem.tidx == nullptr && (!mem.E || !mem.A)) || !xyz || !free_index || !nJ || !nM || !slot || !U || !pivot || !unstable || !first_unstable || !peak_stress ||
         !peak_member || !peak_displace || !peak_joint || (C > 0 && (!cols || !Z)))
         return (int)hipErrorInvalidValue;
-    const int g = sets_pass(nJ_max, nM_max, L);
+    const int g = pass(nJ_max, nM_max, L, WAVES, OWN);
     if (g <= 0) return (int)hipErrorInvalidValue;   // (the kernel's pass loop steps by g)
     static const int lds_limit_set = (int)hipFuncSetAttribute(   // once per process, not per launch
         reinterpret_cast<const void*>(trs_sets_apply_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET);
     (void)lds_limit_set;
     const int slices = (Sc + TRS_SETS_SLICE - 1) / TRS_SETS_SLICE;
     hipLaunchKernelGGL(trs_sets_apply_kernel, dim3((unsigned)slices * (unsigned)B), dim3(64 * WAVES),
-                       sets_lds(nJ_max, nM_max, g), stream, L, g, S, s0, Sc, C, TRS_SETS_SLICE, xyz, mem, free_index, nJ,
+                       lds(nJ_max, nM_max, g, WAVES, OWN), stream, L, g, S, s0, Sc, C, TRS_SETS_SLICE, xyz, mem, free_index, nJ,
                        nM, nJ_max, nM_max, cols, slot, gamma, Z, U, ld_f, r_tol, pivot, unstable, first_unstable,
                        peak_stress, peak_member, peak_displace, peak_joint, N_after, u_after, joint_out);
     return (int)hipGetLastError();
@@ -426,7 +300,7 @@ extern "C" {
 int trs_sets_abi_version(void) { return TRS_SETS_ABI_VERSION; }
 
 int trs_sets_fits(int nJ_max, int nM_max, int L) {
-    return nJ_max >= 0 && nM_max >= 0 && L >= 0 && sets_lds(nJ_max, nM_max, 1) <= LDS_BUDGET;
+    return fits(nJ_max, nM_max, L, WAVES, OWN);
 }
 
 int trs_sets_rhs(int B, int C, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* E,

@@ -1,6 +1,7 @@
-"""The four resident-factor analyses (`solve_load_cases`, `solve_effect_cases`, `solve_gradients`, `solve_modes`) give
-the SAME BITS as the build that recorded `tests/golden/analysis_bits.json`: SHA-256 digests of every field of the four
-result dataclasses, for both member forms and with and without a joint order.  The kernels use no floating-point
+"""The resident-factor analyses (`solve_load_cases`, `solve_effect_cases`, `solve_gradients`, `solve_modes` and the three
+on the columns inv(K_ff) b_e: `solve_member_loss`, `solve_member_sets`, `solve_influence`) give the SAME BITS as the
+build that recorded `tests/golden/analysis_bits.json`: SHA-256 digests of every field (that is not None) of the result
+dataclasses, for both member forms and with and without a joint order.  The kernels use no floating-point
 atomics, so the digests are stable from run to run; they are promised per compiler only, so the fixture names the stack
 that recorded it and the tests skip on any other.  A change that is meant to keep the bits is checked by recording at
 the commit before it and running the tests after it:
@@ -26,7 +27,13 @@ NAMES = ["bar-6_input_0", "bar-10_input_0", "bar-25_input_0", "bar-47_input_0", 
 L, P = 17, 3   # two case groups of the substitution (16 + 1); three modes
 CONFIGS = {"general": dict(table=False, reorder=False), "general-profile": dict(table=False, reorder="profile"),
            "table": dict(table=True, reorder=False), "table-profile": dict(table=True, reorder="profile")}
-ANALYSES = ("load_cases", "effect_cases", "gradients", "modes")
+ANALYSES = ("load_cases", "effect_cases", "gradients", "modes", "member_loss", "member_sets", "influence")
+# the column analyses: nine cases are two uneven passes of their apply kernels (8 at most per pass: 5 + 4); chunk 48
+# leaves a partial last range of members; 40 scenarios are two slices of 32, the second partial; the path is the first
+# twelve joints and back to joint 0
+L_COL, CHUNK, S_SETS, P_PATH = 9, 48, 40, 12
+SMALL = 6   # the trusses before bar-942: one bucket, where the results per member pair and per scenario are small
+TRAIN = [(1.0, 0.0), (2.0, 30.0), (1.5, 75.0)]
 
 
 def packed_batch(table):
@@ -51,6 +58,52 @@ def inputs(packed):
             "joint_mass": rng.uniform(0.0, 50.0, size=(B, nJ_max)) * joints}
 
 
+def scenarios(packed):
+    """Seeded scenarios of `solve_member_sets`: sets int64 [B, S_SETS, 8] (-1 padding) of 0 .. min(8, nM) distinct
+    members - the first empty, the second a single removal - and factors from {0, 0, 0.5, 2}."""
+    rng = np.random.default_rng(7)
+    sets = np.full([packed.B, S_SETS, 8], -1, dtype=np.int64)
+    for b in range(packed.B):
+        nM = int(packed.nM[b])
+        for s in range(S_SETS):
+            k = s if s < 2 else int(rng.integers(0, min(8, nM) + 1))
+            sets[b, s, :k] = rng.choice(nM, size=k, replace=False)
+    factors = rng.choice([0.0, 0.0, 0.5, 2.0], size=sets.shape)
+    factors[:, 1] = 0.0
+    return sets, factors
+
+
+def moving_load(packed):
+    """The path of `solve_influence` per truss (joints 0 .. min(nJ, P_PATH) - 1 in id order, then joint 0 again; -1
+    padding) and a seeded load vector [B, 3], nothing along z on a 2D truss."""
+    rng = np.random.default_rng(11)
+    path = np.full([packed.B, P_PATH + 1], -1, dtype=np.int64)
+    for b in range(packed.B):
+        n = min(int(packed.nJ[b]), P_PATH)
+        path[b, :n + 1] = list(range(n)) + [0]
+    axes = np.arange(3)[None, :] < np.asarray(packed.dim).reshape(packed.B, 1)
+    return path, rng.uniform(-1.0, 1.0, size=(packed.B, 3)) * axes
+
+
+def column_calls(analysis, packed, x):
+    """{name: (function name, arguments, keywords)} of a column analysis: "full" on the whole batch with chunk 48 and
+    no result per member pair, "small" on the trusses before bar-942 with the default chunk and every optional result."""
+    small = packed.take(np.arange(SMALL)).trimmed()
+    loads = x["loads"][:, :L_COL]
+    loads_small = loads[:SMALL, :, :small.nJ_max]
+    if analysis == "member_loss":
+        return {"full": ("solve_member_loss", (packed, loads), dict(chunk=CHUNK, want_forces=False)),
+                "small": ("solve_member_loss", (small, loads_small), dict(want_forces=True))}
+    if analysis == "member_sets":
+        sets, factors = scenarios(packed)
+        return {"full": ("solve_member_sets", (packed, sets, factors, loads), dict(chunk=CHUNK)),
+                "small": ("solve_member_sets", (small, sets[:SMALL], factors[:SMALL], loads_small),
+                          dict(want_forces=True, want_displace=True))}
+    path, direction = moving_load(packed)
+    return {"full": ("solve_influence", (packed, path, direction, TRAIN), dict(chunk=CHUNK)),
+            "small": ("solve_influence", (small, path[:SMALL], direction[:SMALL], TRAIN), dict(want_lines=True))}
+
+
 def run(analysis, packed, x, reorder):
     """The result dataclasses of one analysis, as {name: dataclass}."""
     from python_stable_3d_truss_analysis_amd import batch
@@ -63,14 +116,20 @@ def run(analysis, packed, x, reorder):
         forward, grads = batch.solve_gradients(packed, x["loads"], x["grad_u"], x["grad_f_ext"], x["grad_N"],
                                                reorder=reorder)
         return {"forward": forward, "grads": grads}
+    if analysis in ("member_loss", "member_sets", "influence"):
+        return {name: getattr(batch, fn)(*args, reorder=reorder, **kw)
+                for name, (fn, args, kw) in column_calls(analysis, packed, x).items()}
     return {"modes": batch.solve_modes(packed, p=P, joint_mass=x["joint_mass"], reorder=reorder)}
 
 
 def digests(results):
-    """{"<result>.<field>": SHA-256 of the field's dtype, shape and raw bytes}, every field of every dataclass."""
+    """{"<result>.<field>": SHA-256 of the field's dtype, shape and raw bytes}, every field of every dataclass that is
+    not None (an optional result that was not asked for)."""
     out = {}
     for name, res in results.items():
         for field, value in vars(res).items():
+            if value is None:
+                continue
             a = np.ascontiguousarray(value)
             h = hashlib.sha256(f"{a.dtype.str} {a.shape} ".encode())
             h.update(a.tobytes())
@@ -118,6 +177,25 @@ def test_the_batch_exercises_every_fold():
     assert (held.any(axis=2) & ~held.all(axis=2))[0, :packed.nJ[0]].any() and packed.dim.reshape(-1)[0] == 3
     assert packed_batch(True).is_table and not packed.is_table
     assert L > 16 and L % 16 != 0
+    # the column analyses: more cases than one pass of the apply kernels holds, a partial last chunk of members and a
+    # partial last slice of scenarios in every bucket, several ranges of scenarios, every set size, a valid path
+    assert 8 < L_COL < 16 and S_SETS > 32 and S_SETS % 32 != 0 and CHUNK % 16 == 0
+    buckets = [packed.take(idx).trimmed() for idx in batch.size_buckets(packed)]
+    assert sorted(b.nM_max for b in buckets) == [120, 942] and packed.take(np.arange(SMALL)).trimmed().nM_max == 120
+    assert all(b.nM_max > CHUNK and b.nM_max % CHUNK != 0 for b in buckets)
+    x = inputs(packed)
+    sets, factors = scenarios(packed)
+    assert not (sets[:, 0] >= 0).any() and ((sets[:, 1] >= 0).sum(axis=1) == 1).all()
+    assert {int(k) for k in (sets >= 0).sum(axis=2).reshape(-1)} == set(range(9))
+    assert {0.0, 0.5, 2.0} == set(factors.reshape(-1).tolist())
+    for chunk, part in ((CHUNK, packed), (64, packed.take(np.arange(SMALL)).trimmed())):
+        got = batch._check_member_sets_args(part, sets[:part.B], factors[:part.B], x["loads"][:part.B, :L_COL, :part.nJ_max],
+                                            batch.MEMBER_LOSS_R_TOL, None, chunk=chunk)
+        assert len(batch.plan_member_sets(got[0], chunk, part.nM_max)) > 1
+    path, direction = moving_load(packed)
+    path, path_len = batch._check_influence_args(packed, path, direction, TRAIN, None, chunk=CHUNK)[:2]
+    assert path_len.tolist() == [min(int(n), P_PATH) + 1 for n in packed.nJ]
+    assert not direction[packed.dim.reshape(-1) == 2, 2].any()
 
 
 @pytest.fixture(scope="module")

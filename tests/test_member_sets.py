@@ -151,11 +151,15 @@ def test_header_table_exports_and_the_fits_rule_agree():
     assert loaded.trs_sets_abi_version() == _capi.SETS_ABI_VERSION == 1 and _capi.SETS_MAX == 8
     makefile = open(os.path.join(_capi.CSRC_DIR, "Makefile")).read()
     assert " sets.hip " in makefile and " influence.hip " in makefile and "../../include/trs_sets.h" in makefile
-    assert " trs_loss_row.h " in makefile
-    # the row of the right-hand side exists once: both kernels call the shared header
+    assert " trs_columns.h " in makefile
+    # the row of the right-hand side exists once: the shared header forms it, the ONE rhs kernel (loss.hip) calls it,
+    # and trs_sets_rhs goes through that kernel's launcher
+    texts = {src: open(os.path.join(_capi.CSRC_DIR, src)).read() for src in ("loss.hip", "sets.hip", "trs_columns.h")}
     for src in ("loss.hip", "sets.hip"):
-        text = open(os.path.join(_capi.CSRC_DIR, src)).read()
-        assert '#include "trs_loss_row.h"' in text and "trs_loss_row::write_row(" in text and "int at[6]" not in text
+        assert '#include "trs_columns.h"' in texts[src] and "int at[6]" not in texts[src]
+    assert texts["trs_columns.h"].count("int at[6]") == 1
+    assert texts["loss.hip"].count("write_row(") == 1 and "write_row(" not in texts["sets.hip"]
+    assert "rhs_kernel" not in texts["sets.hip"] and texts["sets.hip"].count("return rhs_launch(") == 1
     # trs_sets_fits is its documented rule, on both sides of the limit
     shapes = [(244, 942), (6, 10), (0, 0), (10, 1 << 20), (3000, 100), (1200, 1500), (1100, 1500), (500, 2400),
               (500, 2500), (2200, 0), (2300, 0), (-1, 5), (5, -1)]
