@@ -39,7 +39,7 @@ __all__ = ["Truss", "Member", "MemberType", "SupportType", "MetapathType", "Task
            "solve_gradients", "GradientResult", "DifferentiableTruss",
            "solve_modes", "ModeResult", "solve_effect_cases", "EffectCaseResult", "LoadCase",
            "solve_member_loss", "MemberLossResult", "solve_influence", "InfluenceResult",
-           "solve_member_sets", "MemberSetResult"]
+           "solve_member_sets", "MemberSetResult", "solve_transient", "TransientResult"]
 
 
 def __getattr__(name):
@@ -47,7 +47,7 @@ def __getattr__(name):
     if name in ("solve_batch", "pack_trusses", "PackedBatch", "BatchResult", "RaggedSolver", "DeviceBatch",
                 "solve_load_cases", "LoadCaseResult", "solve_gradients", "GradientResult", "solve_modes", "ModeResult",
                 "solve_effect_cases", "EffectCaseResult", "solve_member_loss", "MemberLossResult", "solve_influence",
-                "InfluenceResult", "solve_member_sets", "MemberSetResult"):
+                "InfluenceResult", "solve_member_sets", "MemberSetResult", "solve_transient", "TransientResult"):
         from . import batch
         return getattr(batch, name)
     if name == "DifferentiableTruss":

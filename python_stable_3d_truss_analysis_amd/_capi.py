@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h`, `include/trs_influence.h` and `include/trs_sets.h` (library: `libtrs_hip.so`, in-tree).
+"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h`, `include/trs_influence.h`, `include/trs_sets.h` and `include/trs_dynamics.h` (library: `libtrs_hip.so`, in-tree).
 
 There is no fallback: if the library is missing, `load()` raises `HipExtensionError`.
 """
@@ -137,6 +137,19 @@ SETS_SIGNATURES = {
                                 _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
+#: every symbol `include/trs_dynamics.h` declares (transient response: Newmark time stepping on a factor of K + sigma M;
+#: csrc/dynamics.hip, the same library)
+DYN_SIGNATURES = {
+    "trs_dyn_abi_version": (_I, []),
+    "trs_dyn_fits": (_I, [_I, _I, _I]),
+    "trs_dyn_shift": (_I, [_I, _P, _I, _I, _P, _P, _I, _D, _P]),
+    "trs_dyn_step": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _D, _D, _D, _D, _D,
+                          _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P]),
+    "trs_dyn_tab_step": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _D, _D, _D, _D,
+                              _D, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P]),
+    "trs_dyn_collect": (_I, [_I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+}
+
 #: must equal TRS_ABI_VERSION of include/trs_solver.h
 ABI_VERSION = 10
 #: must equal TRS_MODES_ABI_VERSION of include/trs_modes.h
@@ -149,6 +162,8 @@ LOSS_ABI_VERSION = 1
 INFLUENCE_ABI_VERSION = 1
 #: must equal TRS_SETS_ABI_VERSION of include/trs_sets.h
 SETS_ABI_VERSION = 1
+#: must equal TRS_DYN_ABI_VERSION of include/trs_dynamics.h
+DYN_ABI_VERSION = 1
 #: TRS_SETS_MAX of include/trs_sets.h: members per scenario at most
 SETS_MAX = 8
 #: TRS_MODES_BLOCK of include/trs_modes.h: vectors per truss of the block iteration (one case group)
@@ -197,7 +212,7 @@ def load():
     except OSError as exc:
         raise HipExtensionError(f"cannot load {LIB_PATH}: {exc}") from exc
     for table in (SIGNATURES, MODES_SIGNATURES, EFFECTS_SIGNATURES, LOSS_SIGNATURES, INFLUENCE_SIGNATURES,
-                  SETS_SIGNATURES):
+                  SETS_SIGNATURES, DYN_SIGNATURES):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype = restype
@@ -205,7 +220,7 @@ def load():
     if lib.trs_abi_version() != ABI_VERSION or lib.trs_modes_abi_version() != MODES_ABI_VERSION \
             or lib.trs_effects_abi_version() != EFFECTS_ABI_VERSION or lib.trs_loss_abi_version() != LOSS_ABI_VERSION \
             or lib.trs_influence_abi_version() != INFLUENCE_ABI_VERSION \
-            or lib.trs_sets_abi_version() != SETS_ABI_VERSION:
+            or lib.trs_sets_abi_version() != SETS_ABI_VERSION or lib.trs_dyn_abi_version() != DYN_ABI_VERSION:
         raise HipExtensionError("libtrs_hip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -573,6 +573,38 @@ def _member_set_arrays(who, sets, gamma, B, nM, nM_max):
     return dense.astype(np.int32), np.ascontiguousarray(g)
 
 
+def newmark_constants(dt, beta=0.25, gamma=0.5, damp_mass=0.0, damp_stiff=0.0):
+    """The constants of the Newmark scheme of include/trs_dynamics.h as plain Python floats (the library forms the same
+    ones in the same order): a0 .. a5, s = 1 + a1 damp_stiff and sigma = (a0 + a1 damp_mass) / s, the multiple of the mass
+    that `DeviceBatch.factor_dynamic` adds to the stiffness.  ValueError for dt <= 0, beta <= 0, gamma < 1/2 and negative
+    or non-finite damping."""
+    for name, x in (("dt", dt), ("beta", beta), ("gamma", gamma), ("damp_mass", damp_mass), ("damp_stiff", damp_stiff)):
+        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x):
+            raise ValueError(f"transient: {name} must be a finite number, got {x!r}")
+    dt, beta, gamma, damp_mass, damp_stiff = (float(x) for x in (dt, beta, gamma, damp_mass, damp_stiff))
+    if not dt > 0.0:
+        raise ValueError(f"transient: dt must be positive, got {dt!r}")
+    if not beta > 0.0:
+        raise ValueError(f"transient: beta must be positive, got {beta!r}")
+    if not gamma >= 0.5:
+        raise ValueError(f"transient: gamma must be at least 1/2, got {gamma!r}")
+    if damp_mass < 0.0 or damp_stiff < 0.0:
+        raise ValueError(f"transient: damp_mass and damp_stiff must be non-negative, got {damp_mass!r}, {damp_stiff!r}")
+    a0, a1, a2 = 1.0 / (beta * dt * dt), gamma / (beta * dt), 1.0 / (beta * dt)
+    a3, a4, a5 = 1.0 / (2.0 * beta) - 1.0, gamma / beta - 1.0, 0.5 * dt * (gamma / beta - 2.0)
+    s = 1.0 + a1 * damp_stiff
+    return {"dt": dt, "beta": beta, "gamma": gamma, "damp_mass": damp_mass, "damp_stiff": damp_stiff, "a0": a0, "a1": a1,
+            "a2": a2, "a3": a3, "a4": a4, "a5": a5, "s": s, "sigma": (a0 + a1 * damp_mass) / s}
+
+
+def _check_mass_args(who, B, nJ_max, joint_mass_shape, mass_scale, joint_mass_min=None):
+    """The mass arguments that the transient analysis shares with `modes` (`_check_mode_args`), refused in `who`'s name."""
+    try:
+        _check_mode_args(B, nJ_max, 1, joint_mass_shape, mass_scale, 1.0, 1, joint_mass_min=joint_mass_min)
+    except ValueError as exc:
+        raise ValueError(str(exc).replace("modes:", who + ":", 1)) from None
+
+
 def _ptr(x):
     """The device address of an optional tensor argument of a C call."""
     return None if x is None else x.data_ptr()
@@ -907,6 +939,7 @@ class DeviceBatch:
             self.assemble()
             self.potrf()
         self._factored = True
+        self._dynamic = None   # (the slab holds a factor of K_ff again: `transient` refuses until `factor_dynamic`)
         self._bump_generation()
 
     # what the analyses on the resident factor share (solve_cases, solve_effect_cases, adjoint_cases, modes)
@@ -1060,7 +1093,7 @@ class DeviceBatch:
 
     @property
     def generation(self):
-        """Counts the `factor()`, `solve_cases()` (also the one inside `member_loss()`), `solve_effect_cases()` and `modes()` calls of this batch: a forward state is identified by the value
+        """Counts the `factor()`, `factor_dynamic()`, `solve_cases()` (also the one inside `member_loss()`), `solve_effect_cases()` and `modes()` calls of this batch: a forward state is identified by the value
         after its `solve_cases()`, and `adjoint_cases` refuses any other."""
         return getattr(self, "_generation", 0)
 
@@ -1396,6 +1429,172 @@ class DeviceBatch:
         out["resid"].copy_(ws["resid"][:, :p])
         out["n_modes"].copy_(ws["n_mass"].clamp(max=p))
         out["iters"].copy_(ws["state"])
+        return out
+
+    # -- transient response: Newmark time stepping on a factor of K + sigma M (include/trs_dynamics.h) ------------------
+    def factor_dynamic(self, dt, beta=0.25, gamma=0.5, damp_mass=0.0, damp_stiff=0.0, joint_mass=None, mass_scale=1.0):
+        """`factor()` for the time domain: dofmap, assembly, the lumped mass of `modes` (`trs_modes_mass`, the same
+        `joint_mass` and `mass_scale`), the diagonal shift S[c][c] += sigma Mf[c] (`trs_dyn_shift`) and the Cholesky
+        factorisation - the slab then holds a factor of K_ff + sigma M, sigma = (a0 + a1 damp_mass) / (1 + a1 damp_stiff)
+        of the Newmark scheme (`beta`, `gamma`, step `dt`) with Rayleigh damping C = damp_mass M + damp_stiff K_ff, for
+        any number of `transient` calls.  The static analyses (`solve_cases`, `modes`, `member_loss`, ...) refuse with
+        their "no factor" error until a plain `factor()`, which in turn ends the dynamic state; `generation` is bumped;
+        `self.info` keeps its meaning.  The compact member form of the assembly (`options["compact"]`) has no slab to
+        shift and is refused, as is a batch on the fused small-system path."""
+        t = self.torch
+        if self.small:
+            raise ValueError("factor_dynamic(): this batch takes the fused small-system kernel, which keeps no factor - "
+                             "build the DeviceBatch with use_small=False")
+        if self.options["compact"]:
+            raise ValueError("factor_dynamic(): options['compact'] leaves no slab whose diagonal could be shifted")
+        const = newmark_constants(dt, beta, gamma, damp_mass, damp_stiff)
+        _check_mass_args("factor_dynamic()", self.B, self.nJ_max, None if joint_mass is None else tuple(joint_mass.shape),
+                         mass_scale)
+        if joint_mass is not None:
+            if joint_mass.dtype != t.float64 or joint_mass.device != self.device:
+                raise ValueError(f"factor_dynamic(): joint_mass must be float64 [B={self.B}, nJ_max={self.nJ_max}] on "
+                                 f"{self.device}")
+            joint_mass = joint_mass.contiguous()
+        if self.B and not self.lib.trs_modes_fits(self.nJ_max, self.nM_max):
+            raise HipExtensionError(f"factor_dynamic(): a truss of {self.nJ_max} joints / {self.nM_max} members exceeds "
+                                    "the LDS of the mass kernel (trs_modes_fits)")
+        self._factored = False
+        self._dynamic = None
+        with t.cuda.device(self.device):
+            self.dofmap()
+            self.assemble()
+            Mf, n_mass = self._lumped_mass(joint_mass, mass_scale)
+            if self.B:
+                _capi.check(self.lib.trs_dyn_shift(self.B, self.n_free.data_ptr(), self.ld, self.rows, self.S.data_ptr(),
+                                                   Mf.data_ptr(), self.rows, const["sigma"], self._stream()),
+                            "trs_dyn_shift")
+            self.potrf()
+        self._bump_generation()
+        self._forward = None
+        self._dynamic = dict(const, Mf=Mf, n_mass=n_mass, generation=self.generation)
+
+    def _lumped_mass(self, joint_mass, mass_scale):
+        """(Mf [B, rows], n_mass [B]) of `trs_modes_mass` for the resident batch (`dofmap()` first): the lumped mass of
+        every free DOF in the reduced numbering, zero on the padding."""
+        t = self.torch
+        Mf = t.zeros([self.B, self.rows], dtype=t.float64, device=self.device)
+        n_mass = t.zeros([self.B], dtype=t.int32, device=self.device)
+        if self.B:
+            jo, stream, tab = self._case_launch()
+            members = self._members() if self.table else (self.conn.data_ptr(), self.A.data_ptr(), self.rho.data_ptr())
+            _capi.check(getattr(self.lib, f"trs_modes{tab}_mass")(
+                self.B, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *members, _ptr(joint_mass), jo,
+                float(mass_scale), self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(),
+                self.nM.data_ptr(), Mf.data_ptr(), self.rows, n_mass.data_ptr(), stream), f"trs_modes{tab}_mass")
+        return Mf, n_mass
+
+    #: the results of `transient`: key -> (trailing shape, dtype); "L", "nJ", "nM", "T1", "Pj", "Pm" are the call's sizes
+    TRANSIENT_SHAPES = {"u": (("L", "nJ", 3), "float64"), "v": (("L", "nJ", 3), "float64"), "a": (("L", "nJ", 3), "float64"),
+                        "u_peak": (("L", "nJ", 3), "float64"), "u_step": (("L", "nJ", 3), "int32"),
+                        "N_max": (("L", "nM"), "float64"), "N_max_step": (("L", "nM"), "int32"),
+                        "N_min": (("L", "nM"), "float64"), "N_min_step": (("L", "nM"), "int32"),
+                        "hist_u": (("L", "T1", "Pj", 3), "float64"), "hist_N": (("L", "T1", "Pm"), "float64")}
+
+    def _monitor_ids(self, what, ids, device_order):
+        """A monitor list of `transient`: int32 [B, P] on this device (None: P = 0), -1 = none; `device_order`: caller's
+        joint ids are translated into the batch's joint order."""
+        t = self.torch
+        if ids is None:
+            return t.zeros([self.B, 0], dtype=t.int32, device=self.device)
+        if ids.dim() != 2 or int(ids.shape[0]) != self.B or ids.dtype != t.int32 or ids.device != self.device:
+            raise ValueError(f"transient(): {what} must be int32 [B={self.B}, P] on {self.device}")
+        ids = ids.contiguous()
+        if device_order and self.joint_out is not None and int(ids.shape[1]):
+            where = t.empty_like(self.joint_out)   # where[b, caller's id] = the joint's place in the batch's order
+            where.scatter_(1, self.joint_out.long(), t.arange(self.nJ_max, dtype=t.int32, device=self.device)
+                           .expand(self.B, -1).contiguous())
+            inside = (ids >= 0) & (ids < self.nJ_max)
+            ids = t.where(inside, where.gather(1, ids.clamp(0, self.nJ_max - 1).long()), t.full_like(ids, -1)).contiguous()
+        return ids
+
+    def transient(self, pattern, steps, scale=None, accel=None, monitor_joints=None, monitor_members=None, state=None,
+                  out=None):
+        """`steps` Newmark steps of M u'' + C u' + K_ff u = scale(t) P - M iota(accel(t)) for L excitations per truss on
+        the factor that `factor_dynamic` left: per step one `trs_potrs_cases` launch and one `trs_dyn_step` launch.
+        `pattern`: float64 device tensor [B, L, nJ_max, 3], the load pattern P in the CALLER's joint numbering (reduced
+        once by `trs_gather_cases`); `scale` [B, L, steps + 1] (None: 1) and `accel` [B, L, steps + 1, 3] (ground
+        acceleration, None: 0; the displacements are then relative to the ground) at the time points 0 .. steps of this
+        call; `monitor_joints` [B, Pj], `monitor_members` [B, Pm]: int32 device tensors of caller's joint ids / member ids
+        (-1: none) whose histories are wanted.  Starts from rest (u = v = 0, a = f_0 / M) or, with `state` = the
+        "state" of an earlier call on this batch, from where that call ended (its time point `steps` is this call's time
+        point 0; the state's tensors are advanced in place).  Returns a dict of device tensors: the envelopes over this
+        call's time points - u_peak [B, L, nJ_max, 3] = max |u| with u_step (int32, the FIRST point that attains it),
+        N_max, N_min [B, L, nM_max] with N_max_step, N_min_step -, the histories hist_u [B, L, steps + 1, Pj, 3] and
+        hist_N [B, L, steps + 1, Pm], the last u, v, a [B, L, nJ_max, 3] (caller's numbering), and "state".  A state of
+        another batch, another `factor_dynamic` or another L is refused."""
+        t = self.torch
+        dyn = getattr(self, "_dynamic", None)
+        if dyn is None:
+            raise ValueError("transient(): no dynamic factor - call factor_dynamic() first")
+        pattern = self._check_loads("transient", pattern)
+        L = int(pattern.shape[1])
+        if isinstance(steps, bool) or int(steps) != steps or int(steps) < 1:
+            raise ValueError(f"transient(): steps must be an integer of at least 1, got {steps!r}")
+        T1 = int(steps) + 1
+        for name, x, tail in (("scale", scale, ()), ("accel", accel, (3,))):
+            if x is not None and (tuple(int(v) for v in x.shape) != (self.B, L, T1) + tail or x.dtype != t.float64
+                                  or x.device != self.device):
+                raise ValueError(f"transient(): {name} must be float64 {[self.B, L, T1] + list(tail)} on {self.device}")
+        scale = None if scale is None else scale.contiguous()
+        accel = None if accel is None else accel.contiguous()
+        mon_j = self._monitor_ids("monitor_joints", monitor_joints, True)
+        mon_m = self._monitor_ids("monitor_members", monitor_members, False)
+        Pj, Pm = int(mon_j.shape[1]), int(mon_m.shape[1])
+        if state is not None:
+            if state.get("batch") is not self or state.get("generation") != dyn["generation"] or state.get("L") != L:
+                raise ValueError("transient(): state belongs to another batch, another factor_dynamic() or another L")
+        sizes = {"L": L, "nJ": self.nJ_max, "nM": self.nM_max, "T1": T1, "Pj": Pj, "Pm": Pm}
+        shapes = {k: ([self.B] + [sizes.get(n, n) for n in shape], getattr(t, dtype))
+                  for k, (shape, dtype) in self.TRANSIENT_SHAPES.items()}
+        out = self._out_tensors("transient", shapes, out)
+        if state is None:
+            f64 = lambda: t.empty([self.B, L, self.rows], dtype=t.float64, device=self.device)
+            state = {"U": f64(), "V": f64(), "Acc": f64(), "step": 0, "batch": self, "generation": dyn["generation"], "L": L}
+            first = 1
+        else:
+            first = 2
+        out["state"] = state
+        if self.B == 0 or L == 0:
+            return out
+        damped = dyn["damp_stiff"] > 0.0
+        if not self.lib.trs_dyn_fits(self.nJ_max, self.nM_max, int(damped)):
+            raise HipExtensionError(f"transient(): a truss of {self.nJ_max} joints / {self.nM_max} members exceeds the LDS "
+                                    "of the step kernel (trs_dyn_fits)")
+        Pr = self._dyn_Pr = self._case_block("_dyn_Pr", L)
+        F = self._dyn_F = self._case_block("_dyn_F", L)
+        jo, stream, tab = self._case_launch()
+        fn = getattr(self.lib, f"trs_dyn{tab}_step")
+
+        def step(first, n):
+            _capi.check(fn(
+                self.B, L, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *self._members(), self.free_index.data_ptr(),
+                self.n_free.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), dyn["Mf"].data_ptr(), Pr.data_ptr(),
+                _ptr(scale), _ptr(accel), T1, n, first, dyn["dt"], dyn["beta"], dyn["gamma"], dyn["damp_mass"],
+                dyn["damp_stiff"], F.data_ptr(), state["U"].data_ptr(), state["V"].data_ptr(), state["Acc"].data_ptr(),
+                self.rows, out["u_peak"].data_ptr(), out["u_step"].data_ptr(), out["N_max"].data_ptr(),
+                out["N_max_step"].data_ptr(), out["N_min"].data_ptr(), out["N_min_step"].data_ptr(),
+                mon_j.data_ptr() if Pj else None, Pj, mon_m.data_ptr() if Pm else None, Pm,
+                out["hist_u"].data_ptr() if Pj else None, out["hist_N"].data_ptr() if Pm else None, jo, stream),
+                f"trs_dyn{tab}_step")
+
+        with t.cuda.device(self.device):
+            _capi.check(self.lib.trs_gather_cases(self.B, L, self.nJ_max, pattern.data_ptr(), self.free_index.data_ptr(),
+                                                  self.n_free.data_ptr(), self.nJ.data_ptr(), jo, Pr.data_ptr(),
+                                                  self.rows, stream), "trs_gather_cases")
+            step(first, 0)
+            for n in range(1, T1):
+                self._potrs_cases(F, L)
+                step(0, n)
+            _capi.check(self.lib.trs_dyn_collect(
+                self.B, L, self.nJ_max, state["U"].data_ptr(), state["V"].data_ptr(), state["Acc"].data_ptr(), self.rows,
+                self.free_index.data_ptr(), self.nJ.data_ptr(), jo, out["u"].data_ptr(), out["v"].data_ptr(),
+                out["a"].data_ptr(), stream), "trs_dyn_collect")
+        state["step"] += T1 - 1
         return out
 
     def fitness(self, allow_stress, allow_displace, out=None):
@@ -2750,11 +2949,11 @@ class _Bucket:
         dst[tuple(index)] = src
 
 
-def _factored_buckets(packed, dev, info, max_slab_bytes, reorder, options, use_envelope, cases=1):
+def _factored_buckets(packed, dev, info, max_slab_bytes, reorder, options, use_envelope, cases=1, factor=None):
     """The loop that the analyses on a resident factor share: per size bucket (`size_buckets`) the trusses are uploaded,
     ordered and factored on the staged pipeline, and (DeviceBatch, _Bucket) is yielded for the analysis; afterwards the
     factorisation's status goes to the bucket's rows of `info`.  Nothing is factored for an empty batch or for
-    `cases` = 0 load cases."""
+    `cases` = 0 load cases.  `factor(db, part)` (None: `db.factor()`) is what factors a bucket."""
     import torch
     if not packed.B or not cases:
         return
@@ -2763,7 +2962,10 @@ def _factored_buckets(packed, dev, info, max_slab_bytes, reorder, options, use_e
         part = _Bucket(torch.from_numpy(np.asarray(idx, dtype=np.int64)).to(dev), sub.nJ_max, sub.nM_max)
         part.index = np.asarray(idx, dtype=np.int64)   # (the same places on the host: `solve_member_sets` plans there)
         db = DeviceBatch(sub, dev, use_envelope=use_envelope, use_small=False, reorder=reorder, options=options)
-        db.factor()
+        if factor is None:
+            db.factor()
+        else:
+            factor(db, part)
         yield db, part
         info[part.rows] = db.info
 
@@ -3058,6 +3260,138 @@ def solve_modes(trusses_or_packed, p=6, joint_mass=None, mass_scale=1.0, tol=1e-
             part.put(getattr(out, field), res[key])
     out.omega = out.eigenvalue.sqrt()
     return out if on_device else _host_result(torch, dev, out)
+
+
+@dataclass
+class TransientResult:
+    """Results of `solve_transient` for L excitations per truss over the time points 0 .. T (T = `steps`).  The state at
+    the last point: displace, velocity, acceleration [B, L, nJ_max, 3] (caller's joint numbering, zero at held DOFs;
+    relative to the ground when a ground acceleration was given).  The envelopes over all points: peak_displace
+    [B, L, nJ_max, 3] = max |u| per DOF with peak_displace_step (int32: the first point that attains it), force_max and
+    force_min [B, L, nM_max] (signed member forces, tension positive) with force_max_step, force_min_step.  The
+    histories of the monitored joints and members: history_displace [B, L, T + 1, Pj, 3], history_force
+    [B, L, T + 1, Pm] (zeros for a monitor id of -1).  info [B]: the status of the factorisation of K + sigma M - a truss
+    with info != 0 has meaningless numbers, the others are unaffected."""
+    displace: np.ndarray
+    velocity: np.ndarray
+    acceleration: np.ndarray
+    peak_displace: np.ndarray
+    peak_displace_step: np.ndarray
+    force_max: np.ndarray
+    force_max_step: np.ndarray
+    force_min: np.ndarray
+    force_min_step: np.ndarray
+    history_displace: np.ndarray
+    history_force: np.ndarray
+    info: np.ndarray
+
+    FIELDS = {"displace": ("u", 0.0, "float64", ("L", "nJ", 3)), "velocity": ("v", 0.0, "float64", ("L", "nJ", 3)),
+              "acceleration": ("a", 0.0, "float64", ("L", "nJ", 3)),
+              "peak_displace": ("u_peak", 0.0, "float64", ("L", "nJ", 3)),
+              "peak_displace_step": ("u_step", 0, "int32", ("L", "nJ", 3)),
+              "force_max": ("N_max", 0.0, "float64", ("L", "nM")), "force_max_step": ("N_max_step", 0, "int32", ("L", "nM")),
+              "force_min": ("N_min", 0.0, "float64", ("L", "nM")), "force_min_step": ("N_min_step", 0, "int32", ("L", "nM")),
+              "history_displace": ("hist_u", 0.0, "float64", ("L", "T1", "Pj", 3)),
+              "history_force": ("hist_N", 0.0, "float64", ("L", "T1", "Pm"))}
+
+
+def _check_transient_args(packed, pattern, dt, steps, beta=0.25, gamma=0.5, damp_mass=0.0, damp_stiff=0.0, scale=None,
+                          accel=None, monitor_joints=None, monitor_members=None, joint_mass=None, mass_scale=1.0,
+                          sections=None, max_result_bytes=4 << 30):
+    """The argument errors of `solve_transient` that need no device (ValueError).  Returns the arguments as contiguous
+    host arrays: {"pattern" [B, L, nJ_max, 3], "scale" [B, L, T + 1] or None, "accel" [B, L, T + 1, 3] or None,
+    "monitor_joints" [B, Pj], "monitor_members" [B, Pm] (int32), "joint_mass" [B, nJ_max] or None}."""
+    who = "solve_transient"
+    if sections is not None:
+        raise ValueError(f"{who}: sections= variants cannot be combined with the transient analysis")
+    newmark_constants(dt, beta, gamma, damp_mass, damp_stiff)
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < 1:
+        raise ValueError(f"{who}: steps must be an integer of at least 1, got {steps!r}")
+    B, nJ_max, nM_max, T1 = packed.B, packed.nJ_max, packed.nM_max, int(steps) + 1
+    flat = np.asarray(packed.dim).reshape(-1) == 2   # trusses embedded with z fixed
+
+    def vectors(name, x, lead):
+        x = _host_array(x, np.float64)
+        if x.ndim != len(lead) + 1 or x.shape[:-1] != lead or x.shape[-1] not in (2, 3):
+            raise ValueError(f"{who}: {name} must be {list(lead)} + [2 or 3], got {list(x.shape)}")
+        if not np.isfinite(x).all():
+            raise ValueError(f"{who}: {name} has a non-finite entry")
+        if x.shape[-1] == 2:
+            x = np.concatenate([x, np.zeros(x.shape[:-1] + (1,))], axis=-1)
+        elif flat.any() and np.any(x[flat][..., 2] != 0.0):
+            raise ValueError(f"{who}: {name} has a z component on a 2D truss")
+        return np.ascontiguousarray(x)
+
+    shape = tuple(np.shape(pattern)) if not hasattr(pattern, "shape") else tuple(int(v) for v in pattern.shape)
+    if len(shape) != 4 or shape[0] != B or shape[1] < 1 or shape[2] != nJ_max:
+        raise ValueError(f"{who}: pattern must be [B={B}, L >= 1, nJ_max={nJ_max}, 2 or 3], got {list(shape)}")
+    L = shape[1]
+    given = {"pattern": vectors("pattern", pattern, (B, L, nJ_max)), "scale": None, "accel": None, "joint_mass": None}
+    if scale is not None:
+        x = _host_array(scale, np.float64)
+        if x.shape != (B, L, T1):
+            raise ValueError(f"{who}: scale must be [B={B}, L={L}, steps + 1 = {T1}], got {list(x.shape)}")
+        if not np.isfinite(x).all():
+            raise ValueError(f"{who}: scale has a non-finite entry")
+        given["scale"] = np.ascontiguousarray(x)
+    if accel is not None:
+        given["accel"] = vectors("accel", accel, (B, L, T1))
+    for name, ids, counts in (("monitor_joints", monitor_joints, packed.nJ), ("monitor_members", monitor_members, packed.nM)):
+        x = np.zeros([B, 0], dtype=np.int32) if ids is None else _host_array(ids, None)
+        if x.ndim != 2 or x.shape[0] != B or (x.size and not np.issubdtype(x.dtype, np.integer)):
+            raise ValueError(f"{who}: {name} must be an integer array [B={B}, P], got {x.dtype} {list(x.shape)}")
+        if x.size and (np.any(x < -1) or np.any(x >= np.asarray(counts).reshape(-1, 1))):
+            raise ValueError(f"{who}: {name} has an id outside its truss (-1 = none)")
+        given[name] = np.ascontiguousarray(x, dtype=np.int32)
+    if joint_mass is not None:
+        x = _host_array(joint_mass, np.float64)
+        finite = bool(np.isfinite(x).all())
+        _check_mass_args(who, B, nJ_max, x.shape, mass_scale,
+                         joint_mass_min=(float(x.min()) if x.size else 0.0) if finite else float("nan"))
+        given["joint_mass"] = np.ascontiguousarray(x)
+    else:
+        _check_mass_args(who, B, nJ_max, None, mass_scale)
+    Pj, Pm = given["monitor_joints"].shape[1], given["monitor_members"].shape[1]
+    nbytes = B * L * (8 * (4 * 3 * nJ_max + 2 * nM_max + T1 * (3 * Pj + Pm)) + 4 * (3 * nJ_max + 2 * nM_max))
+    if nbytes > max_result_bytes:
+        raise ValueError(f"{who}: the results of B={B} trusses, L={L} cases and {T1} time points take {nbytes} bytes, more "
+                         f"than max_result_bytes = {max_result_bytes}")
+    return given
+
+
+def solve_transient(trusses_or_packed, pattern, dt, steps, scale=None, accel=None, beta=0.25, gamma=0.5, damp_mass=0.0,
+                    damp_stiff=0.0, joint_mass=None, mass_scale=1.0, monitor_joints=None, monitor_members=None,
+                    device=None, reorder=False, options=None, on_device=False, sections=None, use_envelope=True,
+                    max_slab_bytes=64 << 30, max_result_bytes=4 << 30):
+    """The transient response of every truss of a batch to L excitations each, by Newmark time stepping
+    (`beta`, `gamma`; the defaults are the unconditionally stable average acceleration) with step `dt` over `steps`
+    steps, from ONE factorisation per truss (of K + sigma M; `DeviceBatch.factor_dynamic` / `DeviceBatch.transient`,
+    include/trs_dynamics.h).  M u'' + C u' + K u = scale(t) P - M iota(accel(t)): lumped mass as `solve_modes`
+    (`joint_mass` [B, nJ_max], `mass_scale`), Rayleigh damping C = damp_mass M + damp_stiff K, `pattern`
+    [B, L, nJ_max, dim] the load pattern of every case (caller's joint numbering; dim 2 or 3), `scale` [B, L, steps + 1]
+    its time function (None: 1, a step load), `accel` [B, L, steps + 1, dim] a ground acceleration (None: none; the
+    displacements are then relative to the ground).  The start is at rest: u = v = 0, a = f(0) / M.
+    `monitor_joints` [B, Pj], `monitor_members` [B, Pm]: joint / member ids (-1: none) whose histories are returned; the
+    envelopes cover every DOF and member.  Buckets, member forms, `reorder` plans, `options`, `on_device` and
+    `use_envelope` as `solve_load_cases`.  Bad arguments (`_check_transient_args`) raise ValueError before any device
+    work; there is no continuation at this level (`DeviceBatch.transient` carries a state).  Returns a `TransientResult`."""
+    packed = _as_packed(trusses_or_packed)
+    given = _check_transient_args(packed, pattern, dt, steps, beta, gamma, damp_mass, damp_stiff, scale, accel,
+                                  monitor_joints, monitor_members, joint_mass, mass_scale, sections, max_result_bytes)
+    torch, dev = _require_gpu(device)
+    L, T1 = int(given["pattern"].shape[1]), int(steps) + 1
+    on = {k: _device_f64(torch, dev, given[k]) for k in ("pattern", "scale", "accel", "joint_mass")}
+    mon = {k: torch.from_numpy(given[k]).to(dev) for k in ("monitor_joints", "monitor_members")}
+    out = _new_result(torch, dev, TransientResult, packed.B,
+                      {"L": L, "nJ": packed.nJ_max, "nM": packed.nM_max, "T1": T1,
+                       "Pj": int(mon["monitor_joints"].shape[1]), "Pm": int(mon["monitor_members"].shape[1])})
+    factor = lambda db, part: db.factor_dynamic(dt, beta, gamma, damp_mass, damp_stiff,
+                                                joint_mass=part.cut(on["joint_mass"], nJ=1), mass_scale=mass_scale)
+    for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope, factor=factor):
+        _put_result(part, out, db.transient(part.cut(on["pattern"], nJ=2), int(steps), scale=part.cut(on["scale"]),
+                                            accel=part.cut(on["accel"]), monitor_joints=part.cut(mon["monitor_joints"]),
+                                            monitor_members=part.cut(mon["monitor_members"])))
+    return _finish_result(torch, dev, out, on_device)
 
 
 @dataclass

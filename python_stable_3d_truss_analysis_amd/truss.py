@@ -445,6 +445,55 @@ class Truss:
         shapes = [dict(zip(range(nJ), result.shape[0, k, :nJ, :dim].copy())) for k in range(count)]
         return omega, shapes
 
+    def TransientResponse(self, dt, steps, cases=None, scale=None, groundAcceleration=None, beta=0.25, gamma=0.5,
+                          dampMass=0.0, dampStiff=0.0, jointMasses=None, massScale=1.0, monitorJoints=(),
+                          monitorMembers=()):
+        """What this truss does under a load history or a ground motion: `steps` Newmark steps of size `dt` (`beta`,
+        `gamma`; the defaults are the average-acceleration rule) of M u'' + C u' + K u = scale(t) P - M iota(ag(t)) from
+        rest, with the lumped mass of `NaturalFrequencies` (`jointMasses`, `massScale`) and Rayleigh damping
+        C = dampMass M + dampStiff K, from ONE factorisation (`batch.solve_transient`).  `cases`: a list of
+        `{jointID: vector}` load patterns P as `SolveLoadCases` takes them (None: the truss's own forces as one case);
+        `scale`: [L, steps + 1] or [steps + 1] (the same for every case), None = 1; `groundAcceleration`:
+        [L, steps + 1, dim] or [steps + 1, dim], None = none (the displacements are then relative to the ground).
+        Returns a dict of numpy arrays, L the number of cases, T = steps:
+          "displace", "velocity", "acceleration"   [L, nJ, dim]   the state at the last time point,
+          "peakDisplace", "peakDisplaceStep"       [L, nJ, dim]   max |u| over the points 0 .. T and the first point there,
+          "forceMax", "forceMaxStep", "forceMin", "forceMinStep"  [L, nM]   the signed extremes of the member forces,
+          "historyDisplace" [L, T + 1, len(monitorJoints), dim], "historyForce" [L, T + 1, len(monitorMembers)].
+        The truss's loads, its solved state and its results stay as they are.  Raises ValueError for bad arguments (as
+        `batch.solve_transient`), `TrussNotStableError` when the counting test fails and `numpy.linalg.LinAlgError`
+        when K + sigma M is not positive definite."""
+        if not self.isStable:
+            raise TrussNotStableError("The truss is not stable !")
+        from .batch import pack_trusses, solve_transient  # late import: keeps the model importable without torch
+        packed = pack_trusses([self])
+        nJ, nM, dim = len(self._pos), len(self._bars), self._dim
+        pattern = np.asarray(packed.loads, dtype=np.float64)[:, None] if cases is None \
+            else self._case_loads(list(cases), packed.nJ_max)
+        L = pattern.shape[1]
+        spread = lambda x, nd: None if x is None else \
+            np.array(np.broadcast_to(np.asarray(x, dtype=np.float64), (L,) + np.shape(x)[-nd:]))[None]
+        masses = None
+        if jointMasses:
+            masses = np.zeros([1, packed.nJ_max])
+            for jointID, mass in jointMasses.items():
+                masses[0, jointID] = mass
+        result = solve_transient(packed, pattern, dt, steps, scale=spread(scale, 1), accel=spread(groundAcceleration, 2),
+                                 beta=beta, gamma=gamma, damp_mass=dampMass, damp_stiff=dampStiff, joint_mass=masses,
+                                 mass_scale=massScale,
+                                 monitor_joints=np.asarray(list(monitorJoints), dtype=np.int64).reshape(1, -1),
+                                 monitor_members=np.asarray(list(monitorMembers), dtype=np.int64).reshape(1, -1))
+        if int(result.info[0]) != 0:
+            raise np.linalg.LinAlgError("Singular matrix")
+        return {"displace": result.displace[0, :, :nJ, :dim].copy(), "velocity": result.velocity[0, :, :nJ, :dim].copy(),
+                "acceleration": result.acceleration[0, :, :nJ, :dim].copy(),
+                "peakDisplace": result.peak_displace[0, :, :nJ, :dim].copy(),
+                "peakDisplaceStep": result.peak_displace_step[0, :, :nJ, :dim].copy(),
+                "forceMax": result.force_max[0, :, :nM].copy(), "forceMaxStep": result.force_max_step[0, :, :nM].copy(),
+                "forceMin": result.force_min[0, :, :nM].copy(), "forceMinStep": result.force_min_step[0, :, :nM].copy(),
+                "historyDisplace": result.history_displace[0, ..., :dim].copy(),
+                "historyForce": result.history_force[0].copy()}
+
     def MemberLoss(self, cases=None, rTol=None, returnForces=False):
         """What the loss of any ONE member does to this truss, for every member and every load case, from ONE
         factorisation (`batch.solve_member_loss`): `cases` is a list of `{jointID: vector}` dicts as `SolveLoadCases`
