@@ -39,7 +39,8 @@ __all__ = ["Truss", "Member", "MemberType", "SupportType", "MetapathType", "Task
            "solve_gradients", "GradientResult", "DifferentiableTruss",
            "solve_modes", "ModeResult", "solve_effect_cases", "EffectCaseResult", "LoadCase",
            "solve_member_loss", "MemberLossResult", "solve_influence", "InfluenceResult",
-           "solve_member_sets", "MemberSetResult", "solve_transient", "TransientResult"]
+           "solve_member_sets", "MemberSetResult", "solve_transient", "TransientResult",
+           "solve_nonlinear", "NonlinearResult"]
 
 
 def __getattr__(name):
@@ -47,7 +48,8 @@ def __getattr__(name):
     if name in ("solve_batch", "pack_trusses", "PackedBatch", "BatchResult", "RaggedSolver", "DeviceBatch",
                 "solve_load_cases", "LoadCaseResult", "solve_gradients", "GradientResult", "solve_modes", "ModeResult",
                 "solve_effect_cases", "EffectCaseResult", "solve_member_loss", "MemberLossResult", "solve_influence",
-                "InfluenceResult", "solve_member_sets", "MemberSetResult", "solve_transient", "TransientResult"):
+                "InfluenceResult", "solve_member_sets", "MemberSetResult", "solve_transient", "TransientResult",
+                "solve_nonlinear", "NonlinearResult"):
         from . import batch
         return getattr(batch, name)
     if name == "DifferentiableTruss":

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h`, `include/trs_influence.h`, `include/trs_sets.h` and `include/trs_dynamics.h` (library: `libtrs_hip.so`, in-tree).
+"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h`, `include/trs_influence.h`, `include/trs_sets.h`, `include/trs_dynamics.h` and `include/trs_nonlinear.h` (library: `libtrs_hip.so`, in-tree).
 
 There is no fallback: if the library is missing, `load()` raises `HipExtensionError`.
 """
@@ -150,6 +150,20 @@ DYN_SIGNATURES = {
     "trs_dyn_collect": (_I, [_I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
 }
 
+#: every symbol `include/trs_nonlinear.h` declares (geometrically nonlinear statics: Newton on the tangent factor;
+#: csrc/nonlinear.hip, the same library)
+NL_SIGNATURES = {
+    "trs_nl_abi_version": (_I, []),
+    "trs_nl_fits": (_I, [_I, _I]),
+    "trs_nl_state": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _D, _D, _I, _I, _I, _I, _P, _P, _P, _P, _P,
+                          _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "trs_nl_state_tab": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _D, _D, _I, _I, _I, _I, _P, _P, _P, _P,
+                              _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "trs_nl_tangent": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _P, _P]),
+    "trs_nl_tangent_tab": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _P, _P]),
+    "trs_nl_update": (_I, [_I, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P]),
+}
+
 #: must equal TRS_ABI_VERSION of include/trs_solver.h
 ABI_VERSION = 10
 #: must equal TRS_MODES_ABI_VERSION of include/trs_modes.h
@@ -164,6 +178,10 @@ INFLUENCE_ABI_VERSION = 1
 SETS_ABI_VERSION = 1
 #: must equal TRS_DYN_ABI_VERSION of include/trs_dynamics.h
 DYN_ABI_VERSION = 1
+#: must equal TRS_NL_ABI_VERSION of include/trs_nonlinear.h
+NL_ABI_VERSION = 1
+#: TRS_NL_* of include/trs_nonlinear.h: the status of a truss in a load step of the nonlinear analysis
+NL_ACTIVE, NL_CONVERGED, NL_ITER_LIMIT, NL_NOT_PD, NL_NOT_ATTEMPTED = -1, 0, 1, 2, 3
 #: TRS_SETS_MAX of include/trs_sets.h: members per scenario at most
 SETS_MAX = 8
 #: TRS_MODES_BLOCK of include/trs_modes.h: vectors per truss of the block iteration (one case group)
@@ -212,7 +230,7 @@ def load():
     except OSError as exc:
         raise HipExtensionError(f"cannot load {LIB_PATH}: {exc}") from exc
     for table in (SIGNATURES, MODES_SIGNATURES, EFFECTS_SIGNATURES, LOSS_SIGNATURES, INFLUENCE_SIGNATURES,
-                  SETS_SIGNATURES, DYN_SIGNATURES):
+                  SETS_SIGNATURES, DYN_SIGNATURES, NL_SIGNATURES):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype = restype
@@ -220,7 +238,8 @@ def load():
     if lib.trs_abi_version() != ABI_VERSION or lib.trs_modes_abi_version() != MODES_ABI_VERSION \
             or lib.trs_effects_abi_version() != EFFECTS_ABI_VERSION or lib.trs_loss_abi_version() != LOSS_ABI_VERSION \
             or lib.trs_influence_abi_version() != INFLUENCE_ABI_VERSION \
-            or lib.trs_sets_abi_version() != SETS_ABI_VERSION or lib.trs_dyn_abi_version() != DYN_ABI_VERSION:
+            or lib.trs_sets_abi_version() != SETS_ABI_VERSION or lib.trs_dyn_abi_version() != DYN_ABI_VERSION \
+            or lib.trs_nl_abi_version() != NL_ABI_VERSION:
         raise HipExtensionError("libtrs_hip.so ABI version mismatch")
     _lib = lib
     return lib

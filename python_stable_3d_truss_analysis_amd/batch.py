@@ -597,6 +597,25 @@ def newmark_constants(dt, beta=0.25, gamma=0.5, damp_mass=0.0, damp_stiff=0.0):
             "a2": a2, "a3": a3, "a4": a4, "a5": a5, "s": s, "sigma": (a0 + a1 * damp_mass) / s}
 
 
+def _check_newton_args(who, load_factors, tol=1e-9, max_iters=25, check_every=1):
+    """The Newton arguments of the nonlinear analysis (ValueError): `load_factors` a non-empty sequence of finite
+    numbers, `tol` finite and positive, `max_iters` and `check_every` integers of at least 1.  Returns the load factors
+    as a list of floats."""
+    try:
+        lams = [float(x) for x in np.asarray(load_factors, dtype=np.float64).reshape(-1)] \
+            if np.ndim(load_factors) == 1 else None
+    except (TypeError, ValueError):
+        lams = None
+    if not lams or not np.isfinite(lams).all():
+        raise ValueError(f"{who}: load_factors must be a non-empty sequence of finite numbers, got {load_factors!r}")
+    if isinstance(tol, bool) or not isinstance(tol, (int, float, np.floating)) or not np.isfinite(tol) or not tol > 0:
+        raise ValueError(f"{who}: tol must be a finite positive number, got {tol!r}")
+    for name, x in (("max_iters", max_iters), ("check_every", check_every)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 1:
+            raise ValueError(f"{who}: {name} must be an integer of at least 1, got {x!r}")
+    return lams
+
+
 def _check_mass_args(who, B, nJ_max, joint_mass_shape, mass_scale, joint_mass_min=None):
     """The mass arguments that the transient analysis shares with `modes` (`_check_mode_args`), refused in `who`'s name."""
     try:
@@ -805,12 +824,15 @@ class DeviceBatch:
                (HINT_ALL_TILES if self.all_tiles and has_env else 0) | \
                (HINT_ALL_WIDE if self.options["all_wide"] and has_env else 0)
 
-    def assemble(self, flags=0):
+    def assemble(self, flags=0, xyz=None, loads=None):
+        """`trs_assemble` of the resident batch; `xyz`, `loads` (float64 [B, nJ_max, 3] device tensors in the batch's own
+        joint numbering): other coordinates and loads than the batch's own (`nonlinear`: the deformed coordinates and
+        the residual)."""
         flags |= self._assemble_flags()
         fn, what = self._fn("trs_assemble")
         _capi.check(fn(
-            self.B, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *self._members(),
-            self.loads.data_ptr(), self.free_index.data_ptr(),
+            self.B, self.nJ_max, self.nM_max, (self.xyz if xyz is None else xyz).data_ptr(), *self._members(),
+            (self.loads if loads is None else loads).data_ptr(), self.free_index.data_ptr(),
             self.n_free.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), self.ld, self.rows,
             self.S.data_ptr(), flags, self.work.data_ptr(), self._env_ptr(), self.uf.data_ptr(), self.rows,
             self._stream()), what)
@@ -1596,6 +1618,109 @@ class DeviceBatch:
                 out["a"].data_ptr(), stream), "trs_dyn_collect")
         state["step"] += T1 - 1
         return out
+
+    #: the results of `nonlinear`: key -> (trailing shape, dtype); "S", "nJ", "nM" are the call's sizes
+    NONLINEAR_SHAPES = {"u": (("S", "nJ", 3), "float64"), "N": (("S", "nM"), "float64"),
+                        "f_ext": (("S", "nJ", 3), "float64"), "iters": (("S",), "int32"), "status": (("S",), "int32"),
+                        "residual": (("S",), "float64")}
+
+    def nonlinear(self, load_factors, tol=1e-9, max_iters=25, check_every=1, out=None):
+        """Geometrically nonlinear statics of the resident batch under `load_factors` times its own loads
+        (include/trs_nonlinear.h: corotational bars, Newton's method on the tangent factor).  The load steps run in the
+        given order, each from the previous step's converged u (the first from u = 0).  Per Newton iteration six
+        launches: `trs_nl_state` (member forces, residual, convergence test), `trs_assemble` at the deformed
+        coordinates with the residual as load, `trs_nl_tangent` (the slab then holds K_t), `trs_potrf_batched` and
+        `trs_potrs_batched` as they are, `trs_nl_update`.  A truss is converged when |r|_inf <= `tol` |lambda P|_inf;
+        it is then frozen, as is one whose tangent is not positive definite (`info != 0`: it keeps its last accepted u),
+        so a truss's results depend neither on the others nor on `check_every` nor on `max_iters` beyond its own count.
+        Every `check_every` iterations one int32 - the number of trusses still iterating - is downloaded to end a step
+        early.  Returns a dict of device tensors over the S load steps, in the caller's joint numbering: u, f_ext
+        [B, S, nJ_max, 3] (f_ext: the applied load at free DOFs, the reaction at held ones), N [B, S, nM_max], iters,
+        status (int32 [B, S]: 0 converged, 1 iteration limit, 2 tangent not positive definite - u is the last accepted
+        iterate, iters the number of accepted updates -, 3 not attempted because an earlier step failed) and residual
+        [B, S] = |r|_inf at the u returned.  Afterwards the slab holds a tangent factor: the static analyses and
+        `transient` refuse with their "no factor" errors until `factor()` / `factor_dynamic()`; `generation` is bumped;
+        `self.xyz` and `self.loads` are untouched.  The compact member form of the assembly (`options["compact"]`) has
+        no slab to amend and is refused, as is a batch on the fused small-system path."""
+        t = self.torch
+        if self.small:
+            raise ValueError("nonlinear(): this batch takes the fused small-system kernel, which keeps no factor - "
+                             "build the DeviceBatch with use_small=False")
+        if self.options["compact"]:
+            raise ValueError("nonlinear(): options['compact'] leaves no slab that could be amended to the tangent")
+        lams = _check_newton_args("nonlinear()", load_factors, tol, max_iters, check_every)
+        S = len(lams)
+        shapes = {k: ([self.B] + [{"S": S, "nJ": self.nJ_max, "nM": self.nM_max}.get(n, n) for n in shape], getattr(t, dtype))
+                  for k, (shape, dtype) in self.NONLINEAR_SHAPES.items()}
+        out = self._out_tensors("nonlinear", shapes, out)
+        if self.B == 0:
+            return out
+        if not self.lib.trs_nl_fits(self.nJ_max, self.nM_max):
+            raise HipExtensionError(f"nonlinear(): a truss of {self.nJ_max} joints / {self.nM_max} members exceeds the LDS "
+                                    "of the state kernel (trs_nl_fits)")
+        self._factored = False
+        self._dynamic = None
+        self._forward = None
+        ws = self._nl_workspace(max_iters, out)
+        with t.cuda.device(self.device):
+            self.dofmap()
+            for step, lam in enumerate(lams):
+                ws["active"].zero_()
+                it = 0
+                while True:
+                    last = it == max_iters
+                    self._nl_state(ws, lam, tol, it, last, step, S, it)
+                    if last:
+                        break
+                    if it % check_every == 0 and int(ws["active"][it].item()) == 0:
+                        self._nl_state(ws, lam, tol, it, 2, step, S, max_iters + 1)   # (no truss is active: outputs only)
+                        break
+                    self.assemble(xyz=ws["Xc"], loads=ws["R"])
+                    self._nl_tangent(ws)
+                    self.potrf()
+                    self.potrs()
+                    it += 1
+                    self._nl_update(ws, it)
+            # (what the factorisation reported for the tangent that ended a truss with status 2; 0 for every other truss)
+            self.info.copy_(ws["st"][:, 2])
+        self._bump_generation()
+        return out
+
+    # the stages of `nonlinear` (tools/bench_nonlinear.py times them one by one)
+    def _nl_workspace(self, max_iters, out):
+        """The state of a `nonlinear` run: U [B, nJ_max, 3] (joint layout, the batch's numbering) and the status words
+        st [B, 4], zeroed; Xc, R (the inputs of the assembly), the member table W and the `active` counters - one per
+        iteration of a load step, plus one for the call that only writes the outputs."""
+        t, dev = self.torch, self.device
+        U = t.zeros([self.B, self.nJ_max, 3], dtype=t.float64, device=dev)
+        return {"U": U, "st": t.zeros([self.B, 4], dtype=t.int32, device=dev), "Xc": t.empty_like(U), "R": t.empty_like(U),
+                "W": t.empty([self.B, max(self.nM_max, 1), 6], dtype=t.float64, device=dev),
+                "active": t.zeros([max_iters + 2], dtype=t.int32, device=dev), "out": out}
+
+    def _nl_state(self, ws, lam, tol, it, last, step, S, slot):
+        jo, stream, tab = self._case_launch()
+        out = ws["out"]
+        _capi.check(getattr(self.lib, "trs_nl_state" + tab)(
+            self.B, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *self._members(), self.loads.data_ptr(),
+            self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), self.rows,
+            float(lam), float(tol), it, int(last), step, S, ws["U"].data_ptr(), ws["st"].data_ptr(), ws["Xc"].data_ptr(),
+            ws["R"].data_ptr(), ws["W"].data_ptr(), ws["active"][slot:].data_ptr(), out["u"].data_ptr(),
+            out["N"].data_ptr(), out["f_ext"].data_ptr(), out["iters"].data_ptr(), out["status"].data_ptr(),
+            out["residual"].data_ptr(), jo, stream), "trs_nl_state" + tab)
+
+    def _nl_tangent(self, ws, flags=0):
+        """`flags`: what the assembly before it was given beside the batch's own flags (tests: ASM_FULL_SYMMETRIC)."""
+        _, stream, tab = self._case_launch()
+        _capi.check(getattr(self.lib, "trs_nl_tangent" + tab)(
+            self.B, self.nJ_max, self.nM_max, *self._members(), self.free_index.data_ptr(), self.n_free.data_ptr(),
+            self.nJ.data_ptr(), self.nM.data_ptr(), self.ld, self.rows, self.S.data_ptr(), self._env_ptr(),
+            flags | self._assemble_flags(), ws["W"].data_ptr(), stream), "trs_nl_tangent" + tab)
+
+    def _nl_update(self, ws, it):
+        _capi.check(self.lib.trs_nl_update(
+            self.B, self.nJ_max, self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(),
+            self.uf.data_ptr(), self.rows, self.info.data_ptr(), it, ws["U"].data_ptr(), ws["st"].data_ptr(),
+            self._stream()), "trs_nl_update")
 
     def fitness(self, allow_stress, allow_displace, out=None):
         """(weight, stress_violation, displacement_violation) per truss, on device."""
@@ -3391,6 +3516,69 @@ def solve_transient(trusses_or_packed, pattern, dt, steps, scale=None, accel=Non
         _put_result(part, out, db.transient(part.cut(on["pattern"], nJ=2), int(steps), scale=part.cut(on["scale"]),
                                             accel=part.cut(on["accel"]), monitor_joints=part.cut(mon["monitor_joints"]),
                                             monitor_members=part.cut(mon["monitor_members"])))
+    return _finish_result(torch, dev, out, on_device)
+
+
+@dataclass
+class NonlinearResult:
+    """Results of `solve_nonlinear` over the S load steps, in the caller's joint numbering: displace, external
+    [B, S, nJ_max, 3] (external: the applied load at free DOFs, the reaction at held ones), internal [B, S, nM_max]
+    (member forces, tension positive), iterations and status (int32 [B, S]: 0 converged, 1 iteration limit, 2 tangent not
+    positive definite - displace is then the last accepted iterate and iterations the number of accepted updates -, 3 not
+    attempted because an earlier step failed), residual [B, S] = |lambda P - f_int|_inf over the free DOFs at the
+    displacements returned.  info [B]: 0, or for a truss that ended with status 2 what the factorisation reported for the tangent
+    that was not positive definite (k > 0: its pivot k), latched when the status was set."""
+    displace: np.ndarray
+    internal: np.ndarray
+    external: np.ndarray
+    iterations: np.ndarray
+    status: np.ndarray
+    residual: np.ndarray
+    info: np.ndarray
+
+    FIELDS = {"displace": ("u", 0.0, "float64", ("S", "nJ", 3)), "internal": ("N", 0.0, "float64", ("S", "nM")),
+              "external": ("f_ext", 0.0, "float64", ("S", "nJ", 3)), "iterations": ("iters", 0, "int32", ("S",)),
+              "status": ("status", 0, "int32", ("S",)), "residual": ("residual", 0.0, "float64", ("S",))}
+
+
+def _check_nonlinear_args(packed, load_factors, tol=1e-9, max_iters=25, check_every=1, options=None, sections=None,
+                          max_result_bytes=4 << 30):
+    """The argument errors of `solve_nonlinear` that need no device (ValueError).  Returns the load factors as a list
+    of floats."""
+    who = "solve_nonlinear"
+    if sections is not None:
+        raise ValueError(f"{who}: sections= variants cannot be combined with the nonlinear analysis")
+    if options and options.get("compact"):
+        raise ValueError(f"{who}: options['compact'] leaves no slab that could be amended to the tangent")
+    lams = _check_newton_args(who, load_factors, tol, max_iters, check_every)
+    nbytes = packed.B * len(lams) * (8 * (6 * packed.nJ_max + packed.nM_max + 1) + 8)
+    if nbytes > max_result_bytes:
+        raise ValueError(f"{who}: the results of B={packed.B} trusses and {len(lams)} load steps take {nbytes} bytes, "
+                         f"more than max_result_bytes = {max_result_bytes}")
+    return lams
+
+
+def solve_nonlinear(trusses_or_packed, load_factors=(1.0,), tol=1e-9, max_iters=25, check_every=1, device=None,
+                    reorder=False, options=None, on_device=False, sections=None, use_envelope=True,
+                    max_slab_bytes=64 << 30, max_result_bytes=4 << 30):
+    """Geometrically nonlinear statics of every truss of a batch (large displacements, small strains; corotational
+    bars, include/trs_nonlinear.h) under `load_factors` times its own loads, one load step per factor in the given order,
+    each started from the previous step's displacements: Newton's method on the tangent stiffness, which has the
+    sparsity of K and is factored in the batch's slab (`DeviceBatch.nonlinear`).  `tol`: a truss is converged when
+    |lambda P - f_int|_inf <= tol |lambda P|_inf over its free DOFs; `max_iters` Newton iterations per step at most;
+    `check_every`: how often the host looks whether every truss is done.  A truss whose tangent is not positive definite
+    at an iterate (a limit point was passed: no path following here) stops with status 2 and its later steps get
+    status 3; the other trusses are unaffected.  Buckets, member forms, `reorder` plans, `options`, `on_device` and
+    `use_envelope` as `solve_load_cases`.  Bad arguments (`_check_nonlinear_args`) raise ValueError before any device
+    work.  Returns a `NonlinearResult`."""
+    packed = _as_packed(trusses_or_packed)
+    lams = _check_nonlinear_args(packed, load_factors, tol, max_iters, check_every, options, sections, max_result_bytes)
+    torch, dev = _require_gpu(device)
+    out = _new_result(torch, dev, NonlinearResult, packed.B, {"S": len(lams), "nJ": packed.nJ_max, "nM": packed.nM_max})
+    # (nothing to factor ahead: every Newton iteration assembles and factors its own tangent)
+    for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope,
+                                      factor=lambda db, part: None):
+        _put_result(part, out, db.nonlinear(lams, tol=tol, max_iters=max_iters, check_every=check_every))
     return _finish_result(torch, dev, out, on_device)
 
 

@@ -1,0 +1,499 @@
+// Geometrically nonlinear statics: Newton's method on the batch's tangent factor (include/trs_nonlinear.h).  The
+// assembly, the factorisation and the substitution of every iteration are trs_assemble, trs_potrf_batched and
+// trs_potrs_batched as they are; this file holds what goes around them:
+//
+//   trs_nl_state     one iterate: member forces, internal forces, Xc = X + u, R = lambda P - f_int, the convergence test,
+//                    the member table of the tangent kernel and - at the end of a load step - the step's outputs
+//   trs_nl_tangent   S += delta_m per member on the assembled slab: it then holds the tangent stiffness
+//   trs_nl_update    u += du for the trusses that are still iterating
+//
+// The formulation, per member m with ends j0, j1, undeformed coordinates X and displacement u:
+//     D = X_j1 - X_j0, L0 = |D|, dl = u_j1 - u_j0, d = D + dl, l = |d|, n = d / l
+//     e = (2 D.dl + dl.dl) / (L0 (l + L0))   (= (l - L0) / L0 exactly, without subtracting two lengths),  N = E A e
+//     internal force +N n at j1, -N n at j0
+//     k_t = (EA / L0) n n^T + (N / l)(I - n n^T);  trs_assemble at X + u writes (EA / l) n n^T, so
+//     delta_m = (EA/L0 - EA/l - N/l) n n^T + (N/l) I is what is missing: + on the diagonal blocks, - on the coupling ones
+//
+// trs_nl_state: one 256-thread work-group per truss.  One thread per DOF stages u in LDS (joint layout) and writes Xc;
+// one thread per member forms n, l, N; one thread per joint sums +- N n over its end list (trs_rec::build_end_lists,
+// add_end_force - the shape of trs_effects_rhs and trs_dyn_step -, the lists then re-sorted by (far joint, member id):
+// order_by_neighbour); the two norms are maxima, which do not depend on the order of the reduction.
+// trs_nl_tangent: one 256-thread work-group per truss, 16 slab rows (one 16-row chunk: one cend, one mask word) per pass,
+// 16 threads per row.  One thread owns a slab entry; no floating-point atomic; every sum in the lists' order.
+#include "../../include/trs_nonlinear.h"
+#include "../../include/trs_solver.h"
+#include "trs_common.h"
+#include "trs_recover.h"
+
+namespace {
+
+using namespace trs_rec;
+
+constexpr size_t NL_LDS_BUDGET = 160 * 1024;   // a CU's LDS
+constexpr int NL_W = 6;                        // doubles per member of the table W
+
+// LDS tables of the state kernel
+struct StateTables : EndLists {
+    double* red;  // [4]         the wave maxima of the two norms
+    double* v;    // [3 nJ_max]  u in joint layout, then r (free DOFs) / f_int (held DOFs)
+    double* pm;   // [nM_max]    N
+    double* pn;   // [3 nM_max]  n
+    int* oth;     // [2 nM_max]  the far joint of every list entry
+};
+
+__device__ __forceinline__ StateTables state_tables(double* sh, int nJ_max, int nM_max) {
+    StateTables t;
+    t.red = sh;
+    t.v = sh + 4;
+    t.pm = t.v + 3 * nJ_max;
+    t.pn = t.pm + nM_max;
+    t.cnt = reinterpret_cast<int*>(t.pn + 3 * nM_max);
+    t.start = t.cnt + nJ_max;
+    t.ends = t.start + nJ_max + 1;
+    t.oth = t.ends + 2 * nM_max;
+    return t;
+}
+
+size_t state_lds(int nJ_max, int nM_max) {
+    const size_t bytes = ((size_t)4 + 3 * (size_t)nJ_max + 4 * (size_t)nM_max) * sizeof(double) +
+                         ((size_t)2 * nJ_max + 1 + 4 * (size_t)nM_max) * sizeof(int);
+    return (bytes + 15) / 16 * 16;
+}
+
+// LDS tables of the tangent kernel: the joints' own delta blocks (6 doubles each) | end lists | other joint of every list
+// entry | free_index | DOF of a reduced row
+size_t tangent_lds(int nJ_max, int nM_max, int slab_rows) {
+    const size_t ints = (size_t)2 * nJ_max + 1 + 4 * (size_t)nM_max + 3 * (size_t)nJ_max + (size_t)slab_rows;
+    return ((size_t)6 * nJ_max * sizeof(double) + ints * sizeof(int) + 15) / 16 * 16;
+}
+
+// the joints whose end lists are built: those of the truss (an end-joint id outside them is left out of the sums)
+struct InTruss {
+    int joints;
+    __device__ __forceinline__ bool operator()(int j) const { return (j >= 0) & (j < joints); }
+};
+
+// The far joint of every list entry into `far` (-1: outside the truss), and every list re-sorted by (far joint, member id) -
+// the order of trs_assemble's adjacency lists, so that a sum here rounds as the assembly's own sums do: parallel members lie
+// side by side, and a member listed twice gives the bits of one member of twice the area wherever the linear solve does.
+// The sort is stable and the lists arrive in member-id order.  Thread j % 256 owns joint j here as in build_end_lists'
+// own sort, so no barrier is needed between the two; the caller places one before another thread reads a list.
+__device__ __forceinline__ void order_by_neighbour(const EndLists& t, int* far_all, const TrsMembers& mem, const size_t mbase,
+                                                   const int joints, const int tid) {
+    for (int j = tid; j < joints; j += 256) {
+        int* list = t.ends + t.start[j];
+        int* far = far_all + t.start[j];
+        const int deg = t.cnt[j];
+        for (int i = 0; i < deg; ++i) {
+            const int2 c = mem.ends(mbase + (list[i] >> 1));
+            const int o = (list[i] & 1) ? c.x : c.y;
+            far[i] = InTruss{joints}(o) ? o : -1;
+        }
+        for (int i = 1; i < deg; ++i) {
+            const int kf = far[i], ke = list[i];
+            int p = i - 1;
+            while (p >= 0 && far[p] > kf) {
+                far[p + 1] = far[p];
+                list[p + 1] = list[p];
+                --p;
+            }
+            far[p + 1] = kf;
+            list[p + 1] = ke;
+        }
+    }
+}
+
+// a maximum that keeps a NaN of either side (a NaN residual must never pass the convergence test)
+__device__ __forceinline__ double nan_max(const double a, const double b) { return (a > b || a != a) ? a : b; }
+
+__device__ __forceinline__ double block_nan_max(double v, double* slot, const int tid) {   // slot [4], 256 threads
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = nan_max(v, __shfl_xor(v, off));
+    __syncthreads();   // (the previous readers of slot are done)
+    if ((tid & 63) == 0) slot[tid >> 6] = v;
+    __syncthreads();
+    return nan_max(nan_max(slot[0], slot[1]), nan_max(slot[2], slot[3]));
+}
+
+__global__ __launch_bounds__(256) void trs_nl_state_kernel(
+    const double* __restrict__ xyz, const TrsMembers mem, const double* __restrict__ loads,
+    const int* __restrict__ free_index, const int* __restrict__ n_free, const int* __restrict__ nJ,
+    const int* __restrict__ nM, const int nJ_max, const int nM_max, const int ld_f, const double lambda, const double tol,
+    const int it, const int last, const int step, const int S, const double* __restrict__ U, int* __restrict__ st,
+    double* __restrict__ Xc, double* __restrict__ R, double* __restrict__ W, int* __restrict__ active,
+    double* __restrict__ u_out, double* __restrict__ N_out, double* __restrict__ f_out, int* __restrict__ iters,
+    int* __restrict__ status_out, double* __restrict__ residual, const int* __restrict__ joint_out) {
+    extern __shared__ double sh[];   // (no static LDS beside it: the dynamic ceiling is the whole of a CU's)
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int joints = min(max(nJ[b], 0), nJ_max), members = min(max(nM[b], 0), nM_max);
+    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
+    const int n = min(max(n_free[b], 0), ld_f);
+    const StateTables t = state_tables(sh, nJ_max, nM_max);
+    double* ush = t.v;
+    const int* fi = free_index + (size_t)b * ndof_max;
+    const double* X = xyz + (size_t)b * ndof_max;
+    const double* P = loads + (size_t)b * ndof_max;
+    const double* Ub = U + (size_t)b * ndof_max;
+    const size_t mbase = (size_t)b * nM_max;
+    const int* jo = joint_out != nullptr ? joint_out + (size_t)b * nJ_max : nullptr;
+    // (every thread reads the status word before the barriers below; thread 0 writes it behind them)
+    int status = st[4 * b], its = st[4 * b + 1];
+    if (it == 0 && last != 2) {   // the load step begins (not again in a call that only writes the outputs)
+        status = status >= TRS_NL_ITER_LIMIT ? TRS_NL_NOT_ATTEMPTED : TRS_NL_ACTIVE;
+        its = 0;
+    }
+    auto row_of = [&](int d) {   // the reduced row of DOF d, -1: held, past the truss's joints or outside the arrays
+        const int r = d < ndof ? fi[d] : -1;
+        return r < n ? r : -1;
+    };
+    build_end_lists(t, mem, mbase, joints, members, nJ_max, tid, InTruss{joints});
+    order_by_neighbour(t, t.oth, mem, mbase, joints, tid);
+    // ---- the state, one thread per DOF ----
+    for (int d = tid; d < ndof_max; d += 256) {
+        const double u = row_of(d) >= 0 ? Ub[d] : 0.0;
+        ush[d] = u;
+        Xc[(size_t)b * ndof_max + d] = X[d] + u;
+    }
+    __syncthreads();   // (u is staged, the end lists are sorted)
+    // ---- one thread per member: n, l, N ----
+    for (int m = tid; m < members; m += 256) {
+        int2 c = mem.ends(mbase + m);
+        c.x = min(max(c.x, 0), nJ_max - 1);
+        c.y = min(max(c.y, 0), nJ_max - 1);
+        double D[3], dl[3], d[3], L02 = 0.0, l2 = 0.0, Ddl = 0.0, dldl = 0.0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            D[a] = X[3 * c.y + a] - X[3 * c.x + a];
+            dl[a] = ush[3 * c.y + a] - ush[3 * c.x + a];
+            d[a] = D[a] + dl[a];
+            L02 += D[a] * D[a];
+            l2 += d[a] * d[a];
+            Ddl += D[a] * dl[a];
+            dldl += dl[a] * dl[a];
+        }
+        const double L0 = sqrt(L02), l = sqrt(l2);
+        const double EA = mem.EA(mbase + m);
+        const double e = (2.0 * Ddl + dldl) / (L0 * (l + L0));
+        const double N = EA * e;
+        const double g = N / l;
+        double* w = W + (mbase + m) * NL_W;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double na = d[a] / l;
+            t.pn[3 * m + a] = na;
+            w[a] = na;
+        }
+        t.pm[m] = N;
+        w[3] = EA / L0 - EA / l - g;
+        w[4] = g;
+        w[5] = N;
+    }
+    __syncthreads();   // (the readers of u in ush are done; N and n are in place)
+    // ---- one thread per joint: f_int, r = lambda P - f_int at its free DOFs ----
+    double rmax = 0.0, pmax = 0.0;
+    for (int j = tid; j < joints; j += 256) {
+        double f[3] = {0.0, 0.0, 0.0};
+        const int* list = t.ends + t.start[j];
+        const int deg = t.cnt[j];
+        for (int i = 0; i < deg; ++i) {
+            const int m = list[i] >> 1, end = list[i] & 1;
+            const double c3[3] = {t.pn[3 * m], t.pn[3 * m + 1], t.pn[3 * m + 2]};
+            add_end_force(f, c3, t.pm[m], end);
+        }
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const int d = 3 * j + a;
+            if (row_of(d) >= 0) {
+                const double p = lambda * P[d];
+                const double r = p - f[a];
+                ush[d] = r;
+                rmax = nan_max(rmax, fabs(r));
+                pmax = nan_max(pmax, fabs(p));
+            } else {
+                ush[d] = f[a];   // the reaction
+            }
+        }
+    }
+    rmax = block_nan_max(rmax, t.red, tid);
+    pmax = block_nan_max(pmax, t.red, tid);
+    if (status == TRS_NL_ACTIVE) {
+        if (pmax == 0.0 || rmax <= tol * pmax)
+            status = TRS_NL_CONVERGED;
+        else if (last)
+            status = TRS_NL_ITER_LIMIT;
+    }
+    const bool still = status == TRS_NL_ACTIVE;
+    for (int d = tid; d < ndof_max; d += 256) R[(size_t)b * ndof_max + d] = (still && row_of(d) >= 0) ? ush[d] : 0.0;
+    if (tid == 0) {
+        st[4 * b] = status;
+        st[4 * b + 1] = its;
+        if (still) atomicAdd(active, 1);
+    }
+    if (!last) return;
+    // ---- the outputs of this load step, in the caller's numbering ----
+    const size_t bs = (size_t)b * S + step;
+    for (int d = tid; d < ndof_max; d += 256) {
+        const int j = d / 3;
+        int id = jo != nullptr ? jo[j] : j;
+        id = ((id >= 0) & (id < nJ_max)) ? id : j;
+        const size_t o = bs * ndof_max + 3 * id + d % 3;
+        const bool free_dof = row_of(d) >= 0;
+        u_out[o] = free_dof ? Ub[d] : 0.0;
+        f_out[o] = d < ndof ? (free_dof ? lambda * P[d] : ush[d]) : 0.0;
+    }
+    for (int m = tid; m < nM_max; m += 256) N_out[bs * nM_max + m] = m < members ? t.pm[m] : 0.0;
+    if (tid == 0) {
+        iters[bs] = its;
+        status_out[bs] = status;
+        residual[bs] = rmax;
+    }
+}
+
+__global__ __launch_bounds__(256) void trs_nl_tangent_kernel(
+    const TrsMembers mem, const int* __restrict__ free_index, const int* __restrict__ n_free,
+    const int* __restrict__ nJ, const int* __restrict__ nM, const int nJ_max, const int nM_max, const int ld,
+    const int slab_rows, double* __restrict__ S_all, const int* __restrict__ env_all, const int full,
+    const double* __restrict__ W) {
+    extern __shared__ double sh[];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int joints = min(max(nJ[b], 0), nJ_max), members = min(max(nM[b], 0), nM_max);
+    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
+    const int n = min(max(n_free[b], 0), slab_rows), npad = min(trs_round_up(n, TRS_NB), slab_rows);
+    const int nch = npad / 16;
+    double* own = sh;   // [nJ_max][6] the sum of +delta_m over a joint's member ends: xx xy xz yy yz zz
+    EndLists t;
+    t.cnt = reinterpret_cast<int*>(sh + 6 * nJ_max);
+    t.start = t.cnt + nJ_max;
+    t.ends = t.start + nJ_max + 1;
+    int* oth = t.ends + 2 * nM_max;   // [2 nM_max] the joint at the far end of every list entry
+    int* fi = oth + 2 * nM_max;       // [3 nJ_max] reduced row per DOF, -1: none
+    int* rowdof = fi + ndof_max;      // [slab_rows] DOF of a reduced row, -1: none
+    const size_t mbase = (size_t)b * nM_max;
+    const int* fig = free_index + (size_t)b * ndof_max;
+    for (int c = tid; c < slab_rows; c += 256) rowdof[c] = -1;
+    build_end_lists(t, mem, mbase, joints, members, nJ_max, tid, InTruss{joints});
+    __syncthreads();   // (the lists are sorted; rowdof is cleared)
+    for (int d = tid; d < ndof_max; d += 256) {
+        int r = d < ndof ? fig[d] : -1;
+        r = r < n ? r : -1;
+        fi[d] = r;
+        if (r >= 0) rowdof[r] = d;
+    }
+    order_by_neighbour(t, oth, mem, mbase, joints, tid);
+    const double* Wb = W + mbase * NL_W;
+    // delta_m = w3 n n^T + w4 I, entry (r, s) formed as w3 (n_r n_s) [+ w4]: symmetric to the bit, as the assembly's k (c_r c_s)
+    auto delta = [&](int m, double (&v)[6]) {
+        const double* w = Wb + (size_t)m * NL_W;
+        const d2 n01 = *reinterpret_cast<const d2*>(w), n2a = *reinterpret_cast<const d2*>(w + 2);
+        const double g = w[4];
+        v[0] = n2a.y * (n01.x * n01.x) + g;
+        v[1] = n2a.y * (n01.x * n01.y);
+        v[2] = n2a.y * (n01.x * n2a.x);
+        v[3] = n2a.y * (n01.y * n01.y) + g;
+        v[4] = n2a.y * (n01.y * n2a.x);
+        v[5] = n2a.y * (n2a.x * n2a.x) + g;
+    };
+    // one thread per joint, once: its own block (every row pass below would otherwise walk the whole list again, one
+    // dependent load of W after the other; the thread that owns the joint's lists sums them, so no barrier before)
+    for (int j = tid; j < joints; j += 256) {
+        double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        const int s0 = t.start[j], deg = t.cnt[j];
+        for (int i = 0; i < deg; ++i) {
+            if (oth[s0 + i] < 0 || oth[s0 + i] == j) continue;
+            double v[6];
+            delta(t.ends[s0 + i] >> 1, v);
+#pragma unroll
+            for (int q = 0; q < 6; ++q) acc[q] += v[q];
+        }
+#pragma unroll
+        for (int q = 0; q < 6; ++q) own[6 * j + q] = acc[q];
+    }
+    __syncthreads();
+    const int* cend = nullptr;
+    const int* kmask = nullptr;
+    if (env_all != nullptr) {
+        const int* env = env_all + (size_t)b * trs_env_stride(slab_rows);
+        cend = env + trs_env_cend_offset(slab_rows);
+        kmask = env + trs_env_kmask_offset(slab_rows);
+    }
+    double* Sb = S_all + (size_t)b * slab_rows * ld;
+    const int rr = tid >> 4, e = tid & 15;
+    for (int c0 = 0; c0 < n; c0 += 16) {
+        const int c = c0 + rr;
+        if (c >= n) continue;
+        const int dof = rowdof[c];
+        if (dof < 0) continue;
+        const int a = dof / 3, r = dof - 3 * a;
+        const int chunk = c0 >> 4;
+        // the stored part of this row (trs_assemble's row loop): columns [i_lo, i_hi), the tiles of the mask word
+        const int i_lo = full ? 0 : 16 * chunk;
+        const int i_hi = (cend != nullptr && !full) ? 16 * min(max(cend[chunk], 0), nch) : npad;
+        const int km = (kmask != nullptr && !full) ? kmask[chunk] : -1;
+        auto stored = [&](int q) {
+            if (q < i_lo || q >= i_hi) return false;
+            if (km == -1) return true;
+            const int tl = (q >> 4) - chunk;
+            return tl >= 0 && tl < 32 && (((unsigned)km >> tl) & 1u) != 0u;
+        };
+        // row r of [xx xy xz; xy yy yz; xz yz zz]
+        const int k0 = r, k1 = r == 0 ? 1 : (r == 1 ? 3 : 4), k2 = r == 0 ? 2 : (r == 1 ? 4 : 5);
+        const int s0 = t.start[a], deg = t.cnt[a];
+        double* row = Sb + (size_t)c * ld;
+        if (e == 15) {   // the joint's own block: + delta_m over all its member ends, summed above in list order
+            const double acc[3] = {own[6 * a + k0], own[6 * a + k1], own[6 * a + k2]};
+#pragma unroll
+            for (int s = 0; s < 3; ++s) {
+                const int q = fi[3 * a + s];
+                if (q >= 0 && stored(q) && acc[s] != 0.0) row[q] += acc[s];
+            }
+            continue;
+        }
+        for (int i = e; i < deg; i += 15) {   // the coupling block of the neighbour whose FIRST end this is
+            const int other = oth[s0 + i];
+            if (other < 0 || other == a) continue;
+            if (i > 0 && oth[s0 + i - 1] == other) continue;   // (the lists are sorted by neighbour)
+            double acc[3] = {0.0, 0.0, 0.0};
+            for (int p = i; p < deg && oth[s0 + p] == other; ++p) {   // parallel members: side by side, in member-id order
+                double v[6];
+                delta(t.ends[s0 + p] >> 1, v);
+                acc[0] -= v[k0];
+                acc[1] -= v[k1];
+                acc[2] -= v[k2];
+            }
+#pragma unroll
+            for (int s = 0; s < 3; ++s) {
+                const int q = fi[3 * other + s];
+                if (q >= 0 && stored(q) && acc[s] != 0.0) row[q] += acc[s];
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void trs_nl_update_kernel(const int nJ_max, const int* __restrict__ free_index,
+                                                            const int* __restrict__ n_free, const int* __restrict__ nJ,
+                                                            const double* __restrict__ uf, const int ld_uf,
+                                                            const int* __restrict__ info, const int it,
+                                                            double* __restrict__ U, int* __restrict__ st) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (st[4 * b] != TRS_NL_ACTIVE) return;   // (uniform over the work-group; only thread 0 writes it, behind the barrier)
+    const int pivot = info[b];
+    const bool ok = pivot == 0;
+    __syncthreads();
+    if (tid == 0) {
+        if (ok)
+            st[4 * b + 1] = it;
+        else
+            st[4 * b] = TRS_NL_NOT_PD;
+            st[4 * b + 2] = pivot;   // (latched: later factorisations of the frozen tangent do not count)
+    }
+    if (!ok) return;
+    const int ndof_max = 3 * nJ_max, ndof = 3 * min(max(nJ[b], 0), nJ_max);
+    const int n = min(max(n_free[b], 0), ld_uf);
+    const int* fi = free_index + (size_t)b * ndof_max;
+    for (int d = tid; d < ndof; d += 256) {
+        const int r = fi[d];
+        if (r < 0 || r >= n) continue;
+        double* u = U + (size_t)b * ndof_max + d;
+        const double du = uf[(size_t)b * ld_uf + r];
+        *u = *u == 0.0 ? du : *u + du;   // (0 + du is du, bits and all: the first iterate is the substitution's output)
+    }
+}
+
+int nl_state_launch(int B, int nJ_max, int nM_max, const double* xyz, const TrsMembers& mem, const double* loads,
+                    const int* free_index, const int* n_free, const int* nJ, const int* nM, int ld_f, double lambda,
+                    double tol, int it, int last, int step, int S, const double* U, int* st, double* Xc, double* R,
+                    double* W, int* active, double* u, double* N, double* f_ext, int* iters, int* status,
+                    double* residual, const int* joint_out, hipStream_t stream) {
+    if (B < 0 || nJ_max <= 0 || nM_max < 0 || ld_f < 0 || it < 0 || last < 0 || last > 2 || S < 1 || step < 0 || step >= S)
+        return (int)hipErrorInvalidValue;
+    if (!(tol >= 0.0) || !U || !st || !Xc || !R || !W || !active) return (int)hipErrorInvalidValue;
+    if (last && (!u || !N || !f_ext || !iters || !status || !residual)) return (int)hipErrorInvalidValue;
+    if (B == 0) return 0;
+    if (!trs_nl_fits(nJ_max, nM_max)) return (int)hipErrorInvalidValue;
+    static const int lds_limit_set = (int)hipFuncSetAttribute(   // once per process, not per launch
+        reinterpret_cast<const void*>(trs_nl_state_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)lds_limit_set;
+    hipLaunchKernelGGL(trs_nl_state_kernel, dim3(B), dim3(256), state_lds(nJ_max, nM_max), stream, xyz, mem, loads,
+                       free_index, n_free, nJ, nM, nJ_max, nM_max, ld_f, lambda, tol, it, last, step, S, U, st, Xc, R, W,
+                       active, u, N, f_ext, iters, status, residual, joint_out);
+    return (int)hipGetLastError();
+}
+
+int nl_tangent_launch(int B, int nJ_max, int nM_max, const TrsMembers& mem, const int* free_index, const int* n_free,
+                      const int* nJ, const int* nM, int ld, int slab_rows, double* S, const int* env, int flags,
+                      const double* W, hipStream_t stream) {
+    if (B < 0 || nJ_max <= 0 || nM_max < 0 || slab_rows <= 0 || slab_rows % TRS_NB != 0 || ld < slab_rows || !S || !W)
+        return (int)hipErrorInvalidValue;
+    if ((flags & TRS_ASM_COMPACT) != 0) return (int)hipErrorInvalidValue;   // (no slab to amend)
+    if (B == 0) return 0;
+    const size_t lds = tangent_lds(nJ_max, nM_max, slab_rows);
+    if (lds > NL_LDS_BUDGET) return (int)hipErrorInvalidValue;
+    static const int lds_limit_set = (int)hipFuncSetAttribute(
+        reinterpret_cast<const void*>(trs_nl_tangent_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)lds_limit_set;
+    hipLaunchKernelGGL(trs_nl_tangent_kernel, dim3(B), dim3(256), lds, stream, mem, free_index, n_free, nJ, nM, nJ_max,
+                       nM_max, ld, slab_rows, S, env, (flags & TRS_ASM_FULL_SYMMETRIC) != 0 ? 1 : 0, W);
+    return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+int trs_nl_abi_version(void) { return TRS_NL_ABI_VERSION; }
+
+int trs_nl_fits(int nJ_max, int nM_max) {
+    if (nJ_max < 0 || nM_max < 0 || nJ_max > 65535) return 0;
+    return state_lds(nJ_max, nM_max) <= NL_LDS_BUDGET &&
+           tangent_lds(nJ_max, nM_max, trs_round_up(3 * nJ_max < 1 ? 1 : 3 * nJ_max, TRS_NB)) <= NL_LDS_BUDGET;
+}
+
+int trs_nl_state(int B, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* E, const double* A,
+                 const double* loads, const int32_t* free_index, const int32_t* n_free, const int32_t* nJ,
+                 const int32_t* nM, int ld_f, double lambda, double tol, int it, int last, int step, int S,
+                 const double* U, int32_t* st, double* Xc, double* R, double* W, int32_t* active, double* u, double* N,
+                 double* f_ext, int32_t* iters, int32_t* status, double* residual, const int32_t* joint_out,
+                 void* stream) {
+    return nl_state_launch(B, nJ_max, nM_max, xyz, trs_members_general(conn, E, A), loads, free_index, n_free, nJ, nM,
+                           ld_f, lambda, tol, it, last, step, S, U, st, Xc, R, W, active, u, N, f_ext, iters, status,
+                           residual, joint_out, (hipStream_t)stream);
+}
+
+int trs_nl_state_tab(int B, int nJ_max, int nM_max, const double* xyz, const uint16_t* conn16, const uint8_t* type_idx,
+                     const double* types, const double* loads, const int32_t* free_index, const int32_t* n_free,
+                     const int32_t* nJ, const int32_t* nM, int ld_f, double lambda, double tol, int it, int last,
+                     int step, int S, const double* U, int32_t* st, double* Xc, double* R, double* W, int32_t* active,
+                     double* u, double* N, double* f_ext, int32_t* iters, int32_t* status, double* residual,
+                     const int32_t* joint_out, void* stream) {
+    if (B > 0 && (!conn16 || !type_idx || !types)) return (int)hipErrorInvalidValue;
+    return nl_state_launch(B, nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), loads, free_index, n_free,
+                           nJ, nM, ld_f, lambda, tol, it, last, step, S, U, st, Xc, R, W, active, u, N, f_ext, iters,
+                           status, residual, joint_out, (hipStream_t)stream);
+}
+
+int trs_nl_tangent(int B, int nJ_max, int nM_max, const int32_t* conn, const double* E, const double* A,
+                   const int32_t* free_index, const int32_t* n_free, const int32_t* nJ, const int32_t* nM, int ld,
+                   int slab_rows, double* S, const int32_t* env, int flags, const double* W, void* stream) {
+    return nl_tangent_launch(B, nJ_max, nM_max, trs_members_general(conn, E, A), free_index, n_free, nJ, nM, ld,
+                             slab_rows, S, env, flags, W, (hipStream_t)stream);
+}
+
+int trs_nl_tangent_tab(int B, int nJ_max, int nM_max, const uint16_t* conn16, const uint8_t* type_idx,
+                       const double* types, const int32_t* free_index, const int32_t* n_free, const int32_t* nJ,
+                       const int32_t* nM, int ld, int slab_rows, double* S, const int32_t* env, int flags,
+                       const double* W, void* stream) {
+    if (B > 0 && (!conn16 || !type_idx || !types)) return (int)hipErrorInvalidValue;
+    return nl_tangent_launch(B, nJ_max, nM_max, trs_members_table(conn16, type_idx, types), free_index, n_free, nJ, nM,
+                             ld, slab_rows, S, env, flags, W, (hipStream_t)stream);
+}
+
+int trs_nl_update(int B, int nJ_max, const int32_t* free_index, const int32_t* n_free, const int32_t* nJ,
+                  const double* uf, int ld_uf, const int32_t* info, int it, double* U, int32_t* st, void* stream) {
+    if (B < 0 || nJ_max <= 0 || ld_uf < 0 || it < 1 || !uf || !info || !U || !st) return (int)hipErrorInvalidValue;
+    if (B == 0) return 0;
+    hipLaunchKernelGGL(trs_nl_update_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, nJ_max, free_index, n_free, nJ,
+                       uf, ld_uf, info, it, U, st);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

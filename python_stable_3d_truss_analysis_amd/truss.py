@@ -494,6 +494,26 @@ class Truss:
                 "historyDisplace": result.history_displace[0, ..., :dim].copy(),
                 "historyForce": result.history_force[0].copy()}
 
+    def SolveNonlinear(self, load_factors=(1.0,), tol=1e-9, maxIters=25):
+        """Geometrically nonlinear statics of this truss (large displacements, small strains) under `load_factors`
+        times its own forces, one load step per factor in the given order, each started from the previous step's
+        displacements: Newton's method on the tangent stiffness (`batch.solve_nonlinear`).  Returns a dict of numpy
+        arrays, S the number of load steps:
+          "displace" [S, nJ, dim], "internal" [S, nM] (member forces, tension positive), "external" [S, nJ, dim] (the
+          applied force at free DOFs, the reaction at held ones), "iterations", "status" [S] (0 converged, 1 iteration
+          limit, 2 tangent not positive definite - the truss has passed a limit point; "displace" is then the last
+          accepted iterate -, 3 not attempted because an earlier step failed) and "residual" [S].
+        The truss's loads, its solved state and its linear results stay as they are.  Raises ValueError for bad
+        arguments (as `batch.solve_nonlinear`) and `TrussNotStableError` when the counting test fails."""
+        if not self.isStable:
+            raise TrussNotStableError("The truss is not stable !")
+        from .batch import pack_trusses, solve_nonlinear  # late import: keeps the model importable without torch
+        nJ, nM, dim = len(self._pos), len(self._bars), self._dim
+        result = solve_nonlinear(pack_trusses([self]), load_factors, tol=tol, max_iters=maxIters)
+        return {"displace": result.displace[0, :, :nJ, :dim].copy(), "internal": result.internal[0, :, :nM].copy(),
+                "external": result.external[0, :, :nJ, :dim].copy(), "iterations": result.iterations[0].copy(),
+                "status": result.status[0].copy(), "residual": result.residual[0].copy()}
+
     def MemberLoss(self, cases=None, rTol=None, returnForces=False):
         """What the loss of any ONE member does to this truss, for every member and every load case, from ONE
         factorisation (`batch.solve_member_loss`): `cases` is a list of `{jointID: vector}` dicts as `SolveLoadCases`
