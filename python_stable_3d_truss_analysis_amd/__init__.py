@@ -40,7 +40,7 @@ __all__ = ["Truss", "Member", "MemberType", "SupportType", "MetapathType", "Task
            "solve_modes", "ModeResult", "solve_effect_cases", "EffectCaseResult", "LoadCase",
            "solve_member_loss", "MemberLossResult", "solve_influence", "InfluenceResult",
            "solve_member_sets", "MemberSetResult", "solve_transient", "TransientResult",
-           "solve_nonlinear", "NonlinearResult"]
+           "solve_nonlinear", "NonlinearResult", "solve_buckling", "BucklingResult"]
 
 
 def __getattr__(name):
@@ -49,7 +49,7 @@ def __getattr__(name):
                 "solve_load_cases", "LoadCaseResult", "solve_gradients", "GradientResult", "solve_modes", "ModeResult",
                 "solve_effect_cases", "EffectCaseResult", "solve_member_loss", "MemberLossResult", "solve_influence",
                 "InfluenceResult", "solve_member_sets", "MemberSetResult", "solve_transient", "TransientResult",
-                "solve_nonlinear", "NonlinearResult"):
+                "solve_nonlinear", "NonlinearResult", "solve_buckling", "BucklingResult"):
         from . import batch
         return getattr(batch, name)
     if name == "DifferentiableTruss":

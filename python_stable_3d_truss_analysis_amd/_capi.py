@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h`, `include/trs_influence.h`, `include/trs_sets.h`, `include/trs_dynamics.h` and `include/trs_nonlinear.h` (library: `libtrs_hip.so`, in-tree).
+"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h`, `include/trs_influence.h`, `include/trs_sets.h`, `include/trs_dynamics.h`, `include/trs_nonlinear.h` and `include/trs_buckling.h` (library: `libtrs_hip.so`, in-tree).
 
 There is no fallback: if the library is missing, `load()` raises `HipExtensionError`.
 """
@@ -164,6 +164,18 @@ NL_SIGNATURES = {
     "trs_nl_update": (_I, [_I, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P]),
 }
 
+#: every symbol `include/trs_buckling.h` declares (linear buckling: critical load factors from shifted factors of
+#: K + theta Kg; csrc/buckling.hip, the same library)
+BK_SIGNATURES = {
+    "trs_bk_abi_version": (_I, []),
+    "trs_bk_fits": (_I, [_I, _I]),
+    "trs_bk_members": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "trs_bk_members_tab": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "trs_bk_product": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "trs_bk_step": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _D, _P]),
+    "trs_bk_shapes": (_I, [_I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+}
+
 #: must equal TRS_ABI_VERSION of include/trs_solver.h
 ABI_VERSION = 10
 #: must equal TRS_MODES_ABI_VERSION of include/trs_modes.h
@@ -180,6 +192,8 @@ SETS_ABI_VERSION = 1
 DYN_ABI_VERSION = 1
 #: must equal TRS_NL_ABI_VERSION of include/trs_nonlinear.h
 NL_ABI_VERSION = 1
+#: must equal TRS_BK_ABI_VERSION of include/trs_buckling.h
+BK_ABI_VERSION = 1
 #: TRS_NL_* of include/trs_nonlinear.h: the status of a truss in a load step of the nonlinear analysis
 NL_ACTIVE, NL_CONVERGED, NL_ITER_LIMIT, NL_NOT_PD, NL_NOT_ATTEMPTED = -1, 0, 1, 2, 3
 #: TRS_SETS_MAX of include/trs_sets.h: members per scenario at most
@@ -230,7 +244,7 @@ def load():
     except OSError as exc:
         raise HipExtensionError(f"cannot load {LIB_PATH}: {exc}") from exc
     for table in (SIGNATURES, MODES_SIGNATURES, EFFECTS_SIGNATURES, LOSS_SIGNATURES, INFLUENCE_SIGNATURES,
-                  SETS_SIGNATURES, DYN_SIGNATURES, NL_SIGNATURES):
+                  SETS_SIGNATURES, DYN_SIGNATURES, NL_SIGNATURES, BK_SIGNATURES):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype = restype
@@ -239,7 +253,7 @@ def load():
             or lib.trs_effects_abi_version() != EFFECTS_ABI_VERSION or lib.trs_loss_abi_version() != LOSS_ABI_VERSION \
             or lib.trs_influence_abi_version() != INFLUENCE_ABI_VERSION \
             or lib.trs_sets_abi_version() != SETS_ABI_VERSION or lib.trs_dyn_abi_version() != DYN_ABI_VERSION \
-            or lib.trs_nl_abi_version() != NL_ABI_VERSION:
+            or lib.trs_nl_abi_version() != NL_ABI_VERSION or lib.trs_bk_abi_version() != BK_ABI_VERSION:
         raise HipExtensionError("libtrs_hip.so ABI version mismatch")
     _lib = lib
     return lib

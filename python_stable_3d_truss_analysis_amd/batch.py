@@ -624,6 +624,12 @@ def _check_mass_args(who, B, nJ_max, joint_mass_shape, mass_scale, joint_mass_mi
         raise ValueError(str(exc).replace("modes:", who + ":", 1)) from None
 
 
+#: `status` of `DeviceBatch.buckling` / `solve_buckling`: the critical factor was found; the truss has no positive factor;
+#: `max_shifts` rounds ended with negative factors only; the last round did not converge within `max_iters`; the
+#: factorisation of K + theta Kg failed
+BK_FOUND, BK_NONE, BK_SHIFT_LIMIT, BK_ITER_LIMIT, BK_NOT_PD = 0, 1, 2, 3, 4
+
+
 def _ptr(x):
     """The device address of an optional tensor argument of a C call."""
     return None if x is None else x.data_ptr()
@@ -1721,6 +1727,146 @@ class DeviceBatch:
             self.B, self.nJ_max, self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(),
             self.uf.data_ptr(), self.rows, self.info.data_ptr(), it, ws["U"].data_ptr(), ws["st"].data_ptr(),
             self._stream()), "trs_nl_update")
+
+    # -- linear buckling: critical load factors from shifted factors of K + theta Kg (include/trs_buckling.h) ------------
+    def buckling(self, p, shift=0.0, max_shifts=6, tol=1e-10, max_iters=256, check_every=4, out=None):
+        """Linear buckling of the resident batch under its own loads (`factor()` first; include/trs_buckling.h): the
+        load factors lambda of K_ff phi = lambda H phi, H = -Kg the geometric stiffness of the linear member forces, and
+        per truss the smallest positive one.  The linear solution comes from one substitution against the resident
+        factor, `trs_bk_members` makes the member tables.  A round at the per-truss shift theta (round 0: `shift`) is
+        `assemble` -> `trs_nl_tangent` with W(theta) -> `potrf` (the slab then holds a factor of K + theta Kg; round 0 at
+        shift 0 takes the resident factor as it is) and the block iteration: per iteration `trs_potrs_cases` on 16
+        vectors, `trs_bk_product`, `trs_bk_step`; every `check_every` iterations the residuals are formed, the trusses
+        whose n_modes = min(p, rank) pairs nearest theta are below `tol` freeze, and one small read-back decides whether
+        to go on, up to `max_iters`.  After a round a truss is done with its critical factor if its pairs hold a positive
+        lambda, done without one if rank < p (the whole spectrum has been seen); otherwise all p pairs are negative, no
+        eigenvalue lies within d = max |lambda_i - theta| of theta, and the next round runs at theta + d, `max_shifts`
+        rounds at most.  The rounds' outputs are merged per truss on the device; one read-back per round.
+        Returns a dict of device tensors: factor [B, p] (signed, nearest the final shift first, NaN beyond n_modes),
+        critical [B] (NaN: none found), critical_mode [B] (int32, -1: none), bound [B] (every positive factor is >= bound;
+        +inf: there is none; the critical factor where one was found), shift [B] (of the truss's last round), rounds [B],
+        iters [B] (the iteration at which the last round converged, 0: it did not), residual [B, p], n_modes [B],
+        shape [B, p, nJ_max, 3] (caller's numbering, largest component +1), status [B] (BK_FOUND 0, BK_NONE 1 no positive
+        factor exists, BK_SHIFT_LIMIT 2, BK_ITER_LIMIT 3 the last round did not converge, BK_NOT_PD 4 the factorisation
+        of K + theta Kg failed: the outputs of the previous round are kept) and info [B] (what the last factorisation of
+        the truss reported; also left in `self.info`).  `max_shifts=1` with a caller's `shift` is the plain signed
+        analysis at that shift.  Afterwards the batch is WITHOUT a static factor (the slab may hold a factor of
+        K + theta Kg): the static analyses refuse with their "no factor" error until `factor()`; `generation` is bumped
+        and the buffer of `solve_cases`' right-hand sides is reused, as `modes` does.  The compact member form of the
+        assembly (`options["compact"]`) has no slab to amend and is refused, as is a batch on the fused small path."""
+        t = self.torch
+        if self.small:
+            raise ValueError("buckling(): this batch takes the fused small-system kernel, which keeps no factor - "
+                             "build the DeviceBatch with use_small=False")
+        if self.options["compact"]:
+            raise ValueError("buckling(): options['compact'] leaves no slab that could be amended to K + theta Kg")
+        _check_buckling_args(p, shift, max_shifts, tol, max_iters, check_every)
+        self._need_factor("buckling")
+        p, shift = int(p), float(shift)
+        B, Q, dev = self.B, MODES_BLOCK, self.device
+        sizes = {"P": p, "nJ": self.nJ_max}
+        shapes = {key: ([B] + [sizes.get(n, n) for n in shape], getattr(t, dtype))
+                  for key, fill, dtype, shape in BucklingResult.FIELDS.values()}
+        shapes["info"] = ([B], t.int32)
+        out = self._out_tensors("buckling", shapes, out)
+        if B == 0:
+            return out
+        if not self.lib.trs_bk_fits(self.nJ_max, self.nM_max) or not self.lib.trs_nl_fits(self.nJ_max, self.nM_max):
+            raise HipExtensionError(f"buckling(): a truss of {self.nJ_max} joints / {self.nM_max} members exceeds the LDS "
+                                    "of the product or the amend kernel (trs_bk_fits, trs_nl_fits)")
+        F = self.cases_F = self._case_block("cases_F", Q)   # the block's right-hand sides / solutions
+        self._bump_generation()
+        self._factored = False
+        self._forward = None
+        f64 = lambda *shape, fill=0.0: t.full(list(shape), fill, dtype=t.float64, device=dev)
+        i32 = lambda *shape, fill=0: t.full(list(shape), fill, dtype=t.int32, device=dev)
+        nM = max(self.nM_max, 1)
+        nan, inf = float("nan"), float("inf")
+        # (kept on the batch as `modes` keeps its own: tools/buckling_speed.py times the launches on it one by one)
+        ws = self._bk_ws = {
+              "X": f64(B, Q, self.rows), "G": f64(B, Q, self.rows), "Fk": f64(B, Q, self.rows), "lam": f64(B, Q, fill=nan),
+              "resid": f64(B, Q, fill=nan), "rank": i32(B), "state": i32(B), "theta": f64(B, fill=shift),
+              "u0": f64(B, 1, self.rows), "N": f64(B, nM), "ends": i32(B, nM, 2), "Mt": f64(B, nM, 4), "W": f64(B, nM, 6)}
+        for key, fill, dtype, shape in BucklingResult.FIELDS.values():
+            out[key].fill_(fill)
+        out["shift"].fill_(shift)
+        jo, stream, tab = self._case_launch()
+        theta, state, rank = ws["theta"], ws["state"], ws["rank"]
+
+        def step(first, check, it):
+            _capi.check(self.lib.trs_bk_step(
+                B, p, self.n_free.data_ptr(), theta.data_ptr(), F.data_ptr(), ws["G"].data_ptr(), ws["Fk"].data_ptr(),
+                ws["X"].data_ptr(), self.rows, ws["lam"].data_ptr(), ws["resid"].data_ptr(), rank.data_ptr(),
+                state.data_ptr(), first, check, it, float(tol), stream), "trs_bk_step")
+
+        with t.cuda.device(dev):
+            # the linear solution under the batch's own loads (already in the batch's joint order: no joint_in)
+            _capi.check(self.lib.trs_gather_cases(B, 1, self.nJ_max, self.loads.data_ptr(), self.free_index.data_ptr(),
+                                                  self.n_free.data_ptr(), self.nJ.data_ptr(), None, ws["u0"].data_ptr(),
+                                                  self.rows, stream), "trs_gather_cases")
+            self._potrs_cases(ws["u0"], 1)
+            active = t.ones([B], dtype=t.bool, device=dev)
+            col = t.arange(p, device=dev)[None, :]
+            for rnd in range(int(max_shifts)):
+                _capi.check(getattr(self.lib, "trs_bk_members" + tab)(
+                    B, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *self._members(), self.free_index.data_ptr(),
+                    self.n_free.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), ws["u0"].data_ptr(), self.rows,
+                    theta.data_ptr(), ws["N"].data_ptr(), ws["ends"].data_ptr(), ws["Mt"].data_ptr(), ws["W"].data_ptr(),
+                    stream), "trs_bk_members" + tab)
+                if rnd > 0 or shift != 0.0:   # (round 0 at shift 0: the resident factor, no amend)
+                    self.assemble()
+                    self._nl_tangent(ws)
+                    self.potrf()
+                info = self.info.clone()
+                took = active & (info == 0)
+                state.copy_(t.where(took, 0, -1))
+                step(1, 0, 0)
+                for it in range(1, int(max_iters) + 1):
+                    check = it % check_every == 0 or it == max_iters
+                    self._potrs_cases(F, Q)
+                    _capi.check(self.lib.trs_bk_product(
+                        B, self.nJ_max, self.nM_max, ws["ends"].data_ptr(), ws["Mt"].data_ptr(),
+                        self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(),
+                        F.data_ptr(), ws["G"].data_ptr(), self.rows, stream), "trs_bk_product")
+                    step(0, int(check), it)
+                    if check and not bool((state == 0).any().item()):   # the one read-back per check point
+                        break
+                # the round's verdict per truss, merged into the outputs on the device
+                conv = took & (state > 0)
+                n_modes = rank.clamp(max=p)
+                lam = ws["lam"][:, :p]
+                valid = col < n_modes[:, None]
+                pos = valid & (lam > 0) & conv[:, None]
+                found = pos.any(1)
+                crit, mode = t.where(pos, lam, inf).min(1)
+                none = conv & ~found & (n_modes < p)
+                negative = conv & ~found & ~none
+                reach = t.where(valid, (lam - theta[:, None]).abs(), 0.0).max(1).values
+                status = t.where(found, BK_FOUND, t.where(none, BK_NONE, t.where(negative, BK_SHIFT_LIMIT, BK_ITER_LIMIT)))
+                status = t.where(took, status, BK_NOT_PD).to(t.int32)
+                bound = t.where(found, crit, t.where(none, inf, t.where(negative, theta + reach, theta)))
+                out["status"].copy_(t.where(active, status, out["status"]))
+                out["rounds"].add_(active.to(t.int32))
+                out["info"].copy_(t.where(active, info, out["info"]))
+                out["shift"].copy_(t.where(took, theta, out["shift"]))
+                out["bound"].copy_(t.where(took, bound, out["bound"]))
+                out["critical"].copy_(t.where(found, crit, out["critical"]))
+                out["critical_mode"].copy_(t.where(found, mode.to(t.int32), out["critical_mode"]))
+                out["iters"].copy_(t.where(took, state.clamp(min=0), out["iters"]))
+                active = negative
+                theta.copy_(t.where(negative, theta + reach, theta))
+                if rnd + 1 == max_shifts or not bool(active.any().item()):   # the one read-back per round
+                    break
+            _capi.check(self.lib.trs_bk_shapes(B, p, self.nJ_max, ws["X"].data_ptr(), self.rows,
+                                               self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(),
+                                               rank.data_ptr(), jo, out["shape"].data_ptr(), stream), "trs_bk_shapes")
+            n_modes = rank.clamp(max=p)
+            valid = col < n_modes[:, None]
+            out["factor"].copy_(t.where(valid, ws["lam"][:, :p], nan))
+            out["residual"].copy_(t.where(valid, ws["resid"][:, :p], nan))
+            out["n_modes"].copy_(n_modes)
+            self.info.copy_(out["info"])
+        return out
 
     def fitness(self, allow_stress, allow_displace, out=None):
         """(weight, stress_violation, displacement_violation) per truss, on device."""
@@ -3579,6 +3725,75 @@ def solve_nonlinear(trusses_or_packed, load_factors=(1.0,), tol=1e-9, max_iters=
     for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope,
                                       factor=lambda db, part: None):
         _put_result(part, out, db.nonlinear(lams, tol=tol, max_iters=max_iters, check_every=check_every))
+    return _finish_result(torch, dev, out, on_device)
+
+
+@dataclass
+class BucklingResult:
+    """Results of `solve_buckling`: factor [B, p] (the load factors lambda of K phi = lambda H phi nearest the truss's
+    final shift, nearest first, signed: a positive one scales the loads as applied, a negative one the reversed loads;
+    NaN beyond n_modes), critical [B] (the smallest positive factor; NaN where none was found), critical_mode [B] (its
+    place in `factor`, -1: none), bound [B] (every positive factor is >= bound: the critical factor where one was found,
+    +inf where the truss has none, else the last proven value), shift, rounds [B] (the truss's last shift and how many
+    rounds it took part in), iters [B] (the iteration at which its last round converged, 0: it did not), residual [B, p]
+    (|H phi - nu Kbar phi|_2 / |nu Kbar phi|_2), n_modes [B], shape [B, p, nJ_max, 3] (caller's joint numbering, largest
+    component +1, zero at held DOFs and beyond n_modes), status [B] (`BK_FOUND` 0, `BK_NONE` 1, `BK_SHIFT_LIMIT` 2,
+    `BK_ITER_LIMIT` 3, `BK_NOT_PD` 4) and info [B] (the status of the truss's last factorisation: for info != 0 in round 0
+    the truss has NaN factors, the others are unaffected)."""
+    factor: np.ndarray
+    critical: np.ndarray
+    critical_mode: np.ndarray
+    bound: np.ndarray
+    shift: np.ndarray
+    rounds: np.ndarray
+    iters: np.ndarray
+    residual: np.ndarray
+    n_modes: np.ndarray
+    shape: np.ndarray
+    status: np.ndarray
+    info: np.ndarray
+
+    FIELDS = {"factor": ("factor", float("nan"), "float64", ("P",)), "critical": ("critical", float("nan"), "float64", ()),
+              "critical_mode": ("critical_mode", -1, "int32", ()), "bound": ("bound", 0.0, "float64", ()),
+              "shift": ("shift", 0.0, "float64", ()), "rounds": ("rounds", 0, "int32", ()), "iters": ("iters", 0, "int32", ()),
+              "residual": ("residual", float("nan"), "float64", ("P",)), "n_modes": ("n_modes", 0, "int32", ()),
+              "shape": ("shape", 0.0, "float64", ("P", "nJ", 3)), "status": ("status", BK_SHIFT_LIMIT, "int32", ())}
+
+
+def _check_buckling_args(p, shift=0.0, max_shifts=6, tol=1e-10, max_iters=256, check_every=4, options=None):
+    """The argument errors of `solve_buckling` / `DeviceBatch.buckling` that need no device (ValueError)."""
+    who = "buckling"
+    if isinstance(p, bool) or not isinstance(p, (int, np.integer)) or not 1 <= int(p) <= 8:
+        raise ValueError(f"{who}: p must be an integer in 1 .. 8 (one block of {MODES_BLOCK} vectors delivers at most 8 "
+                         f"pairs), got {p!r}")
+    if isinstance(shift, bool) or not isinstance(shift, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(shift) or shift < 0:
+        raise ValueError(f"{who}: shift must be a finite number >= 0, got {shift!r}")
+    if isinstance(tol, bool) or not isinstance(tol, (int, float, np.floating)) or not np.isfinite(tol) or not tol > 0:
+        raise ValueError(f"{who}: tol must be a finite positive number, got {tol!r}")
+    for name, x in (("max_shifts", max_shifts), ("max_iters", max_iters), ("check_every", check_every)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 1:
+            raise ValueError(f"{who}: {name} must be an integer of at least 1, got {x!r}")
+    if options and options.get("compact"):
+        raise ValueError(f"{who}: options['compact'] leaves no slab that could be amended to K + theta Kg")
+
+
+def solve_buckling(trusses_or_packed, p=4, shift=0.0, max_shifts=6, tol=1e-10, max_iters=256, check_every=4, device=None,
+                   reorder=False, options=None, max_slab_bytes=64 << 30, on_device=False, use_envelope=True):
+    """Linear buckling of every truss of a batch under its own loads: by what factor can the load grow before the truss
+    buckles?  Per truss the `p` (1 .. 8) load factors nearest its final shift, signed, and `critical`, the smallest
+    positive one, found by block inverse iteration on factors of K + theta Kg with a sequence of provably safe shifts
+    (`DeviceBatch.buckling`, include/trs_buckling.h).  `shift`, `max_shifts`: the first shift and the number of rounds at
+    most (`max_shifts=1`: the plain signed analysis at `shift`).  Buckles of single members (Euler) are not part of it.
+    Buckets, member forms, `reorder` plans, `options`, `on_device` and `use_envelope` as `solve_load_cases`.  Bad
+    arguments raise ValueError before any device work.  Returns a `BucklingResult`."""
+    packed = _as_packed(trusses_or_packed)
+    _check_buckling_args(p, shift, max_shifts, tol, max_iters, check_every, options)
+    torch, dev = _require_gpu(device)
+    out = _new_result(torch, dev, BucklingResult, packed.B, {"P": int(p), "nJ": packed.nJ_max})
+    for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope):
+        _put_result(part, out, db.buckling(p, shift=shift, max_shifts=max_shifts, tol=tol, max_iters=max_iters,
+                                           check_every=check_every))
     return _finish_result(torch, dev, out, on_device)
 
 

@@ -136,4 +136,35 @@ __device__ __forceinline__ void build_end_lists(const EndLists& t, const TrsMemb
     }
 }
 
+// The far joint of every list entry into `far` (-1: outside the truss), and every list re-sorted by (far joint, member id) -
+// the order of trs_assemble's adjacency lists, so that a sum over a list rounds as the assembly's own sums do: parallel
+// members lie side by side, and a member listed twice gives the bits of one member of twice the area wherever the linear
+// solve does.  What the nonlinear kernels (nonlinear.hip) and the buckling product (buckling.hip) sum over.
+// The sort is stable and the lists arrive in member-id order.  Thread j % 256 owns joint j here as in build_end_lists'
+// own sort, so no barrier is needed between the two; the caller places one before another thread reads a list.
+__device__ __forceinline__ void order_by_neighbour(const EndLists& t, int* far_all, const TrsMembers& mem, const size_t mbase,
+                                                   const int joints, const int tid) {
+    for (int j = tid; j < joints; j += 256) {
+        int* list = t.ends + t.start[j];
+        int* far = far_all + t.start[j];
+        const int deg = t.cnt[j];
+        for (int i = 0; i < deg; ++i) {
+            const int2 c = mem.ends(mbase + (list[i] >> 1));
+            const int o = (list[i] & 1) ? c.x : c.y;
+            far[i] = ((o >= 0) & (o < joints)) ? o : -1;
+        }
+        for (int i = 1; i < deg; ++i) {
+            const int kf = far[i], ke = list[i];
+            int p = i - 1;
+            while (p >= 0 && far[p] > kf) {
+                far[p + 1] = far[p];
+                list[p + 1] = list[p];
+                --p;
+            }
+            far[p + 1] = kf;
+            list[p + 1] = ke;
+        }
+    }
+}
+
 }  // namespace trs_rec

@@ -445,6 +445,30 @@ class Truss:
         shapes = [dict(zip(range(nJ), result.shape[0, k, :nJ, :dim].copy())) for k in range(count)]
         return omega, shapes
 
+    def BucklingFactors(self, nModes=4, returnShapes=False, maxShifts=6):
+        """By what factor can this truss's loads grow before it buckles (linear buckling, `batch.solve_buckling`)?
+        Returns `(critical, factors)`: `critical` the smallest positive load factor (NaN when none was found within
+        `maxShifts` shift rounds, or when the truss has none - under pure tension, or without loads) and `factors` the
+        up to `nModes` (1 .. 8) signed factors nearest the last shift, nearest first (a negative factor means buckling
+        under the reversed loads).  `returnShapes=True`: also a list of `{jointID: vector}` dicts, one per factor
+        (largest component +1).  Buckling of single members between their joints (Euler) is not part of it.  The
+        truss's loads, its solved state and its results stay as they are.  Raises `TrussNotStableError` when the
+        counting test fails and `numpy.linalg.LinAlgError` when the reduced stiffness matrix is not positive definite,
+        as `Solve()` does."""
+        if not self.isStable:
+            raise TrussNotStableError("The truss is not stable !")
+        from .batch import pack_trusses, solve_buckling  # late import: keeps the model importable without torch
+        result = solve_buckling(pack_trusses([self]), p=nModes, max_shifts=maxShifts)
+        if int(result.info[0]) != 0:
+            raise np.linalg.LinAlgError("Singular matrix")
+        count = int(result.n_modes[0])
+        critical, factors = float(result.critical[0]), result.factor[0, :count].copy()
+        if not returnShapes:
+            return critical, factors
+        nJ, dim = len(self._pos), self._dim
+        shapes = [dict(zip(range(nJ), result.shape[0, k, :nJ, :dim].copy())) for k in range(count)]
+        return critical, factors, shapes
+
     def TransientResponse(self, dt, steps, cases=None, scale=None, groundAcceleration=None, beta=0.25, gamma=0.5,
                           dampMass=0.0, dampStiff=0.0, jointMasses=None, massScale=1.0, monitorJoints=(),
                           monitorMembers=()):
