@@ -1429,7 +1429,6 @@ class DeviceBatch:
             ws = self._modes_ws = {"X": f64(self.B, Q, self.rows), "Mf": f64(self.B, self.rows), "lam": f64(self.B, Q),
                                    "resid": f64(self.B, Q), "n_mass": i32(self.B), "state": i32(self.B)}
         jo, stream, tab = self._case_launch()
-        members = self._members() if self.table else (self.conn.data_ptr(), self.A.data_ptr(), self.rho.data_ptr())
 
         def step(first, check, it):
             _capi.check(self.lib.trs_modes_step(
@@ -1438,18 +1437,8 @@ class DeviceBatch:
                 first, check, it, float(tol), stream), "trs_modes_step")
 
         with t.cuda.device(self.device):
-            _capi.check(getattr(self.lib, f"trs_modes{tab}_mass")(
-                self.B, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *members, _ptr(joint_mass), jo,
-                float(mass_scale), self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(),
-                self.nM.data_ptr(), ws["Mf"].data_ptr(), self.rows, ws["n_mass"].data_ptr(), stream),
-                f"trs_modes{tab}_mass")
-            step(1, 0, 0)
-            for it in range(1, max_iters + 1):
-                check = it % check_every == 0 or it == max_iters
-                self._potrs_cases(F, Q)
-                step(0, int(check), it)
-                if check and not bool((ws["state"] == 0).any().item()):   # the one read-back per check point
-                    break
+            self._lumped_mass(joint_mass, mass_scale, into=(ws["Mf"], ws["n_mass"]))
+            self._block_iteration(F, step, ws["state"], max_iters, check_every)
             _capi.check(self.lib.trs_modes_shapes(self.B, p, self.nJ_max, ws["X"].data_ptr(), self.rows,
                                                   self.free_index.data_ptr(), self.nJ.data_ptr(), jo,
                                                   out["phi"].data_ptr(), stream), "trs_modes_shapes")
@@ -1501,12 +1490,26 @@ class DeviceBatch:
         self._forward = None
         self._dynamic = dict(const, Mf=Mf, n_mass=n_mass, generation=self.generation)
 
-    def _lumped_mass(self, joint_mass, mass_scale):
+    def _block_iteration(self, F, step, state, max_iters, check_every, between=None):
+        """The loop of `modes` and of a round of `buckling` on the block `F` of 16 vectors: `step(1, 0, 0)` starts it; an
+        iteration is `trs_potrs_cases` on F, `between()` if given, and `step(0, check, it)` with the residuals on every
+        `check_every`-th iteration and on the last, where ONE small read-back (any `state` still 0?) ends the loop."""
+        step(1, 0, 0)
+        for it in range(1, max_iters + 1):
+            check = it % check_every == 0 or it == max_iters
+            self._potrs_cases(F, MODES_BLOCK)
+            if between is not None:
+                between()
+            step(0, int(check), it)
+            if check and not bool((state == 0).any().item()):   # the one read-back per check point
+                break
+
+    def _lumped_mass(self, joint_mass, mass_scale, into=None):
         """(Mf [B, rows], n_mass [B]) of `trs_modes_mass` for the resident batch (`dofmap()` first): the lumped mass of
-        every free DOF in the reduced numbering, zero on the padding."""
+        every free DOF in the reduced numbering, zero on the padding.  `into`: (Mf, n_mass) to fill, not new ones."""
         t = self.torch
-        Mf = t.zeros([self.B, self.rows], dtype=t.float64, device=self.device)
-        n_mass = t.zeros([self.B], dtype=t.int32, device=self.device)
+        Mf, n_mass = into or (t.zeros([self.B, self.rows], dtype=t.float64, device=self.device),
+                              t.zeros([self.B], dtype=t.int32, device=self.device))
         if self.B:
             jo, stream, tab = self._case_launch()
             members = self._members() if self.table else (self.conn.data_ptr(), self.A.data_ptr(), self.rho.data_ptr())
@@ -1799,6 +1802,12 @@ class DeviceBatch:
                 ws["X"].data_ptr(), self.rows, ws["lam"].data_ptr(), ws["resid"].data_ptr(), rank.data_ptr(),
                 state.data_ptr(), first, check, it, float(tol), stream), "trs_bk_step")
 
+        def product():
+            _capi.check(self.lib.trs_bk_product(
+                B, self.nJ_max, self.nM_max, ws["ends"].data_ptr(), ws["Mt"].data_ptr(), self.free_index.data_ptr(),
+                self.n_free.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), F.data_ptr(), ws["G"].data_ptr(),
+                self.rows, stream), "trs_bk_product")
+
         with t.cuda.device(dev):
             # the linear solution under the batch's own loads (already in the batch's joint order: no joint_in)
             _capi.check(self.lib.trs_gather_cases(B, 1, self.nJ_max, self.loads.data_ptr(), self.free_index.data_ptr(),
@@ -1820,17 +1829,7 @@ class DeviceBatch:
                 info = self.info.clone()
                 took = active & (info == 0)
                 state.copy_(t.where(took, 0, -1))
-                step(1, 0, 0)
-                for it in range(1, int(max_iters) + 1):
-                    check = it % check_every == 0 or it == max_iters
-                    self._potrs_cases(F, Q)
-                    _capi.check(self.lib.trs_bk_product(
-                        B, self.nJ_max, self.nM_max, ws["ends"].data_ptr(), ws["Mt"].data_ptr(),
-                        self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(),
-                        F.data_ptr(), ws["G"].data_ptr(), self.rows, stream), "trs_bk_product")
-                    step(0, int(check), it)
-                    if check and not bool((state == 0).any().item()):   # the one read-back per check point
-                        break
+                self._block_iteration(F, step, state, int(max_iters), int(check_every), between=product)
                 # the round's verdict per truss, merged into the outputs on the device
                 conv = took & (state > 0)
                 n_modes = rank.clamp(max=p)
@@ -3479,6 +3478,11 @@ class ModeResult:
     iters: np.ndarray
     info: np.ndarray
 
+    # (`modes` returns no "omega": the field keeps its fill until `solve_modes` takes the root of the eigenvalues)
+    FIELDS = {"eigenvalue": ("lam", float("nan"), "float64", ("P",)), "omega": ("omega", float("nan"), "float64", ("P",)),
+              "shape": ("phi", 0.0, "float64", ("P", "nJ", 3)), "residual": ("resid", float("nan"), "float64", ("P",)),
+              "n_modes": ("n_modes", 0, "int32", ()), "iters": ("iters", 0, "int32", ())}
+
 
 def _check_mode_args(B, nJ_max, p, joint_mass_shape, mass_scale, tol, max_iters, check_every=8, joint_mass_min=None):
     """The argument errors of `solve_modes` / `DeviceBatch.modes` that need no device."""
@@ -3521,16 +3525,12 @@ def solve_modes(trusses_or_packed, p=6, joint_mass=None, mass_scale=1.0, tol=1e-
     p = int(p)
     torch, dev = _require_gpu(device)
     joint_mass = _device_f64(torch, dev, joint_mass)
-    full = lambda shape, value, dtype=torch.float64: torch.full(shape, value, dtype=dtype, device=dev)
-    out = ModeResult(full([B, p], float("nan")), None, full([B, p, nJ_max, 3], 0.0), full([B, p], float("nan")),
-                     full([B], 0, torch.int32), full([B], 0, torch.int32), full([B], 0, torch.int32))
+    out = _new_result(torch, dev, ModeResult, B, {"P": p, "nJ": nJ_max})
     for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope):
-        res = db.modes(p, tol=tol, max_iters=max_iters, joint_mass=part.cut(joint_mass, nJ=1), mass_scale=mass_scale)
-        part.put(out.shape, res["phi"], nJ=2)
-        for field, key in (("eigenvalue", "lam"), ("residual", "resid"), ("n_modes", "n_modes"), ("iters", "iters")):
-            part.put(getattr(out, field), res[key])
+        _put_result(part, out, db.modes(p, tol=tol, max_iters=max_iters, joint_mass=part.cut(joint_mass, nJ=1),
+                                        mass_scale=mass_scale))
     out.omega = out.eigenvalue.sqrt()
-    return out if on_device else _host_result(torch, dev, out)
+    return _finish_result(torch, dev, out, on_device)
 
 
 @dataclass

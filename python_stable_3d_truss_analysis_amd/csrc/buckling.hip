@@ -13,24 +13,23 @@
 // K_ff phi = lambda H phi with H = -Kg; with Kbar = K_ff + theta Kg positive definite the iteration runs on
 // H phi = nu Kbar phi and lambda = theta + 1 / nu.
 //
-// trs_bk_step: ONE WAVE per truss, shaped after trs_modes_step (modes.hip): pass 1 forms the two Gram matrices with the
-// value a lane loaded serving as A element of Y and as B element of G / Fk; the reduced problem lives in the wave's
-// LDS; pass 2 rotates Y, G (and, on a checking step, Fk) by Q^T, each lane reading and writing its own elements only.
+// trs_bk_step: ONE WAVE per truss, shaped after trs_modes_step (modes.hip; what the two share is trs_ritz.h): pass 1
+// forms the two Gram matrices with the value a lane loaded serving as A element of Y and as B element of G / Fk; the
+// reduced problem lives in the wave's LDS; pass 2 rotates Y, G (and, on a checking step, Fk) by Q^T, each lane reading
+// and writing its own elements only.
 #include "../../include/trs_buckling.h"
 #include "trs_common.h"
 #include "trs_recover.h"
+#include "trs_ritz.h"
 
 namespace {
 
 using namespace trs_rec;
+using namespace trs_ritz;
 
+static_assert(QB == TRS_BK_BLOCK, "the block of trs_buckling.h is the one of trs_ritz.h");
 constexpr size_t BK_LDS_BUDGET = 160 * 1024;   // a CU's LDS
-constexpr int QB = TRS_BK_BLOCK;               // vectors per truss
-constexpr int LP = QB + 1;                     // padded leading dimension of the 16 x 16 matrices in LDS
-constexpr int JACOBI_SWEEPS = 30;              // (a sweep without a rotation ends the loop)
 constexpr double BK_DEFLATE = 9.094947017729282e-13;   // 2^-40
-
-__device__ __forceinline__ double bk_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 
 // ---- the reference state --------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void trs_bk_members_kernel(
@@ -161,15 +160,7 @@ __global__ __launch_bounds__(256) void trs_bk_product_kernel(
     }
 }
 
-// ---- the step -------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double start_value(int c, int k) {   // the start block of trs_modes.h
-    unsigned long long z = ((unsigned long long)c * QB + (unsigned long long)k + 1ULL) * 0x9e3779b97f4a7c15ULL;
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
-    z ^= z >> 31;
-    return ((double)(z >> 11) + 0.5) * (1.0 / 4503599627370496.0) - 1.0;  // (-1, 1)
-}
-
+// ---- the step (the start block, the Jacobi sweeps, the rank sort and the residual vote: trs_ritz.h) -----------------
 struct ReducedLds {
     double A[QB][LP];   // A_r, then C = T^T A_r T, then the rotated C
     double B[QB][LP];   // B_r, rotated to diag(D); then A_r T
@@ -181,64 +172,16 @@ struct ReducedLds {
     int r;
 };
 
-// Cyclic Jacobi on the leading q x q part of the symmetric M, in the round-robin order (eight disjoint rotations per
-// round: round r pairs 15 with r and (r + k) % 15 with (r - k) % 15, k = 1 .. 7), by the whole wave; the rotations are
-// accumulated into W (the identity on entry).  On exit the diagonal of M holds the eigenvalues, unsorted.
-__device__ void jacobi16(double (*M)[LP], double (*W)[LP], ReducedLds& R, const int q, const int lane) {
-    const int li = lane & 15, lq = lane >> 4;
-    double v[4], w[4];
-    for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep) {
-        int rotated = 0;
-        for (int round = 0; round < QB - 1; ++round) {
-            if (lane < 8) {
-                const int a = lane == 0 ? QB - 1 : (round + lane) % (QB - 1);
-                const int c = lane == 0 ? round : (round + QB - 1 - lane) % (QB - 1);
-                double cc = 1.0, ss = 0.0;
-                if (a < q && c < q) {
-                    const double app = M[a][a], aqq = M[c][c], apq = M[a][c];
-                    if (fabs(apq) > 1.1102230246251565e-16 * sqrt(fabs(app * aqq)) && fabs(apq) > 0.0) {
-                        const double tau = (aqq - app) / (2.0 * apq);
-                        const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-                        cc = 1.0 / sqrt(1.0 + t * t);
-                        ss = t * cc;
-                        rotated = 1;
-                    }
-                }
-                R.cs[a] = cc, R.tn[a] = -ss, R.partner[a] = c;
-                R.cs[c] = cc, R.tn[c] = ss, R.partner[c] = a;
-            }
-            __syncthreads();
-            const int pj = R.partner[li];
-            const double cj = R.cs[li], tj = R.tn[li];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int i = lq + 4 * r, pi = R.partner[i];
-                const double ci = R.cs[i], ti = R.tn[i];
-                v[r] = ci * (cj * M[i][li] + tj * M[i][pj]) + ti * (cj * M[pi][li] + tj * M[pi][pj]);
-                w[r] = cj * W[i][li] + tj * W[i][pj];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                M[lq + 4 * r][li] = v[r];
-                W[lq + 4 * r][li] = w[r];
-            }
-            __syncthreads();
-        }
-        if (!__any(rotated)) break;
-    }
-}
-
 // A_r Q = B_r Q diag(nu) of one truss with deflation, by the whole wave.  In: R.A, R.B (as the accumulators left them).
 // Out: R.r, R.Q (columns >= r zero), R.nu (NaN beyond r), |nu| descending.
 __device__ void reduced_eigenproblem(ReducedLds& R, const int lane) {
     const int li = lane & 15, lq = lane >> 4;
+    const JacobiScratch scratch = {R.cs, R.tn, R.partner};
     double v[4], w[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const int i = lq + 4 * r;
-        v[r] = 0.5 * (R.A[i][li] + R.A[li][i]);
-        w[r] = 0.5 * (R.B[i][li] + R.B[li][i]);
+        v[r] = symmetric(R.A, lq + 4 * r, li);
+        w[r] = symmetric(R.B, lq + 4 * r, li);
     }
     __syncthreads();
 #pragma unroll
@@ -252,7 +195,7 @@ __device__ void reduced_eigenproblem(ReducedLds& R, const int lane) {
     }
     __syncthreads();
     // B_r = V D V^T; the directions with D_k <= 2^-40 max D are dropped, the others keep their order
-    jacobi16(R.B, R.W, R, QB, lane);
+    jacobi16(R.B, R.W, scratch, QB, lane);
     if (lane < QB) R.d[lane] = R.B[lane][lane];
     __syncthreads();
     if (lane < QB) {
@@ -302,10 +245,7 @@ __device__ void reduced_eigenproblem(ReducedLds& R, const int lane) {
     for (int r = 0; r < 4; ++r) R.A[lq + 4 * r][li] = v[r];
     __syncthreads();
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int i = lq + 4 * r;
-        v[r] = 0.5 * (R.A[i][li] + R.A[li][i]);
-    }
+    for (int r = 0; r < 4; ++r) v[r] = symmetric(R.A, lq + 4 * r, li);
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -314,18 +254,13 @@ __device__ void reduced_eigenproblem(ReducedLds& R, const int lane) {
         R.W[i][li] = i == li ? 1.0 : 0.0;
     }
     __syncthreads();
-    jacobi16(R.A, R.W, R, q, lane);
+    jacobi16(R.A, R.W, scratch, q, lane);
     // |nu| descending (ties by index), then Q = T W[:, order]
     if (lane < QB) R.d[lane] = lane < q ? R.A[lane][lane] : 0.0;
     __syncthreads();
     if (lane < QB) {
-        R.nu[lane] = bk_nan();
-        if (lane < q) {
-            const double mine = fabs(R.d[lane]);
-            int rank = 0;
-            for (int j = 0; j < q; ++j) rank += (fabs(R.d[j]) > mine) | ((fabs(R.d[j]) == mine) & (j < lane));
-            R.order[rank] = lane;
-        }
+        R.nu[lane] = quiet_nan();
+        rank_sort(R.d, q, lane, R.order, [](double x) { return -fabs(x); });
     }
     __syncthreads();
     if (lane < q) R.nu[lane] = R.d[R.order[lane]];
@@ -361,7 +296,7 @@ __global__ __launch_bounds__(64) void trs_bk_step_kernel(const int p, const int*
     double* X = X_all + (size_t)b * QB * ld_f;
     double* lam = lam_all + (size_t)b * QB;
     double* resid = resid_all + (size_t)b * QB;
-    const double nan = bk_nan();
+    const double nan = quiet_nan();
     if (first) {
         // vector lq + 4 r, DOF 16 t + li: runs of 128 contiguous bytes
         const int q = min(QB, n);
@@ -454,20 +389,7 @@ __global__ __launch_bounds__(64) void trs_bk_step_kernel(const int p, const int*
     if (lane < QB) lam[lane] = lane < q ? theta + 1.0 / R.nu[lane] : nan;
     if (lane == 0) rank_all[b] = q;
     if (!check) return;
-    bool bad = false;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-        for (int off = 1; off < 16; off <<= 1) {   // over the 16 lanes of one lq: a fixed tree
-            num[r] += __shfl_xor(num[r], off);
-            den[r] += __shfl_xor(den[r], off);
-        }
-        const int k = lq + 4 * r;
-        const double res = k < q ? sqrt(num[r] / den[r]) : nan;
-        if (li == 0) resid[k] = res;
-        bad |= (k < n_modes) & !(res <= tol);
-    }
-    if (__any(bad)) return;
+    if (!step_converged(num, den, q, n_modes, tol, resid, lane)) return;
     // converged: frozen from here on, and the substitutions that still run over this truss get zeros
     for (int t = 0; t < nch; ++t)
 #pragma unroll
@@ -485,8 +407,6 @@ __global__ __launch_bounds__(256) void trs_bk_shapes_kernel(const int p, const i
                                                             const int* __restrict__ rank,
                                                             const int* __restrict__ joint_out,
                                                             double* __restrict__ phi) {
-    __shared__ double best_v[256];
-    __shared__ int best_o[256];
     const int b = blockIdx.x / p, k = blockIdx.x - b * p, tid = threadIdx.x;
     const int ndof = 3 * min(max(nJ[b], 0), nJ_max), ndof_max = 3 * nJ_max;
     const int n = min(max(n_free[b], 0), ld_f);
@@ -505,29 +425,7 @@ __global__ __launch_bounds__(256) void trs_bk_shapes_kernel(const int p, const i
         id = ((id >= 0) & (id < nJ_max)) ? id : j;
         return 3 * id + d - 3 * j;
     };
-    auto better = [](double v, int o, double bv, int bo) {
-        return fabs(v) > fabs(bv) || (fabs(v) == fabs(bv) && o < bo);
-    };
-    double bv = 0.0;
-    int bo = 0x7fffffff;
-    for (int d = tid; d < ndof; d += 256) {
-        const int r = row_of(d);
-        if (r < 0) continue;
-        const int o = place_of(d);
-        const double v = x[r];
-        if (better(v, o, bv, bo)) bv = v, bo = o;
-    }
-    best_v[tid] = bv;
-    best_o[tid] = bo;
-    __syncthreads();
-    for (int half = 128; half > 0; half >>= 1) {
-        if (tid < half && better(best_v[tid + half], best_o[tid + half], best_v[tid], best_o[tid])) {
-            best_v[tid] = best_v[tid + half];
-            best_o[tid] = best_o[tid + half];
-        }
-        __syncthreads();
-    }
-    const double top = best_v[0];
+    const double top = largest_component(x, ndof, tid, row_of, place_of);
     for (int d = tid; d < ndof_max; d += 256) {
         const int r = row_of(d);
         out[place_of(d)] = (r >= 0 && top != 0.0) ? x[r] / top : 0.0;

@@ -22,14 +22,14 @@
 #include "../../include/trs_modes.h"
 #include "trs_common.h"
 #include "trs_recover.h"
+#include "trs_ritz.h"
 
 namespace {
 
 using namespace trs_rec;
+using namespace trs_ritz;
 
-constexpr int QB = TRS_MODES_BLOCK;  // vectors per truss
-constexpr int LP = QB + 1;           // padded leading dimension of the 16 x 16 matrices in LDS
-constexpr int JACOBI_SWEEPS = 30;    // (a sweep without a rotation ends the loop; 6-9 are taken)
+static_assert(QB == TRS_MODES_BLOCK, "the block of trs_modes.h is the one of trs_ritz.h");
 
 // ---- lumped mass ----------------------------------------------------------------------------------------------------
 // One work-group per truss.  Half the mass of every member and its end joints go to LDS, then one thread per joint
@@ -84,15 +84,7 @@ __global__ __launch_bounds__(256) void trs_modes_mass_kernel(
     if (tid == 0) n_mass[b] = count;
 }
 
-// ---- the Rayleigh-Ritz step -----------------------------------------------------------------------------------------
-__device__ __forceinline__ double start_value(int c, int k) {
-    unsigned long long z = ((unsigned long long)c * QB + (unsigned long long)k + 1ULL) * 0x9e3779b97f4a7c15ULL;
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
-    z ^= z >> 31;
-    return ((double)(z >> 11) + 0.5) * (1.0 / 4503599627370496.0) - 1.0;  // (-1, 1)
-}
-
+// ---- the Rayleigh-Ritz step (the pieces shared with buckling.hip: trs_ritz.h) ----------------------------------------
 struct ReducedLds {
     double K[QB][LP];   // K_r, then C = inv(L) K_r inv(L)^T, then the rotated C
     double M[QB][LP];   // M_r, eliminated in place
@@ -113,8 +105,8 @@ __device__ void reduced_eigenproblem(ReducedLds& R, const int q, const int lane)
     for (int r = 0; r < 4; ++r) {
         const int i = lq + 4 * r;
         const bool in = (i < q) & (li < q);
-        v[r] = in ? 0.5 * (R.K[i][li] + R.K[li][i]) : 0.0;
-        w[r] = in ? 0.5 * (R.M[i][li] + R.M[li][i]) : 0.0;
+        v[r] = in ? symmetric(R.K, i, li) : 0.0;
+        w[r] = in ? symmetric(R.M, i, li) : 0.0;
     }
     __syncthreads();
 #pragma unroll
@@ -161,66 +153,18 @@ __device__ void reduced_eigenproblem(ReducedLds& R, const int q, const int lane)
     }
     __syncthreads();
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int i = lq + 4 * r;
-        v[r] = 0.5 * (R.K[i][li] + R.K[li][i]);
-    }
+    for (int r = 0; r < 4; ++r) v[r] = symmetric(R.K, lq + 4 * r, li);
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < 4; ++r) R.K[lq + 4 * r][li] = v[r];
     __syncthreads();
-    // cyclic Jacobi, round-robin order: round r pairs 15 with r and (r + k) % 15 with (r - k) % 15, k = 1 .. 7
-    for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep) {
-        int rotated = 0;
-        for (int round = 0; round < QB - 1; ++round) {
-            if (lane < 8) {
-                const int a = lane == 0 ? QB - 1 : (round + lane) % (QB - 1);
-                const int c = lane == 0 ? round : (round + QB - 1 - lane) % (QB - 1);
-                double cc = 1.0, ss = 0.0;
-                if (a < q && c < q) {
-                    const double app = R.K[a][a], aqq = R.K[c][c], apq = R.K[a][c];
-                    if (fabs(apq) > 1.1102230246251565e-16 * sqrt(fabs(app * aqq)) && fabs(apq) > 0.0) {
-                        const double tau = (aqq - app) / (2.0 * apq);
-                        const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-                        cc = 1.0 / sqrt(1.0 + t * t);
-                        ss = t * cc;
-                        rotated = 1;
-                    }
-                }
-                R.cs[a] = cc, R.tn[a] = -ss, R.partner[a] = c;
-                R.cs[c] = cc, R.tn[c] = ss, R.partner[c] = a;
-            }
-            __syncthreads();
-            const int pj = R.partner[li];
-            const double cj = R.cs[li], tj = R.tn[li];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int i = lq + 4 * r, pi = R.partner[i];
-                const double ci = R.cs[i], ti = R.tn[i];
-                v[r] = ci * (cj * R.K[i][li] + tj * R.K[i][pj]) + ti * (cj * R.K[pi][li] + tj * R.K[pi][pj]);
-                w[r] = cj * R.W[i][li] + tj * R.W[i][pj];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                R.K[lq + 4 * r][li] = v[r];
-                R.W[lq + 4 * r][li] = w[r];
-            }
-            __syncthreads();
-        }
-        if (!__any(rotated)) break;
-    }
+    jacobi16(R.K, R.W, {R.cs, R.tn, R.partner}, q, lane);
     // ascending order (ties by index), then Q = inv(L)^T W[:, order]
     if (lane < QB) R.theta[lane] = lane < q ? R.K[lane][lane] : 0.0;
     __syncthreads();
     if (lane < QB) {
-        R.lam[lane] = __longlong_as_double(0x7ff8000000000000LL);
-        if (lane < q) {
-            const double mine = R.theta[lane];
-            int rank = 0;
-            for (int j = 0; j < q; ++j) rank += (R.theta[j] < mine) | ((R.theta[j] == mine) & (j < lane));
-            R.order[rank] = lane;
-        }
+        R.lam[lane] = quiet_nan();
+        rank_sort(R.theta, q, lane, R.order, [](double x) { return x; });
     }
     __syncthreads();
     if (lane < q) {
@@ -252,7 +196,7 @@ __global__ __launch_bounds__(64) void trs_modes_step_kernel(const int p, const i
     double* X = X_all + (size_t)b * QB * ld_f;
     double* lam = lam_all + (size_t)b * QB;
     double* resid = resid_all + (size_t)b * QB;
-    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    const double nan = quiet_nan();
     if (first) {
         // vector lq + 4 r, DOF 16 t + li: runs of 128 contiguous bytes
         for (int t = 0; t < nch; ++t) {
@@ -334,20 +278,7 @@ __global__ __launch_bounds__(64) void trs_modes_step_kernel(const int p, const i
     }
     if (lane < QB) lam[lane] = R.lam[lane];
     if (!check) return;
-    bool bad = false;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-        for (int off = 1; off < 16; off <<= 1) {   // over the 16 lanes of one lq: a fixed tree
-            num[r] += __shfl_xor(num[r], off);
-            den[r] += __shfl_xor(den[r], off);
-        }
-        const int k = lq + 4 * r;
-        const double res = k < q ? sqrt(num[r] / den[r]) : nan;
-        if (li == 0) resid[k] = res;
-        bad |= (k < n_modes) & !(res <= tol);
-    }
-    if (__any(bad)) return;
+    if (!step_converged(num, den, q, n_modes, tol, resid, lane)) return;
     // converged: frozen from here on, and the substitutions that still run over this truss get zeros
     for (int t = 0; t < nch; ++t)
 #pragma unroll
@@ -364,40 +295,17 @@ __global__ __launch_bounds__(256) void trs_modes_shapes_kernel(const int p, cons
                                                                const int* __restrict__ nJ,
                                                                const int* __restrict__ joint_out,
                                                                double* __restrict__ phi) {
-    __shared__ double best_v[256];
-    __shared__ int best_o[256];
     const int b = blockIdx.x / p, k = blockIdx.x - b * p, tid = threadIdx.x;
     const int ndof = 3 * nJ[b], ndof_max = 3 * nJ_max;
     const int* fi = free_index + (size_t)b * ndof_max;
     const int* jo = joint_out != nullptr ? joint_out + (size_t)b * nJ_max : nullptr;
     const double* x = X_all + ((size_t)b * QB + k) * ld_f;
     double* out = phi + (size_t)blockIdx.x * ndof_max;
-    auto better = [](double v, int o, double bv, int bo) {
-        return fabs(v) > fabs(bv) || (fabs(v) == fabs(bv) && o < bo);
-    };
-    double bv = 0.0;
-    int bo = 0x7fffffff;
-    for (int d = tid; d < ndof; d += 256) {
-        const int r = fi[d];
-        if (r < 0) continue;
-        const int o = jo != nullptr ? 3 * jo[d / 3] + d % 3 : d;
-        const double v = x[r];
-        if (better(v, o, bv, bo)) bv = v, bo = o;
-    }
-    best_v[tid] = bv;
-    best_o[tid] = bo;
-    __syncthreads();
-    for (int half = 128; half > 0; half >>= 1) {
-        if (tid < half && better(best_v[tid + half], best_o[tid + half], best_v[tid], best_o[tid])) {
-            best_v[tid] = best_v[tid + half];
-            best_o[tid] = best_o[tid + half];
-        }
-        __syncthreads();
-    }
-    const bool flip = best_v[0] < 0.0;
+    auto place_of = [&](int d) { return jo != nullptr ? 3 * jo[d / 3] + d % 3 : d; };
+    const bool flip = largest_component(x, ndof, tid, [&](int d) { return fi[d]; }, place_of) < 0.0;
     for (int d = tid; d < ndof_max; d += 256) {
         const int r = d < ndof ? fi[d] : -1;
-        const int o = jo != nullptr ? 3 * jo[d / 3] + d % 3 : d;
+        const int o = place_of(d);
         const double v = r >= 0 ? x[r] : 0.0;
         out[o] = (flip && r >= 0) ? -v : v;
     }

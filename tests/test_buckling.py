@@ -189,6 +189,22 @@ def test_header_table_and_library_agree():
     assert {"solve_buckling", "BucklingResult"} <= set(pkg.__all__)
 
 
+def test_the_rayleigh_ritz_core_exists_once():
+    """modes.hip and buckling.hip take the start block, the Jacobi sweep, the rank sort, the residual vote and the
+    largest-component reduction from trs_ritz.h; neither keeps a copy (the hash constant, the rotation threshold, the
+    shuffle tree and the reduction's arrays are written once)."""
+    makefile = open(os.path.join(_capi.CSRC_DIR, "Makefile")).read()
+    assert " trs_ritz.h " in makefile
+    texts = {src: open(os.path.join(_capi.CSRC_DIR, src)).read() for src in ("modes.hip", "buckling.hip", "trs_ritz.h")}
+    for mark in ("0x9e3779b97f4a7c15", "1.1102230246251565e-16", "__shfl_xor", "best_v[256]", "order[rank] = lane"):
+        assert texts["trs_ritz.h"].count(mark) >= 1, mark
+        assert mark not in texts["modes.hip"] and mark not in texts["buckling.hip"], mark
+    for src, block in (("modes.hip", "TRS_MODES_BLOCK"), ("buckling.hip", "TRS_BK_BLOCK")):
+        assert '#include "trs_ritz.h"' in texts[src] and f"static_assert(QB == {block}" in texts[src]
+        assert texts[src].count("jacobi16(") >= 1 and texts[src].count("step_converged(") == 1
+        assert texts[src].count("largest_component(") == 1 and texts[src].count("rank_sort(") == 1
+
+
 def test_fits_rule_in_bytes():
     """The member kernel: u in joint layout (24 nJ bytes).  The product kernel: the member table (32 nM), the end lists
     with their far joints (4 (2 nJ + 1 + 4 nM)) and vc vectors in joint layout (24 nJ vc), rounded up to 16; a shape fits
