@@ -37,7 +37,8 @@ __all__ = ["Truss", "Member", "MemberType", "SupportType", "MetapathType", "Task
            "ShardedSolver", "solve_batch_sharded", "solve_batch_distributed",
            "solve_load_cases", "LoadCaseResult", "load_cases_from_json",
            "solve_gradients", "GradientResult", "DifferentiableTruss",
-           "solve_modes", "ModeResult", "solve_effect_cases", "EffectCaseResult", "LoadCase",
+           "solve_modes", "ModeResult", "solve_mode_gradients", "ModeGradientResult",
+           "solve_effect_cases", "EffectCaseResult", "LoadCase",
            "solve_member_loss", "MemberLossResult", "solve_influence", "InfluenceResult",
            "solve_member_sets", "MemberSetResult", "solve_transient", "TransientResult",
            "solve_nonlinear", "NonlinearResult", "solve_buckling", "BucklingResult"]
@@ -49,7 +50,8 @@ def __getattr__(name):
                 "solve_load_cases", "LoadCaseResult", "solve_gradients", "GradientResult", "solve_modes", "ModeResult",
                 "solve_effect_cases", "EffectCaseResult", "solve_member_loss", "MemberLossResult", "solve_influence",
                 "InfluenceResult", "solve_member_sets", "MemberSetResult", "solve_transient", "TransientResult",
-                "solve_nonlinear", "NonlinearResult", "solve_buckling", "BucklingResult"):
+                "solve_nonlinear", "NonlinearResult", "solve_buckling", "BucklingResult", "solve_mode_gradients",
+                "ModeGradientResult"):
         from . import batch
         return getattr(batch, name)
     if name == "DifferentiableTruss":

@@ -1446,6 +1446,88 @@ class DeviceBatch:
         out["resid"].copy_(ws["resid"][:, :p])
         out["n_modes"].copy_(ws["n_mass"].clamp(max=p))
         out["iters"].copy_(ws["state"])
+        # what `mode_gradients` differentiates: the block stays in the workspace until the generation moves on
+        self._modes_state = {"p": p, "mass_scale": float(mass_scale), "joint_mass": joint_mass,
+                             "generation": self.generation}
+        return out
+
+    # -- gradients of the eigenvalues from the converged block (include/trs_modegrad.h) ------------------
+    #: the gradients `mode_gradients` can give
+    MODE_GRADIENTS = ("A", "E", "rho", "xyz", "joint_mass")
+
+    def _mode_gradient_shape(self, key, R):
+        return {"A": [self.B, R, self.nM_max], "E": [self.B, R, self.nM_max], "rho": [self.B, R, self.nM_max],
+                "xyz": [self.B, R, self.nJ_max, 3], "joint_mass": [self.B, R, self.nJ_max]}[key]
+
+    def mode_gradients(self, weights=None, want=None, out=None, generation=None):
+        """The derivatives of the eigenvalues of the last `modes()` with respect to the member areas, moduli and
+        densities [B, R, nM_max], the joint coordinates [B, R, nJ_max, 3] (every joint, held ones included; z = 0 for a
+        2D truss) and the caller's `joint_mass` [B, R, nJ_max] (caller's joint numbering), as a dict of device tensors
+        with the keys named in `want` plus `gap` (`want` None: all of `MODE_GRADIENTS`, "joint_mass" only when `modes()`
+        was given masses - asked for by name without them it is refused; `out`: such a dict to write into).  `weights` None: R = p, row k is
+        the gradient of lambda_k; `weights` [B, p] (float64 device tensor): R = 1, the row is sum_k w_k d lambda_k
+        (a weight beyond the truss's n_modes is ignored, whatever it holds).  One launch on the current stream
+        (`trs_mg_grad`: one pass over the members with the block X that `modes()` left resident - no solve, no
+        factorisation); rows beyond n_modes, padding members and joints and members of zero length get zeros.
+        d omega = d lambda / (2 omega).
+        `gap` [B, p]: min over the other Ritz values of the block (i < min(16, DOFs with mass), i != k) of
+        |lam_i - lam_k| / |lam_k|, +inf where there is no other, NaN beyond n_modes.  The formula holds for a SIMPLE
+        eigenvalue: a row of a repeated one (gap of the order of the residual - symmetric trusses have them) is the
+        formula on whichever vector of the invariant subspace came out and means nothing alone, while equal weights
+        over a closed cluster always give the derivative of the cluster's sum.
+        The `modes()` state must be current: any call that bumps `generation` since (`factor()`, `solve_cases()`, a later
+        `modes()`, `buckling()`, ...) makes this raise ValueError (`generation`: the value the caller saw after ITS
+        `modes()`, checked as well).  Nothing is bumped or overwritten here: the call can be repeated."""
+        t = self.torch
+        state = getattr(self, "_modes_state", None)
+        if not getattr(self, "_factored", False) or state is None:
+            raise ValueError("mode_gradients(): no forward solution - call factor() and modes(p) first")
+        if state["generation"] != self.generation or (generation is not None and generation != self.generation):
+            raise ValueError("mode_gradients(): the forward solution is stale - factor(), solve_cases() or another "
+                             "analysis ran since the modes() these gradients belong to")
+        p = state["p"]
+        if want is None:
+            want = tuple(k for k in self.MODE_GRADIENTS if k != "joint_mass" or state["joint_mass"] is not None)
+        want = tuple(want)
+        if any(k not in self.MODE_GRADIENTS for k in want):
+            raise ValueError(f"mode_gradients(): want must name some of {self.MODE_GRADIENTS}, got {want}")
+        if "joint_mass" in want and state["joint_mass"] is None:
+            raise ValueError("mode_gradients(): 'joint_mass' is wanted, but modes() was given no joint_mass")
+        if weights is not None:
+            if tuple(weights.shape) != (self.B, p) or weights.dtype != t.float64 or weights.device != self.device:
+                raise ValueError(f"mode_gradients(): weights must be float64 [B={self.B}, p={p}] on {self.device} (the "
+                                 f"last modes() had p = {p}), got {weights.dtype} {list(weights.shape)} on "
+                                 f"{weights.device}")
+            weights = weights.contiguous()
+        R = p if weights is None else 1
+        shapes = {k: self._mode_gradient_shape(k, R) for k in want}
+        shapes["gap"] = [self.B, p]
+        out = self._out_tensors("mode_gradients", shapes, out)
+        if self.B == 0:
+            return out
+        if not self.lib.trs_mg_fits(self.nJ_max, self.nM_max, p):
+            raise HipExtensionError(f"mode_gradients(): a truss of {self.nJ_max} joints / {self.nM_max} members exceeds "
+                                    "the LDS of the gradient kernel (trs_mg_fits)")
+        ws = self._modes_ws
+        jo, stream, tab = self._case_launch()
+        members = self._members() if self.table else \
+            (self.conn.data_ptr(), self.E.data_ptr(), self.A.data_ptr(), self.rho.data_ptr())
+        with t.cuda.device(self.device):
+            _capi.check(getattr(self.lib, f"trs_mg{tab}_grad")(
+                self.B, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *members, self.free_index.data_ptr(),
+                self.n_free.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), jo, ws["X"].data_ptr(), self.rows,
+                ws["lam"].data_ptr(), ws["n_mass"].data_ptr(), p, state["mass_scale"], _ptr(weights), _ptr(out.get("A")),
+                _ptr(out.get("E")), _ptr(out.get("rho")), _ptr(out.get("xyz")), _ptr(out.get("joint_mass")), stream),
+                f"trs_mg{tab}_grad")
+            # the gaps, from the block's 16 Ritz values
+            lam = ws["lam"]
+            other = t.arange(MODES_BLOCK, device=self.device)
+            valid = other[None, None, :] < ws["n_mass"].clamp(max=MODES_BLOCK)[:, None, None]
+            valid = valid & (other[None, None, :] != other[None, :p, None])
+            mine = lam[:, :p, None]
+            dist = (lam[:, None, :] - mine).abs() / mine.abs()
+            gap = t.where(valid, dist, t.full_like(dist, float("inf"))).amin(dim=2)
+            out["gap"].copy_(t.where(mine[:, :, 0].isnan(), mine[:, :, 0], gap))
         return out
 
     # -- transient response: Newmark time stepping on a factor of K + sigma M (include/trs_dynamics.h) ------------------
@@ -3529,6 +3611,97 @@ def solve_modes(trusses_or_packed, p=6, joint_mass=None, mass_scale=1.0, tol=1e-
     for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope):
         _put_result(part, out, db.modes(p, tol=tol, max_iters=max_iters, joint_mass=part.cut(joint_mass, nJ=1),
                                         mass_scale=mass_scale))
+    out.omega = out.eigenvalue.sqrt()
+    return _finish_result(torch, dev, out, on_device)
+
+
+@dataclass
+class ModeGradientResult:
+    """Results of `solve_mode_gradients`: eigenvalue, omega, gap, residual [B, p], n_modes, iters, info [B] as
+    `ModeResult` (gap: the relative distance of eigenvalue k to the nearest other Ritz value of the truss's block, +inf
+    where there is none, NaN beyond n_modes), and the gradients dA, dE, drho [B, R, nM_max] (per member, also in the
+    table member form), dxyz [B, R, nJ_max, 3] (every joint, held ones included; z = 0 for a 2D truss) and djoint_mass
+    [B, R, nJ_max] (caller's joint numbering).  R = p without weights (row k: the gradient of eigenvalue k; zeros
+    beyond n_modes), R = 1 with weights (sum_k w_k row k).  d omega = d eigenvalue / (2 omega).  A row of a repeated
+    eigenvalue (a gap of the order of the residual) means nothing alone; equal weights over a closed cluster always give
+    the derivative of the cluster's sum.  A gradient that was not wanted is zeros."""
+    eigenvalue: np.ndarray
+    omega: np.ndarray
+    gap: np.ndarray
+    residual: np.ndarray
+    n_modes: np.ndarray
+    iters: np.ndarray
+    dA: np.ndarray
+    dE: np.ndarray
+    drho: np.ndarray
+    dxyz: np.ndarray
+    djoint_mass: np.ndarray
+    info: np.ndarray
+
+    # (`modes` returns no "omega": the field keeps its fill until `solve_mode_gradients` takes the root)
+    FIELDS = {"eigenvalue": ("lam", float("nan"), "float64", ("P",)), "omega": ("omega", float("nan"), "float64", ("P",)),
+              "gap": ("gap", float("nan"), "float64", ("P",)), "residual": ("resid", float("nan"), "float64", ("P",)),
+              "n_modes": ("n_modes", 0, "int32", ()), "iters": ("iters", 0, "int32", ()),
+              "dA": ("A", 0.0, "float64", ("R", "nM")), "dE": ("E", 0.0, "float64", ("R", "nM")),
+              "drho": ("rho", 0.0, "float64", ("R", "nM")), "dxyz": ("xyz", 0.0, "float64", ("R", "nJ", 3)),
+              "djoint_mass": ("joint_mass", 0.0, "float64", ("R", "nJ"))}
+
+
+def _check_mode_gradient_args(B, nJ_max, p, joint_mass_shape, mass_scale, tol, max_iters, weights=None, want=None,
+                              sections=None, joint_mass_min=None):
+    """The argument errors of `solve_mode_gradients` that need no device: those of `solve_modes`, and weights of the wrong
+    shape or not finite (`weights`: a host array or None), unknown names in `want`, "joint_mass" wanted without masses,
+    and `sections=`.  Returns `want` as a tuple (None: every gradient, "joint_mass" only when there are masses)."""
+    if sections is not None:
+        raise ValueError("solve_mode_gradients: sections= variants cannot be combined with gradients")
+    _check_mode_args(B, nJ_max, p, joint_mass_shape, mass_scale, tol, max_iters, joint_mass_min=joint_mass_min)
+    if want is None:
+        want = tuple(k for k in DeviceBatch.MODE_GRADIENTS if k != "joint_mass" or joint_mass_shape is not None)
+    if isinstance(want, str):
+        raise ValueError(f"solve_mode_gradients: want must be a sequence of names out of {DeviceBatch.MODE_GRADIENTS}")
+    want = tuple(want)
+    if any(k not in DeviceBatch.MODE_GRADIENTS for k in want):
+        raise ValueError(f"solve_mode_gradients: want must name some of {DeviceBatch.MODE_GRADIENTS}, got {want}")
+    if "joint_mass" in want and joint_mass_shape is None:
+        raise ValueError("solve_mode_gradients: 'joint_mass' is wanted, but no joint_mass was given")
+    if weights is not None:
+        got = tuple(int(x) for x in weights.shape)
+        if got != (B, int(p)):
+            raise ValueError(f"solve_mode_gradients: weights must be [B={B}, p={int(p)}], got {got}")
+        if not np.isfinite(weights).all():
+            raise ValueError("solve_mode_gradients: weights must be finite")
+    return want
+
+
+def solve_mode_gradients(trusses_or_packed, p=6, weights=None, joint_mass=None, mass_scale=1.0, want=None, tol=1e-10,
+                         max_iters=256, device=None, reorder=False, options=None, max_slab_bytes=64 << 30,
+                         on_device=False, use_envelope=True, sections=None):
+    """`solve_modes` plus the derivatives of the eigenvalues lambda = omega^2 with respect to the member areas, moduli and
+    densities, the joint coordinates and the non-structural joint masses: every truss is factored ONCE, its `p` lowest
+    pairs are iterated, and one pass over the members with the converged block gives the gradients
+    (`DeviceBatch.mode_gradients`, include/trs_modegrad.h; no finite differences, no further solve).  `weights` None:
+    the Jacobian, one row per eigenvalue; `weights` [B, p] (numpy or torch, finite): the one row sum_k w_k d lambda_k.
+    `want`: some of `DeviceBatch.MODE_GRADIENTS` (default: all, "joint_mass" only when `joint_mass` is given).  The other
+    arguments as `solve_modes`.  Returns a `ModeGradientResult`; read its `gap` before trusting a single row."""
+    packed = _as_packed(trusses_or_packed)
+    B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
+    jm_shape = jm_min = None
+    if joint_mass is not None:
+        jm_shape = tuple(int(x) for x in joint_mass.shape)
+        jm = _host_array(joint_mass, np.float64)
+        jm_min = (float(jm.min()) if jm.size else 0.0) if np.isfinite(jm).all() else float("nan")
+    want = _check_mode_gradient_args(B, nJ_max, p, jm_shape, mass_scale, tol, max_iters,
+                                     weights=None if weights is None else _host_array(weights, np.float64), want=want,
+                                     sections=sections, joint_mass_min=jm_min)
+    p = int(p)
+    torch, dev = _require_gpu(device)
+    joint_mass, weights = _device_f64(torch, dev, joint_mass), _device_f64(torch, dev, weights)
+    out = _new_result(torch, dev, ModeGradientResult, B,
+                      {"P": p, "R": p if weights is None else 1, "nJ": nJ_max, "nM": nM_max})
+    for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope):
+        res = db.modes(p, tol=tol, max_iters=max_iters, joint_mass=part.cut(joint_mass, nJ=1), mass_scale=mass_scale)
+        res.update(db.mode_gradients(weights=part.cut(weights), want=want))
+        _put_result(part, out, res)
     out.omega = out.eigenvalue.sqrt()
     return _finish_result(torch, dev, out, on_device)
 

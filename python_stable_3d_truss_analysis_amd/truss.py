@@ -445,6 +445,37 @@ class Truss:
         shapes = [dict(zip(range(nJ), result.shape[0, k, :nJ, :dim].copy())) for k in range(count)]
         return omega, shapes
 
+    def FrequencyGradients(self, nModes=6, jointMasses=None, massScale=1.0):
+        """The derivatives of the `nModes` (1 .. 8) lowest eigenvalues lambda = omega^2 of `NaturalFrequencies` (the same
+        lumped mass, `jointMasses`, `massScale`) with respect to this truss's design, from one factorisation and one
+        pass over the members with the converged mode shapes (`batch.solve_mode_gradients`).  Returns a dict of numpy
+        arrays in the truss's own joint and member ids, n the number of values the truss has: "eigenvalue", "omega",
+        "gap" [n]; "dA", "dE", "drho" [n, members] (area, modulus, density of every member); "dxyz" [n, joints, dim]
+        (every joint, supports included); "djoint_mass" [n, joints] when `jointMasses` is given.
+        d omega = d lambda / (2 omega).  "gap" is the relative distance to the nearest other eigenvalue: a row with a
+        tiny gap belongs to a repeated eigenvalue (symmetric trusses have them) and means nothing alone - the sum of
+        the rows of the whole cluster is the derivative of the sum of its eigenvalues.  The truss's loads, its solved
+        state and its results stay as they are; errors as `NaturalFrequencies`."""
+        if not self.isStable:
+            raise TrussNotStableError("The truss is not stable !")
+        from .batch import pack_trusses, solve_mode_gradients  # late import: keeps the model importable without torch
+        packed = pack_trusses([self])
+        masses = None
+        if jointMasses:
+            masses = np.zeros([1, packed.nJ_max])
+            for jointID, mass in jointMasses.items():
+                masses[0, jointID] = mass
+        result = solve_mode_gradients(packed, p=nModes, joint_mass=masses, mass_scale=massScale)
+        if int(result.info[0]) != 0:
+            raise np.linalg.LinAlgError("Singular matrix")
+        n, nJ, nM, dim = int(result.n_modes[0]), len(self._pos), int(packed.nM[0]), self._dim
+        out = {"eigenvalue": result.eigenvalue[0, :n].copy(), "omega": result.omega[0, :n].copy(),
+               "gap": result.gap[0, :n].copy(), "dA": result.dA[0, :n, :nM].copy(), "dE": result.dE[0, :n, :nM].copy(),
+               "drho": result.drho[0, :n, :nM].copy(), "dxyz": result.dxyz[0, :n, :nJ, :dim].copy()}
+        if masses is not None:
+            out["djoint_mass"] = result.djoint_mass[0, :n, :nJ].copy()
+        return out
+
     def BucklingFactors(self, nModes=4, returnShapes=False, maxShifts=6):
         """By what factor can this truss's loads grow before it buckles (linear buckling, `batch.solve_buckling`)?
         Returns `(critical, factors)`: `critical` the smallest positive load factor (NaN when none was found within
