@@ -22,15 +22,11 @@
 // forms.
 #include "../../include/trs_solver.h"
 #include "trs_common.h"
-#include "trs_recover.h"
+#include "trs_lds.h"
 
 namespace {
 
 using namespace trs_rec;
-
-__device__ __forceinline__ double member_modulus(const TrsMembers& mem, size_t mm) {
-    return mem.table() ? mem.types[3 * (int)mem.tidx[mm] + 1] : mem.E[mm];
-}
 
 // LDS tables of one truss (both kernels; the right-hand-side kernel uses one of the two DOF vectors)
 struct AdjTables : EndLists {  // (the member-end lists of EVERY joint: trs_recover.h)
@@ -39,14 +35,13 @@ struct AdjTables : EndLists {  // (the member-end lists of EVERY joint: trs_reco
     double* pm;   // [nM_max]    one double per member
 };
 
-__device__ __forceinline__ AdjTables adj_tables(double* sh, int nJ_max, int nM_max) {
+template <class Arena>
+__host__ __device__ inline AdjTables layout(Arena& a, int nJ_max, int nM_max) {
     AdjTables t;
-    t.v0 = sh;
-    t.v1 = sh + 3 * nJ_max;
-    t.pm = t.v1 + 3 * nJ_max;
-    t.cnt = reinterpret_cast<int*>(t.pm + nM_max);
-    t.start = t.cnt + nJ_max;
-    t.ends = t.start + nJ_max + 1;
+    t.v0 = a.template take<double>(3, nJ_max);
+    t.v1 = a.template take<double>(3, nJ_max);
+    t.pm = a.template take<double>(nM_max);
+    trs_lds::take_end_lists(a, t, nJ_max, nM_max);
     return t;
 }
 
@@ -60,7 +55,8 @@ __global__ __launch_bounds__(256) void trs_adjoint_rhs_kernel(
     const int b = blockIdx.x, tid = threadIdx.x;
     const int joints = nJ[b], members = nM[b];
     const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
-    const AdjTables t = adj_tables(sh, nJ_max, nM_max);
+    trs_lds::Carve lds(sh);
+    const AdjTables t = layout(lds, nJ_max, nM_max);
     double* gh = t.v0;  // g^: gf at the constrained DOFs, device numbering
     double* s = t.pm;   // member pseudo-force
     const int* fi = free_index + (size_t)b * ndof_max;
@@ -123,7 +119,8 @@ __global__ __launch_bounds__(256) void trs_adjoint_grad_kernel(
     const int b = blockIdx.x, tid = threadIdx.x;
     const int joints = nJ[b], members = nM[b];
     const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
-    const AdjTables t = adj_tables(sh, nJ_max, nM_max);
+    trs_lds::Carve lds(sh);
+    const AdjTables t = layout(lds, nJ_max, nM_max);
     double* u = t.v0;    // forward displacements of one case, device numbering
     double* mu = t.v1;   // adjoint field of that case
     double* acc = t.pm;  // sum over the cases of N_m t_m
@@ -202,7 +199,7 @@ __global__ __launch_bounds__(256) void trs_adjoint_grad_kernel(
     for (int m = tid; m < nM_max; m += 256) {
         const bool live = m < members;
         if (gA != nullptr) gA[mbase + m] = live ? acc[m] / mem.area(mbase + m) : 0.0;
-        if (gE != nullptr) gE[mbase + m] = live ? acc[m] / member_modulus(mem, mbase + m) : 0.0;
+        if (gE != nullptr) gE[mbase + m] = live ? acc[m] / modulus(mem, mbase + m) : 0.0;
     }
     if (gx != nullptr)
         for (int j = joints + tid; j < nJ_max; j += 256) {
@@ -214,8 +211,7 @@ __global__ __launch_bounds__(256) void trs_adjoint_grad_kernel(
 }  // namespace
 
 extern "C" size_t trs_adjoint_lds(int nJ_max, int nM_max) {
-    return (((size_t)6 * nJ_max + (size_t)nM_max) * sizeof(double) +
-            ((size_t)2 * nJ_max + 1 + 2 * (size_t)nM_max) * sizeof(int) + 15) / 16 * 16;
+    return trs_lds::count([&](auto& a) { layout(a, nJ_max, nM_max); });
 }
 
 extern "C" int trs_adjoint_rhs_launch(int B, int L, int nJ_max, int nM_max, const double* xyz, const TrsMembers* members,
@@ -224,10 +220,8 @@ extern "C" int trs_adjoint_rhs_launch(int B, int L, int nJ_max, int nM_max, cons
                                       int ld_f, hipStream_t stream) {
     if (B <= 0 || L <= 0) return 0;
     const size_t lds = trs_adjoint_lds(nJ_max, nM_max);
-    if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
-    static const int lds_limit_set = (int)hipFuncSetAttribute(   // once per process, not per launch
-        reinterpret_cast<const void*>(trs_adjoint_rhs_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)lds_limit_set;
+    if (lds > TRS_LDS_BYTES) return (int)hipErrorInvalidValue;
+    trs_lds::raise_lds_once<trs_adjoint_rhs_kernel>();
     hipLaunchKernelGGL(trs_adjoint_rhs_kernel, dim3(B), dim3(256), lds, stream, L, xyz, *members, gu, gf, gN, free_index,
                        n_free, nJ, nM, nJ_max, nM_max, joint_in, F, ld_f);
     return (int)hipGetLastError();
@@ -240,10 +234,8 @@ extern "C" int trs_adjoint_grad_launch(int B, int L, int nJ_max, int nM_max, con
                                        hipStream_t stream) {
     if (B <= 0 || L <= 0) return 0;
     const size_t lds = trs_adjoint_lds(nJ_max, nM_max);
-    if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
-    static const int lds_limit_set = (int)hipFuncSetAttribute(   // once per process, not per launch
-        reinterpret_cast<const void*>(trs_adjoint_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)lds_limit_set;
+    if (lds > TRS_LDS_BYTES) return (int)hipErrorInvalidValue;
+    trs_lds::raise_lds_once<trs_adjoint_grad_kernel>();
     hipLaunchKernelGGL(trs_adjoint_grad_kernel, dim3(B), dim3(256), lds, stream, L, xyz, *members, gf, gN, free_index, nJ,
                        nM, nJ_max, nM_max, Fu, Lam, ld_f, gA, gE, gxyz, gloads, joint_out);
     return (int)hipGetLastError();

@@ -19,7 +19,7 @@
 // and writing its own elements only.
 #include "../../include/trs_buckling.h"
 #include "trs_common.h"
-#include "trs_recover.h"
+#include "trs_lds.h"
 #include "trs_ritz.h"
 
 namespace {
@@ -28,16 +28,26 @@ using namespace trs_rec;
 using namespace trs_ritz;
 
 static_assert(QB == TRS_BK_BLOCK, "the block of trs_buckling.h is the one of trs_ritz.h");
-constexpr size_t BK_LDS_BUDGET = 160 * 1024;   // a CU's LDS
 constexpr double BK_DEFLATE = 9.094947017729282e-13;   // 2^-40
 
 // ---- the reference state --------------------------------------------------------------------------------------------
+struct MemberTables { double* u; };   // [3 nJ_max] u in joint layout
+
+template <class Arena>
+__host__ __device__ inline MemberTables members_layout(Arena& a, int nJ_max) {
+    return MemberTables{a.template take<double>(3, nJ_max)};
+}
+
+size_t members_lds(int nJ_max) { return trs_lds::count([&](auto& a) { members_layout(a, nJ_max); }); }
+
 __global__ __launch_bounds__(256) void trs_bk_members_kernel(
     const double* __restrict__ xyz, const TrsMembers mem, const int* __restrict__ free_index,
     const int* __restrict__ n_free, const int* __restrict__ nJ, const int* __restrict__ nM, const int nJ_max,
     const int nM_max, const double* __restrict__ uf, const int ld_uf, const double* __restrict__ theta_all,
     double* __restrict__ N_out, int* __restrict__ ends_out, double* __restrict__ Mt, double* __restrict__ W) {
-    extern __shared__ double sh[];   // u in joint layout [3 nJ_max]
+    extern __shared__ double sh[];
+    trs_lds::Carve lds(sh);
+    double* u = members_layout(lds, nJ_max).u;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int joints = min(max(nJ[b], 0), nJ_max), members = min(max(nM[b], 0), nM_max);
     const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
@@ -48,7 +58,7 @@ __global__ __launch_bounds__(256) void trs_bk_members_kernel(
     const double theta = theta_all != nullptr ? theta_all[b] : 0.0;
     for (int d = tid; d < ndof_max; d += 256) {
         const int r = d < ndof ? fi[d] : -1;
-        sh[d] = (r >= 0 && r < n) ? uf[(size_t)b * ld_uf + r] : 0.0;
+        u[d] = (r >= 0 && r < n) ? uf[(size_t)b * ld_uf + r] : 0.0;
     }
     __syncthreads();
     for (int m = tid; m < nM_max; m += 256) {
@@ -69,7 +79,7 @@ __global__ __launch_bounds__(256) void trs_bk_members_kernel(
         e[1] = c.y;
         const int j0 = min(max(c.x, 0), nJ_max - 1), j1 = min(max(c.y, 0), nJ_max - 1);
         const MemberGeom geo = member_geom(X, j0, j1);
-        const double N = member_axial(geo, mem.EA(mbase + m), sh, j0, j1);
+        const double N = member_axial(geo, mem.EA(mbase + m), u, j0, j1);
         const double g = N / geo.len;
         N_out[mbase + m] = N;
 #pragma unroll
@@ -82,16 +92,30 @@ __global__ __launch_bounds__(256) void trs_bk_members_kernel(
 }
 
 // ---- G = H Y --------------------------------------------------------------------------------------------------------
+struct ProductTables : EndLists {
+    double* tab;   // [nM_max][4]      n, g
+    double* ysh;   // [vc][3 nJ_max]   the vectors of this chunk in joint layout
+    int* far;      // [2 nM_max]       the joint at the far end of every list entry
+};
+
+template <class Arena>
+__host__ __device__ inline ProductTables product_layout(Arena& a, int nJ_max, int nM_max, int vc) {
+    ProductTables t;
+    t.tab = a.template take<double>((size_t)4 * nM_max);
+    t.ysh = a.template take<double>((size_t)vc * 3 * nJ_max);
+    trs_lds::take_end_lists(a, t, nJ_max, nM_max);
+    t.far = a.template take<int>(2, nM_max);
+    return t;
+}
+
 size_t product_lds(int nJ_max, int nM_max, int vc) {
-    const size_t bytes = ((size_t)4 * nM_max + (size_t)3 * nJ_max * vc) * sizeof(double) +
-                         ((size_t)2 * nJ_max + 1 + 4 * (size_t)nM_max) * sizeof(int);
-    return (bytes + 15) / 16 * 16;
+    return trs_lds::count([&](auto& a) { product_layout(a, nJ_max, nM_max, vc); });
 }
 
 // the vectors staged at once: the largest of 16, 8, 4, 2, 1 that fits the LDS, 0: none does
 int product_chunk(int nJ_max, int nM_max) {
     for (int vc = QB; vc >= 1; vc >>= 1)
-        if (product_lds(nJ_max, nM_max, vc) <= BK_LDS_BUDGET) return vc;
+        if (product_lds(nJ_max, nM_max, vc) <= TRS_LDS_BYTES) return vc;
     return 0;
 }
 
@@ -104,13 +128,10 @@ __global__ __launch_bounds__(256) void trs_bk_product_kernel(
     const int joints = min(max(nJ[b], 0), nJ_max), members = min(max(nM[b], 0), nM_max);
     const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
     const int n = min(max(n_free[b], 0), ld_f), npad = trs_round_up(n, TRS_NB);   // (ld_f is a multiple of TRS_NB)
-    double* tab = sh;                       // [nM_max][4] n, g
-    double* ysh = tab + 4 * (size_t)nM_max; // [vc][3 nJ_max] the vectors of this chunk in joint layout
-    EndLists t;
-    t.cnt = reinterpret_cast<int*>(ysh + (size_t)vc * ndof_max);
-    t.start = t.cnt + nJ_max;
-    t.ends = t.start + nJ_max + 1;
-    int* far = t.ends + 2 * nM_max;         // [2 nM_max] the joint at the far end of every list entry
+    trs_lds::Carve lds(sh);
+    const ProductTables t = product_layout(lds, nJ_max, nM_max, vc);
+    double *tab = t.tab, *ysh = t.ysh;
+    int* far = t.far;
     const size_t mbase = (size_t)b * nM_max;
     const TrsMembers mem = TrsMembers{ends_all, nullptr, nullptr, nullptr, nullptr, nullptr};   // (int32 end joints only)
     const int* fi = free_index + (size_t)b * ndof_max;
@@ -120,8 +141,7 @@ __global__ __launch_bounds__(256) void trs_bk_product_kernel(
         const int r = d < ndof ? fi[d] : -1;
         return r < n ? r : -1;
     };
-    auto in_truss = [joints](int j) { return (j >= 0) & (j < joints); };
-    build_end_lists(t, mem, mbase, joints, members, nJ_max, tid, in_truss);
+    build_end_lists(t, mem, mbase, joints, members, nJ_max, tid, InTruss{joints});
     order_by_neighbour(t, far, mem, mbase, joints, tid);
     for (int i = tid; i < 4 * members; i += 256) tab[i] = Mt[mbase * 4 + i];
     for (int i = tid; i < QB * (npad - n); i += 256) {
@@ -439,10 +459,8 @@ int bk_members_launch(int B, int nJ_max, int nM_max, const double* xyz, const Tr
         return (int)hipErrorInvalidValue;
     if (B == 0) return 0;
     if (!trs_bk_fits(nJ_max, nM_max)) return (int)hipErrorInvalidValue;
-    static const int lds_limit_set = (int)hipFuncSetAttribute(   // once per process, not per launch
-        reinterpret_cast<const void*>(trs_bk_members_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)lds_limit_set;
-    hipLaunchKernelGGL(trs_bk_members_kernel, dim3(B), dim3(256), (size_t)3 * nJ_max * sizeof(double), stream, xyz, mem,
+    trs_lds::raise_lds_once<trs_bk_members_kernel>();
+    hipLaunchKernelGGL(trs_bk_members_kernel, dim3(B), dim3(256), members_lds(nJ_max), stream, xyz, mem,
                        free_index, n_free, nJ, nM, nJ_max, nM_max, uf, ld_uf, theta, N, ends, Mt, W);
     return (int)hipGetLastError();
 }
@@ -455,7 +473,7 @@ int trs_bk_abi_version(void) { return TRS_BK_ABI_VERSION; }
 
 int trs_bk_fits(int nJ_max, int nM_max) {
     if (nJ_max < 0 || nM_max < 0 || nJ_max > 65535) return 0;
-    return (size_t)3 * nJ_max * sizeof(double) <= BK_LDS_BUDGET && product_chunk(nJ_max, nM_max) >= 1;
+    return members_lds(nJ_max) <= TRS_LDS_BYTES && product_chunk(nJ_max, nM_max) >= 1;
 }
 
 int trs_bk_members(int B, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* E, const double* A,
@@ -483,9 +501,7 @@ int trs_bk_product(int B, int nJ_max, int nM_max, const int32_t* ends, const dou
     if (B == 0) return 0;
     const int vc = nJ_max <= 65535 ? product_chunk(nJ_max, nM_max) : 0;
     if (vc < 1) return (int)hipErrorInvalidValue;
-    static const int lds_limit_set = (int)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(trs_bk_product_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)lds_limit_set;
+    trs_lds::raise_lds_once<trs_bk_product_kernel>();
     hipLaunchKernelGGL(trs_bk_product_kernel, dim3(B), dim3(256), product_lds(nJ_max, nM_max, vc), (hipStream_t)stream,
                        ends, Mt, free_index, n_free, nJ, nM, nJ_max, nM_max, Y, G, ld_f, vc);
     return (int)hipGetLastError();

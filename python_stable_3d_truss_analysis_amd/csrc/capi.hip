@@ -3,6 +3,7 @@
 #include <string.h>
 #include "../../include/trs_solver.h"
 #include "trs_common.h"
+#include "trs_lds.h"
 
 extern "C" {
 int trs_dofmap_launch(int, int, const uint8_t*, const int*, int*, int*, hipStream_t);
@@ -428,7 +429,7 @@ int trs_potrs_cases(int B, int L, const int32_t* n_free, int ld, int slab_rows, 
 }
 
 int trs_recover_cases_fits(int nJ_max, int nM_max) {
-    return nJ_max >= 0 && nM_max >= 0 && trs_recover_cases_lds(nJ_max, nM_max) <= 160 * 1024;
+    return nJ_max >= 0 && nM_max >= 0 && trs_recover_cases_lds(nJ_max, nM_max) <= TRS_LDS_BYTES;
 }
 
 int trs_recover_cases(int B, int L, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* E,
@@ -463,7 +464,7 @@ int trs_adjoint_grad_launch(int, int, int, int, const double*, const TrsMembers*
 size_t trs_adjoint_lds(int, int);
 
 int trs_adjoint_fits(int nJ_max, int nM_max) {
-    return nJ_max >= 0 && nM_max >= 0 && trs_adjoint_lds(nJ_max, nM_max) <= 160 * 1024;
+    return nJ_max >= 0 && nM_max >= 0 && trs_adjoint_lds(nJ_max, nM_max) <= TRS_LDS_BYTES;
 }
 
 int trs_adjoint_rhs(int B, int L, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* E,

@@ -18,7 +18,7 @@
 // than the ring holds works on its slice of F in global memory instead (same arithmetic, same bits).
 #include "../../include/trs_solver.h"
 #include "trs_common.h"
-#include "trs_recover.h"
+#include "trs_lds.h"
 
 namespace {
 
@@ -265,6 +265,18 @@ __global__ __launch_bounds__(64) void trs_potrs_cases_kernel(const int L, const 
 }
 
 // ---- recovery -------------------------------------------------------------------------------------------------------
+struct RecoverTables : EndLists {   // (the member-end lists of the constrained joints: trs_recover.h)
+    double* u;   // [3 nJ_max]  displacements of one case, device numbering
+};
+
+template <class Arena>
+__host__ __device__ inline RecoverTables recover_layout(Arena& a, int nJ_max, int nM_max) {
+    RecoverTables t;
+    t.u = a.template take<double>(3, nJ_max);
+    trs_lds::take_end_lists(a, t, nJ_max, nM_max);
+    return t;
+}
+
 // trs_recover's staged path (recover.hip) with the truss's tables built once and a loop over the cases: the member-end
 // lists of the constrained joints are counting-sorted once, then per case u is staged in LDS (device numbering),
 // N and the reactions are formed by the SAME functions (trs_recover.h) in the same order, and u / f_ext go out through
@@ -278,11 +290,9 @@ __global__ __launch_bounds__(256) void trs_recover_cases_kernel(
     const int b = blockIdx.x, tid = threadIdx.x;
     const int joints = nJ[b], members = nM[b];
     const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
-    double* u = sh;                                              // [ndof_max]
-    EndLists t;
-    t.cnt = reinterpret_cast<int*>(sh + ndof_max);               // [nJ_max]
-    t.start = t.cnt + nJ_max;                                    // [nJ_max + 1]
-    t.ends = t.start + nJ_max + 1;                               // [2 nM_max]
+    trs_lds::Carve lds(sh);
+    const RecoverTables t = recover_layout(lds, nJ_max, nM_max);
+    double* u = t.u;
     const int* fi = free_index + (size_t)b * ndof_max;
     const double* X = xyz + (size_t)b * ndof_max;
     const size_t mbase = (size_t)b * nM_max;
@@ -364,7 +374,7 @@ extern "C" int trs_potrs_cases_launch(int B, int L, const int* n_free, int ld, s
 }
 
 extern "C" size_t trs_recover_cases_lds(int nJ_max, int nM_max) {
-    return ((size_t)3 * nJ_max * sizeof(double) + ((size_t)2 * nJ_max + 1 + 2 * (size_t)nM_max) * sizeof(int) + 15) / 16 * 16;
+    return trs_lds::count([&](auto& a) { recover_layout(a, nJ_max, nM_max); });
 }
 
 extern "C" int trs_recover_cases_launch(int B, int L, int nJ_max, int nM_max, const double* xyz, const TrsMembers* members,
@@ -373,10 +383,8 @@ extern "C" int trs_recover_cases_launch(int B, int L, int nJ_max, int nM_max, co
                                         const int* joint_out, hipStream_t stream) {
     if (B <= 0 || L <= 0) return 0;
     const size_t lds = trs_recover_cases_lds(nJ_max, nM_max);
-    if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
-    static const int lds_limit_set = (int)hipFuncSetAttribute(   // once per process, not per launch
-        reinterpret_cast<const void*>(trs_recover_cases_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)lds_limit_set;
+    if (lds > TRS_LDS_BYTES) return (int)hipErrorInvalidValue;
+    trs_lds::raise_lds_once<trs_recover_cases_kernel>();
     hipLaunchKernelGGL(trs_recover_cases_kernel, dim3(B), dim3(256), lds, stream, L, xyz, *members, loads, free_index,
                        nJ, nM, nJ_max, nM_max, F, ld_f, u, f_ext, N, joint_out);
     return (int)hipGetLastError();

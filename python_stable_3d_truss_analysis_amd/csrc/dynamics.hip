@@ -21,13 +21,11 @@
 // and time point, latency- and geometry-bound, not memory-bound).
 #include "../../include/trs_dynamics.h"
 #include "trs_common.h"
-#include "trs_recover.h"
+#include "trs_lds.h"
 
 namespace {
 
 using namespace trs_rec;
-
-constexpr size_t DYN_LDS_BUDGET = 160 * 1024;   // a CU's LDS
 
 // the scheme's constants (include/trs_dynamics.h), formed once on the host in plain double arithmetic
 struct DynCoef {
@@ -63,27 +61,20 @@ struct DynTables : EndLists {   // (the member-end lists: beta_R > 0 only)
     double* pm;   // [nM_max]    s_m of that case (beta_R > 0 only)
 };
 
-__device__ __forceinline__ DynTables dyn_tables(double* sh, int nJ_max, int nM_max) {
-    DynTables t;
-    t.v = sh;
-    t.pm = sh + 3 * nJ_max;
-    t.cnt = reinterpret_cast<int*>(t.pm + nM_max);
-    t.start = t.cnt + nJ_max;
-    t.ends = t.start + nJ_max + 1;
+// (an undamped launch allocates v alone; the kernel carves with damped = true and touches nothing behind v then)
+template <class Arena>
+__host__ __device__ inline DynTables layout(Arena& a, int nJ_max, int nM_max, bool damped) {
+    DynTables t = {};
+    t.v = a.template take<double>(3, nJ_max);
+    if (!damped) return t;
+    t.pm = a.template take<double>(nM_max);
+    trs_lds::take_end_lists(a, t, nJ_max, nM_max);
     return t;
 }
 
 size_t dyn_lds(int nJ_max, int nM_max, int damped) {
-    size_t bytes = (size_t)3 * nJ_max * sizeof(double);
-    if (damped) bytes += (size_t)nM_max * sizeof(double) + ((size_t)2 * nJ_max + 1 + 2 * (size_t)nM_max) * sizeof(int);
-    return (bytes + 15) / 16 * 16;
+    return trs_lds::count([&](auto& a) { layout(a, nJ_max, nM_max, damped != 0); });
 }
-
-// the joints whose end lists are built: those of the truss (an end-joint id outside them is left out of the sums)
-struct InTruss {
-    int joints;
-    __device__ __forceinline__ bool operator()(int j) const { return (j >= 0) & (j < joints); }
-};
 
 // k c . (v_j1 - v_j0) of member mm for a joint-layout vector v, the end-joint ids clamped to the arrays
 __device__ __forceinline__ double member_force(const TrsMembers& mem, const size_t mm, const double* __restrict__ X,
@@ -141,7 +132,8 @@ __global__ __launch_bounds__(256) void trs_dyn_step_kernel(
     const int joints = min(max(nJ[b], 0), nJ_max), members = min(max(nM[b], 0), nM_max);
     const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
     const int n = min(max(n_free[b], 0), ld_f), npad = min(trs_round_up(n, TRS_NB), ld_f);
-    const DynTables t = dyn_tables(sh, nJ_max, nM_max);
+    trs_lds::Carve lds(sh);
+    const DynTables t = layout(lds, nJ_max, nM_max, true);
     double* ush = t.v;
     const int* fi = free_index + (size_t)b * ndof_max;
     const double* X = xyz + (size_t)b * ndof_max;
@@ -314,9 +306,7 @@ int dyn_step_launch(int B, int L, int nJ_max, int nM_max, const double* xyz, con
     if (B == 0 || L == 0) return 0;
     const int damped = damp_stiff > 0.0;
     if (!trs_dyn_fits(nJ_max, nM_max, damped)) return (int)hipErrorInvalidValue;
-    static const int lds_limit_set = (int)hipFuncSetAttribute(   // once per process, not per launch
-        reinterpret_cast<const void*>(trs_dyn_step_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)lds_limit_set;
+    trs_lds::raise_lds_once<trs_dyn_step_kernel>();
     hipLaunchKernelGGL(trs_dyn_step_kernel, dim3(B), dim3(256), dyn_lds(nJ_max, nM_max, damped), stream, L, xyz, mem,
                        free_index, n_free, nJ, nM, nJ_max, nM_max, Mf, Pr, scale, ag, T1, n, first,
                        dyn_coef(dt, beta, gamma, damp_mass, damp_stiff), F, U, V, Acc, ld_f, u_peak, u_step, N_max,
@@ -331,7 +321,7 @@ extern "C" {
 int trs_dyn_abi_version(void) { return TRS_DYN_ABI_VERSION; }
 
 int trs_dyn_fits(int nJ_max, int nM_max, int damped) {
-    return nJ_max >= 0 && nM_max >= 0 && dyn_lds(nJ_max, nM_max, damped != 0) <= DYN_LDS_BUDGET;
+    return nJ_max >= 0 && nM_max >= 0 && dyn_lds(nJ_max, nM_max, damped != 0) <= TRS_LDS_BYTES;
 }
 
 int trs_dyn_shift(int B, const int32_t* n_free, int ld, int slab_rows, double* S, const double* Mf, int ld_f,

@@ -20,7 +20,7 @@
 // the one that trs_recover_cases and the adjoint kernels use.
 #include "../../include/trs_effects.h"
 #include "trs_common.h"
-#include "trs_recover.h"
+#include "trs_lds.h"
 
 namespace {
 
@@ -32,20 +32,16 @@ struct EffTables : EndLists {  // (the member-end lists of EVERY joint: trs_reco
     double* pm;   // [nM_max]    one double per member: s_m or N_m of that case
 };
 
-__device__ __forceinline__ EffTables eff_tables(double* sh, int nJ_max, int nM_max) {
+template <class Arena>
+__host__ __device__ inline EffTables layout(Arena& a, int nJ_max, int nM_max) {
     EffTables t;
-    t.v = sh;
-    t.pm = sh + 3 * nJ_max;
-    t.cnt = reinterpret_cast<int*>(t.pm + nM_max);
-    t.start = t.cnt + nJ_max;
-    t.ends = t.start + nJ_max + 1;
+    t.v = a.template take<double>(3, nJ_max);
+    t.pm = a.template take<double>(nM_max);
+    trs_lds::take_end_lists(a, t, nJ_max, nM_max);
     return t;
 }
 
-size_t effects_lds(int nJ_max, int nM_max) {
-    return (((size_t)3 * nJ_max + (size_t)nM_max) * sizeof(double) +
-            ((size_t)2 * nJ_max + 1 + 2 * (size_t)nM_max) * sizeof(int) + 15) / 16 * 16;
-}
+size_t effects_lds(int nJ_max, int nM_max) { return trs_lds::count([&](auto& a) { layout(a, nJ_max, nM_max); }); }
 
 // Half the weight of member mm on one of its end joints, added to the joint's running body load: the product in
 // Member.weight's order (trs_modes_mass forms the same half), ONE function with explicit fused multiply-adds for both
@@ -68,7 +64,8 @@ __global__ __launch_bounds__(256) void trs_effects_rhs_kernel(
     const int b = blockIdx.x, tid = threadIdx.x;
     const int joints = nJ[b], members = nM[b];
     const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
-    const EffTables t = eff_tables(sh, nJ_max, nM_max);
+    trs_lds::Carve lds(sh);
+    const EffTables t = layout(lds, nJ_max, nM_max);
     double* ub = t.v;   // ubar at the constrained DOFs, zero elsewhere, device numbering
     double* s = t.pm;   // member term
     const int* fi = free_index + (size_t)b * ndof_max;
@@ -149,7 +146,8 @@ __global__ __launch_bounds__(256) void trs_effects_recover_kernel(
     const int b = blockIdx.x, tid = threadIdx.x;
     const int joints = nJ[b], members = nM[b];
     const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
-    const EffTables t = eff_tables(sh, nJ_max, nM_max);
+    trs_lds::Carve lds(sh);
+    const EffTables t = layout(lds, nJ_max, nM_max);
     double* u = t.v;    // displacements of one case, device numbering: solved at the free DOFs, ubar at the others
     double* Nm = t.pm;  // axial forces of that case
     const int* fi = free_index + (size_t)b * ndof_max;
@@ -224,9 +222,7 @@ int effects_rhs_launch(int B, int L, int nJ_max, int nM_max, const double* xyz, 
     if (B == 0 || L == 0) return 0;
     if (!trs_effects_fits(nJ_max, nM_max)) return (int)hipErrorInvalidValue;
     if (accel != nullptr && mem.tidx == nullptr && mem.rho == nullptr) return (int)hipErrorInvalidValue;
-    static const int lds_limit_set = (int)hipFuncSetAttribute(   // once per process, not per launch
-        reinterpret_cast<const void*>(trs_effects_rhs_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)lds_limit_set;
+    trs_lds::raise_lds_once<trs_effects_rhs_kernel>();
     hipLaunchKernelGGL(trs_effects_rhs_kernel, dim3(B), dim3(256), effects_lds(nJ_max, nM_max), stream, L, xyz, mem,
                        loads, eps0, ubar, accel, free_index, n_free, nJ, nM, nJ_max, nM_max, joint_in, F, ld_f);
     return (int)hipGetLastError();
@@ -240,10 +236,7 @@ int effects_recover_launch(int B, int L, int nJ_max, int nM_max, const double* x
     if (B == 0 || L == 0) return 0;
     if (!trs_effects_fits(nJ_max, nM_max)) return (int)hipErrorInvalidValue;
     if (accel != nullptr && mem.tidx == nullptr && mem.rho == nullptr) return (int)hipErrorInvalidValue;
-    static const int lds_limit_set = (int)hipFuncSetAttribute(   // once per process, not per launch
-        reinterpret_cast<const void*>(trs_effects_recover_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-        160 * 1024);
-    (void)lds_limit_set;
+    trs_lds::raise_lds_once<trs_effects_recover_kernel>();
     hipLaunchKernelGGL(trs_effects_recover_kernel, dim3(B), dim3(256), effects_lds(nJ_max, nM_max), stream, L, xyz, mem,
                        loads, eps0, ubar, accel, free_index, nJ, nM, nJ_max, nM_max, F, ld_f, u, f_ext, N, body,
                        joint_out);
@@ -257,7 +250,7 @@ extern "C" {
 int trs_effects_abi_version(void) { return TRS_EFFECTS_ABI_VERSION; }
 
 int trs_effects_fits(int nJ_max, int nM_max) {
-    return nJ_max >= 0 && nM_max >= 0 && effects_lds(nJ_max, nM_max) <= 160 * 1024;
+    return nJ_max >= 0 && nM_max >= 0 && effects_lds(nJ_max, nM_max) <= TRS_LDS_BYTES;
 }
 
 int trs_effects_rhs(int B, int L, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* E,

@@ -29,18 +29,11 @@ using namespace trs_rec;
 using trs_col::wave_extreme_index;
 
 constexpr int WAVES = 4;                    // waves per work-group; trs_influence_fits' rule counts their eta vectors
-using trs_col::LDS_BUDGET;                  // (behind trs_influence_fits and the launch too)
 #ifndef TRS_INFLUENCE_SLICE
 #define TRS_INFLUENCE_SLICE 16              // members per work-group
 #endif
 
-// LDS of the apply kernel (the rule of trs_influence_fits)
-size_t influence_lds(int nJ_max, int P_max, int A) {
-    const size_t doubles = (size_t)(4 + WAVES) * P_max + (size_t)2 * A;
-    const size_t ints = (size_t)4 * P_max + (size_t)nJ_max;
-    return (doubles * sizeof(double) + ints * sizeof(int) + 15) / 16 * 16;
-}
-
+// LDS tables of the apply kernel
 struct InfluenceTables {
     double* s;        // [P_max]      arc length of path joint p
     double* dw;       // [3 P_max]    d's component on axis a of path joint p
@@ -51,17 +44,22 @@ struct InfluenceTables {
     int* inv;         // [nJ_max]     caller's joint id -> solver's
 };
 
-__device__ __forceinline__ InfluenceTables influence_tables(double* sh, int nJ_max, int P_max, int A) {
+template <class Arena>
+__host__ __device__ inline InfluenceTables layout(Arena& a, int nJ_max, int P_max, int A) {
     InfluenceTables t;
-    t.s = sh;
-    t.dw = t.s + P_max;
-    t.eta = t.dw + (size_t)3 * P_max;
-    t.tw = t.eta + (size_t)WAVES * P_max;
-    t.to = t.tw + A;
-    t.pj = reinterpret_cast<int*>(t.to + A);
-    t.di = t.pj + P_max;
-    t.inv = t.di + (size_t)3 * P_max;
+    t.s = a.template take<double>((size_t)P_max);
+    t.dw = a.template take<double>((size_t)3 * P_max);
+    t.eta = a.template take<double>((size_t)WAVES * P_max);
+    t.tw = a.template take<double>((size_t)A);
+    t.to = a.template take<double>((size_t)A);
+    t.pj = a.template take<int>((size_t)P_max);
+    t.di = a.template take<int>((size_t)3 * P_max);
+    t.inv = a.template take<int>((size_t)nJ_max);
     return t;
+}
+
+size_t influence_lds(int nJ_max, int P_max, int A) {
+    return trs_lds::count([&](auto& a) { layout(a, nJ_max, P_max, A); });
 }
 
 // eta_m at arc position t of a path of P >= 1 joints (s: its arc lengths, S = s[P - 1], eps = 1e-12 S), 0 off the path
@@ -98,7 +96,8 @@ __global__ __launch_bounds__(64 * WAVES) void trs_influence_apply_kernel(
     if (first >= last) return;
     const int joints = nJ[b], members = nM[b];
     const int P = joints > 0 ? max(0, min(path_len[b], P_max)) : 0;
-    const InfluenceTables t = influence_tables(sh, nJ_max, P_max, A);
+    trs_lds::Carve lds(sh);
+    const InfluenceTables t = layout(lds, nJ_max, P_max, A);
     const size_t mbase = (size_t)b * nM_max;
     const double* X = xyz + (size_t)b * 3 * nJ_max;
     const int* fi = free_index + (size_t)b * 3 * nJ_max;
@@ -251,10 +250,7 @@ int influence_launch(int B, int e0, int C, int nJ_max, int nM_max, int P_max, in
     if (B == 0 || C == 0 || e0 >= nM_max) return 0;
     if (!trs_influence_fits(nJ_max, P_max, A)) return (int)hipErrorInvalidValue;
     if ((long long)P_max * A > INT_MAX - 64) return (int)hipErrorInvalidValue;   // (the candidate index is an int)
-    static const int lds_limit_set = (int)hipFuncSetAttribute(   // once per process, not per launch
-        reinterpret_cast<const void*>(trs_influence_apply_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-        (int)LDS_BUDGET);
-    (void)lds_limit_set;
+    trs_lds::raise_lds_once<trs_influence_apply_kernel>();
     const int slices = (C + TRS_INFLUENCE_SLICE - 1) / TRS_INFLUENCE_SLICE;
     hipLaunchKernelGGL(trs_influence_apply_kernel, dim3((unsigned)slices * (unsigned)B), dim3(64 * WAVES),
                        influence_lds(nJ_max, P_max, A), stream, e0, C, TRS_INFLUENCE_SLICE, P_max, A, xyz, mem,
@@ -270,7 +266,7 @@ extern "C" {
 int trs_influence_abi_version(void) { return TRS_INFLUENCE_ABI_VERSION; }
 
 int trs_influence_fits(int nJ_max, int P_max, int A) {
-    return nJ_max >= 0 && P_max >= 0 && A >= 1 && influence_lds(nJ_max, P_max, A) <= LDS_BUDGET;
+    return nJ_max >= 0 && P_max >= 0 && A >= 1 && influence_lds(nJ_max, P_max, A) <= TRS_LDS_BYTES;
 }
 
 int trs_influence_apply(int B, int e0, int C, int nJ_max, int nM_max, int P_max, int A, const double* xyz,

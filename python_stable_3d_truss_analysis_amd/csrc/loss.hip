@@ -63,7 +63,8 @@ __global__ __launch_bounds__(64 * WAVES) void trs_loss_apply_kernel(
     // trimmed to the arrays, so that no table entry and no output lies outside them whatever nJ[b] and nM[b] hold
     const int joints = min(max(nJ[b], 0), nJ_max), members = min(max(nM[b], 0), nM_max);
     const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
-    const Tables t = tables(sh, nJ_max, nM_max, g, WAVES, 0);
+    trs_lds::Carve carve(sh);
+    const Tables t = layout(carve, nJ_max, nM_max, g, WAVES, 0);
     const size_t mbase = (size_t)b * nM_max;
     double* zw = t.z + (size_t)wave * ndof_max;
     const double inf = __builtin_huge_val(), nan = __builtin_nan("");
@@ -198,9 +199,7 @@ int loss_apply_launch(int B, int L, int e0, int C, int nJ_max, int nM_max, const
     if (!trs_loss_fits(nJ_max, nM_max, L)) return (int)hipErrorInvalidValue;
     const int g = pass(nJ_max, nM_max, L, WAVES, 0);
     if (g <= 0) return (int)hipErrorInvalidValue;   // (the kernel's pass loop steps by g)
-    static const int lds_limit_set = (int)hipFuncSetAttribute(   // once per process, not per launch
-        reinterpret_cast<const void*>(trs_loss_apply_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET);
-    (void)lds_limit_set;
+    trs_lds::raise_lds_once<trs_loss_apply_kernel>();
     const int slices = (C + TRS_LOSS_SLICE - 1) / TRS_LOSS_SLICE;
     hipLaunchKernelGGL(trs_loss_apply_kernel, dim3((unsigned)slices * (unsigned)B), dim3(64 * WAVES),
                        lds(nJ_max, nM_max, g, WAVES, 0), stream, L, g, e0, C, TRS_LOSS_SLICE, xyz, mem, free_index, nJ, nM,

@@ -21,15 +21,13 @@
 #include "../../include/trs_modegrad.h"
 #include "../../include/trs_modes.h"
 #include "trs_common.h"
-#include "trs_recover.h"
+#include "trs_lds.h"
 
 namespace {
 
 using namespace trs_rec;
 
 static_assert(TRS_MG_BLOCK == TRS_MODES_BLOCK, "the block of trs_modegrad.h is the one of trs_modes.h");
-
-constexpr size_t MG_LDS_BUDGET = 160 * 1024;   // a CU's LDS
 
 // LDS tables of one truss
 struct MgTables : EndLists {   // (the member-end lists of EVERY joint: trs_recover.h)
@@ -41,35 +39,23 @@ struct MgTables : EndLists {   // (the member-end lists of EVERY joint: trs_reco
     int2* mends;               // [nM_max]  end joints, clamped
 };
 
-__host__ __device__ inline size_t mg_lds(int nJ_max, int nM_max, int pc) {
-    const size_t doubles = (size_t)6 * nM_max + (size_t)3 * nJ_max * pc;
-    const size_t ints = (size_t)2 * nM_max + (size_t)2 * nJ_max + 1 + (size_t)2 * nM_max;
-    return (doubles * sizeof(double) + ints * sizeof(int) + 15) / 16 * 16;
-}
-
-__device__ __forceinline__ MgTables mg_tables(double* sh, int nJ_max, int nM_max, int pc) {
+template <class Arena>
+__host__ __device__ inline MgTables layout(Arena& a, int nJ_max, int nM_max, int pc) {
     MgTables t;
-    t.cx = sh;
-    t.cy = t.cx + nM_max;
-    t.cz = t.cy + nM_max;
-    t.len = t.cz + nM_max;
-    t.kl = t.len + nM_max;
-    t.mg = t.kl + nM_max;
-    t.phi = t.mg + nM_max;
-    t.mends = reinterpret_cast<int2*>(t.phi + (size_t)pc * 3 * nJ_max);
-    t.cnt = reinterpret_cast<int*>(t.mends + nM_max);
-    t.start = t.cnt + nJ_max;
-    t.ends = t.start + nJ_max + 1;
+    t.cx = a.template take<double>(nM_max);
+    t.cy = a.template take<double>(nM_max);
+    t.cz = a.template take<double>(nM_max);
+    t.len = a.template take<double>(nM_max);
+    t.kl = a.template take<double>(nM_max);
+    t.mg = a.template take<double>(nM_max);
+    t.phi = a.template take<double>((size_t)pc * 3 * nJ_max);
+    t.mends = a.template take<int2>(nM_max);
+    trs_lds::take_end_lists(a, t, nJ_max, nM_max);
     return t;
 }
 
-struct InsideTruss {   // the joints that get a list: an end joint outside the truss would index LDS outside the lists
-    int joints;
-    __device__ __forceinline__ bool operator()(int j) const { return (j >= 0) & (j < joints); }
-};
-
-__device__ __forceinline__ double member_modulus(const TrsMembers& mem, size_t mm) {
-    return mem.table() ? mem.types[3 * (int)mem.tidx[mm] + 1] : mem.E[mm];
+size_t mg_lds(int nJ_max, int nM_max, int pc) {
+    return trs_lds::count([&](auto& a) { layout(a, nJ_max, nM_max, pc); });
 }
 
 // What the two loops take from phi for member (c0, c1): Dphi, s = c . Dphi and h = |phi_j0|^2 + |phi_j1|^2.  ONE
@@ -106,7 +92,8 @@ __global__ __launch_bounds__(256) void trs_mg_grad_kernel(
     const int n_modes = min(p, max(n_mass[b], 0));
     const bool weighted = w_all != nullptr;
     const int R = weighted ? 1 : p;
-    const MgTables t = mg_tables(sh, nJ_max, nM_max, pc);
+    trs_lds::Carve lds(sh);
+    const MgTables t = layout(lds, nJ_max, nM_max, pc);
     const int* fi = free_index + (size_t)b * ndof_max;
     const double* Xyz = xyz + (size_t)b * ndof_max;
     const size_t mbase = (size_t)b * nM_max;
@@ -152,7 +139,7 @@ __global__ __launch_bounds__(256) void trs_mg_grad_kernel(
         t.kl[m] = live ? mem.EA(mbase + m) / g.len / g.len : 0.0;
         t.mg[m] = live ? mass_scale * (0.5 * (mem.area(mbase + m) * mem.density(mbase + m))) : 0.0;
     }
-    if (gxyz != nullptr) build_end_lists(t, mem, mbase, joints, members, nJ_max, tid, InsideTruss{joints});
+    if (gxyz != nullptr) build_end_lists(t, mem, mbase, joints, members, nJ_max, tid, InTruss{joints});
 
     for (int k0 = 0; k0 < n_modes; k0 += pc) {
         const int kc = min(pc, n_modes - k0);
@@ -174,7 +161,7 @@ __global__ __launch_bounds__(256) void trs_mg_grad_kernel(
                     c = t.mends[m];
                     cx = t.cx[m], cy = t.cy[m], cz = t.cz[m];
                     const double len = t.len[m], a = mem.area(mbase + m), rho = mem.density(mbase + m);
-                    ke = member_modulus(mem, mbase + m) / len;
+                    ke = modulus(mem, mbase + m) / len;
                     ka = a / len;
                     mh = mass_scale * (0.5 * (len * rho));
                     mr = mass_scale * (0.5 * (a * len));
@@ -279,9 +266,9 @@ __global__ __launch_bounds__(256) void trs_mg_grad_kernel(
 // row is carried in mode order whatever a pass holds, so the choice changes no bit.
 int mg_pass(int nJ_max, int nM_max, int p) {
     int pc = p;
-    while (pc > 0 && mg_lds(nJ_max, nM_max, pc) > MG_LDS_BUDGET) --pc;
+    while (pc > 0 && mg_lds(nJ_max, nM_max, pc) > TRS_LDS_BYTES) --pc;
     int half = pc;
-    while (half > 0 && mg_lds(nJ_max, nM_max, half) > MG_LDS_BUDGET / 2) --half;
+    while (half > 0 && mg_lds(nJ_max, nM_max, half) > TRS_LDS_BYTES / 2) --half;
     return half >= 2 ? half : pc;
 }
 
@@ -294,10 +281,7 @@ int mg_launch(int B, int nJ_max, int nM_max, const double* xyz, const TrsMembers
         return (int)hipErrorInvalidValue;
     if (gA == nullptr && gE == nullptr && grho == nullptr && gxyz == nullptr && gmass == nullptr) return 0;
     const int pc = mg_pass(nJ_max, nM_max, p);
-    static const int lds_limit_set = (int)hipFuncSetAttribute(   // once per process, not per launch
-        reinterpret_cast<const void*>(trs_mg_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-        (int)MG_LDS_BUDGET);
-    (void)lds_limit_set;
+    trs_lds::raise_lds_once<trs_mg_grad_kernel>();
     hipLaunchKernelGGL(trs_mg_grad_kernel, dim3(B), dim3(256), mg_lds(nJ_max, nM_max, pc), stream, xyz, mem, free_index,
                        n_free, nJ, nM, joint_out, nJ_max, nM_max, X, ld_f, lam, n_mass, p, pc, mass_scale, w, gA, gE, grho,
                        gxyz, gmass);
@@ -311,7 +295,7 @@ extern "C" {
 int trs_mg_abi_version(void) { return TRS_MG_ABI_VERSION; }
 
 int trs_mg_fits(int nJ_max, int nM_max, int p) {
-    return nJ_max >= 0 && nM_max >= 0 && p >= 1 && p <= TRS_MG_MAX_MODES && mg_lds(nJ_max, nM_max, 1) <= MG_LDS_BUDGET;
+    return nJ_max >= 0 && nM_max >= 0 && p >= 1 && p <= TRS_MG_MAX_MODES && mg_lds(nJ_max, nM_max, 1) <= TRS_LDS_BYTES;
 }
 
 int trs_mg_grad(int B, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* E, const double* A,

@@ -21,7 +21,7 @@
 //           four runs of 128 contiguous bytes.  On a checking step X Q is formed the same way for the residuals.
 #include "../../include/trs_modes.h"
 #include "trs_common.h"
-#include "trs_recover.h"
+#include "trs_lds.h"
 #include "trs_ritz.h"
 
 namespace {
@@ -34,6 +34,21 @@ static_assert(QB == TRS_MODES_BLOCK, "the block of trs_modes.h is the one of trs
 // ---- lumped mass ----------------------------------------------------------------------------------------------------
 // One work-group per truss.  Half the mass of every member and its end joints go to LDS, then one thread per joint
 // walks the members in id order and sums the halves that end at its joint.
+struct MassTables {
+    double* half;   // [nM_max]  half the mass of every member
+    int2* ends;     // [nM_max]  its end joints
+    int* count;     // [1]       DOFs with mass (no static LDS beside the dynamic part)
+};
+
+template <class Arena>
+__host__ __device__ inline MassTables mass_layout(Arena& a, int nM_max) {
+    MassTables t;
+    t.half = a.template take<double>(nM_max);
+    t.ends = a.template take<int2>(nM_max);
+    t.count = a.template take<int>(1);
+    return t;
+}
+
 __global__ __launch_bounds__(256) void trs_modes_mass_kernel(
     const double* __restrict__ xyz, const TrsMembers mem, const double* __restrict__ joint_mass,
     const int* __restrict__ joint_in, const double mass_scale, const int* __restrict__ free_index,
@@ -42,9 +57,11 @@ __global__ __launch_bounds__(256) void trs_modes_mass_kernel(
     extern __shared__ double sh[];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int joints = nJ[b], members = nM[b];
-    double* half = sh;                                        // [nM_max]
-    int2* ends = reinterpret_cast<int2*>(sh + nM_max);        // [nM_max]
-    int& count = *reinterpret_cast<int*>(ends + nM_max);      // DOFs with mass (no static LDS beside the dynamic part)
+    trs_lds::Carve lds(sh);
+    const MassTables t = mass_layout(lds, nM_max);
+    double* half = t.half;
+    int2* ends = t.ends;
+    int& count = *t.count;
     const int* fi = free_index + (size_t)b * 3 * nJ_max;
     const double* X = xyz + (size_t)b * 3 * nJ_max;
     const size_t mbase = (size_t)b * nM_max;
@@ -311,16 +328,14 @@ __global__ __launch_bounds__(256) void trs_modes_shapes_kernel(const int p, cons
     }
 }
 
-size_t modes_mass_lds(int nM_max) { return (size_t)nM_max * (sizeof(double) + sizeof(int2)) + 16; }
+size_t modes_mass_lds(int nM_max) { return trs_lds::count([&](auto& a) { mass_layout(a, nM_max); }); }
 
 int modes_mass_launch(int B, int nJ_max, int nM_max, const double* xyz, const TrsMembers& mem, const double* joint_mass,
                       const int* joint_in, double mass_scale, const int* free_index, const int* n_free, const int* nJ,
                       const int* nM, double* Mf, int ld_f, int* n_mass, hipStream_t stream) {
     if (B <= 0) return 0;
     if (!trs_modes_fits(nJ_max, nM_max)) return (int)hipErrorInvalidValue;
-    static const int lds_limit_set = (int)hipFuncSetAttribute(   // once per process, not per launch
-        reinterpret_cast<const void*>(trs_modes_mass_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)lds_limit_set;
+    trs_lds::raise_lds_once<trs_modes_mass_kernel>();
     hipLaunchKernelGGL(trs_modes_mass_kernel, dim3(B), dim3(256), modes_mass_lds(nM_max), stream, xyz, mem, joint_mass,
                        joint_in, mass_scale, free_index, n_free, nJ, nM, nJ_max, nM_max, Mf, ld_f, n_mass);
     return (int)hipGetLastError();
@@ -333,7 +348,7 @@ extern "C" {
 int trs_modes_abi_version(void) { return TRS_MODES_ABI_VERSION; }
 
 int trs_modes_fits(int nJ_max, int nM_max) {
-    return nJ_max >= 0 && nM_max >= 0 && modes_mass_lds(nM_max) <= 160 * 1024;
+    return nJ_max >= 0 && nM_max >= 0 && modes_mass_lds(nM_max) <= TRS_LDS_BYTES;
 }
 
 int trs_modes_mass(int B, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* A,

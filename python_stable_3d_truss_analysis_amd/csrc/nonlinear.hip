@@ -23,14 +23,13 @@
 #include "../../include/trs_nonlinear.h"
 #include "../../include/trs_solver.h"
 #include "trs_common.h"
-#include "trs_recover.h"
+#include "trs_lds.h"
 
 namespace {
 
 using namespace trs_rec;
 
-constexpr size_t NL_LDS_BUDGET = 160 * 1024;   // a CU's LDS
-constexpr int NL_W = 6;                        // doubles per member of the table W
+constexpr int NL_W = 6;   // doubles per member of the table W
 
 // LDS tables of the state kernel
 struct StateTables : EndLists {
@@ -41,37 +40,42 @@ struct StateTables : EndLists {
     int* oth;     // [2 nM_max]  the far joint of every list entry
 };
 
-__device__ __forceinline__ StateTables state_tables(double* sh, int nJ_max, int nM_max) {
+template <class Arena>
+__host__ __device__ inline StateTables state_layout(Arena& a, int nJ_max, int nM_max) {
     StateTables t;
-    t.red = sh;
-    t.v = sh + 4;
-    t.pm = t.v + 3 * nJ_max;
-    t.pn = t.pm + nM_max;
-    t.cnt = reinterpret_cast<int*>(t.pn + 3 * nM_max);
-    t.start = t.cnt + nJ_max;
-    t.ends = t.start + nJ_max + 1;
-    t.oth = t.ends + 2 * nM_max;
+    t.red = a.template take<double>(4);
+    t.v = a.template take<double>((size_t)3 * nJ_max);
+    t.pm = a.template take<double>(nM_max);
+    t.pn = a.template take<double>((size_t)3 * nM_max);
+    trs_lds::take_end_lists(a, t, nJ_max, nM_max);
+    t.oth = a.template take<int>((size_t)2 * nM_max);
     return t;
 }
 
-size_t state_lds(int nJ_max, int nM_max) {
-    const size_t bytes = ((size_t)4 + 3 * (size_t)nJ_max + 4 * (size_t)nM_max) * sizeof(double) +
-                         ((size_t)2 * nJ_max + 1 + 4 * (size_t)nM_max) * sizeof(int);
-    return (bytes + 15) / 16 * 16;
-}
-
-// LDS tables of the tangent kernel: the joints' own delta blocks (6 doubles each) | end lists | other joint of every list
-// entry | free_index | DOF of a reduced row
-size_t tangent_lds(int nJ_max, int nM_max, int slab_rows) {
-    const size_t ints = (size_t)2 * nJ_max + 1 + 4 * (size_t)nM_max + 3 * (size_t)nJ_max + (size_t)slab_rows;
-    return ((size_t)6 * nJ_max * sizeof(double) + ints * sizeof(int) + 15) / 16 * 16;
-}
-
-// the joints whose end lists are built: those of the truss (an end-joint id outside them is left out of the sums)
-struct InTruss {
-    int joints;
-    __device__ __forceinline__ bool operator()(int j) const { return (j >= 0) & (j < joints); }
+// LDS tables of the tangent kernel
+struct TangentTables : EndLists {
+    double* own;   // [nJ_max][6]   the sum of +delta_m over a joint's member ends: xx xy xz yy yz zz
+    int* oth;      // [2 nM_max]    the joint at the far end of every list entry
+    int* fi;       // [3 nJ_max]    reduced row per DOF, -1: none
+    int* rowdof;   // [slab_rows]   DOF of a reduced row, -1: none
 };
+
+template <class Arena>
+__host__ __device__ inline TangentTables tangent_layout(Arena& a, int nJ_max, int nM_max, int slab_rows) {
+    TangentTables t;
+    t.own = a.template take<double>(6, nJ_max);
+    trs_lds::take_end_lists(a, t, nJ_max, nM_max);
+    t.oth = a.template take<int>(2, nM_max);
+    t.fi = a.template take<int>(3, nJ_max);
+    t.rowdof = a.template take<int>(slab_rows);
+    return t;
+}
+
+size_t state_lds(int nJ_max, int nM_max) { return trs_lds::count([&](auto& a) { state_layout(a, nJ_max, nM_max); }); }
+
+size_t tangent_lds(int nJ_max, int nM_max, int slab_rows) {
+    return trs_lds::count([&](auto& a) { tangent_layout(a, nJ_max, nM_max, slab_rows); });
+}
 
 // a maximum that keeps a NaN of either side (a NaN residual must never pass the convergence test)
 __device__ __forceinline__ double nan_max(const double a, const double b) { return (a > b || a != a) ? a : b; }
@@ -98,7 +102,8 @@ __global__ __launch_bounds__(256) void trs_nl_state_kernel(
     const int joints = min(max(nJ[b], 0), nJ_max), members = min(max(nM[b], 0), nM_max);
     const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
     const int n = min(max(n_free[b], 0), ld_f);
-    const StateTables t = state_tables(sh, nJ_max, nM_max);
+    trs_lds::Carve lds(sh);
+    const StateTables t = state_layout(lds, nJ_max, nM_max);
     double* ush = t.v;
     const int* fi = free_index + (size_t)b * ndof_max;
     const double* X = xyz + (size_t)b * ndof_max;
@@ -230,14 +235,10 @@ __global__ __launch_bounds__(256) void trs_nl_tangent_kernel(
     const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
     const int n = min(max(n_free[b], 0), slab_rows), npad = min(trs_round_up(n, TRS_NB), slab_rows);
     const int nch = npad / 16;
-    double* own = sh;   // [nJ_max][6] the sum of +delta_m over a joint's member ends: xx xy xz yy yz zz
-    EndLists t;
-    t.cnt = reinterpret_cast<int*>(sh + 6 * nJ_max);
-    t.start = t.cnt + nJ_max;
-    t.ends = t.start + nJ_max + 1;
-    int* oth = t.ends + 2 * nM_max;   // [2 nM_max] the joint at the far end of every list entry
-    int* fi = oth + 2 * nM_max;       // [3 nJ_max] reduced row per DOF, -1: none
-    int* rowdof = fi + ndof_max;      // [slab_rows] DOF of a reduced row, -1: none
+    trs_lds::Carve lds(sh);
+    const TangentTables t = tangent_layout(lds, nJ_max, nM_max, slab_rows);
+    double* own = t.own;
+    int *oth = t.oth, *fi = t.fi, *rowdof = t.rowdof;
     const size_t mbase = (size_t)b * nM_max;
     const int* fig = free_index + (size_t)b * ndof_max;
     for (int c = tid; c < slab_rows; c += 256) rowdof[c] = -1;
@@ -380,9 +381,7 @@ int nl_state_launch(int B, int nJ_max, int nM_max, const double* xyz, const TrsM
     if (last && (!u || !N || !f_ext || !iters || !status || !residual)) return (int)hipErrorInvalidValue;
     if (B == 0) return 0;
     if (!trs_nl_fits(nJ_max, nM_max)) return (int)hipErrorInvalidValue;
-    static const int lds_limit_set = (int)hipFuncSetAttribute(   // once per process, not per launch
-        reinterpret_cast<const void*>(trs_nl_state_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)lds_limit_set;
+    trs_lds::raise_lds_once<trs_nl_state_kernel>();
     hipLaunchKernelGGL(trs_nl_state_kernel, dim3(B), dim3(256), state_lds(nJ_max, nM_max), stream, xyz, mem, loads,
                        free_index, n_free, nJ, nM, nJ_max, nM_max, ld_f, lambda, tol, it, last, step, S, U, st, Xc, R, W,
                        active, u, N, f_ext, iters, status, residual, joint_out);
@@ -397,10 +396,8 @@ int nl_tangent_launch(int B, int nJ_max, int nM_max, const TrsMembers& mem, cons
     if ((flags & TRS_ASM_COMPACT) != 0) return (int)hipErrorInvalidValue;   // (no slab to amend)
     if (B == 0) return 0;
     const size_t lds = tangent_lds(nJ_max, nM_max, slab_rows);
-    if (lds > NL_LDS_BUDGET) return (int)hipErrorInvalidValue;
-    static const int lds_limit_set = (int)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(trs_nl_tangent_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)lds_limit_set;
+    if (lds > TRS_LDS_BYTES) return (int)hipErrorInvalidValue;
+    trs_lds::raise_lds_once<trs_nl_tangent_kernel>();
     hipLaunchKernelGGL(trs_nl_tangent_kernel, dim3(B), dim3(256), lds, stream, mem, free_index, n_free, nJ, nM, nJ_max,
                        nM_max, ld, slab_rows, S, env, (flags & TRS_ASM_FULL_SYMMETRIC) != 0 ? 1 : 0, W);
     return (int)hipGetLastError();
@@ -414,8 +411,8 @@ int trs_nl_abi_version(void) { return TRS_NL_ABI_VERSION; }
 
 int trs_nl_fits(int nJ_max, int nM_max) {
     if (nJ_max < 0 || nM_max < 0 || nJ_max > 65535) return 0;
-    return state_lds(nJ_max, nM_max) <= NL_LDS_BUDGET &&
-           tangent_lds(nJ_max, nM_max, trs_round_up(3 * nJ_max < 1 ? 1 : 3 * nJ_max, TRS_NB)) <= NL_LDS_BUDGET;
+    return state_lds(nJ_max, nM_max) <= TRS_LDS_BYTES &&
+           tangent_lds(nJ_max, nM_max, trs_round_up(3 * nJ_max < 1 ? 1 : 3 * nJ_max, TRS_NB)) <= TRS_LDS_BYTES;
 }
 
 int trs_nl_state(int B, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* E, const double* A,

@@ -58,7 +58,8 @@ __global__ __launch_bounds__(64 * WAVES) void trs_sets_apply_kernel(
     // trimmed to the arrays, so that no table entry and no output lies outside them whatever nJ[b] and nM[b] hold
     const int joints = min(max(nJ[b], 0), nJ_max), members = min(max(nM[b], 0), nM_max);
     const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
-    const Tables t = tables(sh, nJ_max, nM_max, g, WAVES, OWN);
+    trs_lds::Carve carve(sh);
+    const Tables t = layout(carve, nJ_max, nM_max, g, WAVES, OWN);
     double* zw = t.z + (size_t)wave * ndof_max;
     double* luw = t.own + OWN * wave;
     double* aw = luw + 64;
@@ -282,9 +283,7 @@ int sets_apply_launch(int B, int L, int S, int s0, int Sc, int C, int nJ_max, in
         return (int)hipErrorInvalidValue;
     const int g = pass(nJ_max, nM_max, L, WAVES, OWN);
     if (g <= 0) return (int)hipErrorInvalidValue;   // (the kernel's pass loop steps by g)
-    static const int lds_limit_set = (int)hipFuncSetAttribute(   // once per process, not per launch
-        reinterpret_cast<const void*>(trs_sets_apply_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET);
-    (void)lds_limit_set;
+    trs_lds::raise_lds_once<trs_sets_apply_kernel>();
     const int slices = (Sc + TRS_SETS_SLICE - 1) / TRS_SETS_SLICE;
     hipLaunchKernelGGL(trs_sets_apply_kernel, dim3((unsigned)slices * (unsigned)B), dim3(64 * WAVES),
                        lds(nJ_max, nM_max, g, WAVES, OWN), stream, L, g, S, s0, Sc, C, TRS_SETS_SLICE, xyz, mem, free_index, nJ,

@@ -3,14 +3,14 @@
 //     asks for it: trs_loss_rhs (members e0 .. e0 + C - 1) or trs_sets_rhs (the members of an id list);
 //   - the wave extreme that carries the index with the value, and the close of a peak with it;
 //   - for the two apply kernels that run one work-group per (truss, slice) over staged tables (trs_loss_apply,
-//     trs_sets_apply): the LDS rule behind trs_loss_fits / trs_sets_fits, the passes and the launch; the tables and
-//     their carving; the stage; and c_m . (v[j1] - v[j0]), the ONE expression behind N, q_m, r_e and a set's pivots.
+//     trs_sets_apply): the tables and their layout in LDS (trs_lds.h), which is the rule behind trs_loss_fits /
+//     trs_sets_fits, the passes and the launch; the stage; and c_m . (v[j1] - v[j0]), the ONE expression behind N, q_m, r_e and a set's pivots.
 // The stage trims nJ[b] and nM[b] to the arrays, clamps end-joint ids, fills the DOF map and the joint order for all
 // nJ_max joints (-1 = held past the truss's own) and zeroes the waves' vectors: whatever the inputs hold, nothing is
 // read or written outside the arrays, and entries past the truss's joints read as zero.
 #pragma once
 #include "trs_common.h"
-#include "trs_recover.h"
+#include "trs_lds.h"
 
 #include <limits.h>
 
@@ -19,10 +19,8 @@ namespace trs_col {
 #ifndef TRS_LOSS_WAVES
 #define TRS_LOSS_WAVES 4   // waves per work-group of trs_loss_apply and of the rhs kernel (EXPERIMENTS R14)
 #endif
-constexpr int MAX_PASS = 8;                 // load cases per pass at most (loss: their maxima live in registers; sets:
-                                            // lane 8 l + i substitutes case l)
-constexpr size_t LDS_BUDGET = 160 * 1024;   // a CU's LDS: the ONE number behind the fits rules, the passes and the launches
-                                            // (bar-942 needs 86 KB with one case, so two work-groups per CU never fit it)
+constexpr int MAX_PASS = 8;   // load cases per pass at most (loss: their maxima live in registers; sets: lane 8 l + i
+                              // substitutes case l)
 
 // Row `row` of Z, by one wave: b_e,f of member `member` (= b * nM_max + e) when `real`, else zeros - +c at the free
 // DOFs of j1 and -c at those of j0 through fi (the truss's free_index), zeros in the other columns below npad.  One
@@ -81,28 +79,8 @@ __device__ __forceinline__ void close_peak(double v, int i, const int lane, doub
     }
 }
 
-// LDS of an apply kernel of `waves` waves with g cases per pass and `extra` doubles of every wave's own
-inline size_t lds(int nJ_max, int nM_max, int g, int waves, int extra) {
-    const size_t doubles = (size_t)5 * nM_max + ((size_t)3 * nJ_max + extra) * waves +
-                           (size_t)g * ((size_t)3 * nJ_max + nM_max);
-    const size_t ints = (size_t)2 * nM_max + (size_t)4 * nJ_max;
-    return (doubles * sizeof(double) + ints * sizeof(int) + 15) / 16 * 16;
-}
-
-// cases per pass: the largest g <= min(L, MAX_PASS) that fits, evened out over the passes it makes necessary; 0 = none
-inline int pass(int nJ_max, int nM_max, int L, int waves, int extra) {
-    int g = L < MAX_PASS ? L : MAX_PASS;
-    while (g > 0 && lds(nJ_max, nM_max, g, waves, extra) > LDS_BUDGET) --g;
-    if (g <= 0) return 0;
-    const int passes = (L + g - 1) / g;
-    return (L + passes - 1) / passes;
-}
-
-// the rule of trs_loss_fits and trs_sets_fits: one case per pass fits
-inline int fits(int nJ_max, int nM_max, int L, int waves, int extra) {
-    return nJ_max >= 0 && nM_max >= 0 && L >= 0 && lds(nJ_max, nM_max, 1, waves, extra) <= LDS_BUDGET;
-}
-
+// The LDS tables of an apply kernel of `waves` waves with g cases per pass and `extra` doubles of every wave's own
+// (bar-942 needs 86 KB with one case, so two work-groups per CU never fit it)
 struct Tables {
     double *cx, *cy, *cz, *k, *ia;   // [nM_max] each: direction cosines, E A / len, 1 / A
     double* z;                       // [waves][3 nJ_max]  a joint-layout vector per wave
@@ -114,22 +92,42 @@ struct Tables {
     int* jo;                         // [nJ_max]
 };
 
-__device__ __forceinline__ Tables tables(double* sh, int nJ_max, int nM_max, int g, int waves, int extra) {
+template <class Arena>
+__host__ __device__ inline Tables layout(Arena& a, int nJ_max, int nM_max, int g, int waves, int extra) {
     Tables t;
-    t.cx = sh;
-    t.cy = t.cx + nM_max;
-    t.cz = t.cy + nM_max;
-    t.k = t.cz + nM_max;
-    t.ia = t.k + nM_max;
-    t.z = t.ia + nM_max;
-    t.own = t.z + (size_t)waves * 3 * nJ_max;
-    t.u = t.own + (size_t)waves * extra;
-    t.N = t.u + (size_t)g * 3 * nJ_max;
-    t.ends = reinterpret_cast<int2*>(t.N + (size_t)g * nM_max);
-    t.fi = reinterpret_cast<int*>(t.ends + nM_max);
-    t.jo = t.fi + 3 * nJ_max;
+    t.cx = a.template take<double>(nM_max);
+    t.cy = a.template take<double>(nM_max);
+    t.cz = a.template take<double>(nM_max);
+    t.k = a.template take<double>(nM_max);
+    t.ia = a.template take<double>(nM_max);
+    t.z = a.template take<double>((size_t)waves * 3 * nJ_max);
+    t.own = a.template take<double>((size_t)waves * extra);
+    t.u = a.template take<double>((size_t)g * 3 * nJ_max);
+    t.N = a.template take<double>((size_t)g * nM_max);
+    t.ends = a.template take<int2>(nM_max);
+    t.fi = a.template take<int>(3, nJ_max);
+    t.jo = a.template take<int>(nJ_max);
     return t;
 }
+
+inline size_t lds(int nJ_max, int nM_max, int g, int waves, int extra) {
+    return trs_lds::count([&](auto& a) { layout(a, nJ_max, nM_max, g, waves, extra); });
+}
+
+// cases per pass: the largest g <= min(L, MAX_PASS) that fits, evened out over the passes it makes necessary; 0 = none
+inline int pass(int nJ_max, int nM_max, int L, int waves, int extra) {
+    int g = L < MAX_PASS ? L : MAX_PASS;
+    while (g > 0 && lds(nJ_max, nM_max, g, waves, extra) > TRS_LDS_BYTES) --g;
+    if (g <= 0) return 0;
+    const int passes = (L + g - 1) / g;
+    return (L + passes - 1) / passes;
+}
+
+// the rule of trs_loss_fits and trs_sets_fits: one case per pass fits
+inline int fits(int nJ_max, int nM_max, int L, int waves, int extra) {
+    return nJ_max >= 0 && nM_max >= 0 && L >= 0 && lds(nJ_max, nM_max, 1, waves, extra) <= TRS_LDS_BYTES;
+}
+
 
 // c_m . d for the staged member m, and c_m . (v[j1] - v[j0]) for a joint-layout vector v: times k_m the member force of
 // the displacements v.  The order of the two fused multiply-adds is part of the results' bits.

@@ -1,7 +1,8 @@
 // trs_recover.h - the per-member and per-joint arithmetic of the result recovery, shared by trs_recover
 // (recover.hip) and the multi-case recovery trs_recover_cases (cases.hip): both paths call the same functions,
 // so case k of a multi-case recovery rounds exactly like a single recovery of case k.  Also the builder of the
-// per-joint member-end lists in LDS that cases.hip, adjoint.hip and effects.hip sum over (build_end_lists).
+// per-joint member-end lists in LDS that the analysis kernels sum over (build_end_lists) with its joint predicates
+// (EveryJoint, InTruss) and order_by_neighbour; where the lists lie in a kernel's LDS is its layout's affair (trs_lds.h).
 #pragma once
 #include "trs_common.h"
 
@@ -23,6 +24,11 @@ __device__ __forceinline__ MemberGeom member_geom(const double* X, int j0, int j
 #pragma unroll
     for (int a = 0; a < 3; ++a) g.c[a] = d[a] / g.len;
     return g;
+}
+
+// Young's modulus of a member, either member form (not beside TrsMembers::EA: bench.py fingerprints trs_common.h)
+__device__ __forceinline__ double modulus(const TrsMembers& mem, size_t mm) {
+    return mem.table() ? mem.types[3 * (int)mem.tidx[mm] + 1] : mem.E[mm];
 }
 
 // axial force of a member from the displacements of its end joints: N = (E A / L) c . (u1 - u0)
@@ -78,6 +84,11 @@ struct EndLists {
 
 struct EveryJoint {
     __device__ __forceinline__ bool operator()(int) const { return true; }
+};
+// the joints of the truss: an end joint outside them gets no list (it would index LDS outside the lists) and no sum
+struct InTruss {
+    int joints;
+    __device__ __forceinline__ bool operator()(int j) const { return (j >= 0) & (j < joints); }
 };
 
 // Builds the lists of the joints that `keep(j)` admits (the others get empty lists), by a work-group of 256 threads:
