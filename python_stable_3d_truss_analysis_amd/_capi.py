@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h`, `include/trs_influence.h`, `include/trs_sets.h`, `include/trs_dynamics.h`, `include/trs_nonlinear.h`, `include/trs_buckling.h` and `include/trs_modegrad.h` (library: `libtrs_hip.so`, in-tree).
+"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h`, `include/trs_influence.h`, `include/trs_sets.h`, `include/trs_dynamics.h`, `include/trs_nonlinear.h`, `include/trs_buckling.h`, `include/trs_modegrad.h` and `include/trs_spectrum.h` (library: `libtrs_hip.so`, in-tree).
 
 There is no fallback: if the library is missing, `load()` raises `HipExtensionError`.
 """
@@ -187,6 +187,19 @@ MG_SIGNATURES = {
                              _P]),
 }
 
+#: every symbol `include/trs_spectrum.h` declares (response spectrum analysis from the converged mode block;
+#: csrc/spectrum.hip, the same library)
+RS_SIGNATURES = {
+    "trs_rs_abi_version": (_I, []),
+    "trs_rs_fits": (_I, [_I, _I, _I]),
+    "trs_rs_modal": (_I, [_I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _D, _I, _I, _P, _P, _P, _P, _P,
+                          _P, _P, _P, _P]),
+    "trs_rs_combine": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _I, _I, _P, _P, _P,
+                            _P, _P, _P, _P, _P]),
+    "trs_rs_combine_tab": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _I, _I, _P, _P,
+                                _P, _P, _P, _P, _P, _P]),
+}
+
 #: must equal TRS_ABI_VERSION of include/trs_solver.h
 ABI_VERSION = 10
 #: must equal TRS_MODES_ABI_VERSION of include/trs_modes.h
@@ -207,6 +220,10 @@ NL_ABI_VERSION = 1
 BK_ABI_VERSION = 1
 #: must equal TRS_MG_ABI_VERSION of include/trs_modegrad.h
 MG_ABI_VERSION = 1
+#: must equal TRS_RS_ABI_VERSION of include/trs_spectrum.h
+RS_ABI_VERSION = 1
+#: TRS_RS_SRSS, TRS_RS_CQC, TRS_RS_ABS of include/trs_spectrum.h: the modal combination rules
+RS_RULES = {"srss": 0, "cqc": 1, "abs": 2}
 #: TRS_NL_* of include/trs_nonlinear.h: the status of a truss in a load step of the nonlinear analysis
 NL_ACTIVE, NL_CONVERGED, NL_ITER_LIMIT, NL_NOT_PD, NL_NOT_ATTEMPTED = -1, 0, 1, 2, 3
 #: TRS_SETS_MAX of include/trs_sets.h: members per scenario at most
@@ -257,7 +274,7 @@ def load():
     except OSError as exc:
         raise HipExtensionError(f"cannot load {LIB_PATH}: {exc}") from exc
     for table in (SIGNATURES, MODES_SIGNATURES, EFFECTS_SIGNATURES, LOSS_SIGNATURES, INFLUENCE_SIGNATURES,
-                  SETS_SIGNATURES, DYN_SIGNATURES, NL_SIGNATURES, BK_SIGNATURES, MG_SIGNATURES):
+                  SETS_SIGNATURES, DYN_SIGNATURES, NL_SIGNATURES, BK_SIGNATURES, MG_SIGNATURES, RS_SIGNATURES):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype = restype
@@ -267,7 +284,7 @@ def load():
             or lib.trs_influence_abi_version() != INFLUENCE_ABI_VERSION \
             or lib.trs_sets_abi_version() != SETS_ABI_VERSION or lib.trs_dyn_abi_version() != DYN_ABI_VERSION \
             or lib.trs_nl_abi_version() != NL_ABI_VERSION or lib.trs_bk_abi_version() != BK_ABI_VERSION \
-            or lib.trs_mg_abi_version() != MG_ABI_VERSION:
+            or lib.trs_mg_abi_version() != MG_ABI_VERSION or lib.trs_rs_abi_version() != RS_ABI_VERSION:
         raise HipExtensionError("libtrs_hip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -1530,6 +1530,91 @@ class DeviceBatch:
             out["gap"].copy_(t.where(mine[:, :, 0].isnan(), mine[:, :, 0], gap))
         return out
 
+    # -- response spectrum analysis from the converged block (include/trs_spectrum.h) ------------------
+    #: the combined results `response_spectrum` can give, and where their axes lie after [B, G]
+    SPECTRUM_RESULTS = ("u", "N", "R")
+
+    def _spectrum_shapes(self, G, p, want, want_modal):
+        per = {"u": [self.nJ_max, 3], "N": [self.nM_max], "R": [self.nJ_max, 3]}
+        t = self.torch
+        shapes = {"gamma": [self.B, G, p], "sa": [self.B, G, p], "meff": [self.B, G, p], "mtot": [self.B, G],
+                  "base": [self.B, G], "n_modes": ([self.B], t.int32)}
+        for k in want:
+            shapes[k] = [self.B, G] + per[k]
+            if want_modal:
+                shapes["modal_" + k] = [self.B, G, p + 1] + per[k]
+        return shapes
+
+    def response_spectrum(self, directions, periods, accel, damping=0.05, rule="cqc", missing_mass=True, zpa=None,
+                          want=SPECTRUM_RESULTS, want_modal=False, out=None, generation=None):
+        """The seismic response spectrum analysis of every truss with the modes of the last `modes()`: participation
+        factors and effective modal masses per ground direction, the spectral ordinate of every mode, and the peak
+        displacements `u` [B, G, nJ_max, 3], member forces `N` [B, G, nM_max] and support reactions `R`
+        [B, G, nJ_max, 3] combined over the modes by `rule` ("srss", "cqc" - Der Kiureghian, needs `damping` > 0 -
+        or "abs"), include/trs_spectrum.h.  Shared by the batch (numpy, torch or lists): `directions` [G, 3] (or
+        [G, 2]; 1 <= G <= 3, the length is a scale), the spectrum table `periods` [K] (strictly ascending, >= 0,
+        2 <= K <= 64) and `accel` [G, K] (pseudo-accelerations, >= 0; linear between the points, constant outside
+        them), `zpa` [G] (the zero-period acceleration of the missing-mass correction; None: accel[:, 0]).
+        `missing_mass`: the mass the truncated modes leave out responds statically - one more substitution against
+        the resident factor (`trs_potrs_cases`), one more response vector per direction in slot p, uncorrelated with
+        the modes.  Returns a dict of device tensors: gamma, sa, meff [B, G, p] (zeros beyond n_modes), mtot, base
+        [B, G] (the mass that takes part and the combined base shear), n_modes [B], the results named in `want` (caller's
+        joint numbering; u zero at held DOFs, R zero at free ones) and, with `want_modal`, their signed modal values
+        modal_u, modal_R [B, G, p + 1, nJ_max, 3], modal_N [B, G, p + 1, nM_max] (slot p: the missing mass, zeros
+        without it).  `out`: such a dict to write into.
+        Guarded as `mode_gradients`: the `modes()` state must be current (ValueError when `factor()`,
+        `solve_cases()`, ... ran since; `generation`: the value the caller saw after ITS `modes()`, checked as well).
+        Nothing is bumped here: `modes()` already invalidated what `adjoint_cases` differentiates, the case block is
+        only scratch, and X, lam and n_mass are only read - `mode_gradients` works afterwards with the same bits, and
+        the call can be repeated."""
+        t = self.torch
+        state = getattr(self, "_modes_state", None)
+        if not getattr(self, "_factored", False) or state is None:
+            raise ValueError("response_spectrum(): no modes - call factor() and modes(p) first")
+        if state["generation"] != self.generation or (generation is not None and generation != self.generation):
+            raise ValueError("response_spectrum(): the modes are stale - factor(), solve_cases() or another analysis "
+                             "ran since the modes() this analysis belongs to")
+        p = state["p"]
+        dirs, T, Sa, zpa, code, want = _check_spectrum_args(p, directions, periods, accel, damping, rule, zpa, want)
+        G, K = int(Sa.shape[0]), int(Sa.shape[1])
+        if self.B and not self.lib.trs_rs_fits(self.nJ_max, self.nM_max, p):     # (before any output is allocated)
+            raise HipExtensionError(f"response_spectrum(): the response vectors of a truss of {self.nJ_max} joints / "
+                                    f"{self.nM_max} members exceed the LDS of the combine kernel (trs_rs_fits)")
+        out = self._out_tensors("response_spectrum", self._spectrum_shapes(G, p, want, bool(want_modal)), out)
+        if self.B == 0:
+            return out
+        ws = self._modes_ws
+        sc = getattr(self, "_rs_ws", None)
+        if sc is None or tuple(sc["q"].shape) != (self.B, G, p):
+            sc = self._rs_ws = {"q": t.empty([self.B, G, p], dtype=t.float64, device=self.device),
+                                "rho": t.empty([self.B, 8, 8], dtype=t.float64, device=self.device)}
+        dev = lambda x: t.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(self.device)
+        jo, stream, tab = self._case_launch()
+        F = None
+        with t.cuda.device(self.device):
+            dirs_d, T_d, Sa_d, zpa_d = dev(dirs), dev(T), dev(Sa), dev(zpa)
+            if missing_mass:
+                F = self.cases_F = self._case_block("cases_F", MODES_BLOCK)
+            _capi.check(self.lib.trs_rs_modal(
+                self.B, self.nJ_max, self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(),
+                ws["X"].data_ptr(), self.rows, ws["lam"].data_ptr(), ws["Mf"].data_ptr(), ws["n_mass"].data_ptr(), p, G,
+                dirs_d.data_ptr(), K, T_d.data_ptr(), Sa_d.data_ptr(), zpa_d.data_ptr(), float(damping), code,
+                int(bool(missing_mass)), out["gamma"].data_ptr(), out["sa"].data_ptr(), out["meff"].data_ptr(),
+                out["mtot"].data_ptr(), out["base"].data_ptr(), sc["q"].data_ptr(), sc["rho"].data_ptr(), _ptr(F), stream),
+                "trs_rs_modal")
+            if missing_mass:
+                self._potrs_cases(F, MODES_BLOCK)
+            if want:
+                modal = lambda k: _ptr(out.get("modal_" + k))
+                _capi.check(getattr(self.lib, f"trs_rs_combine{tab}")(
+                    self.B, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *self._members(), self.free_index.data_ptr(),
+                    self.n_free.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), jo, ws["X"].data_ptr(), self.rows,
+                    ws["n_mass"].data_ptr(), p, G, sc["q"].data_ptr(), sc["rho"].data_ptr(), code, int(bool(missing_mass)),
+                    _ptr(F), _ptr(out.get("u")), _ptr(out.get("R")), _ptr(out.get("N")), modal("u"), modal("R"),
+                    modal("N"), stream), f"trs_rs_combine{tab}")
+            out["n_modes"].copy_(ws["n_mass"].clamp(max=p))
+        return out
+
     # -- transient response: Newmark time stepping on a factor of K + sigma M (include/trs_dynamics.h) ------------------
     def factor_dynamic(self, dt, beta=0.25, gamma=0.5, damp_mass=0.0, damp_stiff=0.0, joint_mass=None, mass_scale=1.0):
         """`factor()` for the time domain: dofmap, assembly, the lumped mass of `modes` (`trs_modes_mass`, the same
@@ -3703,6 +3788,136 @@ def solve_mode_gradients(trusses_or_packed, p=6, weights=None, joint_mass=None, 
         res.update(db.mode_gradients(weights=part.cut(weights), want=want))
         _put_result(part, out, res)
     out.omega = out.eigenvalue.sqrt()
+    return _finish_result(torch, dev, out, on_device)
+
+
+@dataclass
+class SpectrumResult:
+    """Results of `solve_response_spectrum`: eigenvalue, omega, residual [B, p], n_modes, iters, info [B] as `ModeResult`;
+    gamma, sa, meff [B, G, p] (participation factor, spectral ordinate and effective-mass fraction of every mode per
+    ground direction; zeros beyond n_modes), mtot, base [B, G] (the mass on free DOFs weighted by the direction, and the
+    combined base shear); displace, reaction [B, G, nJ_max, 3] and force [B, G, nM_max] (the peaks per direction,
+    combined over the modes: non-negative; displace zero at held DOFs, reaction zero at free ones); displace_all,
+    reaction_all [B, nJ_max, 3] and force_all [B, nM_max] (SRSS over the G directions); with `want_modal` the signed
+    modal values modal_displace, modal_reaction [B, G, p + 1, nJ_max, 3] and modal_force [B, G, p + 1, nM_max] (slot
+    p: the missing-mass response), else None."""
+    eigenvalue: np.ndarray
+    omega: np.ndarray
+    residual: np.ndarray
+    n_modes: np.ndarray
+    iters: np.ndarray
+    gamma: np.ndarray
+    sa: np.ndarray
+    meff: np.ndarray
+    mtot: np.ndarray
+    base: np.ndarray
+    displace: np.ndarray
+    force: np.ndarray
+    reaction: np.ndarray
+    displace_all: np.ndarray
+    force_all: np.ndarray
+    reaction_all: np.ndarray
+    modal_displace: np.ndarray
+    modal_force: np.ndarray
+    modal_reaction: np.ndarray
+    info: np.ndarray
+
+    # (`modes` returns no "omega" and `response_spectrum` no "*_all": `solve_response_spectrum` forms them with torch)
+    FIELDS = {"eigenvalue": ("lam", float("nan"), "float64", ("P",)), "omega": ("omega", float("nan"), "float64", ("P",)),
+              "residual": ("resid", float("nan"), "float64", ("P",)), "n_modes": ("n_modes", 0, "int32", ()),
+              "iters": ("iters", 0, "int32", ()), "gamma": ("gamma", 0.0, "float64", ("G", "P")),
+              "sa": ("sa", 0.0, "float64", ("G", "P")), "meff": ("meff", 0.0, "float64", ("G", "P")),
+              "mtot": ("mtot", 0.0, "float64", ("G",)), "base": ("base", 0.0, "float64", ("G",)),
+              "displace": ("u", 0.0, "float64", ("G", "nJ", 3)), "force": ("N", 0.0, "float64", ("G", "nM")),
+              "reaction": ("R", 0.0, "float64", ("G", "nJ", 3)), "displace_all": ("u_all", 0.0, "float64", ("nJ", 3)),
+              "force_all": ("N_all", 0.0, "float64", ("nM",)), "reaction_all": ("R_all", 0.0, "float64", ("nJ", 3)),
+              "modal_displace": ("modal_u", 0.0, "float64", ("G", "V", "nJ", 3)),
+              "modal_force": ("modal_N", 0.0, "float64", ("G", "V", "nM")),
+              "modal_reaction": ("modal_R", 0.0, "float64", ("G", "V", "nJ", 3))}
+
+
+def _check_spectrum_args(p, directions, periods, accel, damping=0.05, rule="cqc", zpa=None,
+                         want=DeviceBatch.SPECTRUM_RESULTS):
+    """The argument errors of `DeviceBatch.response_spectrum` / `solve_response_spectrum` that need no device.  Returns
+    (directions [G, 3], periods [K], accel [G, K], zpa [G]) as host float64 arrays, the rule's code and `want` as a
+    tuple."""
+    who = "response_spectrum"
+    if isinstance(p, bool) or int(p) != p or not 1 <= int(p) <= 8:
+        raise ValueError(f"{who}: p must be an integer in 1 .. 8, got {p!r}")
+    dirs = _host_array(directions, np.float64)
+    if dirs.ndim != 2 or not 1 <= dirs.shape[0] <= 3 or dirs.shape[1] not in (2, 3):
+        raise ValueError(f"{who}: directions must be [G, 3] (or [G, 2]) with 1 <= G <= 3, got {dirs.shape}")
+    if dirs.shape[1] == 2:
+        dirs = np.concatenate([dirs, np.zeros([len(dirs), 1])], axis=1)
+    if not np.isfinite(dirs).all():
+        raise ValueError(f"{who}: directions must be finite")
+    G = len(dirs)
+    T = _host_array(periods, np.float64)
+    if T.ndim != 1 or not 2 <= T.size <= 64:
+        raise ValueError(f"{who}: periods must be [K] with 2 <= K <= 64, got {T.shape}")
+    if not (np.isfinite(T).all() and T[0] >= 0 and (np.diff(T) > 0).all()):
+        raise ValueError(f"{who}: periods must be finite, non-negative and strictly ascending")
+    Sa = _host_array(accel, np.float64)
+    if Sa.shape != (G, T.size):
+        raise ValueError(f"{who}: accel must be [G={G}, K={T.size}], got {Sa.shape}")
+    if not (np.isfinite(Sa).all() and (Sa >= 0).all()):
+        raise ValueError(f"{who}: accel must be finite and non-negative")
+    if zpa is None:
+        zpa = Sa[:, 0].copy()
+    zpa = _host_array(zpa, np.float64)
+    if zpa.shape != (G,) or not (np.isfinite(zpa).all() and (zpa >= 0).all()):
+        raise ValueError(f"{who}: zpa must be [G={G}], finite and non-negative")
+    if not isinstance(rule, str) or rule.lower() not in _capi.RS_RULES:
+        raise ValueError(f"{who}: rule must be one of {sorted(_capi.RS_RULES)}, got {rule!r}")
+    if isinstance(damping, (bool, str)) or not isinstance(damping, (int, float, np.integer, np.floating)) \
+            or not (np.isfinite(damping) and damping >= 0):
+        raise ValueError(f"{who}: damping must be a non-negative finite number, got {damping!r}")
+    if rule.lower() == "cqc" and not damping > 0:
+        raise ValueError(f"{who}: rule 'cqc' needs damping > 0, got {damping!r}")
+    if isinstance(want, str):
+        raise ValueError(f"{who}: want must be a sequence of names out of {DeviceBatch.SPECTRUM_RESULTS}")
+    want = tuple(want)
+    if any(k not in DeviceBatch.SPECTRUM_RESULTS for k in want):
+        raise ValueError(f"{who}: want must name some of {DeviceBatch.SPECTRUM_RESULTS}, got {want}")
+    return dirs, T, Sa, zpa, _capi.RS_RULES[rule.lower()], want
+
+
+def solve_response_spectrum(trusses_or_packed, directions, periods, accel, p=6, damping=0.05, rule="cqc",
+                            missing_mass=True, zpa=None, joint_mass=None, mass_scale=1.0, want_modal=False, tol=1e-10,
+                            max_iters=256, device=None, reorder=False, options=None, max_slab_bytes=64 << 30,
+                            on_device=False, use_envelope=True):
+    """The seismic response spectrum analysis of every truss of a batch, from ONE factorisation per truss: the `p`
+    (1 .. 8) lowest modes (`solve_modes`: the same lumped mass, `joint_mass`, `mass_scale`), then per ground direction
+    the participation factors, the spectral ordinates and the peak displacements, member forces and support reactions
+    combined over the modes by `rule` ("srss", "cqc", "abs"), with the missing-mass correction by one more
+    substitution against the resident factor (`DeviceBatch.response_spectrum`, include/trs_spectrum.h, where
+    `directions`, `periods`, `accel`, `zpa` and `damping` are described; they are shared by the batch).  The G
+    directions are combined by SRSS into displace_all, force_all and reaction_all.  The other arguments as
+    `solve_modes`.  Returns a `SpectrumResult`."""
+    packed = _as_packed(trusses_or_packed)
+    B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
+    jm_shape = jm_min = None
+    if joint_mass is not None:
+        jm_shape = tuple(int(x) for x in joint_mass.shape)
+        jm = _host_array(joint_mass, np.float64)
+        jm_min = (float(jm.min()) if jm.size else 0.0) if np.isfinite(jm).all() else float("nan")
+    _check_mode_args(B, nJ_max, p, jm_shape, mass_scale, tol, max_iters, joint_mass_min=jm_min)
+    dirs, T, Sa, zpa, _, want = _check_spectrum_args(p, directions, periods, accel, damping, rule, zpa)
+    p, G = int(p), len(dirs)
+    torch, dev = _require_gpu(device)
+    joint_mass = _device_f64(torch, dev, joint_mass)
+    modal = ("modal_displace", "modal_force", "modal_reaction")
+    out = _new_result(torch, dev, SpectrumResult, B, {"P": p, "G": G, "V": p + 1, "nJ": nJ_max, "nM": nM_max},
+                      without=() if want_modal else modal)
+    for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope):
+        res = db.modes(p, tol=tol, max_iters=max_iters, joint_mass=part.cut(joint_mass, nJ=1), mass_scale=mass_scale)
+        res.update(db.response_spectrum(dirs, T, Sa, damping=damping, rule=rule, missing_mass=missing_mass, zpa=zpa,
+                                        want=want, want_modal=want_modal))
+        _put_result(part, out, res)
+    out.omega = out.eigenvalue.sqrt()
+    out.displace_all = out.displace.square().sum(1).sqrt()
+    out.force_all = out.force.square().sum(1).sqrt()
+    out.reaction_all = out.reaction.square().sum(1).sqrt()
     return _finish_result(torch, dev, out, on_device)
 
 

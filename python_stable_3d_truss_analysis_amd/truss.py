@@ -476,6 +476,42 @@ class Truss:
             out["djoint_mass"] = result.djoint_mass[0, :n, :nJ].copy()
         return out
 
+    def ResponseSpectrum(self, directions, periods, accelerations, nModes=6, damping=0.05, rule="cqc", missingMass=True,
+                         jointMasses=None, massScale=1.0):
+        """The seismic response spectrum analysis of this truss with its `nModes` (1 .. 8) lowest modes (the lumped mass,
+        `jointMasses` and `massScale` of `NaturalFrequencies`): `directions` [G, dim] ground directions (1 <= G <= 3;
+        the length is a scale), the spectrum table `periods` [K] (ascending) and `accelerations` [G, K]
+        (pseudo-accelerations, linear between the points and constant outside them), the modal `damping` ratio and the
+        combination `rule` ("srss", "cqc" or "abs"); `missingMass`: the mass the truncated modes leave out responds
+        statically at accelerations[:, 0] (`batch.solve_response_spectrum`).  Returns a dict of numpy arrays in the
+        truss's own joint and member ids, n the number of modes the truss has: "eigenvalue", "omega" [n]; "gamma", "sa",
+        "meff" [G, n] (participation factor, spectral ordinate, effective-mass fraction); "mtot", "base" [G] (the mass
+        taking part and the combined base shear); the peaks per direction "displace", "reaction" [G, joints, dim] and
+        "force" [G, members]; and their SRSS over the directions "displace_all", "reaction_all" [joints, dim] and
+        "force_all" [members].  The truss's loads, its solved state and its results stay as they are; errors as
+        `NaturalFrequencies`."""
+        if not self.isStable:
+            raise TrussNotStableError("The truss is not stable !")
+        from .batch import pack_trusses, solve_response_spectrum  # late import: keeps the model importable without torch
+        packed = pack_trusses([self])
+        masses = None
+        if jointMasses:
+            masses = np.zeros([1, packed.nJ_max])
+            for jointID, mass in jointMasses.items():
+                masses[0, jointID] = mass
+        result = solve_response_spectrum(packed, directions, periods, accelerations, p=nModes, damping=damping, rule=rule,
+                                         missing_mass=missingMass, joint_mass=masses, mass_scale=massScale)
+        if int(result.info[0]) != 0:
+            raise np.linalg.LinAlgError("Singular matrix")
+        n, nJ, nM, dim = int(result.n_modes[0]), len(self._pos), int(packed.nM[0]), self._dim
+        return {"eigenvalue": result.eigenvalue[0, :n].copy(), "omega": result.omega[0, :n].copy(),
+                "gamma": result.gamma[0, :, :n].copy(), "sa": result.sa[0, :, :n].copy(),
+                "meff": result.meff[0, :, :n].copy(), "mtot": result.mtot[0].copy(), "base": result.base[0].copy(),
+                "displace": result.displace[0, :, :nJ, :dim].copy(), "force": result.force[0, :, :nM].copy(),
+                "reaction": result.reaction[0, :, :nJ, :dim].copy(),
+                "displace_all": result.displace_all[0, :nJ, :dim].copy(), "force_all": result.force_all[0, :nM].copy(),
+                "reaction_all": result.reaction_all[0, :nJ, :dim].copy()}
+
     def BucklingFactors(self, nModes=4, returnShapes=False, maxShifts=6):
         """By what factor can this truss's loads grow before it buckles (linear buckling, `batch.solve_buckling`)?
         Returns `(critical, factors)`: `critical` the smallest positive load factor (NaN when none was found within

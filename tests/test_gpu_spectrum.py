@@ -1,0 +1,435 @@
+"""Response spectrum analysis on the GPU (`DeviceBatch.response_spectrum`, `solve_response_spectrum`,
+`Truss.ResponseSpectrum`; C ABI include/trs_spectrum.h) against the numpy restatement of `tests/spectrum_reference.py`: on
+the device's own shapes (kernel parity), on `eigh`'s (truth), by the identities that need no reference, and bit for bit
+where the interface promises bits.
+
+The parity bound is max(1e-11, 100 x a) of the size class (tests/golden/spectrum_tol.json), entry by entry, scaled by the
+largest entry of the quantity.  ONE kind of entry cannot meet it in any floating-point evaluation and is compared through
+its square instead (`check_entries`): a combined SRSS / CQC value - the root of a sum over the modes - where that sum
+cancels.  With the two vectors of a repeated eigenvalue an entry at rest by symmetry has r_i = -r_j and rho_ij = 1; the sum
+is 1e-16 of its terms instead of zero and its root 1e-8 of them, in the restatement as on the device (on `eigh`'s own
+shapes of bar-72 the restatement's CQC member forces in float64 lie 1.7e-10 from themselves in longdouble).  Which entries:
+float64 evaluates s = sum_ij rho_ij r_i r_j with an error of up to n u T, T = sum_ij |rho_ij r_i r_j|, u = 2^-53 and n = 80
+(64 products and additions, and the roundings the r_i arrive with), and the root passes an error ds on as ds / (2 sqrt s).
+An entry whose value `want` satisfies 2 want (bound x scale) <= n u T is therefore not delivered to the bound by float64
+itself - that is decided from the restatement's own modal values, not from the device's.  Such an entry is held to
+|got^2 - want^2| <= bound x scale^2: the sum itself, before the root, within the bound.  Every other entry of every
+quantity - all signed modal values, everything under abs, every combined value whose sum does not cancel - is held to the
+bound as the issue states it.  EXPERIMENTS R24 lists the entries that took the other way on the MI355X."""
+import os
+
+import numpy as np
+import pytest
+
+from tests import helpers as H
+from tests import mode_gradients_reference as G
+from tests import spectrum_reference as S
+from tests.test_gpu_mode_gradients import CONFIGS, IDENTITY_TOL, RAGGED, RAGGED_SCALE, Run, ragged_masses, run_of, size_class
+from tests.test_spectrum import ACCEL, CLUSTERS, DIRS, PERIODS, RULES, SIMPLE, ZETA, modes_of, tolerances, truth_differences
+
+pytestmark = pytest.mark.gpu
+P = 8
+SINGLE = [n for n in H.data_case_names() if n.endswith("_input_0")]
+BIG = "bar-942_input_0"
+CASES = [(rule, mm) for rule in RULES for mm in (True, False)]
+
+
+def class_bound(n_members, key, floor):
+    return max(floor, 100 * tolerances()[size_class(n_members)][key])
+
+
+def spectrum(run, rule="cqc", missing_mass=True, want_modal=True, periods=PERIODS, accel=ACCEL, **kw):
+    """`response_spectrum` of a run with the tests' table (or another), as host arrays."""
+    import torch
+    out = run.db.response_spectrum(DIRS, periods, accel, damping=ZETA, rule=rule, missing_mass=missing_mass,
+                                   want_modal=want_modal, **kw)
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def cut(out, b, key, d):
+    """Truss b's part of an output, trimmed to its own joints / members."""
+    x = out[key][b]
+    nJ, nM = len(d["xyz"]), len(d["conn"])
+    if key in ("u", "R"):
+        return x[:, :nJ]
+    if key in ("modal_u", "modal_R"):
+        return x[:, :, :nJ]
+    return x[:, :nM] if key == "N" else x[:, :, :nM] if key == "modal_N" else x
+
+
+ROOTS = ("u", "N", "R", "base")
+_restated = {}
+
+
+def restated(d, phi, lam, rule, mm, mass_scale, dtype=np.float64):
+    """The restatement on given shapes, once per (shapes, rule, missing mass, precision): the member forms give the same
+    bits, so their comparisons share it."""
+    key = (phi.tobytes(), lam.tobytes(), rule, mm, mass_scale, dtype)
+    if key not in _restated:
+        _restated[key] = S.response(d, phi, lam, DIRS, PERIODS, ACCEL, ZETA, rule, mm, mass_scale=mass_scale, dtype=dtype)
+    return _restated[key]
+
+
+def check_entries(key, rule, got, want, terms, bound):
+    """(worst direct error, entries compared through their squares) of one quantity: see the module's docstring.
+    `terms`: T = sum_ij |rho_ij r_i r_j| per entry for a combined value under srss / cqc, else None."""
+    got, want = (np.abs(got), np.abs(want)) if key == "gamma" else (got, want)
+    scale = np.abs(want).max() if want.size and np.abs(want).max() > 0 else 1.0
+    err = np.abs(got - want) / scale
+    if terms is None:
+        assert (err <= bound).all(), (key, rule, float(err.max()), bound)
+        return float(err.max()) if err.size else 0.0, 0
+    ill = (terms > 0) & (2.0 * np.abs(want) * (bound * scale) <= 80 * 2.0 ** -53 * terms)
+    assert (err[~ill] <= bound).all(), (key, rule, float(err[~ill].max()), bound)       # the issue's bound
+    squares = np.abs(got * got - want * want) / (scale * scale)
+    assert (squares[ill] <= bound).all(), (key, rule, float(squares[ill].max()), bound)
+    return float(err[~ill].max()) if (~ill).any() else 0.0, int(ill.sum())
+
+
+def sum_of_terms(want, key):
+    """T = sum_ij |rho_ij r_i r_j| of every entry of the combined quantity `key`, from the restatement's modal values."""
+    r = np.abs(want["modal_" + key])
+    return np.einsum("ij,gi...,gj...->g...", np.abs(want["rho"]), r, r)
+
+
+def check_parity(run, what, cases=CASES):
+    """The kernels against the restatement on the device's OWN shapes and eigenvalues (NaN beyond n_modes)."""
+    for rule, mm in cases:
+        out = spectrum(run, rule, mm)
+        for b, d in enumerate(run.arrays):
+            nJ = len(d["xyz"])
+            phi, lam = np.ascontiguousarray(run.phi[b, :, :nJ]), run.lam[b]
+            want = restated(d, phi, lam, rule, mm, run.mass_scale)
+            bound = class_bound(len(d["conn"]), "a_float64_against_longdouble", 1e-11)
+            assert int(out["n_modes"][b]) == int(run.n_modes[b])
+            for key in S.KEYS:
+                terms = sum_of_terms(want, key) if key in ROOTS and rule in ("srss", "cqc") else None
+                worst, through_squares = check_entries(key, rule, cut(out, b, key, d), want[key], terms, bound)
+                print(f"{what} {rule} missing={mm} truss {b} {key}: parity {worst:.2e} (bound {bound:.1e})"
+                      + (f", {through_squares} of {want[key].size} entries through their squares" if through_squares else ""))
+
+
+# ---- kernel parity -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("config", sorted(CONFIGS))
+def test_parity_of_every_fixture(config):
+    """bar-6 has 5 free DOFs < p (n_modes < p, NaN eigenvalues), bar-10 exactly 8; bar-942 once."""
+    for name in SINGLE:
+        if name != BIG or config == "general":
+            check_parity(run_of(name, config), f"{name} [{config}]")
+
+
+@pytest.mark.parametrize("config", sorted(CONFIGS))
+def test_parity_of_the_ragged_batch(config):
+    """bar-6, bar-25, bar-72 and two cube-7 cases in one padded batch, with joint masses and mass_scale = 0.5."""
+    run = run_of("ragged", config)
+    assert run.packed.nJ_max > min(len(d["joint"]) for d in run.datas)
+    check_parity(run, f"ragged [{config}]")
+
+
+def test_parity_of_a_truss_of_more_than_256_joints():
+    """Two copies of bar-942 in one truss (test_gpu_mode_gradients): 488 joints, 1884 members - every loop strides."""
+    base = H.load_json(BIG)
+    nJ = len(base["joint"])
+    data = {"joint": base["joint"] + base["joint"], "force": base["force"],
+            "member": base["member"] + [[[j0 + nJ, j1 + nJ], [a, 1.3 * e, rho]] for (j0, j1), (a, e, rho) in base["member"]]}
+    run = Run([data])
+    assert run.packed.nJ_max == 488 > 256 and run.packed.nM_max == 1884
+    check_parity(run, "bar-942 twice", cases=[("cqc", True)])
+
+
+# ---- truth -------------------------------------------------------------------------------------------------------------
+_seven = {}
+
+
+def truth_run(name):
+    """The run whose modes are compared with `eigh`'s: bar-120 with its seven lowest (tests/test_spectrum.py)."""
+    if modes_of(name) == P:
+        return run_of(name)
+    if name not in _seven:
+        _seven[name] = Run([H.load_json(name)], p=modes_of(name))
+    return _seven[name]
+
+
+@pytest.mark.parametrize("name", SINGLE)
+def test_truth_against_eigh(name):
+    """CQC everywhere; SRSS and ABS, and the per-mode values, where the spectrum is simple."""
+    run = truth_run(name)
+    d = run.arrays[0]
+    bound = class_bound(len(d["conn"]), "b_iteration_against_eigh", 1e-9)
+    for rule in RULES:
+        if name in CLUSTERS and rule != "cqc":
+            continue
+        out = spectrum(run, rule)
+        got = {k: cut(out, 0, k, d) for k in S.KEYS}
+        want = S.exact_response(d, run.p, DIRS, PERIODS, ACCEL, zeta=ZETA, rule=rule, missing_mass=True)
+        n = want["gamma"].shape[1]
+        got = {k: (v[:, :n] if k in ("gamma", "sa", "meff") else
+                   np.concatenate([v[:, :n], v[:, run.p:]], axis=1) if k.startswith("modal_") else v) for k, v in got.items()}
+        diffs = truth_differences(name, got, want, n, rule)
+        assert len(diffs) == (len(S.KEYS) if name in SIMPLE + [BIG] else 8)
+        for key, diff in diffs.items():
+            print(f"{name} {rule} {key}: truth {diff:.2e} (bound {bound:.1e})")
+            assert diff <= bound, (name, rule, key, diff, bound)
+
+
+# ---- the identities on the device's numbers ---------------------------------------------------------------------------
+def joint_masses(d, mass_scale):
+    """m_j of every joint (include/trs_modes.h) from the arrays of a truss."""
+    length = np.sqrt(((d["xyz"][d["conn"][:, 1]] - d["xyz"][d["conn"][:, 0]]) ** 2).sum(1))
+    half = 0.5 * (d["A"] * length * d["rho"])
+    mj = np.zeros(len(d["xyz"]))
+    np.add.at(mj, d["conn"][:, 0], half)
+    np.add.at(mj, d["conn"][:, 1], half)
+    return mass_scale * mj + d["joint_mass"]
+
+
+@pytest.mark.parametrize("kind", ["ragged", "bar-10_input_0", "bar-47_input_0"])
+def test_identities_on_the_devices_numbers(kind):
+    """(c) per slot, reactions . direction = -(the slot's base shear), with the test's table; (b) under a flat spectrum
+    Sa = zpa = a0 the plain sum of the signed modal displacements and the missing-mass vector is the static answer to
+    a0 M iota - taken from `solve_cases`, another kernel family on the same factor."""
+    import torch
+    if kind == "ragged":
+        datas, jm = ragged_masses()
+        run = Run(datas, joint_mass=jm, mass_scale=RAGGED_SCALE, reorder="device")
+    else:
+        run = Run([H.load_json(kind)], reorder="device")
+    out = spectrum(run, "srss")
+    p = run.p
+    for b, d in enumerate(run.arrays):
+        shear = np.concatenate([out["gamma"][b] ** 2 * out["sa"][b],
+                                (ACCEL[:, 0] * (out["mtot"][b] - (out["gamma"][b] ** 2).sum(1)))[:, None]], axis=1)
+        react = -np.einsum("gvja,ga->gv", out["modal_R"][b], DIRS)
+        assert np.abs(react - shear).max() <= IDENTITY_TOL * np.abs(shear).max(), (kind, b, react, shear)
+        assert (out["meff"][b].sum(1) <= 1 + IDENTITY_TOL).all() and (out["meff"][b] >= 0).all()
+    a0 = 0.7
+    flat = spectrum(run, "abs", periods=[0.0, 1.0], accel=np.full([3, 2], a0))
+    loads = np.zeros([len(run.arrays), 3, run.packed.nJ_max, 3])
+    for b, d in enumerate(run.arrays):
+        nJ = len(d["xyz"])
+        loads[b, :, :nJ] = a0 * joint_masses(d, run.mass_scale)[None, :, None] * DIRS[:, None, :] * d["free"][None]
+    static = run.db.solve_cases(torch.from_numpy(loads).to("cuda:0"))["u"].cpu().numpy()      # (bumps the generation)
+    for b in range(len(run.arrays)):
+        total = flat["modal_u"][b].sum(1)
+        assert np.abs(total - static[b]).max() <= IDENTITY_TOL * np.abs(static[b]).max(), (kind, b)
+    with pytest.raises(ValueError, match="stale"):
+        run.db.response_spectrum(DIRS, PERIODS, ACCEL)
+
+
+@pytest.mark.parametrize("name", ["bar-6_input_0", "bar-10_input_0"])
+def test_all_modes_leave_no_missing_mass(name):
+    """p = 8 >= the free DOFs of bar-6 (5) and bar-10 (8): the effective masses sum to 1 and the missing-mass slot
+    vanishes."""
+    run = run_of(name)
+    out = spectrum(run, "cqc")
+    assert int(out["n_modes"][0]) == int(run.arrays[0]["free"].sum()) <= P
+    live = out["mtot"][0] > 0
+    assert live.any() and np.abs(out["meff"][0].sum(1)[live] - 1).max() <= IDENTITY_TOL
+    for key in ("modal_u", "modal_N", "modal_R"):
+        assert np.abs(out[key][0][:, P]).max() <= IDENTITY_TOL * np.abs(out[key][0]).max(), key
+
+
+# ---- bits --------------------------------------------------------------------------------------------------------------
+def assert_same(a, b, what):
+    assert sorted(a) == sorted(b)
+    for key in a:
+        np.testing.assert_array_equal(a[key], b[key], err_msg=f"{what} {key}")
+
+
+@pytest.mark.parametrize("kind", ["ragged", BIG, "bar-47_input_0"])
+def test_the_general_form_equals_the_table_form(kind):
+    for reorder in ("", "-reorder"):
+        for rule, mm in (("cqc", True), ("abs", False)):
+            assert_same(spectrum(run_of(kind, "general" + reorder), rule, mm),
+                        spectrum(run_of(kind, "table" + reorder), rule, mm), f"{kind}{reorder} {rule}")
+
+
+@pytest.mark.parametrize("config", ["general", "general-reorder"])
+def test_a_truss_alone_equals_the_truss_in_the_ragged_batch(config):
+    run = run_of("ragged", config)
+    whole = spectrum(run)
+    datas, jm = ragged_masses()
+    for b in (0, 2, 4):
+        d = run.arrays[b]
+        nJ = len(datas[b]["joint"])
+        alone = Run([datas[b]], joint_mass=jm[b:b + 1, :nJ], mass_scale=RAGGED_SCALE, **CONFIGS[config])
+        mine = spectrum(alone)
+        for key in S.KEYS:
+            np.testing.assert_array_equal(cut(mine, 0, key, d), cut(whole, b, key, d), err_msg=f"truss {b} {key}")
+
+
+def test_repeats_streams_and_mode_gradients_afterwards():
+    """A second call gives the first one's bits, a call on a side stream those of the current stream, and
+    `mode_gradients` the same bits before and after `response_spectrum(missing_mass=True)`: nothing it reads is touched,
+    nothing is bumped."""
+    import torch
+    run = run_of("ragged", "table-reorder")
+    before = run.gradients()
+    seen = run.db.generation
+    first = spectrum(run, "cqc", True)
+    assert run.db.generation == seen
+    assert_same(first, spectrum(run, "cqc", True, generation=seen), "second call")
+    after = run.gradients()
+    assert_same(before, after, "mode_gradients")
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream(device="cuda:0")
+    with torch.cuda.stream(side):
+        got = run.db.response_spectrum(DIRS, PERIODS, ACCEL, damping=ZETA, want_modal=True)
+    torch.cuda.synchronize()
+    assert_same(first, {k: v.cpu().numpy() for k, v in got.items()}, "side stream")
+    # a narrow `want` gives the same bits and no other key
+    only = spectrum(run, "cqc", True, want_modal=False, want=("N",))
+    assert sorted(only) == ["N", "base", "gamma", "meff", "mtot", "n_modes", "sa"]
+    np.testing.assert_array_equal(only["N"], first["N"])
+
+
+# ---- zeros, NaN and padding --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("config", ["general", "table-reorder"])
+def test_zeros_under_poisoned_outputs(config):
+    """Every entry is written: padding joints and members, the modes k >= n_modes (bar-6: five), held DOFs of u, free
+    DOFs of R, and without missing mass the slot p - under `out` tensors full of NaN."""
+    import torch
+    run = run_of("ragged", config)
+    b6 = RAGGED.index("bar-6_input_0")
+    assert int(run.n_modes[b6]) == 5 and np.isnan(run.lam[b6, 5:]).all()
+    for rule, mm in CASES:
+        shapes = run.db._spectrum_shapes(3, P, ("u", "N", "R"), True)
+        poison = {k: torch.full(s, float("nan"), dtype=torch.float64, device="cuda:0")
+                  for k, s in shapes.items() if k != "n_modes"}
+        out = run.db.response_spectrum(DIRS, PERIODS, ACCEL, damping=ZETA, rule=rule, missing_mass=mm, want_modal=True,
+                                       out=poison)
+        assert out["u"] is poison["u"]
+        out = {k: v.cpu().numpy() for k, v in out.items()}
+        for key in S.KEYS:
+            assert np.isfinite(out[key]).all(), (rule, mm, key)                  # no NaN anywhere, healthy trusses
+        for key in ("gamma", "sa", "meff"):
+            assert not out[key][b6, :, 5:].any() and out[key][b6, :, :5].any(), key
+        for key in ("modal_u", "modal_N", "modal_R"):
+            assert not out[key][b6, :, 5:P].any(), key
+            assert out[key][:, :, P].any() == mm, key
+        for b, d in enumerate(run.arrays):
+            nJ, nM = len(d["xyz"]), len(d["conn"])
+            assert not out["u"][b, :, nJ:].any() and not out["R"][b, :, nJ:].any() and not out["N"][b, :, nM:].any()
+            assert not out["modal_u"][b, :, :, nJ:].any() and not out["modal_N"][b, :, :, nM:].any()
+            assert not out["u"][b, :, :nJ][:, ~d["free"]].any() and not out["R"][b, :, :nJ][:, d["free"]].any()
+            assert out["u"][b].any() and out["R"][b].any() and out["N"][b].any() and (out["base"][b] > 0).all()
+        assert (out["u"] >= 0).all() and (out["N"] >= 0).all() and (out["R"] >= 0).all()
+
+
+# ---- guards ------------------------------------------------------------------------------------------------------------
+def test_guards_of_the_resident_state():
+    import torch
+    from python_stable_3d_truss_analysis_amd import batch
+    from python_stable_3d_truss_analysis_amd.utils import HipExtensionError
+    data = H.load_json("bar-25_input_0")
+    packed = batch.pack_json([data] * 2)
+    db = batch.DeviceBatch(packed, "cuda:0", use_small=False)
+    call = lambda **kw: db.response_spectrum(DIRS, PERIODS, ACCEL, **kw)
+    with pytest.raises(ValueError, match="no modes"):
+        call()
+    db.factor()
+    with pytest.raises(ValueError, match="no modes"):
+        call()
+    db.modes(4)
+    seen = db.generation
+    out = call(generation=seen)
+    assert db.generation == seen                                                     # nothing is bumped
+    assert sorted(out) == ["N", "R", "base", "gamma", "meff", "mtot", "n_modes", "sa", "u"]
+    assert list(out["u"].shape) == [2, 3, packed.nJ_max, 3] and list(out["gamma"].shape) == [2, 3, 4]
+    again = call(out=out)                                                            # and the call can be repeated
+    assert again["u"] is out["u"]
+    assert list(call(want_modal=True, want=("N",))["modal_N"].shape) == [2, 3, 5, packed.nM_max]
+    with pytest.raises(ValueError, match="rule"):
+        call(rule="sum")
+    with pytest.raises(ValueError, match="damping"):
+        call(damping=0.0)
+    with pytest.raises(ValueError, match="want"):
+        call(want=("f_ext",))
+    with pytest.raises(ValueError, match="out"):
+        call(out={"u": torch.zeros([2, 3, packed.nJ_max, 3], dtype=torch.float32, device="cuda:0")})
+    with pytest.raises(ValueError, match="out"):
+        call(out={"N": torch.zeros([2, 3, packed.nM_max], dtype=torch.float64)})       # a host tensor
+    with pytest.raises(ValueError, match="out"):
+        call(out={"gamma": torch.zeros([2, 3, 5], dtype=torch.float64, device="cuda:0")})
+    with pytest.raises(ValueError, match="stale"):
+        call(generation=seen - 1)
+    db.factor()
+    with pytest.raises(ValueError, match="stale"):
+        call()
+    db.modes(4)
+    call()
+    db.solve_cases(torch.zeros([2, 1, packed.nJ_max, 3], dtype=torch.float64, device="cuda:0"))
+    with pytest.raises(ValueError, match="stale"):
+        call()
+    # a shape whose vectors do not fit the LDS is refused by name: three copies of bar-942 in one truss (moduli x 1, 1.3, 1.7:
+    # a simple spectrum), 732 joints - eight modes and three missing-mass vectors take 193 KB
+    base = H.load_json("bar-942_input_0")
+    nJ = len(base["joint"])
+    data = {"joint": base["joint"] * 3, "force": base["force"],
+            "member": [[[j0 + c * nJ, j1 + c * nJ], [a, f * e, rho]] for c, f in enumerate((1.0, 1.3, 1.7))
+                       for (j0, j1), (a, e, rho) in base["member"]]}
+    big = batch.DeviceBatch(batch.pack_json([data]), "cuda:0", use_small=False)
+    assert big.lib.trs_rs_fits(big.nJ_max, big.nM_max, 8) == 0 and big.lib.trs_rs_fits(big.nJ_max, big.nM_max, 1) == 1
+    big.factor()
+    big.modes(8)
+    with pytest.raises(HipExtensionError, match="trs_rs_fits"):
+        big.response_spectrum(DIRS, PERIODS, ACCEL)
+    big.modes(1)
+    assert bool(big.response_spectrum(DIRS, PERIODS, ACCEL)["N"].isfinite().all())
+
+
+# ---- the drivers above the resident batch -----------------------------------------------------------------------------
+def test_solve_response_spectrum_and_the_truss_method():
+    from python_stable_3d_truss_analysis_amd import Truss, batch
+    from oracle import truss_oracle as orc
+    run = run_of("ragged", "general")
+    want = spectrum(run, "cqc", True)
+    datas, jm = ragged_masses()
+    res = batch.solve_response_spectrum(batch.pack_json(datas), DIRS, PERIODS, ACCEL, p=P, damping=ZETA, joint_mass=jm,
+                                        mass_scale=RAGGED_SCALE, want_modal=True)
+    np.testing.assert_array_equal(res.eigenvalue, run.lam)
+    np.testing.assert_array_equal(res.omega, np.sqrt(run.lam))
+    np.testing.assert_array_equal(res.n_modes, run.n_modes)
+    assert (res.info == 0).all() and (res.iters > 0).all()
+    fields = {"gamma": res.gamma, "sa": res.sa, "meff": res.meff, "mtot": res.mtot, "base": res.base, "u": res.displace,
+              "N": res.force, "R": res.reaction, "modal_u": res.modal_displace, "modal_N": res.modal_force,
+              "modal_R": res.modal_reaction}
+    for key, got in fields.items():
+        np.testing.assert_array_equal(got, want[key], err_msg=key)               # the buckets trim; the bits stay
+    np.testing.assert_allclose(res.force_all, np.sqrt((want["N"] ** 2).sum(1)), rtol=1e-14)
+    np.testing.assert_allclose(res.displace_all, np.sqrt((want["u"] ** 2).sum(1)), rtol=1e-14)
+    np.testing.assert_allclose(res.reaction_all, np.sqrt((want["R"] ** 2).sum(1)), rtol=1e-14)
+    # two size buckets, results left on the device
+    import torch
+    from python_stable_3d_truss_analysis_amd.batch import size_buckets
+    mixed = batch.pack_json(datas + [H.load_json(BIG)])
+    assert len(list(size_buckets(mixed, 64 << 30))) >= 2
+    dev = batch.solve_response_spectrum(mixed, DIRS[:1], PERIODS, ACCEL[:1], p=4, rule="srss", missing_mass=False,
+                                        on_device=True)
+    assert isinstance(dev.force, torch.Tensor) and dev.force.is_cuda and dev.modal_force is None
+    assert list(dev.force.shape) == [6, 1, mixed.nM_max] and (dev.info == 0).all() and bool(dev.force[5].any())
+    one = batch.solve_response_spectrum(batch.pack_json([H.load_json(BIG)]), DIRS[:1], PERIODS, ACCEL[:1], p=4, rule="srss",
+                                        missing_mass=False)
+    np.testing.assert_array_equal(dev.force[5].cpu().numpy(), one.force[0])
+    # the model's method, in the truss's own ids, against the restatement on eigh's shapes
+    name = "bar-25_input_0"
+    data = H.load_json(name)
+    truss = Truss(orc.truss_dim(data)).LoadFromJSON(os.path.join(H.GOLDEN, "data", name + ".json"))
+    before = truss.Serialize()
+    out = truss.ResponseSpectrum(DIRS, PERIODS, ACCEL, nModes=6, damping=ZETA, rule="cqc")
+    assert truss.Serialize() == before
+    assert sorted(out) == ["base", "displace", "displace_all", "eigenvalue", "force", "force_all", "gamma", "meff", "mtot",
+                           "omega", "reaction", "reaction_all", "sa"]
+    d = G.arrays(data)
+    ref = S.exact_response(d, 6, DIRS, PERIODS, ACCEL, zeta=ZETA, rule="cqc", missing_mass=True)
+    bound = class_bound(len(d["conn"]), "b_iteration_against_eigh", 1e-9)
+    for mine, key in (("displace", "u"), ("force", "N"), ("reaction", "R"), ("base", "base"), ("sa", "sa"), ("meff", "meff")):
+        assert out[mine].shape == ref[key].shape, mine
+        assert G.scaled_difference(out[mine], ref[key]) <= bound, mine
+    assert G.scaled_difference(out["force_all"], np.sqrt((ref["N"] ** 2).sum(0))) <= bound
+    masses = {j: 2.0 + j for j in range(0, len(data["joint"]), 3)}
+    out2 = truss.ResponseSpectrum(DIRS[:2], PERIODS, ACCEL[:2], nModes=3, rule="abs", missingMass=False, jointMasses=masses,
+                                  massScale=0.5)
+    assert out2["force"].shape == (2, len(data["member"])) and out2["gamma"].shape == (2, 3)
+    assert np.isfinite(out2["force"]).all() and out2["force"].any() and (out2["mtot"] > 0).all()
