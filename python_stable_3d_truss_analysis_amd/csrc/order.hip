@@ -20,13 +20,16 @@
 //                         level is rank-sorted by (parent position, degree, id) - which IS the queue order of
 //                         the serial algorithm; three sweeps per component;
 //   phase B (per WAVE)    the four waves take different candidates at the same time, no work-group barriers: a
-//                         sweep is ONE rank sort of 64-bit keys (bin, bin, bin, id), pricing is a wave scan of
-//                         the free-DOF counts, a neighbour minimum per joint, integer atomic minima per row
-//                         chunk and a suffix minimum with shuffles;
+//                         sweep is ONE sort of the keys (bin, bin, bin, position in the id list) - 32-bit keys of
+//                         up to 256 free joints in the wave's registers by a bitonic network (trs_wavesort.h),
+//                         a rank sort over the wave's LDS slice beyond that and for the rare 64-bit keys -,
+//                         pricing is a wave scan of the free-DOF counts, a neighbour minimum per joint, integer
+//                         atomic minima per row chunk and a suffix minimum with shuffles;
 //   phase C (work-group)  the cheapest (cost, evaluation order) wins; permutation, envelope reach (the launch hint
 //                         of trs_solver.h; kept by the wave that priced the winner) and, if asked, the renumbered
 //                         inputs go to HBM.
 #include "trs_common.h"
+#include "trs_wavesort.h"
 #include "../../include/trs_solver.h"
 #include <type_traits>
 
@@ -47,6 +50,11 @@ static_assert(NT == 128 || NT == 256 || NT == 512, "two, four or eight waves");
 constexpr int ID_BITS = 13;                 // joint ids in the sort keys: nJ_max < 8192
 constexpr int PERMANENT = 0x40000000;       // visit stamp of a joint that has its final Cuthill-McKee number
 constexpr unsigned long long NO_COST = ~0ull;
+#ifndef TRS_ORDER_WAVESORT_MAX        // 256 (four keys per lane) keeps the kernel at the 80 VGPRs and 10 spilled values it had
+#define TRS_ORDER_WAVESORT_MAX 256    // with the rank sort alone; 512 (eight per lane) spills 14 (60 instead of 44 B of scratch)
+#endif
+constexpr int WAVESORT_MAX = TRS_ORDER_WAVESORT_MAX;   // free joints up to which a sweep's 32-bit keys are sorted in registers
+static_assert(WAVESORT_MAX == 256 || WAVESORT_MAX == 512, "four or eight keys per lane");
 constexpr int RCM_BELOW = 128;              // effort 3: free joints below which the Cuthill-McKee candidates are still
                                             // priced (= TRS_ORDER_RCM_BELOW of csrc/reorder.c)
 
@@ -764,16 +772,37 @@ __global__ __launch_bounds__(NT, TRS_ORDER_MIN_WG) void trs_joint_order_kernel(
             const int ax = i == 0 ? first_ax : (i <= first_ax ? i - 1 : i);
 #endif
             const int a0 = axis_of(ax, 0), a1 = axis_of(ax, 1), a2 = axis_of(ax, 2);
-            // lexicographic by (bin a0, bin a1, bin a2, id): ONE rank sort.  x = position in the ascending id
-            // list, so (bins, x) orders like (bins, id).  32-bit keys when the three bin fields and x fit (any
-            // lattice-like truss: a few dozen bins per axis) - four keys per LDS read, one compare each -,
-            // 64-bit keys otherwise.
-            if (!wide_keys) {
-                for (int x = lane; x < nf; x += 64) {
-                    const int j = t.ids[x];
-                    k32[x] = ((((unsigned)t.bins[3 * j + a0] << bits_of(a1) | (unsigned)t.bins[3 * j + a1]) << bits_of(a2) |
-                               (unsigned)t.bins[3 * j + a2]) << xbits) | (unsigned)x;
-                }
+            // lexicographic by (bin a0, bin a1, bin a2, id): ONE sort.  x = position in the ascending id list, so
+            // (bins, x) orders like (bins, id).  32-bit keys when the three bin fields and x fit (any lattice-like
+            // truss: a few dozen bins per axis), 64-bit keys otherwise.
+            auto key32 = [&](int x) {
+                const int j = t.ids[x];
+                return ((((unsigned)t.bins[3 * j + a0] << bits_of(a1) | (unsigned)t.bins[3 * j + a1]) << bits_of(a2) |
+                         (unsigned)t.bins[3 * j + a2]) << xbits) | (unsigned)x;
+            };
+            // up to WAVESORT_MAX free joints: the keys never touch LDS - key 64 r + lane in register r, padded with
+            // 0xffffffff to 64 R, sorted by the wave's bitonic network (trs_wavesort.h), and register r written as
+            // positions 64 r .. 64 r + 63 of the candidate.  The keys are distinct (x in the low bits), so this is
+            // the array the rank sort below produces.
+            auto wave_sort = [&](auto rc) {
+                constexpr int R = decltype(rc)::value;
+                unsigned v[R];
+#pragma unroll
+                for (int r = 0; r < R; ++r) v[r] = 64 * r + lane < nf ? key32(64 * r + lane) : 0xffffffffu;
+                int ln = lane;
+                asm volatile("" : "+v"(ln));   // the network's lane predicates are formed here, not kept in SGPRs across the sweeps
+                trs_wavesort::sort<R>(v, ln);
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+                    if (64 * r + lane < nf) cand[64 * r + lane] = t.ids[v[r] & ((1u << xbits) - 1)];
+            };
+            if (!wide_keys && nf <= WAVESORT_MAX) {
+                if (nf <= 64) wave_sort(std::integral_constant<int, 1>{});
+                else if (nf <= 128) wave_sort(std::integral_constant<int, 2>{});
+                else if (WAVESORT_MAX == 256 || nf <= 256) wave_sort(std::integral_constant<int, 4>{});
+                else if constexpr (WAVESORT_MAX == 512) wave_sort(std::integral_constant<int, 8>{});
+            } else if (!wide_keys) {   // more keys than a wave holds in registers: the rank sort over the wave's key slice
+                for (int x = lane; x < nf; x += 64) k32[x] = key32(x);
                 for (int x = nf + lane; x < ((nf + 3) & ~3); x += 64) k32[x] = 0xffffffffu;  // pad the last quad
                 __builtin_amdgcn_wave_barrier();
                 // a lane ranks up to R of its keys in ONE pass over the list: a quad of keys per LDS read is
@@ -804,7 +833,8 @@ __global__ __launch_bounds__(NT, TRS_ORDER_MIN_WG) void trs_joint_order_kernel(
                 for (; nf - x0 > 128; x0 += 256) rank_pass(std::integral_constant<int, 4>{}, x0);
                 if (nf - x0 > 64) rank_pass(std::integral_constant<int, 2>{}, x0);
                 else if (nf - x0 > 0) rank_pass(std::integral_constant<int, 1>{}, x0);
-            } else {
+            } else {   // 64-bit keys stay a rank sort: rare (huge coordinate ranges), two registers per key, and the
+                       // keys lie in the slices of this wave and its neighbour, which therefore sweeps nothing
                 for (int x = lane; x < nf; x += 64) {
                     const int j = t.ids[x];
                     keys[x] = ((unsigned long long)t.bins[3 * j + a0] << (32 + ID_BITS)) |
