@@ -46,25 +46,20 @@ __host__ __device__ inline AdjTables layout(Arena& a, int nJ_max, int nM_max) {
 }
 
 // ---- step 1: the reduced right-hand side of the adjoint system ------------------------------------------------------
-__global__ __launch_bounds__(256) void trs_adjoint_rhs_kernel(
-    const int L, const double* __restrict__ xyz, const TrsMembers mem, const double* __restrict__ gu,
-    const double* __restrict__ gf, const double* __restrict__ gN, const int* __restrict__ free_index,
-    const int* __restrict__ n_free, const int* __restrict__ nJ, const int* __restrict__ nM, const int nJ_max,
-    const int nM_max, const int* __restrict__ joint_in, double* __restrict__ F, const int ld_f) {
+// (The batch's joint_out slot holds joint_in here: the same map, read the other way.)
+__global__ __launch_bounds__(256) void trs_adjoint_rhs_kernel(const TrsBatch bt, const int L,
+                                                              const double* __restrict__ gu, const double* __restrict__ gf,
+                                                              const double* __restrict__ gN, double* __restrict__ F) {
     extern __shared__ double sh[];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int joints = nJ[b], members = nM[b];
-    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
+    const TrussView v = bt.truss(b);
+    const int nM_max = bt.nM_max, ld_f = bt.ld_f, ndof_max = v.ndof_max;
     trs_lds::Carve lds(sh);
-    const AdjTables t = layout(lds, nJ_max, nM_max);
+    const AdjTables t = layout(lds, bt.nJ_max, nM_max);
     double* gh = t.v0;  // g^: gf at the constrained DOFs, device numbering
     double* s = t.pm;   // member pseudo-force
-    const int* fi = free_index + (size_t)b * ndof_max;
-    const double* X = xyz + (size_t)b * ndof_max;
-    const size_t mbase = (size_t)b * nM_max;
-    const int* ji = joint_in != nullptr ? joint_in + (size_t)b * nJ_max : nullptr;
-    const int n = n_free[b], npad = trs_round_up(n, TRS_NB);
-    build_end_lists(t, mem, mbase, joints, members, nJ_max, tid);
+    const int n = v.nfree, npad = min(trs_round_up(n, TRS_NB), ld_f);
+    build_end_lists(t, v, tid);
     __syncthreads();
     for (int k = 0; k < L; ++k) {
         const size_t bk = (size_t)b * L + k;
@@ -73,34 +68,35 @@ __global__ __launch_bounds__(256) void trs_adjoint_rhs_kernel(
         const double* gNk = gN != nullptr ? gN + bk * nM_max : nullptr;
         double* f = F + bk * ld_f;
         __syncthreads();  // (the previous case's readers of gh and s are done)
-        for (int d = tid; d < ndof; d += 256) {
-            const int o = ji != nullptr ? 3 * ji[d / 3] + d % 3 : d;
-            gh[d] = (gfk != nullptr && fi[d] < 0) ? gfk[o] : 0.0;
+        for (int d = tid; d < v.ndof; d += 256) {
+            const int o = 3 * v.place(d / 3) + d % 3;
+            gh[d] = (gfk != nullptr && v.row_of(d) < 0) ? gfk[o] : 0.0;
         }
         __syncthreads();
-        for (int m = tid; m < members; m += 256) {
-            const int2 c = mem.ends(mbase + m);
-            const MemberGeom g = member_geom(X, c.x, c.y);
+        for (int m = tid; m < v.members; m += 256) {
+            const int2 c = v.ends(m).c;
+            const MemberGeom g = member_geom(v.X, c.x, c.y);
             // k c . (g^_j1 - g^_j0): the axial "force" of the field g^
-            const double proj = member_axial(g, mem.EA(mbase + m), gh, c.x, c.y);
-            s[m] = gNk != nullptr ? fma(mem.EA(mbase + m) / g.len, gNk[m], proj) : proj;
+            const double proj = member_axial(g, v.mem.EA(v.mbase + m), gh, c.x, c.y);
+            s[m] = gNk != nullptr ? fma(v.mem.EA(v.mbase + m) / g.len, gNk[m], proj) : proj;
         }
         __syncthreads();
-        for (int j = tid; j < joints; j += 256) {
-            if ((fi[3 * j] < 0) & (fi[3 * j + 1] < 0) & (fi[3 * j + 2] < 0)) continue;  // no free DOF here
+        for (int j = tid; j < v.joints; j += 256) {
+            const TrussView::Rows rows = v.rows(j);
+            if (rows.all_held()) continue;  // no free DOF here
             double r[3] = {0.0, 0.0, 0.0};
             const int* list = t.ends + t.start[j];
             const int deg = t.cnt[j];
             for (int i = 0; i < deg; ++i) {
                 const int m = list[i] >> 1, end = list[i] & 1;
-                const int2 c = mem.ends(mbase + m);
-                const MemberGeom g = member_geom(X, c.x, c.y);
+                const int2 c = v.ends(m).c;
+                const MemberGeom g = member_geom(v.X, c.x, c.y);
                 add_end_force(r, g.c, s[m], end);
             }
-            const int o = ji != nullptr ? 3 * ji[j] : 3 * j;
+            const int o = 3 * v.place(j);
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
-                const int row = fi[3 * j + a];
+                const int row = rows.r[a];
                 if (row >= 0) f[row] = guk != nullptr ? r[a] + guk[o + a] : r[a];
             }
         }
@@ -110,28 +106,23 @@ __global__ __launch_bounds__(256) void trs_adjoint_rhs_kernel(
 
 // ---- step 3: contraction of the adjoint field with the forward field ------------------------------------------------
 __global__ __launch_bounds__(256) void trs_adjoint_grad_kernel(
-    const int L, const double* __restrict__ xyz, const TrsMembers mem, const double* __restrict__ gf,
-    const double* __restrict__ gN, const int* __restrict__ free_index, const int* __restrict__ nJ,
-    const int* __restrict__ nM, const int nJ_max, const int nM_max, const double* __restrict__ Fu,
-    const double* __restrict__ Lam, const int ld_f, double* __restrict__ gA, double* __restrict__ gE,
-    double* __restrict__ gxyz, double* __restrict__ gloads, const int* __restrict__ joint_out) {
+    const TrsBatch bt, const int L, const double* __restrict__ gf, const double* __restrict__ gN,
+    const double* __restrict__ Fu, const double* __restrict__ Lam, double* __restrict__ gA, double* __restrict__ gE,
+    double* __restrict__ gxyz, double* __restrict__ gloads) {
     extern __shared__ double sh[];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int joints = nJ[b], members = nM[b];
-    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
+    const TrussView v = bt.truss(b);
+    const int nJ_max = bt.nJ_max, nM_max = bt.nM_max, ld_f = bt.ld_f, ndof = v.ndof, ndof_max = v.ndof_max;
+    const size_t mbase = v.mbase;
     trs_lds::Carve lds(sh);
     const AdjTables t = layout(lds, nJ_max, nM_max);
     double* u = t.v0;    // forward displacements of one case, device numbering
     double* mu = t.v1;   // adjoint field of that case
     double* acc = t.pm;  // sum over the cases of N_m t_m
-    const int* fi = free_index + (size_t)b * ndof_max;
-    const double* X = xyz + (size_t)b * ndof_max;
-    const size_t mbase = (size_t)b * nM_max;
-    const int* jo = joint_out != nullptr ? joint_out + (size_t)b * nJ_max : nullptr;
     const bool want_sections = (gA != nullptr) | (gE != nullptr);
     double* gx = gxyz != nullptr ? gxyz + (size_t)b * ndof_max : nullptr;
     if (gx != nullptr) {
-        build_end_lists(t, mem, mbase, joints, members, nJ_max, tid);
+        build_end_lists(t, v, tid);
         __syncthreads();
     }
     for (int k = 0; k < L; ++k) {
@@ -143,8 +134,8 @@ __global__ __launch_bounds__(256) void trs_adjoint_grad_kernel(
         double* glk = gloads != nullptr ? gloads + bk * ndof_max : nullptr;
         __syncthreads();  // (the previous case's readers of u and mu are done)
         for (int d = tid; d < ndof_max; d += 256) {
-            const int r = d < ndof ? fi[d] : -1;
-            const int o = jo != nullptr ? 3 * jo[d / 3] + d % 3 : d;
+            const int r = v.row_of(d);
+            const int o = 3 * v.place(d / 3) + d % 3;
             const double gfo = (gfk != nullptr && d < ndof) ? gfk[o] : 0.0;
             const double lam = r >= 0 ? lk[r] : 0.0;
             u[d] = r >= 0 ? uk[r] : 0.0;
@@ -153,10 +144,10 @@ __global__ __launch_bounds__(256) void trs_adjoint_grad_kernel(
         }
         __syncthreads();
         if (want_sections)
-            for (int m = tid; m < members; m += 256) {
-                const int2 c = mem.ends(mbase + m);
-                const MemberGeom g = member_geom(X, c.x, c.y);
-                const double EA = mem.EA(mbase + m);
+            for (int m = tid; m < v.members; m += 256) {
+                const int2 c = v.ends(m).c;
+                const MemberGeom g = member_geom(v.X, c.x, c.y);
+                const double EA = v.mem.EA(mbase + m);
                 const double axial = member_axial(g, EA, u, c.x, c.y);  // the bits of the recovery's N
                 double cm = 0.0;
 #pragma unroll
@@ -165,15 +156,15 @@ __global__ __launch_bounds__(256) void trs_adjoint_grad_kernel(
                 acc[m] = k == 0 ? axial * tm : fma(axial, tm, acc[m]);
             }
         if (gx != nullptr)
-            for (int j = tid; j < joints; j += 256) {
+            for (int j = tid; j < v.joints; j += 256) {
                 double r[3] = {0.0, 0.0, 0.0};
                 const int* list = t.ends + t.start[j];
                 const int deg = t.cnt[j];
                 for (int i = 0; i < deg; ++i) {
                     const int m = list[i] >> 1, end = list[i] & 1;
-                    const int2 c = mem.ends(mbase + m);
-                    const MemberGeom g = member_geom(X, c.x, c.y);
-                    const double kl = mem.EA(mbase + m) / g.len / g.len;
+                    const int2 c = v.ends(m).c;
+                    const MemberGeom g = member_geom(v.X, c.x, c.y);
+                    const double kl = v.mem.EA(mbase + m) / g.len / g.len;
                     double du[3], dm[3], cu = 0.0, cm = 0.0;
 #pragma unroll
                     for (int a = 0; a < 3; ++a) {
@@ -190,20 +181,20 @@ __global__ __launch_bounds__(256) void trs_adjoint_grad_kernel(
                     add_end_force(r, gm, kl, end);
                 }
                 // accumulated over the cases in the output itself: joint j is this thread's in every case
-                const int o = jo != nullptr ? 3 * jo[j] : 3 * j;
+                const int o = 3 * v.place(j);
 #pragma unroll
                 for (int a = 0; a < 3; ++a) gx[o + a] = k == 0 ? r[a] : gx[o + a] + r[a];
             }
     }
     __syncthreads();
     for (int m = tid; m < nM_max; m += 256) {
-        const bool live = m < members;
-        if (gA != nullptr) gA[mbase + m] = live ? acc[m] / mem.area(mbase + m) : 0.0;
-        if (gE != nullptr) gE[mbase + m] = live ? acc[m] / modulus(mem, mbase + m) : 0.0;
+        const bool live = m < v.members;
+        if (gA != nullptr) gA[mbase + m] = live ? acc[m] / v.mem.area(mbase + m) : 0.0;
+        if (gE != nullptr) gE[mbase + m] = live ? acc[m] / modulus(v.mem, mbase + m) : 0.0;
     }
     if (gx != nullptr)
-        for (int j = joints + tid; j < nJ_max; j += 256) {
-            const int o = jo != nullptr ? 3 * jo[j] : 3 * j;
+        for (int j = v.joints + tid; j < nJ_max; j += 256) {
+            const int o = 3 * v.place(j);
             gx[o] = gx[o + 1] = gx[o + 2] = 0.0;
         }
 }
@@ -214,29 +205,23 @@ extern "C" size_t trs_adjoint_lds(int nJ_max, int nM_max) {
     return trs_lds::count([&](auto& a) { layout(a, nJ_max, nM_max); });
 }
 
-extern "C" int trs_adjoint_rhs_launch(int B, int L, int nJ_max, int nM_max, const double* xyz, const TrsMembers* members,
-                                      const double* gu, const double* gf, const double* gN, const int* free_index,
-                                      const int* n_free, const int* nJ, const int* nM, const int* joint_in, double* F,
-                                      int ld_f, hipStream_t stream) {
+int trs_adjoint_rhs_launch(int B, const TrsBatch& bt, int L, const double* gu, const double* gf, const double* gN, double* F,
+                           hipStream_t stream) {
     if (B <= 0 || L <= 0) return 0;
-    const size_t lds = trs_adjoint_lds(nJ_max, nM_max);
+    const size_t lds = trs_adjoint_lds(bt.nJ_max, bt.nM_max);
     if (lds > TRS_LDS_BYTES) return (int)hipErrorInvalidValue;
     trs_lds::raise_lds_once<trs_adjoint_rhs_kernel>();
-    hipLaunchKernelGGL(trs_adjoint_rhs_kernel, dim3(B), dim3(256), lds, stream, L, xyz, *members, gu, gf, gN, free_index,
-                       n_free, nJ, nM, nJ_max, nM_max, joint_in, F, ld_f);
+    hipLaunchKernelGGL(trs_adjoint_rhs_kernel, dim3(B), dim3(256), lds, stream, bt, L, gu, gf, gN, F);
     return (int)hipGetLastError();
 }
 
-extern "C" int trs_adjoint_grad_launch(int B, int L, int nJ_max, int nM_max, const double* xyz, const TrsMembers* members,
-                                       const double* gf, const double* gN, const int* free_index, const int* nJ,
-                                       const int* nM, const double* Fu, const double* Lam, int ld_f, double* gA,
-                                       double* gE, double* gxyz, double* gloads, const int* joint_out,
-                                       hipStream_t stream) {
+int trs_adjoint_grad_launch(int B, const TrsBatch& bt, int L, const double* gf, const double* gN, const double* Fu,
+                            const double* Lam, double* gA, double* gE, double* gxyz, double* gloads, hipStream_t stream) {
     if (B <= 0 || L <= 0) return 0;
-    const size_t lds = trs_adjoint_lds(nJ_max, nM_max);
+    const size_t lds = trs_adjoint_lds(bt.nJ_max, bt.nM_max);
     if (lds > TRS_LDS_BYTES) return (int)hipErrorInvalidValue;
     trs_lds::raise_lds_once<trs_adjoint_grad_kernel>();
-    hipLaunchKernelGGL(trs_adjoint_grad_kernel, dim3(B), dim3(256), lds, stream, L, xyz, *members, gf, gN, free_index, nJ,
-                       nM, nJ_max, nM_max, Fu, Lam, ld_f, gA, gE, gxyz, gloads, joint_out);
+    hipLaunchKernelGGL(trs_adjoint_grad_kernel, dim3(B), dim3(256), lds, stream, bt, L, gf, gN, Fu, Lam, gA, gE, gxyz,
+                       gloads);
     return (int)hipGetLastError();
 }

@@ -40,32 +40,29 @@ __host__ __device__ inline MemberTables members_layout(Arena& a, int nJ_max) {
 
 size_t members_lds(int nJ_max) { return trs_lds::count([&](auto& a) { members_layout(a, nJ_max); }); }
 
-__global__ __launch_bounds__(256) void trs_bk_members_kernel(
-    const double* __restrict__ xyz, const TrsMembers mem, const int* __restrict__ free_index,
-    const int* __restrict__ n_free, const int* __restrict__ nJ, const int* __restrict__ nM, const int nJ_max,
-    const int nM_max, const double* __restrict__ uf, const int ld_uf, const double* __restrict__ theta_all,
-    double* __restrict__ N_out, int* __restrict__ ends_out, double* __restrict__ Mt, double* __restrict__ W) {
+// (The batch's ld_f is ld_uf here.)
+__global__ __launch_bounds__(256) void trs_bk_members_kernel(const TrsBatch bt, const double* __restrict__ uf,
+                                                             const double* __restrict__ theta_all,
+                                                             double* __restrict__ N_out, int* __restrict__ ends_out,
+                                                             double* __restrict__ Mt, double* __restrict__ W) {
     extern __shared__ double sh[];
     trs_lds::Carve lds(sh);
-    double* u = members_layout(lds, nJ_max).u;
+    double* u = members_layout(lds, bt.nJ_max).u;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int joints = min(max(nJ[b], 0), nJ_max), members = min(max(nM[b], 0), nM_max);
-    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
-    const int n = min(max(n_free[b], 0), ld_uf);
-    const int* fi = free_index + (size_t)b * ndof_max;
-    const double* X = xyz + (size_t)b * ndof_max;
-    const size_t mbase = (size_t)b * nM_max;
+    const TrussView v = bt.truss(b);
+    const int nM_max = bt.nM_max;
+    const size_t mbase = v.mbase;
     const double theta = theta_all != nullptr ? theta_all[b] : 0.0;
-    for (int d = tid; d < ndof_max; d += 256) {
-        const int r = d < ndof ? fi[d] : -1;
-        u[d] = (r >= 0 && r < n) ? uf[(size_t)b * ld_uf + r] : 0.0;
+    for (int d = tid; d < v.ndof_max; d += 256) {
+        const int r = v.row_of(d);
+        u[d] = r >= 0 ? uf[(size_t)b * bt.ld_f + r] : 0.0;
     }
     __syncthreads();
     for (int m = tid; m < nM_max; m += 256) {
         double* mt = Mt + (mbase + m) * 4;
         double* w = W + (mbase + m) * 6;
         int* e = ends_out + (mbase + m) * 2;
-        if (m >= members) {
+        if (m >= v.members) {
             N_out[mbase + m] = 0.0;
             e[0] = e[1] = -1;
 #pragma unroll
@@ -74,12 +71,11 @@ __global__ __launch_bounds__(256) void trs_bk_members_kernel(
             for (int a = 0; a < 6; ++a) w[a] = 0.0;
             continue;
         }
-        const int2 c = mem.ends(mbase + m);
-        e[0] = c.x;
-        e[1] = c.y;
-        const int j0 = min(max(c.x, 0), nJ_max - 1), j1 = min(max(c.y, 0), nJ_max - 1);
-        const MemberGeom geo = member_geom(X, j0, j1);
-        const double N = member_axial(geo, mem.EA(mbase + m), u, j0, j1);
+        const int2 raw = v.raw_ends(m), c = v.ends(m).c;   // (the ids go out as they are: the product tests them again)
+        e[0] = raw.x;
+        e[1] = raw.y;
+        const MemberGeom geo = member_geom(v.X, c.x, c.y);
+        const double N = member_axial(geo, v.mem.EA(mbase + m), u, c.x, c.y);
         const double g = N / geo.len;
         N_out[mbase + m] = N;
 #pragma unroll
@@ -119,30 +115,24 @@ int product_chunk(int nJ_max, int nM_max) {
     return 0;
 }
 
-__global__ __launch_bounds__(256) void trs_bk_product_kernel(
-    const int* __restrict__ ends_all, const double* __restrict__ Mt, const int* __restrict__ free_index,
-    const int* __restrict__ n_free, const int* __restrict__ nJ, const int* __restrict__ nM, const int nJ_max,
-    const int nM_max, const double* __restrict__ Y_all, double* __restrict__ G_all, const int ld_f, const int vc) {
+// (The batch's members are the int32 end joints that trs_bk_members wrote, nothing else.)
+__global__ __launch_bounds__(256) void trs_bk_product_kernel(const TrsBatch bt, const double* __restrict__ Mt,
+                                                             const double* __restrict__ Y_all, double* __restrict__ G_all,
+                                                             const int vc) {
     extern __shared__ double sh[];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int joints = min(max(nJ[b], 0), nJ_max), members = min(max(nM[b], 0), nM_max);
-    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
-    const int n = min(max(n_free[b], 0), ld_f), npad = trs_round_up(n, TRS_NB);   // (ld_f is a multiple of TRS_NB)
+    const TrussView v = bt.truss(b);
+    const int ld_f = bt.ld_f, joints = v.joints, members = v.members, ndof_max = v.ndof_max;
+    const int n = v.nfree, npad = trs_round_up(n, TRS_NB);   // (ld_f is a multiple of TRS_NB)
     trs_lds::Carve lds(sh);
-    const ProductTables t = product_layout(lds, nJ_max, nM_max, vc);
+    const ProductTables t = product_layout(lds, bt.nJ_max, bt.nM_max, vc);
     double *tab = t.tab, *ysh = t.ysh;
     int* far = t.far;
-    const size_t mbase = (size_t)b * nM_max;
-    const TrsMembers mem = TrsMembers{ends_all, nullptr, nullptr, nullptr, nullptr, nullptr};   // (int32 end joints only)
-    const int* fi = free_index + (size_t)b * ndof_max;
+    const size_t mbase = v.mbase;
     const double* Y = Y_all + (size_t)b * QB * ld_f;
     double* G = G_all + (size_t)b * QB * ld_f;
-    auto row_of = [&](int d) {   // the reduced row of DOF d, -1: held, past the truss's joints or outside the arrays
-        const int r = d < ndof ? fi[d] : -1;
-        return r < n ? r : -1;
-    };
-    build_end_lists(t, mem, mbase, joints, members, nJ_max, tid, InTruss{joints});
-    order_by_neighbour(t, far, mem, mbase, joints, tid);
+    build_end_lists(t, v, tid);
+    order_by_neighbour(t, far, v, tid);
     for (int i = tid; i < 4 * members; i += 256) tab[i] = Mt[mbase * 4 + i];
     for (int i = tid; i < QB * (npad - n); i += 256) {
         const int k = i / (npad - n), c = n + i - k * (npad - n);
@@ -152,13 +142,13 @@ __global__ __launch_bounds__(256) void trs_bk_product_kernel(
         __syncthreads();   // (the lists are sorted, the table is in place; the readers of the last chunk are done)
         for (int i = tid; i < vc * ndof_max; i += 256) {
             const int k = i / ndof_max, d = i - k * ndof_max;
-            const int r = row_of(d);
+            const int r = v.row_of(d);
             ysh[i] = r >= 0 ? Y[(size_t)(v0 + k) * ld_f + r] : 0.0;
         }
         __syncthreads();
         for (int i = tid; i < vc * joints; i += 256) {
             const int k = i / joints, j = i - k * joints;
-            const int rows[3] = {row_of(3 * j), row_of(3 * j + 1), row_of(3 * j + 2)};
+            const int rows[3] = {v.row_of(3 * j), v.row_of(3 * j + 1), v.row_of(3 * j + 2)};
             if ((rows[0] & rows[1] & rows[2]) < 0) continue;   // a joint without a free DOF owns no row
             const double* yk = ysh + (size_t)k * ndof_max;
             const double yj[3] = {yk[3 * j], yk[3 * j + 1], yk[3 * j + 2]};
@@ -420,48 +410,31 @@ __global__ __launch_bounds__(64) void trs_bk_step_kernel(const int p, const int*
 // ---- shapes ---------------------------------------------------------------------------------------------------------
 // One work-group per (truss, mode): the component of largest magnitude - the first in the caller's DOF order on a
 // tie - becomes +1 (an exact, order-free reduction), then the column goes out through free_index and joint_out.
-__global__ __launch_bounds__(256) void trs_bk_shapes_kernel(const int p, const int nJ_max,
-                                                            const double* __restrict__ X_all, const int ld_f,
-                                                            const int* __restrict__ free_index,
-                                                            const int* __restrict__ n_free, const int* __restrict__ nJ,
-                                                            const int* __restrict__ rank,
-                                                            const int* __restrict__ joint_out,
-                                                            double* __restrict__ phi) {
+__global__ __launch_bounds__(256) void trs_bk_shapes_kernel(const TrsBatch bt, const int p,
+                                                            const double* __restrict__ X_all,
+                                                            const int* __restrict__ rank, double* __restrict__ phi) {
     const int b = blockIdx.x / p, k = blockIdx.x - b * p, tid = threadIdx.x;
-    const int ndof = 3 * min(max(nJ[b], 0), nJ_max), ndof_max = 3 * nJ_max;
-    const int n = min(max(n_free[b], 0), ld_f);
+    const TrussView v = bt.truss(b);
     const bool delivered = k < min(p, rank[b]);
-    const int* fi = free_index + (size_t)b * ndof_max;
-    const int* jo = joint_out != nullptr ? joint_out + (size_t)b * nJ_max : nullptr;
-    const double* x = X_all + ((size_t)b * QB + k) * ld_f;
-    double* out = phi + (size_t)blockIdx.x * ndof_max;
-    auto row_of = [&](int d) {
-        const int r = (delivered && d < ndof) ? fi[d] : -1;
-        return r < n ? r : -1;
-    };
-    auto place_of = [&](int d) {   // where DOF d goes in the caller's numbering
-        const int j = d / 3;
-        int id = jo != nullptr ? jo[j] : j;
-        id = ((id >= 0) & (id < nJ_max)) ? id : j;
-        return 3 * id + d - 3 * j;
-    };
-    const double top = largest_component(x, ndof, tid, row_of, place_of);
-    for (int d = tid; d < ndof_max; d += 256) {
-        const int r = row_of(d);
-        out[place_of(d)] = (r >= 0 && top != 0.0) ? x[r] / top : 0.0;
+    const double* x = X_all + ((size_t)b * QB + k) * bt.ld_f;
+    double* out = phi + (size_t)blockIdx.x * v.ndof_max;
+    auto shape_row = [&](int d) { return delivered ? v.row_of(d) : -1; };   // (a mode that was not delivered: zeros)
+    const double top = largest_component(x, v.ndof, tid, shape_row, [&](int d) { return v.place_dof(d); });
+    for (int d = tid; d < v.ndof_max; d += 256) {
+        const int r = shape_row(d);
+        out[v.place_dof(d)] = (r >= 0 && top != 0.0) ? x[r] / top : 0.0;
     }
 }
 
-int bk_members_launch(int B, int nJ_max, int nM_max, const double* xyz, const TrsMembers& mem, const int* free_index,
-                      const int* n_free, const int* nJ, const int* nM, const double* uf, int ld_uf, const double* theta,
-                      double* N, int* ends, double* Mt, double* W, hipStream_t stream) {
-    if (B < 0 || nJ_max <= 0 || nM_max < 0 || ld_uf < 0 || !uf || !N || !ends || !Mt || !W)
+int bk_members_launch(int B, const TrsBatch& bt, const double* uf, const double* theta, double* N, int* ends, double* Mt,
+                      double* W, hipStream_t stream) {
+    if (B < 0 || bt.nJ_max <= 0 || bt.nM_max < 0 || bt.ld_f < 0 || !uf || !N || !ends || !Mt || !W)
         return (int)hipErrorInvalidValue;
     if (B == 0) return 0;
-    if (!trs_bk_fits(nJ_max, nM_max)) return (int)hipErrorInvalidValue;
+    if (!trs_bk_fits(bt.nJ_max, bt.nM_max)) return (int)hipErrorInvalidValue;
     trs_lds::raise_lds_once<trs_bk_members_kernel>();
-    hipLaunchKernelGGL(trs_bk_members_kernel, dim3(B), dim3(256), members_lds(nJ_max), stream, xyz, mem,
-                       free_index, n_free, nJ, nM, nJ_max, nM_max, uf, ld_uf, theta, N, ends, Mt, W);
+    hipLaunchKernelGGL(trs_bk_members_kernel, dim3(B), dim3(256), members_lds(bt.nJ_max), stream, bt, uf, theta, N, ends,
+                       Mt, W);
     return (int)hipGetLastError();
 }
 
@@ -480,8 +453,9 @@ int trs_bk_members(int B, int nJ_max, int nM_max, const double* xyz, const int32
                    const int32_t* free_index, const int32_t* n_free, const int32_t* nJ, const int32_t* nM,
                    const double* uf, int ld_uf, const double* theta, double* N, int32_t* ends, double* Mt, double* W,
                    void* stream) {
-    return bk_members_launch(B, nJ_max, nM_max, xyz, trs_members_general(conn, E, A), free_index, n_free, nJ, nM, uf,
-                             ld_uf, theta, N, ends, Mt, W, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_general(conn, E, A), free_index, n_free, nJ, nM,
+                                  nullptr, ld_uf);
+    return bk_members_launch(B, bt, uf, theta, N, ends, Mt, W, (hipStream_t)stream);
 }
 
 int trs_bk_members_tab(int B, int nJ_max, int nM_max, const double* xyz, const uint16_t* conn16, const uint8_t* type_idx,
@@ -489,8 +463,9 @@ int trs_bk_members_tab(int B, int nJ_max, int nM_max, const double* xyz, const u
                        const int32_t* nM, const double* uf, int ld_uf, const double* theta, double* N, int32_t* ends,
                        double* Mt, double* W, void* stream) {
     if (B > 0 && (!conn16 || !type_idx || !types)) return (int)hipErrorInvalidValue;
-    return bk_members_launch(B, nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), free_index, n_free, nJ,
-                             nM, uf, ld_uf, theta, N, ends, Mt, W, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), free_index, n_free, nJ,
+                                  nM, nullptr, ld_uf);
+    return bk_members_launch(B, bt, uf, theta, N, ends, Mt, W, (hipStream_t)stream);
 }
 
 int trs_bk_product(int B, int nJ_max, int nM_max, const int32_t* ends, const double* Mt, const int32_t* free_index,
@@ -502,8 +477,10 @@ int trs_bk_product(int B, int nJ_max, int nM_max, const int32_t* ends, const dou
     const int vc = nJ_max <= 65535 ? product_chunk(nJ_max, nM_max) : 0;
     if (vc < 1) return (int)hipErrorInvalidValue;
     trs_lds::raise_lds_once<trs_bk_product_kernel>();
-    hipLaunchKernelGGL(trs_bk_product_kernel, dim3(B), dim3(256), product_lds(nJ_max, nM_max, vc), (hipStream_t)stream,
-                       ends, Mt, free_index, n_free, nJ, nM, nJ_max, nM_max, Y, G, ld_f, vc);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, nullptr, trs_members_general(ends, nullptr, nullptr), free_index, n_free,
+                                  nJ, nM, nullptr, ld_f);
+    hipLaunchKernelGGL(trs_bk_product_kernel, dim3(B), dim3(256), product_lds(nJ_max, nM_max, vc), (hipStream_t)stream, bt,
+                       Mt, Y, G, vc);
     return (int)hipGetLastError();
 }
 
@@ -523,8 +500,8 @@ int trs_bk_shapes(int B, int p, int nJ_max, const double* X, int ld_f, const int
                   const int32_t* nJ, const int32_t* rank, const int32_t* joint_out, double* phi, void* stream) {
     if (B < 0 || p < 0 || p > QB || nJ_max <= 0 || ld_f < 0 || !X || !rank || !phi) return (int)hipErrorInvalidValue;
     if (B == 0 || p == 0) return 0;
-    hipLaunchKernelGGL(trs_bk_shapes_kernel, dim3((unsigned)B * (unsigned)p), dim3(256), 0, (hipStream_t)stream, p,
-                       nJ_max, X, ld_f, free_index, n_free, nJ, rank, joint_out, phi);
+    hipLaunchKernelGGL(trs_bk_shapes_kernel, dim3((unsigned)B * (unsigned)p), dim3(256), 0, (hipStream_t)stream,
+                       trs_batch_dofs(nJ_max, free_index, n_free, nJ, joint_out, ld_f), p, X, rank, phi);
     return (int)hipGetLastError();
 }
 

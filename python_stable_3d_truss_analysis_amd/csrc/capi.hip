@@ -407,18 +407,18 @@ int trs_solve_rows_tab(int B, int nJ_max, int nM_max, int n_max_bound, const dou
 }  // extern "C"
 
 // ---- load cases (include/trs_solver.h "Load cases"; csrc/cases.hip) ----
+int trs_gather_cases_launch(int, const TrsBatch&, int, const double*, double*, hipStream_t);
+int trs_recover_cases_launch(int, const TrsBatch&, int, const double*, const double*, double*, double*, double*,
+                             hipStream_t);
 extern "C" {
-int trs_gather_cases_launch(int, int, int, const double*, const int*, const int*, const int*, const int*, double*, int,
-                            hipStream_t);
 int trs_potrs_cases_launch(int, int, const int*, int, size_t, int, const double*, double*, int, const int*, hipStream_t);
-int trs_recover_cases_launch(int, int, int, int, const double*, const TrsMembers*, const double*, const int*, const int*,
-                             const int*, const double*, int, double*, double*, double*, const int*, hipStream_t);
 size_t trs_recover_cases_lds(int, int);
 
 int trs_gather_cases(int B, int L, int nJ_max, const double* loads, const int32_t* free_index, const int32_t* n_free,
                      const int32_t* nJ, const int32_t* joint_in, double* F, int ld_f, void* stream) {
     if (B < 0 || L < 0 || nJ_max < 0 || ld_f < 0) return (int)hipErrorInvalidValue;
-    return trs_gather_cases_launch(B, L, nJ_max, loads, free_index, n_free, nJ, joint_in, F, ld_f, (hipStream_t)stream);
+    return trs_gather_cases_launch(B, trs_batch_dofs(nJ_max, free_index, n_free, nJ, joint_in, ld_f), L, loads, F,
+                                   (hipStream_t)stream);
 }
 
 int trs_potrs_cases(int B, int L, const int32_t* n_free, int ld, int slab_rows, const double* S, double* F, int ld_f,
@@ -437,9 +437,9 @@ int trs_recover_cases(int B, int L, int nJ_max, int nM_max, const double* xyz, c
                       const int32_t* nM, const double* F, int ld_f, double* u, double* f_ext, double* N,
                       const int32_t* joint_out, void* stream) {
     if (B < 0 || L < 0) return (int)hipErrorInvalidValue;
-    const TrsMembers mem = trs_members_general(conn, E, A);
-    return trs_recover_cases_launch(B, L, nJ_max, nM_max, xyz, &mem, loads, free_index, nJ, nM, F, ld_f, u, f_ext, N,
-                                    joint_out, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_general(conn, E, A), free_index, nullptr, nJ, nM,
+                                  joint_out, ld_f);
+    return trs_recover_cases_launch(B, bt, L, loads, F, u, f_ext, N, (hipStream_t)stream);
 }
 
 int trs_recover_tab_cases(int B, int L, int nJ_max, int nM_max, const double* xyz, const uint16_t* conn16,
@@ -447,20 +447,17 @@ int trs_recover_tab_cases(int B, int L, int nJ_max, int nM_max, const double* xy
                           const int32_t* nJ, const int32_t* nM, const double* F, int ld_f, double* u, double* f_ext,
                           double* N, const int32_t* joint_out, void* stream) {
     if (B < 0 || L < 0 || (B > 0 && (!conn16 || !type_idx || !types))) return (int)hipErrorInvalidValue;
-    const TrsMembers mem = trs_members_table(conn16, type_idx, types);
-    return trs_recover_cases_launch(B, L, nJ_max, nM_max, xyz, &mem, loads, free_index, nJ, nM, F, ld_f, u, f_ext, N,
-                                    joint_out, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), free_index, nullptr, nJ,
+                                  nM, joint_out, ld_f);
+    return trs_recover_cases_launch(B, bt, L, loads, F, u, f_ext, N, (hipStream_t)stream);
 }
 }  // extern "C"
 
 // ---- adjoint gradients (include/trs_solver.h "Adjoint gradients"; csrc/adjoint.hip) ----
+int trs_adjoint_rhs_launch(int, const TrsBatch&, int, const double*, const double*, const double*, double*, hipStream_t);
+int trs_adjoint_grad_launch(int, const TrsBatch&, int, const double*, const double*, const double*, const double*, double*,
+                            double*, double*, double*, hipStream_t);
 extern "C" {
-int trs_adjoint_rhs_launch(int, int, int, int, const double*, const TrsMembers*, const double*, const double*,
-                           const double*, const int*, const int*, const int*, const int*, const int*, double*, int,
-                           hipStream_t);
-int trs_adjoint_grad_launch(int, int, int, int, const double*, const TrsMembers*, const double*, const double*, const int*,
-                            const int*, const int*, const double*, const double*, int, double*, double*, double*, double*,
-                            const int*, hipStream_t);
 size_t trs_adjoint_lds(int, int);
 
 int trs_adjoint_fits(int nJ_max, int nM_max) {
@@ -472,9 +469,9 @@ int trs_adjoint_rhs(int B, int L, int nJ_max, int nM_max, const double* xyz, con
                     const int32_t* free_index, const int32_t* n_free, const int32_t* nJ, const int32_t* nM,
                     const int32_t* joint_in, double* F, int ld_f, void* stream) {
     if (B < 0 || L < 0 || nJ_max < 0 || nM_max < 0 || ld_f < 0) return (int)hipErrorInvalidValue;
-    const TrsMembers mem = trs_members_general(conn, E, A);
-    return trs_adjoint_rhs_launch(B, L, nJ_max, nM_max, xyz, &mem, grad_u, grad_f_ext, grad_N, free_index, n_free, nJ, nM,
-                                  joint_in, F, ld_f, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_general(conn, E, A), free_index, n_free, nJ, nM,
+                                  joint_in, ld_f);
+    return trs_adjoint_rhs_launch(B, bt, L, grad_u, grad_f_ext, grad_N, F, (hipStream_t)stream);
 }
 
 int trs_adjoint_tab_rhs(int B, int L, int nJ_max, int nM_max, const double* xyz, const uint16_t* conn16,
@@ -483,9 +480,9 @@ int trs_adjoint_tab_rhs(int B, int L, int nJ_max, int nM_max, const double* xyz,
                         const int32_t* nM, const int32_t* joint_in, double* F, int ld_f, void* stream) {
     if (B < 0 || L < 0 || nJ_max < 0 || nM_max < 0 || ld_f < 0 || (B > 0 && (!conn16 || !type_idx || !types)))
         return (int)hipErrorInvalidValue;
-    const TrsMembers mem = trs_members_table(conn16, type_idx, types);
-    return trs_adjoint_rhs_launch(B, L, nJ_max, nM_max, xyz, &mem, grad_u, grad_f_ext, grad_N, free_index, n_free, nJ, nM,
-                                  joint_in, F, ld_f, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), free_index, n_free, nJ,
+                                  nM, joint_in, ld_f);
+    return trs_adjoint_rhs_launch(B, bt, L, grad_u, grad_f_ext, grad_N, F, (hipStream_t)stream);
 }
 
 int trs_adjoint_grad(int B, int L, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* E,
@@ -493,9 +490,9 @@ int trs_adjoint_grad(int B, int L, int nJ_max, int nM_max, const double* xyz, co
                      const int32_t* nJ, const int32_t* nM, const double* F, const double* Lam, int ld_f, double* gA,
                      double* gE, double* gxyz, double* gloads, const int32_t* joint_out, void* stream) {
     if (B < 0 || L < 0 || nJ_max < 0 || nM_max < 0 || ld_f < 0) return (int)hipErrorInvalidValue;
-    const TrsMembers mem = trs_members_general(conn, E, A);
-    return trs_adjoint_grad_launch(B, L, nJ_max, nM_max, xyz, &mem, grad_f_ext, grad_N, free_index, nJ, nM, F, Lam, ld_f,
-                                   gA, gE, gxyz, gloads, joint_out, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_general(conn, E, A), free_index, nullptr, nJ, nM,
+                                  joint_out, ld_f);
+    return trs_adjoint_grad_launch(B, bt, L, grad_f_ext, grad_N, F, Lam, gA, gE, gxyz, gloads, (hipStream_t)stream);
 }
 
 int trs_adjoint_tab_grad(int B, int L, int nJ_max, int nM_max, const double* xyz, const uint16_t* conn16,
@@ -505,8 +502,8 @@ int trs_adjoint_tab_grad(int B, int L, int nJ_max, int nM_max, const double* xyz
                          const int32_t* joint_out, void* stream) {
     if (B < 0 || L < 0 || nJ_max < 0 || nM_max < 0 || ld_f < 0 || (B > 0 && (!conn16 || !type_idx || !types)))
         return (int)hipErrorInvalidValue;
-    const TrsMembers mem = trs_members_table(conn16, type_idx, types);
-    return trs_adjoint_grad_launch(B, L, nJ_max, nM_max, xyz, &mem, grad_f_ext, grad_N, free_index, nJ, nM, F, Lam, ld_f,
-                                   gA, gE, gxyz, gloads, joint_out, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), free_index, nullptr, nJ,
+                                  nM, joint_out, ld_f);
+    return trs_adjoint_grad_launch(B, bt, L, grad_f_ext, grad_N, F, Lam, gA, gE, gxyz, gloads, (hipStream_t)stream);
 }
 }  // extern "C"

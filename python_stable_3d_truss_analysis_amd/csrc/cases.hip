@@ -33,22 +33,17 @@ constexpr int CG = 16;  // cases per group = the N of the MFMA tile
 // ---- gather ---------------------------------------------------------------------------------------------------------
 // F[b][k][free_index[b][dof]] = loads[b][k][3 joint_in[b][j] + a] for the free DOFs (dof = 3 j + a), zero on the
 // padding rows n_free[b] <= c < n_pad.  One work-group per (truss, case).
-__global__ __launch_bounds__(256) void trs_gather_cases_kernel(const int L, const int nJ_max,
-                                                               const double* __restrict__ loads,
-                                                               const int* __restrict__ free_index,
-                                                               const int* __restrict__ n_free, const int* __restrict__ nJ,
-                                                               const int* __restrict__ joint_in,
-                                                               double* __restrict__ F, const int ld_f) {
+// (The batch's joint_out slot holds joint_in here: the same map, read the other way.)
+__global__ __launch_bounds__(256) void trs_gather_cases_kernel(const TrsBatch bt, const int L,
+                                                               const double* __restrict__ loads, double* __restrict__ F) {
     const int bk = blockIdx.x, b = bk / L, tid = threadIdx.x;
-    const size_t ndof_max = (size_t)3 * nJ_max;
-    const double* ld_case = loads + (size_t)bk * ndof_max;
-    const int* fi = free_index + (size_t)b * ndof_max;
-    const int* ji = joint_in != nullptr ? joint_in + (size_t)b * nJ_max : nullptr;
-    double* f = F + (size_t)bk * ld_f;
-    const int ndof = 3 * nJ[b], n = n_free[b], npad = trs_round_up(n, TRS_NB);
-    for (int d = tid; d < ndof; d += 256) {
-        const int r = fi[d];
-        if (r >= 0) f[r] = ld_case[ji != nullptr ? 3 * ji[d / 3] + d % 3 : d];
+    const TrussView v = bt.truss(b);
+    const double* ld_case = loads + (size_t)bk * v.ndof_max;
+    double* f = F + (size_t)bk * bt.ld_f;
+    const int n = v.nfree, npad = min(trs_round_up(n, TRS_NB), bt.ld_f);
+    for (int d = tid; d < v.ndof; d += 256) {
+        const int r = v.row_of(d);
+        if (r >= 0) f[r] = ld_case[3 * v.place(d / 3) + d % 3];
     }
     for (int c = n + tid; c < npad; c += 256) f[c] = 0.0;
 }
@@ -281,26 +276,20 @@ __host__ __device__ inline RecoverTables recover_layout(Arena& a, int nJ_max, in
 // lists of the constrained joints are counting-sorted once, then per case u is staged in LDS (device numbering),
 // N and the reactions are formed by the SAME functions (trs_recover.h) in the same order, and u / f_ext go out through
 // joint_out.  f_ext at a free DOF is the case's applied load.  One work-group per truss.
-__global__ __launch_bounds__(256) void trs_recover_cases_kernel(
-    const int L, const double* __restrict__ xyz, const TrsMembers mem, const double* __restrict__ loads,
-    const int* __restrict__ free_index, const int* __restrict__ nJ, const int* __restrict__ nM, const int nJ_max,
-    const int nM_max, const double* __restrict__ F, const int ld_f, double* __restrict__ u_out,
-    double* __restrict__ f_out, double* __restrict__ N_out, const int* __restrict__ joint_out) {
+__global__ __launch_bounds__(256) void trs_recover_cases_kernel(const TrsBatch bt, const int L,
+                                                                const double* __restrict__ loads,
+                                                                const double* __restrict__ F, double* __restrict__ u_out,
+                                                                double* __restrict__ f_out, double* __restrict__ N_out) {
     extern __shared__ double sh[];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int joints = nJ[b], members = nM[b];
-    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
+    const TrussView v = bt.truss(b);
+    const int nJ_max = bt.nJ_max, nM_max = bt.nM_max, ld_f = bt.ld_f, ndof_max = v.ndof_max;
     trs_lds::Carve lds(sh);
     const RecoverTables t = recover_layout(lds, nJ_max, nM_max);
     double* u = t.u;
-    const int* fi = free_index + (size_t)b * ndof_max;
-    const double* X = xyz + (size_t)b * ndof_max;
-    const size_t mbase = (size_t)b * nM_max;
-    const int* jo = joint_out != nullptr ? joint_out + (size_t)b * nJ_max : nullptr;
-    auto constrained = [&](int j) { return (fi[3 * j] < 0) | (fi[3 * j + 1] < 0) | (fi[3 * j + 2] < 0); };
     // sorted by member id once (joint_reaction sorts in place; later cases find the lists sorted); the case loop opens
     // with the barrier that the builder leaves to its caller
-    build_end_lists(t, mem, mbase, joints, members, nJ_max, tid, constrained);
+    build_end_lists(t, v, tid, [&](int j) { return v.any_held(j); });
     for (int k = 0; k < L; ++k) {
         const size_t bk = (size_t)b * L + k;
         const double* fk = F + bk * ld_f;
@@ -309,54 +298,43 @@ __global__ __launch_bounds__(256) void trs_recover_cases_kernel(
         double* fo = f_out + bk * ndof_max;
         __syncthreads();  // (the previous case's readers of u are done)
         for (int d = tid; d < ndof_max; d += 256) {
-            const int r = d < ndof ? fi[d] : -1;
-            const double v = r >= 0 ? fk[r] : 0.0;
-            u[d] = v;
-            const int o = jo != nullptr ? 3 * jo[d / 3] + d % 3 : d;
-            uo[o] = v;
+            const int r = v.row_of(d);
+            const double val = r >= 0 ? fk[r] : 0.0;
+            u[d] = val;
+            const int o = 3 * v.place(d / 3) + d % 3;
+            uo[o] = val;
             if (r >= 0) fo[o] = lk[o];                    // free DOF: the applied load
-            else if (d >= ndof) fo[o] = 0.0;              // padding
+            else if (d >= v.ndof) fo[o] = 0.0;            // padding
         }
         __syncthreads();
         for (int m = tid; m < nM_max; m += 256) {
             double axial = 0.0;
-            if (m < members) {
-                const int2 c = mem.ends(mbase + m);
-                const MemberGeom g = member_geom(X, c.x, c.y);
-                axial = member_axial(g, mem.EA(mbase + m), u, c.x, c.y);
+            if (m < v.members) {
+                const int2 c = v.ends(m).c;
+                const MemberGeom g = member_geom(v.X, c.x, c.y);
+                axial = member_axial(g, v.mem.EA(v.mbase + m), u, c.x, c.y);
             }
             N_out[bk * nM_max + m] = axial;
         }
-        for (int j = tid; j < joints; j += 256) {
+        for (int j = tid; j < v.joints; j += 256) {
             const int deg = t.cnt[j];
-            if (deg == 0) {
-                // a constrained joint without members: zero reaction
-                if (constrained(j)) {
-                    const int o = jo != nullptr ? 3 * jo[j] : 3 * j;
-#pragma unroll
-                    for (int a = 0; a < 3; ++a)
-                        if (fi[3 * j + a] < 0) fo[o + a] = 0.0;
-                }
-                continue;
-            }
-            double r[3];
-            joint_reaction(t.ends + t.start[j], deg, mem, X, mbase, u, nullptr, r);
-            const int o = jo != nullptr ? 3 * jo[j] : 3 * j;
+            double r[3] = {0.0, 0.0, 0.0};   // (a constrained joint without members: zero reaction)
+            if (deg == 0 && !v.any_held(j)) continue;
+            if (deg != 0) joint_reaction(t.ends + t.start[j], deg, v, u, r);
+            const int o = 3 * v.place(j);
+            const TrussView::Rows rows = v.rows(j);   // (read here, behind the reaction: fewer scalars live across it)
 #pragma unroll
             for (int a = 0; a < 3; ++a)
-                if (fi[3 * j + a] < 0) fo[o + a] = r[a];
+                if (rows.held(a)) fo[o + a] = r[a];
         }
     }
 }
 
 }  // namespace
 
-extern "C" int trs_gather_cases_launch(int B, int L, int nJ_max, const double* loads, const int* free_index,
-                                       const int* n_free, const int* nJ, const int* joint_in, double* F, int ld_f,
-                                       hipStream_t stream) {
+int trs_gather_cases_launch(int B, const TrsBatch& bt, int L, const double* loads, double* F, hipStream_t stream) {
     if (B <= 0 || L <= 0) return 0;
-    hipLaunchKernelGGL(trs_gather_cases_kernel, dim3((unsigned)B * (unsigned)L), dim3(256), 0, stream, L, nJ_max, loads,
-                       free_index, n_free, nJ, joint_in, F, ld_f);
+    hipLaunchKernelGGL(trs_gather_cases_kernel, dim3((unsigned)B * (unsigned)L), dim3(256), 0, stream, bt, L, loads, F);
     return (int)hipGetLastError();
 }
 
@@ -377,15 +355,12 @@ extern "C" size_t trs_recover_cases_lds(int nJ_max, int nM_max) {
     return trs_lds::count([&](auto& a) { recover_layout(a, nJ_max, nM_max); });
 }
 
-extern "C" int trs_recover_cases_launch(int B, int L, int nJ_max, int nM_max, const double* xyz, const TrsMembers* members,
-                                        const double* loads, const int* free_index, const int* nJ, const int* nM,
-                                        const double* F, int ld_f, double* u, double* f_ext, double* N,
-                                        const int* joint_out, hipStream_t stream) {
+int trs_recover_cases_launch(int B, const TrsBatch& bt, int L, const double* loads, const double* F, double* u,
+                             double* f_ext, double* N, hipStream_t stream) {
     if (B <= 0 || L <= 0) return 0;
-    const size_t lds = trs_recover_cases_lds(nJ_max, nM_max);
+    const size_t lds = trs_recover_cases_lds(bt.nJ_max, bt.nM_max);
     if (lds > TRS_LDS_BYTES) return (int)hipErrorInvalidValue;
     trs_lds::raise_lds_once<trs_recover_cases_kernel>();
-    hipLaunchKernelGGL(trs_recover_cases_kernel, dim3(B), dim3(256), lds, stream, L, xyz, *members, loads, free_index,
-                       nJ, nM, nJ_max, nM_max, F, ld_f, u, f_ext, N, joint_out);
+    hipLaunchKernelGGL(trs_recover_cases_kernel, dim3(B), dim3(256), lds, stream, bt, L, loads, F, u, f_ext, N);
     return (int)hipGetLastError();
 }

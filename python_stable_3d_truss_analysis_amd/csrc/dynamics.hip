@@ -76,14 +76,11 @@ size_t dyn_lds(int nJ_max, int nM_max, int damped) {
     return trs_lds::count([&](auto& a) { layout(a, nJ_max, nM_max, damped != 0); });
 }
 
-// k c . (v_j1 - v_j0) of member mm for a joint-layout vector v, the end-joint ids clamped to the arrays
-__device__ __forceinline__ double member_force(const TrsMembers& mem, const size_t mm, const double* __restrict__ X,
-                                               const double* v, const int nJ_max) {
-    int2 c = mem.ends(mm);
-    c.x = min(max(c.x, 0), nJ_max - 1);
-    c.y = min(max(c.y, 0), nJ_max - 1);
-    const MemberGeom g = member_geom(X, c.x, c.y);
-    return member_axial(g, mem.EA(mm), v, c.x, c.y);
+// k c . (v_j1 - v_j0) of member m for a joint-layout vector v
+__device__ __forceinline__ double member_force(const TrussView& tr, const int m, const double* v) {
+    const int2 c = tr.ends(m).c;
+    const MemberGeom g = member_geom(tr.X, c.x, c.y);
+    return member_axial(g, tr.mem.EA(tr.mbase + m), v, c.x, c.y);
 }
 
 // The right-hand side of the next point at one free DOF: f + M [cu u + cv v + ca a] (+ beta_R (K w)) over s.  ONE
@@ -119,36 +116,27 @@ __device__ __forceinline__ void take_min(double* __restrict__ peak, int* __restr
 }
 
 __global__ __launch_bounds__(256) void trs_dyn_step_kernel(
-    const int L, const double* __restrict__ xyz, const TrsMembers mem, const int* __restrict__ free_index,
-    const int* __restrict__ n_free, const int* __restrict__ nJ, const int* __restrict__ nM, const int nJ_max,
-    const int nM_max, const double* __restrict__ Mf, const double* __restrict__ Pr, const double* __restrict__ scale,
-    const double* __restrict__ ag, const int T1, const int step, const int first, const DynCoef co, double* F, double* U,
-    double* V, double* Acc, const int ld_f, double* __restrict__ u_peak, int* __restrict__ u_step,
+    const TrsBatch bt, const int L, const double* __restrict__ Mf, const double* __restrict__ Pr,
+    const double* __restrict__ scale, const double* __restrict__ ag, const int T1, const int step, const int first,
+    const DynCoef co, double* F, double* U, double* V, double* Acc, double* __restrict__ u_peak, int* __restrict__ u_step,
     double* __restrict__ N_max, int* __restrict__ N_max_step, double* __restrict__ N_min, int* __restrict__ N_min_step,
     const int* __restrict__ mon_joint, const int Pj, const int* __restrict__ mon_member, const int Pm,
-    double* __restrict__ hist_u, double* __restrict__ hist_N, const int* __restrict__ joint_out) {
+    double* __restrict__ hist_u, double* __restrict__ hist_N) {
     extern __shared__ double sh[];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int joints = min(max(nJ[b], 0), nJ_max), members = min(max(nM[b], 0), nM_max);
-    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
-    const int n = min(max(n_free[b], 0), ld_f), npad = min(trs_round_up(n, TRS_NB), ld_f);
+    const TrussView tr = bt.truss(b);
+    const int nJ_max = bt.nJ_max, nM_max = bt.nM_max, ld_f = bt.ld_f;
+    const int joints = tr.joints, members = tr.members, ndof_max = tr.ndof_max;
+    const int n = tr.nfree, npad = min(trs_round_up(n, TRS_NB), ld_f);
     trs_lds::Carve lds(sh);
     const DynTables t = layout(lds, nJ_max, nM_max, true);
     double* ush = t.v;
-    const int* fi = free_index + (size_t)b * ndof_max;
-    const double* X = xyz + (size_t)b * ndof_max;
-    const size_t mbase = (size_t)b * nM_max;
-    const int* jo = joint_out != nullptr ? joint_out + (size_t)b * nJ_max : nullptr;
     const double* mf = Mf + (size_t)b * ld_f;
     const bool last = step == T1 - 1, init = first != 0;
     const bool damped = co.beta_r > 0.0;
     const bool stiff_term = damped & !last;
     // (the case loop opens with the barrier that the builder leaves to its caller)
-    if (stiff_term) build_end_lists(t, mem, mbase, joints, members, nJ_max, tid, InTruss{joints});
-    auto row_of = [&](int d) {   // the reduced row of DOF d, -1: held, past the truss's joints or outside the arrays
-        const int r = d < ndof ? fi[d] : -1;
-        return r < n ? r : -1;
-    };
+    if (stiff_term) build_end_lists(t, tr, tid);
     for (int l = 0; l < L; ++l) {
         const size_t bl = (size_t)b * L + l;
         double* f = F + bl * ld_f;
@@ -163,7 +151,7 @@ __global__ __launch_bounds__(256) void trs_dyn_step_kernel(
         __syncthreads();   // (the previous case's readers of ush and pm are done; the end lists are sorted)
         // ---- phase 1: the state, one thread per DOF ----
         for (int d = tid; d < ndof_max; d += 256) {
-            const int r = row_of(d);
+            const int r = tr.row_of(d);
             const int axis = d % 3;
             double u = 0.0;
             if (r >= 0) {
@@ -192,10 +180,7 @@ __global__ __launch_bounds__(256) void trs_dyn_step_kernel(
                     f[r] = next_rhs(co, false, load_at(sc_next, pr[r], m, ag_next, axis), m, u, v, a, 0.0);
             }
             ush[d] = u;
-            const int j = d / 3;
-            int id = jo != nullptr ? jo[j] : j;
-            id = ((id >= 0) & (id < nJ_max)) ? id : j;
-            take_max(u_peak, u_step, bl * ndof_max + 3 * id + axis, fabs(u), step, init);
+            take_max(u_peak, u_step, bl * ndof_max + 3 * tr.place(d / 3) + axis, fabs(u), step, init);
         }
         for (int c = n + tid; c < npad; c += 256) {   // the padding rows
             if (!last) f[c] = 0.0;
@@ -208,7 +193,7 @@ __global__ __launch_bounds__(256) void trs_dyn_step_kernel(
         __syncthreads();
         // ---- phase 2: member forces, envelopes, monitor rows ----
         for (int m = tid; m < nM_max; m += 256) {
-            const double axial = m < members ? member_force(mem, mbase + m, X, ush, nJ_max) : 0.0;
+            const double axial = m < members ? member_force(tr, m, ush) : 0.0;
             take_max(N_max, N_max_step, bl * nM_max + m, axial, step, init);
             take_min(N_min, N_min_step, bl * nM_max + m, axial, step, init);
         }
@@ -219,30 +204,28 @@ __global__ __launch_bounds__(256) void trs_dyn_step_kernel(
         for (int p = tid; p < Pm; p += 256) {
             const int m = mon_member[(size_t)b * Pm + p];
             hist_N[(bl * T1 + step) * Pm + p] =
-                ((m >= 0) & (m < members)) ? member_force(mem, mbase + m, X, ush, nJ_max) : 0.0;
+                ((m >= 0) & (m < members)) ? member_force(tr, m, ush) : 0.0;
         }
         if (!stiff_term) continue;
         // ---- phase 3: beta_R K_ff w into the right-hand side of the next point ----
         __syncthreads();   // (the readers of u in ush are done)
         for (int d = tid; d < ndof_max; d += 256) {
-            const int r = row_of(d);
+            const int r = tr.row_of(d);
             ush[d] = r >= 0 ? fma(co.a5, Ac[r], fma(co.a4, Vc[r], co.a1 * Uc[r])) : 0.0;
         }
         __syncthreads();
-        for (int m = tid; m < members; m += 256) t.pm[m] = member_force(mem, mbase + m, X, ush, nJ_max);
+        for (int m = tid; m < members; m += 256) t.pm[m] = member_force(tr, m, ush);
         __syncthreads();
         for (int j = tid; j < joints; j += 256) {
-            const int r3[3] = {row_of(3 * j), row_of(3 * j + 1), row_of(3 * j + 2)};
+            const int r3[3] = {tr.row_of(3 * j), tr.row_of(3 * j + 1), tr.row_of(3 * j + 2)};
             if ((r3[0] & r3[1] & r3[2]) < 0) continue;   // no free DOF here
             double kw[3] = {0.0, 0.0, 0.0};
             const int* list = t.ends + t.start[j];
             const int deg = t.cnt[j];
             for (int i = 0; i < deg; ++i) {
                 const int m = list[i] >> 1, end = list[i] & 1;
-                int2 c = mem.ends(mbase + m);
-                c.x = min(max(c.x, 0), nJ_max - 1);
-                c.y = min(max(c.y, 0), nJ_max - 1);
-                const MemberGeom g = member_geom(X, c.x, c.y);
+                const int2 c = tr.ends(m).c;
+                const MemberGeom g = member_geom(tr.X, c.x, c.y);
                 add_end_force(kw, g.c, t.pm[m], end);
             }
 #pragma unroll
@@ -267,50 +250,40 @@ __global__ __launch_bounds__(256) void trs_dyn_shift_kernel(const int* __restric
     *diag = fma(sigma, Mf[(size_t)b * ld_f + c], *diag);
 }
 
-__global__ __launch_bounds__(256) void trs_dyn_collect_kernel(const int L, const int nJ_max, const double* __restrict__ U,
+__global__ __launch_bounds__(256) void trs_dyn_collect_kernel(const TrsBatch bt, const int L, const double* __restrict__ U,
                                                               const double* __restrict__ V, const double* __restrict__ Acc,
-                                                              const int ld_f, const int* __restrict__ free_index,
-                                                              const int* __restrict__ nJ,
-                                                              const int* __restrict__ joint_out, double* __restrict__ u,
-                                                              double* __restrict__ v, double* __restrict__ a) {
+                                                              double* __restrict__ u, double* __restrict__ v,
+                                                              double* __restrict__ a) {
     const int bl = blockIdx.x, b = bl / L, tid = threadIdx.x;
-    const int ndof_max = 3 * nJ_max, ndof = 3 * min(max(nJ[b], 0), nJ_max);
-    const int* fi = free_index + (size_t)b * ndof_max;
-    const int* jo = joint_out != nullptr ? joint_out + (size_t)b * nJ_max : nullptr;
-    const size_t in = (size_t)bl * ld_f, out = (size_t)bl * ndof_max;
-    for (int d = tid; d < ndof_max; d += 256) {
-        int r = d < ndof ? fi[d] : -1;
-        r = r < ld_f ? r : -1;
-        const int j = d / 3;
-        int id = jo != nullptr ? jo[j] : j;
-        id = ((id >= 0) & (id < nJ_max)) ? id : j;
-        const size_t o = out + 3 * id + d % 3;
+    const TrussView tr = bt.truss(b);
+    const size_t in = (size_t)bl * bt.ld_f, out = (size_t)bl * tr.ndof_max;
+    for (int d = tid; d < tr.ndof_max; d += 256) {
+        const int r = tr.row_of(d);
+        const size_t o = out + tr.place_dof(d);
         u[o] = r >= 0 ? U[in + r] : 0.0;
         v[o] = r >= 0 ? V[in + r] : 0.0;
         a[o] = r >= 0 ? Acc[in + r] : 0.0;
     }
 }
 
-int dyn_step_launch(int B, int L, int nJ_max, int nM_max, const double* xyz, const TrsMembers& mem,
-                    const int* free_index, const int* n_free, const int* nJ, const int* nM, const double* Mf,
-                    const double* Pr, const double* scale, const double* ag, int T1, int n, int first, double dt,
-                    double beta, double gamma, double damp_mass, double damp_stiff, double* F, double* U, double* V,
-                    double* Acc, int ld_f, double* u_peak, int* u_step, double* N_max, int* N_max_step, double* N_min,
-                    int* N_min_step, const int* mon_joint, int Pj, const int* mon_member, int Pm, double* hist_u,
-                    double* hist_N, const int* joint_out, hipStream_t stream) {
-    if (B < 0 || L < 0 || nJ_max <= 0 || nM_max < 0 || ld_f < 0 || Pj < 0 || Pm < 0) return (int)hipErrorInvalidValue;
+int dyn_step_launch(int B, const TrsBatch& bt, int L, const double* Mf, const double* Pr, const double* scale,
+                    const double* ag, int T1, int n, int first, double dt, double beta, double gamma, double damp_mass,
+                    double damp_stiff, double* F, double* U, double* V, double* Acc, double* u_peak, int* u_step,
+                    double* N_max, int* N_max_step, double* N_min, int* N_min_step, const int* mon_joint, int Pj,
+                    const int* mon_member, int Pm, double* hist_u, double* hist_N, hipStream_t stream) {
+    if (B < 0 || L < 0 || bt.nJ_max <= 0 || bt.nM_max < 0 || bt.ld_f < 0 || Pj < 0 || Pm < 0)
+        return (int)hipErrorInvalidValue;
     if (T1 < 1 || n < 0 || n >= T1 || first < 0 || first > 2 || (first != 0) != (n == 0)) return (int)hipErrorInvalidValue;
     if (!(dt > 0.0) || !(beta > 0.0) || !(gamma >= 0.5) || !(damp_mass >= 0.0) || !(damp_stiff >= 0.0))
         return (int)hipErrorInvalidValue;
     if ((Pj > 0 && (!mon_joint || !hist_u)) || (Pm > 0 && (!mon_member || !hist_N))) return (int)hipErrorInvalidValue;
     if (B == 0 || L == 0) return 0;
     const int damped = damp_stiff > 0.0;
-    if (!trs_dyn_fits(nJ_max, nM_max, damped)) return (int)hipErrorInvalidValue;
+    if (!trs_dyn_fits(bt.nJ_max, bt.nM_max, damped)) return (int)hipErrorInvalidValue;
     trs_lds::raise_lds_once<trs_dyn_step_kernel>();
-    hipLaunchKernelGGL(trs_dyn_step_kernel, dim3(B), dim3(256), dyn_lds(nJ_max, nM_max, damped), stream, L, xyz, mem,
-                       free_index, n_free, nJ, nM, nJ_max, nM_max, Mf, Pr, scale, ag, T1, n, first,
-                       dyn_coef(dt, beta, gamma, damp_mass, damp_stiff), F, U, V, Acc, ld_f, u_peak, u_step, N_max,
-                       N_max_step, N_min, N_min_step, mon_joint, Pj, mon_member, Pm, hist_u, hist_N, joint_out);
+    hipLaunchKernelGGL(trs_dyn_step_kernel, dim3(B), dim3(256), dyn_lds(bt.nJ_max, bt.nM_max, damped), stream, bt, L, Mf,
+                       Pr, scale, ag, T1, n, first, dyn_coef(dt, beta, gamma, damp_mass, damp_stiff), F, U, V, Acc, u_peak,
+                       u_step, N_max, N_max_step, N_min, N_min_step, mon_joint, Pj, mon_member, Pm, hist_u, hist_N);
     return (int)hipGetLastError();
 }
 
@@ -340,10 +313,11 @@ int trs_dyn_step(int B, int L, int nJ_max, int nM_max, const double* xyz, const 
                  double* V, double* Acc, int ld_f, double* u_peak, int32_t* u_step, double* N_max, int32_t* N_max_step,
                  double* N_min, int32_t* N_min_step, const int32_t* mon_joint, int Pj, const int32_t* mon_member, int Pm,
                  double* hist_u, double* hist_N, const int32_t* joint_out, void* stream) {
-    return dyn_step_launch(B, L, nJ_max, nM_max, xyz, trs_members_general(conn, E, A), free_index, n_free, nJ, nM, Mf, Pr,
-                           scale, ag, T1, n, first, dt, beta, gamma, damp_mass, damp_stiff, F, U, V, Acc, ld_f, u_peak,
-                           u_step, N_max, N_max_step, N_min, N_min_step, mon_joint, Pj, mon_member, Pm, hist_u, hist_N,
-                           joint_out, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_general(conn, E, A), free_index, n_free, nJ, nM,
+                                  joint_out, ld_f);
+    return dyn_step_launch(B, bt, L, Mf, Pr, scale, ag, T1, n, first, dt, beta, gamma, damp_mass, damp_stiff, F, U, V, Acc,
+                           u_peak, u_step, N_max, N_max_step, N_min, N_min_step, mon_joint, Pj, mon_member, Pm, hist_u,
+                           hist_N, (hipStream_t)stream);
 }
 
 int trs_dyn_tab_step(int B, int L, int nJ_max, int nM_max, const double* xyz, const uint16_t* conn16,
@@ -355,10 +329,11 @@ int trs_dyn_tab_step(int B, int L, int nJ_max, int nM_max, const double* xyz, co
                      const int32_t* mon_joint, int Pj, const int32_t* mon_member, int Pm, double* hist_u, double* hist_N,
                      const int32_t* joint_out, void* stream) {
     if (B > 0 && (!conn16 || !type_idx || !types)) return (int)hipErrorInvalidValue;
-    return dyn_step_launch(B, L, nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), free_index, n_free, nJ,
-                           nM, Mf, Pr, scale, ag, T1, n, first, dt, beta, gamma, damp_mass, damp_stiff, F, U, V, Acc, ld_f,
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), free_index, n_free, nJ,
+                                  nM, joint_out, ld_f);
+    return dyn_step_launch(B, bt, L, Mf, Pr, scale, ag, T1, n, first, dt, beta, gamma, damp_mass, damp_stiff, F, U, V, Acc,
                            u_peak, u_step, N_max, N_max_step, N_min, N_min_step, mon_joint, Pj, mon_member, Pm, hist_u,
-                           hist_N, joint_out, (hipStream_t)stream);
+                           hist_N, (hipStream_t)stream);
 }
 
 int trs_dyn_collect(int B, int L, int nJ_max, const double* U, const double* V, const double* Acc, int ld_f,
@@ -366,8 +341,8 @@ int trs_dyn_collect(int B, int L, int nJ_max, const double* U, const double* V, 
                     double* a, void* stream) {
     if (B < 0 || L < 0 || nJ_max < 0 || ld_f < 0) return (int)hipErrorInvalidValue;
     if (B == 0 || L == 0 || nJ_max == 0) return 0;
-    hipLaunchKernelGGL(trs_dyn_collect_kernel, dim3((unsigned)B * (unsigned)L), dim3(256), 0, (hipStream_t)stream, L,
-                       nJ_max, U, V, Acc, ld_f, free_index, nJ, joint_out, u, v, a);
+    hipLaunchKernelGGL(trs_dyn_collect_kernel, dim3((unsigned)B * (unsigned)L), dim3(256), 0, (hipStream_t)stream,
+                       trs_batch_dofs(nJ_max, free_index, nullptr, nJ, joint_out, ld_f), L, U, V, Acc, u, v, a);
     return (int)hipGetLastError();
 }
 

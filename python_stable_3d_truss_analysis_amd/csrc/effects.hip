@@ -54,29 +54,26 @@ __device__ __forceinline__ void add_end_weight(double (&bd)[3], const TrsMembers
 }
 
 // ---- the reduced right-hand side ------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void trs_effects_rhs_kernel(
-    const int L, const double* __restrict__ xyz, const TrsMembers mem, const double* __restrict__ loads,
-    const double* __restrict__ eps0, const double* __restrict__ ubar, const double* __restrict__ accel,
-    const int* __restrict__ free_index, const int* __restrict__ n_free, const int* __restrict__ nJ,
-    const int* __restrict__ nM, const int nJ_max, const int nM_max, const int* __restrict__ joint_in,
-    double* __restrict__ F, const int ld_f) {
+// (The batch's joint_out slot holds joint_in here: the same map, read the other way.)
+__global__ __launch_bounds__(256) void trs_effects_rhs_kernel(const TrsBatch bt, const int L,
+                                                              const double* __restrict__ loads,
+                                                              const double* __restrict__ eps0,
+                                                              const double* __restrict__ ubar,
+                                                              const double* __restrict__ accel, double* __restrict__ F) {
     extern __shared__ double sh[];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int joints = nJ[b], members = nM[b];
-    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
+    const TrussView v = bt.truss(b);
+    const int nM_max = bt.nM_max, ld_f = bt.ld_f, ndof_max = v.ndof_max;
+    const size_t mbase = v.mbase;
     trs_lds::Carve lds(sh);
-    const EffTables t = layout(lds, nJ_max, nM_max);
+    const EffTables t = layout(lds, bt.nJ_max, nM_max);
     double* ub = t.v;   // ubar at the constrained DOFs, zero elsewhere, device numbering
     double* s = t.pm;   // member term
-    const int* fi = free_index + (size_t)b * ndof_max;
-    const double* X = xyz + (size_t)b * ndof_max;
-    const size_t mbase = (size_t)b * nM_max;
-    const int* ji = joint_in != nullptr ? joint_in + (size_t)b * nJ_max : nullptr;
-    const int n = n_free[b], npad = trs_round_up(n, TRS_NB);
+    const int n = v.nfree, npad = min(trs_round_up(n, TRS_NB), ld_f);
     const bool member_terms = (eps0 != nullptr) | (ubar != nullptr);
     const bool lists = member_terms | (accel != nullptr);
     if (lists) {
-        build_end_lists(t, mem, mbase, joints, members, nJ_max, tid);
+        build_end_lists(t, v, tid);
         __syncthreads();
     }
     for (int k = 0; k < L; ++k) {
@@ -89,15 +86,15 @@ __global__ __launch_bounds__(256) void trs_effects_rhs_kernel(
         if (member_terms) {
             __syncthreads();  // (the previous case's readers of ub and s are done)
             if (ubk != nullptr)
-                for (int d = tid; d < ndof; d += 256) {
-                    const int o = ji != nullptr ? 3 * ji[d / 3] + d % 3 : d;
-                    ub[d] = fi[d] < 0 ? ubk[o] : 0.0;
+                for (int d = tid; d < v.ndof; d += 256) {
+                    const int o = 3 * v.place(d / 3) + d % 3;
+                    ub[d] = v.row_of(d) < 0 ? ubk[o] : 0.0;
                 }
             __syncthreads();
-            for (int m = tid; m < members; m += 256) {
-                const int2 c = mem.ends(mbase + m);
-                const MemberGeom g = member_geom(X, c.x, c.y);
-                const double EA = mem.EA(mbase + m);
+            for (int m = tid; m < v.members; m += 256) {
+                const int2 c = v.ends(m).c;
+                const MemberGeom g = member_geom(v.X, c.x, c.y);
+                const double EA = v.mem.EA(mbase + m);
                 // - k c . (ubar_j1 - ubar_j0): what the settled supports push into the free DOFs (-K_fc ubar_c)
                 double sm = ubk != nullptr ? -member_axial(g, EA, ub, c.x, c.y) : 0.0;
                 if (ek != nullptr) sm = fma(EA, ek[m], sm);
@@ -105,29 +102,30 @@ __global__ __launch_bounds__(256) void trs_effects_rhs_kernel(
             }
             __syncthreads();
         }
-        for (int j = tid; j < joints; j += 256) {
-            if ((fi[3 * j] < 0) & (fi[3 * j + 1] < 0) & (fi[3 * j + 2] < 0)) continue;  // no free DOF here
+        for (int j = tid; j < v.joints; j += 256) {
+            const TrussView::Rows rows = v.rows(j);
+            if (rows.all_held()) continue;  // no free DOF here
             double r[3] = {0.0, 0.0, 0.0}, bd[3] = {0.0, 0.0, 0.0};
             if (lists) {
                 const int* list = t.ends + t.start[j];
                 const int deg = t.cnt[j];
                 for (int i = 0; i < deg; ++i) {
                     const int m = list[i] >> 1, end = list[i] & 1;
-                    const int2 c = mem.ends(mbase + m);
-                    const MemberGeom g = member_geom(X, c.x, c.y);
+                    const int2 c = v.ends(m).c;
+                    const MemberGeom g = member_geom(v.X, c.x, c.y);
                     if (member_terms) add_end_force(r, g.c, s[m], end);
-                    if (gk != nullptr) add_end_weight(bd, mem, mbase + m, g.len, gk);
+                    if (gk != nullptr) add_end_weight(bd, v.mem, mbase + m, g.len, gk);
                 }
             }
-            const int o = ji != nullptr ? 3 * ji[j] : 3 * j;
+            const int o = 3 * v.place(j);
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
-                const int row = fi[3 * j + a];
+                const int row = rows.r[a];
                 if (row < 0) continue;
-                double v = lk != nullptr ? lk[o + a] : 0.0;
-                if (gk != nullptr) v += bd[a];
-                if (member_terms) v += r[a];
-                f[row] = v;
+                double val = lk != nullptr ? lk[o + a] : 0.0;
+                if (gk != nullptr) val += bd[a];
+                if (member_terms) val += r[a];
+                f[row] = val;
             }
         }
         for (int c = n + tid; c < npad; c += 256) f[c] = 0.0;
@@ -136,25 +134,19 @@ __global__ __launch_bounds__(256) void trs_effects_rhs_kernel(
 
 // ---- the recovery ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void trs_effects_recover_kernel(
-    const int L, const double* __restrict__ xyz, const TrsMembers mem, const double* __restrict__ loads,
-    const double* __restrict__ eps0, const double* __restrict__ ubar, const double* __restrict__ accel,
-    const int* __restrict__ free_index, const int* __restrict__ nJ, const int* __restrict__ nM, const int nJ_max,
-    const int nM_max, const double* __restrict__ F, const int ld_f, double* __restrict__ u_out,
-    double* __restrict__ f_out, double* __restrict__ N_out, double* __restrict__ body_out,
-    const int* __restrict__ joint_out) {
+    const TrsBatch bt, const int L, const double* __restrict__ loads, const double* __restrict__ eps0,
+    const double* __restrict__ ubar, const double* __restrict__ accel, const double* __restrict__ F,
+    double* __restrict__ u_out, double* __restrict__ f_out, double* __restrict__ N_out, double* __restrict__ body_out) {
     extern __shared__ double sh[];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int joints = nJ[b], members = nM[b];
-    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
+    const TrussView v = bt.truss(b);
+    const int nM_max = bt.nM_max, ld_f = bt.ld_f, ndof = v.ndof, ndof_max = v.ndof_max;
+    const size_t mbase = v.mbase;
     trs_lds::Carve lds(sh);
-    const EffTables t = layout(lds, nJ_max, nM_max);
+    const EffTables t = layout(lds, bt.nJ_max, nM_max);
     double* u = t.v;    // displacements of one case, device numbering: solved at the free DOFs, ubar at the others
     double* Nm = t.pm;  // axial forces of that case
-    const int* fi = free_index + (size_t)b * ndof_max;
-    const double* X = xyz + (size_t)b * ndof_max;
-    const size_t mbase = (size_t)b * nM_max;
-    const int* jo = joint_out != nullptr ? joint_out + (size_t)b * nJ_max : nullptr;
-    build_end_lists(t, mem, mbase, joints, members, nJ_max, tid);
+    build_end_lists(t, v, tid);
     __syncthreads();
     for (int k = 0; k < L; ++k) {
         const size_t bk = (size_t)b * L + k;
@@ -168,11 +160,11 @@ __global__ __launch_bounds__(256) void trs_effects_recover_kernel(
         double* bo = body_out != nullptr ? body_out + bk * ndof_max : nullptr;
         __syncthreads();  // (the previous case's readers of u and Nm are done)
         for (int d = tid; d < ndof_max; d += 256) {
-            const int r = d < ndof ? fi[d] : -1;
-            const int o = jo != nullptr ? 3 * jo[d / 3] + d % 3 : d;
-            const double v = r >= 0 ? fk[r] : ((ubk != nullptr && d < ndof) ? ubk[o] : 0.0);
-            u[d] = v;
-            uo[o] = v;
+            const int r = v.row_of(d);
+            const int o = 3 * v.place(d / 3) + d % 3;
+            const double val = r >= 0 ? fk[r] : ((ubk != nullptr && d < ndof) ? ubk[o] : 0.0);
+            u[d] = val;
+            uo[o] = val;
             if (r >= 0) fo[o] = lk != nullptr ? lk[o] : 0.0;  // free DOF: the applied load
             else if (d >= ndof) fo[o] = 0.0;                  // padding
             if (bo != nullptr && d >= ndof) bo[o] = 0.0;
@@ -180,10 +172,10 @@ __global__ __launch_bounds__(256) void trs_effects_recover_kernel(
         __syncthreads();
         for (int m = tid; m < nM_max; m += 256) {
             double axial = 0.0;
-            if (m < members) {
-                const int2 c = mem.ends(mbase + m);
-                const MemberGeom g = member_geom(X, c.x, c.y);
-                const double EA = mem.EA(mbase + m);
+            if (m < v.members) {
+                const int2 c = v.ends(m).c;
+                const MemberGeom g = member_geom(v.X, c.x, c.y);
+                const double EA = v.mem.EA(mbase + m);
                 axial = member_axial(g, EA, u, c.x, c.y);
                 if (ek != nullptr) axial = fma(-EA, ek[m], axial);
                 Nm[m] = axial;
@@ -191,55 +183,54 @@ __global__ __launch_bounds__(256) void trs_effects_recover_kernel(
             N_out[bk * nM_max + m] = axial;
         }
         __syncthreads();
-        for (int j = tid; j < joints; j += 256) {
-            const bool held = (fi[3 * j] < 0) | (fi[3 * j + 1] < 0) | (fi[3 * j + 2] < 0);
+        for (int j = tid; j < v.joints; j += 256) {
+            const TrussView::Rows rows = v.rows(j);
+            const bool held = rows.any_held();
             if (!held && bo == nullptr) continue;  // nothing of this joint is written here
             double r[3] = {0.0, 0.0, 0.0}, bd[3] = {0.0, 0.0, 0.0};
             const int* list = t.ends + t.start[j];
             const int deg = t.cnt[j];
             for (int i = 0; i < deg; ++i) {
                 const int m = list[i] >> 1, end = list[i] & 1;
-                const int2 c = mem.ends(mbase + m);
-                const MemberGeom g = member_geom(X, c.x, c.y);
+                const int2 c = v.ends(m).c;
+                const MemberGeom g = member_geom(v.X, c.x, c.y);
                 if (held) add_end_force(r, g.c, Nm[m], end);
-                if (gk != nullptr) add_end_weight(bd, mem, mbase + m, g.len, gk);
+                if (gk != nullptr) add_end_weight(bd, v.mem, mbase + m, g.len, gk);
             }
-            const int o = jo != nullptr ? 3 * jo[j] : 3 * j;
+            const int o = 3 * v.place(j);
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
-                if (fi[3 * j + a] < 0) fo[o + a] = gk != nullptr ? r[a] - bd[a] : r[a];
+                if (rows.held(a)) fo[o + a] = gk != nullptr ? r[a] - bd[a] : r[a];
                 if (bo != nullptr) bo[o + a] = bd[a];
             }
         }
     }
 }
 
-int effects_rhs_launch(int B, int L, int nJ_max, int nM_max, const double* xyz, const TrsMembers& mem,
-                       const double* loads, const double* eps0, const double* ubar, const double* accel,
-                       const int* free_index, const int* n_free, const int* nJ, const int* nM, const int* joint_in,
-                       double* F, int ld_f, hipStream_t stream) {
-    if (B < 0 || L < 0 || nJ_max < 0 || nM_max < 0 || ld_f < 0) return (int)hipErrorInvalidValue;
+bool effects_args_ok(const TrsBatch& bt, int B, int L, const double* accel) {
+    if (B < 0 || L < 0 || bt.nJ_max < 0 || bt.nM_max < 0 || bt.ld_f < 0) return false;
+    if (B == 0 || L == 0) return true;
+    return trs_effects_fits(bt.nJ_max, bt.nM_max) && !(accel != nullptr && bt.mem.tidx == nullptr && bt.mem.rho == nullptr);
+}
+
+int effects_rhs_launch(int B, const TrsBatch& bt, int L, const double* loads, const double* eps0, const double* ubar,
+                       const double* accel, double* F, hipStream_t stream) {
+    if (!effects_args_ok(bt, B, L, accel)) return (int)hipErrorInvalidValue;
     if (B == 0 || L == 0) return 0;
-    if (!trs_effects_fits(nJ_max, nM_max)) return (int)hipErrorInvalidValue;
-    if (accel != nullptr && mem.tidx == nullptr && mem.rho == nullptr) return (int)hipErrorInvalidValue;
     trs_lds::raise_lds_once<trs_effects_rhs_kernel>();
-    hipLaunchKernelGGL(trs_effects_rhs_kernel, dim3(B), dim3(256), effects_lds(nJ_max, nM_max), stream, L, xyz, mem,
-                       loads, eps0, ubar, accel, free_index, n_free, nJ, nM, nJ_max, nM_max, joint_in, F, ld_f);
+    hipLaunchKernelGGL(trs_effects_rhs_kernel, dim3(B), dim3(256), effects_lds(bt.nJ_max, bt.nM_max), stream, bt, L, loads,
+                       eps0, ubar, accel, F);
     return (int)hipGetLastError();
 }
 
-int effects_recover_launch(int B, int L, int nJ_max, int nM_max, const double* xyz, const TrsMembers& mem,
-                           const double* loads, const double* eps0, const double* ubar, const double* accel,
-                           const int* free_index, const int* nJ, const int* nM, const double* F, int ld_f, double* u,
-                           double* f_ext, double* N, double* body, const int* joint_out, hipStream_t stream) {
-    if (B < 0 || L < 0 || nJ_max < 0 || nM_max < 0 || ld_f < 0) return (int)hipErrorInvalidValue;
+int effects_recover_launch(int B, const TrsBatch& bt, int L, const double* loads, const double* eps0, const double* ubar,
+                           const double* accel, const double* F, double* u, double* f_ext, double* N, double* body,
+                           hipStream_t stream) {
+    if (!effects_args_ok(bt, B, L, accel)) return (int)hipErrorInvalidValue;
     if (B == 0 || L == 0) return 0;
-    if (!trs_effects_fits(nJ_max, nM_max)) return (int)hipErrorInvalidValue;
-    if (accel != nullptr && mem.tidx == nullptr && mem.rho == nullptr) return (int)hipErrorInvalidValue;
     trs_lds::raise_lds_once<trs_effects_recover_kernel>();
-    hipLaunchKernelGGL(trs_effects_recover_kernel, dim3(B), dim3(256), effects_lds(nJ_max, nM_max), stream, L, xyz, mem,
-                       loads, eps0, ubar, accel, free_index, nJ, nM, nJ_max, nM_max, F, ld_f, u, f_ext, N, body,
-                       joint_out);
+    hipLaunchKernelGGL(trs_effects_recover_kernel, dim3(B), dim3(256), effects_lds(bt.nJ_max, bt.nM_max), stream, bt, L,
+                       loads, eps0, ubar, accel, F, u, f_ext, N, body);
     return (int)hipGetLastError();
 }
 
@@ -257,8 +248,9 @@ int trs_effects_rhs(int B, int L, int nJ_max, int nM_max, const double* xyz, con
                     const double* A, const double* rho, const double* loads, const double* eps0, const double* ubar,
                     const double* accel, const int32_t* free_index, const int32_t* n_free, const int32_t* nJ,
                     const int32_t* nM, const int32_t* joint_in, double* F, int ld_f, void* stream) {
-    return effects_rhs_launch(B, L, nJ_max, nM_max, xyz, trs_members_general(conn, E, A, rho), loads, eps0, ubar, accel,
-                              free_index, n_free, nJ, nM, joint_in, F, ld_f, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_general(conn, E, A, rho), free_index, n_free, nJ, nM,
+                                  joint_in, ld_f);
+    return effects_rhs_launch(B, bt, L, loads, eps0, ubar, accel, F, (hipStream_t)stream);
 }
 
 int trs_effects_tab_rhs(int B, int L, int nJ_max, int nM_max, const double* xyz, const uint16_t* conn16,
@@ -267,8 +259,9 @@ int trs_effects_tab_rhs(int B, int L, int nJ_max, int nM_max, const double* xyz,
                         const int32_t* nJ, const int32_t* nM, const int32_t* joint_in, double* F, int ld_f,
                         void* stream) {
     if (B > 0 && (!conn16 || !type_idx || !types)) return (int)hipErrorInvalidValue;
-    return effects_rhs_launch(B, L, nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), loads, eps0, ubar,
-                              accel, free_index, n_free, nJ, nM, joint_in, F, ld_f, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), free_index, n_free, nJ,
+                                  nM, joint_in, ld_f);
+    return effects_rhs_launch(B, bt, L, loads, eps0, ubar, accel, F, (hipStream_t)stream);
 }
 
 int trs_effects_recover(int B, int L, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* E,
@@ -276,8 +269,9 @@ int trs_effects_recover(int B, int L, int nJ_max, int nM_max, const double* xyz,
                         const double* accel, const int32_t* free_index, const int32_t* nJ, const int32_t* nM,
                         const double* F, int ld_f, double* u, double* f_ext, double* N, double* body,
                         const int32_t* joint_out, void* stream) {
-    return effects_recover_launch(B, L, nJ_max, nM_max, xyz, trs_members_general(conn, E, A, rho), loads, eps0, ubar,
-                                  accel, free_index, nJ, nM, F, ld_f, u, f_ext, N, body, joint_out, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_general(conn, E, A, rho), free_index, nullptr, nJ, nM,
+                                  joint_out, ld_f);
+    return effects_recover_launch(B, bt, L, loads, eps0, ubar, accel, F, u, f_ext, N, body, (hipStream_t)stream);
 }
 
 int trs_effects_tab_recover(int B, int L, int nJ_max, int nM_max, const double* xyz, const uint16_t* conn16,
@@ -286,8 +280,9 @@ int trs_effects_tab_recover(int B, int L, int nJ_max, int nM_max, const double* 
                             const int32_t* nM, const double* F, int ld_f, double* u, double* f_ext, double* N,
                             double* body, const int32_t* joint_out, void* stream) {
     if (B > 0 && (!conn16 || !type_idx || !types)) return (int)hipErrorInvalidValue;
-    return effects_recover_launch(B, L, nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), loads, eps0, ubar,
-                                  accel, free_index, nJ, nM, F, ld_f, u, f_ext, N, body, joint_out, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), free_index, nullptr, nJ,
+                                  nM, joint_out, ld_f);
+    return effects_recover_launch(B, bt, L, loads, eps0, ubar, accel, F, u, f_ext, N, body, (hipStream_t)stream);
 }
 
 }  // extern "C"

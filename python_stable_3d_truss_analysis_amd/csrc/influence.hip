@@ -80,27 +80,26 @@ __device__ __forceinline__ double line_at(const double* s, const double* eta, co
 }
 
 __global__ __launch_bounds__(64 * WAVES) void trs_influence_apply_kernel(
-    const int e0, const int C, const int slice, const int P_max, const int A, const double* __restrict__ xyz,
-    const TrsMembers mem, const int* __restrict__ free_index, const int* __restrict__ nJ, const int* __restrict__ nM,
-    const int nJ_max, const int nM_max, const int* __restrict__ path, const int* __restrict__ path_len,
-    const double* __restrict__ dir, const double* __restrict__ train_w, const double* __restrict__ train_o,
-    const double* __restrict__ Z, const int ld_f, double* __restrict__ eta_out, double* __restrict__ nmax_out,
-    double* __restrict__ nmin_out, double* __restrict__ xmax_out, double* __restrict__ xmin_out,
-    double* __restrict__ apos_out, double* __restrict__ aneg_out, const int* __restrict__ joint_out) {
+    const TrsBatch bt, const int e0, const int C, const int slice, const int P_max, const int A,
+    const int* __restrict__ path, const int* __restrict__ path_len, const double* __restrict__ dir,
+    const double* __restrict__ train_w, const double* __restrict__ train_o, const double* __restrict__ Z,
+    double* __restrict__ eta_out, double* __restrict__ nmax_out, double* __restrict__ nmin_out,
+    double* __restrict__ xmax_out, double* __restrict__ xmin_out, double* __restrict__ apos_out,
+    double* __restrict__ aneg_out) {
     extern __shared__ double sh[];
     const int slices = (C + slice - 1) / slice;   // work-groups per truss
     const int b = blockIdx.x / slices, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // the members of this work-group: first <= m < last (inside the chunk and inside the arrays)
     const int first = e0 + (blockIdx.x - b * slices) * slice;
-    const int last = min(min(first + slice, e0 + C), nM_max);
+    const int last = min(min(first + slice, e0 + C), bt.nM_max);
     if (first >= last) return;
-    const int joints = nJ[b], members = nM[b];
+    const TrussView tr = bt.truss(b);
+    const int joints = tr.joints, members = tr.members, ld_f = bt.ld_f;
     const int P = joints > 0 ? max(0, min(path_len[b], P_max)) : 0;
     trs_lds::Carve lds(sh);
-    const InfluenceTables t = layout(lds, nJ_max, P_max, A);
-    const size_t mbase = (size_t)b * nM_max;
-    const double* X = xyz + (size_t)b * 3 * nJ_max;
-    const int* fi = free_index + (size_t)b * 3 * nJ_max;
+    const InfluenceTables t = layout(lds, bt.nJ_max, P_max, A);
+    const size_t mbase = tr.mbase;
+    const double* __restrict__ X = tr.X;
     double* ew = t.eta + (size_t)wave * P_max;
     const double nan = __builtin_nan("");
 
@@ -112,8 +111,8 @@ __global__ __launch_bounds__(64 * WAVES) void trs_influence_apply_kernel(
     }
     __syncthreads();
     for (int j = tid; j < joints; j += 64 * WAVES) {
-        const int id = joint_out != nullptr ? joint_out[(size_t)b * nJ_max + j] : j;
-        if (id >= 0 && id < joints) t.inv[id] = j;
+        const int id = tr.place(j);
+        if (id < joints) t.inv[id] = j;
     }
     __syncthreads();
     for (int p = tid; p < P; p += 64 * WAVES) {
@@ -122,7 +121,7 @@ __global__ __launch_bounds__(64 * WAVES) void trs_influence_apply_kernel(
         t.pj[p] = j;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-            t.di[3 * p + a] = fi[3 * j + a];
+            t.di[3 * p + a] = tr.row_of(3 * j + a);
             t.dw[3 * p + a] = dir[(size_t)b * 3 + a];
         }
     }
@@ -165,9 +164,9 @@ __global__ __launch_bounds__(64 * WAVES) void trs_influence_apply_kernel(
             continue;
         }
         // k_m as the member-loss kernel forms it (every lane: broadcast reads)
-        const int2 c = mem.ends(o);
+        const int2 c = tr.ends(m).c;
         const MemberGeom mg = member_geom(X, c.x, c.y);
-        const double km = mem.EA(o) / mg.len;
+        const double km = tr.mem.EA(o) / mg.len;
         // eta of this member along the path (this wave's own vector: written and read by this wave only)
         const double* zm = Z + ((size_t)b * C + (m - e0)) * ld_f;
         for (int p = lane; p < P_max; p += 64) {
@@ -240,22 +239,20 @@ __global__ __launch_bounds__(64 * WAVES) void trs_influence_apply_kernel(
     }
 }
 
-int influence_launch(int B, int e0, int C, int nJ_max, int nM_max, int P_max, int A, const double* xyz,
-                     const TrsMembers& mem, const int* free_index, const int* nJ, const int* nM, const int* path,
-                     const int* path_len, const double* dir, const double* train_w, const double* train_o,
-                     const double* Z, int ld_f, double* eta_out, double* N_max, double* N_min, double* x_max,
-                     double* x_min, double* area_pos, double* area_neg, const int* joint_out, hipStream_t stream) {
-    if (B < 0 || e0 < 0 || C < 0 || nJ_max < 0 || nM_max < 0 || P_max < 0 || A < 1 || ld_f < 0)
+int influence_launch(int B, const TrsBatch& bt, int e0, int C, int P_max, int A, const int* path, const int* path_len,
+                     const double* dir, const double* train_w, const double* train_o, const double* Z, double* eta_out,
+                     double* N_max, double* N_min, double* x_max, double* x_min, double* area_pos, double* area_neg,
+                     hipStream_t stream) {
+    if (B < 0 || e0 < 0 || C < 0 || bt.nJ_max < 0 || bt.nM_max < 0 || P_max < 0 || A < 1 || bt.ld_f < 0)
         return (int)hipErrorInvalidValue;
-    if (B == 0 || C == 0 || e0 >= nM_max) return 0;
-    if (!trs_influence_fits(nJ_max, P_max, A)) return (int)hipErrorInvalidValue;
+    if (B == 0 || C == 0 || e0 >= bt.nM_max) return 0;
+    if (!trs_influence_fits(bt.nJ_max, P_max, A)) return (int)hipErrorInvalidValue;
     if ((long long)P_max * A > INT_MAX - 64) return (int)hipErrorInvalidValue;   // (the candidate index is an int)
     trs_lds::raise_lds_once<trs_influence_apply_kernel>();
     const int slices = (C + TRS_INFLUENCE_SLICE - 1) / TRS_INFLUENCE_SLICE;
     hipLaunchKernelGGL(trs_influence_apply_kernel, dim3((unsigned)slices * (unsigned)B), dim3(64 * WAVES),
-                       influence_lds(nJ_max, P_max, A), stream, e0, C, TRS_INFLUENCE_SLICE, P_max, A, xyz, mem,
-                       free_index, nJ, nM, nJ_max, nM_max, path, path_len, dir, train_w, train_o, Z, ld_f, eta_out, N_max,
-                       N_min, x_max, x_min, area_pos, area_neg, joint_out);
+                       influence_lds(bt.nJ_max, P_max, A), stream, bt, e0, C, TRS_INFLUENCE_SLICE, P_max, A, path, path_len,
+                       dir, train_w, train_o, Z, eta_out, N_max, N_min, x_max, x_min, area_pos, area_neg);
     return (int)hipGetLastError();
 }
 
@@ -275,9 +272,10 @@ int trs_influence_apply(int B, int e0, int C, int nJ_max, int nM_max, int P_max,
                         const double* dir, const double* train_w, const double* train_o, const double* Z, int ld_f,
                         double* eta_out, double* N_max, double* N_min, double* x_max, double* x_min, double* area_pos,
                         double* area_neg, const int32_t* joint_out, void* stream) {
-    return influence_launch(B, e0, C, nJ_max, nM_max, P_max, A, xyz, trs_members_general(conn, E, Amem), free_index, nJ,
-                            nM, path, path_len, dir, train_w, train_o, Z, ld_f, eta_out, N_max, N_min, x_max, x_min,
-                            area_pos, area_neg, joint_out, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_general(conn, E, Amem), free_index, nullptr, nJ, nM,
+                                  joint_out, ld_f);
+    return influence_launch(B, bt, e0, C, P_max, A, path, path_len, dir, train_w, train_o, Z, eta_out, N_max, N_min, x_max,
+                            x_min, area_pos, area_neg, (hipStream_t)stream);
 }
 
 int trs_influence_tab_apply(int B, int e0, int C, int nJ_max, int nM_max, int P_max, int A, const double* xyz,
@@ -287,9 +285,10 @@ int trs_influence_tab_apply(int B, int e0, int C, int nJ_max, int nM_max, int P_
                             const double* Z, int ld_f, double* eta_out, double* N_max, double* N_min, double* x_max,
                             double* x_min, double* area_pos, double* area_neg, const int32_t* joint_out, void* stream) {
     if (B > 0 && (!conn16 || !type_idx || !types)) return (int)hipErrorInvalidValue;
-    return influence_launch(B, e0, C, nJ_max, nM_max, P_max, A, xyz, trs_members_table(conn16, type_idx, types),
-                            free_index, nJ, nM, path, path_len, dir, train_w, train_o, Z, ld_f, eta_out, N_max, N_min,
-                            x_max, x_min, area_pos, area_neg, joint_out, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), free_index, nullptr, nJ,
+                                  nM, joint_out, ld_f);
+    return influence_launch(B, bt, e0, C, P_max, A, path, path_len, dir, train_w, train_o, Z, eta_out, N_max, N_min, x_max,
+                            x_min, area_pos, area_neg, (hipStream_t)stream);
 }
 
 }  // extern "C"

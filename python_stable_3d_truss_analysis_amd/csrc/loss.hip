@@ -30,46 +30,43 @@ constexpr int WAVES = TRS_LOSS_WAVES;   // each owns one z vector in LDS; trs_lo
 #endif
 
 // ---- the right-hand sides: one wave per row --------------------------------------------------------------------------
-__global__ __launch_bounds__(64 * WAVES) void trs_columns_rhs_kernel(
-    const int e0, const int* __restrict__ cols, const int C, const double* __restrict__ xyz, const TrsMembers mem,
-    const int* __restrict__ free_index, const int* __restrict__ n_free, const int* __restrict__ nM, const int nJ_max,
-    const int nM_max, double* __restrict__ Z, const int ld_f) {
+__global__ __launch_bounds__(64 * WAVES) void trs_columns_rhs_kernel(const TrsBatch bt, const int e0,
+                                                                     const int* __restrict__ cols, const int C,
+                                                                     double* __restrict__ Z) {
     const int per_truss = (C + WAVES - 1) / WAVES;   // work-groups per truss
     const int b = blockIdx.x / per_truss, lane = threadIdx.x & 63;
     const int i = (blockIdx.x - b * per_truss) * WAVES + (threadIdx.x >> 6);
     if (i >= C) return;
+    const TrussView v = bt.truss(b);
     const int e = cols != nullptr ? cols[(size_t)b * C + i] : e0 + i;
-    const bool real = e >= 0 && e < nM[b];
-    const int npad = min(trs_round_up(n_free[b], TRS_NB), ld_f);
-    write_row(Z + ((size_t)b * C + i) * ld_f, npad, lane, real, (size_t)b * nM_max + (real ? e : 0), mem,
-              xyz + (size_t)b * 3 * nJ_max, free_index + (size_t)b * 3 * nJ_max);
+    const bool real = e >= 0 && e < v.members;
+    const int npad = min(trs_round_up(v.nfree, TRS_NB), bt.ld_f);
+    write_row(Z + ((size_t)b * C + i) * bt.ld_f, npad, lane, real, real ? e : 0, v);
 }
 
 // ---- the apply kernel ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64 * WAVES) void trs_loss_apply_kernel(
-    const int L, const int g, const int e0, const int C, const int slice, const double* __restrict__ xyz,
-    const TrsMembers mem, const int* __restrict__ free_index, const int* __restrict__ nJ, const int* __restrict__ nM,
-    const int nJ_max, const int nM_max, const double* __restrict__ Z, const double* __restrict__ U, const int ld_f,
-    const double r_tol, double* __restrict__ r_out, int* __restrict__ crit_out, double* __restrict__ ps_out,
-    int* __restrict__ pm_out, double* __restrict__ pd_out, int* __restrict__ pj_out, double* __restrict__ NA,
-    const int* __restrict__ joint_out) {
+    const TrsBatch bt, const int L, const int g, const int e0, const int C, const int slice, const double* __restrict__ Z,
+    const double* __restrict__ U, const double r_tol, double* __restrict__ r_out, int* __restrict__ crit_out,
+    double* __restrict__ ps_out, int* __restrict__ pm_out, double* __restrict__ pd_out, int* __restrict__ pj_out,
+    double* __restrict__ NA) {
     extern __shared__ double sh[];
+    const int nJ_max = bt.nJ_max, nM_max = bt.nM_max, ld_f = bt.ld_f;
     const int slices = (C + slice - 1) / slice;   // work-groups per truss
     const int b = blockIdx.x / slices, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // the removed members of this work-group: first <= e < last (inside the chunk and inside the arrays)
     const int first = e0 + (blockIdx.x - b * slices) * slice;
     const int last = min(min(first + slice, e0 + C), nM_max);
     if (first >= last) return;
-    // trimmed to the arrays, so that no table entry and no output lies outside them whatever nJ[b] and nM[b] hold
-    const int joints = min(max(nJ[b], 0), nJ_max), members = min(max(nM[b], 0), nM_max);
-    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
+    const TrussView v = bt.truss(b);
+    const int joints = v.joints, members = v.members, ndof = v.ndof, ndof_max = v.ndof_max;
     trs_lds::Carve carve(sh);
     const Tables t = layout(carve, nJ_max, nM_max, g, WAVES, 0);
-    const size_t mbase = (size_t)b * nM_max;
+    const size_t mbase = v.mbase;
     double* zw = t.z + (size_t)wave * ndof_max;
     const double inf = __builtin_huge_val(), nan = __builtin_nan("");
 
-    stage(t, tid, 64 * WAVES, b, joints, members, nJ_max, nM_max, xyz, mem, free_index, joint_out, ld_f);
+    stage(t, tid, 64 * WAVES, v);
     for (int l0 = 0; l0 < L; l0 += g) {
         const int lg = min(g, L - l0);   // the cases of this pass: l0 .. l0 + lg - 1
         stage_pass(t, tid, 64 * WAVES, lg, members, nJ_max, nM_max, U + ((size_t)b * L + l0) * ld_f, ld_f);
@@ -187,13 +184,11 @@ __global__ __launch_bounds__(64 * WAVES) void trs_loss_apply_kernel(
     }
 }
 
-int loss_apply_launch(int B, int L, int e0, int C, int nJ_max, int nM_max, const double* xyz, const TrsMembers& mem,
-                      const int* free_index, const int* nJ, const int* nM, const double* Z, const double* U, int ld_f,
-                      double r_tol, double* r, int* critical, double* peak_stress, int* peak_member,
-                      double* peak_displace, int* peak_joint, double* N_after, const int* joint_out,
-                      hipStream_t stream) {
-    if (B < 0 || L < 0 || e0 < 0 || C < 0 || nJ_max < 0 || nM_max < 0 || ld_f < 0)
-        return (int)hipErrorInvalidValue;
+int loss_apply_launch(int B, const TrsBatch& bt, int L, int e0, int C, const double* Z, const double* U, double r_tol,
+                      double* r, int* critical, double* peak_stress, int* peak_member, double* peak_displace,
+                      int* peak_joint, double* N_after, hipStream_t stream) {
+    const int nJ_max = bt.nJ_max, nM_max = bt.nM_max;
+    if (B < 0 || L < 0 || e0 < 0 || C < 0 || nJ_max < 0 || nM_max < 0 || bt.ld_f < 0) return (int)hipErrorInvalidValue;
     if (B == 0 || L == 0 || C == 0 || e0 >= nM_max) return 0;
     if (nJ_max == 0) return (int)hipErrorInvalidValue;   // (members without joints to end at)
     if (!trs_loss_fits(nJ_max, nM_max, L)) return (int)hipErrorInvalidValue;
@@ -202,21 +197,18 @@ int loss_apply_launch(int B, int L, int e0, int C, int nJ_max, int nM_max, const
     trs_lds::raise_lds_once<trs_loss_apply_kernel>();
     const int slices = (C + TRS_LOSS_SLICE - 1) / TRS_LOSS_SLICE;
     hipLaunchKernelGGL(trs_loss_apply_kernel, dim3((unsigned)slices * (unsigned)B), dim3(64 * WAVES),
-                       lds(nJ_max, nM_max, g, WAVES, 0), stream, L, g, e0, C, TRS_LOSS_SLICE, xyz, mem, free_index, nJ, nM,
-                       nJ_max, nM_max, Z, U, ld_f, r_tol, r, critical, peak_stress, peak_member, peak_displace,
-                       peak_joint, N_after, joint_out);
+                       lds(nJ_max, nM_max, g, WAVES, 0), stream, bt, L, g, e0, C, TRS_LOSS_SLICE, Z, U, r_tol, r, critical,
+                       peak_stress, peak_member, peak_displace, peak_joint, N_after);
     return (int)hipGetLastError();
 }
 
 }  // namespace
 
-int trs_col::rhs_launch(int B, int e0, const int* cols, int C, int nJ_max, int nM_max, const double* xyz,
-                        const TrsMembers& mem, const int* free_index, const int* n_free, const int* nM, double* Z,
-                        int ld_f, hipStream_t stream) {
-    if (B < 0 || e0 < 0 || C < 0 || nJ_max < 0 || nM_max < 0 || ld_f < 0) return (int)hipErrorInvalidValue;
+int trs_col::rhs_launch(int B, const TrsBatch& bt, int e0, const int* cols, int C, double* Z, hipStream_t stream) {
+    if (B < 0 || e0 < 0 || C < 0 || bt.nJ_max < 0 || bt.nM_max < 0 || bt.ld_f < 0) return (int)hipErrorInvalidValue;
     if (B == 0 || C == 0) return 0;
     hipLaunchKernelGGL(trs_columns_rhs_kernel, dim3((unsigned)((C + WAVES - 1) / WAVES) * (unsigned)B), dim3(64 * WAVES),
-                       0, stream, e0, cols, C, xyz, mem, free_index, n_free, nM, nJ_max, nM_max, Z, ld_f);
+                       0, stream, bt, e0, cols, C, Z);
     return (int)hipGetLastError();
 }
 
@@ -231,16 +223,18 @@ int trs_loss_fits(int nJ_max, int nM_max, int L) {
 int trs_loss_rhs(int B, int e0, int C, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* E,
                  const double* A, const int32_t* free_index, const int32_t* n_free, const int32_t* nM, double* Z,
                  int ld_f, void* stream) {
-    return rhs_launch(B, e0, nullptr, C, nJ_max, nM_max, xyz, trs_members_general(conn, E, A), free_index, n_free, nM, Z,
-                           ld_f, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_general(conn, E, A), free_index, n_free, nullptr, nM,
+                                  nullptr, ld_f);
+    return rhs_launch(B, bt, e0, nullptr, C, Z, (hipStream_t)stream);
 }
 
 int trs_loss_tab_rhs(int B, int e0, int C, int nJ_max, int nM_max, const double* xyz, const uint16_t* conn16,
                      const uint8_t* type_idx, const double* types, const int32_t* free_index, const int32_t* n_free,
                      const int32_t* nM, double* Z, int ld_f, void* stream) {
     if (B > 0 && (!conn16 || !type_idx || !types)) return (int)hipErrorInvalidValue;
-    return rhs_launch(B, e0, nullptr, C, nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), free_index, n_free,
-                           nM, Z, ld_f, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), free_index, n_free,
+                                  nullptr, nM, nullptr, ld_f);
+    return rhs_launch(B, bt, e0, nullptr, C, Z, (hipStream_t)stream);
 }
 
 int trs_loss_apply(int B, int L, int e0, int C, int nJ_max, int nM_max, const double* xyz, const int32_t* conn,
@@ -248,9 +242,10 @@ int trs_loss_apply(int B, int L, int e0, int C, int nJ_max, int nM_max, const do
                    const double* Z, const double* U, int ld_f, double r_tol, double* r, int32_t* critical,
                    double* peak_stress, int32_t* peak_member, double* peak_displace, int32_t* peak_joint,
                    double* N_after, const int32_t* joint_out, void* stream) {
-    return loss_apply_launch(B, L, e0, C, nJ_max, nM_max, xyz, trs_members_general(conn, E, A), free_index, nJ, nM, Z, U,
-                             ld_f, r_tol, r, critical, peak_stress, peak_member, peak_displace, peak_joint, N_after,
-                             joint_out, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_general(conn, E, A), free_index, nullptr, nJ, nM,
+                                  joint_out, ld_f);
+    return loss_apply_launch(B, bt, L, e0, C, Z, U, r_tol, r, critical, peak_stress, peak_member, peak_displace, peak_joint,
+                             N_after, (hipStream_t)stream);
 }
 
 int trs_loss_tab_apply(int B, int L, int e0, int C, int nJ_max, int nM_max, const double* xyz, const uint16_t* conn16,
@@ -259,9 +254,10 @@ int trs_loss_tab_apply(int B, int L, int e0, int C, int nJ_max, int nM_max, cons
                        int32_t* critical, double* peak_stress, int32_t* peak_member, double* peak_displace,
                        int32_t* peak_joint, double* N_after, const int32_t* joint_out, void* stream) {
     if (B > 0 && (!conn16 || !type_idx || !types)) return (int)hipErrorInvalidValue;
-    return loss_apply_launch(B, L, e0, C, nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), free_index, nJ,
-                             nM, Z, U, ld_f, r_tol, r, critical, peak_stress, peak_member, peak_displace, peak_joint,
-                             N_after, joint_out, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), free_index, nullptr, nJ,
+                                  nM, joint_out, ld_f);
+    return loss_apply_launch(B, bt, L, e0, C, Z, U, r_tol, r, critical, peak_stress, peak_member, peak_displace, peak_joint,
+                             N_after, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -77,37 +77,27 @@ __device__ __forceinline__ MemberMode member_mode(const double* ph, const int2 c
 }
 
 __global__ __launch_bounds__(256) void trs_mg_grad_kernel(
-    const double* __restrict__ xyz, const TrsMembers mem, const int* __restrict__ free_index,
-    const int* __restrict__ n_free, const int* __restrict__ nJ, const int* __restrict__ nM,
-    const int* __restrict__ joint_out, const int nJ_max, const int nM_max, const double* __restrict__ X_all,
-    const int ld_f, const double* __restrict__ lam_all, const int* __restrict__ n_mass, const int p, const int pc,
-    const double mass_scale, const double* __restrict__ w_all, double* __restrict__ gA, double* __restrict__ gE,
-    double* __restrict__ grho, double* __restrict__ gxyz, double* __restrict__ gmass) {
+    const TrsBatch bt, const double* __restrict__ X_all, const double* __restrict__ lam_all,
+    const int* __restrict__ n_mass, const int p, const int pc, const double mass_scale, const double* __restrict__ w_all,
+    double* __restrict__ gA, double* __restrict__ gE, double* __restrict__ grho, double* __restrict__ gxyz,
+    double* __restrict__ gmass) {
     extern __shared__ double sh[];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int joints = min(max(nJ[b], 0), nJ_max);
-    const int members = nJ_max > 0 ? min(max(nM[b], 0), nM_max) : 0;   // (without a joint there is no end to clamp to)
-    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
-    const int nfree = min(max(n_free[b], 0), ld_f);
+    const TrussView v = bt.truss(b);
+    const int nJ_max = bt.nJ_max, nM_max = bt.nM_max, ld_f = bt.ld_f;
+    const int joints = v.joints, members = v.members, ndof_max = v.ndof_max;
+    const size_t mbase = v.mbase;
+    const TrsMembers& mem = v.mem;
     const int n_modes = min(p, max(n_mass[b], 0));
     const bool weighted = w_all != nullptr;
     const int R = weighted ? 1 : p;
     trs_lds::Carve lds(sh);
     const MgTables t = layout(lds, nJ_max, nM_max, pc);
-    const int* fi = free_index + (size_t)b * ndof_max;
-    const double* Xyz = xyz + (size_t)b * ndof_max;
-    const size_t mbase = (size_t)b * nM_max;
-    const int* jo = joint_out != nullptr ? joint_out + (size_t)b * nJ_max : nullptr;
     const double* Xb = X_all + (size_t)b * TRS_MG_BLOCK * ld_f;
     const double* lam = lam_all + (size_t)b * TRS_MG_BLOCK;
     const double* w = weighted ? w_all + (size_t)b * p : nullptr;
     const bool want_members = (gA != nullptr) | (gE != nullptr) | (grho != nullptr);
     const bool want_joints = (gxyz != nullptr) | (gmass != nullptr);
-    // where joint j's results go: an id outside the arrays falls back to j
-    auto place = [&](int j) {
-        const int id = jo != nullptr ? jo[j] : j;
-        return ((id >= 0) & (id < nJ_max)) ? id : j;
-    };
 
     // ---- the rows without an eigenvalue: zeros (the whole weighted row when the truss has no mode at all)
     for (int r = weighted ? min(n_modes, 1) : n_modes; r < R; ++r) {
@@ -126,10 +116,8 @@ __global__ __launch_bounds__(256) void trs_mg_grad_kernel(
 
     // ---- stage: the member table, once
     for (int m = tid; m < members; m += 256) {
-        int2 c = mem.ends(mbase + m);
-        c.x = min(max(c.x, 0), nJ_max - 1);   // (a joint id outside the arrays would index LDS outside them)
-        c.y = min(max(c.y, 0), nJ_max - 1);
-        const MemberGeom g = member_geom(Xyz, c.x, c.y);
+        const int2 c = v.ends(m).c;
+        const MemberGeom g = member_geom(v.X, c.x, c.y);
         const bool live = g.len > 0.0;
         t.mends[m] = c;
         t.cx[m] = live ? g.c[0] : 0.0;
@@ -139,15 +127,15 @@ __global__ __launch_bounds__(256) void trs_mg_grad_kernel(
         t.kl[m] = live ? mem.EA(mbase + m) / g.len / g.len : 0.0;
         t.mg[m] = live ? mass_scale * (0.5 * (mem.area(mbase + m) * mem.density(mbase + m))) : 0.0;
     }
-    if (gxyz != nullptr) build_end_lists(t, mem, mbase, joints, members, nJ_max, tid, InTruss{joints});
+    if (gxyz != nullptr) build_end_lists(t, v, tid);
 
     for (int k0 = 0; k0 < n_modes; k0 += pc) {
         const int kc = min(pc, n_modes - k0);
         __syncthreads();   // (the tables and the lists are written; the previous pass's readers of phi are done)
         for (int x = tid; x < kc * ndof_max; x += 256) {
             const int kk = x / ndof_max, d = x - kk * ndof_max;
-            const int row = d < ndof ? fi[d] : -1;
-            t.phi[x] = ((row >= 0) & (row < nfree)) ? Xb[(size_t)(k0 + kk) * ld_f + row] : 0.0;
+            const int row = v.row_of(d);
+            t.phi[x] = row >= 0 ? Xb[(size_t)(k0 + kk) * ld_f + row] : 0.0;
         }
         __syncthreads();
 
@@ -205,7 +193,7 @@ __global__ __launch_bounds__(256) void trs_mg_grad_kernel(
         if (want_joints)
             for (int j = tid; j < nJ_max; j += 256) {
                 const bool own = j < joints;
-                const int o = place(j);
+                const int o = v.place(j);
                 const int* list = t.ends + (own && gxyz != nullptr ? t.start[j] : 0);
                 const int deg = own && gxyz != nullptr ? t.cnt[j] : 0;
                 double acc[3] = {0.0, 0.0, 0.0}, accM = 0.0;
@@ -272,19 +260,16 @@ int mg_pass(int nJ_max, int nM_max, int p) {
     return half >= 2 ? half : pc;
 }
 
-int mg_launch(int B, int nJ_max, int nM_max, const double* xyz, const TrsMembers& mem, const int* free_index,
-              const int* n_free, const int* nJ, const int* nM, const int* joint_out, const double* X, int ld_f,
-              const double* lam, const int* n_mass, int p, double mass_scale, const double* w, double* gA, double* gE,
-              double* grho, double* gxyz, double* gmass, hipStream_t stream) {
+int mg_launch(int B, const TrsBatch& bt, const double* X, const double* lam, const int* n_mass, int p, double mass_scale,
+              const double* w, double* gA, double* gE, double* grho, double* gxyz, double* gmass, hipStream_t stream) {
     if (B <= 0) return 0;
-    if (!trs_mg_fits(nJ_max, nM_max, p) || ld_f < 1 || X == nullptr || lam == nullptr || n_mass == nullptr)
+    if (!trs_mg_fits(bt.nJ_max, bt.nM_max, p) || bt.ld_f < 1 || X == nullptr || lam == nullptr || n_mass == nullptr)
         return (int)hipErrorInvalidValue;
     if (gA == nullptr && gE == nullptr && grho == nullptr && gxyz == nullptr && gmass == nullptr) return 0;
-    const int pc = mg_pass(nJ_max, nM_max, p);
+    const int pc = mg_pass(bt.nJ_max, bt.nM_max, p);
     trs_lds::raise_lds_once<trs_mg_grad_kernel>();
-    hipLaunchKernelGGL(trs_mg_grad_kernel, dim3(B), dim3(256), mg_lds(nJ_max, nM_max, pc), stream, xyz, mem, free_index,
-                       n_free, nJ, nM, joint_out, nJ_max, nM_max, X, ld_f, lam, n_mass, p, pc, mass_scale, w, gA, gE, grho,
-                       gxyz, gmass);
+    hipLaunchKernelGGL(trs_mg_grad_kernel, dim3(B), dim3(256), mg_lds(bt.nJ_max, bt.nM_max, pc), stream, bt, X, lam, n_mass,
+                       p, pc, mass_scale, w, gA, gE, grho, gxyz, gmass);
     return (int)hipGetLastError();
 }
 
@@ -303,9 +288,9 @@ int trs_mg_grad(int B, int nJ_max, int nM_max, const double* xyz, const int32_t*
                 const int32_t* nM, const int32_t* joint_out, const double* X, int ld_f, const double* lam,
                 const int32_t* n_mass, int p, double mass_scale, const double* w, double* gA, double* gE, double* grho,
                 double* gxyz, double* gmass, void* stream) {
-    const TrsMembers mem = trs_members_general(conn, E, A, rho);
-    return mg_launch(B, nJ_max, nM_max, xyz, mem, free_index, n_free, nJ, nM, joint_out, X, ld_f, lam, n_mass, p,
-                     mass_scale, w, gA, gE, grho, gxyz, gmass, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_general(conn, E, A, rho), free_index, n_free, nJ, nM,
+                                  joint_out, ld_f);
+    return mg_launch(B, bt, X, lam, n_mass, p, mass_scale, w, gA, gE, grho, gxyz, gmass, (hipStream_t)stream);
 }
 
 int trs_mg_tab_grad(int B, int nJ_max, int nM_max, const double* xyz, const uint16_t* conn16, const uint8_t* type_idx,
@@ -313,9 +298,9 @@ int trs_mg_tab_grad(int B, int nJ_max, int nM_max, const double* xyz, const uint
                     const int32_t* nM, const int32_t* joint_out, const double* X, int ld_f, const double* lam,
                     const int32_t* n_mass, int p, double mass_scale, const double* w, double* gA, double* gE,
                     double* grho, double* gxyz, double* gmass, void* stream) {
-    const TrsMembers mem = trs_members_table(conn16, type_idx, types);
-    return mg_launch(B, nJ_max, nM_max, xyz, mem, free_index, n_free, nJ, nM, joint_out, X, ld_f, lam, n_mass, p,
-                     mass_scale, w, gA, gE, grho, gxyz, gmass, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), free_index, n_free, nJ,
+                                  nM, joint_out, ld_f);
+    return mg_launch(B, bt, X, lam, n_mass, p, mass_scale, w, gA, gE, grho, gxyz, gmass, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -49,47 +49,42 @@ __host__ __device__ inline MassTables mass_layout(Arena& a, int nM_max) {
     return t;
 }
 
-__global__ __launch_bounds__(256) void trs_modes_mass_kernel(
-    const double* __restrict__ xyz, const TrsMembers mem, const double* __restrict__ joint_mass,
-    const int* __restrict__ joint_in, const double mass_scale, const int* __restrict__ free_index,
-    const int* __restrict__ n_free, const int* __restrict__ nJ, const int* __restrict__ nM, const int nJ_max,
-    const int nM_max, double* __restrict__ Mf, const int ld_f, int* __restrict__ n_mass) {
+// (The batch's joint_out slot holds joint_in here: the same map, read the other way.)
+__global__ __launch_bounds__(256) void trs_modes_mass_kernel(const TrsBatch bt, const double* __restrict__ joint_mass,
+                                                             const double mass_scale, double* __restrict__ Mf,
+                                                             int* __restrict__ n_mass) {
     extern __shared__ double sh[];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int joints = nJ[b], members = nM[b];
+    const TrussView v = bt.truss(b);
     trs_lds::Carve lds(sh);
-    const MassTables t = mass_layout(lds, nM_max);
+    const MassTables t = mass_layout(lds, bt.nM_max);
     double* half = t.half;
     int2* ends = t.ends;
     int& count = *t.count;
-    const int* fi = free_index + (size_t)b * 3 * nJ_max;
-    const double* X = xyz + (size_t)b * 3 * nJ_max;
-    const size_t mbase = (size_t)b * nM_max;
-    double* mf = Mf + (size_t)b * ld_f;
-    const int n = n_free[b], npad = trs_round_up(n, TRS_NB);
+    double* mf = Mf + (size_t)b * bt.ld_f;
+    const int n = v.nfree, npad = min(trs_round_up(n, TRS_NB), bt.ld_f);
     if (tid == 0) count = 0;
-    for (int m = tid; m < members; m += 256) {
-        const int2 c = mem.ends(mbase + m);
-        const MemberGeom g = member_geom(X, c.x, c.y);
-        ends[m] = c;
-        half[m] = 0.5 * (mem.area(mbase + m) * g.len * mem.density(mbase + m));
+    for (int m = tid; m < v.members; m += 256) {
+        const int2 c = v.ends(m).c;
+        const MemberGeom g = member_geom(v.X, c.x, c.y);
+        ends[m] = v.raw_ends(m);   // (compared with joint ids, never an index)
+        half[m] = 0.5 * (v.mem.area(v.mbase + m) * g.len * v.mem.density(v.mbase + m));
     }
     for (int c = n + tid; c < npad; c += 256) mf[c] = 0.0;
     __syncthreads();
     int with_mass = 0;
-    for (int j = tid; j < joints; j += 256) {
+    for (int j = tid; j < v.joints; j += 256) {
         double sum = 0.0;
-        for (int m = 0; m < members; ++m) {
+        for (int m = 0; m < v.members; ++m) {
             const int2 c = ends[m];
             if (c.x == j) sum += half[m];
             if (c.y == j) sum += half[m];
         }
         double mj = mass_scale * sum;
-        if (joint_mass != nullptr)
-            mj += joint_mass[(size_t)b * nJ_max + (joint_in != nullptr ? joint_in[(size_t)b * nJ_max + j] : j)];
+        if (joint_mass != nullptr) mj += joint_mass[(size_t)b * bt.nJ_max + v.place(j)];
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-            const int row = fi[3 * j + a];
+            const int row = v.row_of(3 * j + a);
             if (row >= 0) {
                 mf[row] = mj;
                 with_mass += mj > 0.0;
@@ -306,38 +301,31 @@ __global__ __launch_bounds__(64) void trs_modes_step_kernel(const int p, const i
 // ---- shapes ---------------------------------------------------------------------------------------------------------
 // One work-group per (truss, mode): the component of largest magnitude - the first in the caller's DOF order on a
 // tie - decides the sign (an exact, order-free reduction), then the column goes out through free_index and joint_out.
-__global__ __launch_bounds__(256) void trs_modes_shapes_kernel(const int p, const int nJ_max,
-                                                               const double* __restrict__ X_all, const int ld_f,
-                                                               const int* __restrict__ free_index,
-                                                               const int* __restrict__ nJ,
-                                                               const int* __restrict__ joint_out,
+__global__ __launch_bounds__(256) void trs_modes_shapes_kernel(const TrsBatch bt, const int p,
+                                                               const double* __restrict__ X_all,
                                                                double* __restrict__ phi) {
     const int b = blockIdx.x / p, k = blockIdx.x - b * p, tid = threadIdx.x;
-    const int ndof = 3 * nJ[b], ndof_max = 3 * nJ_max;
-    const int* fi = free_index + (size_t)b * ndof_max;
-    const int* jo = joint_out != nullptr ? joint_out + (size_t)b * nJ_max : nullptr;
-    const double* x = X_all + ((size_t)b * QB + k) * ld_f;
-    double* out = phi + (size_t)blockIdx.x * ndof_max;
-    auto place_of = [&](int d) { return jo != nullptr ? 3 * jo[d / 3] + d % 3 : d; };
-    const bool flip = largest_component(x, ndof, tid, [&](int d) { return fi[d]; }, place_of) < 0.0;
-    for (int d = tid; d < ndof_max; d += 256) {
-        const int r = d < ndof ? fi[d] : -1;
-        const int o = place_of(d);
-        const double v = r >= 0 ? x[r] : 0.0;
-        out[o] = (flip && r >= 0) ? -v : v;
+    const TrussView v = bt.truss(b);
+    const double* x = X_all + ((size_t)b * QB + k) * bt.ld_f;
+    double* out = phi + (size_t)blockIdx.x * v.ndof_max;
+    const bool flip = largest_component(x, v.ndof, tid, [&](int d) { return v.row_of(d); },
+                                        [&](int d) { return v.place_dof(d); }) < 0.0;
+    for (int d = tid; d < v.ndof_max; d += 256) {
+        const int r = v.row_of(d);
+        const double val = r >= 0 ? x[r] : 0.0;
+        out[v.place_dof(d)] = (flip && r >= 0) ? -val : val;
     }
 }
 
 size_t modes_mass_lds(int nM_max) { return trs_lds::count([&](auto& a) { mass_layout(a, nM_max); }); }
 
-int modes_mass_launch(int B, int nJ_max, int nM_max, const double* xyz, const TrsMembers& mem, const double* joint_mass,
-                      const int* joint_in, double mass_scale, const int* free_index, const int* n_free, const int* nJ,
-                      const int* nM, double* Mf, int ld_f, int* n_mass, hipStream_t stream) {
+int modes_mass_launch(int B, const TrsBatch& bt, const double* joint_mass, double mass_scale, double* Mf, int* n_mass,
+                      hipStream_t stream) {
     if (B <= 0) return 0;
-    if (!trs_modes_fits(nJ_max, nM_max)) return (int)hipErrorInvalidValue;
+    if (!trs_modes_fits(bt.nJ_max, bt.nM_max)) return (int)hipErrorInvalidValue;
     trs_lds::raise_lds_once<trs_modes_mass_kernel>();
-    hipLaunchKernelGGL(trs_modes_mass_kernel, dim3(B), dim3(256), modes_mass_lds(nM_max), stream, xyz, mem, joint_mass,
-                       joint_in, mass_scale, free_index, n_free, nJ, nM, nJ_max, nM_max, Mf, ld_f, n_mass);
+    hipLaunchKernelGGL(trs_modes_mass_kernel, dim3(B), dim3(256), modes_mass_lds(bt.nM_max), stream, bt, joint_mass,
+                       mass_scale, Mf, n_mass);
     return (int)hipGetLastError();
 }
 
@@ -355,18 +343,18 @@ int trs_modes_mass(int B, int nJ_max, int nM_max, const double* xyz, const int32
                    const double* rho, const double* joint_mass, const int32_t* joint_in, double mass_scale,
                    const int32_t* free_index, const int32_t* n_free, const int32_t* nJ, const int32_t* nM, double* Mf,
                    int ld_f, int32_t* n_mass, void* stream) {
-    const TrsMembers mem = trs_members_general(conn, nullptr, A, rho);
-    return modes_mass_launch(B, nJ_max, nM_max, xyz, mem, joint_mass, joint_in, mass_scale, free_index, n_free, nJ, nM,
-                             Mf, ld_f, n_mass, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_general(conn, nullptr, A, rho), free_index, n_free, nJ,
+                                  nM, joint_in, ld_f);
+    return modes_mass_launch(B, bt, joint_mass, mass_scale, Mf, n_mass, (hipStream_t)stream);
 }
 
 int trs_modes_tab_mass(int B, int nJ_max, int nM_max, const double* xyz, const uint16_t* conn16, const uint8_t* type_idx,
                        const double* types, const double* joint_mass, const int32_t* joint_in, double mass_scale,
                        const int32_t* free_index, const int32_t* n_free, const int32_t* nJ, const int32_t* nM,
                        double* Mf, int ld_f, int32_t* n_mass, void* stream) {
-    const TrsMembers mem = trs_members_table(conn16, type_idx, types);
-    return modes_mass_launch(B, nJ_max, nM_max, xyz, mem, joint_mass, joint_in, mass_scale, free_index, n_free, nJ, nM,
-                             Mf, ld_f, n_mass, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), free_index, n_free, nJ,
+                                  nM, joint_in, ld_f);
+    return modes_mass_launch(B, bt, joint_mass, mass_scale, Mf, n_mass, (hipStream_t)stream);
 }
 
 int trs_modes_step(int B, int p, const int32_t* n_free, const int32_t* n_mass, const double* Mf, double* F, double* X,
@@ -383,8 +371,8 @@ int trs_modes_shapes(int B, int p, int nJ_max, const double* X, int ld_f, const 
                      const int32_t* joint_out, double* phi, void* stream) {
     if (B <= 0 || p <= 0) return 0;
     if (p > QB) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(trs_modes_shapes_kernel, dim3((unsigned)B * (unsigned)p), dim3(256), 0, (hipStream_t)stream, p,
-                       nJ_max, X, ld_f, free_index, nJ, joint_out, phi);
+    hipLaunchKernelGGL(trs_modes_shapes_kernel, dim3((unsigned)B * (unsigned)p), dim3(256), 0, (hipStream_t)stream,
+                       trs_batch_dofs(nJ_max, free_index, nullptr, nJ, joint_out, ld_f), p, X, phi);
     return (int)hipGetLastError();
 }
 

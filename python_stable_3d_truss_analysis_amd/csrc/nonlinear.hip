@@ -90,51 +90,41 @@ __device__ __forceinline__ double block_nan_max(double v, double* slot, const in
 }
 
 __global__ __launch_bounds__(256) void trs_nl_state_kernel(
-    const double* __restrict__ xyz, const TrsMembers mem, const double* __restrict__ loads,
-    const int* __restrict__ free_index, const int* __restrict__ n_free, const int* __restrict__ nJ,
-    const int* __restrict__ nM, const int nJ_max, const int nM_max, const int ld_f, const double lambda, const double tol,
-    const int it, const int last, const int step, const int S, const double* __restrict__ U, int* __restrict__ st,
+    const TrsBatch bt, const double* __restrict__ loads, const double lambda, const double tol, const int it,
+    const int last, const int step, const int S, const double* __restrict__ U, int* __restrict__ st,
     double* __restrict__ Xc, double* __restrict__ R, double* __restrict__ W, int* __restrict__ active,
     double* __restrict__ u_out, double* __restrict__ N_out, double* __restrict__ f_out, int* __restrict__ iters,
-    int* __restrict__ status_out, double* __restrict__ residual, const int* __restrict__ joint_out) {
+    int* __restrict__ status_out, double* __restrict__ residual) {
     extern __shared__ double sh[];   // (no static LDS beside it: the dynamic ceiling is the whole of a CU's)
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int joints = min(max(nJ[b], 0), nJ_max), members = min(max(nM[b], 0), nM_max);
-    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
-    const int n = min(max(n_free[b], 0), ld_f);
+    const TrussView tr = bt.truss(b);
+    const int nJ_max = bt.nJ_max, nM_max = bt.nM_max;
+    const int joints = tr.joints, members = tr.members, ndof = tr.ndof, ndof_max = tr.ndof_max;
     trs_lds::Carve lds(sh);
     const StateTables t = state_layout(lds, nJ_max, nM_max);
     double* ush = t.v;
-    const int* fi = free_index + (size_t)b * ndof_max;
-    const double* X = xyz + (size_t)b * ndof_max;
+    const double* __restrict__ X = tr.X;
     const double* P = loads + (size_t)b * ndof_max;
     const double* Ub = U + (size_t)b * ndof_max;
-    const size_t mbase = (size_t)b * nM_max;
-    const int* jo = joint_out != nullptr ? joint_out + (size_t)b * nJ_max : nullptr;
+    const size_t mbase = tr.mbase;
     // (every thread reads the status word before the barriers below; thread 0 writes it behind them)
     int status = st[4 * b], its = st[4 * b + 1];
     if (it == 0 && last != 2) {   // the load step begins (not again in a call that only writes the outputs)
         status = status >= TRS_NL_ITER_LIMIT ? TRS_NL_NOT_ATTEMPTED : TRS_NL_ACTIVE;
         its = 0;
     }
-    auto row_of = [&](int d) {   // the reduced row of DOF d, -1: held, past the truss's joints or outside the arrays
-        const int r = d < ndof ? fi[d] : -1;
-        return r < n ? r : -1;
-    };
-    build_end_lists(t, mem, mbase, joints, members, nJ_max, tid, InTruss{joints});
-    order_by_neighbour(t, t.oth, mem, mbase, joints, tid);
+    build_end_lists(t, tr, tid);
+    order_by_neighbour(t, t.oth, tr, tid);
     // ---- the state, one thread per DOF ----
     for (int d = tid; d < ndof_max; d += 256) {
-        const double u = row_of(d) >= 0 ? Ub[d] : 0.0;
+        const double u = tr.row_of(d) >= 0 ? Ub[d] : 0.0;
         ush[d] = u;
         Xc[(size_t)b * ndof_max + d] = X[d] + u;
     }
     __syncthreads();   // (u is staged, the end lists are sorted)
     // ---- one thread per member: n, l, N ----
     for (int m = tid; m < members; m += 256) {
-        int2 c = mem.ends(mbase + m);
-        c.x = min(max(c.x, 0), nJ_max - 1);
-        c.y = min(max(c.y, 0), nJ_max - 1);
+        const int2 c = tr.ends(m).c;
         double D[3], dl[3], d[3], L02 = 0.0, l2 = 0.0, Ddl = 0.0, dldl = 0.0;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
@@ -147,7 +137,7 @@ __global__ __launch_bounds__(256) void trs_nl_state_kernel(
             dldl += dl[a] * dl[a];
         }
         const double L0 = sqrt(L02), l = sqrt(l2);
-        const double EA = mem.EA(mbase + m);
+        const double EA = tr.mem.EA(mbase + m);
         const double e = (2.0 * Ddl + dldl) / (L0 * (l + L0));
         const double N = EA * e;
         const double g = N / l;
@@ -178,7 +168,7 @@ __global__ __launch_bounds__(256) void trs_nl_state_kernel(
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             const int d = 3 * j + a;
-            if (row_of(d) >= 0) {
+            if (tr.row_of(d) >= 0) {
                 const double p = lambda * P[d];
                 const double r = p - f[a];
                 ush[d] = r;
@@ -198,7 +188,7 @@ __global__ __launch_bounds__(256) void trs_nl_state_kernel(
             status = TRS_NL_ITER_LIMIT;
     }
     const bool still = status == TRS_NL_ACTIVE;
-    for (int d = tid; d < ndof_max; d += 256) R[(size_t)b * ndof_max + d] = (still && row_of(d) >= 0) ? ush[d] : 0.0;
+    for (int d = tid; d < ndof_max; d += 256) R[(size_t)b * ndof_max + d] = (still && tr.row_of(d) >= 0) ? ush[d] : 0.0;
     if (tid == 0) {
         st[4 * b] = status;
         st[4 * b + 1] = its;
@@ -208,11 +198,8 @@ __global__ __launch_bounds__(256) void trs_nl_state_kernel(
     // ---- the outputs of this load step, in the caller's numbering ----
     const size_t bs = (size_t)b * S + step;
     for (int d = tid; d < ndof_max; d += 256) {
-        const int j = d / 3;
-        int id = jo != nullptr ? jo[j] : j;
-        id = ((id >= 0) & (id < nJ_max)) ? id : j;
-        const size_t o = bs * ndof_max + 3 * id + d % 3;
-        const bool free_dof = row_of(d) >= 0;
+        const size_t o = bs * ndof_max + tr.place_dof(d);
+        const bool free_dof = tr.row_of(d) >= 0;
         u_out[o] = free_dof ? Ub[d] : 0.0;
         f_out[o] = d < ndof ? (free_dof ? lambda * P[d] : ush[d]) : 0.0;
     }
@@ -224,33 +211,30 @@ __global__ __launch_bounds__(256) void trs_nl_state_kernel(
     }
 }
 
-__global__ __launch_bounds__(256) void trs_nl_tangent_kernel(
-    const TrsMembers mem, const int* __restrict__ free_index, const int* __restrict__ n_free,
-    const int* __restrict__ nJ, const int* __restrict__ nM, const int nJ_max, const int nM_max, const int ld,
-    const int slab_rows, double* __restrict__ S_all, const int* __restrict__ env_all, const int full,
-    const double* __restrict__ W) {
+// (The batch's ld_f is slab_rows here: the reduced rows are the slab's.)
+__global__ __launch_bounds__(256) void trs_nl_tangent_kernel(const TrsBatch bt, const int ld, double* __restrict__ S_all,
+                                                             const int* __restrict__ env_all, const int full,
+                                                             const double* __restrict__ W) {
     extern __shared__ double sh[];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int joints = min(max(nJ[b], 0), nJ_max), members = min(max(nM[b], 0), nM_max);
-    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
-    const int n = min(max(n_free[b], 0), slab_rows), npad = min(trs_round_up(n, TRS_NB), slab_rows);
+    const TrussView tr = bt.truss(b);
+    const int slab_rows = bt.ld_f, joints = tr.joints, ndof_max = tr.ndof_max;
+    const int n = tr.nfree, npad = min(trs_round_up(n, TRS_NB), slab_rows);
     const int nch = npad / 16;
     trs_lds::Carve lds(sh);
-    const TangentTables t = tangent_layout(lds, nJ_max, nM_max, slab_rows);
+    const TangentTables t = tangent_layout(lds, bt.nJ_max, bt.nM_max, slab_rows);
     double* own = t.own;
     int *oth = t.oth, *fi = t.fi, *rowdof = t.rowdof;
-    const size_t mbase = (size_t)b * nM_max;
-    const int* fig = free_index + (size_t)b * ndof_max;
+    const size_t mbase = tr.mbase;
     for (int c = tid; c < slab_rows; c += 256) rowdof[c] = -1;
-    build_end_lists(t, mem, mbase, joints, members, nJ_max, tid, InTruss{joints});
+    build_end_lists(t, tr, tid);
     __syncthreads();   // (the lists are sorted; rowdof is cleared)
     for (int d = tid; d < ndof_max; d += 256) {
-        int r = d < ndof ? fig[d] : -1;
-        r = r < n ? r : -1;
+        const int r = tr.row_of(d);
         fi[d] = r;
         if (r >= 0) rowdof[r] = d;
     }
-    order_by_neighbour(t, oth, mem, mbase, joints, tid);
+    order_by_neighbour(t, oth, tr, tid);
     const double* Wb = W + mbase * NL_W;
     // delta_m = w3 n n^T + w4 I, entry (r, s) formed as w3 (n_r n_s) [+ w4]: symmetric to the bit, as the assembly's k (c_r c_s)
     auto delta = [&](int m, double (&v)[6]) {
@@ -340,9 +324,8 @@ __global__ __launch_bounds__(256) void trs_nl_tangent_kernel(
     }
 }
 
-__global__ __launch_bounds__(256) void trs_nl_update_kernel(const int nJ_max, const int* __restrict__ free_index,
-                                                            const int* __restrict__ n_free, const int* __restrict__ nJ,
-                                                            const double* __restrict__ uf, const int ld_uf,
+// (The batch's ld_f is ld_uf here.)
+__global__ __launch_bounds__(256) void trs_nl_update_kernel(const TrsBatch bt, const double* __restrict__ uf,
                                                             const int* __restrict__ info, const int it,
                                                             double* __restrict__ U, int* __restrict__ st) {
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -358,48 +341,45 @@ __global__ __launch_bounds__(256) void trs_nl_update_kernel(const int nJ_max, co
             st[4 * b + 2] = pivot;   // (latched: later factorisations of the frozen tangent do not count)
     }
     if (!ok) return;
-    const int ndof_max = 3 * nJ_max, ndof = 3 * min(max(nJ[b], 0), nJ_max);
-    const int n = min(max(n_free[b], 0), ld_uf);
-    const int* fi = free_index + (size_t)b * ndof_max;
-    for (int d = tid; d < ndof; d += 256) {
-        const int r = fi[d];
-        if (r < 0 || r >= n) continue;
-        double* u = U + (size_t)b * ndof_max + d;
-        const double du = uf[(size_t)b * ld_uf + r];
+    const TrussView tr = bt.truss(b);
+    for (int d = tid; d < tr.ndof; d += 256) {
+        const int r = tr.row_of(d);
+        if (r < 0) continue;
+        double* u = U + (size_t)b * tr.ndof_max + d;
+        const double du = uf[(size_t)b * bt.ld_f + r];
         *u = *u == 0.0 ? du : *u + du;   // (0 + du is du, bits and all: the first iterate is the substitution's output)
     }
 }
 
-int nl_state_launch(int B, int nJ_max, int nM_max, const double* xyz, const TrsMembers& mem, const double* loads,
-                    const int* free_index, const int* n_free, const int* nJ, const int* nM, int ld_f, double lambda,
-                    double tol, int it, int last, int step, int S, const double* U, int* st, double* Xc, double* R,
-                    double* W, int* active, double* u, double* N, double* f_ext, int* iters, int* status,
-                    double* residual, const int* joint_out, hipStream_t stream) {
-    if (B < 0 || nJ_max <= 0 || nM_max < 0 || ld_f < 0 || it < 0 || last < 0 || last > 2 || S < 1 || step < 0 || step >= S)
+int nl_state_launch(int B, const TrsBatch& bt, const double* loads, double lambda, double tol, int it, int last, int step,
+                    int S, const double* U, int* st, double* Xc, double* R, double* W, int* active, double* u, double* N,
+                    double* f_ext, int* iters, int* status, double* residual, hipStream_t stream) {
+    if (B < 0 || bt.nJ_max <= 0 || bt.nM_max < 0 || bt.ld_f < 0 || it < 0 || last < 0 || last > 2 || S < 1 || step < 0 ||
+        step >= S)
         return (int)hipErrorInvalidValue;
     if (!(tol >= 0.0) || !U || !st || !Xc || !R || !W || !active) return (int)hipErrorInvalidValue;
     if (last && (!u || !N || !f_ext || !iters || !status || !residual)) return (int)hipErrorInvalidValue;
     if (B == 0) return 0;
-    if (!trs_nl_fits(nJ_max, nM_max)) return (int)hipErrorInvalidValue;
+    if (!trs_nl_fits(bt.nJ_max, bt.nM_max)) return (int)hipErrorInvalidValue;
     trs_lds::raise_lds_once<trs_nl_state_kernel>();
-    hipLaunchKernelGGL(trs_nl_state_kernel, dim3(B), dim3(256), state_lds(nJ_max, nM_max), stream, xyz, mem, loads,
-                       free_index, n_free, nJ, nM, nJ_max, nM_max, ld_f, lambda, tol, it, last, step, S, U, st, Xc, R, W,
-                       active, u, N, f_ext, iters, status, residual, joint_out);
+    hipLaunchKernelGGL(trs_nl_state_kernel, dim3(B), dim3(256), state_lds(bt.nJ_max, bt.nM_max), stream, bt, loads, lambda,
+                       tol, it, last, step, S, U, st, Xc, R, W, active, u, N, f_ext, iters, status, residual);
     return (int)hipGetLastError();
 }
 
-int nl_tangent_launch(int B, int nJ_max, int nM_max, const TrsMembers& mem, const int* free_index, const int* n_free,
-                      const int* nJ, const int* nM, int ld, int slab_rows, double* S, const int* env, int flags,
-                      const double* W, hipStream_t stream) {
-    if (B < 0 || nJ_max <= 0 || nM_max < 0 || slab_rows <= 0 || slab_rows % TRS_NB != 0 || ld < slab_rows || !S || !W)
+// (bt.ld_f = slab_rows)
+int nl_tangent_launch(int B, const TrsBatch& bt, int ld, double* S, const int* env, int flags, const double* W,
+                      hipStream_t stream) {
+    const int slab_rows = bt.ld_f;
+    if (B < 0 || bt.nJ_max <= 0 || bt.nM_max < 0 || slab_rows <= 0 || slab_rows % TRS_NB != 0 || ld < slab_rows || !S || !W)
         return (int)hipErrorInvalidValue;
     if ((flags & TRS_ASM_COMPACT) != 0) return (int)hipErrorInvalidValue;   // (no slab to amend)
     if (B == 0) return 0;
-    const size_t lds = tangent_lds(nJ_max, nM_max, slab_rows);
+    const size_t lds = tangent_lds(bt.nJ_max, bt.nM_max, slab_rows);
     if (lds > TRS_LDS_BYTES) return (int)hipErrorInvalidValue;
     trs_lds::raise_lds_once<trs_nl_tangent_kernel>();
-    hipLaunchKernelGGL(trs_nl_tangent_kernel, dim3(B), dim3(256), lds, stream, mem, free_index, n_free, nJ, nM, nJ_max,
-                       nM_max, ld, slab_rows, S, env, (flags & TRS_ASM_FULL_SYMMETRIC) != 0 ? 1 : 0, W);
+    hipLaunchKernelGGL(trs_nl_tangent_kernel, dim3(B), dim3(256), lds, stream, bt, ld, S, env,
+                       (flags & TRS_ASM_FULL_SYMMETRIC) != 0 ? 1 : 0, W);
     return (int)hipGetLastError();
 }
 
@@ -421,9 +401,10 @@ int trs_nl_state(int B, int nJ_max, int nM_max, const double* xyz, const int32_t
                  const double* U, int32_t* st, double* Xc, double* R, double* W, int32_t* active, double* u, double* N,
                  double* f_ext, int32_t* iters, int32_t* status, double* residual, const int32_t* joint_out,
                  void* stream) {
-    return nl_state_launch(B, nJ_max, nM_max, xyz, trs_members_general(conn, E, A), loads, free_index, n_free, nJ, nM,
-                           ld_f, lambda, tol, it, last, step, S, U, st, Xc, R, W, active, u, N, f_ext, iters, status,
-                           residual, joint_out, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_general(conn, E, A), free_index, n_free, nJ, nM,
+                                  joint_out, ld_f);
+    return nl_state_launch(B, bt, loads, lambda, tol, it, last, step, S, U, st, Xc, R, W, active, u, N, f_ext, iters,
+                           status, residual, (hipStream_t)stream);
 }
 
 int trs_nl_state_tab(int B, int nJ_max, int nM_max, const double* xyz, const uint16_t* conn16, const uint8_t* type_idx,
@@ -433,16 +414,18 @@ int trs_nl_state_tab(int B, int nJ_max, int nM_max, const double* xyz, const uin
                      double* u, double* N, double* f_ext, int32_t* iters, int32_t* status, double* residual,
                      const int32_t* joint_out, void* stream) {
     if (B > 0 && (!conn16 || !type_idx || !types)) return (int)hipErrorInvalidValue;
-    return nl_state_launch(B, nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), loads, free_index, n_free,
-                           nJ, nM, ld_f, lambda, tol, it, last, step, S, U, st, Xc, R, W, active, u, N, f_ext, iters,
-                           status, residual, joint_out, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), free_index, n_free, nJ,
+                                  nM, joint_out, ld_f);
+    return nl_state_launch(B, bt, loads, lambda, tol, it, last, step, S, U, st, Xc, R, W, active, u, N, f_ext, iters,
+                           status, residual, (hipStream_t)stream);
 }
 
 int trs_nl_tangent(int B, int nJ_max, int nM_max, const int32_t* conn, const double* E, const double* A,
                    const int32_t* free_index, const int32_t* n_free, const int32_t* nJ, const int32_t* nM, int ld,
                    int slab_rows, double* S, const int32_t* env, int flags, const double* W, void* stream) {
-    return nl_tangent_launch(B, nJ_max, nM_max, trs_members_general(conn, E, A), free_index, n_free, nJ, nM, ld,
-                             slab_rows, S, env, flags, W, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, nullptr, trs_members_general(conn, E, A), free_index, n_free, nJ, nM,
+                                  nullptr, slab_rows);
+    return nl_tangent_launch(B, bt, ld, S, env, flags, W, (hipStream_t)stream);
 }
 
 int trs_nl_tangent_tab(int B, int nJ_max, int nM_max, const uint16_t* conn16, const uint8_t* type_idx,
@@ -450,16 +433,17 @@ int trs_nl_tangent_tab(int B, int nJ_max, int nM_max, const uint16_t* conn16, co
                        const int32_t* nM, int ld, int slab_rows, double* S, const int32_t* env, int flags,
                        const double* W, void* stream) {
     if (B > 0 && (!conn16 || !type_idx || !types)) return (int)hipErrorInvalidValue;
-    return nl_tangent_launch(B, nJ_max, nM_max, trs_members_table(conn16, type_idx, types), free_index, n_free, nJ, nM,
-                             ld, slab_rows, S, env, flags, W, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, nullptr, trs_members_table(conn16, type_idx, types), free_index, n_free,
+                                  nJ, nM, nullptr, slab_rows);
+    return nl_tangent_launch(B, bt, ld, S, env, flags, W, (hipStream_t)stream);
 }
 
 int trs_nl_update(int B, int nJ_max, const int32_t* free_index, const int32_t* n_free, const int32_t* nJ,
                   const double* uf, int ld_uf, const int32_t* info, int it, double* U, int32_t* st, void* stream) {
     if (B < 0 || nJ_max <= 0 || ld_uf < 0 || it < 1 || !uf || !info || !U || !st) return (int)hipErrorInvalidValue;
     if (B == 0) return 0;
-    hipLaunchKernelGGL(trs_nl_update_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, nJ_max, free_index, n_free, nJ,
-                       uf, ld_uf, info, it, U, st);
+    hipLaunchKernelGGL(trs_nl_update_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream,
+                       trs_batch_dofs(nJ_max, free_index, n_free, nJ, nullptr, ld_uf), uf, info, it, U, st);
     return (int)hipGetLastError();
 }
 

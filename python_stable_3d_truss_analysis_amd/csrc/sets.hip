@@ -40,24 +40,21 @@ static_assert(KMAX * KMAX == 64 && MAX_PASS * KMAX == 64, "one lane per entry of
 
 // ---- the apply kernel ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64 * WAVES) void trs_sets_apply_kernel(
-    const int L, const int g, const int S, const int s0, const int Sc, const int C, const int slice,
-    const double* __restrict__ xyz, const TrsMembers mem, const int* __restrict__ free_index, const int* __restrict__ nJ,
-    const int* __restrict__ nM, const int nJ_max, const int nM_max, const int* __restrict__ cols,
-    const int* __restrict__ slot, const double* __restrict__ gamma, const double* __restrict__ Z,
-    const double* __restrict__ U, const int ld_f, const double r_tol, double* __restrict__ piv_out,
+    const TrsBatch bt, const int L, const int g, const int S, const int s0, const int Sc, const int C, const int slice,
+    const int* __restrict__ cols, const int* __restrict__ slot, const double* __restrict__ gamma,
+    const double* __restrict__ Z, const double* __restrict__ U, const double r_tol, double* __restrict__ piv_out,
     int* __restrict__ unst_out, int* __restrict__ first_out, double* __restrict__ ps_out, int* __restrict__ pm_out,
-    double* __restrict__ pd_out, int* __restrict__ pj_out, double* __restrict__ NA, double* __restrict__ UA,
-    const int* __restrict__ joint_out) {
+    double* __restrict__ pd_out, int* __restrict__ pj_out, double* __restrict__ NA, double* __restrict__ UA) {
     extern __shared__ double sh[];
+    const int nJ_max = bt.nJ_max, nM_max = bt.nM_max, ld_f = bt.ld_f;
     const int slices = (Sc + slice - 1) / slice;   // work-groups per truss
     const int b = blockIdx.x / slices, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // the scenarios of this work-group, counted within the range: first <= sl < last
     const int first = (blockIdx.x - b * slices) * slice;
     const int last = min(first + slice, Sc);
     if (first >= last) return;
-    // trimmed to the arrays, so that no table entry and no output lies outside them whatever nJ[b] and nM[b] hold
-    const int joints = min(max(nJ[b], 0), nJ_max), members = min(max(nM[b], 0), nM_max);
-    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
+    const TrussView v = bt.truss(b);
+    const int joints = v.joints, members = v.members, ndof = v.ndof, ndof_max = v.ndof_max;
     trs_lds::Carve carve(sh);
     const Tables t = layout(carve, nJ_max, nM_max, g, WAVES, OWN);
     double* zw = t.z + (size_t)wave * ndof_max;
@@ -66,7 +63,7 @@ __global__ __launch_bounds__(64 * WAVES) void trs_sets_apply_kernel(
     const double inf = __builtin_huge_val(), nan = __builtin_nan("");
     const int hi = lane >> 3, lo = lane & 7;   // lane = 8 hi + lo
 
-    stage(t, tid, 64 * WAVES, b, joints, members, nJ_max, nM_max, xyz, mem, free_index, joint_out, ld_f);
+    stage(t, tid, 64 * WAVES, v);
     for (int l0 = 0; l0 < L; l0 += g) {
         const int lg = min(g, L - l0);   // the cases of this pass: l0 .. l0 + lg - 1
         stage_pass(t, tid, 64 * WAVES, lg, members, nJ_max, nM_max, U + ((size_t)b * L + l0) * ld_f, ld_f);
@@ -259,36 +256,36 @@ __global__ __launch_bounds__(64 * WAVES) void trs_sets_apply_kernel(
     }
 }
 
-int sets_rhs_launch(int B, int C, int nJ_max, int nM_max, const double* xyz, const TrsMembers& mem, const int* free_index,
-                    const int* n_free, const int* nM, const int* cols, double* Z, int ld_f, hipStream_t stream) {
-    if (B > 0 && C > 0 && (!mem.conn || !xyz || !free_index || !n_free || !nM || !cols || !Z))
+int sets_rhs_launch(int B, const TrsBatch& bt, int C, const int* cols, double* Z, hipStream_t stream) {
+    if (B > 0 && C > 0 && (!bt.mem.conn || !bt.xyz || !bt.free_index || !bt.n_free || !bt.nM || !cols || !Z))
         return (int)hipErrorInvalidValue;   // (without `cols` the kernel would take the members 0 .. C - 1)
-    return rhs_launch(B, 0, cols, C, nJ_max, nM_max, xyz, mem, free_index, n_free, nM, Z, ld_f, stream);
+    return rhs_launch(B, bt, 0, cols, C, Z, stream);
 }
 
-int sets_apply_launch(int B, int L, int S, int s0, int Sc, int C, int nJ_max, int nM_max, const double* xyz,
-                      const TrsMembers& mem, const int* free_index, const int* nJ, const int* nM, const int* cols,
-                      const int* slot, const double* gamma, const double* Z, const double* U, int ld_f, double r_tol,
-                      double* pivot, int* unstable, int* first_unstable, double* peak_stress, int* peak_member,
-                      double* peak_displace, int* peak_joint, double* N_after, double* u_after, const int* joint_out,
-                      hipStream_t stream) {
-    if (B < 0 || L < 0 || S < 0 || s0 < 0 || Sc < 0 || C < 0 || nJ_max < 0 || nM_max < 0 || ld_f < 0)
+int sets_apply_launch(int B, const TrsBatch& bt, int L, int S, int s0, int Sc, int C, const int* cols, const int* slot,
+                      const double* gamma, const double* Z, const double* U, double r_tol, double* pivot, int* unstable,
+                      int* first_unstable, double* peak_stress, int* peak_member, double* peak_displace, int* peak_joint,
+                      double* N_after, double* u_after, hipStream_t stream) {
+    const int nJ_max = bt.nJ_max, nM_max = bt.nM_max;
+    const TrsMembers& mem = bt.mem;
+    if (B < 0 || L < 0 || S < 0 || s0 < 0 || Sc < 0 || C < 0 || nJ_max < 0 || nM_max < 0 || bt.ld_f < 0)
         return (int)hipErrorInvalidValue;
     if ((long long)s0 + Sc > S) return (int)hipErrorInvalidValue;   // (the outputs hold S scenarios)
     if (B == 0 || L == 0 || Sc == 0) return 0;
     if (nJ_max == 0 && nM_max > 0) return (int)hipErrorInvalidValue;   // (members without joints to end at)
     if (!trs_sets_fits(nJ_max, nM_max, L)) return (int)hipErrorInvalidValue;
-    if (!mem.conn || (mem.tidx == nullptr && (!mem.E || !mem.A)) || !xyz || !free_index || !nJ || !nM || !slot || !U || !pivot || !unstable || !first_unstable || !peak_stress ||
-        !peak_member || !peak_displace || !peak_joint || (C > 0 && (!cols || !Z)))
+    if (!mem.conn || (mem.tidx == nullptr && (!mem.E || !mem.A)) || !bt.xyz || !bt.free_index || !bt.nJ || !bt.nM ||
+        !slot || !U || !pivot || !unstable || !first_unstable || !peak_stress || !peak_member || !peak_displace ||
+        !peak_joint || (C > 0 && (!cols || !Z)))
         return (int)hipErrorInvalidValue;
     const int g = pass(nJ_max, nM_max, L, WAVES, OWN);
     if (g <= 0) return (int)hipErrorInvalidValue;   // (the kernel's pass loop steps by g)
     trs_lds::raise_lds_once<trs_sets_apply_kernel>();
     const int slices = (Sc + TRS_SETS_SLICE - 1) / TRS_SETS_SLICE;
     hipLaunchKernelGGL(trs_sets_apply_kernel, dim3((unsigned)slices * (unsigned)B), dim3(64 * WAVES),
-                       lds(nJ_max, nM_max, g, WAVES, OWN), stream, L, g, S, s0, Sc, C, TRS_SETS_SLICE, xyz, mem, free_index, nJ,
-                       nM, nJ_max, nM_max, cols, slot, gamma, Z, U, ld_f, r_tol, pivot, unstable, first_unstable,
-                       peak_stress, peak_member, peak_displace, peak_joint, N_after, u_after, joint_out);
+                       lds(nJ_max, nM_max, g, WAVES, OWN), stream, bt, L, g, S, s0, Sc, C, TRS_SETS_SLICE, cols, slot, gamma,
+                       Z, U, r_tol, pivot, unstable, first_unstable, peak_stress, peak_member, peak_displace, peak_joint,
+                       N_after, u_after);
     return (int)hipGetLastError();
 }
 
@@ -305,16 +302,18 @@ int trs_sets_fits(int nJ_max, int nM_max, int L) {
 int trs_sets_rhs(int B, int C, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* E,
                  const double* A, const int32_t* free_index, const int32_t* n_free, const int32_t* nM,
                  const int32_t* cols, double* Z, int ld_f, void* stream) {
-    return sets_rhs_launch(B, C, nJ_max, nM_max, xyz, trs_members_general(conn, E, A), free_index, n_free, nM, cols, Z,
-                           ld_f, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_general(conn, E, A), free_index, n_free, nullptr, nM,
+                                  nullptr, ld_f);
+    return sets_rhs_launch(B, bt, C, cols, Z, (hipStream_t)stream);
 }
 
 int trs_sets_tab_rhs(int B, int C, int nJ_max, int nM_max, const double* xyz, const uint16_t* conn16,
                      const uint8_t* type_idx, const double* types, const int32_t* free_index, const int32_t* n_free,
                      const int32_t* nM, const int32_t* cols, double* Z, int ld_f, void* stream) {
     if (B > 0 && (!conn16 || !type_idx || !types)) return (int)hipErrorInvalidValue;
-    return sets_rhs_launch(B, C, nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), free_index, n_free, nM,
-                           cols, Z, ld_f, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), free_index, n_free,
+                                  nullptr, nM, nullptr, ld_f);
+    return sets_rhs_launch(B, bt, C, cols, Z, (hipStream_t)stream);
 }
 
 int trs_sets_apply(int B, int L, int S, int s0, int Sc, int C, int nJ_max, int nM_max, const double* xyz,
@@ -323,9 +322,10 @@ int trs_sets_apply(int B, int L, int S, int s0, int Sc, int C, int nJ_max, int n
                    const double* U, int ld_f, double r_tol, double* pivot, int32_t* unstable, int32_t* first_unstable,
                    double* peak_stress, int32_t* peak_member, double* peak_displace, int32_t* peak_joint,
                    double* N_after, double* u_after, const int32_t* joint_out, void* stream) {
-    return sets_apply_launch(B, L, S, s0, Sc, C, nJ_max, nM_max, xyz, trs_members_general(conn, E, A), free_index, nJ, nM,
-                             cols, slot, gamma, Z, U, ld_f, r_tol, pivot, unstable, first_unstable, peak_stress,
-                             peak_member, peak_displace, peak_joint, N_after, u_after, joint_out, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_general(conn, E, A), free_index, nullptr, nJ, nM,
+                                  joint_out, ld_f);
+    return sets_apply_launch(B, bt, L, S, s0, Sc, C, cols, slot, gamma, Z, U, r_tol, pivot, unstable, first_unstable,
+                             peak_stress, peak_member, peak_displace, peak_joint, N_after, u_after, (hipStream_t)stream);
 }
 
 int trs_sets_tab_apply(int B, int L, int S, int s0, int Sc, int C, int nJ_max, int nM_max, const double* xyz,
@@ -336,10 +336,10 @@ int trs_sets_tab_apply(int B, int L, int S, int s0, int Sc, int C, int nJ_max, i
                        double* peak_displace, int32_t* peak_joint, double* N_after, double* u_after,
                        const int32_t* joint_out, void* stream) {
     if (B > 0 && (!conn16 || !type_idx || !types)) return (int)hipErrorInvalidValue;
-    return sets_apply_launch(B, L, S, s0, Sc, C, nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types),
-                             free_index, nJ, nM, cols, slot, gamma, Z, U, ld_f, r_tol, pivot, unstable, first_unstable,
-                             peak_stress, peak_member, peak_displace, peak_joint, N_after, u_after, joint_out,
-                             (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), free_index, nullptr, nJ,
+                                  nM, joint_out, ld_f);
+    return sets_apply_launch(B, bt, L, S, s0, Sc, C, cols, slot, gamma, Z, U, r_tol, pivot, unstable, first_unstable,
+                             peak_stress, peak_member, peak_displace, peak_joint, N_after, u_after, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -94,8 +94,7 @@ __device__ __forceinline__ double spectrum_at(const double* __restrict__ T, cons
 }
 
 __global__ __launch_bounds__(256) void trs_rs_modal_kernel(
-    const int* __restrict__ free_index, const int* __restrict__ n_free, const int* __restrict__ nJ, const int nJ_max,
-    const double* __restrict__ X_all, const int ld_f, const double* __restrict__ lam_all,
+    const TrsBatch bt, const double* __restrict__ X_all, const double* __restrict__ lam_all,
     const double* __restrict__ Mf_all, const int* __restrict__ n_mass, const int p, const int G,
     const double* __restrict__ dirs, const int K, const double* __restrict__ T, const double* __restrict__ Sa,
     const double* __restrict__ zpa, const double zeta, const int rule, const int missing, double* __restrict__ gamma,
@@ -109,11 +108,9 @@ __global__ __launch_bounds__(256) void trs_rs_modal_kernel(
     __shared__ double om[MODES];              // omega, 0 for a mode that contributes nothing
     __shared__ double rh[MODES * MODES];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int joints = min(max(nJ[b], 0), nJ_max);
-    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
-    const int nfree = min(max(n_free[b], 0), ld_f);
+    const TrussView v = bt.truss(b);
+    const int ld_f = bt.ld_f, ndof = v.ndof;
     const int n_modes = min(p, max(n_mass[b], 0));
-    const int* fi = free_index + (size_t)b * ndof_max;
     const double* Xb = X_all + (size_t)b * TRS_RS_BLOCK * ld_f;
     const double* Mf = Mf_all + (size_t)b * ld_f;
     const double* lam = lam_all + (size_t)b * TRS_RS_BLOCK;
@@ -142,8 +139,8 @@ __global__ __launch_bounds__(256) void trs_rs_modal_kernel(
         for (int k = 0; k < MODES; ++k) acc[g][k] = 0.0;
     }
     for (int d = tid; d < ndof; d += 256) {
-        const int row = fi[d], axis = d % 3;
-        if ((row < 0) | (row >= nfree)) continue;
+        const int row = v.row_of(d), axis = d % 3;
+        if (row < 0) continue;
         const double m = Mf[row];
         double x[MODES];
 #pragma unroll
@@ -238,8 +235,8 @@ __global__ __launch_bounds__(256) void trs_rs_modal_kernel(
         __threadfence_block();
         __syncthreads();   // (the zeros of another thread lie under this thread's entries)
         for (int d = tid; d < ndof; d += 256) {
-            const int row = fi[d], axis = d % 3;
-            if ((row < 0) | (row >= nfree)) continue;
+            const int row = v.row_of(d), axis = d % 3;
+            if (row < 0) continue;
             const double m = Mf[row];
             double x[MODES];
 #pragma unroll
@@ -263,24 +260,20 @@ struct RsMember {
     int2 c;       // end joints, clamped
     bool live;    // inside the truss and of positive length
 };
-__device__ __forceinline__ RsMember load_member(const TrsMembers& mem, const size_t mbase, const int m, const int members,
-                                                const double* __restrict__ Xyz, const int nJ_max, const int joints) {
+__device__ __forceinline__ RsMember load_member(const TrussView& v, const int m) {
     RsMember r;
-    r.live = m < members;
+    r.live = m < v.members;
     r.c = int2{0, 0};
     r.ea = 0.0;
     r.g.len = 0.0;
     r.g.c[0] = r.g.c[1] = r.g.c[2] = 0.0;
     if (r.live) {
-        int2 c = mem.ends(mbase + m);
-        // an end outside the truss is on no end list (InTruss): the member then gives zeros to N as it does to R
-        const bool inside = (c.x >= 0) & (c.x < joints) & (c.y >= 0) & (c.y < joints);
-        c.x = min(max(c.x, 0), nJ_max - 1);   // (a joint id outside the arrays would index LDS outside them)
-        c.y = min(max(c.y, 0), nJ_max - 1);
-        r.c = c;
-        r.g = member_geom(Xyz, c.x, c.y);
-        r.ea = mem.EA(mbase + m);
-        r.live = inside & (r.g.len > 0.0);
+        // an end outside the truss is on no end list: the member then gives zeros to N as it does to R
+        const TrussView::Ends e = v.ends(m);
+        r.c = e.c;
+        r.g = member_geom(v.X, e.c.x, e.c.y);
+        r.ea = v.mem.EA(v.mbase + m);
+        r.live = e.inside & (r.g.len > 0.0);
     }
     return r;
 }
@@ -308,36 +301,22 @@ __device__ __forceinline__ void member_modal(const RsTables& t, const RsMember& 
 }
 
 __global__ __launch_bounds__(256) void trs_rs_combine_kernel(
-    const double* __restrict__ xyz, const TrsMembers mem, const int* __restrict__ free_index,
-    const int* __restrict__ n_free, const int* __restrict__ nJ, const int* __restrict__ nM,
-    const int* __restrict__ joint_out, const int nJ_max, const int nM_max, const double* __restrict__ X_all,
-    const int ld_f, const int* __restrict__ n_mass, const int p, const int G, const double* __restrict__ q_all,
-    const double* __restrict__ rho_all, const int rule, const int missing_in, const double* __restrict__ F_all,
-    double* __restrict__ u, double* __restrict__ R, double* __restrict__ N, double* __restrict__ modal_u,
-    double* __restrict__ modal_R, double* __restrict__ modal_N) {
+    const TrsBatch bt, const double* __restrict__ X_all, const int* __restrict__ n_mass, const int p, const int G,
+    const double* __restrict__ q_all, const double* __restrict__ rho_all, const int rule, const int missing_in,
+    const double* __restrict__ F_all, double* __restrict__ u, double* __restrict__ R, double* __restrict__ N,
+    double* __restrict__ modal_u, double* __restrict__ modal_R, double* __restrict__ modal_N) {
     extern __shared__ double sh[];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int joints = min(max(nJ[b], 0), nJ_max);
-    const int members = nJ_max > 0 ? min(max(nM[b], 0), nM_max) : 0;   // (without a joint there is no end to clamp to)
-    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
-    const int nfree = min(max(n_free[b], 0), ld_f);
+    const TrussView v = bt.truss(b);
+    const int nJ_max = bt.nJ_max, nM_max = bt.nM_max, ld_f = bt.ld_f, joints = v.joints, ndof_max = v.ndof_max;
     const int n_modes = min(p, max(n_mass[b], 0));
     const bool missing = missing_in != 0;
     const int nvec = p + (missing ? G : 0), V = p + 1;
     trs_lds::Carve lds(sh);
     const RsTables t = layout(lds, nJ_max, nM_max, nvec);
-    const int* fi = free_index + (size_t)b * ndof_max;
-    const double* Xyz = xyz + (size_t)b * ndof_max;
-    const size_t mbase = (size_t)b * nM_max;
-    const int* jo = joint_out != nullptr ? joint_out + (size_t)b * nJ_max : nullptr;
     const double* Xb = X_all + (size_t)b * TRS_RS_BLOCK * ld_f;
     const double* Fb = missing ? F_all + (size_t)b * TRS_RS_BLOCK * ld_f : nullptr;
     const bool want_R = (R != nullptr) | (modal_R != nullptr);
-    // where joint j's results go: an id outside the arrays falls back to j
-    auto place = [&](int j) {
-        const int id = jo != nullptr ? jo[j] : j;
-        return ((id >= 0) & (id < nJ_max)) ? id : j;
-    };
 
     // the modes that contribute (rho_kk != 0): a column of X whose lam is not positive and finite is never read
     unsigned live = 0;
@@ -347,14 +326,14 @@ __global__ __launch_bounds__(256) void trs_rs_combine_kernel(
 
     // ---- stage: every response vector in joint layout, zero at held DOFs and past the truss's own joints
     for (int x = tid; x < nvec * ndof_max; x += 256) {
-        const int v = x / ndof_max, d = x - v * ndof_max;
-        const int row = d < ndof ? fi[d] : -1;
+        const int k = x / ndof_max, d = x - k * ndof_max;
+        const int row = v.row_of(d);
         double val = 0.0;
-        if ((row >= 0) & (row < nfree)) {
-            if (v >= p)
-                val = Fb[(size_t)(v - p) * ld_f + row];
-            else if ((live >> v) & 1u)
-                val = Xb[(size_t)v * ld_f + row];
+        if (row >= 0) {
+            if (k >= p)
+                val = Fb[(size_t)(k - p) * ld_f + row];
+            else if ((live >> k) & 1u)
+                val = Xb[(size_t)k * ld_f + row];
         }
         t.vec[x] = val;
     }
@@ -363,13 +342,13 @@ __global__ __launch_bounds__(256) void trs_rs_combine_kernel(
         const int g = tid / MODES, k = tid % MODES;
         t.q[tid] = ((g < G) & (((live >> k) & 1u) != 0)) ? q_all[((size_t)b * G + g) * p + k] : 0.0;
     }
-    if (want_R) build_end_lists(t, mem, mbase, joints, members, nJ_max, tid, InTruss{joints});
+    if (want_R) build_end_lists(t, v, tid);
     __syncthreads();
 
     // ---- members: N and modal_N, every member once
     if ((N != nullptr) | (modal_N != nullptr))
         for (int m = tid; m < nM_max; m += 256) {
-            const RsMember mb = load_member(mem, mbase, m, members, Xyz, nJ_max, joints);
+            const RsMember mb = load_member(v, m);
             double ax[MODES];
             member_axials(t, mb, ndof_max, p, ax);   // (once: the directions share them)
             for (int g = 0; g < G; ++g) {
@@ -390,15 +369,10 @@ __global__ __launch_bounds__(256) void trs_rs_combine_kernel(
     if ((u != nullptr) | (modal_u != nullptr) | want_R)
         for (int j = tid; j < nJ_max; j += 256) {
             const bool own = j < joints;
-            const int o = place(j);
-            bool held[3] = {false, false, false};
-            if (own) {
+            const int o = v.place(j);
+            bool held[3];
 #pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    const int row = fi[3 * j + a];
-                    held[a] = (row < 0) | (row >= nfree);
-                }
-            }
+            for (int a = 0; a < 3; ++a) held[a] = own & v.held(j, a);
             const bool any_held = held[0] | held[1] | held[2];
             for (int g = 0; g < G; ++g) {
                 const size_t row = (size_t)b * G + g;
@@ -427,7 +401,7 @@ __global__ __launch_bounds__(256) void trs_rs_combine_kernel(
                     const int deg = any_held ? t.cnt[j] : 0;
                     for (int i = 0; i < deg; ++i) {
                         const int m = list[i] >> 1, end = list[i] & 1;
-                        const RsMember mb = load_member(mem, mbase, m, members, Xyz, nJ_max, joints);
+                        const RsMember mb = load_member(v, m);
                         double ax[MODES], r[VEC];
                         member_axials(t, mb, ndof_max, p, ax);
                         member_modal(t, mb, ax, ndof_max, p, g, missing, r);
@@ -458,21 +432,18 @@ bool rs_args_ok(int p, int G, int rule) {
     return p >= 1 && p <= TRS_RS_MAX_MODES && G >= 1 && G <= TRS_RS_MAX_DIRS && rule >= TRS_RS_SRSS && rule <= TRS_RS_ABS;
 }
 
-int rs_combine_launch(int B, int nJ_max, int nM_max, const double* xyz, const TrsMembers& mem, const int* free_index,
-                      const int* n_free, const int* nJ, const int* nM, const int* joint_out, const double* X, int ld_f,
-                      const int* n_mass, int p, int G, const double* q, const double* rho, int rule, int missing,
-                      const double* F, double* u, double* R, double* N, double* modal_u, double* modal_R, double* modal_N,
-                      hipStream_t stream) {
+int rs_combine_launch(int B, const TrsBatch& bt, const double* X, const int* n_mass, int p, int G, const double* q,
+                      const double* rho, int rule, int missing, const double* F, double* u, double* R, double* N,
+                      double* modal_u, double* modal_R, double* modal_N, hipStream_t stream) {
     if (B <= 0) return 0;
-    if (!rs_args_ok(p, G, rule) || !trs_rs_fits(nJ_max, nM_max, p) || ld_f < 1 || X == nullptr || n_mass == nullptr ||
-        q == nullptr || rho == nullptr || (missing && F == nullptr))
+    if (!rs_args_ok(p, G, rule) || !trs_rs_fits(bt.nJ_max, bt.nM_max, p) || bt.ld_f < 1 || X == nullptr ||
+        n_mass == nullptr || q == nullptr || rho == nullptr || (missing && F == nullptr))
         return (int)hipErrorInvalidValue;
     if (u == nullptr && R == nullptr && N == nullptr && modal_u == nullptr && modal_R == nullptr && modal_N == nullptr)
         return 0;
     trs_lds::raise_lds_once<trs_rs_combine_kernel>();
-    hipLaunchKernelGGL(trs_rs_combine_kernel, dim3(B), dim3(256), rs_lds(nJ_max, nM_max, p + (missing ? G : 0)), stream,
-                       xyz, mem, free_index, n_free, nJ, nM, joint_out, nJ_max, nM_max, X, ld_f, n_mass, p, G, q, rho, rule,
-                       missing, F, u, R, N, modal_u, modal_R, modal_N);
+    hipLaunchKernelGGL(trs_rs_combine_kernel, dim3(B), dim3(256), rs_lds(bt.nJ_max, bt.nM_max, p + (missing ? G : 0)),
+                       stream, bt, X, n_mass, p, G, q, rho, rule, missing, F, u, R, N, modal_u, modal_R, modal_N);
     return (int)hipGetLastError();
 }
 
@@ -498,9 +469,9 @@ int trs_rs_modal(int B, int nJ_max, const int32_t* free_index, const int32_t* n_
         q == nullptr || rho == nullptr || (rule == TRS_RS_CQC && !(zeta > 0.0)) ||
         (missing_mass && (F == nullptr || zpa == nullptr)))
         return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(trs_rs_modal_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, free_index, n_free, nJ, nJ_max, X,
-                       ld_f, lam, Mf, n_mass, p, G, dirs, K, T, Sa, zpa, zeta, rule, missing_mass, gamma, sa, meff, mtot,
-                       base, q, rho, F);
+    hipLaunchKernelGGL(trs_rs_modal_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream,
+                       trs_batch_dofs(nJ_max, free_index, n_free, nJ, nullptr, ld_f), X, lam, Mf, n_mass, p, G, dirs, K, T,
+                       Sa, zpa, zeta, rule, missing_mass, gamma, sa, meff, mtot, base, q, rho, F);
     return (int)hipGetLastError();
 }
 
@@ -509,9 +480,10 @@ int trs_rs_combine(int B, int nJ_max, int nM_max, const double* xyz, const int32
                    const int32_t* joint_out, const double* X, int ld_f, const int32_t* n_mass, int p, int G,
                    const double* q, const double* rho, int rule, int missing_mass, const double* F, double* u, double* R,
                    double* N, double* modal_u, double* modal_R, double* modal_N, void* stream) {
-    const TrsMembers mem = trs_members_general(conn, E, A);
-    return rs_combine_launch(B, nJ_max, nM_max, xyz, mem, free_index, n_free, nJ, nM, joint_out, X, ld_f, n_mass, p, G, q,
-                             rho, rule, missing_mass, F, u, R, N, modal_u, modal_R, modal_N, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_general(conn, E, A), free_index, n_free, nJ, nM,
+                                  joint_out, ld_f);
+    return rs_combine_launch(B, bt, X, n_mass, p, G, q, rho, rule, missing_mass, F, u, R, N, modal_u, modal_R, modal_N,
+                             (hipStream_t)stream);
 }
 
 int trs_rs_combine_tab(int B, int nJ_max, int nM_max, const double* xyz, const uint16_t* conn16, const uint8_t* type_idx,
@@ -519,9 +491,10 @@ int trs_rs_combine_tab(int B, int nJ_max, int nM_max, const double* xyz, const u
                        const int32_t* nM, const int32_t* joint_out, const double* X, int ld_f, const int32_t* n_mass, int p,
                        int G, const double* q, const double* rho, int rule, int missing_mass, const double* F, double* u,
                        double* R, double* N, double* modal_u, double* modal_R, double* modal_N, void* stream) {
-    const TrsMembers mem = trs_members_table(conn16, type_idx, types);
-    return rs_combine_launch(B, nJ_max, nM_max, xyz, mem, free_index, n_free, nJ, nM, joint_out, X, ld_f, n_mass, p, G, q,
-                             rho, rule, missing_mass, F, u, R, N, modal_u, modal_R, modal_N, (hipStream_t)stream);
+    const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_table(conn16, type_idx, types), free_index, n_free, nJ,
+                                  nM, joint_out, ld_f);
+    return rs_combine_launch(B, bt, X, n_mass, p, G, q, rho, rule, missing_mass, F, u, R, N, modal_u, modal_R, modal_N,
+                             (hipStream_t)stream);
 }
 
 }  // extern "C"

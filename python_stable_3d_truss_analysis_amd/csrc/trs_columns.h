@@ -5,9 +5,9 @@
 //   - for the two apply kernels that run one work-group per (truss, slice) over staged tables (trs_loss_apply,
 //     trs_sets_apply): the tables and their layout in LDS (trs_lds.h), which is the rule behind trs_loss_fits /
 //     trs_sets_fits, the passes and the launch; the stage; and c_m . (v[j1] - v[j0]), the ONE expression behind N, q_m, r_e and a set's pivots.
-// The stage trims nJ[b] and nM[b] to the arrays, clamps end-joint ids, fills the DOF map and the joint order for all
-// nJ_max joints (-1 = held past the truss's own) and zeroes the waves' vectors: whatever the inputs hold, nothing is
-// read or written outside the arrays, and entries past the truss's joints read as zero.
+// The stage works on a truss view (trs_view.h: counts trimmed to the arrays, end-joint ids clamped), fills the DOF map and
+// the joint order for all nJ_max joints (-1 = held past the truss's own) and zeroes the waves' vectors: whatever the
+// inputs hold, nothing is read or written outside the arrays, and entries past the truss's joints read as zero.
 #pragma once
 #include "trs_common.h"
 #include "trs_lds.h"
@@ -22,22 +22,20 @@ namespace trs_col {
 constexpr int MAX_PASS = 8;   // load cases per pass at most (loss: their maxima live in registers; sets: lane 8 l + i
                               // substitutes case l)
 
-// Row `row` of Z, by one wave: b_e,f of member `member` (= b * nM_max + e) when `real`, else zeros - +c at the free
-// DOFs of j1 and -c at those of j0 through fi (the truss's free_index), zeros in the other columns below npad.  One
-// lane writes each entry.
+// Row `row` of Z, by one wave: b_e,f of member e of the truss when `real`, else zeros - +c at the free DOFs of j1 and
+// -c at those of j0, zeros in the other columns below npad.  One lane writes each entry.
 __device__ __forceinline__ void write_row(double* __restrict__ row, const int npad, const int lane, const bool real,
-                                          const size_t member, const TrsMembers& mem, const double* __restrict__ X,
-                                          const int* __restrict__ fi) {
+                                          const int e, const TrussView& v) {
     int at[6] = {-1, -1, -1, -1, -1, -1};
     double val[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (real) {
-        const int2 c = mem.ends(member);
-        const trs_rec::MemberGeom g = trs_rec::member_geom(X, c.x, c.y);
+        const int2 c = v.ends(e).c;
+        const trs_rec::MemberGeom g = trs_rec::member_geom(v.X, c.x, c.y);
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-            at[a] = fi[3 * c.y + a];
+            at[a] = v.row_of(3 * c.y + a);
             val[a] = g.c[a];
-            at[3 + a] = fi[3 * c.x + a];
+            at[3 + a] = v.row_of(3 * c.x + a);
             val[3 + a] = -g.c[a];
         }
     }
@@ -51,9 +49,8 @@ __device__ __forceinline__ void write_row(double* __restrict__ row, const int np
 }
 
 // The launcher of the rhs kernel (defined in loss.hip): row i of Z [B][C][ld_f] is b_e,f of e = cols[b][i] when `cols`
-// is given, else of e = e0 + i; zeros for an e outside [0, nM[b]).
-int rhs_launch(int B, int e0, const int* cols, int C, int nJ_max, int nM_max, const double* xyz, const TrsMembers& mem,
-               const int* free_index, const int* n_free, const int* nM, double* Z, int ld_f, hipStream_t stream);
+// is given, else of e = e0 + i; zeros for an e outside [0, nM[b]).  (The batch carries no nJ: every joint of the arrays.)
+int rhs_launch(int B, const TrsBatch& bt, int e0, const int* cols, int C, double* Z, hipStream_t stream);
 
 // (value, index) extreme over the wave: the larger (MAX) or the smaller value, the lower index among equal values
 template <bool MAX>
@@ -139,39 +136,23 @@ __device__ __forceinline__ double along(const Tables& t, const int m, const doub
     return along(t, m, v[3 * c.y] - v[3 * c.x], v[3 * c.y + 1] - v[3 * c.x + 1], v[3 * c.y + 2] - v[3 * c.x + 2]);
 }
 
-// Once per work-group of `threads` threads (waves = threads / 64), for truss b of `joints` joints and `members`
-// members, both already trimmed to the arrays: the member table, the DOF map, the joint order, zeroed wave vectors.
-// The first stage_pass synchronises.
-__device__ __forceinline__ void stage(const Tables& t, const int tid, const int threads, const int b, const int joints,
-                                      const int members, const int nJ_max, const int nM_max,
-                                      const double* __restrict__ xyz, const TrsMembers& mem,
-                                      const int* __restrict__ free_index, const int* __restrict__ joint_out,
-                                      const int ld_f) {
-    const int ndof = 3 * joints, ndof_max = 3 * nJ_max;
-    const size_t mbase = (size_t)b * nM_max;
-    const double* X = xyz + (size_t)b * ndof_max;
-    for (int m = tid; m < members; m += threads) {
-        int2 c = mem.ends(mbase + m);
-        c.x = min(max(c.x, 0), nJ_max - 1);   // (a joint id outside the arrays would index LDS outside them)
-        c.y = min(max(c.y, 0), nJ_max - 1);
-        const trs_rec::MemberGeom mg = trs_rec::member_geom(X, c.x, c.y);
+// Once per work-group of `threads` threads (waves = threads / 64), for the truss v: the member table, the DOF map, the
+// joint order, zeroed wave vectors.  The first stage_pass synchronises.
+__device__ __forceinline__ void stage(const Tables& t, const int tid, const int threads, const TrussView& v) {
+    for (int m = tid; m < v.members; m += threads) {
+        const int2 c = v.ends(m).c;
+        const trs_rec::MemberGeom mg = trs_rec::member_geom(v.X, c.x, c.y);
         t.ends[m] = c;
         t.cx[m] = mg.c[0];
         t.cy[m] = mg.c[1];
         t.cz[m] = mg.c[2];
-        t.k[m] = mem.EA(mbase + m) / mg.len;
-        t.ia[m] = 1.0 / mem.area(mbase + m);
+        t.k[m] = v.mem.EA(v.mbase + m) / mg.len;
+        t.ia[m] = 1.0 / v.mem.area(v.mbase + m);
     }
     // staged for every joint of the arrays, -1 (held) past the truss's own: an end joint trimmed to there reads zeros
-    for (int d = tid; d < ndof_max; d += threads) {
-        const int row = free_index[(size_t)b * ndof_max + d];
-        t.fi[d] = d < ndof && row < ld_f ? row : -1;
-    }
-    for (int j = tid; j < nJ_max; j += threads) {
-        const int id = joint_out != nullptr ? joint_out[(size_t)b * nJ_max + j] : j;
-        t.jo[j] = id >= 0 && id < nJ_max ? id : j;
-    }
-    for (int d = tid; d < threads / 64 * ndof_max; d += threads) t.z[d] = 0.0;   // (entries past ndof stay zero)
+    for (int d = tid; d < v.ndof_max; d += threads) t.fi[d] = v.row_of(d);
+    for (int j = tid; j < v.nJ_max; j += threads) t.jo[j] = v.place(j);
+    for (int d = tid; d < threads / 64 * v.ndof_max; d += threads) t.z[d] = 0.0;   // (entries past ndof stay zero)
 }
 
 // Per pass: u of the lg cases from Ul (the first case's row of U [..][ld_f]) in joint layout, and N = k c . (u_j1 - u_j0)

@@ -1,10 +1,11 @@
 // trs_recover.h - the per-member and per-joint arithmetic of the result recovery, shared by trs_recover
 // (recover.hip) and the multi-case recovery trs_recover_cases (cases.hip): both paths call the same functions,
 // so case k of a multi-case recovery rounds exactly like a single recovery of case k.  Also the builder of the
-// per-joint member-end lists in LDS that the analysis kernels sum over (build_end_lists) with its joint predicates
-// (EveryJoint, InTruss) and order_by_neighbour; where the lists lie in a kernel's LDS is its layout's affair (trs_lds.h).
+// per-joint member-end lists in LDS that the analysis kernels sum over (build_end_lists, on a truss view: trs_view.h)
+// and order_by_neighbour; where the lists lie in a kernel's LDS is its layout's affair (trs_lds.h).
 #pragma once
 #include "trs_common.h"
+#include "trs_view.h"
 
 namespace trs_rec {
 
@@ -49,12 +50,9 @@ __device__ __forceinline__ void add_end_force(double (&r)[3], const double (&c)[
     for (int a = 0; a < 3; ++a) r[a] = fma(s, c[a], r[a]);
 }
 
-// Reaction at one constrained joint from its list of member ends ((member << 1) | end): the list is sorted by
-// member id in place (insertion sort: the lists are short) and summed in that order.
+// A list of member ends ((member << 1) | end) sorted by member id in place (insertion sort: the lists are short)
 template <class ListPtr>
-__device__ __forceinline__ void joint_reaction(ListPtr list, const int deg, const TrsMembers& mem,
-                                               const double* __restrict__ X, const size_t mbase, const double* u,
-                                               const int* jo, double (&r)[3]) {
+__device__ __forceinline__ void sort_list(ListPtr list, const int deg) {
     for (int i = 1; i < deg; ++i) {
         const int key = list[i];
         int p = i - 1;
@@ -64,6 +62,15 @@ __device__ __forceinline__ void joint_reaction(ListPtr list, const int deg, cons
         }
         list[p + 1] = key;
     }
+}
+
+// Reaction at one constrained joint from its list of member ends: the list is sorted by member id in place and summed in
+// that order.  The form of trs_recover (recover.hip), whose inputs the solve has checked.
+template <class ListPtr>
+__device__ __forceinline__ void joint_reaction(ListPtr list, const int deg, const TrsMembers& mem,
+                                               const double* __restrict__ X, const size_t mbase, const double* u,
+                                               const int* jo, double (&r)[3]) {
+    sort_list(list, deg);
     r[0] = r[1] = r[2] = 0.0;
     for (int i = 0; i < deg; ++i) {
         const int m = list[i] >> 1, end = list[i] & 1;
@@ -71,6 +78,19 @@ __device__ __forceinline__ void joint_reaction(ListPtr list, const int deg, cons
         const MemberGeom g = member_geom(X, c.x, c.y);
         const double axial = member_axial(g, mem.EA(mbase + m), u, jo ? jo[c.x] : c.x, jo ? jo[c.y] : c.y);
         add_end_force(r, g.c, axial, end);
+    }
+}
+// The same on a truss view, u in the device's joint numbering: the ends come clamped.
+template <class ListPtr>
+__device__ __forceinline__ void joint_reaction(ListPtr list, const int deg, const TrussView& v, const double* u,
+                                               double (&r)[3]) {
+    sort_list(list, deg);
+    r[0] = r[1] = r[2] = 0.0;
+    for (int i = 0; i < deg; ++i) {
+        const int m = list[i] >> 1, end = list[i] & 1;
+        const int2 c = v.ends(m).c;
+        const MemberGeom g = member_geom(v.X, c.x, c.y);
+        add_end_force(r, g.c, member_axial(g, v.mem.EA(v.mbase + m), u, c.x, c.y), end);
     }
 }
 
@@ -85,41 +105,36 @@ struct EndLists {
 struct EveryJoint {
     __device__ __forceinline__ bool operator()(int) const { return true; }
 };
-// the joints of the truss: an end joint outside them gets no list (it would index LDS outside the lists) and no sum
-struct InTruss {
-    int joints;
-    __device__ __forceinline__ bool operator()(int j) const { return (j >= 0) & (j < joints); }
-};
 
-// Builds the lists of the joints that `keep(j)` admits (the others get empty lists), by a work-group of 256 threads:
+// Builds the lists of the truss's joints that `keep(j)` admits (the others get empty lists; an end joint outside the
+// truss gets no list - it would index LDS outside the lists - and no sum), by a work-group of 256 threads:
 // count with integer atomics, scan, fill, then every list is sorted by member id - the order in which every kernel
-// sums over a list, whatever order the atomics filled it in.  The ONE builder of trs_recover_cases (cases.hip: the
-// constrained joints), the adjoint kernels (adjoint.hip) and the effect kernels (effects.hip).  There is no barrier
-// after the sort: the caller places one before a thread reads a list that it did not sort itself.
+// sums over a list, whatever order the atomics filled it in.  The ONE builder of every analysis kernel (trs_recover_cases
+// keeps the constrained joints only).  There is no barrier after the sort: the caller places one before a thread reads a
+// list that it did not sort itself.
 template <class Keep = EveryJoint>
-__device__ __forceinline__ void build_end_lists(const EndLists& t, const TrsMembers& mem, const size_t mbase,
-                                                const int joints, const int members, const int nJ_max, const int tid,
-                                                Keep keep = Keep()) {
-    for (int j = tid; j < nJ_max; j += 256) t.cnt[j] = 0;
+__device__ __forceinline__ void build_end_lists(const EndLists& t, const TrussView& v, const int tid, Keep keep = Keep()) {
+    const int joints = v.joints, members = v.members;
+    for (int j = tid; j < v.nJ_max; j += 256) t.cnt[j] = 0;
     __syncthreads();
     for (int m = tid; m < members; m += 256) {
-        const int2 c = mem.ends(mbase + m);
-        if (keep(c.x)) atomicAdd(&t.cnt[c.x], 1);
-        if (keep(c.y)) atomicAdd(&t.cnt[c.y], 1);
+        const int2 c = v.raw_ends(m);
+        if (v.in_truss(c.x) && keep(c.x)) atomicAdd(&t.cnt[c.x], 1);
+        if (v.in_truss(c.y) && keep(c.y)) atomicAdd(&t.cnt[c.y], 1);
     }
     __syncthreads();
     if (tid < 64) {  // exclusive scan of cnt by one wave
         int base = 0;
         for (int j0 = 0; j0 < joints; j0 += 64) {
             const int j = j0 + tid;
-            const int v = j < joints ? t.cnt[j] : 0;
-            int incl = v;
+            const int own = j < joints ? t.cnt[j] : 0;
+            int incl = own;
 #pragma unroll
             for (int off = 1; off < 64; off <<= 1) {
                 const int up = __shfl_up(incl, off);
                 if (tid >= off) incl += up;
             }
-            if (j < joints) t.start[j] = base + incl - v;
+            if (j < joints) t.start[j] = base + incl - own;
             base += __shfl(incl, 63);
         }
     }
@@ -127,24 +142,12 @@ __device__ __forceinline__ void build_end_lists(const EndLists& t, const TrsMemb
     for (int j = tid; j < joints; j += 256) t.cnt[j] = 0;  // the fill cursor
     __syncthreads();
     for (int m = tid; m < members; m += 256) {
-        const int2 c = mem.ends(mbase + m);
-        if (keep(c.x)) t.ends[t.start[c.x] + atomicAdd(&t.cnt[c.x], 1)] = m << 1;
-        if (keep(c.y)) t.ends[t.start[c.y] + atomicAdd(&t.cnt[c.y], 1)] = (m << 1) | 1;
+        const int2 c = v.raw_ends(m);
+        if (v.in_truss(c.x) && keep(c.x)) t.ends[t.start[c.x] + atomicAdd(&t.cnt[c.x], 1)] = m << 1;
+        if (v.in_truss(c.y) && keep(c.y)) t.ends[t.start[c.y] + atomicAdd(&t.cnt[c.y], 1)] = (m << 1) | 1;
     }
     __syncthreads();
-    for (int j = tid; j < joints; j += 256) {
-        int* list = t.ends + t.start[j];
-        const int deg = t.cnt[j];
-        for (int i = 1; i < deg; ++i) {
-            const int key = list[i];
-            int p = i - 1;
-            while (p >= 0 && list[p] > key) {
-                list[p + 1] = list[p];
-                --p;
-            }
-            list[p + 1] = key;
-        }
-    }
+    for (int j = tid; j < joints; j += 256) sort_list(t.ends + t.start[j], t.cnt[j]);
 }
 
 // The far joint of every list entry into `far` (-1: outside the truss), and every list re-sorted by (far joint, member id) -
@@ -153,16 +156,15 @@ __device__ __forceinline__ void build_end_lists(const EndLists& t, const TrsMemb
 // solve does.  What the nonlinear kernels (nonlinear.hip) and the buckling product (buckling.hip) sum over.
 // The sort is stable and the lists arrive in member-id order.  Thread j % 256 owns joint j here as in build_end_lists'
 // own sort, so no barrier is needed between the two; the caller places one before another thread reads a list.
-__device__ __forceinline__ void order_by_neighbour(const EndLists& t, int* far_all, const TrsMembers& mem, const size_t mbase,
-                                                   const int joints, const int tid) {
-    for (int j = tid; j < joints; j += 256) {
+__device__ __forceinline__ void order_by_neighbour(const EndLists& t, int* far_all, const TrussView& v, const int tid) {
+    for (int j = tid; j < v.joints; j += 256) {
         int* list = t.ends + t.start[j];
         int* far = far_all + t.start[j];
         const int deg = t.cnt[j];
         for (int i = 0; i < deg; ++i) {
-            const int2 c = mem.ends(mbase + (list[i] >> 1));
+            const int2 c = v.raw_ends(list[i] >> 1);
             const int o = (list[i] & 1) ? c.x : c.y;
-            far[i] = ((o >= 0) & (o < joints)) ? o : -1;
+            far[i] = v.in_truss(o) ? o : -1;
         }
         for (int i = 1; i < deg; ++i) {
             const int kf = far[i], ke = list[i];

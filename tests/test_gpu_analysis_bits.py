@@ -1,5 +1,5 @@
 """The resident-factor analyses (`solve_load_cases`, `solve_effect_cases`, `solve_gradients`, `solve_modes`,
-`solve_buckling`, `solve_transient`, `solve_nonlinear`, `solve_mode_gradients` and the three on the columns
+`solve_buckling`, `solve_transient`, `solve_nonlinear`, `solve_mode_gradients`, `solve_response_spectrum` and the three on the columns
 inv(K_ff) b_e: `solve_member_loss`, `solve_member_sets`, `solve_influence`) give the SAME BITS as the
 build that recorded `tests/golden/analysis_bits.json`: SHA-256 digests of every field (that is not None) of the result
 dataclasses, for both member forms and with and without a joint order.  The kernels use no floating-point
@@ -29,7 +29,7 @@ L, P = 17, 3   # two case groups of the substitution (16 + 1); three modes
 CONFIGS = {"general": dict(table=False, reorder=False), "general-profile": dict(table=False, reorder="profile"),
            "table": dict(table=True, reorder=False), "table-profile": dict(table=True, reorder="profile")}
 ANALYSES = ("load_cases", "effect_cases", "gradients", "modes", "buckling", "member_loss", "member_sets", "influence",
-            "transient", "nonlinear", "mode_gradients")
+            "transient", "nonlinear", "mode_gradients", "response_spectrum")
 # the transient response: two excitations (the first two load cases as patterns), five Newmark steps, stiffness
 # damping (so the end lists of the members are built), two monitored joints and two monitored members (first and last)
 L_DYN, STEPS, DT, DAMP_STIFF = 2, 5, 1e-3, 1e-4
@@ -42,6 +42,9 @@ NL_FACTORS = (1.0 / 128, 1.0 / 64)
 # leaves a partial last range of members; 40 scenarios are two slices of 32, the second partial; the path is the first
 # twelve joints and back to joint 0
 L_COL, CHUNK, S_SETS, P_PATH = 9, 48, 40, 12
+# the response spectrum: two ground directions (x and y: the 2D trusses have no z) and a five-point table of periods
+RS_DIRS = [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]
+RS_PERIODS = [0.0, 0.02, 0.1, 0.5, 2.0]
 SMALL = 6   # the trusses before bar-942: one bucket, where the results per member pair and per scenario are small
 TRAIN = [(1.0, 0.0), (2.0, 30.0), (1.5, 75.0)]
 
@@ -99,6 +102,12 @@ def moving_load(packed):
     return path, rng.uniform(-1.0, 1.0, size=(packed.B, 3)) * axes
 
 
+def spectrum_table():
+    """The seeded spectral accelerations [2, 5] of `solve_response_spectrum`, from a generator of their own (the inputs
+    of the other analyses stay what they were)."""
+    return np.random.default_rng(23).uniform(0.5, 10.0, size=(len(RS_DIRS), len(RS_PERIODS)))
+
+
 def column_calls(analysis, packed, x):
     """{name: (function name, arguments, keywords)} of a column analysis: "full" on the whole batch with chunk 48 and
     no result per member pair, "small" on the trusses before bar-942 with the default chunk and every optional result."""
@@ -151,6 +160,10 @@ def run(analysis, packed, x, reorder):
         return {"rows": batch.solve_mode_gradients(packed, p=P, joint_mass=x["joint_mass"], reorder=reorder),
                 "weighted": batch.solve_mode_gradients(packed, p=P, weights=x["weights"], joint_mass=x["joint_mass"],
                                                        reorder=reorder)}
+    if analysis == "response_spectrum":
+        return {"spectrum": batch.solve_response_spectrum(packed, RS_DIRS, RS_PERIODS, spectrum_table(), p=P, rule="cqc",
+                                                          missing_mass=True, want_modal=True,
+                                                          joint_mass=x["joint_mass"], reorder=reorder)}
     return {"modes": batch.solve_modes(packed, p=P, joint_mass=x["joint_mass"], reorder=reorder)}
 
 
