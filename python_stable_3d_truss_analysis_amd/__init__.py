@@ -38,7 +38,7 @@ __all__ = ["Truss", "Member", "MemberType", "SupportType", "MetapathType", "Task
            "solve_load_cases", "LoadCaseResult", "load_cases_from_json",
            "solve_gradients", "GradientResult", "DifferentiableTruss",
            "solve_modes", "ModeResult", "solve_mode_gradients", "ModeGradientResult",
-           "solve_response_spectrum", "SpectrumResult",
+           "solve_response_spectrum", "SpectrumResult", "solve_harmonic", "HarmonicResult",
            "solve_effect_cases", "EffectCaseResult", "LoadCase",
            "solve_member_loss", "MemberLossResult", "solve_influence", "InfluenceResult",
            "solve_member_sets", "MemberSetResult", "solve_transient", "TransientResult",
@@ -52,7 +52,8 @@ def __getattr__(name):
                 "solve_effect_cases", "EffectCaseResult", "solve_member_loss", "MemberLossResult", "solve_influence",
                 "InfluenceResult", "solve_member_sets", "MemberSetResult", "solve_transient", "TransientResult",
                 "solve_nonlinear", "NonlinearResult", "solve_buckling", "BucklingResult", "solve_mode_gradients",
-                "ModeGradientResult", "solve_response_spectrum", "SpectrumResult"):
+                "ModeGradientResult", "solve_response_spectrum", "SpectrumResult", "solve_harmonic",
+                "HarmonicResult"):
         from . import batch
         return getattr(batch, name)
     if name == "DifferentiableTruss":

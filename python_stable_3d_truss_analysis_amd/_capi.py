@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h`, `include/trs_influence.h`, `include/trs_sets.h`, `include/trs_dynamics.h`, `include/trs_nonlinear.h`, `include/trs_buckling.h`, `include/trs_modegrad.h` and `include/trs_spectrum.h` (library: `libtrs_hip.so`, in-tree).
+"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h`, `include/trs_influence.h`, `include/trs_sets.h`, `include/trs_dynamics.h`, `include/trs_nonlinear.h`, `include/trs_buckling.h`, `include/trs_modegrad.h`, `include/trs_spectrum.h` and `include/trs_harmonic.h` (library: `libtrs_hip.so`, in-tree).
 
 There is no fallback: if the library is missing, `load()` raises `HipExtensionError`.
 """
@@ -200,6 +200,18 @@ RS_SIGNATURES = {
                                 _P, _P, _P, _P, _P, _P]),
 }
 
+#: every symbol `include/trs_harmonic.h` declares (harmonic response over a frequency sweep from the converged mode
+#: block; csrc/harmonic.hip, the same library)
+HR_SIGNATURES = {
+    "trs_hr_abi_version": (_I, []),
+    "trs_hr_fits": (_I, [_I, _I, _I]),
+    "trs_hr_modal": (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
+    "trs_hr_sweep": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _D, _D, _D,
+                          _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P]),
+    "trs_hr_sweep_tab": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _D, _D,
+                              _D, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P]),
+}
+
 #: must equal TRS_ABI_VERSION of include/trs_solver.h
 ABI_VERSION = 10
 #: must equal TRS_MODES_ABI_VERSION of include/trs_modes.h
@@ -222,6 +234,8 @@ BK_ABI_VERSION = 1
 MG_ABI_VERSION = 1
 #: must equal TRS_RS_ABI_VERSION of include/trs_spectrum.h
 RS_ABI_VERSION = 1
+#: must equal TRS_HR_ABI_VERSION of include/trs_harmonic.h
+HR_ABI_VERSION = 1
 #: TRS_RS_SRSS, TRS_RS_CQC, TRS_RS_ABS of include/trs_spectrum.h: the modal combination rules
 RS_RULES = {"srss": 0, "cqc": 1, "abs": 2}
 #: TRS_NL_* of include/trs_nonlinear.h: the status of a truss in a load step of the nonlinear analysis
@@ -274,7 +288,8 @@ def load():
     except OSError as exc:
         raise HipExtensionError(f"cannot load {LIB_PATH}: {exc}") from exc
     for table in (SIGNATURES, MODES_SIGNATURES, EFFECTS_SIGNATURES, LOSS_SIGNATURES, INFLUENCE_SIGNATURES,
-                  SETS_SIGNATURES, DYN_SIGNATURES, NL_SIGNATURES, BK_SIGNATURES, MG_SIGNATURES, RS_SIGNATURES):
+                  SETS_SIGNATURES, DYN_SIGNATURES, NL_SIGNATURES, BK_SIGNATURES, MG_SIGNATURES, RS_SIGNATURES,
+                  HR_SIGNATURES):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype = restype
@@ -284,7 +299,8 @@ def load():
             or lib.trs_influence_abi_version() != INFLUENCE_ABI_VERSION \
             or lib.trs_sets_abi_version() != SETS_ABI_VERSION or lib.trs_dyn_abi_version() != DYN_ABI_VERSION \
             or lib.trs_nl_abi_version() != NL_ABI_VERSION or lib.trs_bk_abi_version() != BK_ABI_VERSION \
-            or lib.trs_mg_abi_version() != MG_ABI_VERSION or lib.trs_rs_abi_version() != RS_ABI_VERSION:
+            or lib.trs_mg_abi_version() != MG_ABI_VERSION or lib.trs_rs_abi_version() != RS_ABI_VERSION \
+            or lib.trs_hr_abi_version() != HR_ABI_VERSION:
         raise HipExtensionError("libtrs_hip.so ABI version mismatch")
     _lib = lib
     return lib

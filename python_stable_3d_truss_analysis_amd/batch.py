@@ -1615,6 +1615,106 @@ class DeviceBatch:
             out["n_modes"].copy_(ws["n_mass"].clamp(max=p))
         return out
 
+    # -- harmonic response over a frequency sweep from the converged block (include/trs_harmonic.h) -----
+    #: the envelopes `harmonic` can give, and where their axes lie after [B, L]
+    HARMONIC_RESULTS = ("u", "N", "R")
+
+    def _harmonic_shapes(self, L, S, p, want, Pj=0, Pm=0):
+        per = {"u": [self.nJ_max, 3], "N": [self.nM_max], "R": [self.nJ_max, 3]}
+        t = self.torch
+        shapes = {"g": [self.B, L, p], "n_modes": ([self.B], t.int32)}
+        for k in want:
+            shapes[k + "_amp"] = [self.B, L] + per[k]
+            shapes[k + "_at"] = ([self.B, L] + per[k], t.int32)
+        if Pj:
+            shapes["frf_u"] = [self.B, L, S, Pj, 3, 2]
+        if Pm:
+            shapes["frf_N"] = [self.B, L, S, Pm, 2]
+        return shapes
+
+    def harmonic(self, omegas, pattern=None, accel=None, damping=0.02, damp_mass=0.0, damp_stiff=0.0, residual=True,
+                 monitor_joints=None, monitor_members=None, want=HARMONIC_RESULTS, out=None, generation=None,
+                 max_result_bytes=4 << 30):
+        """The steady-state response of every truss to L harmonic excitations Re(f_l e^(i W t)) over the circular
+        forcing frequencies `omegas` [S] (>= 0, finite, any order; shared by the batch), by superposition of the modes
+        of the last `modes()`, include/trs_harmonic.h.  f_l = P_l - M iota(ag_l): `pattern` a float64 device tensor
+        [B, L, nJ_max, 3], the load patterns in the CALLER's joint numbering (reduced once by `trs_gather_cases`), and /
+        or `accel` [L, 3] or [B, L, 3], ground-acceleration amplitudes (the results are then relative to the ground);
+        1 <= L <= 16.  Damping per mode: zeta_k = `damping` + `damp_mass` / (2 w_k) + `damp_stiff` w_k / 2 (a modal
+        ratio and Rayleigh's two constants of `factor_dynamic`; all >= 0, at least one > 0).  `residual`: the truncated
+        modes respond STATICALLY (residual flexibility: one more substitution against the resident factor) - their
+        damping and inertia are ignored, so the answer is the standard mode-acceleration one, good for W well below the
+        frequency of the first mode left out and not beyond it; without it they are dropped altogether.
+        `monitor_joints` [B, Pj], `monitor_members` [B, Pm]: int32 device tensors of caller's joint ids / member ids
+        (-1: none) whose complex response at every frequency is wanted.  Returns a dict of device tensors: for the
+        names in `want` the envelopes u_amp, R_amp [B, L, nJ_max, 3], N_amp [B, L, nM_max] (the largest amplitude over
+        the sweep; caller's joint numbering; u zero at held DOFs, R zero at free ones) with u_at, R_at, N_at (int32: the
+        FIRST index of `omegas` that attains it); frf_u [B, L, S, Pj, 3] and frf_N [B, L, S, Pm] (complex128) when
+        monitors are given; g [B, L, p] (the modal loads, zeros beyond n_modes) and n_modes [B].  `out`: such a dict to
+        write into.  The frf outputs are refused above `max_result_bytes`.
+        Guarded as `response_spectrum`: the `modes()` state must be current (ValueError when `factor()`,
+        `solve_cases()`, ... ran since; `generation`: the value the caller saw after ITS `modes()`, checked as well).
+        Nothing is bumped here: the case block is only scratch, and X, lam and n_mass are only read - `mode_gradients`
+        and `response_spectrum` work afterwards with the same bits, and the call can be repeated."""
+        t = self.torch
+        state = getattr(self, "_modes_state", None)
+        if not getattr(self, "_factored", False) or state is None:
+            raise ValueError("harmonic(): no modes - call factor() and modes(p) first")
+        if state["generation"] != self.generation or (generation is not None and generation != self.generation):
+            raise ValueError("harmonic(): the modes are stale - factor(), solve_cases() or another analysis ran since "
+                             "the modes() this analysis belongs to")
+        p = state["p"]
+        if pattern is not None:
+            pattern = self._check_loads("harmonic", pattern)
+        mon_j = self._monitor_ids("monitor_joints", monitor_joints, True)
+        mon_m = self._monitor_ids("monitor_members", monitor_members, False)
+        Pj, Pm = int(mon_j.shape[1]), int(mon_m.shape[1])
+        W, ag, L, want = _check_harmonic_args(self.B, self.nJ_max, p, omegas, None if pattern is None else pattern.shape,
+                                              accel, damping, damp_mass, damp_stiff, want, Pj, Pm, max_result_bytes)
+        S = int(W.size)
+        if self.B and not self.lib.trs_hr_fits(self.nJ_max, self.nM_max, p):     # (before any output is allocated)
+            raise HipExtensionError(f"harmonic(): the response vectors of a truss of {self.nJ_max} joints / "
+                                    f"{self.nM_max} members exceed the LDS of the sweep kernel (trs_hr_fits)")
+        if out is not None:   # (what an earlier call returned: the complex views of its frf tensors)
+            out = {k: t.view_as_real(x) if k in ("frf_u", "frf_N") and x.is_complex() else x for k, x in out.items()}
+        out = self._out_tensors("harmonic", self._harmonic_shapes(L, S, p, want, Pj, Pm), out)
+        if self.B:
+            ws = self._modes_ws
+            dev = lambda x: t.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(self.device)
+            jo, stream, tab = self._case_launch()
+            F = Pr = None
+            with t.cuda.device(self.device):
+                W_d, ag_d = dev(W), None if ag is None else dev(ag)
+                if pattern is not None:
+                    Pr = self._hr_Pr = self._case_block("_hr_Pr", L)
+                    _capi.check(self.lib.trs_gather_cases(self.B, L, self.nJ_max, pattern.data_ptr(),
+                                                          self.free_index.data_ptr(), self.n_free.data_ptr(),
+                                                          self.nJ.data_ptr(), jo, Pr.data_ptr(), self.rows, stream),
+                                "trs_gather_cases")
+                if residual:
+                    F = self.cases_F = self._case_block("cases_F", MODES_BLOCK)
+                _capi.check(self.lib.trs_hr_modal(
+                    self.B, L, self.nJ_max, self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(),
+                    ws["X"].data_ptr(), self.rows, ws["lam"].data_ptr(), ws["Mf"].data_ptr(), ws["n_mass"].data_ptr(), p,
+                    _ptr(Pr), _ptr(ag_d), int(bool(residual)), out["g"].data_ptr(), _ptr(F), stream), "trs_hr_modal")
+                if residual:
+                    self._potrs_cases(F, MODES_BLOCK)
+                if want or Pj or Pm:
+                    get = lambda k: _ptr(out.get(k))
+                    _capi.check(getattr(self.lib, f"trs_hr_sweep{tab}")(
+                        self.B, L, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *self._members(),
+                        self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), jo,
+                        ws["X"].data_ptr(), self.rows, ws["lam"].data_ptr(), ws["n_mass"].data_ptr(), p,
+                        out["g"].data_ptr(), _ptr(F), S, W_d.data_ptr(), float(damping), float(damp_mass),
+                        float(damp_stiff), get("u_amp"), get("u_at"), get("R_amp"), get("R_at"), get("N_amp"),
+                        get("N_at"), mon_j.data_ptr() if Pj else None, Pj, mon_m.data_ptr() if Pm else None, Pm,
+                        get("frf_u"), get("frf_N"), stream), f"trs_hr_sweep{tab}")
+                out["n_modes"].copy_(ws["n_mass"].clamp(max=p))
+        for k in ("frf_u", "frf_N"):
+            if k in out:
+                out[k] = t.view_as_complex(out[k])
+        return out
+
     # -- transient response: Newmark time stepping on a factor of K + sigma M (include/trs_dynamics.h) ------------------
     def factor_dynamic(self, dt, beta=0.25, gamma=0.5, damp_mass=0.0, damp_stiff=0.0, joint_mass=None, mass_scale=1.0):
         """`factor()` for the time domain: dofmap, assembly, the lumped mass of `modes` (`trs_modes_mass`, the same
@@ -3918,6 +4018,159 @@ def solve_response_spectrum(trusses_or_packed, directions, periods, accel, p=6, 
     out.displace_all = out.displace.square().sum(1).sqrt()
     out.force_all = out.force.square().sum(1).sqrt()
     out.reaction_all = out.reaction.square().sum(1).sqrt()
+    return _finish_result(torch, dev, out, on_device)
+
+
+@dataclass
+class HarmonicResult:
+    """Results of `solve_harmonic` for L harmonic excitations per truss over S forcing frequencies: eigenvalue, omega
+    [B, p], n_modes, iters, info [B] as `ModeResult`; the envelopes displace, reaction [B, L, nJ_max, 3] and force
+    [B, L, nM_max] (the largest steady-state amplitude over the sweep: non-negative; displace zero at held DOFs, reaction
+    zero at free ones; relative to the ground when a ground acceleration was given), displace_at, force_at, reaction_at
+    (int32: the first index of `omegas` that attains it) and displace_omega, force_omega, reaction_omega (the forcing
+    frequency at that index); frf_displace [B, L, S, Pj, 3] and frf_force [B, L, S, Pm] (complex128: the response of the
+    monitored joints and members at every frequency, u(t) = Re(frf e^(i W t)); zeros for a monitor id of -1).  The modes
+    that were truncated respond statically (or not at all with residual=False): see `DeviceBatch.harmonic`."""
+    eigenvalue: np.ndarray
+    omega: np.ndarray
+    n_modes: np.ndarray
+    iters: np.ndarray
+    displace: np.ndarray
+    force: np.ndarray
+    reaction: np.ndarray
+    displace_at: np.ndarray
+    force_at: np.ndarray
+    reaction_at: np.ndarray
+    displace_omega: np.ndarray
+    force_omega: np.ndarray
+    reaction_omega: np.ndarray
+    frf_displace: np.ndarray
+    frf_force: np.ndarray
+    info: np.ndarray
+
+    # (`modes` returns no "omega" and `harmonic` no "*_omega": `solve_harmonic` forms them with torch)
+    FIELDS = {"eigenvalue": ("lam", float("nan"), "float64", ("P",)), "omega": ("omega", float("nan"), "float64", ("P",)),
+              "n_modes": ("n_modes", 0, "int32", ()), "iters": ("iters", 0, "int32", ()),
+              "displace": ("u_amp", 0.0, "float64", ("L", "nJ", 3)), "force": ("N_amp", 0.0, "float64", ("L", "nM")),
+              "reaction": ("R_amp", 0.0, "float64", ("L", "nJ", 3)), "displace_at": ("u_at", 0, "int32", ("L", "nJ", 3)),
+              "force_at": ("N_at", 0, "int32", ("L", "nM")), "reaction_at": ("R_at", 0, "int32", ("L", "nJ", 3)),
+              "displace_omega": ("u_omega", 0.0, "float64", ("L", "nJ", 3)),
+              "force_omega": ("N_omega", 0.0, "float64", ("L", "nM")),
+              "reaction_omega": ("R_omega", 0.0, "float64", ("L", "nJ", 3)),
+              "frf_displace": ("frf_u", 0.0, "complex128", ("L", "S", "Pj", 3)),
+              "frf_force": ("frf_N", 0.0, "complex128", ("L", "S", "Pm"))}
+
+
+def _check_harmonic_args(B, nJ_max, p, omegas, pattern_shape=None, accel=None, damping=0.02, damp_mass=0.0,
+                         damp_stiff=0.0, want=DeviceBatch.HARMONIC_RESULTS, Pj=0, Pm=0, max_result_bytes=4 << 30):
+    """The argument errors of `DeviceBatch.harmonic` / `solve_harmonic` that need no device (ValueError).
+    `pattern_shape`: the shape of the load patterns ([B, L, nJ_max, 2 or 3]) or None.  Returns (omegas [S] as a host
+    float64 array, accel [B, L, 3] as one or None, L, `want` as a tuple)."""
+    who = "harmonic"
+    if isinstance(p, bool) or int(p) != p or not 1 <= int(p) <= 8:
+        raise ValueError(f"{who}: p must be an integer in 1 .. 8, got {p!r}")
+    W = _host_array(omegas, np.float64)
+    if W.ndim != 1 or W.size < 1:
+        raise ValueError(f"{who}: omegas must be [S] with S >= 1, got {list(W.shape)}")
+    if not (np.isfinite(W).all() and (W >= 0).all()):
+        raise ValueError(f"{who}: omegas must be finite and non-negative")
+    if pattern_shape is None and accel is None:
+        raise ValueError(f"{who}: at least one of pattern and accel must be given")
+    L = None
+    if pattern_shape is not None:
+        shape = tuple(int(v) for v in pattern_shape)
+        if len(shape) != 4 or shape[0] != B or shape[2] != nJ_max or shape[3] not in (2, 3):
+            raise ValueError(f"{who}: pattern must be [B={B}, L, nJ_max={nJ_max}, 2 or 3], got {list(shape)}")
+        L = shape[1]
+    ag = None
+    if accel is not None:
+        ag = _host_array(accel, np.float64)
+        if ag.ndim not in (2, 3) or ag.shape[-1] not in (2, 3) or (ag.ndim == 3 and ag.shape[0] != B) \
+                or (L is not None and ag.shape[-2] != L):
+            raise ValueError(f"{who}: accel must be [L, 3] or [B={B}, L, 3] (or 2 components)"
+                             + (f" with L={L} as pattern" if L is not None else "") + f", got {list(ag.shape)}")
+        if not np.isfinite(ag).all():
+            raise ValueError(f"{who}: accel must be finite")
+        if ag.shape[-1] == 2:
+            ag = np.concatenate([ag, np.zeros(ag.shape[:-1] + (1,))], axis=-1)
+        if ag.ndim == 2:
+            ag = np.broadcast_to(ag, (B,) + ag.shape)
+        ag = np.array(ag, dtype=np.float64, order="C")   # (a copy: a broadcast view is not writable)
+        L = int(ag.shape[1])
+    if not 1 <= L <= MODES_BLOCK:
+        raise ValueError(f"{who}: the number of cases L must be in 1 .. {MODES_BLOCK} (pattern or accel), got {L}")
+    for name, x in (("damping", damping), ("damp_mass", damp_mass), ("damp_stiff", damp_stiff)):
+        if isinstance(x, (bool, str)) or not isinstance(x, (int, float, np.integer, np.floating)) \
+                or not (np.isfinite(x) and x >= 0):
+            raise ValueError(f"{who}: {name} must be a non-negative finite number, got {x!r}")
+    if not (damping > 0 or damp_mass > 0 or damp_stiff > 0):
+        raise ValueError(f"{who}: at least one of damping, damp_mass and damp_stiff must be positive - an undamped mode "
+                         "has no steady state at its own frequency")
+    if isinstance(want, str):
+        raise ValueError(f"{who}: want must be a sequence of names out of {DeviceBatch.HARMONIC_RESULTS}")
+    want = tuple(want)
+    if any(k not in DeviceBatch.HARMONIC_RESULTS for k in want):
+        raise ValueError(f"{who}: want must name some of {DeviceBatch.HARMONIC_RESULTS}, got {want}")
+    if Pj < 0 or Pm < 0:
+        raise ValueError(f"{who}: monitor counts must not be negative")
+    nbytes = 16 * B * L * int(W.size) * (3 * Pj + Pm)
+    if nbytes > max_result_bytes:
+        raise ValueError(f"{who}: the responses of {Pj} monitored joints and {Pm} members of B={B} trusses, L={L} cases "
+                         f"at S={W.size} frequencies take {nbytes} bytes, more than max_result_bytes = {max_result_bytes}")
+    return np.ascontiguousarray(W), ag, L, want
+
+
+def solve_harmonic(trusses_or_packed, omegas, pattern=None, accel=None, p=6, damping=0.02, damp_mass=0.0, damp_stiff=0.0,
+                   residual=True, monitor_joints=None, monitor_members=None, joint_mass=None, mass_scale=1.0, tol=1e-10,
+                   max_iters=256, device=None, reorder=False, options=None, max_slab_bytes=64 << 30, on_device=False,
+                   use_envelope=True, max_result_bytes=4 << 30):
+    """The steady-state harmonic response of every truss of a batch over the forcing frequencies `omegas` [S], from ONE
+    factorisation per truss: the `p` (1 .. 8) lowest modes (`solve_modes`: the same lumped mass, `joint_mass`,
+    `mass_scale`), then per case the modal loads, the static correction for the truncated modes by one more substitution
+    against the resident factor, and the sweep (`DeviceBatch.harmonic`, include/trs_harmonic.h, where `pattern`
+    [B, L, nJ_max, dim], `accel` [L, dim] or [B, L, dim], the three dampings and `residual` are described, and what the
+    static correction does NOT cover: frequencies near or above the first mode left out).  `monitor_joints` [B, Pj],
+    `monitor_members` [B, Pm]: joint / member ids (-1: none) whose complex response at every frequency is returned.
+    The other arguments as `solve_modes`.  Returns a `HarmonicResult`."""
+    packed = _as_packed(trusses_or_packed)
+    B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
+    jm_shape = jm_min = None
+    if joint_mass is not None:
+        jm_shape = tuple(int(x) for x in joint_mass.shape)
+        jm = _host_array(joint_mass, np.float64)
+        jm_min = (float(jm.min()) if jm.size else 0.0) if np.isfinite(jm).all() else float("nan")
+    _check_mode_args(B, nJ_max, p, jm_shape, mass_scale, tol, max_iters, joint_mass_min=jm_min)
+    mon = {}
+    for name, ids, counts in (("monitor_joints", monitor_joints, packed.nJ), ("monitor_members", monitor_members, packed.nM)):
+        x = np.zeros([B, 0], dtype=np.int32) if ids is None else _host_array(ids, None)
+        if x.ndim != 2 or x.shape[0] != B or (x.size and not np.issubdtype(x.dtype, np.integer)):
+            raise ValueError(f"harmonic: {name} must be an integer array [B={B}, P], got {x.dtype} {list(x.shape)}")
+        if x.size and (np.any(x < -1) or np.any(x >= np.asarray(counts).reshape(-1, 1))):
+            raise ValueError(f"harmonic: {name} has an id outside its truss (-1 = none)")
+        mon[name] = np.ascontiguousarray(x, dtype=np.int32)
+    Pj, Pm = mon["monitor_joints"].shape[1], mon["monitor_members"].shape[1]
+    W, ag, L, want = _check_harmonic_args(B, nJ_max, p, omegas, None if pattern is None else np.shape(pattern), accel,
+                                          damping, damp_mass, damp_stiff, Pj=Pj, Pm=Pm, max_result_bytes=max_result_bytes)
+    p = int(p)
+    torch, dev = _require_gpu(device)
+    joint_mass = _device_f64(torch, dev, joint_mass)
+    pattern, ag = _device_f64(torch, dev, pattern, vectors=True), _device_f64(torch, dev, ag)
+    mon = {k: torch.from_numpy(x).to(dev) for k, x in mon.items()}
+    out = _new_result(torch, dev, HarmonicResult, B,
+                      {"P": p, "L": L, "S": int(W.size), "Pj": Pj, "Pm": Pm, "nJ": nJ_max, "nM": nM_max})
+    for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope):
+        res = db.modes(p, tol=tol, max_iters=max_iters, joint_mass=part.cut(joint_mass, nJ=1), mass_scale=mass_scale)
+        res.update(db.harmonic(W, pattern=part.cut(pattern, nJ=2), accel=part.cut(ag), damping=damping,
+                               damp_mass=damp_mass, damp_stiff=damp_stiff, residual=residual,
+                               monitor_joints=part.cut(mon["monitor_joints"]) if Pj else None,
+                               monitor_members=part.cut(mon["monitor_members"]) if Pm else None, want=want,
+                               max_result_bytes=max_result_bytes))
+        _put_result(part, out, res)
+    out.omega = out.eigenvalue.sqrt()
+    W_d = torch.from_numpy(W).to(dev)
+    out.displace_omega = W_d[out.displace_at.long()]
+    out.force_omega = W_d[out.force_at.long()]
+    out.reaction_omega = W_d[out.reaction_at.long()]
     return _finish_result(torch, dev, out, on_device)
 
 

@@ -512,6 +512,60 @@ class Truss:
                 "displace_all": result.displace_all[0, :nJ, :dim].copy(), "force_all": result.force_all[0, :nM].copy(),
                 "reaction_all": result.reaction_all[0, :nJ, :dim].copy()}
 
+    def HarmonicResponse(self, omegas, loads=None, accel=None, nModes=6, damping=0.02, dampMass=0.0, dampStiff=0.0,
+                         residual=True, monitorJoints=None, monitorMembers=None, jointMasses=None, massScale=1.0):
+        """The steady-state response of this truss to harmonic excitation over the circular forcing frequencies
+        `omegas` [S], by superposition of its `nModes` (1 .. 8) lowest modes (the lumped mass, `jointMasses` and
+        `massScale` of `NaturalFrequencies`).  `loads`: a list of `{jointID: vector}` dicts, the load amplitudes of one
+        case each (None: the truss's own joint forces as one case, unless only `accel` is given); `accel` [L, dim]:
+        ground-acceleration amplitudes per case (the results are then relative to the ground); up to 16 cases.  Damping
+        of mode k: `damping` + `dampMass` / (2 omega_k) + `dampStiff` omega_k / 2, at least one of them positive.
+        `residual`: the modes beyond `nModes` respond statically (`batch.solve_harmonic`) - good well below the first
+        frequency left out, not near or above it.  Returns a dict of numpy arrays in the truss's own joint and member
+        ids, n the number of modes the truss has: "eigenvalue", "omega" [n]; the largest amplitudes over the sweep
+        "displace", "reaction" [L, joints, dim] and "force" [L, members], the index into `omegas` where each occurs
+        ("displace_at", ...) and that frequency ("displace_omega", ...); with `monitorJoints` / `monitorMembers` (lists of
+        ids) the complex responses "frf_displace" [L, S, len(monitorJoints), dim] and "frf_force"
+        [L, S, len(monitorMembers)].  The truss's loads, its solved state and its results stay as they are; errors as
+        `NaturalFrequencies`."""
+        if not self.isStable:
+            raise TrussNotStableError("The truss is not stable !")
+        from .batch import pack_trusses, solve_harmonic  # late import: keeps the model importable without torch
+        packed = pack_trusses([self])
+        nJ, dim = len(self._pos), self._dim
+        masses = None
+        if jointMasses:
+            masses = np.zeros([1, packed.nJ_max])
+            for jointID, mass in jointMasses.items():
+                masses[0, jointID] = mass
+        if loads is None and accel is None:
+            loads = [self._loads]
+        pattern = None
+        if loads is not None:
+            pattern = np.zeros([1, len(loads), packed.nJ_max, 3])
+            for k, case in enumerate(loads):
+                for jointID, vector in case.items():
+                    pattern[0, k, jointID, :dim] = np.asarray(vector, dtype=float)[:dim]
+        monitors = {}
+        for name, ids in (("monitor_joints", monitorJoints), ("monitor_members", monitorMembers)):
+            monitors[name] = None if ids is None or not len(ids) else np.asarray(ids, dtype=np.int32).reshape(1, -1)
+        result = solve_harmonic(packed, omegas, pattern=pattern, accel=accel, p=nModes, damping=damping,
+                                damp_mass=dampMass, damp_stiff=dampStiff, residual=residual, joint_mass=masses,
+                                mass_scale=massScale, **monitors)
+        if int(result.info[0]) != 0:
+            raise np.linalg.LinAlgError("Singular matrix")
+        n, nM = int(result.n_modes[0]), int(packed.nM[0])
+        out = {"eigenvalue": result.eigenvalue[0, :n].copy(), "omega": result.omega[0, :n].copy()}
+        for tail in ("", "_at", "_omega"):
+            out["displace" + tail] = getattr(result, "displace" + tail)[0, :, :nJ, :dim].copy()
+            out["reaction" + tail] = getattr(result, "reaction" + tail)[0, :, :nJ, :dim].copy()
+            out["force" + tail] = getattr(result, "force" + tail)[0, :, :nM].copy()
+        if monitors["monitor_joints"] is not None:
+            out["frf_displace"] = result.frf_displace[0, ..., :dim].copy()
+        if monitors["monitor_members"] is not None:
+            out["frf_force"] = result.frf_force[0].copy()
+        return out
+
     def BucklingFactors(self, nModes=4, returnShapes=False, maxShifts=6):
         """By what factor can this truss's loads grow before it buckles (linear buckling, `batch.solve_buckling`)?
         Returns `(critical, factors)`: `critical` the smallest positive load factor (NaN when none was found within
