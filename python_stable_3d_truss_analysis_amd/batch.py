@@ -1451,6 +1451,35 @@ class DeviceBatch:
                              "generation": self.generation}
         return out
 
+    # -- what the analyses on the converged block share (mode_gradients, response_spectrum, harmonic) ------------------
+    def _current_modes(self, who, generation):
+        """The state that `modes()` left, if it is current; else ValueError (`mode_gradients` speaks of its forward
+        solution, the others of the modes)."""
+        what, stale, whose = ("forward solution", "is stale", "these gradients belong") if who == "mode_gradients" else \
+            ("modes", "are stale", "this analysis belongs")
+        state = getattr(self, "_modes_state", None)
+        if not getattr(self, "_factored", False) or state is None:
+            raise ValueError(f"{who}(): no {what} - call factor() and modes(p) first")
+        if state["generation"] != self.generation or (generation is not None and generation != self.generation):
+            raise ValueError(f"{who}(): the {what} {stale} - factor(), solve_cases() or another analysis ran since the "
+                             f"modes() {whose} to")
+        return state
+
+    def _to_device(self, x):
+        """A host array as a contiguous float64 tensor on the batch's device."""
+        return self.torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(self.device)
+
+    def _residual_block(self, on, modal):
+        """`modal(F)` launches a modal kernel, which with the correction `on` leaves right-hand sides in the case block
+        F (else None); `trs_potrs_cases` then solves them in place.  Returns F for the second kernel."""
+        F = None
+        if on:
+            F = self.cases_F = self._case_block("cases_F", MODES_BLOCK)
+        modal(F)
+        if on:
+            self._potrs_cases(F, MODES_BLOCK)
+        return F
+
     # -- gradients of the eigenvalues from the converged block (include/trs_modegrad.h) ------------------
     #: the gradients `mode_gradients` can give
     MODE_GRADIENTS = ("A", "E", "rho", "xyz", "joint_mass")
@@ -1479,12 +1508,7 @@ class DeviceBatch:
         `modes()`, `buckling()`, ...) makes this raise ValueError (`generation`: the value the caller saw after ITS
         `modes()`, checked as well).  Nothing is bumped or overwritten here: the call can be repeated."""
         t = self.torch
-        state = getattr(self, "_modes_state", None)
-        if not getattr(self, "_factored", False) or state is None:
-            raise ValueError("mode_gradients(): no forward solution - call factor() and modes(p) first")
-        if state["generation"] != self.generation or (generation is not None and generation != self.generation):
-            raise ValueError("mode_gradients(): the forward solution is stale - factor(), solve_cases() or another "
-                             "analysis ran since the modes() these gradients belong to")
+        state = self._current_modes("mode_gradients", generation)
         p = state["p"]
         if want is None:
             want = tuple(k for k in self.MODE_GRADIENTS if k != "joint_mass" or state["joint_mass"] is not None)
@@ -1562,19 +1586,13 @@ class DeviceBatch:
         joint numbering; u zero at held DOFs, R zero at free ones) and, with `want_modal`, their signed modal values
         modal_u, modal_R [B, G, p + 1, nJ_max, 3], modal_N [B, G, p + 1, nM_max] (slot p: the missing mass, zeros
         without it).  `out`: such a dict to write into.
-        Guarded as `mode_gradients`: the `modes()` state must be current (ValueError when `factor()`,
+        Guarded by `_current_modes`: the `modes()` state must be current (ValueError when `factor()`,
         `solve_cases()`, ... ran since; `generation`: the value the caller saw after ITS `modes()`, checked as well).
         Nothing is bumped here: `modes()` already invalidated what `adjoint_cases` differentiates, the case block is
         only scratch, and X, lam and n_mass are only read - `mode_gradients` works afterwards with the same bits, and
         the call can be repeated."""
         t = self.torch
-        state = getattr(self, "_modes_state", None)
-        if not getattr(self, "_factored", False) or state is None:
-            raise ValueError("response_spectrum(): no modes - call factor() and modes(p) first")
-        if state["generation"] != self.generation or (generation is not None and generation != self.generation):
-            raise ValueError("response_spectrum(): the modes are stale - factor(), solve_cases() or another analysis "
-                             "ran since the modes() this analysis belongs to")
-        p = state["p"]
+        p = self._current_modes("response_spectrum", generation)["p"]
         dirs, T, Sa, zpa, code, want = _check_spectrum_args(p, directions, periods, accel, damping, rule, zpa, want)
         G, K = int(Sa.shape[0]), int(Sa.shape[1])
         if self.B and not self.lib.trs_rs_fits(self.nJ_max, self.nM_max, p):     # (before any output is allocated)
@@ -1588,22 +1606,16 @@ class DeviceBatch:
         if sc is None or tuple(sc["q"].shape) != (self.B, G, p):
             sc = self._rs_ws = {"q": t.empty([self.B, G, p], dtype=t.float64, device=self.device),
                                 "rho": t.empty([self.B, 8, 8], dtype=t.float64, device=self.device)}
-        dev = lambda x: t.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(self.device)
         jo, stream, tab = self._case_launch()
-        F = None
         with t.cuda.device(self.device):
-            dirs_d, T_d, Sa_d, zpa_d = dev(dirs), dev(T), dev(Sa), dev(zpa)
-            if missing_mass:
-                F = self.cases_F = self._case_block("cases_F", MODES_BLOCK)
-            _capi.check(self.lib.trs_rs_modal(
+            dirs_d, T_d, Sa_d, zpa_d = (self._to_device(x) for x in (dirs, T, Sa, zpa))
+            F = self._residual_block(missing_mass, lambda F: _capi.check(self.lib.trs_rs_modal(
                 self.B, self.nJ_max, self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(),
                 ws["X"].data_ptr(), self.rows, ws["lam"].data_ptr(), ws["Mf"].data_ptr(), ws["n_mass"].data_ptr(), p, G,
                 dirs_d.data_ptr(), K, T_d.data_ptr(), Sa_d.data_ptr(), zpa_d.data_ptr(), float(damping), code,
                 int(bool(missing_mass)), out["gamma"].data_ptr(), out["sa"].data_ptr(), out["meff"].data_ptr(),
                 out["mtot"].data_ptr(), out["base"].data_ptr(), sc["q"].data_ptr(), sc["rho"].data_ptr(), _ptr(F), stream),
-                "trs_rs_modal")
-            if missing_mass:
-                self._potrs_cases(F, MODES_BLOCK)
+                "trs_rs_modal"))
             if want:
                 modal = lambda k: _ptr(out.get("modal_" + k))
                 _capi.check(getattr(self.lib, f"trs_rs_combine{tab}")(
@@ -1652,18 +1664,12 @@ class DeviceBatch:
         FIRST index of `omegas` that attains it); frf_u [B, L, S, Pj, 3] and frf_N [B, L, S, Pm] (complex128) when
         monitors are given; g [B, L, p] (the modal loads, zeros beyond n_modes) and n_modes [B].  `out`: such a dict to
         write into.  The frf outputs are refused above `max_result_bytes`.
-        Guarded as `response_spectrum`: the `modes()` state must be current (ValueError when `factor()`,
+        Guarded by `_current_modes`: the `modes()` state must be current (ValueError when `factor()`,
         `solve_cases()`, ... ran since; `generation`: the value the caller saw after ITS `modes()`, checked as well).
         Nothing is bumped here: the case block is only scratch, and X, lam and n_mass are only read - `mode_gradients`
         and `response_spectrum` work afterwards with the same bits, and the call can be repeated."""
         t = self.torch
-        state = getattr(self, "_modes_state", None)
-        if not getattr(self, "_factored", False) or state is None:
-            raise ValueError("harmonic(): no modes - call factor() and modes(p) first")
-        if state["generation"] != self.generation or (generation is not None and generation != self.generation):
-            raise ValueError("harmonic(): the modes are stale - factor(), solve_cases() or another analysis ran since "
-                             "the modes() this analysis belongs to")
-        p = state["p"]
+        p = self._current_modes("harmonic", generation)["p"]
         if pattern is not None:
             pattern = self._check_loads("harmonic", pattern)
         mon_j = self._monitor_ids("monitor_joints", monitor_joints, True)
@@ -1680,25 +1686,20 @@ class DeviceBatch:
         out = self._out_tensors("harmonic", self._harmonic_shapes(L, S, p, want, Pj, Pm), out)
         if self.B:
             ws = self._modes_ws
-            dev = lambda x: t.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(self.device)
             jo, stream, tab = self._case_launch()
-            F = Pr = None
+            Pr = None
             with t.cuda.device(self.device):
-                W_d, ag_d = dev(W), None if ag is None else dev(ag)
+                W_d, ag_d = self._to_device(W), None if ag is None else self._to_device(ag)
                 if pattern is not None:
                     Pr = self._hr_Pr = self._case_block("_hr_Pr", L)
                     _capi.check(self.lib.trs_gather_cases(self.B, L, self.nJ_max, pattern.data_ptr(),
                                                           self.free_index.data_ptr(), self.n_free.data_ptr(),
                                                           self.nJ.data_ptr(), jo, Pr.data_ptr(), self.rows, stream),
                                 "trs_gather_cases")
-                if residual:
-                    F = self.cases_F = self._case_block("cases_F", MODES_BLOCK)
-                _capi.check(self.lib.trs_hr_modal(
+                F = self._residual_block(residual, lambda F: _capi.check(self.lib.trs_hr_modal(
                     self.B, L, self.nJ_max, self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(),
                     ws["X"].data_ptr(), self.rows, ws["lam"].data_ptr(), ws["Mf"].data_ptr(), ws["n_mass"].data_ptr(), p,
-                    _ptr(Pr), _ptr(ag_d), int(bool(residual)), out["g"].data_ptr(), _ptr(F), stream), "trs_hr_modal")
-                if residual:
-                    self._potrs_cases(F, MODES_BLOCK)
+                    _ptr(Pr), _ptr(ag_d), int(bool(residual)), out["g"].data_ptr(), _ptr(F), stream), "trs_hr_modal"))
                 if want or Pj or Pm:
                     get = lambda k: _ptr(out.get(k))
                     _capi.check(getattr(self.lib, f"trs_hr_sweep{tab}")(
@@ -3751,11 +3752,52 @@ class ModeResult:
               "n_modes": ("n_modes", 0, "int32", ()), "iters": ("iters", 0, "int32", ())}
 
 
+def _check_p(who, p, note=""):
+    if isinstance(p, bool) or int(p) != p or not 1 <= int(p) <= 8:
+        raise ValueError(f"{who}: p must be an integer in 1 .. 8{note}, got {p!r}")
+
+
+def _check_want(who, want, names):
+    """`want` as a tuple of some of `names`."""
+    if isinstance(want, str):
+        raise ValueError(f"{who}: want must be a sequence of names out of {names}")
+    want = tuple(want)
+    if any(k not in names for k in want):
+        raise ValueError(f"{who}: want must name some of {names}, got {want}")
+    return want
+
+
+def _check_damping(who, name, x):
+    if isinstance(x, (bool, str)) or not isinstance(x, (int, float, np.integer, np.floating)) \
+            or not (np.isfinite(x) and x >= 0):
+        raise ValueError(f"{who}: {name} must be a non-negative finite number, got {x!r}")
+
+
+def _mass_summary(joint_mass):
+    """(shape, smallest entry - NaN when one is not finite) of a `joint_mass` (numpy or torch), (None, None) of None:
+    what `_check_mode_args` is given."""
+    if joint_mass is None:
+        return None, None
+    jm = _host_array(joint_mass, np.float64)
+    return tuple(int(x) for x in joint_mass.shape), \
+        (float(jm.min()) if jm.size else 0.0) if np.isfinite(jm).all() else float("nan")
+
+
+def _mode_buckets(packed, dev, out, p, joint_mass, mass_scale, tol, max_iters, max_slab_bytes, reorder, options,
+                  use_envelope):
+    """The loop of the analyses on the mode block: `_factored_buckets`, `db.modes(p, ...)` per bucket, and
+    (DeviceBatch, _Bucket, res) is yielded; the analysis adds its own results to the dict `res`, which then goes into
+    `out` (`_put_result`).  At the end `out.omega` is the root of the eigenvalues."""
+    for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope):
+        res = db.modes(p, tol=tol, max_iters=max_iters, joint_mass=part.cut(joint_mass, nJ=1), mass_scale=mass_scale)
+        yield db, part, res
+        _put_result(part, out, res)
+    out.omega = out.eigenvalue.sqrt()
+
+
 def _check_mode_args(B, nJ_max, p, joint_mass_shape, mass_scale, tol, max_iters, check_every=8, joint_mass_min=None):
     """The argument errors of `solve_modes` / `DeviceBatch.modes` that need no device."""
-    if isinstance(p, bool) or int(p) != p or not 1 <= int(p) <= 8:
-        raise ValueError(f"modes: p must be an integer in 1 .. 8 (one block of {MODES_BLOCK} vectors delivers at most 8 "
-                         f"pairs), got {p!r}")
+    _check_p("modes", p, f" (one block of {MODES_BLOCK} vectors delivers at most 8 pairs)")
     if joint_mass_shape is not None and tuple(int(x) for x in joint_mass_shape) != (B, nJ_max):
         raise ValueError(f"modes: joint_mass must be [B={B}, nJ_max={nJ_max}], got {tuple(joint_mass_shape)}")
     if joint_mass_min is not None and not joint_mass_min >= 0:
@@ -3779,24 +3821,15 @@ def solve_modes(trusses_or_packed, p=6, joint_mass=None, mass_scale=1.0, tol=1e-
     `ModeResult`."""
     packed = _as_packed(trusses_or_packed)
     B, nJ_max = packed.B, packed.nJ_max
-    jm_shape = jm_min = None
-    if joint_mass is not None:
-        jm_shape = tuple(int(x) for x in joint_mass.shape)
-        if isinstance(joint_mass, np.ndarray):
-            jm_min = float(joint_mass.min()) if joint_mass.size else 0.0
-            jm_min = jm_min if np.isfinite(joint_mass).all() else float("nan")
-        else:
-            jm_min = float(joint_mass.min()) if joint_mass.numel() else 0.0
-            jm_min = jm_min if bool(joint_mass.isfinite().all()) else float("nan")
+    jm_shape, jm_min = _mass_summary(joint_mass)
     _check_mode_args(B, nJ_max, p, jm_shape, mass_scale, tol, max_iters, joint_mass_min=jm_min)
     p = int(p)
     torch, dev = _require_gpu(device)
     joint_mass = _device_f64(torch, dev, joint_mass)
     out = _new_result(torch, dev, ModeResult, B, {"P": p, "nJ": nJ_max})
-    for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope):
-        _put_result(part, out, db.modes(p, tol=tol, max_iters=max_iters, joint_mass=part.cut(joint_mass, nJ=1),
-                                        mass_scale=mass_scale))
-    out.omega = out.eigenvalue.sqrt()
+    for _ in _mode_buckets(packed, dev, out, p, joint_mass, mass_scale, tol, max_iters, max_slab_bytes, reorder, options,
+                           use_envelope):
+        pass   # (the modes alone)
     return _finish_result(torch, dev, out, on_device)
 
 
@@ -3842,11 +3875,7 @@ def _check_mode_gradient_args(B, nJ_max, p, joint_mass_shape, mass_scale, tol, m
     _check_mode_args(B, nJ_max, p, joint_mass_shape, mass_scale, tol, max_iters, joint_mass_min=joint_mass_min)
     if want is None:
         want = tuple(k for k in DeviceBatch.MODE_GRADIENTS if k != "joint_mass" or joint_mass_shape is not None)
-    if isinstance(want, str):
-        raise ValueError(f"solve_mode_gradients: want must be a sequence of names out of {DeviceBatch.MODE_GRADIENTS}")
-    want = tuple(want)
-    if any(k not in DeviceBatch.MODE_GRADIENTS for k in want):
-        raise ValueError(f"solve_mode_gradients: want must name some of {DeviceBatch.MODE_GRADIENTS}, got {want}")
+    want = _check_want("solve_mode_gradients", want, DeviceBatch.MODE_GRADIENTS)
     if "joint_mass" in want and joint_mass_shape is None:
         raise ValueError("solve_mode_gradients: 'joint_mass' is wanted, but no joint_mass was given")
     if weights is not None:
@@ -3870,11 +3899,7 @@ def solve_mode_gradients(trusses_or_packed, p=6, weights=None, joint_mass=None, 
     arguments as `solve_modes`.  Returns a `ModeGradientResult`; read its `gap` before trusting a single row."""
     packed = _as_packed(trusses_or_packed)
     B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
-    jm_shape = jm_min = None
-    if joint_mass is not None:
-        jm_shape = tuple(int(x) for x in joint_mass.shape)
-        jm = _host_array(joint_mass, np.float64)
-        jm_min = (float(jm.min()) if jm.size else 0.0) if np.isfinite(jm).all() else float("nan")
+    jm_shape, jm_min = _mass_summary(joint_mass)
     want = _check_mode_gradient_args(B, nJ_max, p, jm_shape, mass_scale, tol, max_iters,
                                      weights=None if weights is None else _host_array(weights, np.float64), want=want,
                                      sections=sections, joint_mass_min=jm_min)
@@ -3883,11 +3908,9 @@ def solve_mode_gradients(trusses_or_packed, p=6, weights=None, joint_mass=None, 
     joint_mass, weights = _device_f64(torch, dev, joint_mass), _device_f64(torch, dev, weights)
     out = _new_result(torch, dev, ModeGradientResult, B,
                       {"P": p, "R": p if weights is None else 1, "nJ": nJ_max, "nM": nM_max})
-    for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope):
-        res = db.modes(p, tol=tol, max_iters=max_iters, joint_mass=part.cut(joint_mass, nJ=1), mass_scale=mass_scale)
+    for db, part, res in _mode_buckets(packed, dev, out, p, joint_mass, mass_scale, tol, max_iters, max_slab_bytes,
+                                       reorder, options, use_envelope):
         res.update(db.mode_gradients(weights=part.cut(weights), want=want))
-        _put_result(part, out, res)
-    out.omega = out.eigenvalue.sqrt()
     return _finish_result(torch, dev, out, on_device)
 
 
@@ -3942,8 +3965,7 @@ def _check_spectrum_args(p, directions, periods, accel, damping=0.05, rule="cqc"
     (directions [G, 3], periods [K], accel [G, K], zpa [G]) as host float64 arrays, the rule's code and `want` as a
     tuple."""
     who = "response_spectrum"
-    if isinstance(p, bool) or int(p) != p or not 1 <= int(p) <= 8:
-        raise ValueError(f"{who}: p must be an integer in 1 .. 8, got {p!r}")
+    _check_p(who, p)
     dirs = _host_array(directions, np.float64)
     if dirs.ndim != 2 or not 1 <= dirs.shape[0] <= 3 or dirs.shape[1] not in (2, 3):
         raise ValueError(f"{who}: directions must be [G, 3] (or [G, 2]) with 1 <= G <= 3, got {dirs.shape}")
@@ -3969,16 +3991,10 @@ def _check_spectrum_args(p, directions, periods, accel, damping=0.05, rule="cqc"
         raise ValueError(f"{who}: zpa must be [G={G}], finite and non-negative")
     if not isinstance(rule, str) or rule.lower() not in _capi.RS_RULES:
         raise ValueError(f"{who}: rule must be one of {sorted(_capi.RS_RULES)}, got {rule!r}")
-    if isinstance(damping, (bool, str)) or not isinstance(damping, (int, float, np.integer, np.floating)) \
-            or not (np.isfinite(damping) and damping >= 0):
-        raise ValueError(f"{who}: damping must be a non-negative finite number, got {damping!r}")
+    _check_damping(who, "damping", damping)
     if rule.lower() == "cqc" and not damping > 0:
         raise ValueError(f"{who}: rule 'cqc' needs damping > 0, got {damping!r}")
-    if isinstance(want, str):
-        raise ValueError(f"{who}: want must be a sequence of names out of {DeviceBatch.SPECTRUM_RESULTS}")
-    want = tuple(want)
-    if any(k not in DeviceBatch.SPECTRUM_RESULTS for k in want):
-        raise ValueError(f"{who}: want must name some of {DeviceBatch.SPECTRUM_RESULTS}, got {want}")
+    want = _check_want(who, want, DeviceBatch.SPECTRUM_RESULTS)
     return dirs, T, Sa, zpa, _capi.RS_RULES[rule.lower()], want
 
 
@@ -3996,11 +4012,7 @@ def solve_response_spectrum(trusses_or_packed, directions, periods, accel, p=6, 
     `solve_modes`.  Returns a `SpectrumResult`."""
     packed = _as_packed(trusses_or_packed)
     B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
-    jm_shape = jm_min = None
-    if joint_mass is not None:
-        jm_shape = tuple(int(x) for x in joint_mass.shape)
-        jm = _host_array(joint_mass, np.float64)
-        jm_min = (float(jm.min()) if jm.size else 0.0) if np.isfinite(jm).all() else float("nan")
+    jm_shape, jm_min = _mass_summary(joint_mass)
     _check_mode_args(B, nJ_max, p, jm_shape, mass_scale, tol, max_iters, joint_mass_min=jm_min)
     dirs, T, Sa, zpa, _, want = _check_spectrum_args(p, directions, periods, accel, damping, rule, zpa)
     p, G = int(p), len(dirs)
@@ -4009,12 +4021,10 @@ def solve_response_spectrum(trusses_or_packed, directions, periods, accel, p=6, 
     modal = ("modal_displace", "modal_force", "modal_reaction")
     out = _new_result(torch, dev, SpectrumResult, B, {"P": p, "G": G, "V": p + 1, "nJ": nJ_max, "nM": nM_max},
                       without=() if want_modal else modal)
-    for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope):
-        res = db.modes(p, tol=tol, max_iters=max_iters, joint_mass=part.cut(joint_mass, nJ=1), mass_scale=mass_scale)
+    for db, part, res in _mode_buckets(packed, dev, out, p, joint_mass, mass_scale, tol, max_iters, max_slab_bytes,
+                                       reorder, options, use_envelope):
         res.update(db.response_spectrum(dirs, T, Sa, damping=damping, rule=rule, missing_mass=missing_mass, zpa=zpa,
                                         want=want, want_modal=want_modal))
-        _put_result(part, out, res)
-    out.omega = out.eigenvalue.sqrt()
     out.displace_all = out.displace.square().sum(1).sqrt()
     out.force_all = out.force.square().sum(1).sqrt()
     out.reaction_all = out.reaction.square().sum(1).sqrt()
@@ -4067,8 +4077,7 @@ def _check_harmonic_args(B, nJ_max, p, omegas, pattern_shape=None, accel=None, d
     `pattern_shape`: the shape of the load patterns ([B, L, nJ_max, 2 or 3]) or None.  Returns (omegas [S] as a host
     float64 array, accel [B, L, 3] as one or None, L, `want` as a tuple)."""
     who = "harmonic"
-    if isinstance(p, bool) or int(p) != p or not 1 <= int(p) <= 8:
-        raise ValueError(f"{who}: p must be an integer in 1 .. 8, got {p!r}")
+    _check_p(who, p)
     W = _host_array(omegas, np.float64)
     if W.ndim != 1 or W.size < 1:
         raise ValueError(f"{who}: omegas must be [S] with S >= 1, got {list(W.shape)}")
@@ -4100,17 +4109,11 @@ def _check_harmonic_args(B, nJ_max, p, omegas, pattern_shape=None, accel=None, d
     if not 1 <= L <= MODES_BLOCK:
         raise ValueError(f"{who}: the number of cases L must be in 1 .. {MODES_BLOCK} (pattern or accel), got {L}")
     for name, x in (("damping", damping), ("damp_mass", damp_mass), ("damp_stiff", damp_stiff)):
-        if isinstance(x, (bool, str)) or not isinstance(x, (int, float, np.integer, np.floating)) \
-                or not (np.isfinite(x) and x >= 0):
-            raise ValueError(f"{who}: {name} must be a non-negative finite number, got {x!r}")
+        _check_damping(who, name, x)
     if not (damping > 0 or damp_mass > 0 or damp_stiff > 0):
         raise ValueError(f"{who}: at least one of damping, damp_mass and damp_stiff must be positive - an undamped mode "
                          "has no steady state at its own frequency")
-    if isinstance(want, str):
-        raise ValueError(f"{who}: want must be a sequence of names out of {DeviceBatch.HARMONIC_RESULTS}")
-    want = tuple(want)
-    if any(k not in DeviceBatch.HARMONIC_RESULTS for k in want):
-        raise ValueError(f"{who}: want must name some of {DeviceBatch.HARMONIC_RESULTS}, got {want}")
+    want = _check_want(who, want, DeviceBatch.HARMONIC_RESULTS)
     if Pj < 0 or Pm < 0:
         raise ValueError(f"{who}: monitor counts must not be negative")
     nbytes = 16 * B * L * int(W.size) * (3 * Pj + Pm)
@@ -4134,11 +4137,7 @@ def solve_harmonic(trusses_or_packed, omegas, pattern=None, accel=None, p=6, dam
     The other arguments as `solve_modes`.  Returns a `HarmonicResult`."""
     packed = _as_packed(trusses_or_packed)
     B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
-    jm_shape = jm_min = None
-    if joint_mass is not None:
-        jm_shape = tuple(int(x) for x in joint_mass.shape)
-        jm = _host_array(joint_mass, np.float64)
-        jm_min = (float(jm.min()) if jm.size else 0.0) if np.isfinite(jm).all() else float("nan")
+    jm_shape, jm_min = _mass_summary(joint_mass)
     _check_mode_args(B, nJ_max, p, jm_shape, mass_scale, tol, max_iters, joint_mass_min=jm_min)
     mon = {}
     for name, ids, counts in (("monitor_joints", monitor_joints, packed.nJ), ("monitor_members", monitor_members, packed.nM)):
@@ -4158,15 +4157,13 @@ def solve_harmonic(trusses_or_packed, omegas, pattern=None, accel=None, p=6, dam
     mon = {k: torch.from_numpy(x).to(dev) for k, x in mon.items()}
     out = _new_result(torch, dev, HarmonicResult, B,
                       {"P": p, "L": L, "S": int(W.size), "Pj": Pj, "Pm": Pm, "nJ": nJ_max, "nM": nM_max})
-    for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope):
-        res = db.modes(p, tol=tol, max_iters=max_iters, joint_mass=part.cut(joint_mass, nJ=1), mass_scale=mass_scale)
+    for db, part, res in _mode_buckets(packed, dev, out, p, joint_mass, mass_scale, tol, max_iters, max_slab_bytes,
+                                       reorder, options, use_envelope):
         res.update(db.harmonic(W, pattern=part.cut(pattern, nJ=2), accel=part.cut(ag), damping=damping,
                                damp_mass=damp_mass, damp_stiff=damp_stiff, residual=residual,
                                monitor_joints=part.cut(mon["monitor_joints"]) if Pj else None,
                                monitor_members=part.cut(mon["monitor_members"]) if Pm else None, want=want,
                                max_result_bytes=max_result_bytes))
-        _put_result(part, out, res)
-    out.omega = out.eigenvalue.sqrt()
     W_d = torch.from_numpy(W).to(dev)
     out.displace_omega = W_d[out.displace_at.long()]
     out.force_omega = W_d[out.force_at.long()]

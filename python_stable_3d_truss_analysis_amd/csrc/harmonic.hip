@@ -9,9 +9,9 @@
 //                  N_amp [B][L][nM_max] with the index that attains each, and (Re, Im) of the monitored joints and
 //                  members at every frequency
 //
-// Both are one work-group of 256 threads per (truss, case).  trs_hr_modal walks the DOFs in joint layout exactly as
-// trs_rs_modal does (spectrum.hip).  trs_hr_sweep stages the p mode shapes and the case's u_res in LDS in joint layout,
-// as trs_rs_combine stages its vectors; its hot loop is arithmetic: an item (a member, a joint's three components)
+// Both are one work-group of 256 threads per (truss, case).  The walk over the DOFs and its reduction, the stage of the
+// p mode shapes and the case's u_res in LDS in joint layout, the member and the end forces of a joint are the ones of
+// spectrum.hip: trs_modal.h.  The hot loop of trs_hr_sweep is arithmetic: an item (a member, a joint's three components)
 // forms its p + 1 real coefficients ONCE, in registers, and then runs the frequencies against the table
 // c_lk(W_s) = g_lk H_k(W_s) of one chunk of 64 frequencies, built cooperatively in LDS and read by all lanes at the same
 // address (a broadcast): 2 p + 1 fused multiply-adds per item and frequency, and a square root only where |y|^2 sets a
@@ -19,19 +19,15 @@
 // counts that are uniform over the work-group; the barriers around the table sit in those two loops only.
 // No floating-point atomic, every sum in one fixed order.  sweep_chunk is the ONE function that turns coefficients and
 // table into (Re, Im) per frequency: the three passes and the monitors call it, so a monitored value and the envelope
-// at the same index are the same number.  A column of X whose lam contributes nothing is read by neither kernel.
-#include "../../include/trs_harmonic.h"
-#include "../../include/trs_modes.h"
-#include "trs_common.h"
-#include "trs_lds.h"
+// at the same index are the same number.
+#include "trs_modal.h"
 
 namespace {
 
 using namespace trs_rec;
+using namespace trs_modal;
 
-static_assert(TRS_HR_BLOCK == TRS_MODES_BLOCK, "the block of trs_harmonic.h is the one of trs_modes.h");
-static_assert(TRS_HR_MAX_VEC == TRS_HR_MAX_MODES + 1, "the modes and the residual");
-constexpr int MODES = TRS_HR_MAX_MODES, VEC = TRS_HR_MAX_VEC, CHUNK = TRS_HR_CHUNK;
+constexpr int CHUNK = TRS_HR_CHUNK;
 static_assert(MODES == 8 && (CHUNK * MODES) % 256 == 0, "a thread builds the table entries of ONE mode: tid % 8");
 
 // LDS of the sweep kernel
@@ -56,12 +52,6 @@ size_t hr_lds(int nJ_max, int nM_max, int p) {
     return trs_lds::count([&](auto& a) { layout(a, nJ_max, nM_max, p); });
 }
 
-// whether mode k of a truss takes part: k < n_modes and lam positive and finite
-__device__ __forceinline__ bool takes_part(const double* lam, const int k, const int n_modes) {
-    const double l = k < n_modes ? lam[k] : 0.0;
-    return (l > 0.0) & (l < INFINITY);
-}
-
 __global__ __launch_bounds__(256) void trs_hr_modal_kernel(
     const TrsBatch bt, const int L, const double* __restrict__ X_all, const double* __restrict__ lam_all,
     const double* __restrict__ Mf_all, const int* __restrict__ n_mass, const int p, const double* __restrict__ Pr_all,
@@ -70,11 +60,12 @@ __global__ __launch_bounds__(256) void trs_hr_modal_kernel(
     __shared__ double gl[MODES];        // g (0 for a mode that contributes nothing)
     const int b = blockIdx.x, l = blockIdx.y, tid = threadIdx.x;
     const TrussView v = bt.truss(b);
-    const int ld_f = bt.ld_f, ndof = v.ndof;
-    const int n_modes = min(p, max(n_mass[b], 0));
-    const double* Xb = X_all + (size_t)b * TRS_HR_BLOCK * ld_f;
+    const int ld_f = bt.ld_f;
+    const int n_modes = mode_count(n_mass, b, p);
+    const double* Xb = X_all + (size_t)b * BLOCK * ld_f;
     const double* Mf = Mf_all + (size_t)b * ld_f;
-    const double* lam = lam_all + (size_t)b * TRS_HR_BLOCK;
+    const double* lam = lam_all + (size_t)b * BLOCK;
+    const unsigned use = part_mask(lam, n_modes);   // (a column of X outside it is never read into a result)
     const double* Pr = Pr_all != nullptr ? Pr_all + ((size_t)b * L + l) * ld_f : nullptr;
     double acc_g[3] = {0.0, 0.0, 0.0};   // the ground acceleration of the case
     if (ag_all != nullptr) {
@@ -82,46 +73,23 @@ __global__ __launch_bounds__(256) void trs_hr_modal_kernel(
         for (int a = 0; a < 3; ++a) acc_g[a] = ag_all[((size_t)b * L + l) * 3 + a];
     }
 
-    // the modes that contribute: a column of X whose lam is not positive and finite is never read into a result
-    bool use[MODES];
-#pragma unroll
-    for (int k = 0; k < MODES; ++k) use[k] = takes_part(lam, k, n_modes);
-
     // f of DOF d at reduced row `row`: P - Mf iota(ag)
-    auto load_of = [&](const int row, const int axis) {
+    auto load_of = [&](const int row, const int axis, const double m) {
         const double a = axis == 0 ? acc_g[0] : axis == 1 ? acc_g[1] : acc_g[2];
-        return fma(-Mf[row], a, Pr != nullptr ? Pr[row] : 0.0);
+        return fma(-m, a, Pr != nullptr ? Pr[row] : 0.0);
     };
 
-    // ---- g: this thread's DOFs in ascending order
+    // ---- g
     double acc[MODES];
 #pragma unroll
     for (int k = 0; k < MODES; ++k) acc[k] = 0.0;
-    for (int d = tid; d < ndof; d += 256) {
-        const int row = v.row_of(d), axis = d % 3;
-        if (row < 0) continue;
-        const double f = load_of(row, axis);
+    each_dof(v, Mf, Xb, ld_f, use, tid, [&](const int row, const int axis, const double m, const double (&x)[MODES]) {
+        const double f = load_of(row, axis, m);
 #pragma unroll
-        for (int k = 0; k < MODES; ++k) {
-            const double x = use[k] ? Xb[(size_t)k * ld_f + row] : 0.0;
-            acc[k] = fma(f, x, acc[k]);
-        }
-    }
-    // the wave's 64 partials by the butterfly, then the four waves in order
-    auto fold = [](double v) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-        return v;
-    };
-    const int wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-    for (int k = 0; k < MODES; ++k) {
-        const double s = fold(acc[k]);
-        if (lane == 0) part[wave][k] = s;
-    }
-    __syncthreads();
+        for (int k = 0; k < MODES; ++k) acc[k] = fma(f, x[k], acc[k]);
+    });
+    const double s = block_sums(acc, part, tid);
     if (tid < MODES) {
-        const double s = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
         const double gv = takes_part(lam, tid, n_modes) ? s : 0.0;
         gl[tid] = gv;
         if (tid < p) g_all[((size_t)b * L + l) * p + tid] = gv;
@@ -130,64 +98,28 @@ __global__ __launch_bounds__(256) void trs_hr_modal_kernel(
 
     // ---- the residual load: f - Mf (sum_k g_k X_k) into column l; the work-group of case 0 zeroes the columns L .. 15
     if (residual) {
-        double* Fb = F_all + (size_t)b * TRS_HR_BLOCK * ld_f;
+        double* Fb = F_all + (size_t)b * BLOCK * ld_f;
         double* col = Fb + (size_t)l * ld_f;
-        for (int x = tid; x < ld_f; x += 256) col[x] = 0.0;
-        if (l == 0)
-            for (int x = L * ld_f + tid; x < TRS_HR_BLOCK * ld_f; x += 256) Fb[x] = 0.0;
+        zero_columns(Fb, ld_f, l, l + 1, tid);
+        if (l == 0) zero_columns(Fb, ld_f, L, BLOCK, tid);
         __threadfence_block();
-        __syncthreads();   // (the zeros of another thread lie under this thread's entries)
-        for (int d = tid; d < ndof; d += 256) {
-            const int row = v.row_of(d), axis = d % 3;
-            if (row < 0) continue;
-            const double m = Mf[row];
-            double rest = load_of(row, axis);
+        __syncthreads();
+        each_dof(v, Mf, Xb, ld_f, use, tid, [&](const int row, const int axis, const double m, const double (&x)[MODES]) {
+            double rest = load_of(row, axis, m);
 #pragma unroll
-            for (int k = 0; k < MODES; ++k) {
-                const double x = use[k] ? Xb[(size_t)k * ld_f + row] : 0.0;
-                rest = fma(-gl[k], m * x, rest);
-            }
+            for (int k = 0; k < MODES; ++k) rest = fma(-gl[k], m * x[k], rest);
             col[row] = rest;
-        }
+        });
     }
-}
-
-// One member as the passes of the sweep kernel see it (as spectrum.hip's passes see theirs)
-struct HrMember {
-    MemberGeom g;
-    double ea;
-    int2 c;       // end joints, clamped
-    bool live;    // inside the truss and of positive length
-};
-__device__ __forceinline__ HrMember load_member(const TrussView& v, const int m) {
-    HrMember r;
-    r.live = TrussView::below(m, v.members);
-    r.c = int2{0, 0};
-    r.ea = 0.0;
-    r.g.len = 0.0;
-    r.g.c[0] = r.g.c[1] = r.g.c[2] = 0.0;
-    if (r.live) {
-        // an end outside the truss is on no end list: the member then gives zeros to N as it does to R
-        const TrussView::Ends e = v.ends(m);
-        r.c = e.c;
-        r.g = member_geom(v.X, e.c.x, e.c.y);
-        r.ea = v.mem.EA(v.mbase + m);
-        r.live = e.inside & (r.g.len > 0.0);
-    }
-    return r;
 }
 
 // The p + 1 real coefficients of a member force: the axial value of every mode shape, and of u_res in slot 8; zeros for
 // a member that is not live and for the slots p .. 7.  ONE function, so that N, the reactions and the monitors see the
 // same values.
-__device__ __forceinline__ void member_coefficients(const HrTables& t, const HrMember& mb, const int ndof_max,
+__device__ __forceinline__ void member_coefficients(const HrTables& t, const Member& mb, const int ndof_max,
                                                     const int p, double (&y)[VEC]) {
-#pragma unroll
-    for (int k = 0; k < MODES; ++k) {
-        y[k] = 0.0;
-        if (mb.live & (k < p)) y[k] = member_axial(mb.g, mb.ea, t.vec + (size_t)k * ndof_max, mb.c.x, mb.c.y);
-    }
-    y[MODES] = mb.live ? member_axial(mb.g, mb.ea, t.vec + (size_t)p * ndof_max, mb.c.x, mb.c.y) : 0.0;
+    member_axials(t.vec, mb, ndof_max, p, y);
+    y[MODES] = slot_axial(t.vec, mb, ndof_max, p);
 }
 
 // The coefficients of joint j's three displacement components (zeros for a joint that is not `own`)
@@ -320,36 +252,21 @@ __global__ __launch_bounds__(256) void trs_hr_sweep_kernel(
     const int b = blockIdx.x, l = blockIdx.y, tid = threadIdx.x;
     const TrussView v = bt.truss(b);
     const int nJ_max = bt.nJ_max, nM_max = bt.nM_max, ld_f = bt.ld_f, joints = v.joints, ndof_max = v.ndof_max;
-    const int n_modes = min(p, max(n_mass[b], 0));
+    const int n_modes = mode_count(n_mass, b, p);
     trs_lds::Carve lds(sh);
     const HrTables t = layout(lds, nJ_max, nM_max, p);
-    const double* Xb = X_all + (size_t)b * TRS_HR_BLOCK * ld_f;
-    const double* lam = lam_all + (size_t)b * TRS_HR_BLOCK;
-    const double* ures = F_all != nullptr ? F_all + ((size_t)b * TRS_HR_BLOCK + l) * ld_f : nullptr;
+    const double* Xb = X_all + (size_t)b * BLOCK * ld_f;
+    const double* lam = lam_all + (size_t)b * BLOCK;
+    const double* ures = F_all != nullptr ? F_all + ((size_t)b * BLOCK + l) * ld_f : nullptr;
     const size_t row = (size_t)b * L + l;
     const bool want_u = (u_amp != nullptr) | (u_at != nullptr), want_R = (R_amp != nullptr) | (R_at != nullptr);
     const bool want_N = (N_amp != nullptr) | (N_at != nullptr);
 
-    // the modes that take part: a column of X whose lam is not positive and finite is never read
-    unsigned live = 0;
-#pragma unroll
-    for (int k = 0; k < MODES; ++k)
-        if (takes_part(lam, k, n_modes)) live |= 1u << k;
+    const unsigned live = part_mask(lam, n_modes);   // (a column of X outside it is never read)
 
-    // ---- stage: every response vector in joint layout, zero at held DOFs and past the truss's own joints
-    for (int x = tid; x < (p + 1) * ndof_max; x += 256) {
-        const int k = x / ndof_max, d = x - k * ndof_max;
-        const int r = v.row_of(d);
-        double val = 0.0;
-        if (r >= 0) {
-            if (k == p)
-                val = ures != nullptr ? ures[r] : 0.0;
-            else if ((live >> k) & 1u)
-                val = Xb[(size_t)k * ld_f + r];
-        }
-        t.vec[x] = val;
-    }
-    if (tid < MODES) t.g[tid] = (((live >> tid) & 1u) != 0) ? g_all[row * p + tid] : 0.0;
+    // ---- stage: the mode shapes, then the case's u_res
+    stage_vectors(t.vec, v, Xb, ld_f, live, p, p + 1, tid, [&](int, const int r) { return ures != nullptr ? ures[r] : 0.0; });
+    if (tid < MODES) t.g[tid] = in_mask(live, tid) ? g_all[row * p + tid] : 0.0;
     if (want_R) build_end_lists(t, v, tid);
     __syncthreads();
 
@@ -362,7 +279,7 @@ __global__ __launch_bounds__(256) void trs_hr_sweep_kernel(
     sw.tid = tid;
     {
         const int k = tid % MODES;
-        sw.live = ((live >> k) & 1u) != 0;
+        sw.live = in_mask(live, k);
         sw.lam = sw.live ? lam[k] : 1.0;
         const double w = sqrt(sw.lam);
         const double zk = zeta + damp_mass / (2.0 * w) + damp_stiff * w / 2.0;
@@ -379,7 +296,7 @@ __global__ __launch_bounds__(256) void trs_hr_sweep_kernel(
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int m = m0 + 256 * i + tid;
-                const HrMember mb = load_member(v, m < nM_max ? m : -1);
+                const Member mb = load_member(v, m < nM_max ? m : -1);
                 member_coefficients(t, mb, ndof_max, p, y[i]);
                 live[i] = mb.live;
             }
@@ -423,23 +340,15 @@ __global__ __launch_bounds__(256) void trs_hr_sweep_kernel(
             bool held[3];
 #pragma unroll
             for (int a = 0; a < 3; ++a) held[a] = own && v.held(j, a);
+            double acc[VEC][3], y[3][VEC];
             const bool any_held = held[0] | held[1] | held[2];
-            double acc[VEC][3];
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) acc[k][0] = acc[k][1] = acc[k][2] = 0.0;
-            const int* list = t.ends + (any_held ? t.start[j] : 0);
-            const int deg = any_held ? t.cnt[j] : 0;
-            for (int i = 0; i < deg; ++i) {
-                const int m = list[i] >> 1, end = list[i] & 1;
-                const HrMember mb = load_member(v, m);
-                double ax[VEC];
-                member_coefficients(t, mb, ndof_max, p, ax);
-                if (mb.live) {
-#pragma unroll
-                    for (int k = 0; k < VEC; ++k) add_end_force(acc[k], mb.g.c, ax[k], end);
-                }
+            const EndList el = end_list(t, j, any_held, acc);
+            for (int i = 0; i < el.deg; ++i) {
+                const Member mb = load_member(v, el.ends[i] >> 1);
+                double r[VEC];
+                member_coefficients(t, mb, ndof_max, p, r);
+                add_end_forces(acc, mb, r, el.ends[i] & 1);
             }
-            double y[3][VEC];
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
 #pragma unroll
@@ -473,7 +382,7 @@ __global__ __launch_bounds__(256) void trs_hr_sweep_kernel(
         for (int i0 = 0; i0 < Pm; i0 += 256) {
             const int i = i0 + tid;
             const bool mine = i < Pm;
-            const HrMember mb = load_member(v, mine ? mon_member[(size_t)b * Pm + i] : -1);
+            const Member mb = load_member(v, mine ? mon_member[(size_t)b * Pm + i] : -1);
             double y[1][VEC];
             member_coefficients(t, mb, ndof_max, p, y[0]);
             Monitor<1> mon{frf_N + row * S * Pm * 2, Pm, i};

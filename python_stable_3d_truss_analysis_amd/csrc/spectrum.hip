@@ -10,26 +10,22 @@
 // Both are one work-group of 256 threads per truss.  trs_rs_modal walks the DOFs in joint layout (free_index gives the
 // reduced row, d % 3 the axis): a strided partial per thread, a butterfly inside the wave, the four waves in order.
 // trs_rs_combine stages ALL response vectors of the truss in LDS in joint layout (the p mode shapes once, the G
-// missing-mass solutions behind them), as trs_mg_grad stages phi; then
+// missing-mass solutions behind them); then
 //   members   one thread per member, visited once: geometry and E A in registers, the axial value of every mode formed
 //             once and scaled by q per direction - up to nine modal values in registers, compile-time indexed
 //   joints    one thread per joint: u per direction and component; for a joint with a held DOF the thread walks the
 //             joint's member-end list in member-id order (trs_rec::build_end_lists) for R
 // No floating-point atomic, every sum in one fixed order.  member_axials / member_modal and combine are the ONE function
-// each that the member pass, the reaction pass and the base shear share.  A column of X whose lam contributes nothing is
-// read by neither kernel.
-#include "../../include/trs_spectrum.h"
-#include "../../include/trs_modes.h"
-#include "trs_common.h"
-#include "trs_lds.h"
+// each that the member pass, the reaction pass and the base shear share.  The walk over the DOFs, the reduction, the
+// stage, the member and the end forces of a joint are the ones of harmonic.hip: trs_modal.h.
+#include "trs_modal.h"
 
 namespace {
 
 using namespace trs_rec;
+using namespace trs_modal;
 
-static_assert(TRS_RS_BLOCK == TRS_MODES_BLOCK, "the block of trs_spectrum.h is the one of trs_modes.h");
-static_assert(TRS_RS_MAX_VEC == TRS_RS_MAX_MODES + 1, "the modes and the missing-mass slot");
-constexpr int MODES = TRS_RS_MAX_MODES, DIRS = TRS_RS_MAX_DIRS, VEC = TRS_RS_MAX_VEC;
+constexpr int DIRS = TRS_RS_MAX_DIRS;
 
 // LDS of the combine kernel
 struct RsTables : EndLists {   // (the member-end lists of every joint of the truss: trs_recover.h)
@@ -93,6 +89,13 @@ __device__ __forceinline__ double spectrum_at(const double* __restrict__ T, cons
     return fma(t, Sa[i + 1] - Sa[i], Sa[i]);
 }
 
+// Component `axis` of a direction, chosen among the three VALUES (a choice among the three places, inside a callable,
+// is taken for an index at run time, and the directions then live in scratch)
+__device__ __forceinline__ double component(const double (&d)[3], const int axis) {
+    const double x = d[0], y = d[1], z = d[2];
+    return axis == 0 ? x : axis == 1 ? y : z;
+}
+
 __global__ __launch_bounds__(256) void trs_rs_modal_kernel(
     const TrsBatch bt, const double* __restrict__ X_all, const double* __restrict__ lam_all,
     const double* __restrict__ Mf_all, const int* __restrict__ n_mass, const int p, const int G,
@@ -100,7 +103,7 @@ __global__ __launch_bounds__(256) void trs_rs_modal_kernel(
     const double* __restrict__ zpa, const double zeta, const int rule, const int missing, double* __restrict__ gamma,
     double* __restrict__ sa_out, double* __restrict__ meff, double* __restrict__ mtot, double* __restrict__ base,
     double* __restrict__ q, double* __restrict__ rho, double* __restrict__ F_all) {
-    constexpr int NSUM = DIRS * MODES + DIRS;
+    constexpr int NSUM = DIRS * MODES + DIRS;   // Gamma of (g, k) at g * 8 + k, mtot of g behind them
     __shared__ double part[4][NSUM];          // the four waves' sums
     __shared__ double gam[DIRS][MODES];       // Gamma (0 for a mode that contributes nothing)
     __shared__ double mt[DIRS];               // mtot
@@ -109,11 +112,12 @@ __global__ __launch_bounds__(256) void trs_rs_modal_kernel(
     __shared__ double rh[MODES * MODES];
     const int b = blockIdx.x, tid = threadIdx.x;
     const TrussView v = bt.truss(b);
-    const int ld_f = bt.ld_f, ndof = v.ndof;
-    const int n_modes = min(p, max(n_mass[b], 0));
-    const double* Xb = X_all + (size_t)b * TRS_RS_BLOCK * ld_f;
+    const int ld_f = bt.ld_f;
+    const int n_modes = mode_count(n_mass, b, p);
+    const double* Xb = X_all + (size_t)b * BLOCK * ld_f;
     const double* Mf = Mf_all + (size_t)b * ld_f;
-    const double* lam = lam_all + (size_t)b * TRS_RS_BLOCK;
+    const double* lam = lam_all + (size_t)b * BLOCK;
+    const unsigned use = part_mask(lam, n_modes);   // (a column of X outside it is never read into a result)
 
     double dir[DIRS][3];
 #pragma unroll
@@ -122,58 +126,22 @@ __global__ __launch_bounds__(256) void trs_rs_modal_kernel(
         for (int a = 0; a < 3; ++a) dir[g][a] = g < G ? dirs[3 * g + a] : 0.0;
     }
 
-    // the modes that contribute: a column of X whose lam is not positive and finite is never read into a result
-    bool use[MODES];
+    // ---- Gamma and mtot
+    double acc[NSUM];
 #pragma unroll
-    for (int k = 0; k < MODES; ++k) {
-        const double l = k < n_modes ? lam[k] : 0.0;
-        use[k] = (l > 0.0) & (l < INFINITY);
-    }
-
-    // ---- Gamma and mtot: this thread's DOFs in ascending order
-    double acc[DIRS][MODES], am[DIRS];
-#pragma unroll
-    for (int g = 0; g < DIRS; ++g) {
-        am[g] = 0.0;
-#pragma unroll
-        for (int k = 0; k < MODES; ++k) acc[g][k] = 0.0;
-    }
-    for (int d = tid; d < ndof; d += 256) {
-        const int row = v.row_of(d), axis = d % 3;
-        if (row < 0) continue;
-        const double m = Mf[row];
-        double x[MODES];
-#pragma unroll
-        for (int k = 0; k < MODES; ++k) x[k] = use[k] ? Xb[(size_t)k * ld_f + row] : 0.0;
+    for (int i = 0; i < NSUM; ++i) acc[i] = 0.0;
+    each_dof(v, Mf, Xb, ld_f, use, tid, [&](const int row, const int axis, const double m, const double (&x)[MODES]) {
 #pragma unroll
         for (int g = 0; g < DIRS; ++g) {
-            const double io = axis == 0 ? dir[g][0] : axis == 1 ? dir[g][1] : dir[g][2];
+            const double io = component(dir[g], axis);
             const double mi = m * io;
-            am[g] = fma(mi, io, am[g]);
+            acc[DIRS * MODES + g] = fma(mi, io, acc[DIRS * MODES + g]);
 #pragma unroll
-            for (int k = 0; k < MODES; ++k) acc[g][k] = fma(mi, x[k], acc[g][k]);
+            for (int k = 0; k < MODES; ++k) acc[g * MODES + k] = fma(mi, x[k], acc[g * MODES + k]);
         }
-    }
-    // the wave's 64 partials by the butterfly, then the four waves in order
-    auto fold = [](double v) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-        return v;
-    };
-    const int wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-    for (int g = 0; g < DIRS; ++g) {
-#pragma unroll
-        for (int k = 0; k < MODES; ++k) {
-            const double s = fold(acc[g][k]);
-            if (lane == 0) part[wave][g * MODES + k] = s;
-        }
-        const double s = fold(am[g]);
-        if (lane == 0) part[wave][DIRS * MODES + g] = s;
-    }
-    __syncthreads();
+    });
+    const double s = block_sums(acc, part, tid);
     if (tid < NSUM) {
-        const double s = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
         if (tid < DIRS * MODES)
             gam[tid / MODES][tid % MODES] = s;
         else
@@ -184,9 +152,8 @@ __global__ __launch_bounds__(256) void trs_rs_modal_kernel(
     // ---- per (direction, mode): the ordinate, the amplitude, the effective mass
     if (tid < DIRS * MODES) {
         const int g = tid / MODES, k = tid % MODES;
-        const double l = k < n_modes ? lam[k] : 0.0;
-        const bool good = (l > 0.0) & (l < INFINITY);   // the mode contributes (use[k])
-        const bool live = (g < G) & good;
+        const double l = lam[k];
+        const bool good = takes_part(lam, k, n_modes), live = (g < G) & good;
         double ga = 0.0, s = 0.0, qv = 0.0, me = 0.0, w = 0.0;
         if (live) {
             ga = gam[g][k];
@@ -230,74 +197,33 @@ __global__ __launch_bounds__(256) void trs_rs_modal_kernel(
 
     // ---- missing mass: f_g = zpa_g Mf (iota_g - sum_k Gamma_kg X_k) into column g, zeros everywhere else
     if (missing) {
-        double* Fb = F_all + (size_t)b * TRS_RS_BLOCK * ld_f;
-        for (int x = tid; x < TRS_RS_BLOCK * ld_f; x += 256) Fb[x] = 0.0;
+        double* Fb = F_all + (size_t)b * BLOCK * ld_f;
+        zero_columns(Fb, ld_f, 0, BLOCK, tid);
         __threadfence_block();
-        __syncthreads();   // (the zeros of another thread lie under this thread's entries)
-        for (int d = tid; d < ndof; d += 256) {
-            const int row = v.row_of(d), axis = d % 3;
-            if (row < 0) continue;
-            const double m = Mf[row];
-            double x[MODES];
-#pragma unroll
-            for (int k = 0; k < MODES; ++k) x[k] = use[k] ? Xb[(size_t)k * ld_f + row] : 0.0;
+        __syncthreads();
+        each_dof(v, Mf, Xb, ld_f, use, tid, [&](const int row, const int axis, const double m, const double (&x)[MODES]) {
 #pragma unroll
             for (int g = 0; g < DIRS; ++g) {
                 if (g >= G) continue;
-                double rest = axis == 0 ? dir[g][0] : axis == 1 ? dir[g][1] : dir[g][2];
+                double rest = component(dir[g], axis);
 #pragma unroll
                 for (int k = 0; k < MODES; ++k) rest = fma(-gam[g][k], x[k], rest);
                 Fb[(size_t)g * ld_f + row] = zpa[g] * (m * rest);
             }
-        }
-    }
-}
-
-// One member as the passes of the combine kernel see it
-struct RsMember {
-    MemberGeom g;
-    double ea;
-    int2 c;       // end joints, clamped
-    bool live;    // inside the truss and of positive length
-};
-__device__ __forceinline__ RsMember load_member(const TrussView& v, const int m) {
-    RsMember r;
-    r.live = m < v.members;
-    r.c = int2{0, 0};
-    r.ea = 0.0;
-    r.g.len = 0.0;
-    r.g.c[0] = r.g.c[1] = r.g.c[2] = 0.0;
-    if (r.live) {
-        // an end outside the truss is on no end list: the member then gives zeros to N as it does to R
-        const TrussView::Ends e = v.ends(m);
-        r.c = e.c;
-        r.g = member_geom(v.X, e.c.x, e.c.y);
-        r.ea = v.mem.EA(v.mbase + m);
-        r.live = e.inside & (r.g.len > 0.0);
-    }
-    return r;
-}
-
-// The axial value of every mode shape in a member (no direction in it: q carries that); zeros for a member that is not live
-__device__ __forceinline__ void member_axials(const RsTables& t, const RsMember& mb, const int ndof_max, const int p,
-                                              double (&ax)[MODES]) {
-#pragma unroll
-    for (int k = 0; k < MODES; ++k) {
-        ax[k] = 0.0;
-        if (mb.live & (k < p)) ax[k] = member_axial(mb.g, mb.ea, t.vec + (size_t)k * ndof_max, mb.c.x, mb.c.y);
+        });
     }
 }
 
 // The signed modal member forces of direction g: slot k < p the mode's axial value scaled by q_gk, slot 8 the axial
-// value of the missing-mass solution; zeros for a member that is not live.  ONE function (on member_axials' values), so
+// value of the missing-mass solution; zeros for a member that is not live.  ONE function (on member_axials' values: the
+// axial value of every mode shape, no direction in it), so
 // that N, modal_N and the reactions see the same values.
-__device__ __forceinline__ void member_modal(const RsTables& t, const RsMember& mb, const double (&ax)[MODES],
+__device__ __forceinline__ void member_modal(const RsTables& t, const Member& mb, const double (&ax)[MODES],
                                              const int ndof_max, const int p, const int g, const bool missing,
                                              double (&r)[VEC]) {
 #pragma unroll
     for (int k = 0; k < MODES; ++k) r[k] = t.q[g * MODES + k] * ax[k];
-    r[MODES] = 0.0;
-    if (mb.live & missing) r[MODES] = member_axial(mb.g, mb.ea, t.vec + (size_t)(p + g) * ndof_max, mb.c.x, mb.c.y);
+    r[MODES] = missing ? slot_axial(t.vec, mb, ndof_max, p + g) : 0.0;
 }
 
 __global__ __launch_bounds__(256) void trs_rs_combine_kernel(
@@ -309,38 +235,28 @@ __global__ __launch_bounds__(256) void trs_rs_combine_kernel(
     const int b = blockIdx.x, tid = threadIdx.x;
     const TrussView v = bt.truss(b);
     const int nJ_max = bt.nJ_max, nM_max = bt.nM_max, ld_f = bt.ld_f, joints = v.joints, ndof_max = v.ndof_max;
-    const int n_modes = min(p, max(n_mass[b], 0));
+    const int n_modes = mode_count(n_mass, b, p);
     const bool missing = missing_in != 0;
     const int nvec = p + (missing ? G : 0), V = p + 1;
     trs_lds::Carve lds(sh);
     const RsTables t = layout(lds, nJ_max, nM_max, nvec);
-    const double* Xb = X_all + (size_t)b * TRS_RS_BLOCK * ld_f;
-    const double* Fb = missing ? F_all + (size_t)b * TRS_RS_BLOCK * ld_f : nullptr;
+    const double* Xb = X_all + (size_t)b * BLOCK * ld_f;
+    const double* Fb = missing ? F_all + (size_t)b * BLOCK * ld_f : nullptr;
     const bool want_R = (R != nullptr) | (modal_R != nullptr);
 
-    // the modes that contribute (rho_kk != 0): a column of X whose lam is not positive and finite is never read
+    // the modes that take part, from rho_kk != 0 (lam is not handed to this kernel): trs_rs_modal wrote 1 there for
+    // exactly the modes of part_mask, 0 for the others - the same set
     unsigned live = 0;
 #pragma unroll
     for (int k = 0; k < MODES; ++k)
         if ((k < n_modes) && rho_all[(size_t)b * MODES * MODES + k * (MODES + 1)] != 0.0) live |= 1u << k;
 
-    // ---- stage: every response vector in joint layout, zero at held DOFs and past the truss's own joints
-    for (int x = tid; x < nvec * ndof_max; x += 256) {
-        const int k = x / ndof_max, d = x - k * ndof_max;
-        const int row = v.row_of(d);
-        double val = 0.0;
-        if (row >= 0) {
-            if (k >= p)
-                val = Fb[(size_t)(k - p) * ld_f + row];
-            else if ((live >> k) & 1u)
-                val = Xb[(size_t)k * ld_f + row];
-        }
-        t.vec[x] = val;
-    }
+    // ---- stage: the mode shapes, then direction g's missing-mass solution
+    stage_vectors(t.vec, v, Xb, ld_f, live, p, nvec, tid, [&](const int g, const int row) { return Fb[(size_t)g * ld_f + row]; });
     if (tid < MODES * MODES) t.rho[tid] = rho_all[(size_t)b * MODES * MODES + tid];
     if (tid < DIRS * MODES) {
         const int g = tid / MODES, k = tid % MODES;
-        t.q[tid] = ((g < G) & (((live >> k) & 1u) != 0)) ? q_all[((size_t)b * G + g) * p + k] : 0.0;
+        t.q[tid] = ((g < G) & in_mask(live, k)) ? q_all[((size_t)b * G + g) * p + k] : 0.0;
     }
     if (want_R) build_end_lists(t, v, tid);
     __syncthreads();
@@ -348,9 +264,9 @@ __global__ __launch_bounds__(256) void trs_rs_combine_kernel(
     // ---- members: N and modal_N, every member once
     if ((N != nullptr) | (modal_N != nullptr))
         for (int m = tid; m < nM_max; m += 256) {
-            const RsMember mb = load_member(v, m);
+            const Member mb = load_member(v, m);
             double ax[MODES];
-            member_axials(t, mb, ndof_max, p, ax);   // (once: the directions share them)
+            member_axials(t.vec, mb, ndof_max, p, ax);   // (once: the directions share them)
             for (int g = 0; g < G; ++g) {
                 double r[VEC];
                 member_modal(t, mb, ax, ndof_max, p, g, missing, r);
@@ -373,7 +289,6 @@ __global__ __launch_bounds__(256) void trs_rs_combine_kernel(
             bool held[3];
 #pragma unroll
             for (int a = 0; a < 3; ++a) held[a] = own & v.held(j, a);
-            const bool any_held = held[0] | held[1] | held[2];
             for (int g = 0; g < G; ++g) {
                 const size_t row = (size_t)b * G + g;
                 if ((u != nullptr) | (modal_u != nullptr)) {
@@ -395,20 +310,13 @@ __global__ __launch_bounds__(256) void trs_rs_combine_kernel(
                 }
                 if (want_R) {
                     double acc[VEC][3];
-#pragma unroll
-                    for (int k = 0; k < VEC; ++k) acc[k][0] = acc[k][1] = acc[k][2] = 0.0;
-                    const int* list = t.ends + (any_held ? t.start[j] : 0);
-                    const int deg = any_held ? t.cnt[j] : 0;
-                    for (int i = 0; i < deg; ++i) {
-                        const int m = list[i] >> 1, end = list[i] & 1;
-                        const RsMember mb = load_member(v, m);
+                    const EndList l = end_list(t, j, held[0] | held[1] | held[2], acc);
+                    for (int i = 0; i < l.deg; ++i) {
+                        const Member mb = load_member(v, l.ends[i] >> 1);
                         double ax[MODES], r[VEC];
-                        member_axials(t, mb, ndof_max, p, ax);
+                        member_axials(t.vec, mb, ndof_max, p, ax);
                         member_modal(t, mb, ax, ndof_max, p, g, missing, r);
-                        if (mb.live) {
-#pragma unroll
-                            for (int k = 0; k < VEC; ++k) add_end_force(acc[k], mb.g.c, r[k], end);
-                        }
+                        add_end_forces(acc, mb, r, l.ends[i] & 1);
                     }
 #pragma unroll
                     for (int a = 0; a < 3; ++a) {

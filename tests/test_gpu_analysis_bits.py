@@ -1,5 +1,6 @@
 """The resident-factor analyses (`solve_load_cases`, `solve_effect_cases`, `solve_gradients`, `solve_modes`,
-`solve_buckling`, `solve_transient`, `solve_nonlinear`, `solve_mode_gradients`, `solve_response_spectrum` and the three on the columns
+`solve_buckling`, `solve_transient`, `solve_nonlinear`, `solve_mode_gradients`, `solve_response_spectrum`, `solve_harmonic` and the
+three on the columns
 inv(K_ff) b_e: `solve_member_loss`, `solve_member_sets`, `solve_influence`) give the SAME BITS as the
 build that recorded `tests/golden/analysis_bits.json`: SHA-256 digests of every field (that is not None) of the result
 dataclasses, for both member forms and with and without a joint order.  The kernels use no floating-point
@@ -29,7 +30,7 @@ L, P = 17, 3   # two case groups of the substitution (16 + 1); three modes
 CONFIGS = {"general": dict(table=False, reorder=False), "general-profile": dict(table=False, reorder="profile"),
            "table": dict(table=True, reorder=False), "table-profile": dict(table=True, reorder="profile")}
 ANALYSES = ("load_cases", "effect_cases", "gradients", "modes", "buckling", "member_loss", "member_sets", "influence",
-            "transient", "nonlinear", "mode_gradients", "response_spectrum")
+            "transient", "nonlinear", "mode_gradients", "response_spectrum", "harmonic")
 # the transient response: two excitations (the first two load cases as patterns), five Newmark steps, stiffness
 # damping (so the end lists of the members are built), two monitored joints and two monitored members (first and last)
 L_DYN, STEPS, DT, DAMP_STIFF = 2, 5, 1e-3, 1e-4
@@ -45,6 +46,9 @@ L_COL, CHUNK, S_SETS, P_PATH = 9, 48, 40, 12
 # the response spectrum: two ground directions (x and y: the 2D trusses have no z) and a five-point table of periods
 RS_DIRS = [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]
 RS_PERIODS = [0.0, 0.02, 0.1, 0.5, 2.0]
+# the harmonic response: two cases (the first two load cases as patterns, the first two accelerations as ground motion)
+# over 70 forcing frequencies - two chunks of the sweep's table of 64, the second partial - with all three dampings
+L_HR, HR_OMEGAS, HR_DAMPING = 2, np.linspace(0.0, 2000.0, 70), dict(damping=0.02, damp_mass=0.5, damp_stiff=1e-5)
 SMALL = 6   # the trusses before bar-942: one bucket, where the results per member pair and per scenario are small
 TRAIN = [(1.0, 0.0), (2.0, 30.0), (1.5, 75.0)]
 
@@ -161,9 +165,26 @@ def run(analysis, packed, x, reorder):
                 "weighted": batch.solve_mode_gradients(packed, p=P, weights=x["weights"], joint_mass=x["joint_mass"],
                                                        reorder=reorder)}
     if analysis == "response_spectrum":
+        # CQC with the missing mass and the modal values; the absolute sum without either (the other branch of the
+        # combination, and no response vector behind the p mode shapes)
         return {"spectrum": batch.solve_response_spectrum(packed, RS_DIRS, RS_PERIODS, spectrum_table(), p=P, rule="cqc",
                                                           missing_mass=True, want_modal=True,
-                                                          joint_mass=x["joint_mass"], reorder=reorder)}
+                                                          joint_mass=x["joint_mass"], reorder=reorder),
+                "abs": batch.solve_response_spectrum(packed, RS_DIRS, RS_PERIODS, spectrum_table(), p=P, rule="abs",
+                                                     missing_mass=False, want_modal=False, joint_mass=x["joint_mass"],
+                                                     reorder=reorder)}
+    if analysis == "harmonic":
+        # "full": patterns and ground accelerations together, the static correction, the first and last joint and member
+        # monitored; "bare": ground accelerations alone, no correction, no monitors (no pattern, no residual block and no
+        # monitor arrays reach the kernels)
+        last = lambda counts: np.stack([np.zeros(packed.B, dtype=np.int64), np.asarray(counts).reshape(-1) - 1], axis=1)
+        accel = x["accel"][:, :L_HR]
+        return {"full": batch.solve_harmonic(packed, HR_OMEGAS, pattern=x["loads"][:, :L_HR], accel=accel, p=P,
+                                             residual=True, monitor_joints=last(packed.nJ),
+                                             monitor_members=last(packed.nM), joint_mass=x["joint_mass"],
+                                             reorder=reorder, **HR_DAMPING),
+                "bare": batch.solve_harmonic(packed, HR_OMEGAS, accel=accel, p=P, residual=False,
+                                             joint_mass=x["joint_mass"], reorder=reorder, **HR_DAMPING)}
     return {"modes": batch.solve_modes(packed, p=P, joint_mass=x["joint_mass"], reorder=reorder)}
 
 
@@ -222,6 +243,7 @@ def test_the_batch_exercises_every_fold():
     assert (held.any(axis=2) & ~held.all(axis=2))[0, :packed.nJ[0]].any() and packed.dim.reshape(-1)[0] == 3
     assert packed_batch(True).is_table and not packed.is_table
     assert L > 16 and L % 16 != 0
+    assert 64 < HR_OMEGAS.size < 128 and 1 < L_HR <= L   # (two chunks of the sweep's table of 64, the second partial)
     # the column analyses: more cases than one pass of the apply kernels holds, a partial last chunk of members and a
     # partial last slice of scenarios in every bucket, several ranges of scenarios, every set size, a valid path
     assert 8 < L_COL < 16 and S_SETS > 32 and S_SETS % 32 != 0 and CHUNK % 16 == 0
