@@ -42,7 +42,8 @@ __all__ = ["Truss", "Member", "MemberType", "SupportType", "MetapathType", "Task
            "solve_effect_cases", "EffectCaseResult", "LoadCase",
            "solve_member_loss", "MemberLossResult", "solve_influence", "InfluenceResult",
            "solve_member_sets", "MemberSetResult", "solve_transient", "TransientResult",
-           "solve_nonlinear", "NonlinearResult", "solve_buckling", "BucklingResult"]
+           "solve_nonlinear", "NonlinearResult", "solve_buckling", "BucklingResult",
+           "solve_sizing", "SizingResult"]
 
 
 def __getattr__(name):
@@ -53,7 +54,7 @@ def __getattr__(name):
                 "InfluenceResult", "solve_member_sets", "MemberSetResult", "solve_transient", "TransientResult",
                 "solve_nonlinear", "NonlinearResult", "solve_buckling", "BucklingResult", "solve_mode_gradients",
                 "ModeGradientResult", "solve_response_spectrum", "SpectrumResult", "solve_harmonic",
-                "HarmonicResult"):
+                "HarmonicResult", "solve_sizing", "SizingResult"):
         from . import batch
         return getattr(batch, name)
     if name == "DifferentiableTruss":

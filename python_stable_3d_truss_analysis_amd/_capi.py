@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h`, `include/trs_influence.h`, `include/trs_sets.h`, `include/trs_dynamics.h`, `include/trs_nonlinear.h`, `include/trs_buckling.h`, `include/trs_modegrad.h`, `include/trs_spectrum.h` and `include/trs_harmonic.h` (library: `libtrs_hip.so`, in-tree).
+"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h`, `include/trs_influence.h`, `include/trs_sets.h`, `include/trs_dynamics.h`, `include/trs_nonlinear.h`, `include/trs_buckling.h`, `include/trs_modegrad.h`, `include/trs_spectrum.h`, `include/trs_harmonic.h` and `include/trs_sizing.h` (library: `libtrs_hip.so`, in-tree).
 
 There is no fallback: if the library is missing, `load()` raises `HipExtensionError`.
 """
@@ -212,6 +212,16 @@ HR_SIGNATURES = {
                               _D, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P]),
 }
 
+#: every symbol `include/trs_sizing.h` declares (member sizing: fully stressed design iterated on the device;
+#: csrc/sizing.hip, the same library).  General member form only: the step writes areas, which a type table cannot hold
+SZ_SIGNATURES = {
+    "trs_sz_abi_version": (_I, []),
+    "trs_sz_fits": (_I, [_I, _I]),
+    "trs_sz_step": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _D, _D, _D, _P, _D, _D, _D, _P, _D,
+                         _P, _D, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "trs_sz_snap": (_I, [_I, _I, _P, _P, _P, _I, _P, _P, _P]),
+}
+
 #: must equal TRS_ABI_VERSION of include/trs_solver.h
 ABI_VERSION = 10
 #: must equal TRS_MODES_ABI_VERSION of include/trs_modes.h
@@ -236,10 +246,15 @@ MG_ABI_VERSION = 1
 RS_ABI_VERSION = 1
 #: must equal TRS_HR_ABI_VERSION of include/trs_harmonic.h
 HR_ABI_VERSION = 1
+#: must equal TRS_SZ_ABI_VERSION of include/trs_sizing.h
+SZ_ABI_VERSION = 1
 #: TRS_RS_SRSS, TRS_RS_CQC, TRS_RS_ABS of include/trs_spectrum.h: the modal combination rules
 RS_RULES = {"srss": 0, "cqc": 1, "abs": 2}
 #: TRS_NL_* of include/trs_nonlinear.h: the status of a truss in a load step of the nonlinear analysis
 NL_ACTIVE, NL_CONVERGED, NL_ITER_LIMIT, NL_NOT_PD, NL_NOT_ATTEMPTED = -1, 0, 1, 2, 3
+#: TRS_SZ_* of include/trs_sizing.h: the status of a truss in a sizing run, and the catalogue's size limit
+SZ_ACTIVE, SZ_CONVERGED, SZ_ITER_LIMIT, SZ_NOT_PD = -1, 0, 1, 2
+SZ_MAX_CATALOG = 256
 #: TRS_SETS_MAX of include/trs_sets.h: members per scenario at most
 SETS_MAX = 8
 #: TRS_MODES_BLOCK of include/trs_modes.h: vectors per truss of the block iteration (one case group)
@@ -289,7 +304,7 @@ def load():
         raise HipExtensionError(f"cannot load {LIB_PATH}: {exc}") from exc
     for table in (SIGNATURES, MODES_SIGNATURES, EFFECTS_SIGNATURES, LOSS_SIGNATURES, INFLUENCE_SIGNATURES,
                   SETS_SIGNATURES, DYN_SIGNATURES, NL_SIGNATURES, BK_SIGNATURES, MG_SIGNATURES, RS_SIGNATURES,
-                  HR_SIGNATURES):
+                  HR_SIGNATURES, SZ_SIGNATURES):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype = restype
@@ -300,7 +315,7 @@ def load():
             or lib.trs_sets_abi_version() != SETS_ABI_VERSION or lib.trs_dyn_abi_version() != DYN_ABI_VERSION \
             or lib.trs_nl_abi_version() != NL_ABI_VERSION or lib.trs_bk_abi_version() != BK_ABI_VERSION \
             or lib.trs_mg_abi_version() != MG_ABI_VERSION or lib.trs_rs_abi_version() != RS_ABI_VERSION \
-            or lib.trs_hr_abi_version() != HR_ABI_VERSION:
+            or lib.trs_hr_abi_version() != HR_ABI_VERSION or lib.trs_sz_abi_version() != SZ_ABI_VERSION:
         raise HipExtensionError("libtrs_hip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -616,6 +616,85 @@ def _check_newton_args(who, load_factors, tol=1e-9, max_iters=25, check_every=1)
     return lams
 
 
+def _check_sizing_scalars(who, allow_tension, allow_compression, allow_displace=0.0, euler_kappa=0.0, relax=1.0, tol=1e-4,
+                          max_iters=40, check_every=1, catalog=None, B=None):
+    """The scalar arguments of the member sizing (ValueError): the two allowables finite and positive, `allow_displace`,
+    `euler_kappa` and `tol` finite and >= 0, `relax` in (0, 1], `max_iters` an integer >= 0, `check_every` an integer
+    >= 1, `catalog` (or None) 1 to 256 finite positive areas in strictly ascending order.  With `B` each of the three
+    allowables may also be one value per truss (an array [B], numpy or torch).  Returns them as a dict of floats and
+    ints, an allowable per truss and the catalogue as float64 arrays (or None)."""
+    def number(name, x):
+        if B is not None and name.startswith("allow_") and (np.ndim(x) == 1 or hasattr(x, "detach")):
+            try:
+                arr = np.array(_host_array(x, np.float64), dtype=np.float64)
+            except (TypeError, ValueError):
+                arr = None
+            if arr is None or arr.shape != (B,) or not np.isfinite(arr).all():
+                raise ValueError(f"{who}: {name} must be a finite number or {B} finite numbers, one per truss")
+            return arr
+        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x):
+            raise ValueError(f"{who}: {name} must be a finite number, got {x!r}")
+        return float(x)
+    val = {}
+    for name, x in (("allow_tension", allow_tension), ("allow_compression", allow_compression)):
+        val[name] = number(name, x)
+        if not np.all(val[name] > 0):
+            raise ValueError(f"{who}: {name} must be positive, got {x!r}")
+    for name, x in (("allow_displace", allow_displace), ("euler_kappa", euler_kappa), ("tol", tol)):
+        val[name] = number(name, x)
+        if np.any(val[name] < 0):
+            raise ValueError(f"{who}: {name} must be >= 0, got {x!r}")
+    val["relax"] = number("relax", relax)
+    if not 0 < val["relax"] <= 1:
+        raise ValueError(f"{who}: relax must lie in (0, 1], got {relax!r}")
+    for name, x, least in (("max_iters", max_iters, 0), ("check_every", check_every, 1)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < least:
+            raise ValueError(f"{who}: {name} must be an integer of at least {least}, got {x!r}")
+        val[name] = int(x)
+    val["catalog"] = None
+    if catalog is not None:
+        try:
+            cat = np.array(_host_array(catalog, np.float64), dtype=np.float64)
+        except (TypeError, ValueError):
+            cat = None
+        if cat is None or cat.ndim != 1 or not 1 <= cat.size <= _capi.SZ_MAX_CATALOG or not np.isfinite(cat).all() \
+                or not (cat > 0).all() or not (np.diff(cat) > 0).all():
+            raise ValueError(f"{who}: catalog must hold 1 to {_capi.SZ_MAX_CATALOG} finite positive areas in strictly "
+                             f"ascending order, got {catalog!r}")
+        val["catalog"] = cat
+    return val
+
+
+def _check_area_bounds(who, area_min, area_max, B, nM, nM_max):
+    """`area_min` / `area_max` of the member sizing: each a scalar or an array [B, nM_max] (numpy or torch), finite, with
+    area_min > 0 and area_max >= area_min on every live member (`nM` [B]: the member counts on the host, or None when
+    they are not at hand - then every entry is checked).  Returns ((scalar or None, array or None), the same for max)."""
+    out = []
+    for name, x in (("area_min", area_min), ("area_max", area_max)):
+        if x is None:
+            raise ValueError(f"{who}: {name} must be given: a scalar or an array [B, nM_max]")
+        if np.ndim(x) == 0 and not hasattr(x, "detach"):
+            if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x):
+                raise ValueError(f"{who}: {name} must be a finite number or an array [B, nM_max], got {x!r}")
+            out.append((float(x), None))
+            continue
+        try:
+            arr = _host_array(x, np.float64)
+        except (TypeError, ValueError):
+            arr = None
+        if arr is None or arr.shape != (B, nM_max) or not np.isfinite(arr).all():
+            raise ValueError(f"{who}: {name} must be a finite number or a finite array [B={B}, nM_max={nM_max}]")
+        out.append((None, arr))
+    live = np.ones([B, nM_max], dtype=bool) if nM is None else np.arange(nM_max)[None, :] < np.asarray(nM)[:, None]
+    lo = np.broadcast_to(out[0][0] if out[0][1] is None else out[0][1], [B, nM_max])
+    hi = np.broadcast_to(out[1][0] if out[1][1] is None else out[1][1], [B, nM_max])
+    if not (lo[live] > 0).all():
+        raise ValueError(f"{who}: area_min must be positive on every member")
+    if not (hi[live] >= lo[live]).all():
+        raise ValueError(f"{who}: area_max must be >= area_min on every member")
+    return tuple(out)
+
+
 def _check_mass_args(who, B, nJ_max, joint_mass_shape, mass_scale, joint_mass_min=None):
     """The mass arguments that the transient analysis shares with `modes` (`_check_mode_args`), refused in `who`'s name."""
     try:
@@ -1998,6 +2077,153 @@ class DeviceBatch:
             self.B, self.nJ_max, self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(),
             self.uf.data_ptr(), self.rows, self.info.data_ptr(), it, ws["U"].data_ptr(), ws["st"].data_ptr(),
             self._stream()), "trs_nl_update")
+
+    # -- member sizing: fully stressed design iterated on the device (include/trs_sizing.h) ------------------------------
+    SIZING_SHAPES = {"areas": (("nM",), "float64"), "weight": ((), "float64"), "utilisation": (("nM",), "float64"),
+                     "governing": (("nM",), "int32"), "disp_ratio": ((), "float64"), "iterations": ((), "int32"),
+                     "status": ((), "int32"), "weight_history": (("H",), "float64"), "catalog_index": (("nM",), "uint8")}
+
+    def sizing(self, loads=None, *, allow_tension, allow_compression, allow_displace=0.0, euler_kappa=0.0, area_min,
+               area_max, relax=1.0, tol=1e-4, max_iters=40, check_every=1, catalog=None, out=None):
+        """Member sizing of the resident batch by the stress-ratio method (include/trs_sizing.h: fully stressed design
+        with a displacement envelope): every design is analysed under all L load cases, every member is resized to what
+        its worst case demands - N / `allow_tension` in tension, the larger of P / `allow_compression` and the Euler
+        area sqrt(P L0^2 / (pi^2 E `euler_kappa`)) in compression (I = kappa A^2; 0: no member buckling check), or the
+        displacement ratio max |u_j| / `allow_displace` (0: no limit) where that is larger -, damped by `relax` in
+        (0, 1] and clamped to [`area_min`, `area_max`] (scalars or float64 device tensors [B, nM_max]; equal bounds fix
+        a member), until no area moves by more than `tol` (relative) or `max_iters` resizings are done.  `loads`:
+        float64 device tensor [B, L, nJ_max, 3] as `solve_cases` takes them (None: the batch's own loads as one case).
+        Each of the three allowables is one number for the batch or one per truss (an array [B]).
+        The initial design is the batch's own A.  Per iteration five launches: `trs_assemble`, `trs_potrf_batched`,
+        `trs_gather_cases`, `trs_potrs_cases` and `trs_sz_step`, which reads the L reduced solutions from the case block
+        and writes the next design - neither u nor N of a case goes to HBM.  A converged truss is frozen, as is one whose
+        design cannot be factored (`info != 0`: it goes back to the design before), so a truss's results depend neither
+        on the others nor on `check_every` nor on `max_iters` beyond its own count.  Every `check_every` iterations one
+        int32 - the number of trusses still iterating - is downloaded to stop early.  `catalog` (ascending areas, 1 to
+        256): afterwards every member of a truss of status 0 or 1 goes to the smallest catalogue area >= its area (the
+        largest where there is none) and ONE more analysis rewrites that truss's outputs; status and iterations stay.
+        Returns a dict of device tensors, in the caller's member order: areas, utilisation [B, nM_max] (req / A: stress and
+        member buckling only, <= 1 is feasible), governing (int32 [B, nM_max]: the governing case, -1 where the
+        displacement ratio governs and on the padding), weight, disp_ratio [B], iterations, status (int32 [B]: 0
+        converged, 1 iteration limit, 2 a design could not be factored), weight_history [B, max_iters + 1] (zero beyond
+        the truss's own count) and - with `catalog` - catalog_index (uint8 [B, nM_max]).  `self.info` holds 0, or for a
+        truss of status 2 what the factorisation reported, latched.  Afterwards `self.A` holds the returned areas and
+        the slab the factor of the returned design for every truss of status 0 or 1: `solve_cases`, `solve_effect_cases`
+        and `member_loss` may follow without another `factor()`; `generation` is bumped.  A batch on the fused
+        small-system path, `options["compact"]` and the table member form (the step writes one area per member, which a
+        type table cannot hold: `PackedBatch.general()` first) are refused."""
+        t = self.torch
+        if self.small:
+            raise ValueError("sizing(): this batch takes the fused small-system kernel, which keeps no factor - "
+                             "build the DeviceBatch with use_small=False")
+        if self.options["compact"]:
+            raise ValueError("sizing(): options['compact'] writes no slab that the load cases could be solved against")
+        if self.table:
+            raise ValueError("sizing(): the table member form cannot hold one area per member - use the general form "
+                             "(PackedBatch.general())")
+        val = _check_sizing_scalars("sizing()", allow_tension, allow_compression, allow_displace, euler_kappa, relax, tol,
+                                    max_iters, check_every, catalog, B=self.B)
+        bounds = []
+        for name, x in (("area_min", area_min), ("area_max", area_max)):
+            if hasattr(x, "data_ptr"):
+                if list(x.shape) != [self.B, self.nM_max] or x.dtype != t.float64 or x.device != self.device:
+                    raise ValueError(f"sizing(): {name} must be a number or a float64 [B={self.B}, nM_max={self.nM_max}] "
+                                     f"tensor on {self.device}")
+                bounds.append((x.contiguous(), 0.0))
+            elif isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x):
+                raise ValueError(f"sizing(): {name} must be a finite number or a float64 [B, nM_max] tensor, got {x!r}")
+            else:
+                bounds.append((None, float(x)))
+        if bounds[0][0] is None and not bounds[0][1] > 0:
+            raise ValueError(f"sizing(): area_min must be positive, got {area_min!r}")
+        if bounds[0][0] is None and bounds[1][0] is None and bounds[1][1] < bounds[0][1]:
+            raise ValueError(f"sizing(): area_max must be >= area_min, got {area_max!r} < {area_min!r}")
+        own = loads is None   # (the batch's own loads are already in the batch's joint order: gathered without joint_in)
+        loads = self._check_loads("sizing", self.loads.unsqueeze(1) if own else loads)
+        L, H = int(loads.shape[1]), val["max_iters"] + 1
+        if L < 1:
+            raise ValueError("sizing(): loads must hold at least one case")
+        sizes = {"nM": self.nM_max, "H": H}
+        shapes = {k: ([self.B] + [sizes[n] for n in shape], getattr(t, dtype))
+                  for k, (shape, dtype) in self.SIZING_SHAPES.items() if k != "catalog_index" or val["catalog"] is not None}
+        out = self._out_tensors("sizing", shapes, out)
+        if self.B == 0:
+            return out
+        if not self.lib.trs_sz_fits(self.nJ_max, self.nM_max):
+            raise HipExtensionError(f"sizing(): a truss of {self.nJ_max} joints / {self.nM_max} members exceeds the LDS of "
+                                    "the step kernel (trs_sz_fits)")
+        self._factored = False
+        self._dynamic = None
+        self._forward = None
+        ws = self._sz_workspace(val, bounds, loads, out, own)
+        with t.cuda.device(self.device):
+            self.dofmap()
+            out["weight_history"].zero_()
+            it = 0
+            while True:
+                last = it == val["max_iters"]
+                self._sz_analyse(ws)
+                self._sz_step(ws, it, 1 if last else 0)
+                if last or (it % val["check_every"] == 0 and int(ws["active"][it].item()) == 0):
+                    break
+                it += 1
+            if val["catalog"] is not None:
+                cat = t.from_numpy(val["catalog"]).to(self.device)
+                _capi.check(self.lib.trs_sz_snap(self.B, self.nM_max, self.nM.data_ptr(), ws["st"].data_ptr(), cat.data_ptr(),
+                                                 int(cat.shape[0]), self.A.data_ptr(), out["catalog_index"].data_ptr(),
+                                                 self._stream()), "trs_sz_snap")
+                self._sz_analyse(ws)
+                self._sz_step(ws, it, 2)
+            out["status"].copy_(ws["st"][:, 0])
+            out["iterations"].copy_(ws["st"][:, 1])
+            # (what the factorisation reported for the design that ended a truss with status 2; 0 for every other truss)
+            self.info.copy_(ws["st"][:, 2])
+        self.cases_F = ws["F"]
+        self._factored = True   # (of the returned design, for every truss of status 0 or 1)
+        self._bump_generation()
+        return out
+
+    # the stages of `sizing` (tools/bench_sizing.py times them one by one)
+    def _sz_workspace(self, val, bounds, loads, out, own=False):
+        """The state of a `sizing` run: the design before the last resizing, the status words st [B, 4] and the `active`
+        counters (one per analysis), zeroed; the case block; the arguments (`own`: `loads` are the batch's own, in the
+        batch's joint order); `allow` [B, 3] when an allowable is given per truss."""
+        t, dev = self.torch, self.device
+        L = int(loads.shape[1])
+        names = ("allow_tension", "allow_compression", "allow_displace")
+        allow = None
+        if any(isinstance(val[k], np.ndarray) for k in names):
+            allow = t.from_numpy(np.stack([np.broadcast_to(val[k], [self.B]) for k in names], axis=1).copy()).to(dev)
+            val = dict(val, **{k: float(np.max(val[k])) for k in names})   # (scalars that pass the library's own check)
+        return {"prev": t.zeros([self.B, max(self.nM_max, 1)], dtype=t.float64, device=dev),
+                "st": t.zeros([self.B, 4], dtype=t.int32, device=dev),
+                "active": t.zeros([val["max_iters"] + 1], dtype=t.int32, device=dev),
+                "F": self._case_block("cases_F", L), "L": L, "loads": loads, "own": own, "val": val, "bounds": bounds,
+                "allow": allow, "out": out}
+
+    def _sz_analyse(self, ws):
+        """Assembly and factorisation of the design `self.A`, gather and substitution of the L cases."""
+        jo, stream, _ = self._case_launch()
+        self.assemble()
+        self.potrf()
+        _capi.check(self.lib.trs_gather_cases(self.B, ws["L"], self.nJ_max, ws["loads"].data_ptr(),
+                                              self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(),
+                                              None if ws["own"] else jo,
+                                              ws["F"].data_ptr(), self.rows, stream), "trs_gather_cases")
+        self._potrs_cases(ws["F"], ws["L"])
+
+    def _sz_step(self, ws, it, mode):
+        val, out, (lo, hi) = ws["val"], ws["out"], ws["bounds"]
+        _capi.check(self.lib.trs_sz_step(
+            self.B, ws["L"], self.nJ_max, self.nM_max, self.xyz.data_ptr(), self.conn.data_ptr(), self.E.data_ptr(),
+            self.A.data_ptr(), self.rho.data_ptr(), self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(),
+            self.nM.data_ptr(), ws["F"].data_ptr(), self.rows, self.info.data_ptr(), val["allow_tension"],
+            val["allow_compression"], val["allow_displace"], _ptr(ws["allow"]), val["euler_kappa"], val["relax"],
+            val["tol"], _ptr(lo[0]),
+            lo[1], _ptr(hi[0]), hi[1], it, mode, ws["prev"].data_ptr(), ws["st"].data_ptr(),
+            ws["active"][min(it, val["max_iters"]):].data_ptr(), out["areas"].data_ptr(), out["weight"].data_ptr(),
+            out["utilisation"].data_ptr(), out["governing"].data_ptr(), out["disp_ratio"].data_ptr(),
+            out["weight_history"].data_ptr(), val["max_iters"] + 1, self._stream()), "trs_sz_step")
 
     # -- linear buckling: critical load factors from shifted factors of K + theta Kg (include/trs_buckling.h) ------------
     def buckling(self, p, shift=0.0, max_shifts=6, tol=1e-10, max_iters=256, check_every=4, out=None):
@@ -4363,6 +4589,121 @@ def solve_nonlinear(trusses_or_packed, load_factors=(1.0,), tol=1e-9, max_iters=
     for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope,
                                       factor=lambda db, part: None):
         _put_result(part, out, db.nonlinear(lams, tol=tol, max_iters=max_iters, check_every=check_every))
+    return _finish_result(torch, dev, out, on_device)
+
+
+@dataclass
+class SizingResult:
+    """Results of `solve_sizing`, in the caller's member order, all describing the last design of a truss that could be
+    factored: areas, utilisation [B, nM_max] (required area / area: stress and member buckling only; <= 1 is feasible),
+    governing (int32 [B, nM_max]: the load case whose requirement governs the member, -1 where the displacement ratio
+    does and on the padding), weight [B] (sum of A L rho), disp_ratio [B] (largest joint displacement / allow_displace; 0
+    without a limit), iterations [B] (resizings behind the returned design), status (int32 [B]: 0 converged, 1
+    iteration limit, 2 a design could not be factored - the truss went back to the design before; with iterations 0 its
+    areas are the initial ones and the other results zero), weight_history [B, max_iters + 1] (the weight of every design
+    the truss analysed, zero beyond its own count), catalog_index (uint8 [B, nM_max], or None without a catalogue).
+    info [B]: 0, or what the factorisation reported for the design that ended a truss with status 2."""
+    areas: np.ndarray
+    weight: np.ndarray
+    utilisation: np.ndarray
+    governing: np.ndarray
+    disp_ratio: np.ndarray
+    iterations: np.ndarray
+    status: np.ndarray
+    weight_history: np.ndarray
+    catalog_index: np.ndarray
+    info: np.ndarray
+
+    FIELDS = {"areas": ("areas", 0.0, "float64", ("nM",)), "weight": ("weight", 0.0, "float64", ()),
+              "utilisation": ("utilisation", 0.0, "float64", ("nM",)), "governing": ("governing", -1, "int32", ("nM",)),
+              "disp_ratio": ("disp_ratio", 0.0, "float64", ()), "iterations": ("iterations", 0, "int32", ()),
+              "status": ("status", 0, "int32", ()), "weight_history": ("weight_history", 0.0, "float64", ("H",)),
+              "catalog_index": ("catalog_index", 0, "uint8", ("nM",))}
+
+
+def _check_sizing_args(packed, loads=None, allow_tension=None, allow_compression=None, allow_displace=0.0, euler_kappa=0.0,
+                       area_min=None, area_max=None, relax=1.0, tol=1e-4, max_iters=40, check_every=1, catalog=None,
+                       options=None, sections=None, max_result_bytes=4 << 30):
+    """The argument errors of `solve_sizing` that need no device (ValueError).  Returns the arguments checked: the dict
+    of `_check_sizing_scalars` plus "loads" (a float64 host array [B, L, nJ_max, 3], or None for the batch's own loads)
+    and "area_min" / "area_max" (each a float, or a float64 host array [B, nM_max])."""
+    who = "solve_sizing"
+    if sections is not None:
+        raise ValueError(f"{who}: sections= variants cannot be combined with the member sizing (it writes the sections)")
+    if options and options.get("compact"):
+        raise ValueError(f"{who}: options['compact'] writes no slab that the load cases could be solved against")
+    for name, x in (("allow_tension", allow_tension), ("allow_compression", allow_compression)):
+        if x is None:
+            raise ValueError(f"{who}: {name} must be given")
+    B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
+    val = _check_sizing_scalars(who, allow_tension, allow_compression, allow_displace, euler_kappa, relax, tol, max_iters,
+                                check_every, catalog, B=B)
+    val["loads"] = None
+    if loads is not None:
+        try:
+            x = _host_array(loads, np.float64)
+        except (TypeError, ValueError):
+            x = None
+        shape = None if x is None else tuple(x.shape)
+        if x is None or len(shape) != 4 or shape[0] != B or shape[1] < 1 or shape[2] != nJ_max or shape[3] not in (2, 3):
+            raise ValueError(f"{who}: loads must be [B={B}, L >= 1, nJ_max={nJ_max}, 2 or 3], got {shape}")
+        if not np.isfinite(x).all():
+            raise ValueError(f"{who}: loads must be finite")
+        val["loads"] = np.ascontiguousarray(np.pad(x, [(0, 0)] * 3 + [(0, 3 - shape[3])]))
+    (lo, lo_arr), (hi, hi_arr) = _check_area_bounds(who, area_min, area_max, B, packed.nM, nM_max)
+    val["area_min"], val["area_max"] = (lo if lo_arr is None else lo_arr), (hi if hi_arr is None else hi_arr)
+    live = np.arange(nM_max)[None, :] < np.asarray(packed.nM)[:, None]
+    if B and not (np.asarray(packed.general().A if packed.is_table else packed.A)[live] > 0).all():
+        raise ValueError(f"{who}: the initial design must be positive: every member's area > 0")
+    nbytes = B * (nM_max * (8 + 8 + 4 + 1) + 8 * (val["max_iters"] + 1) + 32)
+    if nbytes > max_result_bytes:
+        raise ValueError(f"{who}: the results of B={B} trusses take {nbytes} bytes, more than max_result_bytes = "
+                         f"{max_result_bytes}")
+    return val
+
+
+def solve_sizing(trusses_or_packed, loads=None, allow_tension=None, allow_compression=None, allow_displace=0.0,
+                 euler_kappa=0.0, area_min=None, area_max=None, relax=1.0, tol=1e-4, max_iters=40, check_every=1,
+                 catalog=None, device=None, reorder=False, options=None, on_device=False, sections=None, use_envelope=True,
+                 max_slab_bytes=64 << 30, max_result_bytes=4 << 30):
+    """Size the members of every truss of a batch by the stress-ratio method - fully stressed design with a displacement
+    envelope (include/trs_sizing.h, `DeviceBatch.sizing`): analyse the design under all load cases, resize every member
+    to what its worst case demands, repeat until the areas stop moving.  `loads`: [B, L, nJ_max, dim] (numpy or torch;
+    the caller's joint numbering; dim 2 or 3) or None for the batch's own loads as one case; `allow_tension`,
+    `allow_compression` (stresses, > 0), `allow_displace` (a joint displacement norm, 0: no limit) - each one number or
+    one per truss, [B] -, `euler_kappa` (the
+    member's second moment of area as I = kappa A^2: 1 / (4 pi) for a solid round bar, 0: no member buckling check);
+    `area_min` > 0 and `area_max` >= `area_min`: scalars or [B, nM_max] (equal bounds fix a member); `relax` in (0, 1]
+    damps the resizing, `tol` is the relative area change at which a truss is converged, `max_iters` the number of
+    resizings at most, `check_every` how often the host looks whether every truss is done; `catalog`: ascending areas
+    (1 to 256) to which the final design is rounded up, followed by one more analysis.  The initial design is the
+    batch's own areas.  What the method is not: where the displacement limit governs, the design is feasible but not
+    weight-optimal (every member is scaled alike), and on redundant trusses the convergence is linear.
+    Every iteration factors its own design (`_factored_buckets` factors nothing ahead).  A table-form batch is converted
+    with `.general()`: the sizing writes one area per member.  Buckets, `reorder` plans, `options`, `on_device` and
+    `use_envelope` as `solve_load_cases`.  Bad arguments (`_check_sizing_args`) raise ValueError before any device work.
+    Returns a `SizingResult`."""
+    packed = _as_packed(trusses_or_packed)
+    val = _check_sizing_args(packed, loads, allow_tension, allow_compression, allow_displace, euler_kappa, area_min,
+                             area_max, relax, tol, max_iters, check_every, catalog, options, sections, max_result_bytes)
+    if packed.is_table:
+        packed = packed.general()
+    torch, dev = _require_gpu(device)
+    out = _new_result(torch, dev, SizingResult, packed.B, {"nM": packed.nM_max, "H": val["max_iters"] + 1},
+                      without=() if val["catalog"] is not None else ("catalog_index",))
+    on = {k: _device_f64(torch, dev, val[k]) if isinstance(val[k], np.ndarray) else val[k]
+          for k in ("loads", "area_min", "area_max")}
+    bound = lambda part, x: part.cut(x, nM=1) if hasattr(x, "data_ptr") else x
+    per_truss = lambda part, x: x[part.index] if isinstance(x, np.ndarray) else x
+    for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope,
+                                      factor=lambda db, part: None):
+        _put_result(part, out, db.sizing(
+            part.cut(on["loads"], nJ=2), allow_tension=per_truss(part, val["allow_tension"]),
+            allow_compression=per_truss(part, val["allow_compression"]),
+            allow_displace=per_truss(part, val["allow_displace"]), euler_kappa=val["euler_kappa"],
+            area_min=bound(part, on["area_min"]),
+            area_max=bound(part, on["area_max"]), relax=val["relax"], tol=val["tol"], max_iters=val["max_iters"],
+            check_every=val["check_every"], catalog=val["catalog"]))
     return _finish_result(torch, dev, out, on_device)
 
 

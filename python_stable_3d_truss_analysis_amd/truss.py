@@ -659,6 +659,55 @@ class Truss:
                 "external": result.external[0, :, :nJ, :dim].copy(), "iterations": result.iterations[0].copy(),
                 "status": result.status[0].copy(), "residual": result.residual[0].copy()}
 
+    def SizeMembers(self, cases=None, allowTension=None, allowCompression=None, allowDisplacement=None, eulerKappa=0.0,
+                    areaMin=None, areaMax=None, relax=1.0, tol=1e-4, maxIters=40, catalog=None):
+        """Size this truss's members by the stress-ratio method - fully stressed design with a displacement envelope
+        (`batch.solve_sizing`): starting from the members' own areas, the design is analysed under all load cases and
+        every member resized to what its worst case demands, until the areas stop moving.  `cases` is a list of
+        `{jointID: vector}` dicts as `SolveLoadCases` takes them (None: the truss's own forces as one case);
+        `allowTension`, `allowCompression`: allowable stresses (> 0); `allowDisplacement`: the largest joint
+        displacement allowed (None: no limit); `eulerKappa`: the member's second moment of area as I = kappa A^2
+        (1 / (4 pi) for a solid round bar; 0: no member buckling check); `areaMin` > 0, `areaMax` >= `areaMin`: scalars or
+        one value per member; `relax` in (0, 1], `tol`, `maxIters` as `batch.solve_sizing`; `catalog`: a list of
+        `MemberType` whose areas (sorted, duplicates dropped) the final design is rounded up to.  Returns a dict of numpy
+        arrays and scalars:
+          "areas", "utilisation" [nM] (required area / area; <= 1 is feasible), "governing" [nM] (the governing case,
+          -1: the displacement limit), "weight", "disp_ratio", "iterations", "status" (0 converged, 1 iteration limit,
+          2 a design could not be factored), "weight_history" [maxIters + 1] and - with `catalog` - "catalog_index" [nM]
+          (into the sorted areas).
+        The truss's own members, loads and solved state stay as they are.  Raises ValueError for bad arguments (as
+        `batch.solve_sizing`) and `TrussNotStableError` when the counting test fails."""
+        if not self.isStable:
+            raise TrussNotStableError("The truss is not stable !")
+        from .batch import pack_trusses, solve_sizing  # late import: keeps the model importable without torch
+        packed = pack_trusses([self])
+        nM = len(self._bars)
+        loads = None
+        if cases is not None:
+            cases = list(cases)
+            if not cases:
+                raise ValueError("SizeMembers: cases must hold at least one load case")
+            loads = self._case_loads(cases, packed.nJ_max)
+
+        def bound(x):
+            if x is None or np.ndim(x) == 0:
+                return x
+            row = np.zeros([1, packed.nM_max])
+            row[0, :nM] = np.asarray(x, dtype=np.float64).reshape(nM)
+            return row
+        areas = None if catalog is None else sorted({float(t.a) for t in catalog})
+        result = solve_sizing(packed, loads, allow_tension=allowTension, allow_compression=allowCompression,
+                              allow_displace=0.0 if allowDisplacement is None else allowDisplacement,
+                              euler_kappa=eulerKappa, area_min=bound(areaMin), area_max=bound(areaMax), relax=relax, tol=tol,
+                              max_iters=maxIters, catalog=areas)
+        out = {"areas": result.areas[0, :nM].copy(), "utilisation": result.utilisation[0, :nM].copy(),
+               "governing": result.governing[0, :nM].copy(), "weight": float(result.weight[0]),
+               "disp_ratio": float(result.disp_ratio[0]), "iterations": int(result.iterations[0]),
+               "status": int(result.status[0]), "weight_history": result.weight_history[0].copy()}
+        if catalog is not None:
+            out["catalog_index"] = result.catalog_index[0, :nM].copy()
+        return out
+
     def MemberLoss(self, cases=None, rTol=None, returnForces=False):
         """What the loss of any ONE member does to this truss, for every member and every load case, from ONE
         factorisation (`batch.solve_member_loss`): `cases` is a list of `{jointID: vector}` dicts as `SolveLoadCases`
