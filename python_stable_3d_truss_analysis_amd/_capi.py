@@ -302,21 +302,20 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as exc:
         raise HipExtensionError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for table in (SIGNATURES, MODES_SIGNATURES, EFFECTS_SIGNATURES, LOSS_SIGNATURES, INFLUENCE_SIGNATURES,
-                  SETS_SIGNATURES, DYN_SIGNATURES, NL_SIGNATURES, BK_SIGNATURES, MG_SIGNATURES, RS_SIGNATURES,
-                  HR_SIGNATURES, SZ_SIGNATURES):
+    for table, version, expected in (   # per header: its signature table, its version symbol, the version bound here
+            (SIGNATURES, "trs_abi_version", ABI_VERSION), (MODES_SIGNATURES, "trs_modes_abi_version", MODES_ABI_VERSION),
+            (EFFECTS_SIGNATURES, "trs_effects_abi_version", EFFECTS_ABI_VERSION),
+            (INFLUENCE_SIGNATURES, "trs_influence_abi_version", INFLUENCE_ABI_VERSION),
+            (LOSS_SIGNATURES, "trs_loss_abi_version", LOSS_ABI_VERSION), (SETS_SIGNATURES, "trs_sets_abi_version", SETS_ABI_VERSION),
+            (DYN_SIGNATURES, "trs_dyn_abi_version", DYN_ABI_VERSION), (NL_SIGNATURES, "trs_nl_abi_version", NL_ABI_VERSION),
+            (BK_SIGNATURES, "trs_bk_abi_version", BK_ABI_VERSION), (MG_SIGNATURES, "trs_mg_abi_version", MG_ABI_VERSION),
+            (RS_SIGNATURES, "trs_rs_abi_version", RS_ABI_VERSION), (HR_SIGNATURES, "trs_hr_abi_version", HR_ABI_VERSION),
+            (SZ_SIGNATURES, "trs_sz_abi_version", SZ_ABI_VERSION)):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
-            fn.restype = restype
-            fn.argtypes = argtypes
-    if lib.trs_abi_version() != ABI_VERSION or lib.trs_modes_abi_version() != MODES_ABI_VERSION \
-            or lib.trs_effects_abi_version() != EFFECTS_ABI_VERSION or lib.trs_loss_abi_version() != LOSS_ABI_VERSION \
-            or lib.trs_influence_abi_version() != INFLUENCE_ABI_VERSION \
-            or lib.trs_sets_abi_version() != SETS_ABI_VERSION or lib.trs_dyn_abi_version() != DYN_ABI_VERSION \
-            or lib.trs_nl_abi_version() != NL_ABI_VERSION or lib.trs_bk_abi_version() != BK_ABI_VERSION \
-            or lib.trs_mg_abi_version() != MG_ABI_VERSION or lib.trs_rs_abi_version() != RS_ABI_VERSION \
-            or lib.trs_hr_abi_version() != HR_ABI_VERSION or lib.trs_sz_abi_version() != SZ_ABI_VERSION:
-        raise HipExtensionError("libtrs_hip.so ABI version mismatch")
+            fn.restype, fn.argtypes = restype, argtypes
+        if getattr(lib, version)() != expected:
+            raise HipExtensionError("libtrs_hip.so ABI version mismatch")
     _lib = lib
     return lib
 

@@ -573,15 +573,65 @@ def _member_set_arrays(who, sets, gamma, B, nM, nM_max):
     return dense.astype(np.int32), np.ascontiguousarray(g)
 
 
+# -- what the analyses' host layers share: the scalar rules, the `sections=` refusal, the output table --------
+#: the types of "a number"; a site that takes no numpy integer (a `tol`, an `r_tol`) passes _REAL_NO_NPINT
+_REAL = (int, float, np.integer, np.floating)
+_REAL_NO_NPINT = (int, float, np.floating)
+
+
+def _check_number(who, name, x, must="be a finite number", above=None, least=None, below=None, types=_REAL):
+    """`x` as a float: a finite number of `types` (never a bool) with x > `above`, x >= `least` and x < `below` where
+    they are given (positive: above=0; non-negative: least=0; an interval: two of them); else ValueError
+    "`who`: `name` must `must`, got ..."."""
+    if isinstance(x, bool) or not isinstance(x, types) or not np.isfinite(x) or (above is not None and not x > above) \
+            or (least is not None and not x >= least) or (below is not None and not x < below):
+        raise ValueError(f"{who}: {name} must {must}, got {x!r}")
+    return float(x)
+
+
+def _check_integer(who, name, x, least=1):
+    """`x` as an int: a Python or numpy integer (never a bool) of at least `least`; else ValueError."""
+    if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < least:
+        raise ValueError(f"{who}: {name} must be an integer of at least {least}, got {x!r}")
+    return int(x)
+
+
+def _refuse_sections(who, what, sections):
+    """`sections=` variants are for `solve_batch` alone: every analysis refuses them in its own words (`what`)."""
+    if sections is not None:
+        raise ValueError(f"{who}: sections= variants cannot be combined with {what}")
+
+
+#: how the device holds a `FIELDS` dtype that it has no kernel type for: (device dtype, trailing axes)
+_DEVICE_DTYPES = {"bool": ("int32", ()), "complex128": ("float64", (2,))}
+
+
+def _field_shapes(fields, B, sizes, keys=None):
+    """{device key: (shape, torch dtype)} - what `DeviceBatch._out_tensors` takes - from a result class's `FIELDS`
+    (field -> (device key, fill, dtype, shape after B)) for the device keys named in `keys` (None: all of them).  A name
+    in a shape ("L", "S", "P", "G", "V", "R", "H", "T1", "Pj", "Pm", "nJ", "nM") is looked up in `sizes`; one that
+    `sizes` lacks is a KeyError that names the field.  `_DEVICE_DTYPES`: a "bool" is int32 on the device, a "complex128"
+    float64 with a trailing axis of 2."""
+    import torch
+    by_key = {key: (field, dtype, shape) for field, (key, fill, dtype, shape) in fields.items()}
+    shapes = {}
+    for key in by_key if keys is None else keys:
+        field, dtype, shape = by_key[key]
+        dtype, tail = _DEVICE_DTYPES.get(dtype, (dtype, ()))
+        missing = [n for n in shape if isinstance(n, str) and n not in sizes]
+        if missing:
+            raise KeyError(f"field {field!r}: no size {missing[0]!r} among {sorted(sizes)}")
+        shapes[key] = ([B] + [sizes[n] if isinstance(n, str) else n for n in shape] + list(tail), getattr(torch, dtype))
+    return shapes
+
+
 def newmark_constants(dt, beta=0.25, gamma=0.5, damp_mass=0.0, damp_stiff=0.0):
     """The constants of the Newmark scheme of include/trs_dynamics.h as plain Python floats (the library forms the same
     ones in the same order): a0 .. a5, s = 1 + a1 damp_stiff and sigma = (a0 + a1 damp_mass) / s, the multiple of the mass
     that `DeviceBatch.factor_dynamic` adds to the stiffness.  ValueError for dt <= 0, beta <= 0, gamma < 1/2 and negative
     or non-finite damping."""
-    for name, x in (("dt", dt), ("beta", beta), ("gamma", gamma), ("damp_mass", damp_mass), ("damp_stiff", damp_stiff)):
-        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x):
-            raise ValueError(f"transient: {name} must be a finite number, got {x!r}")
-    dt, beta, gamma, damp_mass, damp_stiff = (float(x) for x in (dt, beta, gamma, damp_mass, damp_stiff))
+    dt, beta, gamma, damp_mass, damp_stiff = (_check_number("transient", name, x) for name, x in (
+        ("dt", dt), ("beta", beta), ("gamma", gamma), ("damp_mass", damp_mass), ("damp_stiff", damp_stiff)))
     if not dt > 0.0:
         raise ValueError(f"transient: dt must be positive, got {dt!r}")
     if not beta > 0.0:
@@ -608,11 +658,9 @@ def _check_newton_args(who, load_factors, tol=1e-9, max_iters=25, check_every=1)
         lams = None
     if not lams or not np.isfinite(lams).all():
         raise ValueError(f"{who}: load_factors must be a non-empty sequence of finite numbers, got {load_factors!r}")
-    if isinstance(tol, bool) or not isinstance(tol, (int, float, np.floating)) or not np.isfinite(tol) or not tol > 0:
-        raise ValueError(f"{who}: tol must be a finite positive number, got {tol!r}")
-    for name, x in (("max_iters", max_iters), ("check_every", check_every)):
-        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 1:
-            raise ValueError(f"{who}: {name} must be an integer of at least 1, got {x!r}")
+    _check_number(who, "tol", tol, "be a finite positive number", above=0, types=_REAL_NO_NPINT)
+    _check_integer(who, "max_iters", max_iters)
+    _check_integer(who, "check_every", check_every)
     return lams
 
 
@@ -632,9 +680,7 @@ def _check_sizing_scalars(who, allow_tension, allow_compression, allow_displace=
             if arr is None or arr.shape != (B,) or not np.isfinite(arr).all():
                 raise ValueError(f"{who}: {name} must be a finite number or {B} finite numbers, one per truss")
             return arr
-        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x):
-            raise ValueError(f"{who}: {name} must be a finite number, got {x!r}")
-        return float(x)
+        return _check_number(who, name, x)
     val = {}
     for name, x in (("allow_tension", allow_tension), ("allow_compression", allow_compression)):
         val[name] = number(name, x)
@@ -647,10 +693,8 @@ def _check_sizing_scalars(who, allow_tension, allow_compression, allow_displace=
     val["relax"] = number("relax", relax)
     if not 0 < val["relax"] <= 1:
         raise ValueError(f"{who}: relax must lie in (0, 1], got {relax!r}")
-    for name, x, least in (("max_iters", max_iters, 0), ("check_every", check_every, 1)):
-        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < least:
-            raise ValueError(f"{who}: {name} must be an integer of at least {least}, got {x!r}")
-        val[name] = int(x)
+    val["max_iters"] = _check_integer(who, "max_iters", max_iters, least=0)
+    val["check_every"] = _check_integer(who, "check_every", check_every)
     val["catalog"] = None
     if catalog is not None:
         try:
@@ -674,9 +718,7 @@ def _check_area_bounds(who, area_min, area_max, B, nM, nM_max):
         if x is None:
             raise ValueError(f"{who}: {name} must be given: a scalar or an array [B, nM_max]")
         if np.ndim(x) == 0 and not hasattr(x, "detach"):
-            if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x):
-                raise ValueError(f"{who}: {name} must be a finite number or an array [B, nM_max], got {x!r}")
-            out.append((float(x), None))
+            out.append((_check_number(who, name, x, "be a finite number or an array [B, nM_max]"), None))
             continue
         try:
             arr = _host_array(x, np.float64)
@@ -1038,9 +1080,7 @@ class DeviceBatch:
         """dofmap, assembly and Cholesky factorisation of the resident batch, asynchronous on the current stream: the
         factor stays in the slab for any number of `solve_cases` calls (the batch's own `loads` ride along and are not
         needed by them).  A batch on the fused small-system path keeps no factor: build it with `use_small=False`."""
-        if self.small:
-            raise ValueError("factor(): this batch takes the fused small-system kernel, which keeps no factor - "
-                             "build the DeviceBatch with use_small=False")
+        self._need_slab("factor")
         with self.torch.cuda.device(self.device):
             self.dofmap()
             self.assemble()
@@ -1054,19 +1094,41 @@ class DeviceBatch:
         if not getattr(self, "_factored", False):
             raise ValueError(f"{what}(): no factor - call factor() first")
 
+    def _need_slab(self, what, compact=None):
+        """The refusals of a method that keeps or amends a factor in the slab, in `what`'s name: a batch on the fused
+        small-system path, and - with `compact`, the method's reason - the compact member form of the assembly."""
+        if self.small:
+            raise ValueError(f"{what}(): this batch takes the fused small-system kernel, which keeps no factor - "
+                             "build the DeviceBatch with use_small=False")
+        if compact is not None and self.options["compact"]:
+            raise ValueError(f"{what}(): options['compact'] {compact}")
+
+    def _need_fit(self, what, fits, kernel):
+        """`fits`: what the `trs_*_fits` call of `what`'s kernel (`kernel`: its phrase) said of this batch's sizes."""
+        if not fits:
+            raise HipExtensionError(f"{what}(): a truss of {self.nJ_max} joints / {self.nM_max} members exceeds the LDS "
+                                    f"of {kernel}")
+
+    def _gather_cases(self, loads, L, into, own=False):
+        """`trs_gather_cases`: the L cases `loads` [B, L, nJ_max, 3] reduced into the case block `into`.  `own`: they
+        are the batch's own loads, already in the batch's joint order (gathered without `joint_out`)."""
+        jo, stream, _ = self._case_launch()
+        _capi.check(self.lib.trs_gather_cases(self.B, L, self.nJ_max, loads.data_ptr(), self.free_index.data_ptr(),
+                                              self.n_free.data_ptr(), self.nJ.data_ptr(), None if own else jo,
+                                              into.data_ptr(), self.rows, stream), "trs_gather_cases")
+
     def _out_tensors(self, what, shapes, out):
-        """The result dict of `what`: exactly the keys of `shapes` (key -> shape for float64, or (shape, dtype)), taken
-        from `out` where it has them - they must be contiguous device tensors of that shape and type - and allocated
-        (into `out` too, if one was given) where it has not."""
+        """The result dict of `what`: exactly the keys of `shapes` (key -> (shape, dtype), as `_field_shapes` makes
+        them), taken from `out` where it has them - they must be contiguous device tensors of that shape and type -
+        and allocated (into `out` too, if one was given) where it has not."""
         t = self.torch
         out = {} if out is None else out
-        for k, spec in shapes.items():
-            shape, dtype = spec if isinstance(spec, tuple) else (spec, t.float64)
+        for k, (shape, dtype) in shapes.items():
             if k not in out:
                 out[k] = t.zeros(shape, dtype=dtype, device=self.device)
             elif list(out[k].shape) != shape or out[k].dtype != dtype or out[k].device != self.device \
                     or not out[k].is_contiguous():
-                raise ValueError(f"{what}(): out[{k!r}] must be a contiguous {'float64' if spec is shape else dtype} "
+                raise ValueError(f"{what}(): out[{k!r}] must be a contiguous {'float64' if dtype is t.float64 else dtype} "
                                  f"{shape} tensor on {self.device}")
         return {k: out[k] for k in shapes}
 
@@ -1085,8 +1147,9 @@ class DeviceBatch:
             raise ValueError(f"{what}(): loads must be float64 [B={self.B}, L, nJ_max={self.nJ_max}, 3] on {self.device}")
         return loads.contiguous()
 
-    def _case_shapes(self, L):
-        return {"u": [self.B, L, self.nJ_max, 3], "f_ext": [self.B, L, self.nJ_max, 3], "N": [self.B, L, self.nM_max]}
+    def _sizes(self, **sizes):
+        """The sizes a `FIELDS` shape may name: this batch's "nJ" and "nM" and the call's own."""
+        return dict(sizes, nJ=self.nJ_max, nM=self.nM_max)
 
     def _case_launch(self):
         """What every launch of these methods is given: joint_out's pointer (or None), the current stream, and the infix
@@ -1108,18 +1171,15 @@ class DeviceBatch:
         self._need_factor("solve_cases")
         loads = self._check_loads("solve_cases", loads)
         L = int(loads.shape[1])
-        out = self._out_tensors("solve_cases", self._case_shapes(L), out)
+        out = self._out_tensors("solve_cases", _field_shapes(LoadCaseResult.FIELDS, self.B, self._sizes(L=L)), out)
         if self.B == 0 or L == 0:
             return out
-        if not self.lib.trs_recover_cases_fits(self.nJ_max, self.nM_max):
-            raise HipExtensionError(f"solve_cases(): a truss of {self.nJ_max} joints / {self.nM_max} members exceeds the "
-                                    "LDS of the multi-case recovery (trs_recover_cases_fits)")
+        self._need_fit("solve_cases", self.lib.trs_recover_cases_fits(self.nJ_max, self.nM_max),
+                       "the multi-case recovery (trs_recover_cases_fits)")
         F = self._case_block("cases_F", L)
         jo, stream, tab = self._case_launch()
         with t.cuda.device(self.device):
-            _capi.check(self.lib.trs_gather_cases(self.B, L, self.nJ_max, loads.data_ptr(), self.free_index.data_ptr(),
-                                                  self.n_free.data_ptr(), self.nJ.data_ptr(), jo, F.data_ptr(),
-                                                  self.rows, stream), "trs_gather_cases")
+            self._gather_cases(loads, L, F)
             self._potrs_cases(F, L)
             _capi.check(getattr(self.lib, f"trs_recover{tab}_cases")(
                 self.B, L, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *self._members(), loads.data_ptr(),
@@ -1165,15 +1225,13 @@ class DeviceBatch:
             given[name] = x.contiguous()
         if L is None:
             raise ValueError("solve_effect_cases(): give at least one of loads, prestrain, settlement, accel")
-        shapes = self._case_shapes(L)
-        if want_body:
-            shapes["body"] = [self.B, L, self.nJ_max, 3]
-        out = self._out_tensors("solve_effect_cases", shapes, out)
+        keys = ("u", "f_ext", "N") + (("body",) if want_body else ())
+        out = self._out_tensors("solve_effect_cases", _field_shapes(EffectCaseResult.FIELDS, self.B, self._sizes(L=L), keys),
+                                out)
         if self.B == 0 or L == 0:
             return out
-        if not self.lib.trs_effects_fits(self.nJ_max, self.nM_max):
-            raise HipExtensionError(f"solve_effect_cases(): a truss of {self.nJ_max} joints / {self.nM_max} members "
-                                    "exceeds the LDS of the effect kernels (trs_effects_fits)")
+        self._need_fit("solve_effect_cases", self.lib.trs_effects_fits(self.nJ_max, self.nM_max),
+                       "the effect kernels (trs_effects_fits)")
         F = self._case_block("cases_F", L)
         jo, stream, tab = self._case_launch()
         members = self._members() if self.table else self._members() + (_ptr(self.rho),)
@@ -1206,10 +1264,6 @@ class DeviceBatch:
 
     def _bump_generation(self):
         self._generation = self.generation + 1
-
-    def _gradient_shape(self, key, L):
-        return {"A": [self.B, self.nM_max], "E": [self.B, self.nM_max], "xyz": [self.B, self.nJ_max, 3],
-                "loads": [self.B, L, self.nJ_max, 3]}[key]
 
     def adjoint_cases(self, grad_u=None, grad_f_ext=None, grad_N=None, want=GRADIENTS, out=None, generation=None):
         """The vector-Jacobian product of the last `solve_cases(loads)`: for cotangents `grad_u`, `grad_f_ext`
@@ -1244,12 +1298,11 @@ class DeviceBatch:
                 raise ValueError(f"adjoint_cases(): {name} must be float64 {list(shapes[name])} on {self.device} "
                                  f"(the last solve_cases() had L = {L}), got {g.dtype} {list(g.shape)} on {g.device}")
             cot[name] = g.contiguous()
-        out = self._out_tensors("adjoint_cases", {k: self._gradient_shape(k, L) for k in want}, out)
+        out = self._out_tensors("adjoint_cases", _field_shapes(GradientResult.FIELDS, self.B, self._sizes(L=L), want), out)
         if self.B == 0 or L == 0:
             return out
-        if not self.lib.trs_adjoint_fits(self.nJ_max, self.nM_max):
-            raise HipExtensionError(f"adjoint_cases(): a truss of {self.nJ_max} joints / {self.nM_max} members exceeds "
-                                    "the LDS of the adjoint kernels (trs_adjoint_fits)")
+        self._need_fit("adjoint_cases", self.lib.trs_adjoint_fits(self.nJ_max, self.nM_max),
+                       "the adjoint kernels (trs_adjoint_fits)")
         Lam = self._case_block("cases_Lam", L)   # the adjoint systems: a buffer of their own, the forward F survives
         jo, stream, tab = self._case_launch()
         with t.cuda.device(self.device):
@@ -1321,15 +1374,10 @@ class DeviceBatch:
         if want_forces and B * L * nM_max * nM_max * 8 > max_result_bytes:
             raise ValueError(f"member_loss(): N_after [B={B}, L={L}, {nM_max}, {nM_max}] takes {B * L * nM_max * nM_max * 8} "
                              f"bytes, more than max_result_bytes = {max_result_bytes}")
-        i32 = self.torch.int32
-        shapes = dict(self._case_shapes(L), r=[B, nM_max], critical=([B, nM_max], i32), peak_stress=[B, L, nM_max],
-                      peak_member=([B, L, nM_max], i32), peak_displace=[B, L, nM_max], peak_joint=([B, L, nM_max], i32))
-        if want_forces:
-            shapes["N_after"] = [B, L, nM_max, nM_max]
-        out = self._out_tensors("member_loss", shapes, out)
-        if B and L and not self.lib.trs_loss_fits(nJ_max, nM_max, L):
-            raise HipExtensionError(f"member_loss(): a truss of {nJ_max} joints / {nM_max} members exceeds the LDS of "
-                                    "the apply kernel (trs_loss_fits)")
+        keys = [k for k, *_ in MemberLossResult.FIELDS.values() if k != "N_after" or want_forces]
+        out = self._out_tensors("member_loss", _field_shapes(MemberLossResult.FIELDS, B, self._sizes(L=L), keys), out)
+        self._need_fit("member_loss", not (B and L) or self.lib.trs_loss_fits(nJ_max, nM_max, L),
+                       "the apply kernel (trs_loss_fits)")
         self.solve_cases(loads, out={k: out[k] for k in ("u", "f_ext", "N")})
         if B == 0 or L == 0 or nM_max == 0:
             return out
@@ -1379,18 +1427,11 @@ class DeviceBatch:
         if extra > max_result_bytes:
             raise ValueError(f"member_sets(): N_after / u_after of [B={B}, L={L}, S={S}] scenarios take {extra} bytes, "
                              f"more than max_result_bytes = {max_result_bytes}")
-        i32 = self.torch.int32
-        shapes = dict(self._case_shapes(L), pivot=[B, S, MEMBER_SETS_MAX], unstable=([B, S], i32),
-                      first_unstable=([B, S], i32), peak_stress=[B, L, S], peak_member=([B, L, S], i32),
-                      peak_displace=[B, L, S], peak_joint=([B, L, S], i32))
-        if want_forces:
-            shapes["N_after"] = [B, L, S, nM_max]
-        if want_displace:
-            shapes["u_after"] = [B, L, S, nJ_max, 3]
-        out = self._out_tensors("member_sets", shapes, out)
-        if B and L and not self.lib.trs_sets_fits(nJ_max, nM_max, L):
-            raise HipExtensionError(f"member_sets(): a truss of {nJ_max} joints / {nM_max} members exceeds the LDS of "
-                                    "the apply kernel (trs_sets_fits)")
+        keys = [k for k, *_ in MemberSetResult.FIELDS.values()
+                if (k != "N_after" or want_forces) and (k != "u_after" or want_displace)]
+        out = self._out_tensors("member_sets", _field_shapes(MemberSetResult.FIELDS, B, self._sizes(L=L, S=S), keys), out)
+        self._need_fit("member_sets", not (B and L) or self.lib.trs_sets_fits(nJ_max, nM_max, L),
+                       "the apply kernel (trs_sets_fits)")
         self.solve_cases(loads, out={k: out[k] for k in ("u", "f_ext", "N")})
         if B == 0 or L == 0 or S == 0:
             return out
@@ -1447,10 +1488,8 @@ class DeviceBatch:
         if A < 1:
             raise ValueError("influence(): the train has no axle")
         self._check_columns("influence", chunk)
-        shapes = {k: [B, nM_max] for k in ("N_max", "N_min", "x_max", "x_min", "area_pos", "area_neg")}
-        if want_lines:
-            shapes["eta"] = [B, nM_max, P_max]
-        out = self._out_tensors("influence", shapes, out)
+        keys = [k for k, *_ in InfluenceResult.FIELDS.values() if k != "eta" or want_lines]
+        out = self._out_tensors("influence", _field_shapes(InfluenceResult.FIELDS, B, self._sizes(P=P_max), keys), out)
         if not self.lib.trs_influence_fits(nJ_max, P_max, A):
             raise HipExtensionError(f"influence(): a path of {P_max} joints with {A} axles on a truss of {nJ_max} joints "
                                     "exceeds the LDS of the apply kernel (trs_influence_fits)")
@@ -1490,14 +1529,11 @@ class DeviceBatch:
             if joint_mass.dtype != t.float64 or joint_mass.device != self.device:
                 raise ValueError(f"modes(): joint_mass must be float64 [B={self.B}, nJ_max={self.nJ_max}] on {self.device}")
             joint_mass = joint_mass.contiguous()
-        shapes = {"lam": ([self.B, p], t.float64), "phi": ([self.B, p, self.nJ_max, 3], t.float64),
-                  "resid": ([self.B, p], t.float64), "n_modes": ([self.B], t.int32), "iters": ([self.B], t.int32)}
-        out = self._out_tensors("modes", shapes, out)
+        keys = ("lam", "phi", "resid", "n_modes", "iters")   # (no "omega": `ModeResult.FIELDS`)
+        out = self._out_tensors("modes", _field_shapes(ModeResult.FIELDS, self.B, self._sizes(P=p), keys), out)
         if self.B == 0:
             return out
-        if not self.lib.trs_modes_fits(self.nJ_max, self.nM_max):
-            raise HipExtensionError(f"modes(): a truss of {self.nJ_max} joints / {self.nM_max} members exceeds the LDS "
-                                    "of the mass kernel (trs_modes_fits)")
+        self._need_fit("modes", self.lib.trs_modes_fits(self.nJ_max, self.nM_max), "the mass kernel (trs_modes_fits)")
         Q = MODES_BLOCK
         F = self.cases_F = self._case_block("cases_F", Q)   # the block's right-hand sides / solutions
         self._bump_generation()              # (whatever `solve_cases` left there is gone: `adjoint_cases` refuses it)
@@ -1563,10 +1599,6 @@ class DeviceBatch:
     #: the gradients `mode_gradients` can give
     MODE_GRADIENTS = ("A", "E", "rho", "xyz", "joint_mass")
 
-    def _mode_gradient_shape(self, key, R):
-        return {"A": [self.B, R, self.nM_max], "E": [self.B, R, self.nM_max], "rho": [self.B, R, self.nM_max],
-                "xyz": [self.B, R, self.nJ_max, 3], "joint_mass": [self.B, R, self.nJ_max]}[key]
-
     def mode_gradients(self, weights=None, want=None, out=None, generation=None):
         """The derivatives of the eigenvalues of the last `modes()` with respect to the member areas, moduli and
         densities [B, R, nM_max], the joint coordinates [B, R, nJ_max, 3] (every joint, held ones included; z = 0 for a
@@ -1603,14 +1635,12 @@ class DeviceBatch:
                                  f"{weights.device}")
             weights = weights.contiguous()
         R = p if weights is None else 1
-        shapes = {k: self._mode_gradient_shape(k, R) for k in want}
-        shapes["gap"] = [self.B, p]
-        out = self._out_tensors("mode_gradients", shapes, out)
+        out = self._out_tensors("mode_gradients", _field_shapes(ModeGradientResult.FIELDS, self.B, self._sizes(P=p, R=R),
+                                                                want + ("gap",)), out)
         if self.B == 0:
             return out
-        if not self.lib.trs_mg_fits(self.nJ_max, self.nM_max, p):
-            raise HipExtensionError(f"mode_gradients(): a truss of {self.nJ_max} joints / {self.nM_max} members exceeds "
-                                    "the LDS of the gradient kernel (trs_mg_fits)")
+        self._need_fit("mode_gradients", self.lib.trs_mg_fits(self.nJ_max, self.nM_max, p),
+                       "the gradient kernel (trs_mg_fits)")
         ws = self._modes_ws
         jo, stream, tab = self._case_launch()
         members = self._members() if self.table else \
@@ -1636,17 +1666,6 @@ class DeviceBatch:
     # -- response spectrum analysis from the converged block (include/trs_spectrum.h) ------------------
     #: the combined results `response_spectrum` can give, and where their axes lie after [B, G]
     SPECTRUM_RESULTS = ("u", "N", "R")
-
-    def _spectrum_shapes(self, G, p, want, want_modal):
-        per = {"u": [self.nJ_max, 3], "N": [self.nM_max], "R": [self.nJ_max, 3]}
-        t = self.torch
-        shapes = {"gamma": [self.B, G, p], "sa": [self.B, G, p], "meff": [self.B, G, p], "mtot": [self.B, G],
-                  "base": [self.B, G], "n_modes": ([self.B], t.int32)}
-        for k in want:
-            shapes[k] = [self.B, G] + per[k]
-            if want_modal:
-                shapes["modal_" + k] = [self.B, G, p + 1] + per[k]
-        return shapes
 
     def response_spectrum(self, directions, periods, accel, damping=0.05, rule="cqc", missing_mass=True, zpa=None,
                           want=SPECTRUM_RESULTS, want_modal=False, out=None, generation=None):
@@ -1677,7 +1696,10 @@ class DeviceBatch:
         if self.B and not self.lib.trs_rs_fits(self.nJ_max, self.nM_max, p):     # (before any output is allocated)
             raise HipExtensionError(f"response_spectrum(): the response vectors of a truss of {self.nJ_max} joints / "
                                     f"{self.nM_max} members exceed the LDS of the combine kernel (trs_rs_fits)")
-        out = self._out_tensors("response_spectrum", self._spectrum_shapes(G, p, want, bool(want_modal)), out)
+        keys = ("gamma", "sa", "meff", "mtot", "base", "n_modes") + \
+            tuple(pre + k for k in want for pre in (("", "modal_") if want_modal else ("",)))
+        out = self._out_tensors("response_spectrum", _field_shapes(SpectrumResult.FIELDS, self.B,
+                                                                   self._sizes(P=p, G=G, V=p + 1), keys), out)
         if self.B == 0:
             return out
         ws = self._modes_ws
@@ -1709,19 +1731,6 @@ class DeviceBatch:
     # -- harmonic response over a frequency sweep from the converged block (include/trs_harmonic.h) -----
     #: the envelopes `harmonic` can give, and where their axes lie after [B, L]
     HARMONIC_RESULTS = ("u", "N", "R")
-
-    def _harmonic_shapes(self, L, S, p, want, Pj=0, Pm=0):
-        per = {"u": [self.nJ_max, 3], "N": [self.nM_max], "R": [self.nJ_max, 3]}
-        t = self.torch
-        shapes = {"g": [self.B, L, p], "n_modes": ([self.B], t.int32)}
-        for k in want:
-            shapes[k + "_amp"] = [self.B, L] + per[k]
-            shapes[k + "_at"] = ([self.B, L] + per[k], t.int32)
-        if Pj:
-            shapes["frf_u"] = [self.B, L, S, Pj, 3, 2]
-        if Pm:
-            shapes["frf_N"] = [self.B, L, S, Pm, 2]
-        return shapes
 
     def harmonic(self, omegas, pattern=None, accel=None, damping=0.02, damp_mass=0.0, damp_stiff=0.0, residual=True,
                  monitor_joints=None, monitor_members=None, want=HARMONIC_RESULTS, out=None, generation=None,
@@ -1762,7 +1771,11 @@ class DeviceBatch:
                                     f"{self.nM_max} members exceed the LDS of the sweep kernel (trs_hr_fits)")
         if out is not None:   # (what an earlier call returned: the complex views of its frf tensors)
             out = {k: t.view_as_real(x) if k in ("frf_u", "frf_N") and x.is_complex() else x for k, x in out.items()}
-        out = self._out_tensors("harmonic", self._harmonic_shapes(L, S, p, want, Pj, Pm), out)
+        keys = ("n_modes",) + tuple(k + end for k in want for end in ("_amp", "_at")) + \
+            (("frf_u",) if Pj else ()) + (("frf_N",) if Pm else ())
+        shapes = {"g": ([self.B, L, p], t.float64)}   # (the modal loads: no field of `HarmonicResult`)
+        shapes.update(_field_shapes(HarmonicResult.FIELDS, self.B, self._sizes(P=p, L=L, S=S, Pj=Pj, Pm=Pm), keys))
+        out = self._out_tensors("harmonic", shapes, out)
         if self.B:
             ws = self._modes_ws
             jo, stream, tab = self._case_launch()
@@ -1771,10 +1784,7 @@ class DeviceBatch:
                 W_d, ag_d = self._to_device(W), None if ag is None else self._to_device(ag)
                 if pattern is not None:
                     Pr = self._hr_Pr = self._case_block("_hr_Pr", L)
-                    _capi.check(self.lib.trs_gather_cases(self.B, L, self.nJ_max, pattern.data_ptr(),
-                                                          self.free_index.data_ptr(), self.n_free.data_ptr(),
-                                                          self.nJ.data_ptr(), jo, Pr.data_ptr(), self.rows, stream),
-                                "trs_gather_cases")
+                    self._gather_cases(pattern, L, Pr)
                 F = self._residual_block(residual, lambda F: _capi.check(self.lib.trs_hr_modal(
                     self.B, L, self.nJ_max, self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(),
                     ws["X"].data_ptr(), self.rows, ws["lam"].data_ptr(), ws["Mf"].data_ptr(), ws["n_mass"].data_ptr(), p,
@@ -1806,11 +1816,7 @@ class DeviceBatch:
         `self.info` keeps its meaning.  The compact member form of the assembly (`options["compact"]`) has no slab to
         shift and is refused, as is a batch on the fused small-system path."""
         t = self.torch
-        if self.small:
-            raise ValueError("factor_dynamic(): this batch takes the fused small-system kernel, which keeps no factor - "
-                             "build the DeviceBatch with use_small=False")
-        if self.options["compact"]:
-            raise ValueError("factor_dynamic(): options['compact'] leaves no slab whose diagonal could be shifted")
+        self._need_slab("factor_dynamic", "leaves no slab whose diagonal could be shifted")
         const = newmark_constants(dt, beta, gamma, damp_mass, damp_stiff)
         _check_mass_args("factor_dynamic()", self.B, self.nJ_max, None if joint_mass is None else tuple(joint_mass.shape),
                          mass_scale)
@@ -1819,9 +1825,8 @@ class DeviceBatch:
                 raise ValueError(f"factor_dynamic(): joint_mass must be float64 [B={self.B}, nJ_max={self.nJ_max}] on "
                                  f"{self.device}")
             joint_mass = joint_mass.contiguous()
-        if self.B and not self.lib.trs_modes_fits(self.nJ_max, self.nM_max):
-            raise HipExtensionError(f"factor_dynamic(): a truss of {self.nJ_max} joints / {self.nM_max} members exceeds "
-                                    "the LDS of the mass kernel (trs_modes_fits)")
+        self._need_fit("factor_dynamic", not self.B or self.lib.trs_modes_fits(self.nJ_max, self.nM_max),
+                       "the mass kernel (trs_modes_fits)")
         self._factored = False
         self._dynamic = None
         with t.cuda.device(self.device):
@@ -1865,13 +1870,6 @@ class DeviceBatch:
                 float(mass_scale), self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(),
                 self.nM.data_ptr(), Mf.data_ptr(), self.rows, n_mass.data_ptr(), stream), f"trs_modes{tab}_mass")
         return Mf, n_mass
-
-    #: the results of `transient`: key -> (trailing shape, dtype); "L", "nJ", "nM", "T1", "Pj", "Pm" are the call's sizes
-    TRANSIENT_SHAPES = {"u": (("L", "nJ", 3), "float64"), "v": (("L", "nJ", 3), "float64"), "a": (("L", "nJ", 3), "float64"),
-                        "u_peak": (("L", "nJ", 3), "float64"), "u_step": (("L", "nJ", 3), "int32"),
-                        "N_max": (("L", "nM"), "float64"), "N_max_step": (("L", "nM"), "int32"),
-                        "N_min": (("L", "nM"), "float64"), "N_min_step": (("L", "nM"), "int32"),
-                        "hist_u": (("L", "T1", "Pj", 3), "float64"), "hist_N": (("L", "T1", "Pm"), "float64")}
 
     def _monitor_ids(self, what, ids, device_order):
         """A monitor list of `transient`: int32 [B, P] on this device (None: P = 0), -1 = none; `device_order`: caller's
@@ -1926,10 +1924,8 @@ class DeviceBatch:
         if state is not None:
             if state.get("batch") is not self or state.get("generation") != dyn["generation"] or state.get("L") != L:
                 raise ValueError("transient(): state belongs to another batch, another factor_dynamic() or another L")
-        sizes = {"L": L, "nJ": self.nJ_max, "nM": self.nM_max, "T1": T1, "Pj": Pj, "Pm": Pm}
-        shapes = {k: ([self.B] + [sizes.get(n, n) for n in shape], getattr(t, dtype))
-                  for k, (shape, dtype) in self.TRANSIENT_SHAPES.items()}
-        out = self._out_tensors("transient", shapes, out)
+        out = self._out_tensors("transient", _field_shapes(TransientResult.FIELDS, self.B,
+                                                           self._sizes(L=L, T1=T1, Pj=Pj, Pm=Pm)), out)
         if state is None:
             f64 = lambda: t.empty([self.B, L, self.rows], dtype=t.float64, device=self.device)
             state = {"U": f64(), "V": f64(), "Acc": f64(), "step": 0, "batch": self, "generation": dyn["generation"], "L": L}
@@ -1940,9 +1936,8 @@ class DeviceBatch:
         if self.B == 0 or L == 0:
             return out
         damped = dyn["damp_stiff"] > 0.0
-        if not self.lib.trs_dyn_fits(self.nJ_max, self.nM_max, int(damped)):
-            raise HipExtensionError(f"transient(): a truss of {self.nJ_max} joints / {self.nM_max} members exceeds the LDS "
-                                    "of the step kernel (trs_dyn_fits)")
+        self._need_fit("transient", self.lib.trs_dyn_fits(self.nJ_max, self.nM_max, int(damped)),
+                       "the step kernel (trs_dyn_fits)")
         Pr = self._dyn_Pr = self._case_block("_dyn_Pr", L)
         F = self._dyn_F = self._case_block("_dyn_F", L)
         jo, stream, tab = self._case_launch()
@@ -1961,9 +1956,7 @@ class DeviceBatch:
                 f"trs_dyn{tab}_step")
 
         with t.cuda.device(self.device):
-            _capi.check(self.lib.trs_gather_cases(self.B, L, self.nJ_max, pattern.data_ptr(), self.free_index.data_ptr(),
-                                                  self.n_free.data_ptr(), self.nJ.data_ptr(), jo, Pr.data_ptr(),
-                                                  self.rows, stream), "trs_gather_cases")
+            self._gather_cases(pattern, L, Pr)
             step(first, 0)
             for n in range(1, T1):
                 self._potrs_cases(F, L)
@@ -1974,11 +1967,6 @@ class DeviceBatch:
                 out["a"].data_ptr(), stream), "trs_dyn_collect")
         state["step"] += T1 - 1
         return out
-
-    #: the results of `nonlinear`: key -> (trailing shape, dtype); "S", "nJ", "nM" are the call's sizes
-    NONLINEAR_SHAPES = {"u": (("S", "nJ", 3), "float64"), "N": (("S", "nM"), "float64"),
-                        "f_ext": (("S", "nJ", 3), "float64"), "iters": (("S",), "int32"), "status": (("S",), "int32"),
-                        "residual": (("S",), "float64")}
 
     def nonlinear(self, load_factors, tol=1e-9, max_iters=25, check_every=1, out=None):
         """Geometrically nonlinear statics of the resident batch under `load_factors` times its own loads
@@ -1999,21 +1987,13 @@ class DeviceBatch:
         `self.xyz` and `self.loads` are untouched.  The compact member form of the assembly (`options["compact"]`) has
         no slab to amend and is refused, as is a batch on the fused small-system path."""
         t = self.torch
-        if self.small:
-            raise ValueError("nonlinear(): this batch takes the fused small-system kernel, which keeps no factor - "
-                             "build the DeviceBatch with use_small=False")
-        if self.options["compact"]:
-            raise ValueError("nonlinear(): options['compact'] leaves no slab that could be amended to the tangent")
+        self._need_slab("nonlinear", "leaves no slab that could be amended to the tangent")
         lams = _check_newton_args("nonlinear()", load_factors, tol, max_iters, check_every)
         S = len(lams)
-        shapes = {k: ([self.B] + [{"S": S, "nJ": self.nJ_max, "nM": self.nM_max}.get(n, n) for n in shape], getattr(t, dtype))
-                  for k, (shape, dtype) in self.NONLINEAR_SHAPES.items()}
-        out = self._out_tensors("nonlinear", shapes, out)
+        out = self._out_tensors("nonlinear", _field_shapes(NonlinearResult.FIELDS, self.B, self._sizes(S=S)), out)
         if self.B == 0:
             return out
-        if not self.lib.trs_nl_fits(self.nJ_max, self.nM_max):
-            raise HipExtensionError(f"nonlinear(): a truss of {self.nJ_max} joints / {self.nM_max} members exceeds the LDS "
-                                    "of the state kernel (trs_nl_fits)")
+        self._need_fit("nonlinear", self.lib.trs_nl_fits(self.nJ_max, self.nM_max), "the state kernel (trs_nl_fits)")
         self._factored = False
         self._dynamic = None
         self._forward = None
@@ -2079,10 +2059,6 @@ class DeviceBatch:
             self._stream()), "trs_nl_update")
 
     # -- member sizing: fully stressed design iterated on the device (include/trs_sizing.h) ------------------------------
-    SIZING_SHAPES = {"areas": (("nM",), "float64"), "weight": ((), "float64"), "utilisation": (("nM",), "float64"),
-                     "governing": (("nM",), "int32"), "disp_ratio": ((), "float64"), "iterations": ((), "int32"),
-                     "status": ((), "int32"), "weight_history": (("H",), "float64"), "catalog_index": (("nM",), "uint8")}
-
     def sizing(self, loads=None, *, allow_tension, allow_compression, allow_displace=0.0, euler_kappa=0.0, area_min,
                area_max, relax=1.0, tol=1e-4, max_iters=40, check_every=1, catalog=None, out=None):
         """Member sizing of the resident batch by the stress-ratio method (include/trs_sizing.h: fully stressed design
@@ -2113,11 +2089,7 @@ class DeviceBatch:
         small-system path, `options["compact"]` and the table member form (the step writes one area per member, which a
         type table cannot hold: `PackedBatch.general()` first) are refused."""
         t = self.torch
-        if self.small:
-            raise ValueError("sizing(): this batch takes the fused small-system kernel, which keeps no factor - "
-                             "build the DeviceBatch with use_small=False")
-        if self.options["compact"]:
-            raise ValueError("sizing(): options['compact'] writes no slab that the load cases could be solved against")
+        self._need_slab("sizing", "writes no slab that the load cases could be solved against")
         if self.table:
             raise ValueError("sizing(): the table member form cannot hold one area per member - use the general form "
                              "(PackedBatch.general())")
@@ -2130,10 +2102,8 @@ class DeviceBatch:
                     raise ValueError(f"sizing(): {name} must be a number or a float64 [B={self.B}, nM_max={self.nM_max}] "
                                      f"tensor on {self.device}")
                 bounds.append((x.contiguous(), 0.0))
-            elif isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x):
-                raise ValueError(f"sizing(): {name} must be a finite number or a float64 [B, nM_max] tensor, got {x!r}")
             else:
-                bounds.append((None, float(x)))
+                bounds.append((None, _check_number("sizing()", name, x, "be a finite number or a float64 [B, nM_max] tensor")))
         if bounds[0][0] is None and not bounds[0][1] > 0:
             raise ValueError(f"sizing(): area_min must be positive, got {area_min!r}")
         if bounds[0][0] is None and bounds[1][0] is None and bounds[1][1] < bounds[0][1]:
@@ -2143,15 +2113,11 @@ class DeviceBatch:
         L, H = int(loads.shape[1]), val["max_iters"] + 1
         if L < 1:
             raise ValueError("sizing(): loads must hold at least one case")
-        sizes = {"nM": self.nM_max, "H": H}
-        shapes = {k: ([self.B] + [sizes[n] for n in shape], getattr(t, dtype))
-                  for k, (shape, dtype) in self.SIZING_SHAPES.items() if k != "catalog_index" or val["catalog"] is not None}
-        out = self._out_tensors("sizing", shapes, out)
+        keys = [k for k, *_ in SizingResult.FIELDS.values() if k != "catalog_index" or val["catalog"] is not None]
+        out = self._out_tensors("sizing", _field_shapes(SizingResult.FIELDS, self.B, self._sizes(H=H), keys), out)
         if self.B == 0:
             return out
-        if not self.lib.trs_sz_fits(self.nJ_max, self.nM_max):
-            raise HipExtensionError(f"sizing(): a truss of {self.nJ_max} joints / {self.nM_max} members exceeds the LDS of "
-                                    "the step kernel (trs_sz_fits)")
+        self._need_fit("sizing", self.lib.trs_sz_fits(self.nJ_max, self.nM_max), "the step kernel (trs_sz_fits)")
         self._factored = False
         self._dynamic = None
         self._forward = None
@@ -2203,13 +2169,9 @@ class DeviceBatch:
 
     def _sz_analyse(self, ws):
         """Assembly and factorisation of the design `self.A`, gather and substitution of the L cases."""
-        jo, stream, _ = self._case_launch()
         self.assemble()
         self.potrf()
-        _capi.check(self.lib.trs_gather_cases(self.B, ws["L"], self.nJ_max, ws["loads"].data_ptr(),
-                                              self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(),
-                                              None if ws["own"] else jo,
-                                              ws["F"].data_ptr(), self.rows, stream), "trs_gather_cases")
+        self._gather_cases(ws["loads"], ws["L"], ws["F"], own=ws["own"])
         self._potrs_cases(ws["F"], ws["L"])
 
     def _sz_step(self, ws, it, mode):
@@ -2252,25 +2214,19 @@ class DeviceBatch:
         and the buffer of `solve_cases`' right-hand sides is reused, as `modes` does.  The compact member form of the
         assembly (`options["compact"]`) has no slab to amend and is refused, as is a batch on the fused small path."""
         t = self.torch
-        if self.small:
-            raise ValueError("buckling(): this batch takes the fused small-system kernel, which keeps no factor - "
-                             "build the DeviceBatch with use_small=False")
-        if self.options["compact"]:
-            raise ValueError("buckling(): options['compact'] leaves no slab that could be amended to K + theta Kg")
+        self._need_slab("buckling", "leaves no slab that could be amended to K + theta Kg")
         _check_buckling_args(p, shift, max_shifts, tol, max_iters, check_every)
         self._need_factor("buckling")
         p, shift = int(p), float(shift)
         B, Q, dev = self.B, MODES_BLOCK, self.device
-        sizes = {"P": p, "nJ": self.nJ_max}
-        shapes = {key: ([B] + [sizes.get(n, n) for n in shape], getattr(t, dtype))
-                  for key, fill, dtype, shape in BucklingResult.FIELDS.values()}
-        shapes["info"] = ([B], t.int32)
+        shapes = _field_shapes(BucklingResult.FIELDS, B, self._sizes(P=p))
+        shapes["info"] = ([B], t.int32)   # (what the truss's last factorisation reported: no field of the table)
         out = self._out_tensors("buckling", shapes, out)
         if B == 0:
             return out
-        if not self.lib.trs_bk_fits(self.nJ_max, self.nM_max) or not self.lib.trs_nl_fits(self.nJ_max, self.nM_max):
-            raise HipExtensionError(f"buckling(): a truss of {self.nJ_max} joints / {self.nM_max} members exceeds the LDS "
-                                    "of the product or the amend kernel (trs_bk_fits, trs_nl_fits)")
+        self._need_fit("buckling", self.lib.trs_bk_fits(self.nJ_max, self.nM_max)
+                       and self.lib.trs_nl_fits(self.nJ_max, self.nM_max),
+                       "the product or the amend kernel (trs_bk_fits, trs_nl_fits)")
         F = self.cases_F = self._case_block("cases_F", Q)   # the block's right-hand sides / solutions
         self._bump_generation()
         self._factored = False
@@ -2304,9 +2260,7 @@ class DeviceBatch:
 
         with t.cuda.device(dev):
             # the linear solution under the batch's own loads (already in the batch's joint order: no joint_in)
-            _capi.check(self.lib.trs_gather_cases(B, 1, self.nJ_max, self.loads.data_ptr(), self.free_index.data_ptr(),
-                                                  self.n_free.data_ptr(), self.nJ.data_ptr(), None, ws["u0"].data_ptr(),
-                                                  self.rows, stream), "trs_gather_cases")
+            self._gather_cases(self.loads, 1, ws["u0"], own=True)
             self._potrs_cases(ws["u0"], 1)
             active = t.ones([B], dtype=t.bool, device=dev)
             col = t.arange(p, device=dev)[None, :]
@@ -3657,13 +3611,15 @@ def _peak_fields(*shape):
 
 def _new_result(torch, dev, cls, B, sizes, without=()):
     """A result dataclass of an analysis on the resident factor on `dev`, from its table `cls.FIELDS`: field -> (key of the
-    `DeviceBatch` method's dict, fill value, dtype, shape after B).  The shape names its sizes ("L", "S", "P", "nJ",
-    "nM": looked up in `sizes`); "bool" is kept as int32 until `_finish_result`.  Fields named in `without` (optional
-    results that were not asked for) are None; `info` [B] is int32 zeros."""
-    made = {field: None if field in without else
-            torch.full([B] + [sizes.get(n, n) for n in shape], fill, device=dev,
-                       dtype=torch.int32 if dtype == "bool" else getattr(torch, dtype))
-            for field, (key, fill, dtype, shape) in cls.FIELDS.items()}
+    `DeviceBatch` method's dict, fill value, dtype, shape after B).  Shapes and types are the device's (`_field_shapes`):
+    a "bool" is kept as int32 until `_finish_result`, a "complex128" is viewed as complex at once, as the methods return
+    it.  Fields named in `without` (optional results that were not asked for) are None; `info` [B] is int32 zeros."""
+    shapes = _field_shapes(cls.FIELDS, B, sizes, [v[0] for field, v in cls.FIELDS.items() if field not in without])
+    made = dict.fromkeys(cls.FIELDS)
+    for field, (key, fill, dtype, shape) in cls.FIELDS.items():
+        if field not in without:
+            x = torch.full(shapes[key][0], fill, dtype=shapes[key][1], device=dev)
+            made[field] = torch.view_as_complex(x) if dtype == "complex128" else x
     return cls(**made, info=torch.zeros([B], dtype=torch.int32, device=dev))
 
 
@@ -3772,8 +3728,7 @@ def solve_load_cases(trusses_or_packed, loads, device=None, reorder=False, optio
     (host arrays, or torch tensors on the device with `on_device=True`).  Either member form.  Batches of small
     trusses go through the staged pipeline too (the fused small-system kernel keeps no factor).  `sections=` variants
     are not combined with load cases (ValueError).  `use_envelope=False`: the dense mode (`DeviceBatch`)."""
-    if sections is not None:
-        raise ValueError("solve_load_cases: sections= variants cannot be combined with load cases")
+    _refuse_sections("solve_load_cases", "load cases", sections)
     packed = _as_packed(trusses_or_packed)
     torch, dev = _require_gpu(device)
     B, nJ_max = packed.B, packed.nJ_max
@@ -3803,8 +3758,7 @@ class EffectCaseResult:
 def _check_effect_args(packed, loads, prestrain, settlement, accel, sections):
     """The argument errors of `solve_effect_cases` that need no device.  Returns (L, arrays): the given arguments as
     contiguous float64 host arrays, vectors padded to three components."""
-    if sections is not None:
-        raise ValueError("solve_effect_cases: sections= variants cannot be combined with load cases")
+    _refuse_sections("solve_effect_cases", "load cases", sections)
     B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
     # every argument is [B, L] + inner + last: the dimensions after L, and the allowed sizes of the vector axis (if any)
     inner = {"loads": (nJ_max,), "prestrain": (nM_max,), "settlement": (nJ_max,), "accel": ()}
@@ -3897,8 +3851,7 @@ class GradientResult:
 
 def _check_gradient_args(B, nJ_max, nM_max, loads, cotangents, loss, sections):
     """The argument errors of `solve_gradients` that need no device.  Returns L."""
-    if sections is not None:
-        raise ValueError("solve_gradients: sections= variants cannot be combined with gradients")
+    _refuse_sections("solve_gradients", "gradients", sections)
     shape = tuple(int(x) for x in loads.shape)
     if len(shape) != 4 or shape[0] != B or shape[2] != nJ_max or shape[3] not in (2, 3):
         raise ValueError(f"solve_gradients: loads must be [B={B}, L, nJ_max={nJ_max}, 2 or 3], got {shape}")
@@ -4096,8 +4049,7 @@ def _check_mode_gradient_args(B, nJ_max, p, joint_mass_shape, mass_scale, tol, m
     """The argument errors of `solve_mode_gradients` that need no device: those of `solve_modes`, and weights of the wrong
     shape or not finite (`weights`: a host array or None), unknown names in `want`, "joint_mass" wanted without masses,
     and `sections=`.  Returns `want` as a tuple (None: every gradient, "joint_mass" only when there are masses)."""
-    if sections is not None:
-        raise ValueError("solve_mode_gradients: sections= variants cannot be combined with gradients")
+    _refuse_sections("solve_mode_gradients", "gradients", sections)
     _check_mode_args(B, nJ_max, p, joint_mass_shape, mass_scale, tol, max_iters, joint_mass_min=joint_mass_min)
     if want is None:
         want = tuple(k for k in DeviceBatch.MODE_GRADIENTS if k != "joint_mass" or joint_mass_shape is not None)
@@ -4437,11 +4389,9 @@ def _check_transient_args(packed, pattern, dt, steps, beta=0.25, gamma=0.5, damp
     host arrays: {"pattern" [B, L, nJ_max, 3], "scale" [B, L, T + 1] or None, "accel" [B, L, T + 1, 3] or None,
     "monitor_joints" [B, Pj], "monitor_members" [B, Pm] (int32), "joint_mass" [B, nJ_max] or None}."""
     who = "solve_transient"
-    if sections is not None:
-        raise ValueError(f"{who}: sections= variants cannot be combined with the transient analysis")
+    _refuse_sections(who, "the transient analysis", sections)
     newmark_constants(dt, beta, gamma, damp_mass, damp_stiff)
-    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < 1:
-        raise ValueError(f"{who}: steps must be an integer of at least 1, got {steps!r}")
+    _check_integer(who, "steps", steps)
     B, nJ_max, nM_max, T1 = packed.B, packed.nJ_max, packed.nM_max, int(steps) + 1
     flat = np.asarray(packed.dim).reshape(-1) == 2   # trusses embedded with z fixed
 
@@ -4556,8 +4506,7 @@ def _check_nonlinear_args(packed, load_factors, tol=1e-9, max_iters=25, check_ev
     """The argument errors of `solve_nonlinear` that need no device (ValueError).  Returns the load factors as a list
     of floats."""
     who = "solve_nonlinear"
-    if sections is not None:
-        raise ValueError(f"{who}: sections= variants cannot be combined with the nonlinear analysis")
+    _refuse_sections(who, "the nonlinear analysis", sections)
     if options and options.get("compact"):
         raise ValueError(f"{who}: options['compact'] leaves no slab that could be amended to the tangent")
     lams = _check_newton_args(who, load_factors, tol, max_iters, check_every)
@@ -4628,8 +4577,7 @@ def _check_sizing_args(packed, loads=None, allow_tension=None, allow_compression
     of `_check_sizing_scalars` plus "loads" (a float64 host array [B, L, nJ_max, 3], or None for the batch's own loads)
     and "area_min" / "area_max" (each a float, or a float64 host array [B, nM_max])."""
     who = "solve_sizing"
-    if sections is not None:
-        raise ValueError(f"{who}: sections= variants cannot be combined with the member sizing (it writes the sections)")
+    _refuse_sections(who, "the member sizing (it writes the sections)", sections)
     if options and options.get("compact"):
         raise ValueError(f"{who}: options['compact'] writes no slab that the load cases could be solved against")
     for name, x in (("allow_tension", allow_tension), ("allow_compression", allow_compression)):
@@ -4745,14 +4693,10 @@ def _check_buckling_args(p, shift=0.0, max_shifts=6, tol=1e-10, max_iters=256, c
     if isinstance(p, bool) or not isinstance(p, (int, np.integer)) or not 1 <= int(p) <= 8:
         raise ValueError(f"{who}: p must be an integer in 1 .. 8 (one block of {MODES_BLOCK} vectors delivers at most 8 "
                          f"pairs), got {p!r}")
-    if isinstance(shift, bool) or not isinstance(shift, (int, float, np.integer, np.floating)) \
-            or not np.isfinite(shift) or shift < 0:
-        raise ValueError(f"{who}: shift must be a finite number >= 0, got {shift!r}")
-    if isinstance(tol, bool) or not isinstance(tol, (int, float, np.floating)) or not np.isfinite(tol) or not tol > 0:
-        raise ValueError(f"{who}: tol must be a finite positive number, got {tol!r}")
+    _check_number(who, "shift", shift, "be a finite number >= 0", least=0)
+    _check_number(who, "tol", tol, "be a finite positive number", above=0, types=_REAL_NO_NPINT)
     for name, x in (("max_shifts", max_shifts), ("max_iters", max_iters), ("check_every", check_every)):
-        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 1:
-            raise ValueError(f"{who}: {name} must be an integer of at least 1, got {x!r}")
+        _check_integer(who, name, x)
     if options and options.get("compact"):
         raise ValueError(f"{who}: options['compact'] leaves no slab that could be amended to K + theta Kg")
 
@@ -4803,20 +4747,12 @@ class MemberLossResult:
                   **_peak_fields("L", "nM"), internal_after=("N_after", 0.0, "float64", ("L", "nM", "nM")))
 
 
-def _check_chunk(who, chunk):
-    """`chunk` of a `solve_*` wrapper of the column analyses: an integer of at least 1, or ValueError in `who`'s name."""
-    if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
-        raise ValueError(f"{who}: chunk must be an integer of at least 1, got {chunk!r}")
-
-
 def _check_column_args(who, what, packed, loads, r_tol, sections, chunk):
     """The argument errors that `solve_member_loss` and `solve_member_sets` (`who`) share.  Returns the loads as a
     contiguous float64 host array [B, L, nJ_max, 3] (`loads=None`: the batch's own loads as one case)."""
-    if sections is not None:
-        raise ValueError(f"{who}: sections= variants cannot be combined with the {what} analysis")
-    if isinstance(r_tol, bool) or not isinstance(r_tol, (int, float, np.floating)) or not 0.0 < float(r_tol) < 1.0:
-        raise ValueError(f"{who}: r_tol must lie in (0, 1), got {r_tol!r}")
-    _check_chunk(who, chunk)
+    _refuse_sections(who, f"the {what} analysis", sections)
+    _check_number(who, "r_tol", r_tol, "lie in (0, 1)", above=0, below=1, types=_REAL_NO_NPINT)
+    _check_integer(who, "chunk", chunk)
     B, nJ_max = packed.B, packed.nJ_max
     x = np.asarray(packed.loads, dtype=np.float64)[:, None] if loads is None else _host_array(loads, np.float64)
     shape = tuple(x.shape)
@@ -4975,9 +4911,8 @@ class InfluenceResult:
 def _check_influence_args(packed, path, direction, train, sections, want_lines=False, max_result_bytes=4 << 30, chunk=64):
     """The argument errors of `solve_influence` that need no device (the last one needs the library).  Returns host
     arrays: path int32 [B, P_max] (-1 padding), path_len int32 [B], direction float64 [B, 3], train_w, train_o [A]."""
-    if sections is not None:
-        raise ValueError("solve_influence: sections= variants cannot be combined with the influence analysis")
-    _check_chunk("solve_influence", chunk)
+    _refuse_sections("solve_influence", "the influence analysis", sections)
+    _check_integer("solve_influence", "chunk", chunk)
     B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
     # the path: a list of joint-id lists, or [B, P_max] with -1 padding
     if isinstance(path, (list, tuple)) and all(isinstance(row, (list, tuple)) for row in path):

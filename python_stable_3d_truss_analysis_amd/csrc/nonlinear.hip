@@ -334,11 +334,12 @@ __global__ __launch_bounds__(256) void trs_nl_update_kernel(const TrsBatch bt, c
     const bool ok = pivot == 0;
     __syncthreads();
     if (tid == 0) {
-        if (ok)
+        if (ok) {
             st[4 * b + 1] = it;
-        else
+        } else {
             st[4 * b] = TRS_NL_NOT_PD;
             st[4 * b + 2] = pivot;   // (latched: later factorisations of the frozen tangent do not count)
+        }
     }
     if (!ok) return;
     const TrussView tr = bt.truss(b);

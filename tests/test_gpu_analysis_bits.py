@@ -1,6 +1,6 @@
 """The resident-factor analyses (`solve_load_cases`, `solve_effect_cases`, `solve_gradients`, `solve_modes`,
-`solve_buckling`, `solve_transient`, `solve_nonlinear`, `solve_mode_gradients`, `solve_response_spectrum`, `solve_harmonic` and the
-three on the columns
+`solve_buckling`, `solve_transient`, `solve_nonlinear`, `solve_mode_gradients`, `solve_response_spectrum`, `solve_harmonic`,
+`solve_sizing` and the three on the columns
 inv(K_ff) b_e: `solve_member_loss`, `solve_member_sets`, `solve_influence`) give the SAME BITS as the
 build that recorded `tests/golden/analysis_bits.json`: SHA-256 digests of every field (that is not None) of the result
 dataclasses, for both member forms and with and without a joint order.  The kernels use no floating-point
@@ -30,7 +30,7 @@ L, P = 17, 3   # two case groups of the substitution (16 + 1); three modes
 CONFIGS = {"general": dict(table=False, reorder=False), "general-profile": dict(table=False, reorder="profile"),
            "table": dict(table=True, reorder=False), "table-profile": dict(table=True, reorder="profile")}
 ANALYSES = ("load_cases", "effect_cases", "gradients", "modes", "buckling", "member_loss", "member_sets", "influence",
-            "transient", "nonlinear", "mode_gradients", "response_spectrum", "harmonic")
+            "transient", "nonlinear", "mode_gradients", "response_spectrum", "harmonic", "sizing")
 # the transient response: two excitations (the first two load cases as patterns), five Newmark steps, stiffness
 # damping (so the end lists of the members are built), two monitored joints and two monitored members (first and last)
 L_DYN, STEPS, DT, DAMP_STIFF = 2, 5, 1e-3, 1e-4
@@ -49,6 +49,18 @@ RS_PERIODS = [0.0, 0.02, 0.1, 0.5, 2.0]
 # the harmonic response: two cases (the first two load cases as patterns, the first two accelerations as ground motion)
 # over 70 forcing frequencies - two chunks of the sweep's table of 64, the second partial - with all three dampings
 L_HR, HR_OMEGAS, HR_DAMPING = 2, np.linspace(0.0, 2000.0, 70), dict(damping=0.02, damp_mass=0.5, damp_stiff=1e-5)
+# the member sizing: the first two load cases, one allowable of each kind per truss (SZ_ALLOW, in NAMES' order), tensor
+# bounds (a row per truss: 0.1 x its smallest to 1000 x its largest initial area), the member buckling check, a damped
+# resizing, a look at the active count every second iteration, six resizings at most and a catalogue of 8 areas, so every
+# host branch of `DeviceBatch.sizing` is in the digests.  The allowables are 0.5 and 0.4 of the truss's largest initial
+# stress and half its largest initial joint displacement under these two cases, as tests/sizing_reference.py gives them
+# on the CPU, rounded to two digits; there no truss ends with status 2 (which would only hash the fallback).  The commit
+# that recorded the fixture ended every truss, in all four configs, as the yardstick does: status 1 (the iteration limit)
+# after 6 resizings, info 0, and the members spread over seven of the catalogue's eight areas.
+SZ_L, SZ_ITERS, SZ_CATALOG = 2, 6, 8
+SZ_ALLOW = {"allow_tension": [1.9e4, 5.8e4, 1.4e4, 2.1e5, 3.6e4, 6.3e4, 1.0e6],
+            "allow_compression": [1.6e4, 4.6e4, 1.1e4, 1.7e5, 2.9e4, 5.1e4, 8.1e5],
+            "allow_displace": [0.14, 22.0, 0.53, 1.7, 1.8, 3.6, 1.1e6]}
 SMALL = 6   # the trusses before bar-942: one bucket, where the results per member pair and per scenario are small
 TRAIN = [(1.0, 0.0), (2.0, 30.0), (1.5, 75.0)]
 
@@ -110,6 +122,17 @@ def spectrum_table():
     """The seeded spectral accelerations [2, 5] of `solve_response_spectrum`, from a generator of their own (the inputs
     of the other analyses stay what they were)."""
     return np.random.default_rng(23).uniform(0.5, 10.0, size=(len(RS_DIRS), len(RS_PERIODS)))
+
+
+def sizing_arguments(packed, x):
+    """The keyword arguments of `solve_sizing` (see SZ_ALLOW): bounds and catalogue from the batch's own areas."""
+    A = np.asarray((packed.general() if packed.is_table else packed).A, dtype=np.float64)
+    live = np.arange(packed.nM_max)[None, :] < np.asarray(packed.nM).reshape(-1, 1)
+    lo, hi = np.where(live, A, np.inf).min(axis=1), np.where(live, A, 0.0).max(axis=1)
+    return dict(loads=x["loads"][:, :SZ_L], **{k: np.array(v) for k, v in SZ_ALLOW.items()},
+                euler_kappa=1.0 / (4.0 * np.pi), area_min=np.repeat(0.1 * lo[:, None], packed.nM_max, axis=1),
+                area_max=np.repeat(1000.0 * hi[:, None], packed.nM_max, axis=1), relax=0.7, tol=1e-4, max_iters=SZ_ITERS,
+                check_every=2, catalog=np.geomspace(0.1 * lo.min(), 30.0 * hi.max(), SZ_CATALOG))
 
 
 def column_calls(analysis, packed, x):
@@ -185,6 +208,8 @@ def run(analysis, packed, x, reorder):
                                              reorder=reorder, **HR_DAMPING),
                 "bare": batch.solve_harmonic(packed, HR_OMEGAS, accel=accel, p=P, residual=False,
                                              joint_mass=x["joint_mass"], reorder=reorder, **HR_DAMPING)}
+    if analysis == "sizing":
+        return {"sizing": batch.solve_sizing(packed, reorder=reorder, **sizing_arguments(packed, x))}
     return {"modes": batch.solve_modes(packed, p=P, joint_mass=x["joint_mass"], reorder=reorder)}
 
 
@@ -299,6 +324,8 @@ def test_same_bits_as_recorded(recorded, batches, config, analysis):
         assert results["reversed"].rounds.max() >= 2 and (results["loaded"].status == batch.BK_FOUND).any()
     if analysis == "nonlinear":   # (info only speaks of a tangent that was not positive definite)
         assert not results["nonlinear"].status.any() and results["nonlinear"].iterations.min() >= 1
+    if analysis == "sizing":   # (status 2 would only hash the design a truss fell back to)
+        assert (results["sizing"].status == 1).all() and (results["sizing"].iterations == SZ_ITERS).all()
     got, want = digests(results), recorded[config][analysis]
     assert sorted(got) == sorted(want)
     differing = [k for k in got if got[k] != want[k]]

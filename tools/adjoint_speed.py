@@ -64,7 +64,8 @@ for L in (int(x) for x in args.cases.split(",")):
     fwd = {"u": torch.empty([db.B, L, db.nJ_max, 3], dtype=torch.float64, device=dev),
            "f_ext": torch.empty([db.B, L, db.nJ_max, 3], dtype=torch.float64, device=dev),
            "N": torch.empty([db.B, L, db.nM_max], dtype=torch.float64, device=dev)}
-    out = {k: torch.empty(db._gradient_shape(k, L), dtype=torch.float64, device=dev) for k in db.GRADIENTS}
+    out = {k: torch.empty(shape, dtype=dtype, device=dev) for k, (shape, dtype) in
+           batch._field_shapes(batch.GradientResult.FIELDS, db.B, db._sizes(L=L), db.GRADIENTS).items()}
     t_factor = timed(db.factor)
     t_cases = timed(lambda: db.solve_cases(loads, fwd))
     t_adjoint = timed(lambda: db.adjoint_cases(**cots, out=out))
