@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h`, `include/trs_influence.h`, `include/trs_sets.h`, `include/trs_dynamics.h`, `include/trs_nonlinear.h`, `include/trs_buckling.h`, `include/trs_modegrad.h`, `include/trs_spectrum.h`, `include/trs_harmonic.h` and `include/trs_sizing.h` (library: `libtrs_hip.so`, in-tree).
+"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h`, `include/trs_influence.h`, `include/trs_sets.h`, `include/trs_dynamics.h`, `include/trs_nonlinear.h`, `include/trs_buckling.h`, `include/trs_modegrad.h`, `include/trs_spectrum.h`, `include/trs_harmonic.h`, `include/trs_sizing.h` and `include/trs_compliance.h` (library: `libtrs_hip.so`, in-tree).
 
 There is no fallback: if the library is missing, `load()` raises `HipExtensionError`.
 """
@@ -222,6 +222,15 @@ SZ_SIGNATURES = {
     "trs_sz_snap": (_I, [_I, _I, _P, _P, _P, _I, _P, _P, _P]),
 }
 
+#: every symbol `include/trs_compliance.h` declares (compliance sizing: the stiffest design at a given weight, iterated on
+#: the device; csrc/compliance.hip, the same library).  General member form only, as the member sizing
+CM_SIGNATURES = {
+    "trs_cm_abi_version": (_I, []),
+    "trs_cm_fits": (_I, [_I, _I]),
+    "trs_cm_step": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _D, _D, _D, _P, _D, _P,
+                         _D, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
+}
+
 #: must equal TRS_ABI_VERSION of include/trs_solver.h
 ABI_VERSION = 10
 #: must equal TRS_MODES_ABI_VERSION of include/trs_modes.h
@@ -248,6 +257,8 @@ RS_ABI_VERSION = 1
 HR_ABI_VERSION = 1
 #: must equal TRS_SZ_ABI_VERSION of include/trs_sizing.h
 SZ_ABI_VERSION = 1
+#: must equal TRS_CM_ABI_VERSION of include/trs_compliance.h
+CM_ABI_VERSION = 1
 #: TRS_RS_SRSS, TRS_RS_CQC, TRS_RS_ABS of include/trs_spectrum.h: the modal combination rules
 RS_RULES = {"srss": 0, "cqc": 1, "abs": 2}
 #: TRS_NL_* of include/trs_nonlinear.h: the status of a truss in a load step of the nonlinear analysis
@@ -255,6 +266,9 @@ NL_ACTIVE, NL_CONVERGED, NL_ITER_LIMIT, NL_NOT_PD, NL_NOT_ATTEMPTED = -1, 0, 1, 
 #: TRS_SZ_* of include/trs_sizing.h: the status of a truss in a sizing run, and the catalogue's size limit
 SZ_ACTIVE, SZ_CONVERGED, SZ_ITER_LIMIT, SZ_NOT_PD = -1, 0, 1, 2
 SZ_MAX_CATALOG = 256
+#: TRS_CM_* of include/trs_compliance.h: the status of a truss in a compliance sizing run, and the measures
+CM_ACTIVE, CM_CONVERGED, CM_ITER_LIMIT, CM_NOT_PD = -1, 0, 1, 2
+CM_MEASURES = {"weight": 0, "volume": 1}
 #: TRS_SETS_MAX of include/trs_sets.h: members per scenario at most
 SETS_MAX = 8
 #: TRS_MODES_BLOCK of include/trs_modes.h: vectors per truss of the block iteration (one case group)
@@ -310,7 +324,7 @@ def load():
             (DYN_SIGNATURES, "trs_dyn_abi_version", DYN_ABI_VERSION), (NL_SIGNATURES, "trs_nl_abi_version", NL_ABI_VERSION),
             (BK_SIGNATURES, "trs_bk_abi_version", BK_ABI_VERSION), (MG_SIGNATURES, "trs_mg_abi_version", MG_ABI_VERSION),
             (RS_SIGNATURES, "trs_rs_abi_version", RS_ABI_VERSION), (HR_SIGNATURES, "trs_hr_abi_version", HR_ABI_VERSION),
-            (SZ_SIGNATURES, "trs_sz_abi_version", SZ_ABI_VERSION)):
+            (SZ_SIGNATURES, "trs_sz_abi_version", SZ_ABI_VERSION), (CM_SIGNATURES, "trs_cm_abi_version", CM_ABI_VERSION)):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

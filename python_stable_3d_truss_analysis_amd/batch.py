@@ -737,6 +737,49 @@ def _check_area_bounds(who, area_min, area_max, B, nM, nM_max):
     return tuple(out)
 
 
+def _check_min_compliance_scalars(who, alpha=None, measure="weight", eta=0.5, move=0.2, tol=1e-4, max_iters=60,
+                                  check_every=1, L=1):
+    """The scalar arguments of the compliance sizing (ValueError): `alpha` L finite weights >= 0, not all zero (None:
+    ones), `measure` "weight" or "volume", `eta` and `move` in (0, 1], `tol` finite and >= 0, `max_iters` an integer
+    >= 0, `check_every` an integer >= 1.  Returns them as a dict; alpha as a float64 array [L]."""
+    val = {}
+    if alpha is None:
+        val["alpha"] = np.ones([L], dtype=np.float64)
+    else:
+        try:
+            arr = np.array(_host_array(alpha, np.float64), dtype=np.float64)
+        except (TypeError, ValueError):
+            arr = None
+        if arr is None or arr.shape != (L,) or not np.isfinite(arr).all() or (arr < 0).any() or not (arr > 0).any():
+            raise ValueError(f"{who}: alpha must hold {L} finite weights >= 0, one per load case and not all zero, "
+                             f"got {alpha!r}")
+        val["alpha"] = arr
+    if not isinstance(measure, str) or measure not in _capi.CM_MEASURES:
+        raise ValueError(f"{who}: measure must be one of {sorted(_capi.CM_MEASURES)}, got {measure!r}")
+    val["measure"] = measure
+    for name, x in (("eta", eta), ("move", move)):
+        val[name] = _check_number(who, name, x, "lie in (0, 1]", above=0)
+        if val[name] > 1:
+            raise ValueError(f"{who}: {name} must lie in (0, 1], got {x!r}")
+    val["tol"] = _check_number(who, "tol", tol, "be a finite number >= 0", least=0)
+    val["max_iters"] = _check_integer(who, "max_iters", max_iters, least=0)
+    val["check_every"] = _check_integer(who, "check_every", check_every)
+    return val
+
+
+def _check_target(who, target, B):
+    """`target` of the compliance sizing as a float64 array [B]: a finite positive number, or B of them."""
+    if np.ndim(target) == 0 and not hasattr(target, "detach"):
+        return np.full([B], _check_number(who, "target", target, "be a finite positive number or one per truss", above=0))
+    try:
+        arr = np.array(_host_array(target, np.float64), dtype=np.float64)
+    except (TypeError, ValueError):
+        arr = None
+    if arr is None or arr.shape != (B,) or not np.isfinite(arr).all() or not (arr > 0).all():
+        raise ValueError(f"{who}: target must be a finite positive number or {B} of them, one per truss")
+    return arr
+
+
 def _check_mass_args(who, B, nJ_max, joint_mass_shape, mass_scale, joint_mass_min=None):
     """The mass arguments that the transient analysis shares with `modes` (`_check_mode_args`), refused in `who`'s name."""
     try:
@@ -2186,6 +2229,123 @@ class DeviceBatch:
             ws["active"][min(it, val["max_iters"]):].data_ptr(), out["areas"].data_ptr(), out["weight"].data_ptr(),
             out["utilisation"].data_ptr(), out["governing"].data_ptr(), out["disp_ratio"].data_ptr(),
             out["weight_history"].data_ptr(), val["max_iters"] + 1, self._stream()), "trs_sz_step")
+
+    # -- compliance sizing: the stiffest design at a given weight, iterated on the device (include/trs_compliance.h) -----
+    def min_compliance(self, loads=None, *, alpha=None, target=None, measure="weight", eta=0.5, move=0.2, area_min,
+                       area_max, tol=1e-4, max_iters=60, check_every=1, out=None, levels=0):
+        """Compliance sizing of the resident batch (include/trs_compliance.h: the optimality-criteria method): the areas
+        that make every truss stiffest - the smallest J = sum_l `alpha`_l C_l, C_l = f_l.u_l the compliance of load case
+        l - at the measure `target` = sum w A, w = rho L0 (`measure` "weight") or L0 ("volume").  Every design is
+        analysed under all L load cases; the sensitivities -dJ/dA_m = s_m are the members' own strain energies per area
+        (no adjoint solve); every member goes to A_m (s_m / (x w_m))^`eta`, held within `move` (relative) of A_m and
+        within [`area_min`, `area_max`] (scalars or float64 device tensors [B, nM_max]; equal bounds fix a member), the
+        multiplier x found by 64 bisections so that the new design meets the target; until no area moves by more than
+        `tol` (relative) or `max_iters` resizings are done.  `loads`: float64 device tensor [B, L, nJ_max, 3] as
+        `solve_cases` takes them (None: the batch's own loads as one case); `alpha`: L weights >= 0, not all zero (None:
+        ones); `target`: a number > 0, one per truss (an array or float64 device tensor [B]) or None: the measure of
+        the initial design, the batch's own A.  Per iteration five launches: `trs_assemble`, `trs_potrf_batched`,
+        `trs_gather_cases`, `trs_potrs_cases` and `trs_cm_step`, which reads the L reduced solutions from the case block
+        and writes the next design - neither u nor N of a case goes to HBM.  A converged truss is frozen, as is one whose
+        design cannot be factored (`info != 0`: it goes back to the design before), so a truss's results depend neither
+        on the others nor on `check_every` nor on `max_iters` beyond its own count.  `levels`: how many levels of the
+        bisection the kernel evaluates per round (1, 2, 3; 0: the library's choice) - the same bits either way.
+        Returns a dict of device tensors, in the caller's member order: areas, sensitivity [B, nM_max], measure,
+        objective, multiplier [B], compliance [B, L], objective_history [B, max_iters + 1] (zero beyond the truss's own
+        count), iterations, status (int32 [B]: 0 converged, 1 iteration limit, 2 a design could not be factored).
+        `self.info` holds 0, or for a truss of status 2 what the factorisation reported, latched.  Afterwards `self.A`
+        holds the returned areas and the slab the factor of the returned design for every truss of status 0 or 1:
+        `solve_cases` may follow without another `factor()`; `generation` is bumped.  A batch on the fused small-system
+        path, `options["compact"]` and the table member form are refused, as in `sizing()`."""
+        t = self.torch
+        who = "min_compliance()"
+        self._need_slab("min_compliance", "writes no slab that the load cases could be solved against")
+        if self.table:
+            raise ValueError(f"{who}: the table member form cannot hold one area per member - use the general form "
+                             "(PackedBatch.general())")
+        own = loads is None   # (the batch's own loads are already in the batch's joint order: gathered without joint_in)
+        loads = self._check_loads("min_compliance", self.loads.unsqueeze(1) if own else loads)
+        L = int(loads.shape[1])
+        if L < 1:
+            raise ValueError(f"{who}: loads must hold at least one case")
+        val = _check_min_compliance_scalars(who, alpha, measure, eta, move, tol, max_iters, check_every, L)
+        if levels not in (0, 1, 2, 3):
+            raise ValueError(f"{who}: levels must be 0, 1, 2 or 3, got {levels!r}")
+        bounds = []
+        for name, x in (("area_min", area_min), ("area_max", area_max)):
+            if hasattr(x, "data_ptr"):
+                if list(x.shape) != [self.B, self.nM_max] or x.dtype != t.float64 or x.device != self.device:
+                    raise ValueError(f"{who}: {name} must be a number or a float64 [B={self.B}, nM_max={self.nM_max}] "
+                                     f"tensor on {self.device}")
+                bounds.append((x.contiguous(), 0.0))
+            else:
+                bounds.append((None, _check_number(who, name, x, "be a finite number or a float64 [B, nM_max] tensor")))
+        if bounds[0][0] is None and not bounds[0][1] > 0:
+            raise ValueError(f"{who}: area_min must be positive, got {area_min!r}")
+        if bounds[0][0] is None and bounds[1][0] is None and bounds[1][1] < bounds[0][1]:
+            raise ValueError(f"{who}: area_max must be >= area_min, got {area_max!r} < {area_min!r}")
+        if target is None:
+            W = t.zeros([self.B], dtype=t.float64, device=self.device)   # (the step fills in the initial measure)
+        elif hasattr(target, "data_ptr"):
+            if list(target.shape) != [self.B] or target.dtype != t.float64 or target.device != self.device:
+                raise ValueError(f"{who}: target must be a positive number or a float64 [B={self.B}] tensor on {self.device}")
+            W = target.clone()
+        else:
+            W = t.from_numpy(_check_target(who, target, self.B)).to(self.device)
+        H = val["max_iters"] + 1
+        out = self._out_tensors("min_compliance", _field_shapes(MinComplianceResult.FIELDS, self.B, self._sizes(H=H, L=L)),
+                                out)
+        if self.B == 0:
+            return out
+        self._need_fit("min_compliance", self.lib.trs_cm_fits(self.nJ_max, self.nM_max), "the step kernel (trs_cm_fits)")
+        self._factored = False
+        self._dynamic = None
+        self._forward = None
+        ws = self._cm_workspace(val, bounds, loads, W, out, own, levels)
+        with t.cuda.device(self.device):
+            self.dofmap()
+            out["objective_history"].zero_()
+            it = 0
+            while True:
+                last = it == val["max_iters"]
+                self._sz_analyse(ws)
+                self._cm_step(ws, it, 1 if last else 0)
+                if last or (it % val["check_every"] == 0 and int(ws["active"][it].item()) == 0):
+                    break
+                it += 1
+            out["status"].copy_(ws["st"][:, 0])
+            out["iterations"].copy_(ws["st"][:, 1])
+            # (what the factorisation reported for the design that ended a truss with status 2; 0 for every other truss)
+            self.info.copy_(ws["st"][:, 2])
+        self.cases_F = ws["F"]
+        self._factored = True   # (of the returned design, for every truss of status 0 or 1)
+        self._bump_generation()
+        return out
+
+    # the stages of `min_compliance` (tools/bench_compliance.py times them one by one; the analysis is `_sz_analyse`)
+    def _cm_workspace(self, val, bounds, loads, target, out, own=False, levels=0):
+        """The state of a `min_compliance` run: the design before the last resizing, the status words st [B, 4] and the
+        `active` counters (one per analysis), zeroed; the case block; the weights and the targets on the device."""
+        t, dev = self.torch, self.device
+        L = int(loads.shape[1])
+        return {"prev": t.zeros([self.B, max(self.nM_max, 1)], dtype=t.float64, device=dev),
+                "st": t.zeros([self.B, 4], dtype=t.int32, device=dev),
+                "active": t.zeros([val["max_iters"] + 1], dtype=t.int32, device=dev),
+                "alpha": t.from_numpy(val["alpha"]).to(dev), "target": target, "levels": levels,
+                "F": self._case_block("cases_F", L), "L": L, "loads": loads, "own": own, "val": val, "bounds": bounds,
+                "out": out}
+
+    def _cm_step(self, ws, it, mode):
+        val, out, (lo, hi) = ws["val"], ws["out"], ws["bounds"]
+        _capi.check(self.lib.trs_cm_step(
+            self.B, ws["L"], self.nJ_max, self.nM_max, self.xyz.data_ptr(), self.conn.data_ptr(), self.E.data_ptr(),
+            self.A.data_ptr(), self.rho.data_ptr(), self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(),
+            self.nM.data_ptr(), ws["F"].data_ptr(), self.rows, self.info.data_ptr(), ws["alpha"].data_ptr(),
+            _capi.CM_MEASURES[val["measure"]], ws["target"].data_ptr(), val["eta"], val["move"], val["tol"], _ptr(lo[0]),
+            lo[1], _ptr(hi[0]), hi[1], it, mode, ws["levels"], ws["prev"].data_ptr(), ws["st"].data_ptr(),
+            ws["active"][min(it, val["max_iters"]):].data_ptr(), out["areas"].data_ptr(), out["measure"].data_ptr(),
+            out["compliance"].data_ptr(), out["objective"].data_ptr(), out["objective_history"].data_ptr(),
+            val["max_iters"] + 1, out["sensitivity"].data_ptr(), out["multiplier"].data_ptr(), self._stream()),
+            "trs_cm_step")
 
     # -- linear buckling: critical load factors from shifted factors of K + theta Kg (include/trs_buckling.h) ------------
     def buckling(self, p, shift=0.0, max_shifts=6, tol=1e-10, max_iters=256, check_every=4, out=None):
@@ -4652,6 +4812,119 @@ def solve_sizing(trusses_or_packed, loads=None, allow_tension=None, allow_compre
             area_min=bound(part, on["area_min"]),
             area_max=bound(part, on["area_max"]), relax=val["relax"], tol=val["tol"], max_iters=val["max_iters"],
             check_every=val["check_every"], catalog=val["catalog"]))
+    return _finish_result(torch, dev, out, on_device)
+
+
+@dataclass
+class MinComplianceResult:
+    """Results of `solve_min_compliance`, in the caller's member order, all describing the last design of a truss that
+    could be factored: areas [B, nM_max], measure [B] (sum w A of the returned design: the target, from the first
+    resizing on), compliance [B, L] (C_l = f_l.u_l), objective [B] (J = sum alpha_l C_l), objective_history
+    [B, max_iters + 1] (J of every design the truss analysed, zero beyond its own count), sensitivity [B, nM_max]
+    (s_m = -dJ/dA_m), multiplier [B] (of the last resizing computed: at the optimum s_m = multiplier w_m on every member
+    strictly inside its bounds; 0 where the bounds alone decide), iterations [B] (resizings behind the returned design),
+    status (int32 [B]: 0 converged, 1 iteration limit, 2 a design could not be factored - the truss went back to the
+    design before; with iterations 0 its areas are the initial ones and the other results zero).
+    info [B]: 0, or what the factorisation reported for the design that ended a truss with status 2."""
+    areas: np.ndarray
+    measure: np.ndarray
+    compliance: np.ndarray
+    objective: np.ndarray
+    objective_history: np.ndarray
+    sensitivity: np.ndarray
+    multiplier: np.ndarray
+    iterations: np.ndarray
+    status: np.ndarray
+    info: np.ndarray
+
+    FIELDS = {"areas": ("areas", 0.0, "float64", ("nM",)), "measure": ("measure", 0.0, "float64", ()),
+              "compliance": ("compliance", 0.0, "float64", ("L",)), "objective": ("objective", 0.0, "float64", ()),
+              "objective_history": ("objective_history", 0.0, "float64", ("H",)),
+              "sensitivity": ("sensitivity", 0.0, "float64", ("nM",)), "multiplier": ("multiplier", 0.0, "float64", ()),
+              "iterations": ("iterations", 0, "int32", ()), "status": ("status", 0, "int32", ())}
+
+
+def _check_min_compliance_args(packed, loads=None, alpha=None, target=None, measure="weight", eta=0.5, move=0.2,
+                               area_min=None, area_max=None, tol=1e-4, max_iters=60, check_every=1, options=None,
+                               sections=None, max_result_bytes=4 << 30):
+    """The argument errors of `solve_min_compliance` that need no device (ValueError).  Returns the arguments checked:
+    the dict of `_check_min_compliance_scalars` plus "loads" (a float64 host array [B, L, nJ_max, 3], or None for the
+    batch's own loads), "target" (None, or a float64 array [B]) and "area_min" / "area_max" (each a float, or a float64
+    host array [B, nM_max])."""
+    who = "solve_min_compliance"
+    _refuse_sections(who, "the compliance sizing (it writes the sections)", sections)
+    if options and options.get("compact"):
+        raise ValueError(f"{who}: options['compact'] writes no slab that the load cases could be solved against")
+    B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
+    host_loads = None
+    if loads is not None:
+        try:
+            x = _host_array(loads, np.float64)
+        except (TypeError, ValueError):
+            x = None
+        shape = None if x is None else tuple(x.shape)
+        if x is None or len(shape) != 4 or shape[0] != B or shape[1] < 1 or shape[2] != nJ_max or shape[3] not in (2, 3):
+            raise ValueError(f"{who}: loads must be [B={B}, L >= 1, nJ_max={nJ_max}, 2 or 3], got {shape}")
+        if not np.isfinite(x).all():
+            raise ValueError(f"{who}: loads must be finite")
+        host_loads = np.ascontiguousarray(np.pad(x, [(0, 0)] * 3 + [(0, 3 - shape[3])]))
+    L = 1 if host_loads is None else host_loads.shape[1]
+    val = _check_min_compliance_scalars(who, alpha, measure, eta, move, tol, max_iters, check_every, L)
+    val["loads"] = host_loads
+    val["target"] = None if target is None else _check_target(who, target, B)
+    (lo, lo_arr), (hi, hi_arr) = _check_area_bounds(who, area_min, area_max, B, packed.nM, nM_max)
+    val["area_min"], val["area_max"] = (lo if lo_arr is None else lo_arr), (hi if hi_arr is None else hi_arr)
+    live = np.arange(nM_max)[None, :] < np.asarray(packed.nM)[:, None]
+    general = packed.general() if packed.is_table else packed
+    if B and not (np.asarray(general.A)[live] > 0).all():
+        raise ValueError(f"{who}: the initial design must be positive: every member's area > 0")
+    if B and measure == "weight" and not (np.asarray(general.rho)[live] > 0).all():
+        raise ValueError(f"{who}: measure='weight' needs a positive density rho on every member - a member with rho <= 0 "
+                         "weighs nothing; use measure='volume'")
+    nbytes = B * (nM_max * 16 + 8 * (val["max_iters"] + 1) + 8 * L + 40)
+    if nbytes > max_result_bytes:
+        raise ValueError(f"{who}: the results of B={B} trusses take {nbytes} bytes, more than max_result_bytes = "
+                         f"{max_result_bytes}")
+    return val
+
+
+def solve_min_compliance(trusses_or_packed, loads=None, alpha=None, target=None, measure="weight", eta=0.5, move=0.2,
+                         area_min=None, area_max=None, tol=1e-4, max_iters=60, check_every=1, device=None, reorder=False,
+                         options=None, on_device=False, sections=None, use_envelope=True, max_slab_bytes=64 << 30,
+                         max_result_bytes=4 << 30):
+    """The stiffest design of every truss of a batch at a given weight (or volume): compliance sizing by the
+    optimality-criteria method (include/trs_compliance.h, `DeviceBatch.min_compliance`).  The objective is
+    J = sum_l `alpha`_l f_l.u_l over the load cases `loads` [B, L, nJ_max, dim] (numpy or torch; the caller's joint
+    numbering; dim 2 or 3; None: the batch's own loads as one case); `alpha`: L weights >= 0, not all zero (None: ones);
+    the constraint is sum w A = `target` with w = rho L0 (`measure` "weight") or L0 ("volume"); `target`: one number, one
+    per truss [B], or None for the measure of the initial design, the batch's own areas.  `eta` in (0, 1] damps the
+    resizing, `move` in (0, 1] limits the relative change of an area per resizing, `area_min` > 0 and `area_max` >=
+    `area_min`: scalars or [B, nM_max] (equal bounds fix a member); `tol` is the relative area change at which a truss
+    is converged, `max_iters` the number of resizings at most, `check_every` how often the host looks whether every
+    truss is done.  What the method is not: there are no stress or displacement constraints (that is `solve_sizing`),
+    members end on `area_min` rather than being removed, and with several weighted cases the fixed point can be
+    approached slowly.  Every iteration factors its own design (`_factored_buckets` factors nothing
+    ahead).  A table-form batch is converted with `.general()`.  `measure="weight"` is refused when a member has
+    rho <= 0.  Buckets, `reorder` plans, `options`, `on_device` and `use_envelope` as `solve_load_cases`.  Bad arguments
+    (`_check_min_compliance_args`) raise ValueError before any device work.  Returns a `MinComplianceResult`."""
+    packed = _as_packed(trusses_or_packed)
+    val = _check_min_compliance_args(packed, loads, alpha, target, measure, eta, move, area_min, area_max, tol, max_iters,
+                                     check_every, options, sections, max_result_bytes)
+    if packed.is_table:
+        packed = packed.general()
+    torch, dev = _require_gpu(device)
+    L = 1 if val["loads"] is None else int(val["loads"].shape[1])
+    out = _new_result(torch, dev, MinComplianceResult, packed.B, {"nM": packed.nM_max, "H": val["max_iters"] + 1, "L": L})
+    on = {k: _device_f64(torch, dev, val[k]) if isinstance(val[k], np.ndarray) else val[k]
+          for k in ("loads", "area_min", "area_max")}
+    bound = lambda part, x: part.cut(x, nM=1) if hasattr(x, "data_ptr") else x
+    for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope,
+                                      factor=lambda db, part: None):
+        _put_result(part, out, db.min_compliance(
+            part.cut(on["loads"], nJ=2), alpha=val["alpha"], target=None if val["target"] is None else val["target"][part.index],
+            measure=val["measure"], eta=val["eta"], move=val["move"], area_min=bound(part, on["area_min"]),
+            area_max=bound(part, on["area_max"]), tol=val["tol"], max_iters=val["max_iters"],
+            check_every=val["check_every"]))
     return _finish_result(torch, dev, out, on_device)
 
 

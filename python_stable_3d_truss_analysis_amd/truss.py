@@ -708,6 +708,46 @@ class Truss:
             out["catalog_index"] = result.catalog_index[0, :nM].copy()
         return out
 
+    def MinimizeCompliance(self, cases=None, alpha=None, target=None, measure="weight", eta=0.5, move=0.2, areaMin=None,
+                           areaMax=None, tol=1e-4, maxIters=60):
+        """The areas that make this truss stiffest at a given weight (or volume): compliance sizing by the
+        optimality-criteria method (`batch.solve_min_compliance`), starting from the members' own areas.  `cases` is a
+        list of `{jointID: vector}` dicts as `SolveLoadCases` takes them (None: the truss's own forces as one case);
+        `alpha`: one weight >= 0 per case (None: ones); `target`: the weight (`measure` "weight": sum rho L A) or volume
+        ("volume": sum L A) of the design (None: that of the members' own areas); `areaMin` > 0, `areaMax` >= `areaMin`:
+        scalars or one value per member; `eta`, `move`, `tol`, `maxIters` as `batch.solve_min_compliance`.  Returns a
+        dict of numpy arrays and scalars:
+          "areas", "sensitivity" [nM] (-dJ/dA), "measure", "objective", "multiplier", "compliance" [L], "iterations",
+          "status" (0 converged, 1 iteration limit, 2 a design could not be factored), "objective_history"
+          [maxIters + 1].
+        The truss's own members, loads and solved state stay as they are.  Raises ValueError for bad arguments (as
+        `batch.solve_min_compliance`) and `TrussNotStableError` when the counting test fails."""
+        if not self.isStable:
+            raise TrussNotStableError("The truss is not stable !")
+        from .batch import pack_trusses, solve_min_compliance  # late import: keeps the model importable without torch
+        packed = pack_trusses([self])
+        nM = len(self._bars)
+        loads = None
+        if cases is not None:
+            cases = list(cases)
+            if not cases:
+                raise ValueError("MinimizeCompliance: cases must hold at least one load case")
+            loads = self._case_loads(cases, packed.nJ_max)
+
+        def bound(x):
+            if x is None or np.ndim(x) == 0:
+                return x
+            row = np.zeros([1, packed.nM_max])
+            row[0, :nM] = np.asarray(x, dtype=np.float64).reshape(nM)
+            return row
+        result = solve_min_compliance(packed, loads, alpha=alpha, target=target, measure=measure, eta=eta, move=move,
+                                      area_min=bound(areaMin), area_max=bound(areaMax), tol=tol, max_iters=maxIters)
+        return {"areas": result.areas[0, :nM].copy(), "sensitivity": result.sensitivity[0, :nM].copy(),
+                "measure": float(result.measure[0]), "objective": float(result.objective[0]),
+                "multiplier": float(result.multiplier[0]), "compliance": result.compliance[0].copy(),
+                "iterations": int(result.iterations[0]), "status": int(result.status[0]),
+                "objective_history": result.objective_history[0].copy()}
+
     def MemberLoss(self, cases=None, rTol=None, returnForces=False):
         """What the loss of any ONE member does to this truss, for every member and every load case, from ONE
         factorisation (`batch.solve_member_loss`): `cases` is a list of `{jointID: vector}` dicts as `SolveLoadCases`
