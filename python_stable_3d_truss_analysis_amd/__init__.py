@@ -43,7 +43,8 @@ __all__ = ["Truss", "Member", "MemberType", "SupportType", "MetapathType", "Task
            "solve_member_loss", "MemberLossResult", "solve_influence", "InfluenceResult",
            "solve_member_sets", "MemberSetResult", "solve_transient", "TransientResult",
            "solve_nonlinear", "NonlinearResult", "solve_buckling", "BucklingResult",
-           "solve_sizing", "SizingResult", "solve_min_compliance", "MinComplianceResult"]
+           "solve_sizing", "SizingResult", "solve_min_compliance", "MinComplianceResult",
+           "solve_unilateral", "UnilateralResult"]
 
 
 def __getattr__(name):
@@ -54,7 +55,8 @@ def __getattr__(name):
                 "InfluenceResult", "solve_member_sets", "MemberSetResult", "solve_transient", "TransientResult",
                 "solve_nonlinear", "NonlinearResult", "solve_buckling", "BucklingResult", "solve_mode_gradients",
                 "ModeGradientResult", "solve_response_spectrum", "SpectrumResult", "solve_harmonic",
-                "HarmonicResult", "solve_sizing", "SizingResult", "solve_min_compliance", "MinComplianceResult"):
+                "HarmonicResult", "solve_sizing", "SizingResult", "solve_min_compliance", "MinComplianceResult",
+                "solve_unilateral", "UnilateralResult"):
         from . import batch
         return getattr(batch, name)
     if name == "DifferentiableTruss":

@@ -2347,6 +2347,149 @@ class DeviceBatch:
             val["max_iters"] + 1, out["sensitivity"].data_ptr(), out["multiplier"].data_ptr(), self._stream()),
             "trs_cm_step")
 
+    # -- tension-only and compression-only members: the active-set iteration on the device (include/trs_unilateral.h) ----
+    def unilateral(self, kind, loads=None, prestrain=None, slack_factor=0.0, max_iters=20, check_every=1, state=None,
+                   out=None):
+        """One load case of the resident batch with members that carry tension only or compression only (cables, tie
+        rods, counter-bracing, struts that bear against a seat), by the active-set iteration of include/trs_unilateral.h:
+        analyse, switch off every unilateral member that is strained the wrong way, switch on every one that would be
+        strained the right way, repeat until nothing changes.  `kind`: int8 device tensor [B, nM_max] of 0 (bilateral),
+        +1 (tension-only) and -1 (compression-only); `loads`: float64 device tensor [B, nJ_max, 3] in the CALLER's joint
+        numbering (None: the batch's own loads); `prestrain`: float64 [B, nM_max] member initial strains eps0 as
+        `solve_effect_cases` takes them - pretension goes in as a negative eps0 -, or None; `slack_factor` >= 0: the
+        fraction of its area a slack member keeps (0 removes it exactly); `max_iters` >= 0 rounds of flips at most;
+        `state`: int8 [B, nM_max] initial state (1 active, 0 slack; None: all active; bilateral members are always
+        active).  The nominal areas are the batch's own A at the call.  A member is active where kind e > 0 for
+        e = c.(u_j1 - u_j0) - eps0 L0, the elongation beyond its stress-free length; the test is strict and has no
+        threshold, and all flips of an analysis are made at once.  Per analysis five launches: `trs_assemble` and
+        `trs_potrf_batched` of the effective areas, `trs_effects_rhs`, `trs_potrs_cases` and `trs_un_step`, which reads
+        the reduced solution from the case block and writes the next state and the next effective areas.  A converged
+        truss is frozen, as is one whose structure cannot be factored (`info != 0`: it goes back to the state before),
+        so a truss's results depend neither on the others nor on `check_every` nor on `max_iters` beyond its own count.
+        Every `check_every` analyses one int32 - the number of trusses still iterating - is downloaded to stop early.
+        Where a truss ended with status 2 the final states are analysed once more (its slab held a failed factor);
+        `trs_effects_recover` with the effective areas then gives the results.
+        Returns a dict of device tensors: u, f_ext [B, nJ_max, 3] in the caller's numbering, N [B, nM_max], state (int8
+        [B, nM_max]: 1 active, 0 slack and on the padding), status (int32 [B]: 0 converged, 1 iteration limit - the
+        simultaneous flips can cycle -, 2 a structure could not be factored - with `slack_factor` 0 a joint can lose its
+        last support), iterations, violations (int32 [B]: the members that still want to flip in the returned state; 0
+        when converged), flips_history (int32 [B, max_iters + 1]: the flips of every analysis, zero beyond the truss's
+        own count) and areas_effective [B, nM_max].  `self.info` holds 0, or for a truss of status 2 what the
+        factorisation reported, latched.  Afterwards `self.A` holds the effective areas and the slab the factor of the
+        final structure: `solve_cases`, `modes()` and the others may follow on "the structure with its slack cables
+        off" without another `factor()`; `generation` is bumped.  To get the nominal areas back, keep a copy and hand it
+        to `set_sections(A, E, rho)` - or read them from the packed batch.  A batch on the fused small-system path,
+        `options["compact"]` and the table member form are refused, as in `sizing()`."""
+        t = self.torch
+        who = "unilateral()"
+        self._need_slab("unilateral", "writes no slab that the load cases could be solved against")
+        if self.table:
+            raise ValueError(f"{who}: the table member form cannot hold one area per member - use the general form "
+                             "(PackedBatch.general())")
+        slack = _check_number(who, "slack_factor", slack_factor, "be a finite number >= 0", least=0)
+        max_iters = _check_integer(who, "max_iters", max_iters, least=0)
+        check_every = _check_integer(who, "check_every", check_every)
+        given = {"kind": (kind, t.int8, "int8", [self.B, self.nM_max]), "state": (state, t.int8, "int8", [self.B, self.nM_max]),
+                 "prestrain": (prestrain, t.float64, "float64", [self.B, self.nM_max]),
+                 "loads": (loads, t.float64, "float64", [self.B, self.nJ_max, 3])}
+        on = {}
+        for name, (x, dtype, word, shape) in given.items():
+            if x is None and name != "kind":
+                on[name] = None
+                continue
+            if not hasattr(x, "data_ptr") or list(x.shape) != shape or x.dtype != dtype or x.device != self.device:
+                raise ValueError(f"{who}: {name} must be {word} {shape} on {self.device}")
+            on[name] = x.contiguous()
+        if bool(((on["kind"] < -1) | (on["kind"] > 1)).any().item()):
+            raise ValueError(f"{who}: kind must hold 0 (bilateral), 1 (tension-only) or -1 (compression-only)")
+        H = max_iters + 1
+        out = self._out_tensors("unilateral", _field_shapes(UnilateralResult.CASE_FIELDS, self.B, self._sizes(H=H)), out)
+        if self.B == 0:
+            return out
+        if on["state"] is not None and on["state"].data_ptr() == out["state"].data_ptr():
+            on["state"] = on["state"].clone()   # (the state written is zeroed first)
+        self._need_fit("unilateral", self.lib.trs_un_fits(self.nJ_max, self.nM_max), "the step kernel (trs_un_fits)")
+        self._need_fit("unilateral", self.lib.trs_effects_fits(self.nJ_max, self.nM_max),
+                       "the effect kernels (trs_effects_fits)")
+        self._factored = False
+        self._dynamic = None
+        self._forward = None
+        ws = self._un_workspace(on, slack, max_iters, out)
+        with t.cuda.device(self.device):
+            self.dofmap()
+            for key in ("state", "violations", "flips_history"):
+                out[key].zero_()
+            if on["state"] is not None:   # the structure of analysis 0 (all active: the nominal areas as they are)
+                self.A.copy_(t.where((on["kind"] == 0) | (on["state"] != 0), ws["A_nom"], slack * ws["A_nom"]))
+            it = 0
+            while True:
+                last = it == max_iters
+                self._un_analyse(ws)
+                self._un_step(ws, it, 1 if last else 0)
+                if last or (it % check_every == 0 and int(ws["active"][it].item()) == 0):
+                    break
+                it += 1
+            if bool((ws["st"][:, 0] == _capi.UN_NOT_PD).any().item()):
+                # (that truss's slab holds the failed factor of a state it no longer has; the others get the same bits)
+                self._un_analyse(ws)
+                self._un_step(ws, it, 2)
+            jo, stream, _ = self._case_launch()
+            _capi.check(self.lib.trs_effects_recover(
+                self.B, 1, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *self._members(), self.rho.data_ptr(),
+                ws["loads"].data_ptr(), _ptr(on["prestrain"]), None, None, self.free_index.data_ptr(), self.nJ.data_ptr(),
+                self.nM.data_ptr(), ws["F"].data_ptr(), self.rows, out["u"].data_ptr(), out["f_ext"].data_ptr(),
+                out["N"].data_ptr(), None, jo, stream), "trs_effects_recover")
+            out["status"].copy_(ws["st"][:, 0])
+            out["iterations"].copy_(ws["st"][:, 1])
+            live = t.arange(self.nM_max, device=self.device)[None, :] < self.nM[:, None]
+            out["areas_effective"].copy_(t.where(live, self.A, t.zeros_like(self.A)))
+            # (what the factorisation reported for the structure that ended a truss with status 2; 0 for every other truss)
+            self.info.copy_(ws["st"][:, 2])
+        self.cases_F = ws["F"]
+        self._factored = True   # (of the final structure)
+        self._bump_generation()
+        return out
+
+    # the stages of `unilateral` (tools/bench_unilateral.py times them one by one)
+    def _un_workspace(self, on, slack, max_iters, out):
+        """The state of a `unilateral` run: the nominal areas (a copy), the state before the last flips, the status words
+        st [B, 4] and the `active` counters (one per analysis), zeroed; the case block; the loads in the caller's joint
+        numbering (the batch's own are carried there through `joint_out`)."""
+        t, dev = self.torch, self.device
+        loads = on["loads"]
+        if loads is None:
+            loads = self.loads
+            if self.joint_out is not None:
+                index = self.joint_out.long().unsqueeze(-1).expand(-1, -1, 3)
+                loads = t.zeros_like(self.loads).scatter_(1, index, self.loads)
+        return {"A_nom": self.A.clone(), "prev": t.zeros([self.B, max(self.nM_max, 1)], dtype=t.int8, device=dev),
+                "st": t.zeros([self.B, 4], dtype=t.int32, device=dev),
+                "active": t.zeros([max_iters + 1], dtype=t.int32, device=dev), "F": self._case_block("cases_F", 1),
+                "loads": loads.contiguous(), "on": on, "slack": slack, "max_iters": max_iters, "out": out}
+
+    def _un_analyse(self, ws):
+        """Assembly and factorisation of the structure `self.A`, right-hand side (with the pre-strain loads of these
+        areas) and substitution of the one case."""
+        jo, stream, _ = self._case_launch()
+        self.assemble()
+        self.potrf()
+        _capi.check(self.lib.trs_effects_rhs(
+            self.B, 1, self.nJ_max, self.nM_max, self.xyz.data_ptr(), *self._members(), self.rho.data_ptr(),
+            ws["loads"].data_ptr(), _ptr(ws["on"]["prestrain"]), None, None, self.free_index.data_ptr(),
+            self.n_free.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), jo, ws["F"].data_ptr(), self.rows, stream),
+            "trs_effects_rhs")
+        self._potrs_cases(ws["F"], 1)
+
+    def _un_step(self, ws, it, mode):
+        on, out = ws["on"], ws["out"]
+        _capi.check(self.lib.trs_un_step(
+            self.B, self.nJ_max, self.nM_max, self.xyz.data_ptr(), self.conn.data_ptr(), self.A.data_ptr(),
+            self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), ws["F"].data_ptr(),
+            self.rows, self.info.data_ptr(), _ptr(on["prestrain"]), on["kind"].data_ptr(), ws["A_nom"].data_ptr(),
+            ws["slack"], _ptr(on["state"]), it, mode, out["state"].data_ptr(), ws["prev"].data_ptr(), ws["st"].data_ptr(),
+            ws["active"][min(it, ws["max_iters"]):].data_ptr(), out["violations"].data_ptr(),
+            out["flips_history"].data_ptr(), ws["max_iters"] + 1, self._stream()), "trs_un_step")
+
     # -- linear buckling: critical load factors from shifted factors of K + theta Kg (include/trs_buckling.h) ------------
     def buckling(self, p, shift=0.0, max_shifts=6, tol=1e-10, max_iters=256, check_every=4, out=None):
         """Linear buckling of the resident batch under its own loads (`factor()` first; include/trs_buckling.h): the
@@ -4925,6 +5068,151 @@ def solve_min_compliance(trusses_or_packed, loads=None, alpha=None, target=None,
             measure=val["measure"], eta=val["eta"], move=val["move"], area_min=bound(part, on["area_min"]),
             area_max=bound(part, on["area_max"]), tol=val["tol"], max_iters=val["max_iters"],
             check_every=val["check_every"]))
+    return _finish_result(torch, dev, out, on_device)
+
+
+@dataclass
+class UnilateralResult:
+    """Results of `solve_unilateral`, per truss and load case, all describing the state the truss ended with: displace,
+    external [B, L, nJ_max, 3] (the caller's joint numbering), internal [B, L, nM_max] (0 in a member removed exactly),
+    state (int8 [B, L, nM_max]: 1 active, 0 slack and on the padding; bilateral members are always 1), status (int32
+    [B, L]: 0 converged, 1 iteration limit, 2 a structure could not be factored - the truss went back to the state
+    before), iterations [B, L] (rounds of flips behind the returned state), violations (int32 [B, L]: the members that
+    still want to flip in the returned state; 0 when converged), flips_history (int32 [B, L, max_iters + 1]: the flips
+    of every analysis, zero beyond the truss's own count), areas_effective [B, L, nM_max].  info [B]: 0, or what the
+    factorisation reported in the first case that ended the truss with status 2."""
+    displace: np.ndarray
+    external: np.ndarray
+    internal: np.ndarray
+    state: np.ndarray
+    status: np.ndarray
+    iterations: np.ndarray
+    violations: np.ndarray
+    flips_history: np.ndarray
+    areas_effective: np.ndarray
+    info: np.ndarray
+
+    #: one load case, as `DeviceBatch.unilateral` returns it; FIELDS puts the case axis in front
+    CASE_FIELDS = {"displace": ("u", 0.0, "float64", ("nJ", 3)), "external": ("f_ext", 0.0, "float64", ("nJ", 3)),
+                   "internal": ("N", 0.0, "float64", ("nM",)), "state": ("state", 0, "int8", ("nM",)),
+                   "status": ("status", 0, "int32", ()), "iterations": ("iterations", 0, "int32", ()),
+                   "violations": ("violations", 0, "int32", ()), "flips_history": ("flips_history", 0, "int32", ("H",)),
+                   "areas_effective": ("areas_effective", 0.0, "float64", ("nM",))}
+    FIELDS = {field: (key, fill, dtype, ("L",) + shape) for field, (key, fill, dtype, shape) in CASE_FIELDS.items()}
+
+
+def _check_unilateral_args(packed, kind, loads=None, prestrain=None, slack_factor=0.0, max_iters=20, check_every=1,
+                           state=None, options=None, sections=None, max_result_bytes=4 << 30):
+    """The argument errors of `solve_unilateral` that need no device (ValueError).  Returns the arguments checked:
+    "kind" (int8 [B, nM_max], zero on the padding), "loads" (float64 [B, L, nJ_max, 3] or None for the batch's own
+    loads), "prestrain" (float64 [B, L, nM_max] or None), "state" (int8 [B, nM_max] of 0 / 1, or None), "L",
+    "slack_factor", "max_iters", "check_every"."""
+    who = "solve_unilateral"
+    _refuse_sections(who, "unilateral members (the iteration writes the areas)", sections)
+    if options and options.get("compact"):
+        raise ValueError(f"{who}: options['compact'] writes no slab that the load cases could be solved against")
+    B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
+    val = {"slack_factor": _check_number(who, "slack_factor", slack_factor, "be a finite number >= 0", least=0),
+           "max_iters": _check_integer(who, "max_iters", max_iters, least=0),
+           "check_every": _check_integer(who, "check_every", check_every)}
+    live = np.arange(nM_max)[None, :] < np.asarray(packed.nM).reshape(B, 1)
+
+    def members(name, x, what):
+        try:
+            x = _host_array(x, np.float64)
+        except (TypeError, ValueError):
+            x = None
+        if x is None or x.shape != (B, nM_max) or not np.isfinite(x).all():
+            raise ValueError(f"{who}: {name} must be [B={B}, nM_max={nM_max}] of {what}, got "
+                             f"{None if x is None else x.shape}")
+        return np.where(live, x, 0.0)
+    if kind is None:
+        raise ValueError(f"{who}: kind must be given")
+    k = members("kind", kind, "0 (bilateral), 1 (tension-only) and -1 (compression-only)")
+    if not np.isin(k, (-1.0, 0.0, 1.0)).all():
+        raise ValueError(f"{who}: kind must hold 0 (bilateral), 1 (tension-only) or -1 (compression-only)")
+    val["kind"] = np.ascontiguousarray(k.astype(np.int8))
+    val["state"] = None
+    if state is not None:
+        val["state"] = np.ascontiguousarray((members("state", state, "1 (active) and 0 (slack)") != 0).astype(np.int8))
+    val["loads"], val["prestrain"], L = None, None, None
+    if loads is not None:
+        try:
+            x = _host_array(loads, np.float64)
+        except (TypeError, ValueError):
+            x = None
+        shape = None if x is None else tuple(x.shape)
+        if x is None or len(shape) != 4 or shape[0] != B or shape[1] < 1 or shape[2] != nJ_max or shape[3] not in (2, 3):
+            raise ValueError(f"{who}: loads must be [B={B}, L >= 1, nJ_max={nJ_max}, 2 or 3], got {shape}")
+        if not np.isfinite(x).all():
+            raise ValueError(f"{who}: loads must be finite")
+        val["loads"], L = np.ascontiguousarray(np.pad(x, [(0, 0)] * 3 + [(0, 3 - shape[3])])), shape[1]
+    if prestrain is not None:
+        try:
+            x = _host_array(prestrain, np.float64)
+        except (TypeError, ValueError):
+            x = None
+        shape = None if x is None else tuple(x.shape)
+        if x is None or len(shape) != 3 or shape[0] != B or shape[1] < 1 or shape[2] != nM_max or not np.isfinite(x).all():
+            raise ValueError(f"{who}: prestrain must be finite [B={B}, L >= 1, nM_max={nM_max}], got {shape}")
+        if L is not None and shape[1] != L:
+            raise ValueError(f"{who}: prestrain has L = {shape[1]}, loads L = {L}")
+        val["prestrain"], L = np.ascontiguousarray(x), shape[1]
+    val["L"] = 1 if L is None else L
+    nbytes = B * val["L"] * (8 * 6 * nJ_max + (8 + 8 + 1) * nM_max + 4 * (val["max_iters"] + 1) + 12)
+    if nbytes > max_result_bytes:
+        raise ValueError(f"{who}: the results of B={B} trusses take {nbytes} bytes, more than max_result_bytes = "
+                         f"{max_result_bytes}")
+    return val
+
+
+def solve_unilateral(trusses_or_packed, kind, loads=None, prestrain=None, slack_factor=0.0, max_iters=20, check_every=1,
+                     state=None, device=None, reorder=False, options=None, on_device=False, sections=None,
+                     use_envelope=True, max_slab_bytes=64 << 30, max_result_bytes=4 << 30):
+    """Analyse every truss of a batch with members that carry tension only or compression only - cables, tie rods,
+    slender counter-bracing, struts that bear against a seat - by the active-set iteration (include/trs_unilateral.h,
+    `DeviceBatch.unilateral`): analyse, switch off every unilateral member that is strained the wrong way, switch on
+    every one that would be strained the right way, repeat until nothing changes.  `kind`: [B, nM_max] of 0 (bilateral),
+    1 (tension-only), -1 (compression-only); `loads`: [B, L, nJ_max, dim] (numpy or torch; the caller's joint numbering;
+    dim 2 or 3) or None for the batch's own loads; `prestrain`: [B, L, nM_max] member initial strains as
+    `solve_effect_cases` takes them (pretension is a negative eps0) or None; both given agree on L.  Every case is an
+    independent run from the nominal areas - the active set differs per case, so the cases share the upload and nothing
+    else - looped on the resident bucket.  `slack_factor` >= 0: the fraction of its area a slack member keeps (0 removes
+    it exactly; a small positive value lets the iteration walk through states in which a joint has lost its last
+    support); `max_iters`: rounds of flips at most; `check_every`: how often the host looks whether every truss is
+    done; `state`: [B, nM_max] initial state of every case (1 active, 0 slack; None: all active).  What the method is
+    not: the answer is the linear small-displacement one - no cable sag, no geometric stiffness -, all flips are made at
+    once, which can cycle (status 1 with `violations` > 0), and self-weight is not re-formed with the effective areas:
+    pass it as joint loads.  A table-form batch is converted with `.general()`.  Buckets, `reorder` plans,
+    `options`, `on_device` and `use_envelope` as `solve_load_cases`.  Bad arguments (`_check_unilateral_args`) raise
+    ValueError before any device work.  Returns a `UnilateralResult`."""
+    packed = _as_packed(trusses_or_packed)
+    val = _check_unilateral_args(packed, kind, loads, prestrain, slack_factor, max_iters, check_every, state, options,
+                                 sections, max_result_bytes)
+    if packed.is_table:
+        packed = packed.general()
+    torch, dev = _require_gpu(device)
+    L = val["L"]
+    out = _new_result(torch, dev, UnilateralResult, packed.B,
+                      {"L": L, "nJ": packed.nJ_max, "nM": packed.nM_max, "H": val["max_iters"] + 1})
+    up = lambda x: None if x is None else torch.from_numpy(x).to(dev)
+    on = {k: up(val[k]) for k in ("kind", "state", "loads", "prestrain")}
+    case = lambda x, l: None if x is None else x[:, l].contiguous()
+    for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope,
+                                      factor=lambda db, part: None):
+        nominal = db.A.clone()
+        kinds, states = part.cut(on["kind"], nM=1), part.cut(on["state"], nM=1)
+        forces, strains = part.cut(on["loads"], nJ=2), part.cut(on["prestrain"], nM=2)
+        info = torch.zeros_like(db.info)
+        for l in range(L):
+            db.A.copy_(nominal)
+            res = db.unilateral(kinds, case(forces, l), case(strains, l), slack_factor=val["slack_factor"],
+                                max_iters=val["max_iters"], check_every=val["check_every"], state=states)
+            for field, (key, fill, dtype, shape) in UnilateralResult.CASE_FIELDS.items():
+                part.put(getattr(out, field)[:, l], res[key], nJ=1 if "nJ" in shape else None,
+                         nM=1 if "nM" in shape else None)
+            info = torch.where(info != 0, info, db.info)
+        db.info.copy_(info)
     return _finish_result(torch, dev, out, on_device)
 
 

@@ -748,6 +748,71 @@ class Truss:
                 "iterations": int(result.iterations[0]), "status": int(result.status[0]),
                 "objective_history": result.objective_history[0].copy()}
 
+    def SolveUnilateral(self, kinds, cases=None, slackFactor=0.0, maxIters=20):
+        """Solve this truss with members that carry tension only or compression only - cables, tie rods, counter-bracing,
+        struts that bear against a seat - by the active-set iteration (`batch.solve_unilateral`): every case is analysed,
+        the unilateral members that are strained the wrong way are switched off, those that would be strained the right
+        way are switched on, until nothing changes.  `kinds`: {memberID: "tension" | "compression"} (the others are
+        ordinary members), or one value per member of 0, 1 (tension-only), -1 (compression-only); `cases`: a list of
+        `{jointID: vector}` dicts as `SolveLoadCases` takes them, or of `LoadCase`s with forces and prestrains
+        (pretension is a negative pre-strain; settlements and gravity are not taken) - None: the truss's own forces as
+        one case; `slackFactor` >= 0: the fraction of its area a slack member keeps (0 removes it); `maxIters`: rounds of
+        flips at most.  Returns a list, one dict per case:
+          "displacements" [nJ, dim], "forces" [nM] (member forces, tension positive), "reactions" [nJ, dim] (what the
+          supports supply; zero rows at free joints), "slack" (the IDs of the slack members), "status" (0 converged, 1
+          iteration limit, 2 a structure could not be factored), "iterations", "violations".
+        The linear small-displacement answer: no cable sag, no geometric stiffness.  The truss itself, its JSON format
+        and `MemberType` stay as they are.  Raises ValueError for bad arguments (as `batch.solve_unilateral`) and
+        `TrussNotStableError` when the counting test fails."""
+        if not self.isStable:
+            raise TrussNotStableError("The truss is not stable !")
+        from .batch import pack_trusses, solve_unilateral  # late import: keeps the model importable without torch
+        packed = pack_trusses([self])
+        nJ, nM, dim = len(self._pos), len(self._bars), self._dim
+        kind = np.zeros([1, packed.nM_max])
+        if isinstance(kinds, dict):
+            words = {"tension": 1, "compression": -1}
+            for memberID, word in kinds.items():
+                if not (isinstance(memberID, (int, np.integer)) and 0 <= memberID < nM):
+                    raise ValueError(f"SolveUnilateral: no such member [{memberID}] in kinds")
+                if word not in words:
+                    raise ValueError(f"SolveUnilateral: kinds[{memberID}] must be 'tension' or 'compression', got {word!r}")
+                kind[0, memberID] = words[word]
+        else:
+            row = np.asarray(kinds, dtype=np.float64)
+            if row.shape != (nM,):
+                raise ValueError(f"SolveUnilateral: kinds must be a dict or hold one value per member ({nM}), got "
+                                 f"{row.shape}")
+            kind[0, :nM] = row
+        loads, prestrain = None, None
+        if cases is not None:
+            cases = list(cases)
+            if not cases:
+                return []
+            if any(isinstance(c, LoadCase) for c in cases):
+                cases = [c if isinstance(c, LoadCase) else LoadCase(forces=c) for c in cases]
+                if any(c.settlements or c.gravity is not None for c in cases):
+                    raise ValueError("SolveUnilateral: a case may carry forces and prestrains only - pass self-weight as "
+                                     "joint forces")
+                dense = pack_load_cases(cases, nJ, nM, dim)
+                loads = self._case_loads([c.forces for c in cases], packed.nJ_max)
+                if dense["prestrain"] is not None:
+                    prestrain = np.zeros([1, len(cases), packed.nM_max])
+                    prestrain[0, :, :nM] = dense["prestrain"][0]
+            else:
+                loads = self._case_loads(cases, packed.nJ_max)
+        result = solve_unilateral(packed, kind, loads, prestrain, slack_factor=slackFactor, max_iters=maxIters)
+        held = packed.constrained()[0, :nJ, :dim]
+        out = []
+        for k in range(result.status.shape[1]):
+            slack = np.flatnonzero((kind[0, :nM] != 0) & (result.state[0, k, :nM] == 0))
+            out.append({"displacements": result.displace[0, k, :nJ, :dim].copy(),
+                        "forces": result.internal[0, k, :nM].copy(),
+                        "reactions": np.where(held, result.external[0, k, :nJ, :dim], 0.0),
+                        "slack": [int(m) for m in slack], "status": int(result.status[0, k]),
+                        "iterations": int(result.iterations[0, k]), "violations": int(result.violations[0, k])})
+        return out
+
     def MemberLoss(self, cases=None, rTol=None, returnForces=False):
         """What the loss of any ONE member does to this truss, for every member and every load case, from ONE
         factorisation (`batch.solve_member_loss`): `cases` is a list of `{jointID: vector}` dicts as `SolveLoadCases`
