@@ -44,7 +44,7 @@ __all__ = ["Truss", "Member", "MemberType", "SupportType", "MetapathType", "Task
            "solve_member_sets", "MemberSetResult", "solve_transient", "TransientResult",
            "solve_nonlinear", "NonlinearResult", "solve_buckling", "BucklingResult",
            "solve_sizing", "SizingResult", "solve_min_compliance", "MinComplianceResult",
-           "solve_unilateral", "UnilateralResult"]
+           "solve_unilateral", "UnilateralResult", "solve_plastic", "PlasticResult"]
 
 
 def __getattr__(name):
@@ -56,7 +56,7 @@ def __getattr__(name):
                 "solve_nonlinear", "NonlinearResult", "solve_buckling", "BucklingResult", "solve_mode_gradients",
                 "ModeGradientResult", "solve_response_spectrum", "SpectrumResult", "solve_harmonic",
                 "HarmonicResult", "solve_sizing", "SizingResult", "solve_min_compliance", "MinComplianceResult",
-                "solve_unilateral", "UnilateralResult"):
+                "solve_unilateral", "UnilateralResult", "solve_plastic", "PlasticResult"):
         from . import batch
         return getattr(batch, name)
     if name == "DifferentiableTruss":

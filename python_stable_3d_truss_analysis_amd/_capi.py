@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h`, `include/trs_influence.h`, `include/trs_sets.h`, `include/trs_dynamics.h`, `include/trs_nonlinear.h`, `include/trs_buckling.h`, `include/trs_modegrad.h`, `include/trs_spectrum.h`, `include/trs_harmonic.h`, `include/trs_sizing.h`, `include/trs_compliance.h` and `include/trs_unilateral.h` (library: `libtrs_hip.so`, in-tree).
+"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h`, `include/trs_influence.h`, `include/trs_sets.h`, `include/trs_dynamics.h`, `include/trs_nonlinear.h`, `include/trs_buckling.h`, `include/trs_modegrad.h`, `include/trs_spectrum.h`, `include/trs_harmonic.h`, `include/trs_sizing.h`, `include/trs_compliance.h`, `include/trs_unilateral.h` and `include/trs_plastic.h` (library: `libtrs_hip.so`, in-tree).
 
 There is no fallback: if the library is missing, `load()` raises `HipExtensionError`.
 """
@@ -240,6 +240,16 @@ UN_SIGNATURES = {
                          _P, _I, _P]),
 }
 
+#: every symbol `include/trs_plastic.h` declares (collapse load: the event-to-event elastic-plastic analysis on the device;
+#: csrc/plastic.hip, the same library).  General member form only, as the member sizing
+PL_SIGNATURES = {
+    "trs_pl_abi_version": (_I, []),
+    "trs_pl_fits": (_I, [_I, _I]),
+    "trs_pl_step": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _D, _D, _D, _D, _D, _I, _I, _P,
+                         _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "trs_pl_finish": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+}
+
 #: must equal TRS_ABI_VERSION of include/trs_solver.h
 ABI_VERSION = 10
 #: must equal TRS_MODES_ABI_VERSION of include/trs_modes.h
@@ -270,6 +280,8 @@ SZ_ABI_VERSION = 1
 CM_ABI_VERSION = 1
 #: must equal TRS_UN_ABI_VERSION of include/trs_unilateral.h
 UN_ABI_VERSION = 1
+#: must equal TRS_PL_ABI_VERSION of include/trs_plastic.h
+PL_ABI_VERSION = 1
 #: TRS_RS_SRSS, TRS_RS_CQC, TRS_RS_ABS of include/trs_spectrum.h: the modal combination rules
 RS_RULES = {"srss": 0, "cqc": 1, "abs": 2}
 #: TRS_NL_* of include/trs_nonlinear.h: the status of a truss in a load step of the nonlinear analysis
@@ -282,6 +294,8 @@ CM_ACTIVE, CM_CONVERGED, CM_ITER_LIMIT, CM_NOT_PD = -1, 0, 1, 2
 CM_MEASURES = {"weight": 0, "volume": 1}
 #: TRS_UN_* of include/trs_unilateral.h: the status of a truss in a run of the active-set iteration
 UN_ACTIVE, UN_CONVERGED, UN_ITER_LIMIT, UN_NOT_PD = -1, 0, 1, 2
+#: TRS_PL_* of include/trs_plastic.h: the status of a truss in a run of the event-to-event analysis
+PL_ACTIVE, PL_LAMBDA_MAX, PL_EVENT_LIMIT, PL_MECHANISM, PL_DISP_LIMIT = -1, 0, 1, 2, 3
 #: TRS_SETS_MAX of include/trs_sets.h: members per scenario at most
 SETS_MAX = 8
 #: TRS_MODES_BLOCK of include/trs_modes.h: vectors per truss of the block iteration (one case group)
@@ -338,7 +352,7 @@ def load():
             (BK_SIGNATURES, "trs_bk_abi_version", BK_ABI_VERSION), (MG_SIGNATURES, "trs_mg_abi_version", MG_ABI_VERSION),
             (RS_SIGNATURES, "trs_rs_abi_version", RS_ABI_VERSION), (HR_SIGNATURES, "trs_hr_abi_version", HR_ABI_VERSION),
             (SZ_SIGNATURES, "trs_sz_abi_version", SZ_ABI_VERSION), (CM_SIGNATURES, "trs_cm_abi_version", CM_ABI_VERSION),
-            (UN_SIGNATURES, "trs_un_abi_version", UN_ABI_VERSION)):
+            (UN_SIGNATURES, "trs_un_abi_version", UN_ABI_VERSION), (PL_SIGNATURES, "trs_pl_abi_version", PL_ABI_VERSION)):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

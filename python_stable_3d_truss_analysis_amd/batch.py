@@ -2490,6 +2490,138 @@ class DeviceBatch:
             ws["active"][min(it, ws["max_iters"]):].data_ptr(), out["violations"].data_ptr(),
             out["flips_history"].data_ptr(), ws["max_iters"] + 1, self._stream()), "trs_un_step")
 
+    # -- collapse load: elastic-plastic members, event to event on the device (include/trs_plastic.h) -------------------
+    def plastic(self, cap_tension, cap_compression, loads=None, hardening=0.0, lambda_max=1.0, disp_limit=0.0,
+                collapse_ratio=1e8, tie_tol=1e-9, max_events=64, check_every=1, out=None):
+        """How much of one load pattern the trusses of the resident batch carry before they collapse, and in which order
+        their members give way: the event-to-event elastic-plastic analysis of include/trs_plastic.h.  The pattern
+        `loads` (float64 device tensor [B, nJ_max, 3] in the CALLER's joint numbering; None: the batch's own loads) is
+        scaled by the load factor lambda; `cap_tension`, `cap_compression`: float64 device tensors [B, nM_max] of
+        positive member capacities (forces; the padding is not looked at); `hardening` >= 0: the fraction of its
+        stiffness a yielded member keeps (0: perfectly plastic, the member's area is scaled to exactly 0);
+        `lambda_max` > 0 and `disp_limit` >= 0 (the largest |u_d| of a DOF; 0: none) end a run with status 0 and 3;
+        `collapse_ratio` > 1: a tangent structure that moves more than this many times what the elastic one does per
+        unit load is a mechanism that the factorisation let through on rounding noise (status 2 with info 0);
+        `tie_tol` >= 0: members within this relative distance of the governing step yield with it in one event;
+        `max_events` >= 0 events at most (status 1).  The nominal areas are the batch's own A at the call.  Every
+        analysis finds the load increment at which the next elastic member reaches its capacity, advances the
+        accumulated forces, displacements and load factor by it and lets that member yield: it goes on carrying its
+        capacity while the rest picks up the difference.  A yielded member that would unload returns to elastic (an
+        event of its own).  Per analysis five launches: `trs_assemble` and `trs_potrf_batched` of the effective areas,
+        `trs_gather_cases`, `trs_potrs_cases` and `trs_pl_step`.  A truss that has ended is frozen, so a truss's results
+        depend neither on the others nor on `check_every` nor on a larger `max_events`.  Every `check_every` analyses
+        one int32 - the number of trusses still going - is downloaded to stop early.  `trs_pl_finish` then writes the
+        results from the accumulated state; nothing is analysed again.
+        Returns a dict of device tensors: u, f_ext [B, nJ_max, 3] in the caller's numbering (f_ext: lambda P at the free
+        DOFs, the reactions at the held ones), N [B, nM_max], state (int8 [B, nM_max]: 0 elastic and on the padding, +1
+        yielded in tension, -1 in compression), status (int32 [B]: 0 lambda_max reached, 1 event limit, 2 mechanism -
+        the collapse load is `load_factor` -, 3 displacement limit), events (int32 [B]), load_factor [B], and per
+        analysis k < max_events + 1 lambda_history, umax_history (the pushover curve), member_history (int32: the
+        governing member, -1 a release, -2 the terminal analysis) and count_history (members yielded or released), zero
+        beyond the truss's own count; areas_effective [B, nM_max].  `self.info` holds 0, or for a truss that ended as a
+        mechanism because its tangent could not be factored what the factorisation reported, latched; the slab holds no
+        valid factor of such a truss.  For every other truss `self.A` holds the effective areas and the slab their
+        factor: `solve_cases` and the others may follow on the tangent structure without another `factor()`;
+        `generation` is bumped.  A batch on the fused small-system path, `options["compact"]` and the table member form
+        are refused, as in `sizing()`."""
+        t = self.torch
+        who = "plastic()"
+        self._need_slab("plastic", "writes no slab that the load pattern could be solved against")
+        if self.table:
+            raise ValueError(f"{who}: the table member form cannot hold one area per member - use the general form "
+                             "(PackedBatch.general())")
+        val = _check_plastic_scalars(who, hardening, lambda_max, disp_limit, collapse_ratio, tie_tol, max_events, check_every)
+        given = {"cap_tension": (cap_tension, [self.B, self.nM_max]), "cap_compression": (cap_compression, [self.B, self.nM_max]),
+                 "loads": (loads, [self.B, self.nJ_max, 3])}
+        on = {}
+        for name, (x, shape) in given.items():
+            if x is None and name == "loads":
+                on[name] = None
+                continue
+            if not hasattr(x, "data_ptr") or list(x.shape) != shape or x.dtype != t.float64 or x.device != self.device:
+                raise ValueError(f"{who}: {name} must be float64 {shape} on {self.device}")
+            on[name] = x.contiguous()
+        live = t.arange(self.nM_max, device=self.device)[None, :] < self.nM[:, None]
+        for name in ("cap_tension", "cap_compression"):
+            if bool((live & ~((on[name] > 0) & t.isfinite(on[name]))).any().item()):
+                raise ValueError(f"{who}: {name} must be positive and finite")
+        H = val["max_events"] + 1
+        out = self._out_tensors("plastic", _field_shapes(PlasticResult.CASE_FIELDS, self.B, self._sizes(H=H)), out)
+        if self.B == 0:
+            return out
+        self._need_fit("plastic", self.lib.trs_pl_fits(self.nJ_max, self.nM_max), "the step kernel (trs_pl_fits)")
+        self._factored = False
+        self._dynamic = None
+        self._forward = None
+        ws = self._pl_workspace(on, val, out)
+        with t.cuda.device(self.device):
+            self.dofmap()
+            for key in ("N", "state", "lambda_history", "umax_history", "member_history", "count_history"):
+                out[key].zero_()
+            it = 0
+            while True:
+                last = it == val["max_events"]
+                self._pl_analyse(ws)
+                self._pl_step(ws, it, 1 if last else 0)
+                if last or (it % val["check_every"] == 0 and int(ws["active"][it].item()) == 0):
+                    break
+                it += 1
+            jo, stream, _ = self._case_launch()
+            _capi.check(self.lib.trs_pl_finish(
+                self.B, self.nJ_max, self.nM_max, self.xyz.data_ptr(), self.conn.data_ptr(), self.free_index.data_ptr(),
+                self.n_free.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), self.rows, ws["loads"].data_ptr(),
+                out["N"].data_ptr(), ws["U"].data_ptr(), ws["acc"].data_ptr(), jo, out["u"].data_ptr(),
+                out["f_ext"].data_ptr(), stream), "trs_pl_finish")
+            out["status"].copy_(ws["st"][:, 0])
+            out["events"].copy_(ws["st"][:, 1])
+            out["load_factor"].copy_(ws["acc"][:, 0])
+            out["areas_effective"].copy_(t.where(live, self.A, t.zeros_like(self.A)))
+            # (what the factorisation reported for the tangent that ended a truss as a mechanism; 0 for every other truss)
+            self.info.copy_(ws["st"][:, 2])
+        self.cases_F = ws["F"]
+        self._factored = True   # (of the final tangent structure, where info is 0)
+        self._bump_generation()
+        return out
+
+    # the stages of `plastic` (tools/bench_plastic.py times them one by one)
+    def _pl_workspace(self, on, val, out):
+        """The state of a `plastic` run: the nominal areas (a copy), the accumulated displacements U [B, 3 nJ_max] in the
+        batch's joint order, acc [B, 4] (lambda, r_0, the largest |u_d|), the status words st [B, 4] and the `active`
+        counters (one per analysis), zeroed; the case block; the load pattern in the caller's joint numbering (the
+        batch's own is carried there through `joint_out`)."""
+        t, dev = self.torch, self.device
+        loads = on["loads"]
+        if loads is None:
+            loads = self.loads
+            if self.joint_out is not None:
+                index = self.joint_out.long().unsqueeze(-1).expand(-1, -1, 3)
+                loads = t.zeros_like(self.loads).scatter_(1, index, self.loads)
+        return {"A_nom": self.A.clone(), "U": t.zeros([self.B, 3 * self.nJ_max], dtype=t.float64, device=dev),
+                "acc": t.zeros([self.B, 4], dtype=t.float64, device=dev),
+                "st": t.zeros([self.B, 4], dtype=t.int32, device=dev),
+                "active": t.zeros([val["max_events"] + 1], dtype=t.int32, device=dev), "F": self._case_block("cases_F", 1),
+                "loads": loads.contiguous(), "on": on, "val": val, "out": out}
+
+    def _pl_analyse(self, ws):
+        """Assembly and factorisation of the structure `self.A`, gather and substitution of the load pattern."""
+        self.assemble()
+        self.potrf()
+        self._gather_cases(ws["loads"], 1, ws["F"])
+        self._potrs_cases(ws["F"], 1)
+
+    def _pl_step(self, ws, it, mode):
+        on, val, out = ws["on"], ws["val"], ws["out"]
+        _capi.check(self.lib.trs_pl_step(
+            self.B, self.nJ_max, self.nM_max, self.xyz.data_ptr(), self.conn.data_ptr(), self.E.data_ptr(),
+            self.A.data_ptr(), self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(),
+            ws["F"].data_ptr(), self.rows, self.info.data_ptr(), on["cap_tension"].data_ptr(),
+            on["cap_compression"].data_ptr(), ws["A_nom"].data_ptr(), val["hardening"], val["lambda_max"],
+            val["disp_limit"], val["collapse_ratio"], val["tie_tol"], it, mode, out["state"].data_ptr(),
+            out["N"].data_ptr(), ws["U"].data_ptr(), ws["acc"].data_ptr(), ws["st"].data_ptr(),
+            ws["active"][min(it, val["max_events"]):].data_ptr(), out["lambda_history"].data_ptr(),
+            out["member_history"].data_ptr(), out["count_history"].data_ptr(), out["umax_history"].data_ptr(),
+            val["max_events"] + 1, self._stream()), "trs_pl_step")
+
     # -- linear buckling: critical load factors from shifted factors of K + theta Kg (include/trs_buckling.h) ------------
     def buckling(self, p, shift=0.0, max_shifts=6, tol=1e-10, max_iters=256, check_every=4, out=None):
         """Linear buckling of the resident batch under its own loads (`factor()` first; include/trs_buckling.h): the
@@ -5209,6 +5341,151 @@ def solve_unilateral(trusses_or_packed, kind, loads=None, prestrain=None, slack_
             res = db.unilateral(kinds, case(forces, l), case(strains, l), slack_factor=val["slack_factor"],
                                 max_iters=val["max_iters"], check_every=val["check_every"], state=states)
             for field, (key, fill, dtype, shape) in UnilateralResult.CASE_FIELDS.items():
+                part.put(getattr(out, field)[:, l], res[key], nJ=1 if "nJ" in shape else None,
+                         nM=1 if "nM" in shape else None)
+            info = torch.where(info != 0, info, db.info)
+        db.info.copy_(info)
+    return _finish_result(torch, dev, out, on_device)
+
+
+@dataclass
+class PlasticResult:
+    """Results of `solve_plastic`, per truss and load case, all describing the equilibrium state of the truss's last
+    completed event: displace, external [B, L, nJ_max, 3] (the caller's joint numbering; external is lambda P at the free
+    DOFs and the reactions at the held ones), internal [B, L, nM_max], state (int8 [B, L, nM_max]: 0 elastic and on the
+    padding, +1 yielded in tension, -1 in compression), status (int32 [B, L]: 0 lambda_max reached, 1 event limit, 2
+    mechanism - load_factor is the collapse load -, 3 displacement limit), events [B, L], load_factor [B, L], and per
+    analysis k lambda_history, umax_history [B, L, max_events + 1] (the pushover curve), member_history (int32: the
+    governing member, -1 a release, -2 the terminal analysis), count_history (the members yielded or released), zero
+    beyond the truss's own count; areas_effective [B, L, nM_max].  info [B]: 0, or what the factorisation reported in the
+    first case that ended the truss as a mechanism its tangent could not be factored for."""
+    displace: np.ndarray
+    external: np.ndarray
+    internal: np.ndarray
+    state: np.ndarray
+    status: np.ndarray
+    events: np.ndarray
+    load_factor: np.ndarray
+    lambda_history: np.ndarray
+    umax_history: np.ndarray
+    member_history: np.ndarray
+    count_history: np.ndarray
+    areas_effective: np.ndarray
+    info: np.ndarray
+
+    #: one load case, as `DeviceBatch.plastic` returns it; FIELDS puts the case axis in front
+    CASE_FIELDS = {"displace": ("u", 0.0, "float64", ("nJ", 3)), "external": ("f_ext", 0.0, "float64", ("nJ", 3)),
+                   "internal": ("N", 0.0, "float64", ("nM",)), "state": ("state", 0, "int8", ("nM",)),
+                   "status": ("status", 0, "int32", ()), "events": ("events", 0, "int32", ()),
+                   "load_factor": ("load_factor", 0.0, "float64", ()),
+                   "lambda_history": ("lambda_history", 0.0, "float64", ("H",)),
+                   "umax_history": ("umax_history", 0.0, "float64", ("H",)),
+                   "member_history": ("member_history", 0, "int32", ("H",)),
+                   "count_history": ("count_history", 0, "int32", ("H",)),
+                   "areas_effective": ("areas_effective", 0.0, "float64", ("nM",))}
+    FIELDS = {field: (key, fill, dtype, ("L",) + shape) for field, (key, fill, dtype, shape) in CASE_FIELDS.items()}
+
+
+def _check_plastic_scalars(who, hardening, lambda_max, disp_limit, collapse_ratio, tie_tol, max_events, check_every):
+    """The scalar rules of the collapse-load analysis (ValueError), for `DeviceBatch.plastic` and `solve_plastic`."""
+    return {"hardening": _check_number(who, "hardening", hardening, "be a finite number >= 0", least=0),
+            "lambda_max": _check_number(who, "lambda_max", lambda_max, "be a finite number > 0", above=0),
+            "disp_limit": _check_number(who, "disp_limit", disp_limit, "be a finite number >= 0 (0: no limit)", least=0),
+            "collapse_ratio": _check_number(who, "collapse_ratio", collapse_ratio, "be a finite number > 1", above=1),
+            "tie_tol": _check_number(who, "tie_tol", tie_tol, "be a finite number >= 0", least=0),
+            "max_events": _check_integer(who, "max_events", max_events, least=0),
+            "check_every": _check_integer(who, "check_every", check_every)}
+
+
+def _check_plastic_args(packed, cap_tension, cap_compression, loads=None, hardening=0.0, lambda_max=1.0, disp_limit=0.0,
+                        collapse_ratio=1e8, tie_tol=1e-9, max_events=64, check_every=1, options=None, sections=None,
+                        max_result_bytes=4 << 30):
+    """The argument errors of `solve_plastic` that need no device (ValueError).  Returns the arguments checked:
+    "cap_tension", "cap_compression" (float64 [B, nM_max], 1 on the padding), "loads" (float64 [B, L, nJ_max, 3] or None
+    for the batch's own loads), "L" and the scalars."""
+    who = "solve_plastic"
+    _refuse_sections(who, "the collapse-load analysis (the iteration writes the areas)", sections)
+    if options and options.get("compact"):
+        raise ValueError(f"{who}: options['compact'] writes no slab that the load pattern could be solved against")
+    B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
+    val = _check_plastic_scalars(who, hardening, lambda_max, disp_limit, collapse_ratio, tie_tol, max_events, check_every)
+    live = np.arange(nM_max)[None, :] < np.asarray(packed.nM).reshape(B, 1)
+    for name, x in (("cap_tension", cap_tension), ("cap_compression", cap_compression)):
+        try:
+            x = None if x is None else _host_array(x, np.float64)
+        except (TypeError, ValueError):
+            x = None
+        if x is None or x.shape != (B, nM_max):
+            raise ValueError(f"{who}: {name} must be [B={B}, nM_max={nM_max}] of positive forces, got "
+                             f"{None if x is None else x.shape}")
+        x = np.where(live, x, 1.0)
+        if not (np.isfinite(x) & (x > 0)).all():
+            raise ValueError(f"{who}: {name} must be positive and finite")
+        val[name] = np.ascontiguousarray(x)
+    val["loads"], L = None, 1
+    if loads is not None:
+        try:
+            x = _host_array(loads, np.float64)
+        except (TypeError, ValueError):
+            x = None
+        shape = None if x is None else tuple(x.shape)
+        if x is None or len(shape) != 4 or shape[0] != B or shape[1] < 1 or shape[2] != nJ_max or shape[3] not in (2, 3):
+            raise ValueError(f"{who}: loads must be [B={B}, L >= 1, nJ_max={nJ_max}, 2 or 3], got {shape}")
+        if not np.isfinite(x).all():
+            raise ValueError(f"{who}: loads must be finite")
+        val["loads"], L = np.ascontiguousarray(np.pad(x, [(0, 0)] * 3 + [(0, 3 - shape[3])])), shape[1]
+    val["L"] = L
+    nbytes = B * L * (8 * 6 * nJ_max + (8 + 8 + 1) * nM_max + 24 * (val["max_events"] + 1) + 16)
+    if nbytes > max_result_bytes:
+        raise ValueError(f"{who}: the results of B={B} trusses take {nbytes} bytes, more than max_result_bytes = "
+                         f"{max_result_bytes}")
+    return val
+
+
+def solve_plastic(trusses_or_packed, cap_tension, cap_compression, loads=None, hardening=0.0, lambda_max=1.0,
+                  disp_limit=0.0, collapse_ratio=1e8, tie_tol=1e-9, max_events=64, check_every=1, device=None,
+                  reorder=False, options=None, on_device=False, sections=None, use_envelope=True,
+                  max_slab_bytes=64 << 30, max_result_bytes=4 << 30):
+    """The collapse load of every truss of a batch - how much of a load pattern it carries before it becomes a mechanism,
+    and in which order its members give way - by the event-to-event elastic-plastic analysis (include/trs_plastic.h,
+    `DeviceBatch.plastic`): a member that reaches its capacity goes on carrying it while the rest of a redundant truss
+    picks up the difference.  `cap_tension`, `cap_compression`: [B, nM_max] positive member capacities (forces);
+    `loads`: [B, L, nJ_max, dim] load patterns (numpy or torch; the caller's joint numbering; dim 2 or 3) or None for
+    the batch's own loads.  Every case is an independent run from the nominal areas, looped on the resident bucket.
+    `hardening` >= 0: the fraction of its stiffness a yielded member keeps (0: perfectly plastic); `lambda_max` > 0 and
+    `disp_limit` >= 0 (0: none) end a run; `collapse_ratio` > 1, `tie_tol` >= 0, `max_events` and `check_every` as
+    `DeviceBatch.plastic`.  What the method is not: one proportional load pattern with no constant dead
+    load beside it, no pre-strain, small displacements, and a compression capacity is a plateau, not a post-buckling
+    drop; release and re-yield can cycle at a degenerate point, which ends as status 1.  A table-form batch is converted
+    with `.general()`.  Buckets, `reorder` plans, `options`, `on_device` and `use_envelope` as `solve_load_cases`.  Bad
+    arguments (`_check_plastic_args`) raise ValueError before any device work.  Returns a `PlasticResult`."""
+    packed = _as_packed(trusses_or_packed)
+    val = _check_plastic_args(packed, cap_tension, cap_compression, loads, hardening, lambda_max, disp_limit,
+                              collapse_ratio, tie_tol, max_events, check_every, options, sections, max_result_bytes)
+    if packed.is_table:
+        packed = packed.general()
+    torch, dev = _require_gpu(device)
+    L = val["L"]
+    out = _new_result(torch, dev, PlasticResult, packed.B,
+                      {"L": L, "nJ": packed.nJ_max, "nM": packed.nM_max, "H": val["max_events"] + 1})
+    up = lambda x: None if x is None else torch.from_numpy(x).to(dev)
+    on = {k: up(val[k]) for k in ("cap_tension", "cap_compression", "loads")}
+    case = lambda x, l: None if x is None else x[:, l].contiguous()
+    scalars = {k: val[k] for k in ("hardening", "lambda_max", "disp_limit", "collapse_ratio", "tie_tol", "max_events",
+                                   "check_every")}
+    for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope,
+                                      factor=lambda db, part: None):
+        nominal = db.A.clone()
+        tension, compression = part.cut(on["cap_tension"], nM=1), part.cut(on["cap_compression"], nM=1)
+        # (the padding of a bucket narrower or wider than the batch: a capacity that passes the check)
+        live = torch.arange(db.nM_max, device=dev)[None, :] < db.nM[:, None]
+        tension, compression = (torch.where(live, x, torch.ones_like(x)) for x in (tension, compression))
+        forces = part.cut(on["loads"], nJ=2)
+        info = torch.zeros_like(db.info)
+        for l in range(L):
+            db.A.copy_(nominal)
+            res = db.plastic(tension, compression, case(forces, l), **scalars)
+            for field, (key, fill, dtype, shape) in PlasticResult.CASE_FIELDS.items():
                 part.put(getattr(out, field)[:, l], res[key], nJ=1 if "nJ" in shape else None,
                          nM=1 if "nM" in shape else None)
             info = torch.where(info != 0, info, db.info)

@@ -813,6 +813,70 @@ class Truss:
                         "iterations": int(result.iterations[0, k]), "violations": int(result.violations[0, k])})
         return out
 
+    def CollapseLoad(self, capacities, cases=None, hardening=0.0, lambdaMax=1.0, dispLimit=0.0, maxEvents=64,
+                     collapseRatio=1e8, tieTol=1e-9):
+        """How much of a load pattern this truss carries before it collapses, and in which order its members give way:
+        the event-to-event elastic-plastic analysis (`batch.solve_plastic`).  A member that reaches its capacity goes on
+        carrying it while the rest of a redundant truss picks up the difference, until the truss is a mechanism.
+        `capacities`: the member capacities as forces - one positive number, one per member, or
+        {"tension": .., "compression": ..} of either; `cases`: a list of `{jointID: vector}` dicts as `SolveLoadCases`
+        takes them, each a load pattern that the load factor scales - None: the truss's own forces as one case;
+        `hardening` >= 0: the fraction of its stiffness a yielded member keeps; `lambdaMax` > 0 and `dispLimit` >= 0 (0:
+        none) end a run; `maxEvents`: events at most.  Returns a list, one dict per case:
+          "loadFactor", "status" (0 lambdaMax reached, 1 event limit, 2 mechanism: loadFactor is the collapse load, 3
+          displacement limit), "events", "yielded" ({memberID: +1 tension | -1 compression}), "sequence" (the events in
+          order as (loadFactor, memberID) pairs; memberID -1: members unloaded and returned to elastic), "forces" [nM],
+          "displacements" [nJ, dim], "reactions" [nJ, dim] (zero rows at free joints), "curve" (the pushover curve as
+          (loadFactor, largest |u|) pairs, one per analysis).
+        Small displacements, one proportional load pattern, a compression capacity is a plateau.  The truss itself stays
+        unsolved and unchanged.  Raises ValueError for bad arguments (as `batch.solve_plastic`) and
+        `TrussNotStableError` when the counting test fails."""
+        if not self.isStable:
+            raise TrussNotStableError("The truss is not stable !")
+        from .batch import pack_trusses, solve_plastic  # late import: keeps the model importable without torch
+        packed = pack_trusses([self])
+        nJ, nM, dim = len(self._pos), len(self._bars), self._dim
+        if isinstance(capacities, dict):
+            if set(capacities) != {"tension", "compression"}:
+                raise ValueError("CollapseLoad: capacities must be a number, one per member, or a dict with the keys "
+                                 "'tension' and 'compression'")
+            pair = (capacities["tension"], capacities["compression"])
+        else:
+            pair = (capacities, capacities)
+        caps = []
+        for x in pair:
+            try:
+                row = np.asarray(x, dtype=np.float64)
+            except (TypeError, ValueError):
+                row = None
+            if isinstance(x, bool) or row is None or row.shape not in ((), (nM,)):
+                raise ValueError(f"CollapseLoad: a capacity must be one number or one per member ({nM}), got {x!r}")
+            full = np.ones([1, packed.nM_max])
+            full[0, :nM] = row
+            caps.append(full)
+        loads = None
+        if cases is not None:
+            cases = list(cases)
+            if not cases:
+                return []
+            loads = self._case_loads(cases, packed.nJ_max)
+        result = solve_plastic(packed, caps[0], caps[1], loads, hardening=hardening, lambda_max=lambdaMax,
+                               disp_limit=dispLimit, collapse_ratio=collapseRatio, tie_tol=tieTol, max_events=maxEvents)
+        held = packed.constrained()[0, :nJ, :dim]
+        out = []
+        for k in range(result.status.shape[1]):
+            events = int(result.events[0, k])
+            lam, member = result.lambda_history[0, k], result.member_history[0, k]
+            state = result.state[0, k, :nM]
+            out.append({"loadFactor": float(result.load_factor[0, k]), "status": int(result.status[0, k]), "events": events,
+                        "yielded": {int(m): int(state[m]) for m in np.flatnonzero(state)},
+                        "sequence": [(float(lam[i]), int(member[i])) for i in range(events)],
+                        "forces": result.internal[0, k, :nM].copy(),
+                        "displacements": result.displace[0, k, :nJ, :dim].copy(),
+                        "reactions": np.where(held, result.external[0, k, :nJ, :dim], 0.0),
+                        "curve": [(float(lam[i]), float(result.umax_history[0, k, i])) for i in range(events + 1)]})
+        return out
+
     def MemberLoss(self, cases=None, rTol=None, returnForces=False):
         """What the loss of any ONE member does to this truss, for every member and every load case, from ONE
         factorisation (`batch.solve_member_loss`): `cases` is a list of `{jointID: vector}` dicts as `SolveLoadCases`

@@ -1,0 +1,355 @@
+"""Numpy yardstick of the collapse-load analysis (test infrastructure, never imported by the package): the event-to-event
+elastic-plastic analysis of include/trs_plastic.h stated on a dense stiffness matrix, in any floating-point type -
+`numpy.float64`, or `numpy.longdouble` to measure what float64 itself loses.  The linear systems are solved by plain
+elimination without pivoting (the algorithm of `tests/dynamics_reference.Eliminated`, stopped at the first pivot that is
+not positive: that is the positive-definiteness test, in the type of the run), so both types run the same algorithm.
+
+The method (the header, the kernel and this file state it in the same words).  Inputs per truss: one reference load
+pattern P (joint forces), scaled by the load factor lambda; member capacities cap_tension_m > 0 and cap_compression_m > 0
+(forces); hardening h >= 0, the fraction of its stiffness a yielded member keeps (0: perfectly plastic, the area is scaled
+to exactly 0); lambda_max > 0; disp_limit >= 0 (0: none); collapse_ratio > 1; tie_tol >= 0; max_events >= 0; and the
+nominal areas A.  State per truss: s_m in {0 elastic, +1 yielded in tension, -1 yielded in compression}, N [nM], u [DOFs],
+lambda and r_0, all accumulated, all zero at first.  Analysis k (k = 0, 1, ...) of state s_k:
+  1. A_eff,m = A_m where s_m = 0, else h A_m; assemble and factor K(A_eff);
+  2. info != 0: status 2 (mechanism); nothing advances, the info is latched;
+  3. otherwise solve K du = P;
+  4. the softening test: r_k = max over DOFs of |du|; analysis 0 stores r_0; if NOT (r_k <= collapse_ratio r_0): status 2
+     (mechanism) with info left 0; a non-finite r_k counts as collapse (the tangent is softer than the elastic structure
+     by that ratio: the mechanism that got through the factorisation on rounding noise);
+  5. de_m = c_m.(du_j1 - du_j0) and dN_m = (E_m A_eff,m / L0_m) de_m, for every member;
+  6. the release test: a yielded member with s_m de_m < 0 unloads (strict, no threshold); if any member unloads: at
+     k = max_events status 1; otherwise those members return to s = 0, nothing advances, and the analysis counts as an
+     event: its member_history entry is -1 and its count the number released;
+  7. otherwise advance: for every elastic member dl_m = (cap_tension_m - N_m) / dN_m where dN_m > 0,
+     (-cap_compression_m - N_m) / dN_m where dN_m < 0, +inf where dN_m = 0, negative values clamped to 0;
+     dl_y = the minimum of the dl_m, the governing member the lowest index that attains it;
+     dl_L = lambda_max - lambda; dl_u = min over free DOFs with du != 0 of (disp_limit - sign(du) u) / |du|, clamped at 0,
+     +inf with disp_limit = 0;
+     if min(dl_L, dl_u) <= dl_y: advance lambda, N and u by that step; status 0 (lambda_max reached) where dl_L <= dl_u,
+     else status 3 (displacement limit);
+     otherwise, at k = max_events: status 1 without advancing;
+     otherwise advance by dl_y; every elastic member with dl_m <= dl_y (1 + tie_tol) yields with s_m = sign(dN_m) and
+     takes N_m = +cap_tension_m or -cap_compression_m exactly (where the advance brought it, up to rounding and
+     tie_tol), unless it lay beyond that capacity already (dl_m was clamped: a member that hardened past its capacity,
+     unloaded and loads again keeps its force, and the joints their equilibrium); `events` = k + 1;
+  8. the history: analysis k writes entry k (k < H = max_events + 1) of lambda_history, member_history (the governing
+     member, -1 for a release, -2 for a terminal analysis), count_history (the members that yielded or were released, 0
+     for a terminal analysis) and umax_history (the largest |u_d| over the DOFs after the analysis: the pushover curve).
+"Advance by dl": lambda += dl, N_m += dl dN_m for every member, u += dl du.  A truss that ends is always left in the
+equilibrium state of its last completed event; nothing is ever rolled back.  f_ext is lambda P at the free DOFs and the
+sum of the members' end forces N_m c_m at the held ones."""
+import numpy as np
+
+from tests import sizing_reference as sref
+
+ACTIVE, LAMBDA_MAX, EVENT_LIMIT, MECHANISM, DISP_LIMIT = -1, 0, 1, 2, 3
+TERMINAL, RELEASE, ADVANCE_CAP, ADVANCE_YIELD = 0, 1, 2, 3
+COMPARED = ("u", "N", "f_ext", "lam", "lambda_history", "umax_history")
+Geometry = sref.Geometry
+
+
+class Eliminated:
+    """K = L U by plain elimination without pivoting, stopped at the first pivot that is not positive (`pd` False: K is
+    not positive definite in this type)."""
+
+    def __init__(self, K):
+        self.U = np.array(K, copy=True)
+        n = len(K)
+        self.Lm = np.zeros_like(self.U)
+        self.pd, self.pivot_ratio = True, None
+        for k in range(n):
+            if not self.U[k, k] > 0:
+                # the pivot over the diagonal entry it came from: 0 where that entry is itself 0 (a DOF without stiffness)
+                self.pd, self.pivot_ratio = False, (self.U[k, k] / K[k, k] if K[k, k] != 0 else K[k, k])
+                return
+            if k + 1 < n:
+                f = self.U[k + 1:, k] / self.U[k, k]
+                self.Lm[k + 1:, k] = f
+                self.U[k + 1:, k:] -= f[:, None] * self.U[k, k:][None, :]
+
+    def solve(self, rhs):
+        x = np.array(rhs, copy=True)
+        n = len(x)
+        for k in range(n - 1):
+            x[k + 1:] -= self.Lm[k + 1:, k] * x[k]
+        for k in range(n - 1, -1, -1):
+            x[k] /= self.U[k, k]
+            x[:k] -= self.U[:k, k] * x[k]
+        return x
+
+
+def collapse(data, load, cap_tension, cap_compression, hardening=0.0, lambda_max=1.0, disp_limit=0.0, collapse_ratio=1e8,
+             tie_tol=1e-9, max_events=64, dtype=np.float64):
+    """The analysis of one truss.  load [nJ, dim]; cap_tension, cap_compression [nM].  Returns a dict: u, f_ext [nJ, dim],
+    N [nM], lam, state (int8 [nM]), status, events, info (0, or 1 where the factorisation failed), areas_effective [nM],
+    lambda_history, umax_history [H], member_history, count_history (int32 [H]), r0, `soft` (whether the run ended by the
+    softening rule) and `trace`: per analysis the decision and what it rested on (see `margins`)."""
+    geo = Geometry(data, dtype)
+    nM, ndof = len(geo.A0), geo.nJ * geo.dim
+    P = np.asarray(load, dtype=dtype).reshape(-1)
+    ct, cc = np.asarray(cap_tension, dtype=dtype), np.asarray(cap_compression, dtype=dtype)
+    h, lmax, limit = dtype(hardening), dtype(lambda_max), dtype(disp_limit)
+    ratio, tol = dtype(collapse_ratio), dtype(tie_tol)
+    inf = dtype(np.inf)
+    H = max_events + 1
+    s = np.zeros(nM, dtype=np.int8)
+    N, u = np.zeros(nM, dtype=dtype), np.zeros(ndof, dtype=dtype)
+    lam, r0, umax = dtype(0), dtype(0), dtype(0)
+    out = {"status": ACTIVE, "events": 0, "info": 0, "soft": False, "trace": [],
+           "lambda_history": np.zeros(H, dtype=dtype), "umax_history": np.zeros(H, dtype=dtype),
+           "member_history": np.zeros(H, dtype=np.int32), "count_history": np.zeros(H, dtype=np.int32)}
+    k = 0
+    while out["status"] == ACTIVE:
+        last = k == max_events
+        A_eff = np.where(s == 0, geo.A0, h * geo.A0)
+        el = Eliminated(geo.stiffness(A_eff))
+        rec = {"what": TERMINAL, "pd": el.pd, "lam": lam, "pivot_ratio": el.pivot_ratio}
+        out["trace"].append(rec)
+        what, member, count = TERMINAL, -2, 0
+        if not el.pd:
+            out["status"], out["info"] = MECHANISM, 1
+        else:
+            du = np.zeros(ndof, dtype=dtype)
+            du[geo.mask] = el.solve(P[geo.mask])
+            mag = np.abs(du)
+            rk = mag.max() if np.isfinite(mag).all() else inf
+            if k == 0:
+                r0 = rk
+            rec["q"] = rk / (ratio * r0) if r0 > 0 else dtype(0)
+            if not rk <= ratio * r0 or not np.isfinite(rk):
+                out["status"], out["soft"] = MECHANISM, True
+            else:
+                d = du.reshape(geo.nJ, geo.dim)
+                de = ((d[geo.j1] - d[geo.j0]) * geo.c).sum(axis=1)
+                dN = (geo.E * A_eff / geo.L0) * de
+                rec["de"], rec["yielded"] = de, s != 0
+                release = (s != 0) & (s * de < 0)
+                if release.any():
+                    if last:
+                        out["status"] = EVENT_LIMIT
+                    else:
+                        what, member, count = RELEASE, -1, int(release.sum())
+                        s = np.where(release, 0, s).astype(np.int8)
+                else:
+                    with np.errstate(divide="ignore", invalid="ignore"):
+                        dl = np.where(dN > 0, (ct - N) / dN, np.where(dN < 0, (-cc - N) / dN, inf))
+                    dl = np.where(s == 0, np.maximum(dl, 0), inf)
+                    dly = dl.min() if nM else inf
+                    gov = int(dl.argmin()) if nM else -1   # (the first of equal minima: the lowest index)
+                    dlL = lmax - lam
+                    dlu = inf
+                    moving = geo.mask & (du != 0)
+                    if limit > 0 and moving.any():
+                        dlu = np.maximum((limit - np.sign(du[moving]) * u[moving]) / mag[moving], 0).min()
+                    cap = min(dlL, dlu)
+                    rec.update(dl=dl, dly=dly, cap=cap)
+                    step = None
+                    if cap <= dly:
+                        what, step = ADVANCE_CAP, cap
+                        out["status"] = LAMBDA_MAX if dlL <= dlu else DISP_LIMIT
+                    elif last:
+                        out["status"] = EVENT_LIMIT
+                    else:
+                        what, step, member = ADVANCE_YIELD, dly, gov
+                    before = N
+                    if step is not None:
+                        lam = lam + step
+                        N = N + step * dN
+                        u = u + step * du
+                        umax = np.abs(u).max()
+                    if what == ADVANCE_YIELD:
+                        yields = (s == 0) & (dl <= dly * (1 + tol))
+                        rec["group"] = yields
+                        count = int(yields.sum())
+                        beyond = np.where(dN > 0, before > ct, before < -cc)
+                        N = np.where(yields & ~beyond, np.where(dN > 0, ct, -cc), N)
+                        s = np.where(yields, np.where(dN > 0, 1, -1), s).astype(np.int8)
+        rec["what"] = what
+        if what in (RELEASE, ADVANCE_YIELD):
+            out["events"] = k + 1
+        out["lambda_history"][k], out["umax_history"][k] = lam, umax
+        out["member_history"][k], out["count_history"][k] = member, count
+        k += 1
+    R = np.zeros([geo.nJ, geo.dim], dtype=dtype)
+    np.add.at(R, geo.j1, N[:, None] * geo.c)
+    np.add.at(R, geo.j0, -N[:, None] * geo.c)
+    mask = geo.mask.reshape(geo.nJ, geo.dim)
+    out.update(u=u.reshape(geo.nJ, geo.dim), N=N, lam=lam, state=s, r0=r0, residual=R,
+               f_ext=np.where(mask, lam * P.reshape(geo.nJ, geo.dim), R),
+               areas_effective=np.where(s == 0, geo.A0, h * geo.A0))
+    return out
+
+
+def same_path(x, y):
+    """Whether two runs took the same decisions: status, events, state and the integer histories."""
+    return (x["status"], x["events"]) == (y["status"], y["events"]) and np.array_equal(x["state"], y["state"]) \
+        and np.array_equal(x["member_history"], y["member_history"]) \
+        and np.array_equal(x["count_history"], y["count_history"])
+
+
+def margins(x, y, tie_tol=1e-9):
+    """The margins of every decision that run x (float64) took, each beside what float64 itself loses on it: the
+    difference of the same quantity between x and y (the longdouble run of the same inputs, which took the same path).
+    Returns a list of (analysis, name, margin, loss):
+      "pd"       whether both types agree on positive definiteness - margin 1 and loss 0 where they do, or where the type
+                 that did factor ended the truss there by the softening rule (the same state, status 2); else margin 0;
+      "soften"   1 - min(q, 1 / q) for q = r_k / (collapse_ratio r_0): how far the softening test is from its threshold;
+      "release"  the smallest |de| of a yielded member over max |de|;
+      "gap"      (the next dl_m beyond the tie group - dl_y) / (lambda + dl_y), for an analysis that ends in a yield;
+      "cap"      |min(dl_L, dl_u) - dl_y| / (lambda + the step), cap against yield.
+    A run is admissible when every margin >= ADMISSIBLE x its loss."""
+    rows = []
+    L = np.longdouble
+    for k, (a, b) in enumerate(zip(x["trace"], y["trace"])):
+        if a["pd"] != b["pd"]:
+            other = a if a["pd"] else b
+            ends = k == len(x["trace"]) - 1 and "q" in other and not other["q"] <= 1
+            rows.append((k, "pd", 1.0 if ends else 0.0, 0.0))
+            continue
+        rows.append((k, "pd", 1.0, 0.0))
+        if not a["pd"]:
+            continue
+        m = [1 - min(L(r["q"]), 1 / L(r["q"])) if r["q"] > 0 else L(1) for r in (a, b)]
+        rows.append((k, "soften", float(m[0]), float(abs(m[0] - m[1]))))
+        if "de" not in a or "de" not in b:
+            continue
+        top = L(np.abs(b["de"]).max())
+        if a["yielded"].any() and top > 0:
+            Y = a["yielded"]
+            rows.append((k, "release", float(np.abs(a["de"][Y]).min() / top),
+                         float(np.abs(a["de"][Y].astype(L) - b["de"][Y]).max() / top)))
+        if "dl" not in a or "dl" not in b:
+            continue
+        step = min(L(a["cap"]), L(a["dly"]))
+        scale = L(a["lam"]) + step
+        if np.isfinite(a["dly"]) and scale > 0:
+            gap = abs(L(a["cap"]) - L(a["dly"]))
+            rows.append((k, "cap", float(gap / scale),
+                         float(abs((L(a["cap"]) - L(a["dly"])) - (L(b["cap"]) - L(b["dly"]))) / scale)))
+        if a["what"] == ADVANCE_YIELD:
+            rest = ~a["group"] & np.isfinite(a["dl"])
+            loss = abs(L(a["dly"]) - L(b["dly"]))
+            gap = L(np.inf)
+            if rest.any():
+                nxt = int(np.where(rest, a["dl"], np.inf).argmin())
+                gap = L(a["dl"][nxt]) - L(a["dly"])
+                loss = max(loss, abs(L(a["dl"][nxt]) - L(b["dl"][nxt])))
+            rows.append((k, "gap", float(gap / scale), float(loss / scale)))
+    return rows
+
+
+def admissible(x, y):
+    """(ok, worst): whether x and y took the same path and every margin of `margins` is at least ADMISSIBLE x its loss;
+    `worst` is the row with the smallest margin / loss."""
+    if not same_path(x, y) or len(x["trace"]) != len(y["trace"]):
+        return False, None
+    rows = margins(x, y)
+    ratio = lambda r: r[2] / r[3] if r[3] > 0 else (np.inf if r[2] > 0 else 0.0)
+    worst = min(rows, key=ratio)
+    return all(r[2] >= ADMISSIBLE * r[3] and r[2] > 0 for r in rows), worst
+
+
+def info_clear(x, y):
+    """Whether `info` of run x is a decision that another factorisation must share: x ended without a failed pivot
+    (info 0, not by the softening rule), or its failed pivot is clear of rounding - the diagonal entry is itself 0 (a DOF
+    without any stiffness), or |pivot| / diagonal is at least ADMISSIBLE x its float64-against-longdouble difference.
+    The pivot of a true mechanism is rounding noise of either sign: whether a factorisation fails on it or passes and
+    leaves it to the softening rule is luck, and the truss ends in the same state with status 2 either way."""
+    if x["soft"]:
+        return False
+    if x["info"] == 0:
+        return True
+    a, b = x["trace"][-1], y["trace"][-1]
+    if b["pd"] or len(x["trace"]) != len(y["trace"]):
+        return False
+    L = np.longdouble
+    return bool(a["pivot_ratio"] == 0 or abs(L(a["pivot_ratio"])) >= ADMISSIBLE * abs(L(a["pivot_ratio"]) - L(b["pivot_ratio"])))
+
+
+def relative_difference(x, y):
+    """The largest max-scaled difference between two `collapse` results over COMPARED."""
+    worst = 0.0
+    for key in COMPARED:
+        a, b = np.asarray(x[key], dtype=np.longdouble), np.asarray(y[key], dtype=np.longdouble)
+        scale = float(np.abs(b).max())
+        if scale > 0:
+            worst = max(worst, float(np.abs(a - b).max()) / scale)
+    return worst
+
+
+# ---- the inputs that the CPU and the GPU tests share -------------------------------------------------------------------
+BATCH = sref.BATCH
+BIG = sref.BIG
+cases = sref.cases
+ADMISSIBLE = 1000.0
+MAX_EVENTS = 40
+GOLDEN_RATIO = 0.6180339887
+DISP_LIMIT_RULE = 50.0    # times d0 = 1 of the scaled pattern
+
+
+def rule(data, case, lambda_max=10.0, cap_scale=1.0):
+    """(load [nJ, dim], keyword arguments of `collapse`) of a fixture's load case: from the linear solution of the case,
+    s0 = the largest |N| / A and d0 = the largest |u_d|; w_m = 1 + 0.25 frac(0.6180339887 m) breaks the fixtures' symmetry
+    ties; cap_tension = cap_scale s0 A w, cap_compression = 0.8 cap_tension, disp_limit = 50 d0.  The pattern is the
+    case's forces divided by d0, so that d0 = 1 and ONE disp_limit (a scalar of the device call) serves every truss of
+    a batch; s0 and the capacities are those of the scaled pattern, the load factors those of the unscaled one."""
+    geo = Geometry(data, np.float64)
+    load = cases(data)[case]
+
+    def linear(load):
+        el = Eliminated(geo.stiffness(geo.A0))
+        u = np.zeros(geo.nJ * geo.dim)
+        u[geo.mask] = el.solve(load.reshape(-1)[geo.mask])
+        return u, geo.forces(geo.A0, u.reshape(1, geo.nJ, geo.dim))[0]
+    load = load / float(np.abs(linear(load)[0]).max())
+    u, N = linear(load)
+    s0 = float((np.abs(N) / geo.A0).max())
+    w = 1.0 + 0.25 * np.modf(GOLDEN_RATIO * np.arange(len(geo.A0)))[0]
+    ct = cap_scale * s0 * geo.A0 * w
+    return load, {"cap_tension": ct, "cap_compression": 0.8 * ct, "disp_limit": DISP_LIMIT_RULE, "lambda_max": lambda_max}
+
+
+#: the parity runs: name -> (hardening, ((fixture, case, lambda_max), ...)); the trusses of a run share ONE DeviceBatch.
+#: Every one is admissible (tests/test_plastic.py).
+RUNS = {"plastic": (0.0, (("bar-6_input_0", 0, 10.0), ("bar-10_input_0", 0, 10.0), ("bar-25_input_0", 1, 10.0),
+                          ("bar-47_input_0", 0, 10.0), ("bar-72_input_0", 1, 10.0), ("bar-120_input_0", 1, 10.0))),
+        "hardening": (1e-3, (("bar-6_input_0", 0, 10.0), ("bar-10_input_0", 0, 10.0), ("bar-25_input_0", 1, 10.0),
+                             ("bar-47_input_0", 0, 10.0), ("bar-72_input_0", 1, 10.0), ("bar-120_input_0", 1, 10.0))),
+        "big": (0.0, ((BIG, 0, 1.2),))}
+#: what the yardstick gives per run and truss: (status, events, the member_history of the first analyses)
+TABLE = {"plastic": ((2, 2, (3, 2, -2, 0)), (2, 2, (0, 4, -2, 0)), (2, 5, (7, 3, 5, 23)), (2, 4, (3, 18, 8, 0)),
+                     (2, 12, (2, 1, 20, 19)), (2, 12, (18, 17, 115, 41))),
+         "hardening": ((3, 2, (3, 2, -2, 0)), (3, 2, (0, 4, -2, 0)), (3, 5, (7, 3, 5, 23)), (3, 6, (3, 18, 8, 0)),
+                       (3, 17, (2, 1, 20, 19)), (3, 18, (18, 17, 115, 41))),
+         "big": ((0, 8, (907, 909, 795, 793)),)}
+
+
+def run_inputs(name):
+    """[(data, load, keyword arguments)] of the trusses of RUNS[name]; the keyword arguments carry the hardening."""
+    from tests.helpers import load_json
+    h, configs = RUNS[name]
+    rows = []
+    for fixture, case, lmax in configs:
+        data = load_json(fixture)
+        load, kw = rule(data, case, lmax)
+        rows.append((data, load, dict(kw, hardening=h, max_events=MAX_EVENTS)))
+    return rows
+
+
+def three_bars(C=100.0, P=1.0):
+    """Three bars from a ceiling to one loaded joint, at -45, 0 and +45 degrees from the vertical, equal A and E, capacity
+    C: the middle bar yields at lambda P = (1 + 1 / sqrt 2) C, both side bars at (1 + sqrt 2) C.  Returns (data, caps)."""
+    E, A = 1.0e7, 1.5
+    data = {"joint": [[[-1.0, 1.0], "PIN"], [[0.0, 1.0], "PIN"], [[1.0, 1.0], "PIN"], [[0.0, 0.0], "NO"]],
+            "force": [[3, [0.0, -P]]],
+            "member": [[[0, 3], [A, E, 0.1]], [[1, 3], [A, E, 0.1]], [[2, 3], [A, E, 0.1]]]}
+    return data, np.full(3, C)
+
+
+def two_bars(C=100.0, P=1.0):
+    """A statically determinate truss: two bars at +-45 degrees to one joint, loaded off the axis of symmetry."""
+    E, A = 1.0e7, 1.5
+    data = {"joint": [[[-1.0, 1.0], "PIN"], [[1.0, 1.0], "PIN"], [[0.0, 0.0], "NO"]],
+            "force": [[2, [0.3 * P, -P]]],
+            "member": [[[0, 2], [A, E, 0.1]], [[1, 2], [A, E, 0.1]]]}
+    return data, np.full(2, C)

@@ -1,0 +1,187 @@
+#!/usr/bin/env python3
+"""Collapse load: what one analysis of the event-to-event elastic-plastic analysis costs, launch by launch.
+
+    python tools/bench_plastic.py [--copies 4096] [--hardening 0] [--events 12] [--reps 25] [--warmup 3] [--json out.json]
+
+The batch (bar-942 x `--copies`) is resident and ordered on the device; the load pattern is the fixture's own forces.  The
+capacities follow the rule of tests/plastic_reference.py: s0 A w in tension and 0.8 of it in compression, s0 the largest
+|N| / A of the linear solution and w_m = 1 + 0.25 frac(0.6180339887 m).  Warmed up and timed with events `--reps` times,
+median reported:
+  assemble_ms, potrf_ms, gather_ms, potrs_cases_ms, step_ms   the five launches of ONE analysis, each alone, on the buffers
+                              of the first analysis of a run (every truss is active, every member elastic: the step advances
+                              to the first yield)
+  analysis_ms                 the same launches back to back, as `plastic` issues them
+  un_step_ms, sz_step_ms      `trs_un_step` (every fourth member tension-only) and `trs_sz_step` with L = 1 on the same
+                              batch and case block; the three steps are timed in three alternating rounds
+                              (step_rounds_ms), the median round reported
+  finish_ms                   `trs_pl_finish`, once per run
+  plastic_ms, events          a whole `plastic(...)` call (`--events` events at most) and how far it got
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+from python_stable_3d_truss_analysis_amd import _capi, batch  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--copies", type=int, default=4096)
+ap.add_argument("--hardening", type=float, default=0.0)
+ap.add_argument("--events", type=int, default=12)
+ap.add_argument("--reps", type=int, default=25)
+ap.add_argument("--warmup", type=int, default=3)
+ap.add_argument("--json", default=None)
+args = ap.parse_args()
+
+
+def timed(fn, reps=None):
+    for _ in range(args.warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps or args.reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return statistics.median(ts)
+
+
+with open(os.path.join(ROOT, "tests", "golden", "data", "bar-942_input_0.json")) as fh:
+    packed = batch.pack_json([json.load(fh)]).replicate(args.copies)
+dev = torch.device("cuda:0")
+loads = torch.from_numpy(packed.loads).to(dev)              # the caller's joint numbering
+db = batch.DeviceBatch(packed, dev, use_small=False, reorder="device")
+db.factor()
+first = db.solve_cases(loads.unsqueeze(1).contiguous())
+N = first["N"][:, 0]
+A0 = db.A.clone()
+live = torch.arange(db.nM_max, device=dev)[None, :] < db.nM[:, None]
+s0 = float((N.abs() / torch.where(live, A0, torch.ones_like(A0))).max().item())
+w = 1.0 + 0.25 * torch.frac(0.6180339887 * torch.arange(db.nM_max, device=dev, dtype=torch.float64))
+cap_t = torch.where(live, s0 * A0 * w[None, :], torch.ones_like(A0))
+cap_c = torch.where(live, 0.8 * cap_t, torch.ones_like(A0))
+kw = dict(hardening=args.hardening, lambda_max=10.0, max_events=args.events)
+
+
+def plastic():
+    db.A.copy_(A0)
+    return db.plastic(cap_t, cap_c, loads, **kw)
+
+
+out = plastic()
+torch.cuda.synchronize()
+events = int(out["events"].max().item())
+status = sorted(set(out["status"].cpu().numpy().ravel().tolist()))
+sequence = out["member_history"][0, :events + 1].cpu().numpy().tolist()
+t_copy = timed(lambda: db.A.copy_(A0))
+t_plastic = timed(plastic, reps=max(3, args.reps // 5)) - t_copy
+
+# the buffers of the first analysis
+db.A.copy_(A0)
+val = batch._check_plastic_scalars("bench", args.hardening, 10.0, 0.0, 1e8, 1e-9, args.events, 1)
+ws = db._pl_workspace({"cap_tension": cap_t, "cap_compression": cap_c, "loads": loads}, val, out)
+jo, stream, _ = db._case_launch()
+db.dofmap()
+
+
+def gather():
+    db._gather_cases(ws["loads"], 1, ws["F"])
+
+
+def finish():
+    _capi.check(db.lib.trs_pl_finish(
+        db.B, db.nJ_max, db.nM_max, db.xyz.data_ptr(), db.conn.data_ptr(), db.free_index.data_ptr(), db.n_free.data_ptr(),
+        db.nJ.data_ptr(), db.nM.data_ptr(), db.rows, ws["loads"].data_ptr(), out["N"].data_ptr(), ws["U"].data_ptr(),
+        ws["acc"].data_ptr(), jo, out["u"].data_ptr(), out["f_ext"].data_ptr(), stream), "trs_pl_finish")
+
+
+def reset():
+    db.A.copy_(A0)          # (every repeat is analysis 0 of a run that has just begun: nothing freezes)
+    ws["st"].zero_()
+    ws["active"].zero_()
+
+
+def step():
+    reset()
+    db._pl_step(ws, 0, 0)
+
+
+def analysis():
+    reset()
+    db._pl_analyse(ws)
+    db._pl_step(ws, 0, 0)
+
+
+# the step of the tension-only members on the same case block
+chosen = (N.abs() >= 0.05 * N.abs().amax(dim=1, keepdim=True)) & (torch.arange(db.nM_max, device=dev)[None, :] % 4 == 0)
+un_out = db._out_tensors("unilateral", batch._field_shapes(batch.UnilateralResult.CASE_FIELDS, db.B, db._sizes(H=21)), None)
+un = db._un_workspace({"kind": chosen.to(torch.int8), "loads": loads, "prestrain": None, "state": None}, 1e-3, 20, un_out)
+un["F"] = ws["F"]
+
+
+def un_reset():
+    db.A.copy_(A0)
+    un["st"].zero_()
+    un["active"].zero_()
+
+
+def un_step():
+    un_reset()
+    db._un_step(un, 0, 0)
+
+
+# the member sizing's step on the same case block, L = 1
+sz_val = batch._check_sizing_scalars("bench", 0.5 * s0, 0.4 * s0)
+keys = [k for k, *_ in batch.SizingResult.FIELDS.values() if k != "catalog_index"]
+sz_out = db._out_tensors("sizing", batch._field_shapes(batch.SizingResult.FIELDS, db.B, db._sizes(H=sz_val["max_iters"] + 1),
+                                                       keys), None)
+bounds = [(None, 0.1 * float(A0[live].min().item())), (None, 1000.0 * float(A0.max().item()))]
+sz = db._sz_workspace(sz_val, bounds, loads.unsqueeze(1).contiguous(), sz_out)
+sz["F"] = ws["F"]
+
+
+def sz_reset():
+    db.A.copy_(A0)
+    sz["st"].zero_()
+    sz["active"].zero_()
+
+
+def sz_step():
+    sz_reset()
+    db._sz_step(sz, 0, 0)
+
+
+t_assemble = timed(db.assemble)
+t_potrf = timed(lambda: (db.assemble(), db.potrf())) - t_assemble
+t_gather = timed(gather)
+db.assemble()
+db.potrf()
+t_potrs = timed(lambda: (gather(), db._potrs_cases(ws["F"], 1))) - t_gather
+gather()
+db._potrs_cases(ws["F"], 1)
+t_reset, t_un_reset, t_sz_reset = timed(reset), timed(un_reset), timed(sz_reset)
+rounds = []     # the three steps alternate, so that a drift of the machine shows in all
+for _ in range(3):
+    rounds.append((timed(step) - t_reset, timed(un_step) - t_un_reset, timed(sz_step) - t_sz_reset))
+t_step, t_un_step, t_sz_step = (statistics.median(r[i] for r in rounds) for i in range(3))
+t_finish = timed(finish)
+t_analysis = timed(analysis) - t_reset
+summary = {"shape": f"bar-942 x {args.copies}", "B": int(db.B), "rows": int(db.rows), "reps": args.reps,
+           "statistic": "median of event-timed repeats", "hardening": args.hardening, "events": events, "status": status,
+           "sequence": sequence, "assemble_ms": round(t_assemble, 4), "potrf_ms": round(t_potrf, 4),
+           "gather_ms": round(t_gather, 4), "potrs_cases_ms": round(t_potrs, 4), "step_ms": round(t_step, 4),
+           "un_step_ms": round(t_un_step, 4), "sz_step_ms": round(t_sz_step, 4), "finish_ms": round(t_finish, 4),
+           "analysis_ms": round(t_analysis, 4), "plastic_ms": round(t_plastic, 3), "reset_ms": round(t_reset, 4),
+           "un_reset_ms": round(t_un_reset, 4), "sz_reset_ms": round(t_sz_reset, 4),
+           "step_rounds_ms": [[round(x, 4) for x in r] for r in rounds]}
+print(json.dumps(summary))
+if args.json:
+    with open(args.json, "w") as fh:
+        json.dump(summary, fh, indent=1)
