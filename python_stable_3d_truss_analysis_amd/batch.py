@@ -602,6 +602,32 @@ def _refuse_sections(who, what, sections):
         raise ValueError(f"{who}: sections= variants cannot be combined with {what}")
 
 
+def _refuse_variants(who, what, sections, options, cases="load cases"):
+    """What the iterated analyses refuse before any device work: `sections=` variants, in their own words (`what`), and
+    `options["compact"]`, which keeps no slab that their `cases` could be solved against."""
+    _refuse_sections(who, what, sections)
+    if options and options.get("compact"):
+        raise ValueError(f"{who}: options['compact'] writes no slab that the {cases} could be solved against")
+
+
+def _check_case_loads(who, loads, B, nJ_max):
+    """`loads` of an iterated analysis on the host: [B, L >= 1, nJ_max, 2 or 3] (numpy, torch or nested lists), finite.
+    Returns them as a contiguous float64 array [B, L, nJ_max, 3] (two components get z = 0), or None for None: the
+    batch's own loads."""
+    if loads is None:
+        return None
+    try:
+        x = _host_array(loads, np.float64)
+    except (TypeError, ValueError):
+        x = None
+    shape = None if x is None else tuple(x.shape)
+    if x is None or len(shape) != 4 or shape[0] != B or shape[1] < 1 or shape[2] != nJ_max or shape[3] not in (2, 3):
+        raise ValueError(f"{who}: loads must be [B={B}, L >= 1, nJ_max={nJ_max}, 2 or 3], got {shape}")
+    if not np.isfinite(x).all():
+        raise ValueError(f"{who}: loads must be finite")
+    return np.ascontiguousarray(np.pad(x, [(0, 0)] * 3 + [(0, 3 - shape[3])]))
+
+
 #: how the device holds a `FIELDS` dtype that it has no kernel type for: (device dtype, trailing axes)
 _DEVICE_DTYPES = {"bool": ("int32", ()), "complex128": ("float64", (2,))}
 
@@ -2101,6 +2127,91 @@ class DeviceBatch:
             self.uf.data_ptr(), self.rows, self.info.data_ptr(), it, ws["U"].data_ptr(), ws["st"].data_ptr(),
             self._stream()), "trs_nl_update")
 
+    # -- the iterated analyses - sizing, min_compliance, unilateral, plastic - share one driver and one run protocol
+    # (csrc/trs_iterate.h): analyse, one step kernel, one look at one counter ------------------------------
+    def _refuse_iterated(self, name, what="load cases"):
+        """What none of the four runs on: the fused small-system path, `options["compact"]` and the table form."""
+        self._need_slab(name, f"writes no slab that the {what} could be solved against")
+        if self.table:
+            raise ValueError(f"{name}(): the table member form cannot hold one area per member - use the general form "
+                             "(PackedBatch.general())")
+
+    def _begin_iterated(self, name, *fits):
+        """`fits`: (trs_*_fits, what it speaks for) of every kernel with LDS tables of the truss's shape.  The run
+        factors designs of its own: what the batch held of a factor, a dynamic factor or a forward solve is void."""
+        for fits_fn, what in fits:
+            self._need_fit(name, fits_fn(self.nJ_max, self.nM_max), what)
+        self._factored = False
+        self._dynamic = None
+        self._forward = None
+
+    def _run_state(self, limit, L, loads, own=False, **more):
+        """The state every run has: the status words st [B, 4] (status, count, the latched info, spare) and the `active`
+        counters (one per analysis), zeroed; the case block of L cases; `loads` as `_analyse_cases` gathers them (`own`:
+        the batch's own, already in the batch's joint order).  `more`: what the analysis adds."""
+        t, dev = self.torch, self.device
+        return dict(more, st=t.zeros([self.B, 4], dtype=t.int32, device=dev),
+                    active=t.zeros([limit + 1], dtype=t.int32, device=dev), F=self._case_block("cases_F", L), L=L,
+                    loads=loads, own=own, limit=limit)
+
+    def _active(self, ws, it):
+        """The counter that analysis `it` adds to (a report behind the last analysis: the last one's)."""
+        return ws["active"][min(it, ws["limit"]):].data_ptr()
+
+    def _iterate(self, ws, check_every, analyse, step):
+        """analyse(ws), step(ws, it, mode) - mode 1 at the limit, else 0 - until the limit or until, at every
+        `check_every`-th analysis, the one int32 read back says that no truss is still iterating.  Returns the last
+        `it`."""
+        it = 0
+        while True:
+            last = it == ws["limit"]
+            analyse(ws)
+            step(ws, it, 1 if last else 0)
+            if last or (it % check_every == 0 and int(ws["active"][it].item()) == 0):
+                return it
+            it += 1
+
+    def _end_iterated(self, ws, out, count="iterations"):
+        """status and the count from st; `self.info`: what the factorisation reported for the design that ended a truss
+        with the failed status, latched, 0 for every other truss; the slab holds the factor of the final design."""
+        out["status"].copy_(ws["st"][:, 0])
+        out[count].copy_(ws["st"][:, 1])
+        self.info.copy_(ws["st"][:, 2])
+        self.cases_F = ws["F"]
+        self._factored = True
+        self._bump_generation()
+
+    def _area_bounds(self, who, area_min, area_max):
+        """[(tensor or None, number)] of `area_min`, `area_max`: each a number or a float64 [B, nM_max] device tensor."""
+        t, bounds = self.torch, []
+        for name, x in (("area_min", area_min), ("area_max", area_max)):
+            if hasattr(x, "data_ptr"):
+                if list(x.shape) != [self.B, self.nM_max] or x.dtype != t.float64 or x.device != self.device:
+                    raise ValueError(f"{who}: {name} must be a number or a float64 [B={self.B}, nM_max={self.nM_max}] "
+                                     f"tensor on {self.device}")
+                bounds.append((x.contiguous(), 0.0))
+            else:
+                bounds.append((None, _check_number(who, name, x, "be a finite number or a float64 [B, nM_max] tensor")))
+        if bounds[0][0] is None and not bounds[0][1] > 0:
+            raise ValueError(f"{who}: area_min must be positive, got {area_min!r}")
+        if bounds[0][0] is None and bounds[1][0] is None and bounds[1][1] < bounds[0][1]:
+            raise ValueError(f"{who}: area_max must be >= area_min, got {area_max!r} < {area_min!r}")
+        return bounds
+
+    def _own_loads(self):
+        """The batch's own loads [B, nJ_max, 3] in the CALLER's joint numbering (carried there through `joint_out`)."""
+        if self.joint_out is None:
+            return self.loads
+        index = self.joint_out.long().unsqueeze(-1).expand(-1, -1, 3)
+        return self.torch.zeros_like(self.loads).scatter_(1, index, self.loads)
+
+    def _analyse_cases(self, ws):
+        """Assembly and factorisation of the design `self.A`, gather and substitution of the L cases of the run."""
+        self.assemble()
+        self.potrf()
+        self._gather_cases(ws["loads"], ws["L"], ws["F"], own=ws["own"])
+        self._potrs_cases(ws["F"], ws["L"])
+
     # -- member sizing: fully stressed design iterated on the device (include/trs_sizing.h) ------------------------------
     def sizing(self, loads=None, *, allow_tension, allow_compression, allow_displace=0.0, euler_kappa=0.0, area_min,
                area_max, relax=1.0, tol=1e-4, max_iters=40, check_every=1, catalog=None, out=None):
@@ -2132,25 +2243,10 @@ class DeviceBatch:
         small-system path, `options["compact"]` and the table member form (the step writes one area per member, which a
         type table cannot hold: `PackedBatch.general()` first) are refused."""
         t = self.torch
-        self._need_slab("sizing", "writes no slab that the load cases could be solved against")
-        if self.table:
-            raise ValueError("sizing(): the table member form cannot hold one area per member - use the general form "
-                             "(PackedBatch.general())")
+        self._refuse_iterated("sizing")
         val = _check_sizing_scalars("sizing()", allow_tension, allow_compression, allow_displace, euler_kappa, relax, tol,
                                     max_iters, check_every, catalog, B=self.B)
-        bounds = []
-        for name, x in (("area_min", area_min), ("area_max", area_max)):
-            if hasattr(x, "data_ptr"):
-                if list(x.shape) != [self.B, self.nM_max] or x.dtype != t.float64 or x.device != self.device:
-                    raise ValueError(f"sizing(): {name} must be a number or a float64 [B={self.B}, nM_max={self.nM_max}] "
-                                     f"tensor on {self.device}")
-                bounds.append((x.contiguous(), 0.0))
-            else:
-                bounds.append((None, _check_number("sizing()", name, x, "be a finite number or a float64 [B, nM_max] tensor")))
-        if bounds[0][0] is None and not bounds[0][1] > 0:
-            raise ValueError(f"sizing(): area_min must be positive, got {area_min!r}")
-        if bounds[0][0] is None and bounds[1][0] is None and bounds[1][1] < bounds[0][1]:
-            raise ValueError(f"sizing(): area_max must be >= area_min, got {area_max!r} < {area_min!r}")
+        bounds = self._area_bounds("sizing()", area_min, area_max)
         own = loads is None   # (the batch's own loads are already in the batch's joint order: gathered without joint_in)
         loads = self._check_loads("sizing", self.loads.unsqueeze(1) if own else loads)
         L, H = int(loads.shape[1]), val["max_iters"] + 1
@@ -2160,36 +2256,20 @@ class DeviceBatch:
         out = self._out_tensors("sizing", _field_shapes(SizingResult.FIELDS, self.B, self._sizes(H=H), keys), out)
         if self.B == 0:
             return out
-        self._need_fit("sizing", self.lib.trs_sz_fits(self.nJ_max, self.nM_max), "the step kernel (trs_sz_fits)")
-        self._factored = False
-        self._dynamic = None
-        self._forward = None
+        self._begin_iterated("sizing", (self.lib.trs_sz_fits, "the step kernel (trs_sz_fits)"))
         ws = self._sz_workspace(val, bounds, loads, out, own)
         with t.cuda.device(self.device):
             self.dofmap()
             out["weight_history"].zero_()
-            it = 0
-            while True:
-                last = it == val["max_iters"]
-                self._sz_analyse(ws)
-                self._sz_step(ws, it, 1 if last else 0)
-                if last or (it % val["check_every"] == 0 and int(ws["active"][it].item()) == 0):
-                    break
-                it += 1
+            it = self._iterate(ws, val["check_every"], self._analyse_cases, self._sz_step)
             if val["catalog"] is not None:
                 cat = t.from_numpy(val["catalog"]).to(self.device)
                 _capi.check(self.lib.trs_sz_snap(self.B, self.nM_max, self.nM.data_ptr(), ws["st"].data_ptr(), cat.data_ptr(),
                                                  int(cat.shape[0]), self.A.data_ptr(), out["catalog_index"].data_ptr(),
                                                  self._stream()), "trs_sz_snap")
-                self._sz_analyse(ws)
+                self._analyse_cases(ws)
                 self._sz_step(ws, it, 2)
-            out["status"].copy_(ws["st"][:, 0])
-            out["iterations"].copy_(ws["st"][:, 1])
-            # (what the factorisation reported for the design that ended a truss with status 2; 0 for every other truss)
-            self.info.copy_(ws["st"][:, 2])
-        self.cases_F = ws["F"]
-        self._factored = True   # (of the returned design, for every truss of status 0 or 1)
-        self._bump_generation()
+            self._end_iterated(ws, out)   # (the factor: of the returned design, for every truss of status 0 or 1)
         return out
 
     # the stages of `sizing` (tools/bench_sizing.py times them one by one)
@@ -2204,18 +2284,8 @@ class DeviceBatch:
         if any(isinstance(val[k], np.ndarray) for k in names):
             allow = t.from_numpy(np.stack([np.broadcast_to(val[k], [self.B]) for k in names], axis=1).copy()).to(dev)
             val = dict(val, **{k: float(np.max(val[k])) for k in names})   # (scalars that pass the library's own check)
-        return {"prev": t.zeros([self.B, max(self.nM_max, 1)], dtype=t.float64, device=dev),
-                "st": t.zeros([self.B, 4], dtype=t.int32, device=dev),
-                "active": t.zeros([val["max_iters"] + 1], dtype=t.int32, device=dev),
-                "F": self._case_block("cases_F", L), "L": L, "loads": loads, "own": own, "val": val, "bounds": bounds,
-                "allow": allow, "out": out}
-
-    def _sz_analyse(self, ws):
-        """Assembly and factorisation of the design `self.A`, gather and substitution of the L cases."""
-        self.assemble()
-        self.potrf()
-        self._gather_cases(ws["loads"], ws["L"], ws["F"], own=ws["own"])
-        self._potrs_cases(ws["F"], ws["L"])
+        prev = t.zeros([self.B, max(self.nM_max, 1)], dtype=t.float64, device=dev)
+        return self._run_state(val["max_iters"], L, loads, own, prev=prev, val=val, bounds=bounds, allow=allow, out=out)
 
     def _sz_step(self, ws, it, mode):
         val, out, (lo, hi) = ws["val"], ws["out"], ws["bounds"]
@@ -2226,7 +2296,7 @@ class DeviceBatch:
             val["allow_compression"], val["allow_displace"], _ptr(ws["allow"]), val["euler_kappa"], val["relax"],
             val["tol"], _ptr(lo[0]),
             lo[1], _ptr(hi[0]), hi[1], it, mode, ws["prev"].data_ptr(), ws["st"].data_ptr(),
-            ws["active"][min(it, val["max_iters"]):].data_ptr(), out["areas"].data_ptr(), out["weight"].data_ptr(),
+            self._active(ws, it), out["areas"].data_ptr(), out["weight"].data_ptr(),
             out["utilisation"].data_ptr(), out["governing"].data_ptr(), out["disp_ratio"].data_ptr(),
             out["weight_history"].data_ptr(), val["max_iters"] + 1, self._stream()), "trs_sz_step")
 
@@ -2258,10 +2328,7 @@ class DeviceBatch:
         path, `options["compact"]` and the table member form are refused, as in `sizing()`."""
         t = self.torch
         who = "min_compliance()"
-        self._need_slab("min_compliance", "writes no slab that the load cases could be solved against")
-        if self.table:
-            raise ValueError(f"{who}: the table member form cannot hold one area per member - use the general form "
-                             "(PackedBatch.general())")
+        self._refuse_iterated("min_compliance")
         own = loads is None   # (the batch's own loads are already in the batch's joint order: gathered without joint_in)
         loads = self._check_loads("min_compliance", self.loads.unsqueeze(1) if own else loads)
         L = int(loads.shape[1])
@@ -2270,19 +2337,7 @@ class DeviceBatch:
         val = _check_min_compliance_scalars(who, alpha, measure, eta, move, tol, max_iters, check_every, L)
         if levels not in (0, 1, 2, 3):
             raise ValueError(f"{who}: levels must be 0, 1, 2 or 3, got {levels!r}")
-        bounds = []
-        for name, x in (("area_min", area_min), ("area_max", area_max)):
-            if hasattr(x, "data_ptr"):
-                if list(x.shape) != [self.B, self.nM_max] or x.dtype != t.float64 or x.device != self.device:
-                    raise ValueError(f"{who}: {name} must be a number or a float64 [B={self.B}, nM_max={self.nM_max}] "
-                                     f"tensor on {self.device}")
-                bounds.append((x.contiguous(), 0.0))
-            else:
-                bounds.append((None, _check_number(who, name, x, "be a finite number or a float64 [B, nM_max] tensor")))
-        if bounds[0][0] is None and not bounds[0][1] > 0:
-            raise ValueError(f"{who}: area_min must be positive, got {area_min!r}")
-        if bounds[0][0] is None and bounds[1][0] is None and bounds[1][1] < bounds[0][1]:
-            raise ValueError(f"{who}: area_max must be >= area_min, got {area_max!r} < {area_min!r}")
+        bounds = self._area_bounds(who, area_min, area_max)
         if target is None:
             W = t.zeros([self.B], dtype=t.float64, device=self.device)   # (the step fills in the initial measure)
         elif hasattr(target, "data_ptr"):
@@ -2296,43 +2351,24 @@ class DeviceBatch:
                                 out)
         if self.B == 0:
             return out
-        self._need_fit("min_compliance", self.lib.trs_cm_fits(self.nJ_max, self.nM_max), "the step kernel (trs_cm_fits)")
-        self._factored = False
-        self._dynamic = None
-        self._forward = None
+        self._begin_iterated("min_compliance", (self.lib.trs_cm_fits, "the step kernel (trs_cm_fits)"))
         ws = self._cm_workspace(val, bounds, loads, W, out, own, levels)
         with t.cuda.device(self.device):
             self.dofmap()
             out["objective_history"].zero_()
-            it = 0
-            while True:
-                last = it == val["max_iters"]
-                self._sz_analyse(ws)
-                self._cm_step(ws, it, 1 if last else 0)
-                if last or (it % val["check_every"] == 0 and int(ws["active"][it].item()) == 0):
-                    break
-                it += 1
-            out["status"].copy_(ws["st"][:, 0])
-            out["iterations"].copy_(ws["st"][:, 1])
-            # (what the factorisation reported for the design that ended a truss with status 2; 0 for every other truss)
-            self.info.copy_(ws["st"][:, 2])
-        self.cases_F = ws["F"]
-        self._factored = True   # (of the returned design, for every truss of status 0 or 1)
-        self._bump_generation()
+            self._iterate(ws, val["check_every"], self._analyse_cases, self._cm_step)
+            self._end_iterated(ws, out)   # (the factor: of the returned design, for every truss of status 0 or 1)
         return out
 
-    # the stages of `min_compliance` (tools/bench_compliance.py times them one by one; the analysis is `_sz_analyse`)
+    # the stages of `min_compliance` (tools/bench_compliance.py times them one by one; the analysis is `_analyse_cases`)
     def _cm_workspace(self, val, bounds, loads, target, out, own=False, levels=0):
         """The state of a `min_compliance` run: the design before the last resizing, the status words st [B, 4] and the
         `active` counters (one per analysis), zeroed; the case block; the weights and the targets on the device."""
         t, dev = self.torch, self.device
         L = int(loads.shape[1])
-        return {"prev": t.zeros([self.B, max(self.nM_max, 1)], dtype=t.float64, device=dev),
-                "st": t.zeros([self.B, 4], dtype=t.int32, device=dev),
-                "active": t.zeros([val["max_iters"] + 1], dtype=t.int32, device=dev),
-                "alpha": t.from_numpy(val["alpha"]).to(dev), "target": target, "levels": levels,
-                "F": self._case_block("cases_F", L), "L": L, "loads": loads, "own": own, "val": val, "bounds": bounds,
-                "out": out}
+        prev = t.zeros([self.B, max(self.nM_max, 1)], dtype=t.float64, device=dev)
+        return self._run_state(val["max_iters"], L, loads, own, prev=prev, alpha=t.from_numpy(val["alpha"]).to(dev),
+                               target=target, levels=levels, val=val, bounds=bounds, out=out)
 
     def _cm_step(self, ws, it, mode):
         val, out, (lo, hi) = ws["val"], ws["out"], ws["bounds"]
@@ -2342,7 +2378,7 @@ class DeviceBatch:
             self.nM.data_ptr(), ws["F"].data_ptr(), self.rows, self.info.data_ptr(), ws["alpha"].data_ptr(),
             _capi.CM_MEASURES[val["measure"]], ws["target"].data_ptr(), val["eta"], val["move"], val["tol"], _ptr(lo[0]),
             lo[1], _ptr(hi[0]), hi[1], it, mode, ws["levels"], ws["prev"].data_ptr(), ws["st"].data_ptr(),
-            ws["active"][min(it, val["max_iters"]):].data_ptr(), out["areas"].data_ptr(), out["measure"].data_ptr(),
+            self._active(ws, it), out["areas"].data_ptr(), out["measure"].data_ptr(),
             out["compliance"].data_ptr(), out["objective"].data_ptr(), out["objective_history"].data_ptr(),
             val["max_iters"] + 1, out["sensitivity"].data_ptr(), out["multiplier"].data_ptr(), self._stream()),
             "trs_cm_step")
@@ -2382,10 +2418,7 @@ class DeviceBatch:
         `options["compact"]` and the table member form are refused, as in `sizing()`."""
         t = self.torch
         who = "unilateral()"
-        self._need_slab("unilateral", "writes no slab that the load cases could be solved against")
-        if self.table:
-            raise ValueError(f"{who}: the table member form cannot hold one area per member - use the general form "
-                             "(PackedBatch.general())")
+        self._refuse_iterated("unilateral")
         slack = _check_number(who, "slack_factor", slack_factor, "be a finite number >= 0", least=0)
         max_iters = _check_integer(who, "max_iters", max_iters, least=0)
         check_every = _check_integer(who, "check_every", check_every)
@@ -2408,12 +2441,8 @@ class DeviceBatch:
             return out
         if on["state"] is not None and on["state"].data_ptr() == out["state"].data_ptr():
             on["state"] = on["state"].clone()   # (the state written is zeroed first)
-        self._need_fit("unilateral", self.lib.trs_un_fits(self.nJ_max, self.nM_max), "the step kernel (trs_un_fits)")
-        self._need_fit("unilateral", self.lib.trs_effects_fits(self.nJ_max, self.nM_max),
-                       "the effect kernels (trs_effects_fits)")
-        self._factored = False
-        self._dynamic = None
-        self._forward = None
+        self._begin_iterated("unilateral", (self.lib.trs_un_fits, "the step kernel (trs_un_fits)"),
+                             (self.lib.trs_effects_fits, "the effect kernels (trs_effects_fits)"))
         ws = self._un_workspace(on, slack, max_iters, out)
         with t.cuda.device(self.device):
             self.dofmap()
@@ -2421,14 +2450,7 @@ class DeviceBatch:
                 out[key].zero_()
             if on["state"] is not None:   # the structure of analysis 0 (all active: the nominal areas as they are)
                 self.A.copy_(t.where((on["kind"] == 0) | (on["state"] != 0), ws["A_nom"], slack * ws["A_nom"]))
-            it = 0
-            while True:
-                last = it == max_iters
-                self._un_analyse(ws)
-                self._un_step(ws, it, 1 if last else 0)
-                if last or (it % check_every == 0 and int(ws["active"][it].item()) == 0):
-                    break
-                it += 1
+            it = self._iterate(ws, check_every, self._un_analyse, self._un_step)
             if bool((ws["st"][:, 0] == _capi.UN_NOT_PD).any().item()):
                 # (that truss's slab holds the failed factor of a state it no longer has; the others get the same bits)
                 self._un_analyse(ws)
@@ -2439,15 +2461,9 @@ class DeviceBatch:
                 ws["loads"].data_ptr(), _ptr(on["prestrain"]), None, None, self.free_index.data_ptr(), self.nJ.data_ptr(),
                 self.nM.data_ptr(), ws["F"].data_ptr(), self.rows, out["u"].data_ptr(), out["f_ext"].data_ptr(),
                 out["N"].data_ptr(), None, jo, stream), "trs_effects_recover")
-            out["status"].copy_(ws["st"][:, 0])
-            out["iterations"].copy_(ws["st"][:, 1])
             live = t.arange(self.nM_max, device=self.device)[None, :] < self.nM[:, None]
             out["areas_effective"].copy_(t.where(live, self.A, t.zeros_like(self.A)))
-            # (what the factorisation reported for the structure that ended a truss with status 2; 0 for every other truss)
-            self.info.copy_(ws["st"][:, 2])
-        self.cases_F = ws["F"]
-        self._factored = True   # (of the final structure)
-        self._bump_generation()
+            self._end_iterated(ws, out)   # (the factor: of the final structure)
         return out
 
     # the stages of `unilateral` (tools/bench_unilateral.py times them one by one)
@@ -2456,16 +2472,10 @@ class DeviceBatch:
         st [B, 4] and the `active` counters (one per analysis), zeroed; the case block; the loads in the caller's joint
         numbering (the batch's own are carried there through `joint_out`)."""
         t, dev = self.torch, self.device
-        loads = on["loads"]
-        if loads is None:
-            loads = self.loads
-            if self.joint_out is not None:
-                index = self.joint_out.long().unsqueeze(-1).expand(-1, -1, 3)
-                loads = t.zeros_like(self.loads).scatter_(1, index, self.loads)
-        return {"A_nom": self.A.clone(), "prev": t.zeros([self.B, max(self.nM_max, 1)], dtype=t.int8, device=dev),
-                "st": t.zeros([self.B, 4], dtype=t.int32, device=dev),
-                "active": t.zeros([max_iters + 1], dtype=t.int32, device=dev), "F": self._case_block("cases_F", 1),
-                "loads": loads.contiguous(), "on": on, "slack": slack, "max_iters": max_iters, "out": out}
+        loads = self._own_loads() if on["loads"] is None else on["loads"]
+        return self._run_state(max_iters, 1, loads.contiguous(), A_nom=self.A.clone(),
+                               prev=t.zeros([self.B, max(self.nM_max, 1)], dtype=t.int8, device=dev), on=on, slack=slack,
+                               out=out)
 
     def _un_analyse(self, ws):
         """Assembly and factorisation of the structure `self.A`, right-hand side (with the pre-strain loads of these
@@ -2487,8 +2497,8 @@ class DeviceBatch:
             self.free_index.data_ptr(), self.n_free.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), ws["F"].data_ptr(),
             self.rows, self.info.data_ptr(), _ptr(on["prestrain"]), on["kind"].data_ptr(), ws["A_nom"].data_ptr(),
             ws["slack"], _ptr(on["state"]), it, mode, out["state"].data_ptr(), ws["prev"].data_ptr(), ws["st"].data_ptr(),
-            ws["active"][min(it, ws["max_iters"]):].data_ptr(), out["violations"].data_ptr(),
-            out["flips_history"].data_ptr(), ws["max_iters"] + 1, self._stream()), "trs_un_step")
+            self._active(ws, it), out["violations"].data_ptr(), out["flips_history"].data_ptr(), ws["limit"] + 1,
+            self._stream()), "trs_un_step")
 
     # -- collapse load: elastic-plastic members, event to event on the device (include/trs_plastic.h) -------------------
     def plastic(self, cap_tension, cap_compression, loads=None, hardening=0.0, lambda_max=1.0, disp_limit=0.0,
@@ -2526,10 +2536,7 @@ class DeviceBatch:
         are refused, as in `sizing()`."""
         t = self.torch
         who = "plastic()"
-        self._need_slab("plastic", "writes no slab that the load pattern could be solved against")
-        if self.table:
-            raise ValueError(f"{who}: the table member form cannot hold one area per member - use the general form "
-                             "(PackedBatch.general())")
+        self._refuse_iterated("plastic", "load pattern")
         val = _check_plastic_scalars(who, hardening, lambda_max, disp_limit, collapse_ratio, tie_tol, max_events, check_every)
         given = {"cap_tension": (cap_tension, [self.B, self.nM_max]), "cap_compression": (cap_compression, [self.B, self.nM_max]),
                  "loads": (loads, [self.B, self.nJ_max, 3])}
@@ -2549,38 +2556,22 @@ class DeviceBatch:
         out = self._out_tensors("plastic", _field_shapes(PlasticResult.CASE_FIELDS, self.B, self._sizes(H=H)), out)
         if self.B == 0:
             return out
-        self._need_fit("plastic", self.lib.trs_pl_fits(self.nJ_max, self.nM_max), "the step kernel (trs_pl_fits)")
-        self._factored = False
-        self._dynamic = None
-        self._forward = None
+        self._begin_iterated("plastic", (self.lib.trs_pl_fits, "the step kernel (trs_pl_fits)"))
         ws = self._pl_workspace(on, val, out)
         with t.cuda.device(self.device):
             self.dofmap()
             for key in ("N", "state", "lambda_history", "umax_history", "member_history", "count_history"):
                 out[key].zero_()
-            it = 0
-            while True:
-                last = it == val["max_events"]
-                self._pl_analyse(ws)
-                self._pl_step(ws, it, 1 if last else 0)
-                if last or (it % val["check_every"] == 0 and int(ws["active"][it].item()) == 0):
-                    break
-                it += 1
+            self._iterate(ws, val["check_every"], self._analyse_cases, self._pl_step)
             jo, stream, _ = self._case_launch()
             _capi.check(self.lib.trs_pl_finish(
                 self.B, self.nJ_max, self.nM_max, self.xyz.data_ptr(), self.conn.data_ptr(), self.free_index.data_ptr(),
                 self.n_free.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), self.rows, ws["loads"].data_ptr(),
                 out["N"].data_ptr(), ws["U"].data_ptr(), ws["acc"].data_ptr(), jo, out["u"].data_ptr(),
                 out["f_ext"].data_ptr(), stream), "trs_pl_finish")
-            out["status"].copy_(ws["st"][:, 0])
-            out["events"].copy_(ws["st"][:, 1])
             out["load_factor"].copy_(ws["acc"][:, 0])
             out["areas_effective"].copy_(t.where(live, self.A, t.zeros_like(self.A)))
-            # (what the factorisation reported for the tangent that ended a truss as a mechanism; 0 for every other truss)
-            self.info.copy_(ws["st"][:, 2])
-        self.cases_F = ws["F"]
-        self._factored = True   # (of the final tangent structure, where info is 0)
-        self._bump_generation()
+            self._end_iterated(ws, out, count="events")   # (the factor: of the final tangent structure, where info is 0)
         return out
 
     # the stages of `plastic` (tools/bench_plastic.py times them one by one)
@@ -2590,24 +2581,11 @@ class DeviceBatch:
         counters (one per analysis), zeroed; the case block; the load pattern in the caller's joint numbering (the
         batch's own is carried there through `joint_out`)."""
         t, dev = self.torch, self.device
-        loads = on["loads"]
-        if loads is None:
-            loads = self.loads
-            if self.joint_out is not None:
-                index = self.joint_out.long().unsqueeze(-1).expand(-1, -1, 3)
-                loads = t.zeros_like(self.loads).scatter_(1, index, self.loads)
-        return {"A_nom": self.A.clone(), "U": t.zeros([self.B, 3 * self.nJ_max], dtype=t.float64, device=dev),
-                "acc": t.zeros([self.B, 4], dtype=t.float64, device=dev),
-                "st": t.zeros([self.B, 4], dtype=t.int32, device=dev),
-                "active": t.zeros([val["max_events"] + 1], dtype=t.int32, device=dev), "F": self._case_block("cases_F", 1),
-                "loads": loads.contiguous(), "on": on, "val": val, "out": out}
-
-    def _pl_analyse(self, ws):
-        """Assembly and factorisation of the structure `self.A`, gather and substitution of the load pattern."""
-        self.assemble()
-        self.potrf()
-        self._gather_cases(ws["loads"], 1, ws["F"])
-        self._potrs_cases(ws["F"], 1)
+        loads = self._own_loads() if on["loads"] is None else on["loads"]
+        # (own=False: the pattern is in the caller's numbering either way; `_analyse_cases` gathers it through joint_in)
+        return self._run_state(val["max_events"], 1, loads.contiguous(), A_nom=self.A.clone(),
+                               U=t.zeros([self.B, 3 * self.nJ_max], dtype=t.float64, device=dev),
+                               acc=t.zeros([self.B, 4], dtype=t.float64, device=dev), on=on, val=val, out=out)
 
     def _pl_step(self, ws, it, mode):
         on, val, out = ws["on"], ws["val"], ws["out"]
@@ -2618,7 +2596,7 @@ class DeviceBatch:
             on["cap_compression"].data_ptr(), ws["A_nom"].data_ptr(), val["hardening"], val["lambda_max"],
             val["disp_limit"], val["collapse_ratio"], val["tie_tol"], it, mode, out["state"].data_ptr(),
             out["N"].data_ptr(), ws["U"].data_ptr(), ws["acc"].data_ptr(), ws["st"].data_ptr(),
-            ws["active"][min(it, val["max_events"]):].data_ptr(), out["lambda_history"].data_ptr(),
+            self._active(ws, it), out["lambda_history"].data_ptr(),
             out["member_history"].data_ptr(), out["count_history"].data_ptr(), out["umax_history"].data_ptr(),
             val["max_events"] + 1, self._stream()), "trs_pl_step")
 
@@ -4058,6 +4036,31 @@ def _new_result(torch, dev, cls, B, sizes, without=()):
     return cls(**made, info=torch.zeros([B], dtype=torch.int32, device=dev))
 
 
+def _upload_design_args(torch, dev, val):
+    """(`on`, `bound`) of the two sizing analyses: "loads", "area_min" and "area_max" of `val` on `dev` - an array is
+    uploaded, a number or None stays -, and bound(part, x): a bound [B, nM_max] cut to the bucket `part`, a number as it
+    is."""
+    on = {k: _device_f64(torch, dev, val[k]) if isinstance(val[k], np.ndarray) else val[k]
+          for k in ("loads", "area_min", "area_max")}
+    return on, lambda part, x: part.cut(x, nM=1) if hasattr(x, "data_ptr") else x
+
+
+def _per_case_runs(torch, db, part, out, L, run):
+    """The L cases of an analysis whose run writes the areas, on the resident bucket `db`: run(l) -> the dict of the
+    `DeviceBatch` method, each an independent run from the nominal areas, into `out`[:, l] by `CASE_FIELDS`.  `db.info`
+    ends as what the first case with a nonzero info left, per truss."""
+    nominal = db.A.clone()
+    info = torch.zeros_like(db.info)
+    for l in range(L):
+        db.A.copy_(nominal)
+        res = run(l)
+        for field, (key, fill, dtype, shape) in type(out).CASE_FIELDS.items():
+            part.put(getattr(out, field)[:, l], res[key], nJ=1 if "nJ" in shape else None,
+                     nM=1 if "nM" in shape else None)
+        info = torch.where(info != 0, info, db.info)
+    db.info.copy_(info)
+
+
 def _put_result(part, out, res):
     """A bucket's results `res` (the dict of the `DeviceBatch` method) into the full-batch dataclass `out`: the "nJ" and
     "nM" places of a field's shape are the axes `_Bucket.put` narrows; a key that `res` lacks keeps its fill value."""
@@ -5012,27 +5015,14 @@ def _check_sizing_args(packed, loads=None, allow_tension=None, allow_compression
     of `_check_sizing_scalars` plus "loads" (a float64 host array [B, L, nJ_max, 3], or None for the batch's own loads)
     and "area_min" / "area_max" (each a float, or a float64 host array [B, nM_max])."""
     who = "solve_sizing"
-    _refuse_sections(who, "the member sizing (it writes the sections)", sections)
-    if options and options.get("compact"):
-        raise ValueError(f"{who}: options['compact'] writes no slab that the load cases could be solved against")
+    _refuse_variants(who, "the member sizing (it writes the sections)", sections, options)
     for name, x in (("allow_tension", allow_tension), ("allow_compression", allow_compression)):
         if x is None:
             raise ValueError(f"{who}: {name} must be given")
     B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
     val = _check_sizing_scalars(who, allow_tension, allow_compression, allow_displace, euler_kappa, relax, tol, max_iters,
                                 check_every, catalog, B=B)
-    val["loads"] = None
-    if loads is not None:
-        try:
-            x = _host_array(loads, np.float64)
-        except (TypeError, ValueError):
-            x = None
-        shape = None if x is None else tuple(x.shape)
-        if x is None or len(shape) != 4 or shape[0] != B or shape[1] < 1 or shape[2] != nJ_max or shape[3] not in (2, 3):
-            raise ValueError(f"{who}: loads must be [B={B}, L >= 1, nJ_max={nJ_max}, 2 or 3], got {shape}")
-        if not np.isfinite(x).all():
-            raise ValueError(f"{who}: loads must be finite")
-        val["loads"] = np.ascontiguousarray(np.pad(x, [(0, 0)] * 3 + [(0, 3 - shape[3])]))
+    val["loads"] = _check_case_loads(who, loads, B, nJ_max)
     (lo, lo_arr), (hi, hi_arr) = _check_area_bounds(who, area_min, area_max, B, packed.nM, nM_max)
     val["area_min"], val["area_max"] = (lo if lo_arr is None else lo_arr), (hi if hi_arr is None else hi_arr)
     live = np.arange(nM_max)[None, :] < np.asarray(packed.nM)[:, None]
@@ -5074,9 +5064,7 @@ def solve_sizing(trusses_or_packed, loads=None, allow_tension=None, allow_compre
     torch, dev = _require_gpu(device)
     out = _new_result(torch, dev, SizingResult, packed.B, {"nM": packed.nM_max, "H": val["max_iters"] + 1},
                       without=() if val["catalog"] is not None else ("catalog_index",))
-    on = {k: _device_f64(torch, dev, val[k]) if isinstance(val[k], np.ndarray) else val[k]
-          for k in ("loads", "area_min", "area_max")}
-    bound = lambda part, x: part.cut(x, nM=1) if hasattr(x, "data_ptr") else x
+    on, bound = _upload_design_args(torch, dev, val)
     per_truss = lambda part, x: x[part.index] if isinstance(x, np.ndarray) else x
     for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope,
                                       factor=lambda db, part: None):
@@ -5127,22 +5115,9 @@ def _check_min_compliance_args(packed, loads=None, alpha=None, target=None, meas
     batch's own loads), "target" (None, or a float64 array [B]) and "area_min" / "area_max" (each a float, or a float64
     host array [B, nM_max])."""
     who = "solve_min_compliance"
-    _refuse_sections(who, "the compliance sizing (it writes the sections)", sections)
-    if options and options.get("compact"):
-        raise ValueError(f"{who}: options['compact'] writes no slab that the load cases could be solved against")
+    _refuse_variants(who, "the compliance sizing (it writes the sections)", sections, options)
     B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
-    host_loads = None
-    if loads is not None:
-        try:
-            x = _host_array(loads, np.float64)
-        except (TypeError, ValueError):
-            x = None
-        shape = None if x is None else tuple(x.shape)
-        if x is None or len(shape) != 4 or shape[0] != B or shape[1] < 1 or shape[2] != nJ_max or shape[3] not in (2, 3):
-            raise ValueError(f"{who}: loads must be [B={B}, L >= 1, nJ_max={nJ_max}, 2 or 3], got {shape}")
-        if not np.isfinite(x).all():
-            raise ValueError(f"{who}: loads must be finite")
-        host_loads = np.ascontiguousarray(np.pad(x, [(0, 0)] * 3 + [(0, 3 - shape[3])]))
+    host_loads = _check_case_loads(who, loads, B, nJ_max)
     L = 1 if host_loads is None else host_loads.shape[1]
     val = _check_min_compliance_scalars(who, alpha, measure, eta, move, tol, max_iters, check_every, L)
     val["loads"] = host_loads
@@ -5190,9 +5165,7 @@ def solve_min_compliance(trusses_or_packed, loads=None, alpha=None, target=None,
     torch, dev = _require_gpu(device)
     L = 1 if val["loads"] is None else int(val["loads"].shape[1])
     out = _new_result(torch, dev, MinComplianceResult, packed.B, {"nM": packed.nM_max, "H": val["max_iters"] + 1, "L": L})
-    on = {k: _device_f64(torch, dev, val[k]) if isinstance(val[k], np.ndarray) else val[k]
-          for k in ("loads", "area_min", "area_max")}
-    bound = lambda part, x: part.cut(x, nM=1) if hasattr(x, "data_ptr") else x
+    on, bound = _upload_design_args(torch, dev, val)
     for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope,
                                       factor=lambda db, part: None):
         _put_result(part, out, db.min_compliance(
@@ -5240,9 +5213,7 @@ def _check_unilateral_args(packed, kind, loads=None, prestrain=None, slack_facto
     loads), "prestrain" (float64 [B, L, nM_max] or None), "state" (int8 [B, nM_max] of 0 / 1, or None), "L",
     "slack_factor", "max_iters", "check_every"."""
     who = "solve_unilateral"
-    _refuse_sections(who, "unilateral members (the iteration writes the areas)", sections)
-    if options and options.get("compact"):
-        raise ValueError(f"{who}: options['compact'] writes no slab that the load cases could be solved against")
+    _refuse_variants(who, "unilateral members (the iteration writes the areas)", sections, options)
     B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
     val = {"slack_factor": _check_number(who, "slack_factor", slack_factor, "be a finite number >= 0", least=0),
            "max_iters": _check_integer(who, "max_iters", max_iters, least=0),
@@ -5267,18 +5238,8 @@ def _check_unilateral_args(packed, kind, loads=None, prestrain=None, slack_facto
     val["state"] = None
     if state is not None:
         val["state"] = np.ascontiguousarray((members("state", state, "1 (active) and 0 (slack)") != 0).astype(np.int8))
-    val["loads"], val["prestrain"], L = None, None, None
-    if loads is not None:
-        try:
-            x = _host_array(loads, np.float64)
-        except (TypeError, ValueError):
-            x = None
-        shape = None if x is None else tuple(x.shape)
-        if x is None or len(shape) != 4 or shape[0] != B or shape[1] < 1 or shape[2] != nJ_max or shape[3] not in (2, 3):
-            raise ValueError(f"{who}: loads must be [B={B}, L >= 1, nJ_max={nJ_max}, 2 or 3], got {shape}")
-        if not np.isfinite(x).all():
-            raise ValueError(f"{who}: loads must be finite")
-        val["loads"], L = np.ascontiguousarray(np.pad(x, [(0, 0)] * 3 + [(0, 3 - shape[3])])), shape[1]
+    val["loads"], val["prestrain"] = _check_case_loads(who, loads, B, nJ_max), None
+    L = None if val["loads"] is None else val["loads"].shape[1]
     if prestrain is not None:
         try:
             x = _host_array(prestrain, np.float64)
@@ -5332,19 +5293,11 @@ def solve_unilateral(trusses_or_packed, kind, loads=None, prestrain=None, slack_
     case = lambda x, l: None if x is None else x[:, l].contiguous()
     for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope,
                                       factor=lambda db, part: None):
-        nominal = db.A.clone()
         kinds, states = part.cut(on["kind"], nM=1), part.cut(on["state"], nM=1)
         forces, strains = part.cut(on["loads"], nJ=2), part.cut(on["prestrain"], nM=2)
-        info = torch.zeros_like(db.info)
-        for l in range(L):
-            db.A.copy_(nominal)
-            res = db.unilateral(kinds, case(forces, l), case(strains, l), slack_factor=val["slack_factor"],
-                                max_iters=val["max_iters"], check_every=val["check_every"], state=states)
-            for field, (key, fill, dtype, shape) in UnilateralResult.CASE_FIELDS.items():
-                part.put(getattr(out, field)[:, l], res[key], nJ=1 if "nJ" in shape else None,
-                         nM=1 if "nM" in shape else None)
-            info = torch.where(info != 0, info, db.info)
-        db.info.copy_(info)
+        _per_case_runs(torch, db, part, out, L, lambda l: db.unilateral(
+            kinds, case(forces, l), case(strains, l), slack_factor=val["slack_factor"], max_iters=val["max_iters"],
+            check_every=val["check_every"], state=states))
     return _finish_result(torch, dev, out, on_device)
 
 
@@ -5404,9 +5357,8 @@ def _check_plastic_args(packed, cap_tension, cap_compression, loads=None, harden
     "cap_tension", "cap_compression" (float64 [B, nM_max], 1 on the padding), "loads" (float64 [B, L, nJ_max, 3] or None
     for the batch's own loads), "L" and the scalars."""
     who = "solve_plastic"
-    _refuse_sections(who, "the collapse-load analysis (the iteration writes the areas)", sections)
-    if options and options.get("compact"):
-        raise ValueError(f"{who}: options['compact'] writes no slab that the load pattern could be solved against")
+    _refuse_variants(who, "the collapse-load analysis (the iteration writes the areas)", sections, options,
+                     "load pattern")
     B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
     val = _check_plastic_scalars(who, hardening, lambda_max, disp_limit, collapse_ratio, tie_tol, max_events, check_every)
     live = np.arange(nM_max)[None, :] < np.asarray(packed.nM).reshape(B, 1)
@@ -5422,19 +5374,8 @@ def _check_plastic_args(packed, cap_tension, cap_compression, loads=None, harden
         if not (np.isfinite(x) & (x > 0)).all():
             raise ValueError(f"{who}: {name} must be positive and finite")
         val[name] = np.ascontiguousarray(x)
-    val["loads"], L = None, 1
-    if loads is not None:
-        try:
-            x = _host_array(loads, np.float64)
-        except (TypeError, ValueError):
-            x = None
-        shape = None if x is None else tuple(x.shape)
-        if x is None or len(shape) != 4 or shape[0] != B or shape[1] < 1 or shape[2] != nJ_max or shape[3] not in (2, 3):
-            raise ValueError(f"{who}: loads must be [B={B}, L >= 1, nJ_max={nJ_max}, 2 or 3], got {shape}")
-        if not np.isfinite(x).all():
-            raise ValueError(f"{who}: loads must be finite")
-        val["loads"], L = np.ascontiguousarray(np.pad(x, [(0, 0)] * 3 + [(0, 3 - shape[3])])), shape[1]
-    val["L"] = L
+    val["loads"] = _check_case_loads(who, loads, B, nJ_max)
+    val["L"] = L = 1 if val["loads"] is None else val["loads"].shape[1]
     nbytes = B * L * (8 * 6 * nJ_max + (8 + 8 + 1) * nM_max + 24 * (val["max_events"] + 1) + 16)
     if nbytes > max_result_bytes:
         raise ValueError(f"{who}: the results of B={B} trusses take {nbytes} bytes, more than max_result_bytes = "
@@ -5475,21 +5416,12 @@ def solve_plastic(trusses_or_packed, cap_tension, cap_compression, loads=None, h
                                    "check_every")}
     for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope,
                                       factor=lambda db, part: None):
-        nominal = db.A.clone()
         tension, compression = part.cut(on["cap_tension"], nM=1), part.cut(on["cap_compression"], nM=1)
         # (the padding of a bucket narrower or wider than the batch: a capacity that passes the check)
         live = torch.arange(db.nM_max, device=dev)[None, :] < db.nM[:, None]
         tension, compression = (torch.where(live, x, torch.ones_like(x)) for x in (tension, compression))
         forces = part.cut(on["loads"], nJ=2)
-        info = torch.zeros_like(db.info)
-        for l in range(L):
-            db.A.copy_(nominal)
-            res = db.plastic(tension, compression, case(forces, l), **scalars)
-            for field, (key, fill, dtype, shape) in PlasticResult.CASE_FIELDS.items():
-                part.put(getattr(out, field)[:, l], res[key], nJ=1 if "nJ" in shape else None,
-                         nM=1 if "nM" in shape else None)
-            info = torch.where(info != 0, info, db.info)
-        db.info.copy_(info)
+        _per_case_runs(torch, db, part, out, L, lambda l: db.plastic(tension, compression, case(forces, l), **scalars))
     return _finish_result(torch, dev, out, on_device)
 
 

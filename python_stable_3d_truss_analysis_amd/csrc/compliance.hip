@@ -33,9 +33,14 @@
 #include "../../include/trs_compliance.h"
 #include "../../include/trs_solver.h"
 #include "trs_common.h"
+#include "trs_iterate.h"
 #include "trs_lds.h"
 
 namespace {
+
+using Run = trs_iter::Run<TRS_CM_ACTIVE, TRS_CM_NOT_PD>;
+using trs_iter::wave_max;
+using trs_iter::wave_sum;
 
 constexpr int RED = 64;          // doubles for the reductions: two sets of (7 points x 4 waves), rounded up
 
@@ -73,18 +78,6 @@ __host__ __device__ inline StepTables step_layout(Arena& a, int nJ_max, int nM_m
 
 size_t step_lds(int nJ_max, int nM_max) { return trs_lds::count([&](auto& a) { step_layout(a, nJ_max, nM_max); }); }
 
-__device__ __forceinline__ double wave_sum(double v) {   // the butterfly lane ^ 32, ^ 16, ... ^ 1
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-    return v;
-}
-
 // K sums and two maxima of a 256-thread work-group behind one pair of barriers: slot [4 (K + 2)]
 template <int K>
 __device__ __forceinline__ void block_reduce(double (&sum)[K], double (&top)[2], double* slot, const int tid) {
@@ -112,9 +105,7 @@ struct StepArgs {
     const double* alpha;      // [L]
     double* target;           // [B]
     double eta, move, tol;
-    const double* a_min;      // [B][nM_max] or null
-    const double* a_max;
-    double a_min_all, a_max_all;
+    trs_iter::AreaBounds bounds;
     int L, it, mode, H, measure;
     double* A;                // [B][nM_max]
     double* prev;             // [B][nM_max]
@@ -217,14 +208,9 @@ __global__ __launch_bounds__(256) void trs_cm_step_kernel(const TrsBatch bt, con
     const int b = blockIdx.x, tid = threadIdx.x;
     const int nM_max = bt.nM_max, ld_f = bt.ld_f;
     const int mode = g.mode, it = g.it, L = g.L;
-    // (every thread reads the status words and the target here; thread 0 writes them behind the barriers below)
-    int status = g.st[4 * b], its = g.st[4 * b + 1];
-    if (it == 0) {   // the run begins
-        status = TRS_CM_ACTIVE;
-        its = 0;
-    }
-    if (status != TRS_CM_ACTIVE) return;   // (uniform over the work-group) frozen: nothing is touched
-    double W = g.target[b];
+    Run run(g.st + 4 * b, it == 0);   // (no report mode here: nothing follows the last resizing)
+    if (!run.active()) return;        // (uniform over the work-group) frozen: nothing is touched
+    double W = g.target[b];           // (read by every thread here; thread 0 writes it behind the barriers below)
     const TrussView tr = bt.truss(b);
     const int members = tr.members, ndof_max = tr.ndof_max;
     const size_t mbase = tr.mbase;
@@ -242,33 +228,19 @@ __global__ __launch_bounds__(256) void trs_cm_step_kernel(const TrsBatch bt, con
         }
         if (it == 0)
             for (int l = tid; l < L; l += 256) g.compliance[(size_t)b * L + l] = 0.0;
-        __syncthreads();   // (every thread has read the status words)
-        if (tid == 0) {
-            g.st[4 * b] = TRS_CM_NOT_PD;
-            g.st[4 * b + 1] = its > 0 ? its - 1 : 0;
-            g.st[4 * b + 2] = pivot;
-            if (it == 0) {
-                g.measure_out[b] = 0.0;
-                g.objective[b] = 0.0;
-                g.multiplier[b] = 0.0;
-            }
+        run.fail(pivot, run.one_back(), tid);
+        if (tid == 0 && it == 0) {
+            g.measure_out[b] = 0.0;
+            g.objective[b] = 0.0;
+            g.multiplier[b] = 0.0;
         }
         return;
     }
     trs_lds::Carve lds(sh);
     const StepTables t = step_layout(lds, bt.nJ_max, nM_max);
-    const double* Fb = g.F + (size_t)b * L * ld_f;
-    // (thread d % 256 forms and reads row[d]: no barrier between the table and the staging)
-    for (int d = tid; d < ndof_max; d += 256) t.row[d] = tr.row_of(d);
-    auto stage = [&](int l) {   // case l into buffer l & 1: held DOFs and the padding read 0
-        double* u = t.u + (size_t)(l & 1) * ndof_max;
-        const double* f = Fb + (size_t)l * ld_f;
-        for (int d = tid; d < ndof_max; d += 256) {
-            const int r = t.row[d];
-            u[d] = r >= 0 ? f[r] : 0.0;
-        }
-    };
-    stage(0);
+    const trs_iter::CaseStage cases = {t.u, t.row, g.F + (size_t)b * L * ld_f, ndof_max, ld_f};
+    cases.form_rows(tr, tid);
+    cases.stage(0, tid);
     // ---- the member geometry, once; the measure of the design ----
     const bool by_weight = g.measure == TRS_CM_WEIGHT;
     double msum = 0.0;
@@ -297,7 +269,7 @@ __global__ __launch_bounds__(256) void trs_cm_step_kernel(const TrsBatch bt, con
         J += g.alpha[l] * C;
     };
     for (int l = 0; l < L; ++l) {
-        const double* u = t.u + (size_t)(l & 1) * ndof_max;
+        const double* u = cases.buffer(l);
         const double al = g.alpha[l];
         double csum = 0.0;
         for (int m = tid; m < members; m += 256) {
@@ -315,7 +287,7 @@ __global__ __launch_bounds__(256) void trs_cm_step_kernel(const TrsBatch bt, con
         // (slot set l & 1: thread 0 read it for case l - 2 before the barrier of case l - 1)
         if ((tid & 63) == 0) t.red[(l & 1) * 4 + (tid >> 6)] = csum;
         if (tid == 0 && l > 0) fold(l - 1);
-        if (l + 1 < L) stage(l + 1);   // (the other buffer: its readers passed the barrier of case l - 1)
+        if (l + 1 < L) cases.stage(l + 1, tid);   // (the other buffer: its readers passed the barrier of case l - 1)
         __syncthreads();
     }
     if (tid == 0) fold(L - 1);
@@ -329,8 +301,7 @@ __global__ __launch_bounds__(256) void trs_cm_step_kernel(const TrsBatch bt, con
             area = Ab[m];
             s = t.s[m];
             const double w = t.w[m];
-            const double a_lo = g.a_min != nullptr ? g.a_min[mbase + m] : g.a_min_all;
-            const double a_hi = g.a_max != nullptr ? g.a_max[mbase + m] : g.a_max_all;
+            const double a_lo = g.bounds.lo(mbase + m), a_hi = g.bounds.hi(mbase + m);
             double lo, hi, p = 0.0;
             if (w > 0.0) {
                 lo = fmin(fmax((1.0 - move) * area, a_lo), a_hi);
@@ -416,11 +387,10 @@ __global__ __launch_bounds__(256) void trs_cm_step_kernel(const TrsBatch bt, con
         change = top[0];
     }
     if (change <= g.tol)
-        status = TRS_CM_CONVERGED;
+        run.status = TRS_CM_CONVERGED;
     else if (mode == 1)
-        status = TRS_CM_ITER_LIMIT;
-    const bool still = status == TRS_CM_ACTIVE;
-    if (still) {
+        run.status = TRS_CM_ITER_LIMIT;
+    if (run.active()) {
         for (int m = tid; m < members; m += 256) {   // (the thread that owns member m wrote t.k[m])
             g.prev[mbase + m] = Ab[m];
             Ab[m] = t.k[m];
@@ -432,9 +402,7 @@ __global__ __launch_bounds__(256) void trs_cm_step_kernel(const TrsBatch bt, con
         g.multiplier[b] = mult;
         if (it == 0) g.target[b] = W;
         if (it < g.H) g.history[(size_t)b * g.H + it] = J;
-        g.st[4 * b] = status;
-        g.st[4 * b + 1] = still ? it + 1 : its;
-        if (still) atomicAdd(g.active, 1);
+        run.finish(it, g.active);
     }
 }
 
@@ -460,8 +428,8 @@ int trs_cm_step(int B, int L, int nJ_max, int nM_max, const double* xyz, const i
         levels < 0 || levels > 3 || (measure != TRS_CM_WEIGHT && measure != TRS_CM_VOLUME))
         return (int)hipErrorInvalidValue;
     if (!(eta > 0.0) || !(eta <= 1.0) || !(move > 0.0) || !(move <= 1.0) || !(tol >= 0.0)) return (int)hipErrorInvalidValue;
-    if (!a_min && !(a_min_all > 0.0)) return (int)hipErrorInvalidValue;
-    if (!a_min && !a_max && !(a_max_all >= a_min_all)) return (int)hipErrorInvalidValue;
+    const trs_iter::AreaBounds bounds = {a_min, a_max, a_min_all, a_max_all};
+    if (!bounds.valid()) return (int)hipErrorInvalidValue;
     if (B == 0) return 0;
     if (!xyz || !conn || !E || !A || !rho || !free_index || !F || !info || !alpha || !target || !prev || !st || !active ||
         !areas || !measure_out || !compliance || !objective || (H > 0 && !objective_history) || !sensitivity || !multiplier)
@@ -469,7 +437,7 @@ int trs_cm_step(int B, int L, int nJ_max, int nM_max, const double* xyz, const i
     if (!trs_cm_fits(nJ_max, nM_max)) return (int)hipErrorInvalidValue;
     const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_general(conn, E, A, rho), free_index, n_free, nJ, nM,
                                   nullptr, ld_f);
-    const StepArgs g = {F, info, alpha, target, eta, move, tol, a_min, a_max, a_min_all, a_max_all, L, it, mode, H,
+    const StepArgs g = {F, info, alpha, target, eta, move, tol, bounds, L, it, mode, H,
                         measure, A, prev, st, active, areas, measure_out, compliance, objective, objective_history,
                         sensitivity, multiplier};
     trs_lds::raise_lds_once<trs_cm_step_kernel>();

@@ -39,6 +39,7 @@
 #include "../../include/trs_plastic.h"
 #include "../../include/trs_solver.h"
 #include "trs_common.h"
+#include "trs_iterate.h"
 #include "trs_lds.h"
 
 #include <cfloat>
@@ -46,6 +47,8 @@
 #include <cmath>
 
 namespace {
+
+using Run = trs_iter::Run<TRS_PL_ACTIVE, TRS_PL_MECHANISM>;
 
 // LDS tables of the step kernel
 struct StepTables {
@@ -107,30 +110,21 @@ __global__ __launch_bounds__(256) void trs_pl_step_kernel(const TrsBatch bt, con
     extern __shared__ double sh[];   // (no static LDS beside it: the dynamic ceiling is the whole of a CU's)
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int mode = g.mode, it = g.it;
-    // (every thread reads the status words here; thread 0 writes them behind the barriers below)
-    int status = g.st[4 * b], events = g.st[4 * b + 1];
+    // (every thread reads the accumulated state here; thread 0 writes it behind the barriers below)
     double lam = g.acc[4 * b], r0 = g.acc[4 * b + 1], umax = g.acc[4 * b + 2];
     const int pivot = g.info[b];
     const bool begin = it == 0;
-    if (begin) {   // the run begins
-        status = TRS_PL_ACTIVE;
-        events = 0;
-        lam = r0 = umax = 0.0;
-    }
-    if (status != TRS_PL_ACTIVE) return;   // (uniform over the work-group) frozen: nothing is touched
+    Run run(g.st + 4 * b, begin);   // (the count: events)
+    if (begin) lam = r0 = umax = 0.0;   // this analysis's own: the accumulated state begins with the run
+    if (!run.active()) return;   // (uniform over the work-group) frozen: nothing is touched
     const size_t hist = (size_t)b * g.H + it;
-    if (pivot != 0) {   // 2. status 2: nothing advances, the info is latched
-        __syncthreads();   // (every thread has read the status words)
-        if (tid == 0) {
-            g.st[4 * b] = TRS_PL_MECHANISM;
-            g.st[4 * b + 1] = events;
-            g.st[4 * b + 2] = pivot;
-            if (it < g.H) {
-                g.lambda_history[hist] = lam;
-                g.member_history[hist] = -2;
-                g.count_history[hist] = 0;
-                g.umax_history[hist] = umax;
-            }
+    if (pivot != 0) {   // 2. status 2: nothing advances - the events stay, no roll-back -, the info is latched
+        run.fail(pivot, run.count, tid);
+        if (tid == 0 && it < g.H) {
+            g.lambda_history[hist] = lam;
+            g.member_history[hist] = -2;
+            g.count_history[hist] = 0;
+            g.umax_history[hist] = umax;
         }
         return;
     }
@@ -239,10 +233,10 @@ __global__ __launch_bounds__(256) void trs_pl_step_kernel(const TrsBatch bt, con
     int what = TERMINAL;
     double step = 0.0;
     if (!(rk <= g.collapse_ratio * r0) || !(rk <= DBL_MAX)) {
-        status = TRS_PL_MECHANISM;   // 4. (info stays 0)
+        run.status = TRS_PL_MECHANISM;   // 4. (info stays 0)
     } else if (nrel > 0) {
         if (mode == 1)
-            status = TRS_PL_EVENT_LIMIT;
+            run.status = TRS_PL_EVENT_LIMIT;
         else
             what = RELEASE;
     } else {
@@ -251,9 +245,9 @@ __global__ __launch_bounds__(256) void trs_pl_step_kernel(const TrsBatch bt, con
         if (cap <= dly) {
             what = ADVANCE_CAP;
             step = cap;
-            status = dlL <= dlu ? TRS_PL_LAMBDA_MAX : TRS_PL_DISP_LIMIT;
+            run.status = dlL <= dlu ? TRS_PL_LAMBDA_MAX : TRS_PL_DISP_LIMIT;
         } else if (mode == 1) {
-            status = TRS_PL_EVENT_LIMIT;
+            run.status = TRS_PL_EVENT_LIMIT;
         } else {
             what = ADVANCE_YIELD;
             step = dly;
@@ -299,8 +293,7 @@ __global__ __launch_bounds__(256) void trs_pl_step_kernel(const TrsBatch bt, con
             Ub[d] = un;
             top = fmax(top, fabs(un));
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) top = fmax(top, __shfl_xor(top, off));
+        top = trs_iter::wave_max(top);
         if (lane == 0) {
             t.red[12 + wave] = top;
             t.redi[8 + wave] = nyield;
@@ -311,9 +304,7 @@ __global__ __launch_bounds__(256) void trs_pl_step_kernel(const TrsBatch bt, con
         lam += step;
     }
     if (tid == 0) {
-        const bool still = status == TRS_PL_ACTIVE;
-        g.st[4 * b] = status;
-        g.st[4 * b + 1] = still ? it + 1 : events;
+        const bool still = run.active();
         g.acc[4 * b] = lam;
         g.acc[4 * b + 1] = r0;
         g.acc[4 * b + 2] = umax;
@@ -323,7 +314,7 @@ __global__ __launch_bounds__(256) void trs_pl_step_kernel(const TrsBatch bt, con
             g.count_history[hist] = still ? count : 0;
             g.umax_history[hist] = umax;
         }
-        if (still) atomicAdd(g.active, 1);
+        run.finish(it, g.active);
     }
 }
 

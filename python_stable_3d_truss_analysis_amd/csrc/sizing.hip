@@ -25,9 +25,12 @@
 #include "../../include/trs_sizing.h"
 #include "../../include/trs_solver.h"
 #include "trs_common.h"
+#include "trs_iterate.h"
 #include "trs_lds.h"
 
 namespace {
+
+using Run = trs_iter::Run<TRS_SZ_ACTIVE, TRS_SZ_NOT_PD>;
 
 // LDS tables of the step kernel
 struct StepTables {
@@ -64,18 +67,16 @@ __host__ __device__ inline StepTables step_layout(Arena& a, int nJ_max, int nM_m
 size_t step_lds(int nJ_max, int nM_max) { return trs_lds::count([&](auto& a) { step_layout(a, nJ_max, nM_max); }); }
 
 __device__ __forceinline__ double block_max(double v, double* slot, const int tid) {   // slot [4], 256 threads
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+    v = trs_iter::wave_max(v);
     __syncthreads();   // (the previous readers of slot are done)
     if ((tid & 63) == 0) slot[tid >> 6] = v;
     __syncthreads();
     return fmax(fmax(slot[0], slot[1]), fmax(slot[2], slot[3]));
 }
 
-// the butterfly lane ^ 32, ^ 16, ... ^ 1, then the four waves in wave order
+// the wave butterfly, then the four waves in wave order
 __device__ __forceinline__ double block_sum(double v, double* slot, const int tid) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    v = trs_iter::wave_sum(v);
     __syncthreads();
     if ((tid & 63) == 0) slot[tid >> 6] = v;
     __syncthreads();
@@ -87,9 +88,7 @@ struct StepArgs {
     const int* info;          // [B]
     double allow_tension, allow_compression, allow_displace, euler_kappa, relax, tol;
     const double* allow;      // [B][3] or null: the three allowables per truss
-    const double* a_min;      // [B][nM_max] or null
-    const double* a_max;
-    double a_min_all, a_max_all;
+    trs_iter::AreaBounds bounds;
     int L, it, mode, H;
     double* A;                // [B][nM_max]
     double* prev;             // [B][nM_max]
@@ -108,14 +107,10 @@ __global__ __launch_bounds__(256) void trs_sz_step_kernel(const TrsBatch bt, con
     const int b = blockIdx.x, tid = threadIdx.x;
     const int nM_max = bt.nM_max, ld_f = bt.ld_f;
     const int mode = g.mode, it = g.it, L = g.L;
-    // (every thread reads the status words here; thread 0 writes them behind the barriers below)
-    int status = g.st[4 * b], its = g.st[4 * b + 1];
-    if (it == 0 && mode != 2) {   // the run begins
-        status = TRS_SZ_ACTIVE;
-        its = 0;
-    }
-    const bool report = mode == 2 && (status == TRS_SZ_CONVERGED || status == TRS_SZ_ITER_LIMIT);
-    if (status != TRS_SZ_ACTIVE && !report) return;   // (uniform over the work-group) frozen: nothing is touched
+    Run run(g.st + 4 * b, it == 0 && mode != 2);
+    // mode 2, this analysis's own: the snapped design of a truss that ended with status 0 or 1 is reported
+    const bool report = mode == 2 && (run.status == TRS_SZ_CONVERGED || run.status == TRS_SZ_ITER_LIMIT);
+    if (!run.active() && !report) return;   // (uniform over the work-group) frozen: nothing is touched
     const TrussView tr = bt.truss(b);
     const int members = tr.members, joints = tr.joints, ndof_max = tr.ndof_max;
     const size_t mbase = tr.mbase;
@@ -136,32 +131,18 @@ __global__ __launch_bounds__(256) void trs_sz_step_kernel(const TrsBatch bt, con
                 Ab[m] = g.prev[mbase + m];
             }
         }
-        __syncthreads();   // (every thread has read the status words)
-        if (tid == 0) {
-            g.st[4 * b] = TRS_SZ_NOT_PD;
-            g.st[4 * b + 1] = its > 0 ? its - 1 : 0;
-            g.st[4 * b + 2] = pivot;
-            if (it == 0) {
-                g.weight[b] = 0.0;
-                g.disp_ratio[b] = 0.0;
-            }
+        run.fail(pivot, run.one_back(), tid);
+        if (tid == 0 && it == 0) {
+            g.weight[b] = 0.0;
+            g.disp_ratio[b] = 0.0;
         }
         return;
     }
     trs_lds::Carve lds(sh);
     const StepTables t = step_layout(lds, bt.nJ_max, nM_max);
-    const double* Fb = g.F + (size_t)b * L * ld_f;
-    // (thread d % 256 forms and reads row[d]: no barrier between the table and the staging)
-    for (int d = tid; d < ndof_max; d += 256) t.row[d] = tr.row_of(d);
-    auto stage = [&](int l) {   // case l into buffer l & 1: held DOFs and the padding read 0
-        double* u = t.u + (size_t)(l & 1) * ndof_max;
-        const double* f = Fb + (size_t)l * ld_f;
-        for (int d = tid; d < ndof_max; d += 256) {
-            const int r = t.row[d];
-            u[d] = r >= 0 ? f[r] : 0.0;
-        }
-    };
-    stage(0);
+    const trs_iter::CaseStage cases = {t.u, t.row, g.F + (size_t)b * L * ld_f, ndof_max, ld_f};
+    cases.form_rows(tr, tid);
+    cases.stage(0, tid);
     // ---- the member geometry, once; the weight of the design ----
     const double kappa = g.euler_kappa;
     constexpr double PI = 3.14159265358979323846;
@@ -187,7 +168,7 @@ __global__ __launch_bounds__(256) void trs_sz_step_kernel(const TrsBatch bt, con
     const double ad = g.allow != nullptr ? g.allow[3 * b + 2] : g.allow_displace;
     double umax = 0.0;
     for (int l = 0; l < L; ++l) {
-        const double* u = t.u + (size_t)(l & 1) * ndof_max;
+        const double* u = cases.buffer(l);
         for (int m = tid; m < members; m += 256) {
             const int2 c = t.ends[m];
             const double* u0 = u + 3 * c.x;
@@ -213,7 +194,7 @@ __global__ __launch_bounds__(256) void trs_sz_step_kernel(const TrsBatch bt, con
             const double x = u[3 * j], y = u[3 * j + 1], z = u[3 * j + 2];
             umax = fmax(umax, sqrt(x * x + y * y + z * z));
         }
-        if (l + 1 < L) stage(l + 1);   // (the other buffer: its readers passed the barrier of case l - 1)
+        if (l + 1 < L) cases.stage(l + 1, tid);   // (the other buffer: its readers passed the barrier of case l - 1)
         __syncthreads();
     }
     umax = block_max(umax, t.red, tid);
@@ -229,9 +210,8 @@ __global__ __launch_bounds__(256) void trs_sz_step_kernel(const TrsBatch bt, con
             util = t.req[m] / area;
             gov = d > util ? -1 : t.gov[m];
             if (!report) {
-                const double lo = g.a_min != nullptr ? g.a_min[mbase + m] : g.a_min_all;
-                const double hi = g.a_max != nullptr ? g.a_max[mbase + m] : g.a_max_all;
                 const double r = fmax(util, d);
+                const double lo = g.bounds.lo(mbase + m), hi = g.bounds.hi(mbase + m);
                 const double next = fmin(fmax(area * (keep + relax * r), lo), hi);
                 change = fmax(change, fabs(next - area) / area);
                 t.req[m] = next;
@@ -251,11 +231,10 @@ __global__ __launch_bounds__(256) void trs_sz_step_kernel(const TrsBatch bt, con
     }
     change = block_max(change, t.red + 4, tid);
     if (change <= g.tol)
-        status = TRS_SZ_CONVERGED;
+        run.status = TRS_SZ_CONVERGED;
     else if (mode == 1)
-        status = TRS_SZ_ITER_LIMIT;
-    const bool still = status == TRS_SZ_ACTIVE;
-    if (still) {
+        run.status = TRS_SZ_ITER_LIMIT;
+    if (run.active()) {
         for (int m = tid; m < members; m += 256) {   // (the thread that owns member m wrote t.req[m])
             g.prev[mbase + m] = Ab[m];
             Ab[m] = t.req[m];
@@ -265,9 +244,7 @@ __global__ __launch_bounds__(256) void trs_sz_step_kernel(const TrsBatch bt, con
         g.weight[b] = weight;
         g.disp_ratio[b] = d;
         if (it < g.H) g.history[(size_t)b * g.H + it] = weight;
-        g.st[4 * b] = status;
-        g.st[4 * b + 1] = still ? it + 1 : its;
-        if (still) atomicAdd(g.active, 1);
+        run.finish(it, g.active);
     }
 }
 
@@ -324,8 +301,8 @@ int trs_sz_step(int B, int L, int nJ_max, int nM_max, const double* xyz, const i
     if (!allow && (!(allow_tension > 0.0) || !(allow_compression > 0.0) || !(allow_displace >= 0.0)))
         return (int)hipErrorInvalidValue;
     if (!(euler_kappa >= 0.0) || !(relax > 0.0) || !(relax <= 1.0) || !(tol >= 0.0)) return (int)hipErrorInvalidValue;
-    if (!a_min && !(a_min_all > 0.0)) return (int)hipErrorInvalidValue;
-    if (!a_min && !a_max && !(a_max_all >= a_min_all)) return (int)hipErrorInvalidValue;
+    const trs_iter::AreaBounds bounds = {a_min, a_max, a_min_all, a_max_all};
+    if (!bounds.valid()) return (int)hipErrorInvalidValue;
     if (B == 0) return 0;
     if (!xyz || !conn || !E || !A || !rho || !free_index || !F || !info || !prev || !st || !active || !areas || !weight ||
         !utilisation || !governing || !disp_ratio || (H > 0 && !weight_history))
@@ -333,10 +310,9 @@ int trs_sz_step(int B, int L, int nJ_max, int nM_max, const double* xyz, const i
     if (!trs_sz_fits(nJ_max, nM_max)) return (int)hipErrorInvalidValue;
     const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_general(conn, E, A, rho), free_index, n_free, nJ, nM,
                                   nullptr, ld_f);
-    const StepArgs g = {F, info, allow_tension, allow_compression, allow_displace, euler_kappa, relax, tol, allow, a_min,
-                        a_max,
-                        a_min_all, a_max_all, L, it, mode, H, A, prev, st, active, areas, weight, utilisation,
-                        governing, disp_ratio, weight_history};
+    const StepArgs g = {F, info, allow_tension, allow_compression, allow_displace, euler_kappa, relax, tol, allow,
+                        bounds, L, it, mode, H, A, prev, st, active, areas, weight, utilisation, governing, disp_ratio,
+                        weight_history};
     trs_lds::raise_lds_once<trs_sz_step_kernel>();
     hipLaunchKernelGGL(trs_sz_step_kernel, dim3(B), dim3(256), step_lds(nJ_max, nM_max), (hipStream_t)stream, bt, g);
     return (int)hipGetLastError();

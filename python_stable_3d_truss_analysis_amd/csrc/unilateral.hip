@@ -22,9 +22,12 @@
 #include "../../include/trs_unilateral.h"
 #include "../../include/trs_solver.h"
 #include "trs_common.h"
+#include "trs_iterate.h"
 #include "trs_lds.h"
 
 namespace {
+
+using Run = trs_iter::Run<TRS_UN_ACTIVE, TRS_UN_NOT_PD>;
 
 // LDS tables of the step kernel
 struct StepTables {
@@ -66,16 +69,12 @@ __global__ __launch_bounds__(256) void trs_un_step_kernel(const TrsBatch bt, con
     extern __shared__ double sh[];   // (no static LDS beside it: the dynamic ceiling is the whole of a CU's)
     const int b = blockIdx.x, tid = threadIdx.x;
     const int mode = g.mode, it = g.it;
-    // (every thread reads the status words here; thread 0 writes them behind the barriers below)
-    int status = g.st[4 * b], its = g.st[4 * b + 1];
     const int pivot = g.info[b];
     const bool begin = it == 0 && mode != 2;
-    if (begin) {   // the run begins
-        status = TRS_UN_ACTIVE;
-        its = 0;
-    }
-    const bool report = mode == 2 && status != TRS_UN_ACTIVE;
-    if (status != TRS_UN_ACTIVE && !report) return;   // (uniform over the work-group) frozen: nothing is touched
+    Run run(g.st + 4 * b, begin);
+    // mode 2, this analysis's own: the violations of the state a truss ended with, whatever its status
+    const bool report = mode == 2 && !run.active();
+    if (!run.active() && !report) return;   // (uniform over the work-group) frozen: nothing is touched
     if (report && pivot != 0) return;                 // the state it holds could not be analysed: nothing changes
     const TrussView tr = bt.truss(b);
     const int members = tr.members;
@@ -100,13 +99,8 @@ __global__ __launch_bounds__(256) void trs_un_step_kernel(const TrsBatch bt, con
             state[m] = (signed char)s;
             Ab[m] = s ? An[m] : slack * An[m];
         }
-        __syncthreads();   // (every thread has read the status words)
-        if (tid == 0) {
-            g.st[4 * b] = TRS_UN_NOT_PD;
-            g.st[4 * b + 1] = its > 0 ? its - 1 : 0;
-            g.st[4 * b + 2] = pivot;
-            if (begin) g.violations[b] = 0;
-        }
+        run.fail(pivot, run.one_back(), tid);
+        if (tid == 0 && begin) g.violations[b] = 0;
         return;
     }
     trs_lds::Carve lds(sh);
@@ -150,11 +144,10 @@ __global__ __launch_bounds__(256) void trs_un_step_kernel(const TrsBatch bt, con
         return;
     }
     if (changed == 0)
-        status = TRS_UN_CONVERGED;
+        run.status = TRS_UN_CONVERGED;
     else if (mode == 1)
-        status = TRS_UN_ITER_LIMIT;
-    const bool still = status == TRS_UN_ACTIVE;
-    if (still) {
+        run.status = TRS_UN_ITER_LIMIT;
+    if (run.active()) {
         for (int m = tid; m < members; m += 256) {   // (the thread that owns member m wrote t.flag[m])
             const int fl = t.flag[m];
             g.prev_state[mbase + m] = (signed char)(fl >> 1);
@@ -165,9 +158,7 @@ __global__ __launch_bounds__(256) void trs_un_step_kernel(const TrsBatch bt, con
     if (tid == 0) {
         g.violations[b] = changed;
         if (it < g.H) g.history[(size_t)b * g.H + it] = changed;
-        g.st[4 * b] = status;
-        g.st[4 * b + 1] = still ? it + 1 : its;
-        if (still) atomicAdd(g.active, 1);
+        run.finish(it, g.active);
     }
 }
 

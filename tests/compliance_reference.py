@@ -192,6 +192,32 @@ def generated(nx=70, seed=5):
     return {"joint": joints, "force": forces, "member": members}
 
 
+GENERATED, WIDE = "generated", "wide"
+
+
+def fixture(name):
+    """The truss `name`: a fixture of tests/golden/data, or GENERATED / WIDE."""
+    from tests.helpers import load_json
+    return generated() if name == GENERATED else generated(WIDE_NX) if name == WIDE else load_json(name)
+
+
+def batch_arguments(names, which):
+    """(PackedBatch, keyword arguments of `solve_min_compliance` as host arrays) for the trusses `names`, each with its own
+    configuration `which`: the area bounds one row per truss, the target None."""
+    from python_stable_3d_truss_analysis_amd import batch
+    datas = [fixture(n) for n in names]
+    packed = batch.pack_json(datas)
+    B, nJ, nM = packed.B, packed.nJ_max, packed.nM_max
+    kw = {"loads": np.zeros([B, 2, nJ, 3]), "alpha": CONFIGS[which], "area_min": np.ones([B, nM]),
+          "area_max": np.ones([B, nM])}
+    for b, data in enumerate(datas):
+        one = config(data, which)
+        dim = one["loads"].shape[2]
+        kw["loads"][b, :, :one["loads"].shape[1], :dim] = one["loads"]
+        kw["area_min"][b], kw["area_max"][b] = one["area_min"], one["area_max"]
+    return packed, kw
+
+
 def floor(data, which, run, solve=None):
     """(relative difference of the float64 and the longdouble run, the float64 run, the longdouble run)."""
     kw = config(data, which)

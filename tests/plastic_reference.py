@@ -336,6 +336,28 @@ def run_inputs(name):
     return rows
 
 
+_batches = {}
+
+
+def batch_inputs(name):
+    """The trusses of RUNS[name] as ONE batch, for the GPU tests: (packed, host arrays cap_tension, cap_compression
+    [B, nM_max], loads [B, nJ_max, 3], the scalars, rows).  Made once per run."""
+    if name not in _batches:
+        from python_stable_3d_truss_analysis_amd import batch
+        rows = run_inputs(name)
+        packed = batch.pack_json([row[0] for row in rows])
+        B, nJ, nM = packed.B, packed.nJ_max, packed.nM_max
+        ct, cc, loads = np.ones([B, nM]), np.ones([B, nM]), np.zeros([B, nJ, 3])
+        for b, (data, load, kw) in enumerate(rows):
+            ct[b, :len(kw["cap_tension"])] = kw["cap_tension"]
+            cc[b, :len(kw["cap_compression"])] = kw["cap_compression"]
+            loads[b, :load.shape[0], :load.shape[1]] = load
+        scalars = {k: rows[0][2][k] for k in ("hardening", "lambda_max", "disp_limit", "max_events")}
+        assert all(row[2][k] == v for row in rows for k, v in scalars.items())       # (one set for the whole batch)
+        _batches[name] = (packed, ct, cc, loads, scalars, rows)
+    return _batches[name]
+
+
 def three_bars(C=100.0, P=1.0):
     """Three bars from a ceiling to one loaded joint, at -45, 0 and +45 degrees from the vertical, equal A and E, capacity
     C: the middle bar yields at lambda P = (1 + 1 / sqrt 2) C, both side bars at (1 + sqrt 2) C.  Returns (data, caps)."""

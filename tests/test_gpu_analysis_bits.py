@@ -1,6 +1,6 @@
 """The resident-factor analyses (`solve_load_cases`, `solve_effect_cases`, `solve_gradients`, `solve_modes`,
 `solve_buckling`, `solve_transient`, `solve_nonlinear`, `solve_mode_gradients`, `solve_response_spectrum`, `solve_harmonic`,
-`solve_sizing` and the three on the columns
+`solve_sizing`, `solve_min_compliance`, `solve_unilateral`, `solve_plastic` and the three on the columns
 inv(K_ff) b_e: `solve_member_loss`, `solve_member_sets`, `solve_influence`) give the SAME BITS as the
 build that recorded `tests/golden/analysis_bits.json`: SHA-256 digests of every field (that is not None) of the result
 dataclasses, for both member forms and with and without a joint order.  The kernels use no floating-point
@@ -30,7 +30,17 @@ L, P = 17, 3   # two case groups of the substitution (16 + 1); three modes
 CONFIGS = {"general": dict(table=False, reorder=False), "general-profile": dict(table=False, reorder="profile"),
            "table": dict(table=True, reorder=False), "table-profile": dict(table=True, reorder="profile")}
 ANALYSES = ("load_cases", "effect_cases", "gradients", "modes", "buckling", "member_loss", "member_sets", "influence",
-            "transient", "nonlinear", "mode_gradients", "response_spectrum", "harmonic", "sizing")
+            "transient", "nonlinear", "mode_gradients", "response_spectrum", "harmonic", "sizing", "min_compliance",
+            "unilateral", "plastic")
+# the three iterated analyses beside the sizing run on batches of their own, whose yardstick answers the CPU suites hold:
+# every status and count below is an integer the yardstick decides with a margin (tests/test_unilateral.py,
+# tests/test_plastic.py) or that tests/golden/compliance_tol.json records (tests/test_compliance.py forms it again), and
+# no truss ends with status 2 (which would only hash the fallback).  Each has a ragged batch bar-6 .. bar-120 and bar-942
+# alone: unilateral the runs "slack" and "big" of tests/unilateral_reference.py (slack factor 1e-3), plastic the runs
+# "hardening" and "big" of tests/plastic_reference.py, compliance the configuration "weighted" resized to tol 1e-4 within
+# 60 iterations (compliance_reference.FULL).
+OWN_BATCH = ("min_compliance", "unilateral", "plastic")
+UN_RUNS, PL_RUNS = ("slack", "big"), ("hardening", "big")
 # the transient response: two excitations (the first two load cases as patterns), five Newmark steps, stiffness
 # damping (so the end lists of the members are built), two monitored joints and two monitored members (first and last)
 L_DYN, STEPS, DT, DAMP_STIFF = 2, 5, 1e-3, 1e-4
@@ -135,6 +145,41 @@ def sizing_arguments(packed, x):
                 check_every=2, catalog=np.geomspace(0.1 * lo.min(), 30.0 * hi.max(), SZ_CATALOG))
 
 
+_yardstick = {}
+
+
+def own_batch_runs(analysis, table, reorder):
+    """{name: (result dataclass, [(status, count)] of the yardstick per truss)} of an analysis of OWN_BATCH, through its
+    `solve_*` function: the ragged batch and bar-942 alone.  The count is `iterations`, for plastic `events`."""
+    from python_stable_3d_truss_analysis_amd import batch
+    from tests import compliance_reference as cref, plastic_reference as pref, unilateral_reference as uref
+    form = lambda packed: packed.table() if table else packed
+    runs = {}
+    if analysis == "unilateral":
+        for name in UN_RUNS:
+            packed, kind, loads, pre, slack, _ = uref.batch_inputs(name)
+            res = batch.solve_unilateral(form(packed), kind, loads[:, None], None if pre is None else pre[:, None],
+                                         slack_factor=slack, max_iters=uref.MAX_ITERS, reorder=reorder)
+            runs[name] = (res, [row[:2] for row in uref.TABLE[name]])
+    elif analysis == "plastic":
+        for name in PL_RUNS:
+            packed, ct, cc, loads, scalars, _ = pref.batch_inputs(name)
+            res = batch.solve_plastic(form(packed), ct, cc, loads[:, None], reorder=reorder, **scalars)
+            runs[name] = (res, [row[:2] for row in pref.TABLE[name]])
+    else:
+        with open(os.path.join(H.GOLDEN, "compliance_tol.json")) as fh:
+            entry = json.load(fh)["full"]["configs"]["weighted"]
+        if "big" not in _yardstick:      # (not in the record: the yardstick itself, once - LAPACK for its 696 unknowns)
+            data = H.load_json(cref.BIG)
+            ref = cref.minimise(data, solve=np.linalg.solve, **cref.config(data, "weighted"), **cref.FULL)
+            _yardstick["big"] = [(ref["status"], ref["iterations"])]
+        want = {"batch": list(zip(entry["status"], entry["iterations"])), "big": _yardstick["big"]}
+        for name, names in (("batch", cref.BATCH), ("big", (cref.BIG,))):
+            packed, kw = cref.batch_arguments(names, "weighted")
+            runs[name] = (batch.solve_min_compliance(form(packed), reorder=reorder, **kw, **cref.FULL), want[name])
+    return runs
+
+
 def column_calls(analysis, packed, x):
     """{name: (function name, arguments, keywords)} of a column analysis: "full" on the whole batch with chunk 48 and
     no result per member pair, "small" on the trusses before bar-942 with the default chunk and every optional result."""
@@ -210,6 +255,8 @@ def run(analysis, packed, x, reorder):
                                              joint_mass=x["joint_mass"], reorder=reorder, **HR_DAMPING)}
     if analysis == "sizing":
         return {"sizing": batch.solve_sizing(packed, reorder=reorder, **sizing_arguments(packed, x))}
+    if analysis in OWN_BATCH:
+        return {name: res for name, (res, _) in own_batch_runs(analysis, packed.is_table, reorder).items()}
     return {"modes": batch.solve_modes(packed, p=P, joint_mass=x["joint_mass"], reorder=reorder)}
 
 
@@ -317,7 +364,16 @@ def batches():
 def test_same_bits_as_recorded(recorded, batches, config, analysis):
     kw = CONFIGS[config]
     packed, x = batches(kw["table"])
-    results = run(analysis, packed, x, kw["reorder"])
+    if analysis in OWN_BATCH:
+        runs = own_batch_runs(analysis, kw["table"], kw["reorder"])
+        results = {name: res for name, (res, _) in runs.items()}
+        for name, (res, want) in runs.items():   # (the yardstick's, truss by truss; its status is never 2)
+            count = res.events if analysis == "plastic" else res.iterations
+            got = list(zip(res.status.reshape(-1).tolist(), count.reshape(-1).tolist()))
+            print(f"{config} / {analysis} / {name}: status, count {got}, the yardstick's {want}")
+            assert got == [tuple(w) for w in want] and 2 not in res.status, (name, got, want)
+    else:
+        results = run(analysis, packed, x, kw["reorder"])
     assert all(not res.info.any() for res in results.values())
     if analysis == "buckling":   # (else the batch would never shift, or never find a factor)
         from python_stable_3d_truss_analysis_amd import batch

@@ -22,13 +22,12 @@ pytestmark = pytest.mark.gpu
 FLOATS = ("areas", "measure", "compliance", "objective", "objective_history", "sensitivity", "multiplier")
 KEYS = FLOATS + ("iterations", "status")
 DEPTH = {"tol": 0.0, "max_iters": cref.DEPTH}
-GENERATED, WIDE = "generated", "wide"
+GENERATED, WIDE = cref.GENERATED, cref.WIDE
 
 _cache = {}
 
 
-def _data(name):
-    return cref.generated() if name == GENERATED else cref.generated(cref.WIDE_NX) if name == WIDE else load_json(name)
+_data, _arguments = cref.fixture, cref.batch_arguments
 
 
 def _solver(name):
@@ -52,23 +51,6 @@ def _record():
 
 def _floor(part, which):
     return 100.0 * _record()[part]["configs"][which]["relative_difference"]
-
-
-def _arguments(names, which):
-    """(PackedBatch, keyword arguments of `solve_min_compliance` as host arrays) for the trusses `names`, each with its own
-    configuration `which`: the area bounds one row per truss, the target None."""
-    from python_stable_3d_truss_analysis_amd import batch
-    datas = [_data(n) for n in names]
-    packed = batch.pack_json(datas)
-    B, nJ, nM = packed.B, packed.nJ_max, packed.nM_max
-    kw = {"loads": np.zeros([B, 2, nJ, 3]), "alpha": cref.CONFIGS[which], "area_min": np.ones([B, nM]),
-          "area_max": np.ones([B, nM])}
-    for b, data in enumerate(datas):
-        one = cref.config(data, which)
-        dim = one["loads"].shape[2]
-        kw["loads"][b, :, :one["loads"].shape[1], :dim] = one["loads"]
-        kw["area_min"][b], kw["area_max"][b] = one["area_min"], one["area_max"]
-    return packed, kw
 
 
 def _on_device(torch, dev, kw):

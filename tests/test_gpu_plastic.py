@@ -28,22 +28,7 @@ HISTORIES = ("lambda_history", "umax_history", "member_history", "count_history"
 _cache = {}
 
 
-def _inputs(name):
-    """(packed, host arrays cap_tension, cap_compression [B, nM_max], loads [B, nJ_max, 3], the scalars, rows)."""
-    if name not in _cache:
-        from python_stable_3d_truss_analysis_amd import batch
-        rows = pref.run_inputs(name)
-        packed = batch.pack_json([row[0] for row in rows])
-        B, nJ, nM = packed.B, packed.nJ_max, packed.nM_max
-        ct, cc, loads = np.ones([B, nM]), np.ones([B, nM]), np.zeros([B, nJ, 3])
-        for b, (data, load, kw) in enumerate(rows):
-            ct[b, :len(kw["cap_tension"])] = kw["cap_tension"]
-            cc[b, :len(kw["cap_compression"])] = kw["cap_compression"]
-            loads[b, :load.shape[0], :load.shape[1]] = load
-        scalars = {k: rows[0][2][k] for k in ("hardening", "lambda_max", "disp_limit", "max_events")}
-        assert all(row[2][k] == v for row in rows for k, v in scalars.items())       # (one set for the whole batch)
-        _cache[name] = (packed, ct, cc, loads, scalars, rows)
-    return _cache[name]
+_inputs = pref.batch_inputs
 
 
 def _reference(name, b, **kw):

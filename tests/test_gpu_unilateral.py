@@ -22,26 +22,7 @@ KEYS = ("u", "f_ext", "N", "state", "status", "iterations", "violations", "flips
 _cache = {}
 
 
-def _solver(name):
-    return np.linalg.solve if name == "big" else None      # (696 unknowns: a float64 run may use LAPACK)
-
-
-def _inputs(name):
-    """(packed, host arrays kind [B, nM_max] int8, loads [B, nJ_max, 3], prestrain [B, nM_max] or None, slack, rows)."""
-    if name not in _cache:
-        from python_stable_3d_truss_analysis_amd import batch
-        rows, slack = uref.run_inputs(name, solve=_solver(name))
-        packed = batch.pack_json([row[0] for row in rows])
-        B, nJ, nM = packed.B, packed.nJ_max, packed.nM_max
-        kind, loads, pre = np.zeros([B, nM], dtype=np.int8), np.zeros([B, nJ, 3]), np.zeros([B, nM])
-        for b, (data, load, k, eps0) in enumerate(rows):
-            kind[b, :len(k)] = k
-            loads[b, :load.shape[0], :load.shape[1]] = load
-            if eps0 is not None:
-                pre[b, :len(eps0)] = eps0
-        some = any(row[3] is not None for row in rows)
-        _cache[name] = (packed, kind, loads, pre if some else None, slack, rows)
-    return _cache[name]
+_solver, _inputs = uref.solver, uref.batch_inputs
 
 
 def _reference(name, b, **kw):

@@ -177,6 +177,32 @@ def run_inputs(name, solve=None):
     return rows, slack
 
 
+def solver(name):
+    return np.linalg.solve if name == "big" else None      # (696 unknowns: a float64 run may use LAPACK)
+
+
+_batches = {}
+
+
+def batch_inputs(name):
+    """The trusses of RUNS[name] as ONE batch, for the GPU tests: (packed, host arrays kind [B, nM_max] int8, loads
+    [B, nJ_max, 3], prestrain [B, nM_max] or None, slack, rows).  Made once per run."""
+    if name not in _batches:
+        from python_stable_3d_truss_analysis_amd import batch
+        rows, slack = run_inputs(name, solve=solver(name))
+        packed = batch.pack_json([row[0] for row in rows])
+        B, nJ, nM = packed.B, packed.nJ_max, packed.nM_max
+        kind, loads, pre = np.zeros([B, nM], dtype=np.int8), np.zeros([B, nJ, 3]), np.zeros([B, nM])
+        for b, (data, load, k, eps0) in enumerate(rows):
+            kind[b, :len(k)] = k
+            loads[b, :load.shape[0], :load.shape[1]] = load
+            if eps0 is not None:
+                pre[b, :len(eps0)] = eps0
+        some = any(row[3] is not None for row in rows)
+        _batches[name] = (packed, kind, loads, pre if some else None, slack, rows)
+    return _batches[name]
+
+
 def rule(data, which, case, solve=None):
     """(load [nJ, dim], kind [nM], prestrain [nM] or None) of rule `which` on a fixture's load case: from the linear
     solution of the case the candidates are the members with |e| >= CANDIDATE max |e|, the chosen ones the candidates

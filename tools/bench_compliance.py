@@ -120,7 +120,7 @@ def sz_step():
 def iteration():
     reset()
     ws["levels"] = 0
-    db._sz_analyse(ws)
+    db._analyse_cases(ws)
     db._cm_step(ws, 0, 0)
 
 

@@ -115,7 +115,7 @@ def step():
 
 def analysis():
     reset()
-    db._pl_analyse(ws)
+    db._analyse_cases(ws)
     db._pl_step(ws, 0, 0)
 
 

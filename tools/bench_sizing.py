@@ -109,7 +109,7 @@ def recover():
 
 def iteration():
     reset()
-    db._sz_analyse(ws)
+    db._analyse_cases(ws)
     db._sz_step(ws, 0, 0)
 
 
