@@ -25,6 +25,12 @@
 //                         a rank sort over the wave's LDS slice beyond that and for the rare 64-bit keys -,
 //                         pricing is a wave scan of the free-DOF counts, a neighbour minimum per joint, integer
 //                         atomic minima per row chunk and a suffix minimum with shuffles;
+//   phase B1-B3 instead   where the six sweeps are priced alone and a wave sorts their keys in registers (effort 3
+//                         from 128 free joints on, up to 256 of them: bar-942, the larger cube trusses): B1 the six
+//                         sorts, per wave, each leaving its positions and row chunks in tables of all six sweeps;
+//                         B2 ONE walk over the neighbour lists by the work-group, a free joint per thread, which
+//                         takes the atomic minima of all twelve orders; B3 the twelve suffix minima, three per wave.
+//                         Two work-group barriers, between straight-line phases (DESIGN.md "Barrier audit");
 //   phase C (work-group)  the cheapest (cost, evaluation order) wins; permutation, envelope reach (the launch hint
 //                         of trs_solver.h; kept by the wave that priced the winner) and, if asked, the renumbered
 //                         inputs go to HBM.
@@ -61,7 +67,7 @@ constexpr int RCM_BELOW = 128;              // effort 3: free joints below which
 // LDS carve-up shared by host and device (byte offsets, 16-byte aligned parts)
 struct OrdLds {
     size_t nfr, deg, start, fill, lvl, ppos, queue, nextq, order, ids, frank, bins, adj, adjU, keys,
-        cand, best, newidx, c01, cmin, ctrl, red, total;
+        cand, best, newidx, c01, cmin, w_pos, w_c01, w_cmin, ctrl, red, total;
     int nch_max, n4;
 };
 __host__ __device__ inline size_t ord_up(size_t v) { return (v + 15) / 16 * 16; }
@@ -101,6 +107,18 @@ __host__ __device__ inline OrdLds ord_layout(int nJ_max, int nM_max) {
     l.c01 = take(2 * n * NWAVE);            // u16 [4][n] (first row chunk of a joint << 1) | its rows straddle two chunks
     p = p > lists_end ? p : lists_end;
     l.cmin = take(4 * (size_t)l.nch_max * NWAVE);  // int [4][nch]
+    // The joint-parallel walk (phase B1-B3) prices all six sweeps out of tables of its own, which lie OVER the
+    // per-wave slices above (keys .. cmin: none of them is used on that path, and what phase A staged there is dead):
+    // 49 n + 384 B against the slices' 51 n + 128 B, so only shapes below 128 joints grow, by at most 256 B (they
+    // are a few KB: the registers, not LDS, bound their work-groups per CU).
+    {
+        const size_t slices_end = p;
+        p = shared_at;
+        l.w_pos = take(16 * n);             // u16 [n][8] position of a joint in sweep 0..5 (two unused): ONE read per neighbour
+        l.w_c01 = take(4 * n * 6);          // u32 [6][n] c01 of a position forwards | c01 of the same joint backwards << 16
+        l.w_cmin = take(4 * (size_t)l.nch_max * 12);  // int [12][nch] order 2 i: sweep i forwards, 2 i + 1: backwards
+        p = p > slices_end ? p : slices_end;
+    }
     l.ctrl = take(4 * 32);                  // int [32]   0..2 level counters; per wave from 8: rank, 16: choice, 24: reach
     l.red = take(8 * 64);
     l.total = p;
@@ -157,6 +175,9 @@ struct Tables {
     unsigned long long* keys;   // phase A: u64 [2 n4] level-sort keys; phase B: u32 [4][n4] (see the waves' slices)
     unsigned short *cand, *best, *newidx, *c01;
     int *cmin, *ctrl;
+    uint4* w_pos;               // the joint-parallel walk's tables (ord_layout): they lie over keys .. cmin
+    unsigned* w_c01;
+    int* w_cmin;
     unsigned long long* red;
 };
 
@@ -403,6 +424,15 @@ __device__ void price_order_pair(const Tables& t, int nf, Fwd fwd, unsigned shor
     *reach_rev = rr;
 }
 
+// minimum / maximum of two pairs of 16-bit positions, half by half (v_pk_min_u16 / v_pk_max_u16)
+typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned pk_min(unsigned a, unsigned b) {
+    return __builtin_bit_cast(unsigned, __builtin_elementwise_min(__builtin_bit_cast(us2, a), __builtin_bit_cast(us2, b)));
+}
+__device__ __forceinline__ unsigned pk_max(unsigned a, unsigned b) {
+    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(us2, a), __builtin_bit_cast(us2, b)));
+}
+
 // Registers, not LDS, decided the work-groups per CU of the mid-sized shapes: 94 VGPRs are five waves per SIMD = five
 // work-groups per CU, where bar-942's 26 KB of tables leave room for six.  A bound of six work-groups (80 VGPRs, a
 // handful of spilled values) puts 4096 trusses through 2.67 instead of 3.2 rounds of the chip (EXPERIMENTS R10); eight
@@ -449,6 +479,9 @@ __global__ __launch_bounds__(NT, TRS_ORDER_MIN_WG) void trs_joint_order_kernel(
     t.newidx = reinterpret_cast<unsigned short*>(lds + lay.newidx);
     t.c01 = reinterpret_cast<unsigned short*>(lds + lay.c01);
     t.cmin = reinterpret_cast<int*>(lds + lay.cmin);
+    t.w_pos = reinterpret_cast<uint4*>(lds + lay.w_pos);
+    t.w_c01 = reinterpret_cast<unsigned*>(lds + lay.w_c01);
+    t.w_cmin = reinterpret_cast<int*>(lds + lay.w_cmin);
     t.ctrl = reinterpret_cast<int*>(lds + lay.ctrl);
     t.red = reinterpret_cast<unsigned long long*>(lds + lay.red);
 
@@ -636,6 +669,10 @@ __global__ __launch_bounds__(NT, TRS_ORDER_MIN_WG) void trs_joint_order_kernel(
             nb[2] = max(nb[2], redi[4 * w + 2]);
         }
     }
+    // (the same on every thread: as scalars, they and all that phase B derives from them - field widths, first sweep,
+    // which form prices the sweeps - keep out of the vector registers, which are what this kernel is short of)
+#pragma unroll
+    for (int a = 0; a < 3; ++a) nb[a] = __builtin_amdgcn_readfirstlane(nb[a]);
     __syncthreads();  // the staged coordinates are dead: the adjacency fill takes their space
     for_members([&](int a, int c) {
         if (a == c || t.nfr[a] == 0 || t.nfr[c] == 0) return;
@@ -748,7 +785,154 @@ __global__ __launch_bounds__(NT, TRS_ORDER_MIN_WG) void trs_joint_order_kernel(
             __builtin_amdgcn_wave_barrier();
         }
     };
-    if (nf > 0) {
+    // All six sweeps and nothing beside them, keys a wave sorts in registers (bar-942, every larger cube truss): the
+    // twelve orders are priced in ONE walk over the neighbour lists by the whole work-group, a free joint per thread,
+    // out of tables that hold all six sweeps at once - instead of six walks by one wave each, dealt 2 2 1 1 over the
+    // waves.  Same atomic minima, same reductions, same evaluation ranks and choice codes as the per-wave code below.
+    const bool walk = n_sweep == 6 && !use_rcm && key_bits <= 32 && nf <= WAVESORT_MAX;   // (the same on every thread)
+    auto sweep_ax = [&](int i) { return i == 0 ? first_ax : (i <= first_ax ? i - 1 : i); };
+    if (walk) {
+        // ---- B1 (per wave): the six sorts; a sweep leaves its positions and its row chunks in the tables -----
+        unsigned short* pos16 = reinterpret_cast<unsigned short*>(t.w_pos);
+        auto pack = [](int ds, int v) { return (unsigned)(((ds >> 4) << 1) | ((((ds + v - 1) >> 4) != (ds >> 4)) ? 1 : 0)); };
+        for (int x = lane; x < nf; x += 64) ndof += t.nfr[t.ids[x]];   // free DOFs: every order has the same number
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) ndof += __shfl_xor(ndof, off);
+        const int nch = (ndof + 15) >> 4;
+        for (int o = wave; o < 12; o += NWAVE)
+            for (int q = lane; q < nch; q += 64) t.w_cmin[o * lay.nch_max + q] = q;
+        for (int i = wave; i < 6; i += NWAVE) {
+            const int ax = sweep_ax(i);
+            const int a0 = axis_of(ax, 0), a1 = axis_of(ax, 1), a2 = axis_of(ax, 2);
+            auto key32 = [&](int x) {   // (bin a0, bin a1, bin a2, position in the id list): see the per-wave code
+                const int j = t.ids[x];
+                return ((((unsigned)t.bins[3 * j + a0] << bits_of(a1) | (unsigned)t.bins[3 * j + a1]) << bits_of(a2) |
+                         (unsigned)t.bins[3 * j + a2]) << xbits) | (unsigned)x;
+            };
+            unsigned* c01 = t.w_c01 + (size_t)i * nJ_max;
+            // register r of the sorted keys is positions 64 r .. 64 r + 63: the scan of the free-DOF counts in
+            // position order runs straight over the registers, no candidate array in between
+            auto sort_to_tables = [&](auto rc) {
+                constexpr int R = decltype(rc)::value;
+                unsigned v[R];
+#pragma unroll
+                for (int r = 0; r < R; ++r) v[r] = 64 * r + lane < nf ? key32(64 * r + lane) : 0xffffffffu;
+                int ln = lane;
+                asm volatile("" : "+v"(ln));
+                trs_wavesort::sort<R>(v, ln);
+                int carry = 0;
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const int k = 64 * r + lane;
+                    const int old = k < nf ? (int)t.ids[v[r] & ((1u << xbits) - 1)] : 0;
+                    const int f = k < nf ? (int)t.nfr[old] : 0;
+                    const int incl = wave_incl_scan(f, lane);
+                    const int ds = carry + incl - f;
+                    if (k < nf) {
+                        pos16[8 * old + i] = (unsigned short)k;
+                        // backwards the joint's rows start at n - (rows before it) - (its own rows)
+                        c01[k] = pack(ds, f) | (pack(ndof - ds - f, f) << 16);
+                    }
+                    carry += __shfl(incl, 63);
+                }
+            };
+            if (nf <= 64) sort_to_tables(std::integral_constant<int, 1>{});
+            else if (nf <= 128) sort_to_tables(std::integral_constant<int, 2>{});
+            else if (WAVESORT_MAX == 256 || nf <= 256) sort_to_tables(std::integral_constant<int, 4>{});
+            else if constexpr (WAVESORT_MAX == 512) sort_to_tables(std::integral_constant<int, 8>{});
+        }
+        st.mark(3);
+        __syncthreads();   // the tables of all six sweeps are complete
+        // ---- B2 (work-group): one walk, a free joint per thread ----------------------------------------------
+        // A neighbour's positions in the six sweeps are one 16-byte read; lo / hi = first / last position of the
+        // joint and its neighbours, two sweeps per register.
+        for (int x = tid; x < nf; x += NT) {
+            const int old = t.ids[x];
+            const uint4 self = t.w_pos[old];
+            unsigned lo[3] = {self.x, self.y, self.z}, hi[3] = {self.x, self.y, self.z};
+            const int e1 = t.start[old + 1];
+            for (int e = t.start[old]; e < e1; e += 4) {  // four independent look-ups per step (slack behind the lists);
+                const int w0 = t.adj[e], w1 = e + 1 < e1 ? (int)t.adj[e + 1] : old,   // past the list: the joint itself
+                          w2 = e + 2 < e1 ? (int)t.adj[e + 2] : old, w3 = e + 3 < e1 ? (int)t.adj[e + 3] : old;
+                const uint4 p0 = t.w_pos[w0], p1 = t.w_pos[w1], p2 = t.w_pos[w2], p3 = t.w_pos[w3];
+                lo[0] = pk_min(pk_min(lo[0], p0.x), pk_min(pk_min(p1.x, p2.x), p3.x));
+                lo[1] = pk_min(pk_min(lo[1], p0.y), pk_min(pk_min(p1.y, p2.y), p3.y));
+                lo[2] = pk_min(pk_min(lo[2], p0.z), pk_min(pk_min(p1.z, p2.z), p3.z));
+                hi[0] = pk_max(pk_max(hi[0], p0.x), pk_max(pk_max(p1.x, p2.x), p3.x));
+                hi[1] = pk_max(pk_max(hi[1], p0.y), pk_max(pk_max(p1.y, p2.y), p3.y));
+                hi[2] = pk_max(pk_max(hi[2], p0.z), pk_max(pk_max(p1.z, p2.z), p3.z));
+            }
+            const unsigned own[3] = {self.x, self.y, self.z};
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                const int sh = 16 * (i & 1);
+                const int k = (own[i >> 1] >> sh) & 0xffff, l = (lo[i >> 1] >> sh) & 0xffff, h = (hi[i >> 1] >> sh) & 0xffff;
+                const unsigned* c01 = t.w_c01 + (size_t)i * nJ_max;
+                int* cmin_f = t.w_cmin + (size_t)(2 * i) * lay.nch_max;
+                int* cmin_r = cmin_f + lay.nch_max;
+                const unsigned both = c01[k];
+                const int mine = both & 0xffff, miner = both >> 16;
+                const int col = (c01[l] & 0xffff) >> 1, colr = c01[h] >> 17;
+                atomicMin(&cmin_f[mine >> 1], col);
+                if (mine & 1) atomicMin(&cmin_f[(mine >> 1) + 1], col);   // a joint's own rows may straddle two chunks
+                atomicMin(&cmin_r[miner >> 1], colr);
+                if (miner & 1) atomicMin(&cmin_r[(miner >> 1) + 1], colr);
+            }
+        }
+        st.mark(4);
+        __syncthreads();   // every minimum is in
+        // ---- B3 (per wave): suffix minimum, cost and reach of the twelve orders, NPER at a time per wave ------
+        constexpr int NPER = (12 + NWAVE - 1) / NWAVE;
+        unsigned long long cost[NPER];
+        int run[NPER], reach[NPER];
+#pragma unroll
+        for (int p = 0; p < NPER; ++p) {
+            cost[p] = 0;
+            run[p] = nch;
+            reach[p] = 0;
+        }
+        for (int base = (nch - 1) / 64 * 64; base >= 0; base -= 64) {
+            const int q = base + lane;
+            int v[NPER];
+#pragma unroll
+            for (int p = 0; p < NPER; ++p) {
+                const int o = wave + NWAVE * p;
+                v[p] = q < nch && o < 12 ? t.w_cmin[(size_t)o * lay.nch_max + q] : 0x7fffffff;
+            }
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1)
+#pragma unroll
+                for (int p = 0; p < NPER; ++p) {
+                    const int other = __shfl_down(v[p], off);
+                    if (lane + off < 64) v[p] = min(v[p], other);
+                }
+#pragma unroll
+            for (int p = 0; p < NPER; ++p) {
+                v[p] = min(v[p], run[p]);
+                if (q < nch) {
+                    const unsigned long long w = (unsigned long long)(q - v[p] + 1);
+                    cost[p] += w * (w + 12ull);
+                    reach[p] = max(reach[p], reach_term(q, v[p]));
+                }
+                run[p] = __shfl(v[p], 0);
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < NPER; ++p) {
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) cost[p] += __shfl_xor(cost[p], off);
+            const int o = wave + NWAVE * p, i = o >> 1;
+            if (o < 12 && (cost[p] < my_cost || (cost[p] == my_cost && 2 + o < my_rank))) {   // consider(), without a copy of
+                my_cost = cost[p];                                                            // the order: phase C rebuilds
+                my_rank = 2 + o;               // = 2 + 2 i forwards, 3 + 2 i backwards       // the winner from w_pos
+                my_choice = 2 + 2 * sweep_ax(i) + (o & 1);
+                int rl_max = reach[p];
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) rl_max = max(rl_max, __shfl_xor(rl_max, off));
+                my_reach = __builtin_amdgcn_readfirstlane(rl_max);
+            }
+        }
+    } else if (nf > 0) {
         if (!use_rcm && !sweeps && wave == 0) {  // nothing to choose from: the free joints by ascending id
             auto ord = [&](int k) { return (int)t.ids[k]; };
             const unsigned long long cost = price_order(t, nf, ord, newidx, c01, cmin, lane, &ndof, &rl);
@@ -885,8 +1069,16 @@ __global__ __launch_bounds__(NT, TRS_ORDER_MIN_WG) void trs_joint_order_kernel(
     const unsigned short* wperm = t.best + (size_t)win * nJ_max;
     int* inverse = t.fill;
     int* fullperm = t.ppos;   // [nJ_max] the whole permutation (the sweeps' parent positions are dead)
+    // (the walk keeps no copy of an order: the winner is read back from its sweep's positions, backwards if it won so)
+    const int win_choice = t.ctrl[16 + win], win_ax = (win_choice - 2) >> 1;
+    const int win_sweep = win_ax == first_ax ? 0 : (win_ax < first_ax ? win_ax + 1 : win_ax);   // sweep_ax() inverted
+    const unsigned short* win_pos = reinterpret_cast<const unsigned short*>(t.w_pos) + win_sweep;
     for (int k = tid; k < nJ_max; k += NT) {
-        if (k < nf) {
+        if (k < nf && walk) {
+            const int old = t.ids[k], at = win_pos[8 * old], pos = (win_choice & 1) ? nf - 1 - at : at;
+            fullperm[pos] = old;
+            inverse[old] = pos;
+        } else if (k < nf) {
             const int old = wperm[k];
             fullperm[k] = old;
             inverse[old] = k;
