@@ -43,7 +43,7 @@ __all__ = ["Truss", "Member", "MemberType", "SupportType", "MetapathType", "Task
            "solve_member_loss", "MemberLossResult", "solve_influence", "InfluenceResult",
            "solve_member_sets", "MemberSetResult", "solve_transient", "TransientResult",
            "solve_nonlinear", "NonlinearResult", "solve_buckling", "BucklingResult",
-           "solve_sizing", "SizingResult", "solve_min_compliance", "MinComplianceResult",
+           "solve_sizing", "SizingResult", "solve_min_compliance", "MinComplianceResult", "solve_min_weight", "MinWeightResult",
            "solve_unilateral", "UnilateralResult", "solve_plastic", "PlasticResult"]
 
 
@@ -55,7 +55,7 @@ def __getattr__(name):
                 "InfluenceResult", "solve_member_sets", "MemberSetResult", "solve_transient", "TransientResult",
                 "solve_nonlinear", "NonlinearResult", "solve_buckling", "BucklingResult", "solve_mode_gradients",
                 "ModeGradientResult", "solve_response_spectrum", "SpectrumResult", "solve_harmonic",
-                "HarmonicResult", "solve_sizing", "SizingResult", "solve_min_compliance", "MinComplianceResult",
+                "HarmonicResult", "solve_sizing", "SizingResult", "solve_min_compliance", "MinComplianceResult", "solve_min_weight", "MinWeightResult",
                 "solve_unilateral", "UnilateralResult", "solve_plastic", "PlasticResult"):
         from . import batch
         return getattr(batch, name)

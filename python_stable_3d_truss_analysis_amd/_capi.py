@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h`, `include/trs_influence.h`, `include/trs_sets.h`, `include/trs_dynamics.h`, `include/trs_nonlinear.h`, `include/trs_buckling.h`, `include/trs_modegrad.h`, `include/trs_spectrum.h`, `include/trs_harmonic.h`, `include/trs_sizing.h`, `include/trs_compliance.h`, `include/trs_unilateral.h` and `include/trs_plastic.h` (library: `libtrs_hip.so`, in-tree).
+"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h`, `include/trs_influence.h`, `include/trs_sets.h`, `include/trs_dynamics.h`, `include/trs_nonlinear.h`, `include/trs_buckling.h`, `include/trs_modegrad.h`, `include/trs_spectrum.h`, `include/trs_harmonic.h`, `include/trs_sizing.h`, `include/trs_compliance.h`, `include/trs_minweight.h`, `include/trs_unilateral.h` and `include/trs_plastic.h` (library: `libtrs_hip.so`, in-tree).
 
 There is no fallback: if the library is missing, `load()` raises `HipExtensionError`.
 """
@@ -231,6 +231,16 @@ CM_SIGNATURES = {
                          _D, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
 }
 
+#: every symbol `include/trs_minweight.h` declares (minimum weight under displacement limits: the optimality-criteria
+#: method with one multiplier per limit, iterated on the device; csrc/minweight.hip, the same library).  General member
+#: form only, as the member sizing
+MW_SIGNATURES = {
+    "trs_mw_abi_version": (_I, []),
+    "trs_mw_fits": (_I, [_I, _I, _I]),
+    "trs_mw_step": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _D, _D, _D,
+                         _I, _P, _D, _P, _D, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+}
+
 #: every symbol `include/trs_unilateral.h` declares (tension-only and compression-only members: the active-set iteration
 #: on the device; csrc/unilateral.hip, the same library).  General member form only, as the member sizing
 UN_SIGNATURES = {
@@ -278,6 +288,8 @@ HR_ABI_VERSION = 1
 SZ_ABI_VERSION = 1
 #: must equal TRS_CM_ABI_VERSION of include/trs_compliance.h
 CM_ABI_VERSION = 1
+#: must equal TRS_MW_ABI_VERSION of include/trs_minweight.h
+MW_ABI_VERSION = 1
 #: must equal TRS_UN_ABI_VERSION of include/trs_unilateral.h
 UN_ABI_VERSION = 1
 #: must equal TRS_PL_ABI_VERSION of include/trs_plastic.h
@@ -292,6 +304,10 @@ SZ_MAX_CATALOG = 256
 #: TRS_CM_* of include/trs_compliance.h: the status of a truss in a compliance sizing run, and the measures
 CM_ACTIVE, CM_CONVERGED, CM_ITER_LIMIT, CM_NOT_PD = -1, 0, 1, 2
 CM_MEASURES = {"weight": 0, "volume": 1}
+#: TRS_MW_* of include/trs_minweight.h: the status of a truss in a minimum-weight run, the measures and the most limits
+MW_ACTIVE, MW_CONVERGED, MW_ITER_LIMIT, MW_NOT_PD, MW_INFEASIBLE = -1, 0, 1, 2, 3
+MW_MEASURES = {"weight": 0, "volume": 1}
+MW_MAX_LIMITS = 8
 #: TRS_UN_* of include/trs_unilateral.h: the status of a truss in a run of the active-set iteration
 UN_ACTIVE, UN_CONVERGED, UN_ITER_LIMIT, UN_NOT_PD = -1, 0, 1, 2
 #: TRS_PL_* of include/trs_plastic.h: the status of a truss in a run of the event-to-event analysis
@@ -352,6 +368,7 @@ def load():
             (BK_SIGNATURES, "trs_bk_abi_version", BK_ABI_VERSION), (MG_SIGNATURES, "trs_mg_abi_version", MG_ABI_VERSION),
             (RS_SIGNATURES, "trs_rs_abi_version", RS_ABI_VERSION), (HR_SIGNATURES, "trs_hr_abi_version", HR_ABI_VERSION),
             (SZ_SIGNATURES, "trs_sz_abi_version", SZ_ABI_VERSION), (CM_SIGNATURES, "trs_cm_abi_version", CM_ABI_VERSION),
+            (MW_SIGNATURES, "trs_mw_abi_version", MW_ABI_VERSION),
             (UN_SIGNATURES, "trs_un_abi_version", UN_ABI_VERSION), (PL_SIGNATURES, "trs_pl_abi_version", PL_ABI_VERSION)):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)

@@ -806,6 +806,73 @@ def _check_target(who, target, B):
     return arr
 
 
+def _check_min_weight_scalars(who, measure="weight", move=0.2, tol=1e-4, max_iters=60, sweeps=2, limit_tol=1e-2,
+                              check_every=1):
+    """The scalar arguments of the minimum-weight sizing (ValueError): `measure` "weight" or "volume", `move` in (0, 1],
+    `tol` and `limit_tol` finite and >= 0, `max_iters` an integer >= 0, `sweeps` and `check_every` integers >= 1.
+    Returns them as a dict."""
+    val = {}
+    if not isinstance(measure, str) or measure not in _capi.MW_MEASURES:
+        raise ValueError(f"{who}: measure must be one of {sorted(_capi.MW_MEASURES)}, got {measure!r}")
+    val["measure"] = measure
+    val["move"] = _check_number(who, "move", move, "lie in (0, 1]", above=0)
+    if val["move"] > 1:
+        raise ValueError(f"{who}: move must lie in (0, 1], got {move!r}")
+    val["tol"] = _check_number(who, "tol", tol, "be a finite number >= 0", least=0)
+    val["limit_tol"] = _check_number(who, "limit_tol", limit_tol, "be a finite number >= 0", least=0)
+    val["max_iters"] = _check_integer(who, "max_iters", max_iters, least=0)
+    val["sweeps"] = _check_integer(who, "sweeps", sweeps)
+    val["check_every"] = _check_integer(who, "check_every", check_every)
+    return val
+
+
+def _check_limits(who, limit_case, limit_joint, limit_direction, limit_value, B, nJ_max, L, nJ=None):
+    """The displacement limits of the minimum-weight sizing (ValueError), J of them, 1 <= J <= 8: `limit_case` J integers
+    in [0, L), shared by the batch; `limit_joint` integers [J] or [B, J] in the caller's joint numbering, -1 (switched
+    off) to the truss's last joint (`nJ` [B]: the joint counts, or None: nJ_max for every truss); `limit_direction`
+    [J, 2 or 3] or [B, J, 2 or 3], finite and not zero where the limit is switched on; `limit_value` a number, [J] or
+    [B, J]: > 0, +inf switches a limit off.  Returns {"case": int32 [J], "joint": int32 [B, J], "direction": float64
+    [B, J, 3] of unit length (zero where switched off), "value": float64 [B, J], "given": the directions as given,
+    float64 [B, J, 3] - what `solve_min_weight` hands to its buckets, so that a direction is normalised once}."""
+    def array(x, dtype):
+        try:
+            return np.array(_host_array(x, None))
+        except (TypeError, ValueError):
+            return None
+    case = array(limit_case, None)
+    most = _capi.MW_MAX_LIMITS
+    if case is None or case.ndim != 1 or not 1 <= case.size <= most or case.dtype.kind not in "iu" \
+            or (case < 0).any() or (case >= L).any():
+        raise ValueError(f"{who}: limit_case must hold 1 to {most} integers in [0, L={L}), one per limit, got {limit_case!r}")
+    J = int(case.size)
+    joint = array(limit_joint, None)
+    if joint is None or joint.dtype.kind not in "iu" or joint.shape not in ((J,), (B, J)):
+        raise ValueError(f"{who}: limit_joint must be integers [J={J}] or [B={B}, J={J}]")
+    joint = np.broadcast_to(joint, [B, J]).astype(np.int64)
+    top = np.full([B], nJ_max) if nJ is None else np.asarray(nJ).reshape(B)
+    if (joint < -1).any() or (joint >= top[:, None]).any():
+        raise ValueError(f"{who}: limit_joint must name a joint of its truss, or -1 for a limit that is switched off")
+    value = array(limit_value, None)
+    if value is None or value.dtype.kind not in "iuf" or value.shape not in ((), (J,), (B, J)):
+        raise ValueError(f"{who}: limit_value must be a number, [J={J}] or [B={B}, J={J}]")
+    value = np.broadcast_to(value.astype(np.float64), [B, J]).copy()
+    if np.isnan(value).any() or not (value > 0).all():
+        raise ValueError(f"{who}: limit_value must be positive (+inf switches a limit off)")
+    d = array(limit_direction, None)
+    if d is None or d.dtype.kind not in "iuf" or d.shape[:-1] not in ((J,), (B, J)) or d.shape[-1] not in (2, 3) \
+            or not np.isfinite(d).all():
+        raise ValueError(f"{who}: limit_direction must be finite, [J={J}, 2 or 3] or [B={B}, J={J}, 2 or 3]")
+    d = np.broadcast_to(d.astype(np.float64), [B, J, d.shape[-1]])
+    d = np.concatenate([d, np.zeros([B, J, 3 - d.shape[-1]])], axis=2)
+    on = (joint >= 0) & np.isfinite(value)
+    norm = np.sqrt((d * d).sum(axis=2))
+    if not (norm[on] > 0).all():
+        raise ValueError(f"{who}: limit_direction must not be zero where the limit is switched on")
+    unit = np.where(on[..., None], d / np.where(on, norm, 1.0)[..., None], 0.0)
+    return {"case": case.astype(np.int32), "joint": joint.astype(np.int32), "direction": np.ascontiguousarray(unit),
+            "value": value, "given": np.ascontiguousarray(d)}
+
+
 def _check_mass_args(who, B, nJ_max, joint_mass_shape, mass_scale, joint_mass_min=None):
     """The mass arguments that the transient analysis shares with `modes` (`_check_mode_args`), refused in `who`'s name."""
     try:
@@ -2127,10 +2194,10 @@ class DeviceBatch:
             self.uf.data_ptr(), self.rows, self.info.data_ptr(), it, ws["U"].data_ptr(), ws["st"].data_ptr(),
             self._stream()), "trs_nl_update")
 
-    # -- the iterated analyses - sizing, min_compliance, unilateral, plastic - share one driver and one run protocol
+    # -- the iterated analyses - sizing, min_compliance, min_weight, unilateral, plastic - share one driver and one run protocol
     # (csrc/trs_iterate.h): analyse, one step kernel, one look at one counter ------------------------------
     def _refuse_iterated(self, name, what="load cases"):
-        """What none of the four runs on: the fused small-system path, `options["compact"]` and the table form."""
+        """What none of the five runs on: the fused small-system path, `options["compact"]` and the table form."""
         self._need_slab(name, f"writes no slab that the {what} could be solved against")
         if self.table:
             raise ValueError(f"{name}(): the table member form cannot hold one area per member - use the general form "
@@ -2382,6 +2449,104 @@ class DeviceBatch:
             out["compliance"].data_ptr(), out["objective"].data_ptr(), out["objective_history"].data_ptr(),
             val["max_iters"] + 1, out["sensitivity"].data_ptr(), out["multiplier"].data_ptr(), self._stream()),
             "trs_cm_step")
+
+    # -- minimum weight under displacement limits, iterated on the device (include/trs_minweight.h) ---------------------
+    def min_weight(self, loads=None, *, limit_case, limit_joint, limit_direction, limit_value, measure="weight", move=0.2,
+                   area_min, area_max, tol=1e-4, max_iters=60, sweeps=2, limit_tol=1e-2, check_every=1,
+                   want_sensitivity=False, out=None):
+        """Minimum-weight sizing of the resident batch under displacement limits (include/trs_minweight.h: the
+        optimality-criteria method with one multiplier per limit): the lightest design - the smallest sum w A, w = rho L0
+        (`measure` "weight") or L0 ("volume") - with d_j.u_{l_j}(joint_j) <= `limit_value`_j for each of the J <= 8
+        limits.  `limit_case`: J case numbers, shared by the batch; `limit_joint`: integers [J] or [B, J] in the CALLER's
+        joint numbering (-1 switches a limit off for that truss); `limit_direction`: [J, 3] or [B, J, 3], normalised
+        here; `limit_value`: a number, [J] or [B, J], > 0 (+inf switches a limit off); a two-sided limit is two limits
+        with +-d.  Every design is analysed under the L load cases and the J unit loads of the limits, which are just
+        more columns of the case block; the sensitivities are c_mj = (E / L0) proj_m(v_j) proj_m(u_{l_j}); the
+        multipliers are found per truss by `sweeps` passes of one geometric bisection per limit inside the step kernel;
+        every member goes to sqrt(sum_j mu_j q_mj / (w_m + sum_j mu_j n_mj)), held within `move` (relative) of A_m and
+        within [`area_min`, `area_max`] (scalars or float64 device tensors [B, nM_max]; equal bounds fix a member), until
+        no area moves by more than `tol` (relative) or `max_iters` resizings are done.  `loads`: float64 device tensor
+        [B, L, nJ_max, 3] as `solve_cases` takes them (None: the batch's own loads as one case).  Per iteration five
+        launches: `trs_assemble`, `trs_potrf_batched`, `trs_gather_cases`, `trs_potrs_cases` and `trs_mw_step`.  A truss
+        that has left the run is frozen, as in `min_compliance()`: its results depend neither on the others nor on
+        `check_every` nor on `max_iters` beyond its own count.
+        Returns a dict of device tensors, in the caller's member order: areas [B, nM_max], measure [B], measure_history,
+        worst_history [B, max_iters + 1] (zero beyond the truss's own count), displacement, ratio, multipliers [B, J]
+        (g_j, g_j / limit_value_j - 0 for a limit that is switched off - and mu_j), iterations, status (int32 [B]: 0
+        converged within `limit_tol` of its limits, 1 iteration limit, 2 a design could not be factored, 3 converged on
+        its bounds without meeting a limit) and - with `want_sensitivity` - sensitivity [B, J, nM_max] = c_mj.
+        `self.info` holds 0, or for a truss of status 2 what the factorisation reported, latched.  Afterwards `self.A`
+        holds the returned areas and the slab the factor of the returned design for every truss of status 0, 1 or 3:
+        `solve_cases` may follow without another `factor()`; `generation` is bumped.  A batch on the fused small-system
+        path, `options["compact"]` and the table member form are refused, as in `sizing()`."""
+        t = self.torch
+        who = "min_weight()"
+        self._refuse_iterated("min_weight")
+        # (the unit loads are in the caller's numbering, so the batch's own loads are carried there too)
+        loads = self._check_loads("min_weight", self._own_loads().unsqueeze(1) if loads is None else loads)
+        L = int(loads.shape[1])
+        if L < 1:
+            raise ValueError(f"{who}: loads must hold at least one case")
+        val = _check_min_weight_scalars(who, measure, move, tol, max_iters, sweeps, limit_tol, check_every)
+        lim = _check_limits(who, limit_case, limit_joint, limit_direction, limit_value, self.B, self.nJ_max, L)
+        J = int(lim["case"].size)
+        bounds = self._area_bounds(who, area_min, area_max)
+        H = val["max_iters"] + 1
+        keys = [k for k, *_ in MinWeightResult.FIELDS.values() if k != "sensitivity" or want_sensitivity]
+        out = self._out_tensors("min_weight", _field_shapes(MinWeightResult.FIELDS, self.B, self._sizes(H=H, G=J), keys), out)
+        if self.B == 0:
+            return out
+        self._begin_iterated("min_weight", (lambda nJ, nM: self.lib.trs_mw_fits(nJ, nM, J), "the step kernel (trs_mw_fits)"))
+        ws = self._mw_workspace(val, bounds, loads, lim, out)
+        with t.cuda.device(self.device):
+            self.dofmap()
+            out["measure_history"].zero_()
+            out["worst_history"].zero_()
+            self._iterate(ws, val["check_every"], self._analyse_cases, self._mw_step)
+            self._end_iterated(ws, out)   # (the factor: of the returned design, for every truss of status 0, 1 or 3)
+        return out
+
+    # the stages of `min_weight` (tools/bench_minweight.py times them one by one; the analysis is `_analyse_cases`)
+    def _mw_workspace(self, val, bounds, loads, lim, out):
+        """The state of a `min_weight` run: the design before the last resizing, the multipliers mu [B, J], the status
+        words and the `active` counters, zeroed; the case block of L + J columns and its loads - the real cases, then
+        the unit load d_j at every limit's joint (zero where the limit is switched off), in the caller's numbering; the
+        limits on the device, their joints mapped through the batch's joint order into the device's numbering."""
+        t, dev = self.torch, self.device
+        B, L, J = self.B, int(loads.shape[1]), int(lim["case"].size)
+        joint = t.from_numpy(lim["joint"].astype(np.int64)).to(dev)                 # [B, J], the caller's numbering
+        direction = t.from_numpy(lim["direction"]).to(dev)
+        value = t.from_numpy(lim["value"]).to(dev)
+        on = (joint >= 0) & t.isfinite(value)
+        place = joint.clamp(min=0)
+        unit = t.zeros([B, J, self.nJ_max, 3], dtype=t.float64, device=dev)
+        unit.scatter_(2, place.view(B, J, 1, 1).expand(B, J, 1, 3), (direction * on.unsqueeze(-1)).unsqueeze(2))
+        device_joint = place
+        if self.joint_out is not None:   # joint_out[b, i] = the caller's id of the device's joint i: inverted here
+            inverse = t.empty_like(self.joint_out, dtype=t.int64)
+            inverse.scatter_(1, self.joint_out.long(), t.arange(self.nJ_max, device=dev).expand(B, -1))
+            device_joint = inverse.gather(1, place)
+        device_joint = t.where(on, device_joint, t.full_like(device_joint, -1)).to(t.int32).contiguous()
+        prev = t.zeros([B, max(self.nM_max, 1)], dtype=t.float64, device=dev)
+        return self._run_state(val["max_iters"], L + J, t.cat([loads, unit], dim=1).contiguous(), False, prev=prev,
+                               mu=t.zeros([B, J], dtype=t.float64, device=dev), cases=L, J=J,
+                               limit_case=t.from_numpy(lim["case"]).to(dev), limit_joint=device_joint,
+                               limit_dir=direction.contiguous(), limit_value=value.contiguous(), val=val, bounds=bounds,
+                               out=out)
+
+    def _mw_step(self, ws, it, mode):
+        val, out, (lo, hi) = ws["val"], ws["out"], ws["bounds"]
+        _capi.check(self.lib.trs_mw_step(
+            self.B, ws["cases"], ws["J"], self.nJ_max, self.nM_max, self.xyz.data_ptr(), self.conn.data_ptr(),
+            self.E.data_ptr(), self.A.data_ptr(), self.rho.data_ptr(), self.free_index.data_ptr(), self.n_free.data_ptr(),
+            self.nJ.data_ptr(), self.nM.data_ptr(), ws["F"].data_ptr(), self.rows, self.info.data_ptr(),
+            ws["limit_case"].data_ptr(), ws["limit_joint"].data_ptr(), ws["limit_dir"].data_ptr(),
+            ws["limit_value"].data_ptr(), _capi.MW_MEASURES[val["measure"]], val["move"], val["tol"], val["limit_tol"],
+            val["sweeps"], _ptr(lo[0]), lo[1], _ptr(hi[0]), hi[1], it, mode, ws["prev"].data_ptr(), ws["mu"].data_ptr(),
+            ws["st"].data_ptr(), self._active(ws, it), out["areas"].data_ptr(), out["measure"].data_ptr(),
+            out["measure_history"].data_ptr(), out["worst_history"].data_ptr(), val["max_iters"] + 1,
+            out["displacement"].data_ptr(), out["ratio"].data_ptr(), out["multipliers"].data_ptr(),
+            _ptr(out.get("sensitivity")), self._stream()), "trs_mw_step")
 
     # -- tension-only and compression-only members: the active-set iteration on the device (include/trs_unilateral.h) ----
     def unilateral(self, kind, loads=None, prestrain=None, slack_factor=0.0, max_iters=20, check_every=1, state=None,
@@ -5173,6 +5338,126 @@ def solve_min_compliance(trusses_or_packed, loads=None, alpha=None, target=None,
             measure=val["measure"], eta=val["eta"], move=val["move"], area_min=bound(part, on["area_min"]),
             area_max=bound(part, on["area_max"]), tol=val["tol"], max_iters=val["max_iters"],
             check_every=val["check_every"]))
+    return _finish_result(torch, dev, out, on_device)
+
+
+@dataclass
+class MinWeightResult:
+    """Results of `solve_min_weight`, in the caller's member order, all describing the last design of a truss that could
+    be factored: areas [B, nM_max], measure [B] (sum w A of the returned design), measure_history, worst_history
+    [B, max_iters + 1] (the measure and the largest g_j / limit_value_j of every design the truss analysed, zero beyond
+    its own count), displacement [B, J] (g_j = d_j.u_{l_j}(joint_j)), ratio [B, J] (g_j / limit_value_j; 0 for a limit that
+    is switched off), multipliers [B, J] (of the last dual solve: at the optimum sum_j mu_j c_mj = w_m on every member
+    strictly inside its bounds and move limits, and mu_j = 0 for a limit with slack), sensitivity [B, J, nM_max]
+    (c_mj = -dg_j/dA_m; None unless asked for), iterations [B] (resizings behind the returned design), status (int32 [B]:
+    0 converged within limit_tol of its limits, 1 iteration limit, 2 a design could not be factored - the truss went back
+    to the design before; with iterations 0 its areas are the initial ones and the other results zero -, 3 converged on
+    its bounds without meeting a limit).  info [B]: 0, or what the factorisation reported for the design that ended a
+    truss with status 2."""
+    areas: np.ndarray
+    measure: np.ndarray
+    measure_history: np.ndarray
+    worst_history: np.ndarray
+    displacement: np.ndarray
+    ratio: np.ndarray
+    multipliers: np.ndarray
+    sensitivity: np.ndarray
+    iterations: np.ndarray
+    status: np.ndarray
+    info: np.ndarray
+
+    #: ("G": the number of limits g_j, J of the header)
+    FIELDS = {"areas": ("areas", 0.0, "float64", ("nM",)), "measure": ("measure", 0.0, "float64", ()),
+              "measure_history": ("measure_history", 0.0, "float64", ("H",)),
+              "worst_history": ("worst_history", 0.0, "float64", ("H",)),
+              "displacement": ("displacement", 0.0, "float64", ("G",)), "ratio": ("ratio", 0.0, "float64", ("G",)),
+              "multipliers": ("multipliers", 0.0, "float64", ("G",)),
+              "sensitivity": ("sensitivity", 0.0, "float64", ("G", "nM")),
+              "iterations": ("iterations", 0, "int32", ()), "status": ("status", 0, "int32", ())}
+
+
+def _check_min_weight_args(packed, loads=None, limit_case=None, limit_joint=None, limit_direction=None, limit_value=None,
+                           measure="weight", move=0.2, area_min=None, area_max=None, tol=1e-4, max_iters=60, sweeps=2,
+                           limit_tol=1e-2, check_every=1, want_sensitivity=False, options=None, sections=None,
+                           max_result_bytes=4 << 30):
+    """The argument errors of `solve_min_weight` that need no device (ValueError).  Returns the arguments checked: the
+    dict of `_check_min_weight_scalars` plus "loads" (a float64 host array [B, L, nJ_max, 3], or None for the batch's own
+    loads), "limits" (the dict of `_check_limits`), "want_sensitivity" and "area_min" / "area_max" (each a float, or a
+    float64 host array [B, nM_max])."""
+    who = "solve_min_weight"
+    _refuse_variants(who, "the minimum-weight sizing (it writes the sections)", sections, options)
+    B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
+    host_loads = _check_case_loads(who, loads, B, nJ_max)
+    L = 1 if host_loads is None else host_loads.shape[1]
+    val = _check_min_weight_scalars(who, measure, move, tol, max_iters, sweeps, limit_tol, check_every)
+    if not isinstance(want_sensitivity, (bool, np.bool_)):
+        raise ValueError(f"{who}: want_sensitivity must be True or False, got {want_sensitivity!r}")
+    val["want_sensitivity"] = bool(want_sensitivity)
+    val["loads"] = host_loads
+    if limit_case is None or limit_joint is None or limit_direction is None or limit_value is None:
+        raise ValueError(f"{who}: limit_case, limit_joint, limit_direction and limit_value must be given")
+    val["limits"] = _check_limits(who, limit_case, limit_joint, limit_direction, limit_value, B, nJ_max, L, packed.nJ)
+    J = int(val["limits"]["case"].size)
+    (lo, lo_arr), (hi, hi_arr) = _check_area_bounds(who, area_min, area_max, B, packed.nM, nM_max)
+    val["area_min"], val["area_max"] = (lo if lo_arr is None else lo_arr), (hi if hi_arr is None else hi_arr)
+    live = np.arange(nM_max)[None, :] < np.asarray(packed.nM)[:, None]
+    general = packed.general() if packed.is_table else packed
+    if B and not (np.asarray(general.A)[live] > 0).all():
+        raise ValueError(f"{who}: the initial design must be positive: every member's area > 0")
+    if B and measure == "weight" and not (np.asarray(general.rho)[live] > 0).all():
+        raise ValueError(f"{who}: measure='weight' needs a positive density rho on every member - a member with rho <= 0 "
+                         "weighs nothing; use measure='volume'")
+    nbytes = B * (8 * nM_max * (1 + J * val["want_sensitivity"]) + 16 * (val["max_iters"] + 1) + 24 * J + 24)
+    if nbytes > max_result_bytes:
+        raise ValueError(f"{who}: the results of B={B} trusses take {nbytes} bytes, more than max_result_bytes = "
+                         f"{max_result_bytes}")
+    return val
+
+
+def solve_min_weight(trusses_or_packed, loads=None, limit_case=None, limit_joint=None, limit_direction=None,
+                     limit_value=None, measure="weight", move=0.2, area_min=None, area_max=None, tol=1e-4, max_iters=60,
+                     sweeps=2, limit_tol=1e-2, check_every=1, want_sensitivity=False, device=None, reorder=False,
+                     options=None, on_device=False, sections=None, use_envelope=True, max_slab_bytes=64 << 30,
+                     max_result_bytes=4 << 30):
+    """The lightest design of every truss of a batch whose named joint displacements stay within named limits: the
+    optimality-criteria method with one multiplier per limit (include/trs_minweight.h, `DeviceBatch.min_weight`).  The
+    objective is sum w A with w = rho L0 (`measure` "weight") or L0 ("volume"); limit j means
+    d_j.u_{l_j}(joint_j) <= `limit_value`_j under load case l_j = `limit_case`[j] of `loads` [B, L, nJ_max, dim] (numpy or
+    torch; the caller's joint numbering; dim 2 or 3; None: the batch's own loads as one case); `limit_joint`: integers
+    [J] or [B, J] (-1 switches a limit off for that truss), `limit_direction`: [J, dim] or [B, J, dim] (normalised here),
+    `limit_value`: a number, [J] or [B, J], > 0 (+inf switches a limit off); 1 <= J <= 8; a two-sided limit is two limits
+    with +-d.  `move` in (0, 1] limits the relative change of an area per resizing, `area_min` > 0 and `area_max` >=
+    `area_min`: scalars or [B, nM_max] (equal bounds fix a member); `tol` is the relative area change at which a truss is
+    converged, `limit_tol` how far above its limits a converged truss may lie and still get status 0 (else 3),
+    `max_iters` the number of resizings at most, `sweeps` the passes of the dual solve over the limits, `check_every` how
+    often the host looks whether every truss is done.  What the method is not: there are no stress limits
+    inside the run (size for stress first - `solve_sizing` without a displacement limit - and pass its areas as
+    `area_min`), no linked member groups, no limits on member forces or reactions, and with several limits that compete
+    for the same members the resizing can approach its fixed point slowly or cycle inside its move limits.  Every
+    iteration factors its own design (`_factored_buckets` factors nothing ahead).  A table-form batch is converted with
+    `.general()`.  `measure="weight"` is refused when a member has rho <= 0.  Buckets, `reorder` plans, `options`,
+    `on_device` and `use_envelope` as `solve_load_cases`.  Bad arguments (`_check_min_weight_args`) raise ValueError
+    before any device work.  Returns a `MinWeightResult`."""
+    packed = _as_packed(trusses_or_packed)
+    val = _check_min_weight_args(packed, loads, limit_case, limit_joint, limit_direction, limit_value, measure, move,
+                                 area_min, area_max, tol, max_iters, sweeps, limit_tol, check_every, want_sensitivity,
+                                 options, sections, max_result_bytes)
+    if packed.is_table:
+        packed = packed.general()
+    torch, dev = _require_gpu(device)
+    lim = val["limits"]
+    sizes = {"nM": packed.nM_max, "H": val["max_iters"] + 1, "G": int(lim["case"].size)}
+    out = _new_result(torch, dev, MinWeightResult, packed.B, sizes,
+                      without=() if val["want_sensitivity"] else ("sensitivity",))
+    on, bound = _upload_design_args(torch, dev, val)
+    for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope,
+                                      factor=lambda db, part: None):
+        _put_result(part, out, db.min_weight(
+            part.cut(on["loads"], nJ=2), limit_case=lim["case"], limit_joint=lim["joint"][part.index],
+            limit_direction=lim["given"][part.index], limit_value=lim["value"][part.index], measure=val["measure"],
+            move=val["move"], area_min=bound(part, on["area_min"]), area_max=bound(part, on["area_max"]), tol=val["tol"],
+            max_iters=val["max_iters"], sweeps=val["sweeps"], limit_tol=val["limit_tol"],
+            check_every=val["check_every"], want_sensitivity=val["want_sensitivity"]))
     return _finish_result(torch, dev, out, on_device)
 
 

@@ -1,12 +1,13 @@
-// trs_iterate.h - what the step kernels of the four iterated analyses share (sizing.hip, compliance.hip, unilateral.hip,
-// plastic.hip): each iterates analyse -> step -> one counter on a resident batch, one 256-thread work-group per truss.
+// trs_iterate.h - what the step kernels of the five iterated analyses share (sizing.hip, compliance.hip, minweight.hip,
+// unilateral.hip, plastic.hip): each iterates analyse -> step -> one counter on a resident batch, one 256-thread
+// work-group per truss.
 //   - Run: the run protocol on the status words st [B][4] - status, count, latched info, spare - that DESIGN 3r states:
 //     begin, frozen, fail (the latch), finish (the `active` counter).  The status values are the analysis's own, so they
 //     are template parameters; what differs between the analyses - a report mode 2, the count a failure leaves, what
 //     else `begin` resets - is said at the call, and the type has no flag for it;
 //   - wave_sum, wave_max: the butterfly lane ^ 32, ^ 16, ... ^ 1 - the order every sum of these kernels is promised in;
-//   - CaseStage: the L cases of the case block through LDS, one at a time in two buffers (sizing, compliance);
-//   - AreaBounds: area_min / area_max of those two, each one number or one per member, and their argument rule.
+//   - CaseStage: the L cases of the case block through LDS, one at a time in two buffers (sizing, compliance, minweight);
+//   - AreaBounds: area_min / area_max of those three, each one number or one per member, and their argument rule.
 // Everything is __forceinline__: trs_cm_step sits ten registers under the 128 of its fourth wave per SIMD.
 #pragma once
 #include "trs_view.h"

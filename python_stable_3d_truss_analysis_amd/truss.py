@@ -748,6 +748,62 @@ class Truss:
                 "iterations": int(result.iterations[0]), "status": int(result.status[0]),
                 "objective_history": result.objective_history[0].copy()}
 
+    def MinimizeWeight(self, loadCases=None, limits=None, measure="weight", move=0.2, areaMin=None, areaMax=None, tol=1e-4,
+                       maxIters=60, sweeps=2, limitTol=1e-2, returnSensitivity=False):
+        """The lightest areas of this truss whose named joint displacements stay within named limits: minimum-weight
+        sizing by the optimality-criteria method with one multiplier per limit (`batch.solve_min_weight`), starting from
+        the members' own areas.  `loadCases` is a list of `{jointID: vector}` dicts as `SolveLoadCases` takes them (None:
+        the truss's own forces as one case); `limits` is a list of up to 8 `(case, jointID, direction, value)`: under
+        load case `case` the displacement of joint `jointID` along `direction` (any length but zero) must not exceed
+        `value` > 0 - a two-sided limit is two limits with opposite directions; `measure`: what is minimised, the weight
+        (sum rho L A) or the "volume" (sum L A); `areaMin` > 0, `areaMax` >= `areaMin`: scalars or one value per member;
+        `move`, `tol`, `maxIters`, `sweeps`, `limitTol` as `batch.solve_min_weight`.  Returns a dict of numpy arrays and
+        scalars:
+          "areas" [nM], "measure", "displacement", "ratio" (displacement / value; <= 1 is feasible), "multipliers" [J],
+          "iterations", "status" (0 converged within its limits, 1 iteration limit, 2 a design could not be factored, 3
+          converged on its bounds without meeting a limit), "measure_history", "worst_history" [maxIters + 1] and - with
+          `returnSensitivity` - "sensitivity" [J, nM] (minus the derivative of every limited displacement by every area).
+        The truss's own members, loads and solved state stay as they are.  Raises ValueError for bad arguments (as
+        `batch.solve_min_weight`) and `TrussNotStableError` when the counting test fails."""
+        if not self.isStable:
+            raise TrussNotStableError("The truss is not stable !")
+        from .batch import pack_trusses, solve_min_weight  # late import: keeps the model importable without torch
+        packed = pack_trusses([self])
+        nM = len(self._bars)
+        loads = None
+        if loadCases is not None:
+            loadCases = list(loadCases)
+            if not loadCases:
+                raise ValueError("MinimizeWeight: loadCases must hold at least one load case")
+            loads = self._case_loads(loadCases, packed.nJ_max)
+        try:
+            limits = [tuple(one) for one in limits]
+            rows = [(case, jointID, [float(x) for x in direction], value) for case, jointID, direction, value in limits]
+        except (TypeError, ValueError):
+            raise ValueError("MinimizeWeight: limits must be a list of (case, jointID, direction, value)") from None
+        if not rows or any(len(d) != self._dim for _, _, d, _ in rows):
+            raise ValueError(f"MinimizeWeight: limits must hold at least one limit, every direction with {self._dim} "
+                             "components")
+
+        def bound(x):
+            if x is None or np.ndim(x) == 0:
+                return x
+            row = np.zeros([1, packed.nM_max])
+            row[0, :nM] = np.asarray(x, dtype=np.float64).reshape(nM)
+            return row
+        result = solve_min_weight(packed, loads, limit_case=[r[0] for r in rows], limit_joint=[r[1] for r in rows],
+                                  limit_direction=[r[2] for r in rows], limit_value=[r[3] for r in rows], measure=measure,
+                                  move=move, area_min=bound(areaMin), area_max=bound(areaMax), tol=tol, max_iters=maxIters,
+                                  sweeps=sweeps, limit_tol=limitTol, want_sensitivity=returnSensitivity)
+        out = {"areas": result.areas[0, :nM].copy(), "measure": float(result.measure[0]),
+               "displacement": result.displacement[0].copy(), "ratio": result.ratio[0].copy(),
+               "multipliers": result.multipliers[0].copy(), "iterations": int(result.iterations[0]),
+               "status": int(result.status[0]), "measure_history": result.measure_history[0].copy(),
+               "worst_history": result.worst_history[0].copy()}
+        if returnSensitivity:
+            out["sensitivity"] = result.sensitivity[0, :, :nM].copy()
+        return out
+
     def SolveUnilateral(self, kinds, cases=None, slackFactor=0.0, maxIters=20):
         """Solve this truss with members that carry tension only or compression only - cables, tie rods, counter-bracing,
         struts that bear against a seat - by the active-set iteration (`batch.solve_unilateral`): every case is analysed,
