@@ -94,6 +94,7 @@
  * bytes.)
  *
  * General member form only, for the reason trs_sizing.h gives: there is no `_tab` twin; convert a table-form batch first.
+ * Stress limits in the same run: trs_minweight_stress.h (trs_mw_step_stress, a second instantiation of the same kernel).
  */
 #ifndef TRS_MINWEIGHT_H
 #define TRS_MINWEIGHT_H

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h`, `include/trs_influence.h`, `include/trs_sets.h`, `include/trs_dynamics.h`, `include/trs_nonlinear.h`, `include/trs_buckling.h`, `include/trs_modegrad.h`, `include/trs_spectrum.h`, `include/trs_harmonic.h`, `include/trs_sizing.h`, `include/trs_compliance.h`, `include/trs_minweight.h`, `include/trs_unilateral.h` and `include/trs_plastic.h` (library: `libtrs_hip.so`, in-tree).
+"""ctypes binding of the C ABI in `include/trs_solver.h`, `include/trs_modes.h`, `include/trs_effects.h`, `include/trs_loss.h`, `include/trs_influence.h`, `include/trs_sets.h`, `include/trs_dynamics.h`, `include/trs_nonlinear.h`, `include/trs_buckling.h`, `include/trs_modegrad.h`, `include/trs_spectrum.h`, `include/trs_harmonic.h`, `include/trs_sizing.h`, `include/trs_compliance.h`, `include/trs_minweight.h`, `include/trs_minweight_stress.h`, `include/trs_unilateral.h` and `include/trs_plastic.h` (library: `libtrs_hip.so`, in-tree).
 
 There is no fallback: if the library is missing, `load()` raises `HipExtensionError`.
 """
@@ -241,6 +241,17 @@ MW_SIGNATURES = {
                          _I, _P, _D, _P, _D, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
 }
 
+#: every symbol `include/trs_minweight_stress.h` declares (minimum weight under stress and displacement limits in one run:
+#: the stress-ratio area as the lower bound of the optimality-criteria subproblem; csrc/minweight.hip, the same library,
+#: a second instantiation of the same kernel).  A header and a version of its own: `trs_minweight.h` is as it was
+MWS_SIGNATURES = {
+    "trs_mws_abi_version": (_I, []),
+    "trs_mw_fits_stress": (_I, [_I, _I, _I]),
+    "trs_mw_step_stress": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _D, _D,
+                                _D, _I, _P, _D, _P, _D, _D, _D, _P, _D, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P,
+                                _P, _P, _P, _P, _P]),
+}
+
 #: every symbol `include/trs_unilateral.h` declares (tension-only and compression-only members: the active-set iteration
 #: on the device; csrc/unilateral.hip, the same library).  General member form only, as the member sizing
 UN_SIGNATURES = {
@@ -290,6 +301,8 @@ SZ_ABI_VERSION = 1
 CM_ABI_VERSION = 1
 #: must equal TRS_MW_ABI_VERSION of include/trs_minweight.h
 MW_ABI_VERSION = 1
+#: must equal TRS_MWS_ABI_VERSION of include/trs_minweight_stress.h
+MWS_ABI_VERSION = 1
 #: must equal TRS_UN_ABI_VERSION of include/trs_unilateral.h
 UN_ABI_VERSION = 1
 #: must equal TRS_PL_ABI_VERSION of include/trs_plastic.h
@@ -369,6 +382,7 @@ def load():
             (RS_SIGNATURES, "trs_rs_abi_version", RS_ABI_VERSION), (HR_SIGNATURES, "trs_hr_abi_version", HR_ABI_VERSION),
             (SZ_SIGNATURES, "trs_sz_abi_version", SZ_ABI_VERSION), (CM_SIGNATURES, "trs_cm_abi_version", CM_ABI_VERSION),
             (MW_SIGNATURES, "trs_mw_abi_version", MW_ABI_VERSION),
+            (MWS_SIGNATURES, "trs_mws_abi_version", MWS_ABI_VERSION),
             (UN_SIGNATURES, "trs_un_abi_version", UN_ABI_VERSION), (PL_SIGNATURES, "trs_pl_abi_version", PL_ABI_VERSION)):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)

@@ -826,6 +826,45 @@ def _check_min_weight_scalars(who, measure="weight", move=0.2, tol=1e-4, max_ite
     return val
 
 
+#: the results that `min_weight` has only with stress limits
+_MW_STRESS_KEYS = ("utilisation", "governing", "stress_history")
+
+
+def _check_stress_limits(who, allow_tension, allow_compression, euler_kappa, B):
+    """The stress limits of the minimum-weight sizing (ValueError), by the rules of `_check_sizing_scalars`: both
+    allowables None - no stress limits, `euler_kappa` must then be 0 - returns None; one None is refused; else each is a
+    positive number or one per truss (an array [B], numpy or torch), and `euler_kappa` finite and >= 0.  +inf switches a
+    side off: it goes through the check as a positive number and comes back as it was.  Returns {"allow_tension",
+    "allow_compression": a float or a float64 array [B], "euler_kappa": a float}."""
+    if allow_tension is None and allow_compression is None:
+        if _check_number(who, "euler_kappa", euler_kappa) != 0.0:
+            raise ValueError(f"{who}: euler_kappa needs allow_tension and allow_compression (+inf: no stress limit)")
+        return None
+    if allow_tension is None or allow_compression is None:
+        raise ValueError(f"{who}: allow_tension and allow_compression must be given together (+inf switches one off)")
+
+    def raw(x):
+        if np.ndim(x) == 1 or hasattr(x, "detach"):
+            try:
+                return np.array(_host_array(x, np.float64), dtype=np.float64)
+            except (TypeError, ValueError):
+                return x
+        return x
+
+    def finite(x):
+        if isinstance(x, np.ndarray):
+            return np.where(x == np.inf, 1.0, x)
+        return 1.0 if isinstance(x, _REAL) and not isinstance(x, bool) and x == np.inf else x
+    given = {"allow_tension": raw(allow_tension), "allow_compression": raw(allow_compression)}
+    val = _check_sizing_scalars(who, finite(given["allow_tension"]), finite(given["allow_compression"]), 0.0, euler_kappa,
+                                B=B)
+    out = {"euler_kappa": val["euler_kappa"]}
+    for name, x in given.items():
+        off = x == np.inf
+        out[name] = np.where(off, np.inf, val[name]) if isinstance(val[name], np.ndarray) else (np.inf if off else val[name])
+    return out
+
+
 def _check_limits(who, limit_case, limit_joint, limit_direction, limit_value, B, nJ_max, L, nJ=None):
     """The displacement limits of the minimum-weight sizing (ValueError), J of them, 1 <= J <= 8: `limit_case` J integers
     in [0, L), shared by the batch; `limit_joint` integers [J] or [B, J] in the caller's joint numbering, -1 (switched
@@ -2453,7 +2492,7 @@ class DeviceBatch:
     # -- minimum weight under displacement limits, iterated on the device (include/trs_minweight.h) ---------------------
     def min_weight(self, loads=None, *, limit_case, limit_joint, limit_direction, limit_value, measure="weight", move=0.2,
                    area_min, area_max, tol=1e-4, max_iters=60, sweeps=2, limit_tol=1e-2, check_every=1,
-                   want_sensitivity=False, out=None):
+                   want_sensitivity=False, out=None, allow_tension=None, allow_compression=None, euler_kappa=0.0):
         """Minimum-weight sizing of the resident batch under displacement limits (include/trs_minweight.h: the
         optimality-criteria method with one multiplier per limit): the lightest design - the smallest sum w A, w = rho L0
         (`measure` "weight") or L0 ("volume") - with d_j.u_{l_j}(joint_j) <= `limit_value`_j for each of the J <= 8
@@ -2478,7 +2517,18 @@ class DeviceBatch:
         `self.info` holds 0, or for a truss of status 2 what the factorisation reported, latched.  Afterwards `self.A`
         holds the returned areas and the slab the factor of the returned design for every truss of status 0, 1 or 3:
         `solve_cases` may follow without another `factor()`; `generation` is bumped.  A batch on the fused small-system
-        path, `options["compact"]` and the table member form are refused, as in `sizing()`."""
+        path, `options["compact"]` and the table member form are refused, as in `sizing()`.
+        Stress limits in the same run: `allow_tension` and `allow_compression` (both or neither; each a number > 0 or one
+        per truss, an array [B], as `sizing()` takes them; +inf switches a side off) and `euler_kappa` >= 0 (I = kappa A^2;
+        0: no member buckling term).  Every analysis gives every member the area its worst case demands - the stress-ratio
+        area of `sizing()`, Euler term included - and uses it as the member's LOWER bound in the resizing, within the move
+        limit and the area bounds: members governed by stress sit on that floor, members governed by a displacement limit
+        are sized by the multipliers (`trs_mw_step_stress`: the same kernel with three more words per member in LDS).  The
+        dict then also holds utilisation [B, nM_max] (req / A; <= 1 is feasible), governing (int32 [B, nM_max]: the case
+        that sets a member's requirement, -1 where there is none and on the padding) and stress_history
+        [B, max_iters + 1] (the largest utilisation of every design analysed); worst_history stays the displacement
+        figure, and status 0 asks both for <= 1 + `limit_tol`, else 3.  With both None the call is the one without stress
+        limits exactly: `trs_mw_step`, and none of the three keys."""
         t = self.torch
         who = "min_weight()"
         self._refuse_iterated("min_weight")
@@ -2488,31 +2538,44 @@ class DeviceBatch:
         if L < 1:
             raise ValueError(f"{who}: loads must hold at least one case")
         val = _check_min_weight_scalars(who, measure, move, tol, max_iters, sweeps, limit_tol, check_every)
+        stress = _check_stress_limits(who, allow_tension, allow_compression, euler_kappa, self.B)
         lim = _check_limits(who, limit_case, limit_joint, limit_direction, limit_value, self.B, self.nJ_max, L)
         J = int(lim["case"].size)
         bounds = self._area_bounds(who, area_min, area_max)
         H = val["max_iters"] + 1
-        keys = [k for k, *_ in MinWeightResult.FIELDS.values() if k != "sensitivity" or want_sensitivity]
+        keys = [k for k, *_ in MinWeightResult.FIELDS.values()
+                if (k != "sensitivity" or want_sensitivity) and (k not in _MW_STRESS_KEYS or stress is not None)]
         out = self._out_tensors("min_weight", _field_shapes(MinWeightResult.FIELDS, self.B, self._sizes(H=H, G=J), keys), out)
         if self.B == 0:
             return out
-        self._begin_iterated("min_weight", (lambda nJ, nM: self.lib.trs_mw_fits(nJ, nM, J), "the step kernel (trs_mw_fits)"))
-        ws = self._mw_workspace(val, bounds, loads, lim, out)
+        fits, name = (self.lib.trs_mw_fits, "trs_mw_fits") if stress is None else \
+            (self.lib.trs_mw_fits_stress, "trs_mw_fits_stress")
+        self._begin_iterated("min_weight", (lambda nJ, nM: fits(nJ, nM, J), f"the step kernel ({name})"))
+        ws = self._mw_workspace(val, bounds, loads, lim, out, stress)
         with t.cuda.device(self.device):
             self.dofmap()
             out["measure_history"].zero_()
             out["worst_history"].zero_()
+            if stress is not None:
+                out["stress_history"].zero_()
             self._iterate(ws, val["check_every"], self._analyse_cases, self._mw_step)
             self._end_iterated(ws, out)   # (the factor: of the returned design, for every truss of status 0, 1 or 3)
         return out
 
     # the stages of `min_weight` (tools/bench_minweight.py times them one by one; the analysis is `_analyse_cases`)
-    def _mw_workspace(self, val, bounds, loads, lim, out):
+    def _mw_workspace(self, val, bounds, loads, lim, out, stress=None):
         """The state of a `min_weight` run: the design before the last resizing, the multipliers mu [B, J], the status
         words and the `active` counters, zeroed; the case block of L + J columns and its loads - the real cases, then
         the unit load d_j at every limit's joint (zero where the limit is switched off), in the caller's numbering; the
-        limits on the device, their joints mapped through the batch's joint order into the device's numbering."""
+        limits on the device, their joints mapped through the batch's joint order into the device's numbering.
+        `stress`: the dict of `_check_stress_limits` or None; an allowable given per truss makes `allow` [B, 2]."""
         t, dev = self.torch, self.device
+        allow = None
+        if stress is not None:
+            names = ("allow_tension", "allow_compression")
+            if any(isinstance(stress[k], np.ndarray) for k in names):
+                allow = t.from_numpy(np.stack([np.broadcast_to(stress[k], [self.B]) for k in names], axis=1).copy()).to(dev)
+                stress = dict(stress, **dict.fromkeys(names, 1.0))   # (not read beside `allow`)
         B, L, J = self.B, int(loads.shape[1]), int(lim["case"].size)
         joint = t.from_numpy(lim["joint"].astype(np.int64)).to(dev)                 # [B, J], the caller's numbering
         direction = t.from_numpy(lim["direction"]).to(dev)
@@ -2532,10 +2595,26 @@ class DeviceBatch:
                                mu=t.zeros([B, J], dtype=t.float64, device=dev), cases=L, J=J,
                                limit_case=t.from_numpy(lim["case"]).to(dev), limit_joint=device_joint,
                                limit_dir=direction.contiguous(), limit_value=value.contiguous(), val=val, bounds=bounds,
-                               out=out)
+                               out=out, stress=stress, allow=allow)
 
     def _mw_step(self, ws, it, mode):
         val, out, (lo, hi) = ws["val"], ws["out"], ws["bounds"]
+        stress = ws.get("stress")
+        if stress is not None:
+            _capi.check(self.lib.trs_mw_step_stress(
+                self.B, ws["cases"], ws["J"], self.nJ_max, self.nM_max, self.xyz.data_ptr(), self.conn.data_ptr(),
+                self.E.data_ptr(), self.A.data_ptr(), self.rho.data_ptr(), self.free_index.data_ptr(),
+                self.n_free.data_ptr(), self.nJ.data_ptr(), self.nM.data_ptr(), ws["F"].data_ptr(), self.rows,
+                self.info.data_ptr(), ws["limit_case"].data_ptr(), ws["limit_joint"].data_ptr(), ws["limit_dir"].data_ptr(),
+                ws["limit_value"].data_ptr(), _capi.MW_MEASURES[val["measure"]], val["move"], val["tol"], val["limit_tol"],
+                val["sweeps"], _ptr(lo[0]), lo[1], _ptr(hi[0]), hi[1], stress["allow_tension"], stress["allow_compression"],
+                _ptr(ws["allow"]), stress["euler_kappa"], it, mode, ws["prev"].data_ptr(), ws["mu"].data_ptr(),
+                ws["st"].data_ptr(), self._active(ws, it), out["areas"].data_ptr(), out["measure"].data_ptr(),
+                out["measure_history"].data_ptr(), out["worst_history"].data_ptr(), val["max_iters"] + 1,
+                out["displacement"].data_ptr(), out["ratio"].data_ptr(), out["multipliers"].data_ptr(),
+                _ptr(out.get("sensitivity")), out["utilisation"].data_ptr(), out["governing"].data_ptr(),
+                out["stress_history"].data_ptr(), self._stream()), "trs_mw_step_stress")
+            return
         _capi.check(self.lib.trs_mw_step(
             self.B, ws["cases"], ws["J"], self.nJ_max, self.nM_max, self.xyz.data_ptr(), self.conn.data_ptr(),
             self.E.data_ptr(), self.A.data_ptr(), self.rho.data_ptr(), self.free_index.data_ptr(), self.n_free.data_ptr(),
@@ -5353,7 +5432,10 @@ class MinWeightResult:
     0 converged within limit_tol of its limits, 1 iteration limit, 2 a design could not be factored - the truss went back
     to the design before; with iterations 0 its areas are the initial ones and the other results zero -, 3 converged on
     its bounds without meeting a limit).  info [B]: 0, or what the factorisation reported for the design that ended a
-    truss with status 2."""
+    truss with status 2.  With stress limits (None without): utilisation [B, nM_max] (req / A of the returned design: the
+    stress-ratio area of its worst case over its area; <= 1 is feasible), governing (int32 [B, nM_max]: that case, -1
+    where no case asks for any area and on the padding), stress_history [B, max_iters + 1] (the largest utilisation of
+    every design the truss analysed); status 0 then asks the utilisation too for <= 1 + limit_tol."""
     areas: np.ndarray
     measure: np.ndarray
     measure_history: np.ndarray
@@ -5362,6 +5444,9 @@ class MinWeightResult:
     ratio: np.ndarray
     multipliers: np.ndarray
     sensitivity: np.ndarray
+    utilisation: np.ndarray
+    governing: np.ndarray
+    stress_history: np.ndarray
     iterations: np.ndarray
     status: np.ndarray
     info: np.ndarray
@@ -5373,17 +5458,19 @@ class MinWeightResult:
               "displacement": ("displacement", 0.0, "float64", ("G",)), "ratio": ("ratio", 0.0, "float64", ("G",)),
               "multipliers": ("multipliers", 0.0, "float64", ("G",)),
               "sensitivity": ("sensitivity", 0.0, "float64", ("G", "nM")),
+              "utilisation": ("utilisation", 0.0, "float64", ("nM",)), "governing": ("governing", -1, "int32", ("nM",)),
+              "stress_history": ("stress_history", 0.0, "float64", ("H",)),
               "iterations": ("iterations", 0, "int32", ()), "status": ("status", 0, "int32", ())}
 
 
 def _check_min_weight_args(packed, loads=None, limit_case=None, limit_joint=None, limit_direction=None, limit_value=None,
                            measure="weight", move=0.2, area_min=None, area_max=None, tol=1e-4, max_iters=60, sweeps=2,
                            limit_tol=1e-2, check_every=1, want_sensitivity=False, options=None, sections=None,
-                           max_result_bytes=4 << 30):
+                           max_result_bytes=4 << 30, allow_tension=None, allow_compression=None, euler_kappa=0.0):
     """The argument errors of `solve_min_weight` that need no device (ValueError).  Returns the arguments checked: the
     dict of `_check_min_weight_scalars` plus "loads" (a float64 host array [B, L, nJ_max, 3], or None for the batch's own
     loads), "limits" (the dict of `_check_limits`), "want_sensitivity" and "area_min" / "area_max" (each a float, or a
-    float64 host array [B, nM_max])."""
+    float64 host array [B, nM_max]) and "stress" (the dict of `_check_stress_limits`, or None)."""
     who = "solve_min_weight"
     _refuse_variants(who, "the minimum-weight sizing (it writes the sections)", sections, options)
     B, nJ_max, nM_max = packed.B, packed.nJ_max, packed.nM_max
@@ -5393,6 +5480,7 @@ def _check_min_weight_args(packed, loads=None, limit_case=None, limit_joint=None
     if not isinstance(want_sensitivity, (bool, np.bool_)):
         raise ValueError(f"{who}: want_sensitivity must be True or False, got {want_sensitivity!r}")
     val["want_sensitivity"] = bool(want_sensitivity)
+    val["stress"] = _check_stress_limits(who, allow_tension, allow_compression, euler_kappa, B)
     val["loads"] = host_loads
     if limit_case is None or limit_joint is None or limit_direction is None or limit_value is None:
         raise ValueError(f"{who}: limit_case, limit_joint, limit_direction and limit_value must be given")
@@ -5408,6 +5496,8 @@ def _check_min_weight_args(packed, loads=None, limit_case=None, limit_joint=None
         raise ValueError(f"{who}: measure='weight' needs a positive density rho on every member - a member with rho <= 0 "
                          "weighs nothing; use measure='volume'")
     nbytes = B * (8 * nM_max * (1 + J * val["want_sensitivity"]) + 16 * (val["max_iters"] + 1) + 24 * J + 24)
+    if val["stress"] is not None:
+        nbytes += B * (12 * nM_max + 8 * (val["max_iters"] + 1))
     if nbytes > max_result_bytes:
         raise ValueError(f"{who}: the results of B={B} trusses take {nbytes} bytes, more than max_result_bytes = "
                          f"{max_result_bytes}")
@@ -5418,7 +5508,7 @@ def solve_min_weight(trusses_or_packed, loads=None, limit_case=None, limit_joint
                      limit_value=None, measure="weight", move=0.2, area_min=None, area_max=None, tol=1e-4, max_iters=60,
                      sweeps=2, limit_tol=1e-2, check_every=1, want_sensitivity=False, device=None, reorder=False,
                      options=None, on_device=False, sections=None, use_envelope=True, max_slab_bytes=64 << 30,
-                     max_result_bytes=4 << 30):
+                     max_result_bytes=4 << 30, allow_tension=None, allow_compression=None, euler_kappa=0.0):
     """The lightest design of every truss of a batch whose named joint displacements stay within named limits: the
     optimality-criteria method with one multiplier per limit (include/trs_minweight.h, `DeviceBatch.min_weight`).  The
     objective is sum w A with w = rho L0 (`measure` "weight") or L0 ("volume"); limit j means
@@ -5430,10 +5520,16 @@ def solve_min_weight(trusses_or_packed, loads=None, limit_case=None, limit_joint
     `area_min`: scalars or [B, nM_max] (equal bounds fix a member); `tol` is the relative area change at which a truss is
     converged, `limit_tol` how far above its limits a converged truss may lie and still get status 0 (else 3),
     `max_iters` the number of resizings at most, `sweeps` the passes of the dual solve over the limits, `check_every` how
-    often the host looks whether every truss is done.  What the method is not: there are no stress limits
-    inside the run (size for stress first - `solve_sizing` without a displacement limit - and pass its areas as
-    `area_min`), no linked member groups, no limits on member forces or reactions, and with several limits that compete
-    for the same members the resizing can approach its fixed point slowly or cycle inside its move limits.  Every
+    often the host looks whether every truss is done.  Stress limits in the same run: `allow_tension` and
+    `allow_compression` (both or neither; each a number > 0 or one per truss [B]; +inf switches a side off) and
+    `euler_kappa` >= 0, as `solve_sizing` takes them - every analysis makes the stress-ratio area of a member's worst
+    case the member's lower bound in the resizing, and the result gains utilisation, governing and stress_history
+    (`DeviceBatch.min_weight`); without them the three are None.  What the method is not: the stress floor
+    is the stress-ratio estimate, exact only where the member forces do not depend on the areas; there are at most 8
+    named displacement limits, not an envelope over all joints; a large `move` can stall on small members, and a truss
+    with many members on the floor converges slowly; no linked member groups, no limits on reactions, and with several
+    limits that compete for the same members the resizing can approach its fixed point slowly or cycle inside its move
+    limits.  Every
     iteration factors its own design (`_factored_buckets` factors nothing ahead).  A table-form batch is converted with
     `.general()`.  `measure="weight"` is refused when a member has rho <= 0.  Buckets, `reorder` plans, `options`,
     `on_device` and `use_envelope` as `solve_load_cases`.  Bad arguments (`_check_min_weight_args`) raise ValueError
@@ -5441,14 +5537,16 @@ def solve_min_weight(trusses_or_packed, loads=None, limit_case=None, limit_joint
     packed = _as_packed(trusses_or_packed)
     val = _check_min_weight_args(packed, loads, limit_case, limit_joint, limit_direction, limit_value, measure, move,
                                  area_min, area_max, tol, max_iters, sweeps, limit_tol, check_every, want_sensitivity,
-                                 options, sections, max_result_bytes)
+                                 options, sections, max_result_bytes, allow_tension, allow_compression, euler_kappa)
     if packed.is_table:
         packed = packed.general()
     torch, dev = _require_gpu(device)
     lim = val["limits"]
     sizes = {"nM": packed.nM_max, "H": val["max_iters"] + 1, "G": int(lim["case"].size)}
+    stress = val["stress"]
     out = _new_result(torch, dev, MinWeightResult, packed.B, sizes,
-                      without=() if val["want_sensitivity"] else ("sensitivity",))
+                      without=(() if val["want_sensitivity"] else ("sensitivity",)) + (_MW_STRESS_KEYS if stress is None else ()))
+    cut = lambda part, x: x[part.index] if isinstance(x, np.ndarray) else x   # (an allowable per truss: the bucket's)
     on, bound = _upload_design_args(torch, dev, val)
     for db, part in _factored_buckets(packed, dev, out.info, max_slab_bytes, reorder, options, use_envelope,
                                       factor=lambda db, part: None):
@@ -5457,7 +5555,10 @@ def solve_min_weight(trusses_or_packed, loads=None, limit_case=None, limit_joint
             limit_direction=lim["given"][part.index], limit_value=lim["value"][part.index], measure=val["measure"],
             move=val["move"], area_min=bound(part, on["area_min"]), area_max=bound(part, on["area_max"]), tol=val["tol"],
             max_iters=val["max_iters"], sweeps=val["sweeps"], limit_tol=val["limit_tol"],
-            check_every=val["check_every"], want_sensitivity=val["want_sensitivity"]))
+            check_every=val["check_every"], want_sensitivity=val["want_sensitivity"],
+            **({} if stress is None else {"allow_tension": cut(part, stress["allow_tension"]),
+                                          "allow_compression": cut(part, stress["allow_compression"]),
+                                          "euler_kappa": stress["euler_kappa"]})))
     return _finish_result(torch, dev, out, on_device)
 
 

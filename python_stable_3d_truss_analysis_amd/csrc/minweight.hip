@@ -1,11 +1,13 @@
 // Minimum weight under displacement limits: the optimality-criteria method with one multiplier per limit, iterated on
-// the device (include/trs_minweight.h).  The assembly, the factorisation, the gather and the multi-case substitution of
+// the device (include/trs_minweight.h; with stress limits include/trs_minweight_stress.h).  The assembly, the factorisation, the gather and the multi-case substitution of
 // every iteration are trs_assemble, trs_potrf_batched, trs_gather_cases and trs_potrs_cases as they are - the virtual
 // unit loads of the limits are just more columns of the case block; this file holds what turns the L + J reduced
 // solutions into the next design:
 //
-//   trs_mw_step   one analysis: the limit values g_j, the sensitivities c_mj, the dual solve (per limit a geometric
-//                 bisection on its multiplier, `sweeps` passes), the resizing, the convergence test and the outputs
+//   trs_mw_step          one analysis: the limit values g_j, the sensitivities c_mj, the dual solve (per limit a
+//                        geometric bisection on its multiplier, `sweeps` passes), the resizing, the convergence test and
+//                        the outputs
+//   trs_mw_step_stress   the same with stress limits: the stress-ratio area of every member as its lower bound
 //
 // The method, analysis k of design A (the header and tests/minweight_reference.py state it in the same words):
 //     proj_m(x) = c_m.(x_j1 - x_j0);  c_mj = (E_m / L0_m) proj_m(v_j) proj_m(u_{l_j}) = -dg_j/dA_m
@@ -20,6 +22,17 @@
 //     x0 = 2^-300 x1: xm = sqrt(x0 x1); if gt_j(xm) <= ubar_j then x1 = xm, else x0 = xm;  mu_j = x1
 //     change = max_m |A'_m - A_m| / A_m;  worst = max_j g_j / ubar_j
 //     change <= tol: status 0 if worst <= 1 + limit_tol, else 3; else k = max_iters: status 1; else A_{k+1} = A'
+// With stress limits (trs_mw_step_stress; tests/minweight_stress_reference.py), all of the above and:
+//     N_ml = ((E_m / L0_m) A_m) proj_m(u_l) for every REAL case l < L;  the required area in case l is N / allow_tension
+//     for N > 0; for P = -N > 0 it is max(P / allow_compression, sqrt(P L0^2 / (pi^2 E kappa))), the second term only
+//     when kappa > 0 (trs_sizing.h's words and its expression order)
+//     req_m = the maximum over the cases in ascending l, on a tie the lowest l governs; governing_m = that l, or -1
+//     where req_m = 0
+//     the floor: lo_m = min(max(lo_m, req_m), hi_m) - a member that needs more than (1 + move) A_m grows at the move
+//     limit, a member with w_m <= 0 keeps lo_m = hi_m;  the subproblem, the cut, the dual solve, the bisection, A'(mu)
+//     and `change` are unchanged: only lo differs
+//     utilisation_m = req_m / A_m;  stress_worst = its maximum over the live members (an extreme: exact in any order)
+//     change <= tol: status 0 if max(worst, stress_worst) <= 1 + limit_tol, else 3
 //
 // trs_mw_step: one 256-thread work-group per truss.  A thread owns the members tid, tid + 256, ...: it forms their
 // geometry once (c, E / L0, w, A), keeps it in LDS, and is the only thread that ever touches those entries - the member
@@ -31,7 +44,14 @@
 // behind ONE barrier: reduction e writes the slot set e & 1, whose readers of reduction e - 2 passed the barrier of
 // reduction e - 1.  Every sum runs per thread in ascending m, then by the wave butterfly, then over the four waves in
 // order.  No floating-point atomic.
+//
+// The kernel is a template on `bool STRESS`: the instantiation without stress limits is compiled from the statements it
+// had before the stress limits came (every addition stands under `if constexpr (STRESS)`), and it is the one trs_mw_step
+// launches.  The other keeps three more words per member in LDS, formed ahead of the case loop - the running req_m, its
+// case, the Euler coefficient L0^2 / (pi^2 E kappa) - and updates the running requirement as each real case passes
+// through the stage: no further pass over the case block, no u and no N to HBM.
 #include "../../include/trs_minweight.h"
+#include "../../include/trs_minweight_stress.h"
 #include "../../include/trs_solver.h"
 #include "trs_common.h"
 #include "trs_iterate.h"
@@ -59,11 +79,15 @@ struct StepTables {
     double* c;      // [J][nM_max]    proj_m(u_{l_j}), then c_mj
     int2* ends;     // [nM_max]       end joints, clamped
     int* row;       // [3 nJ_max]     row_of every DOF (-1: reads 0), formed once: a column's staging is one load deep
+    // with stress limits only:
+    double* req;    // [nM_max]       the running required area
+    double* eul;    // [nM_max]       L0^2 / (pi^2 E kappa), 0 without a member buckling term
+    int* gov;       // [nM_max]       the case that set req (-1: none)
 };
 
-template <class Arena>
+template <bool STRESS, class Arena>
 __host__ __device__ inline StepTables step_layout(Arena& a, int nJ_max, int nM_max, int J) {
-    StepTables t;
+    StepTables t = {};
     t.u = a.template take<double>(6, nJ_max);
     t.red = a.template take<double>(RED);
     t.c0 = a.template take<double>(nM_max);
@@ -73,13 +97,19 @@ __host__ __device__ inline StepTables step_layout(Arena& a, int nJ_max, int nM_m
     t.w = a.template take<double>(nM_max);
     t.a = a.template take<double>(nM_max);
     t.c = a.template take<double>(J, nM_max);
+    if constexpr (STRESS) {
+        t.req = a.template take<double>(nM_max);
+        t.eul = a.template take<double>(nM_max);
+    }
     t.ends = a.template take<int2>(nM_max);
     t.row = a.template take<int>(3, nJ_max);
+    if constexpr (STRESS) t.gov = a.template take<int>(nM_max);
     return t;
 }
 
+template <bool STRESS>
 size_t step_lds(int nJ_max, int nM_max, int J) {
-    return trs_lds::count([&](auto& a) { step_layout(a, nJ_max, nM_max, J); });
+    return trs_lds::count([&](auto& a) { step_layout<STRESS>(a, nJ_max, nM_max, J); });
 }
 
 struct StepArgs {
@@ -105,6 +135,12 @@ struct StepArgs {
     double* ratio;            // [B][J]
     double* multipliers;      // [B][J]
     double* sens;             // [B][J][nM_max] or null
+    // with stress limits only (behind the rest: the words above keep their places)
+    double allow_tension, allow_compression, euler_kappa;
+    const double* allow;      // [B][2] or null
+    double* util;             // [B][nM_max]
+    int* governing;           // [B][nM_max]
+    double* stress_history;   // [B][H]
 };
 
 // One reduction of the work-group behind one barrier; `e` counts the reductions of the kernel (uniform).
@@ -179,6 +215,7 @@ struct Dual {
     }
 };
 
+template <bool STRESS>
 __global__ __launch_bounds__(256) void trs_mw_step_kernel(const TrsBatch bt, const StepArgs g) {
     extern __shared__ double sh[];   // (no static LDS beside it: the dynamic ceiling is the whole of a CU's)
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -198,6 +235,10 @@ __global__ __launch_bounds__(256) void trs_mw_step_kernel(const TrsBatch bt, con
                 g.areas[mbase + m] = m < members ? Ab[m] : 0.0;
                 if (g.sens != nullptr)
                     for (int j = 0; j < J; ++j) g.sens[((size_t)b * J + j) * nM_max + m] = 0.0;
+                if constexpr (STRESS) {
+                    g.util[mbase + m] = 0.0;
+                    g.governing[mbase + m] = -1;
+                }
             } else if (m < members) {
                 Ab[m] = g.prev[mbase + m];
             }
@@ -212,7 +253,7 @@ __global__ __launch_bounds__(256) void trs_mw_step_kernel(const TrsBatch bt, con
         return;
     }
     trs_lds::Carve lds(sh);
-    const StepTables t = step_layout(lds, bt.nJ_max, nM_max, J);
+    const StepTables t = step_layout<STRESS>(lds, bt.nJ_max, nM_max, J);
     const int columns = L + J;
     const trs_iter::CaseStage cases = {t.u, t.row, g.F + (size_t)b * columns * ld_f, ndof_max, ld_f};
     cases.form_rows(tr, tid);
@@ -258,6 +299,17 @@ __global__ __launch_bounds__(256) void trs_mw_step_kernel(const TrsBatch bt, con
 #pragma unroll
         for (int j = 0; j < JMAX; ++j)
             if (j < J) t.c[j * nM_max + m] = 0.0;   // (a limit that is switched off keeps c_mj = 0)
+        if constexpr (STRESS) {
+            constexpr double PI = 3.14159265358979323846;
+            t.req[m] = 0.0;
+            t.gov[m] = -1;
+            t.eul[m] = g.euler_kappa > 0.0 ? (geo.len * geo.len) / (((PI * PI) * E) * g.euler_kappa) : 0.0;
+        }
+    }
+    double at = 0.0, ac = 0.0;   // (the allowables of this truss)
+    if constexpr (STRESS) {
+        at = g.allow != nullptr ? g.allow[2 * b] : g.allow_tension;
+        ac = g.allow != nullptr ? g.allow[2 * b + 1] : g.allow_compression;
     }
     __syncthreads();   // (column 0 is staged)
     // ---- the columns: a real case leaves proj_m(u_l) with every limit that names it, limit j's own column makes c_mj ----
@@ -281,6 +333,7 @@ __global__ __launch_bounds__(256) void trs_mw_step_kernel(const TrsBatch bt, con
         if (own < 0) {
 #pragma unroll
             for (int j = 0; j < JMAX; ++j) wanted |= j < J && lcase[j] == col;
+            if constexpr (STRESS) wanted = true;   // (every real case sets the members' requirement)
         } else {
 #pragma unroll
             for (int j = 0; j < JMAX; ++j) wanted &= j != own || lcase[j] >= 0;
@@ -297,6 +350,21 @@ __global__ __launch_bounds__(256) void trs_mw_step_kernel(const TrsBatch bt, con
 #pragma unroll
                     for (int j = 0; j < JMAX; ++j)
                         if (j < J && lcase[j] == col) t.c[j * nM_max + m] = proj;
+                    if constexpr (STRESS) {
+                        const double N = (t.ek[m] * t.a[m]) * proj;
+                        double r = 0.0;
+                        if (N > 0.0) {
+                            r = N / at;
+                        } else if (N < 0.0) {
+                            const double P = -N;
+                            r = P / ac;
+                            if (g.euler_kappa > 0.0) r = fmax(r, sqrt(P * t.eul[m]));
+                        }
+                        if (r > t.req[m]) {   // (strictly: on a tie the lowest l governs)
+                            t.req[m] = r;
+                            t.gov[m] = col;
+                        }
+                    }
                 } else {
                     t.c[own * nM_max + m] = (t.ek[m] * proj) * t.c[own * nM_max + m];
                 }
@@ -307,8 +375,11 @@ __global__ __launch_bounds__(256) void trs_mw_step_kernel(const TrsBatch bt, con
     }
     // ---- the outputs of this design; lo, hi of the resizing (over c0, c1: the columns are behind) ----
     const double move = g.move;
+    double stress_worst = 0.0;
     for (int m = tid; m < nM_max; m += 256) {
         double area = 0.0;
+        [[maybe_unused]] double util = 0.0;
+        [[maybe_unused]] int gov = -1;
         if (m < members) {
             area = t.a[m];
             const double a_lo = g.bounds.lo(mbase + m), a_hi = g.bounds.hi(mbase + m);
@@ -319,16 +390,27 @@ __global__ __launch_bounds__(256) void trs_mw_step_kernel(const TrsBatch bt, con
             } else {
                 lo = hi = fmin(fmax(area, a_lo), a_hi);
             }
+            if constexpr (STRESS) {   // the floor: what the member's worst case demands, within the interval
+                lo = fmin(fmax(lo, t.req[m]), hi);
+                util = t.req[m] / area;
+                gov = t.gov[m];
+                stress_worst = fmax(stress_worst, util);
+            }
             t.c0[m] = lo;
             t.c1[m] = hi;
         }
         g.areas[mbase + m] = area;
+        if constexpr (STRESS) {
+            g.util[mbase + m] = util;
+            g.governing[mbase + m] = gov;
+        }
         if (g.sens != nullptr) {
             for (int j = 0; j < J; ++j) g.sens[((size_t)b * J + j) * nM_max + m] = m < members ? t.c[j * nM_max + m] : 0.0;
         }
     }
     Reducer red = {t.red, 0, tid};
     const double measure = red.sum(msum);
+    if constexpr (STRESS) stress_worst = red.max(stress_worst);
     // ---- a member off a limit's load path (|c_mj| A_m <= 2^-30 max_m |c_mj| A_m) counts with q_mj = n_mj = 0 ----
     for (int j = 0; j < J; ++j) {
         double top = 0.0;
@@ -387,8 +469,10 @@ __global__ __launch_bounds__(256) void trs_mw_step_kernel(const TrsBatch bt, con
         }
     }
     if (!any) worst = 0.0;
+    double bound = worst;   // (what a converged truss must keep within 1 + limit_tol)
+    if constexpr (STRESS) bound = fmax(worst, stress_worst);
     if (change <= g.tol)
-        run.status = worst <= 1.0 + g.limit_tol ? TRS_MW_CONVERGED : TRS_MW_INFEASIBLE;
+        run.status = bound <= 1.0 + g.limit_tol ? TRS_MW_CONVERGED : TRS_MW_INFEASIBLE;
     else if (mode == 1)
         run.status = TRS_MW_ITER_LIMIT;
     if (run.active()) {
@@ -402,6 +486,7 @@ __global__ __launch_bounds__(256) void trs_mw_step_kernel(const TrsBatch bt, con
         if (it < g.H) {
             g.measure_history[(size_t)b * g.H + it] = measure;
             g.worst_history[(size_t)b * g.H + it] = worst;
+            if constexpr (STRESS) g.stress_history[(size_t)b * g.H + it] = stress_worst;
         }
 #pragma unroll
         for (int j = 0; j < JMAX; ++j) {
@@ -417,25 +502,25 @@ __global__ __launch_bounds__(256) void trs_mw_step_kernel(const TrsBatch bt, con
     }
 }
 
-}  // namespace
+// What trs_mw_step_stress takes beyond trs_mw_step
+struct StressIO {
+    double allow_tension, allow_compression, euler_kappa;
+    const double* allow;
+    double* util;
+    int* governing;
+    double* stress_history;
+};
 
-extern "C" {
-
-int trs_mw_abi_version(void) { return TRS_MW_ABI_VERSION; }
-
-int trs_mw_fits(int nJ_max, int nM_max, int J) {
-    if (nJ_max < 0 || nM_max < 0 || nJ_max > 65535 || J < 1 || J > TRS_MW_MAX_LIMITS) return 0;
-    return step_lds(nJ_max, nM_max, J) <= TRS_LDS_BYTES;
-}
-
-int trs_mw_step(int B, int L, int J, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* E,
-                double* A, const double* rho, const int32_t* free_index, const int32_t* n_free, const int32_t* nJ,
-                const int32_t* nM, const double* F, int ld_f, const int32_t* info, const int32_t* limit_case,
-                const int32_t* limit_joint, const double* limit_dir, const double* limit_value, int measure, double move,
-                double tol, double limit_tol, int sweeps, const double* a_min, double a_min_all, const double* a_max,
-                double a_max_all, int it, int mode, double* prev, double* mu, int32_t* st, int32_t* active, double* areas,
-                double* measure_out, double* measure_history, double* worst_history, int H, double* displacement,
-                double* ratio, double* multipliers, double* sensitivity, void* stream) {
+// The argument rules and the launch that the two entry points share
+template <bool STRESS>
+int step(int B, int L, int J, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* E, double* A,
+         const double* rho, const int32_t* free_index, const int32_t* n_free, const int32_t* nJ, const int32_t* nM,
+         const double* F, int ld_f, const int32_t* info, const int32_t* limit_case, const int32_t* limit_joint,
+         const double* limit_dir, const double* limit_value, int measure, double move, double tol, double limit_tol,
+         int sweeps, const double* a_min, double a_min_all, const double* a_max, double a_max_all, int it, int mode,
+         double* prev, double* mu, int32_t* st, int32_t* active, double* areas, double* measure_out, double* measure_history,
+         double* worst_history, int H, double* displacement, double* ratio, double* multipliers, double* sensitivity,
+         const StressIO s, void* stream) {
     if (B < 0 || L < 1 || J < 1 || J > TRS_MW_MAX_LIMITS || nJ_max <= 0 || nM_max < 0 || ld_f < 0 || it < 0 || mode < 0 ||
         mode > 1 || H < 0 || sweeps < 1 || (measure != TRS_MW_WEIGHT && measure != TRS_MW_VOLUME))
         return (int)hipErrorInvalidValue;
@@ -447,15 +532,69 @@ int trs_mw_step(int B, int L, int J, int nJ_max, int nM_max, const double* xyz, 
         !limit_value || !prev || !mu || !st || !active || !areas || !measure_out ||
         (H > 0 && (!measure_history || !worst_history)) || !displacement || !ratio || !multipliers)
         return (int)hipErrorInvalidValue;
-    if (!trs_mw_fits(nJ_max, nM_max, J)) return (int)hipErrorInvalidValue;
+    if (step_lds<STRESS>(nJ_max, nM_max, J) > TRS_LDS_BYTES || nJ_max > 65535) return (int)hipErrorInvalidValue;
     const TrsBatch bt = trs_batch(nJ_max, nM_max, xyz, trs_members_general(conn, E, A, rho), free_index, n_free, nJ, nM,
                                   nullptr, ld_f);
     const StepArgs g = {F, info, limit_case, limit_joint, limit_dir, limit_value, move, tol, limit_tol, bounds, L, J, it,
                         mode, H, measure, sweeps, A, prev, mu, st, active, areas, measure_out, measure_history,
-                        worst_history, displacement, ratio, multipliers, sensitivity};
-    trs_lds::raise_lds_once<trs_mw_step_kernel>();
-    hipLaunchKernelGGL(trs_mw_step_kernel, dim3(B), dim3(256), step_lds(nJ_max, nM_max, J), (hipStream_t)stream, bt, g);
+                        worst_history, displacement, ratio, multipliers, sensitivity, s.allow_tension,
+                        s.allow_compression, s.euler_kappa, s.allow, s.util, s.governing, s.stress_history};
+    trs_lds::raise_lds_once<trs_mw_step_kernel<STRESS>>();
+    hipLaunchKernelGGL(trs_mw_step_kernel<STRESS>, dim3(B), dim3(256), step_lds<STRESS>(nJ_max, nM_max, J),
+                       (hipStream_t)stream, bt, g);
     return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+int trs_mw_abi_version(void) { return TRS_MW_ABI_VERSION; }
+
+int trs_mws_abi_version(void) { return TRS_MWS_ABI_VERSION; }
+
+int trs_mw_fits(int nJ_max, int nM_max, int J) {
+    if (nJ_max < 0 || nM_max < 0 || nJ_max > 65535 || J < 1 || J > TRS_MW_MAX_LIMITS) return 0;
+    return step_lds<false>(nJ_max, nM_max, J) <= TRS_LDS_BYTES;
+}
+
+int trs_mw_fits_stress(int nJ_max, int nM_max, int J) {
+    if (nJ_max < 0 || nM_max < 0 || nJ_max > 65535 || J < 1 || J > TRS_MW_MAX_LIMITS) return 0;
+    return step_lds<true>(nJ_max, nM_max, J) <= TRS_LDS_BYTES;
+}
+
+int trs_mw_step(int B, int L, int J, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* E,
+                double* A, const double* rho, const int32_t* free_index, const int32_t* n_free, const int32_t* nJ,
+                const int32_t* nM, const double* F, int ld_f, const int32_t* info, const int32_t* limit_case,
+                const int32_t* limit_joint, const double* limit_dir, const double* limit_value, int measure, double move,
+                double tol, double limit_tol, int sweeps, const double* a_min, double a_min_all, const double* a_max,
+                double a_max_all, int it, int mode, double* prev, double* mu, int32_t* st, int32_t* active, double* areas,
+                double* measure_out, double* measure_history, double* worst_history, int H, double* displacement,
+                double* ratio, double* multipliers, double* sensitivity, void* stream) {
+    return step<false>(B, L, J, nJ_max, nM_max, xyz, conn, E, A, rho, free_index, n_free, nJ, nM, F, ld_f, info, limit_case,
+                       limit_joint, limit_dir, limit_value, measure, move, tol, limit_tol, sweeps, a_min, a_min_all, a_max,
+                       a_max_all, it, mode, prev, mu, st, active, areas, measure_out, measure_history, worst_history, H,
+                       displacement, ratio, multipliers, sensitivity, {}, stream);
+}
+
+int trs_mw_step_stress(int B, int L, int J, int nJ_max, int nM_max, const double* xyz, const int32_t* conn, const double* E,
+                       double* A, const double* rho, const int32_t* free_index, const int32_t* n_free, const int32_t* nJ,
+                       const int32_t* nM, const double* F, int ld_f, const int32_t* info, const int32_t* limit_case,
+                       const int32_t* limit_joint, const double* limit_dir, const double* limit_value, int measure,
+                       double move, double tol, double limit_tol, int sweeps, const double* a_min, double a_min_all,
+                       const double* a_max, double a_max_all, double allow_tension, double allow_compression,
+                       const double* allow, double euler_kappa, int it, int mode, double* prev, double* mu, int32_t* st,
+                       int32_t* active, double* areas, double* measure_out, double* measure_history, double* worst_history,
+                       int H, double* displacement, double* ratio, double* multipliers, double* sensitivity,
+                       double* utilisation, int32_t* governing, double* stress_history, void* stream) {
+    if (!allow && (!(allow_tension > 0.0) || !(allow_compression > 0.0))) return (int)hipErrorInvalidValue;
+    if (!(euler_kappa >= 0.0) || !(euler_kappa < INFINITY)) return (int)hipErrorInvalidValue;
+    if (B > 0 && (!utilisation || !governing || (H > 0 && !stress_history))) return (int)hipErrorInvalidValue;
+    const StressIO s = {allow_tension, allow_compression, euler_kappa, allow, utilisation, governing, stress_history};
+    return step<true>(B, L, J, nJ_max, nM_max, xyz, conn, E, A, rho, free_index, n_free, nJ, nM, F, ld_f, info, limit_case,
+                      limit_joint, limit_dir, limit_value, measure, move, tol, limit_tol, sweeps, a_min, a_min_all, a_max,
+                      a_max_all, it, mode, prev, mu, st, active, areas, measure_out, measure_history, worst_history, H,
+                      displacement, ratio, multipliers, sensitivity, s, stream);
 }
 
 }  // extern "C"

@@ -749,7 +749,8 @@ class Truss:
                 "objective_history": result.objective_history[0].copy()}
 
     def MinimizeWeight(self, loadCases=None, limits=None, measure="weight", move=0.2, areaMin=None, areaMax=None, tol=1e-4,
-                       maxIters=60, sweeps=2, limitTol=1e-2, returnSensitivity=False):
+                       maxIters=60, sweeps=2, limitTol=1e-2, returnSensitivity=False, allowTension=None,
+                       allowCompression=None, eulerKappa=0.0):
         """The lightest areas of this truss whose named joint displacements stay within named limits: minimum-weight
         sizing by the optimality-criteria method with one multiplier per limit (`batch.solve_min_weight`), starting from
         the members' own areas.  `loadCases` is a list of `{jointID: vector}` dicts as `SolveLoadCases` takes them (None:
@@ -763,6 +764,11 @@ class Truss:
           "iterations", "status" (0 converged within its limits, 1 iteration limit, 2 a design could not be factored, 3
           converged on its bounds without meeting a limit), "measure_history", "worst_history" [maxIters + 1] and - with
           `returnSensitivity` - "sensitivity" [J, nM] (minus the derivative of every limited displacement by every area).
+        `allowTension`, `allowCompression` (both or neither, > 0; +inf switches a side off) and `eulerKappa` >= 0 (I =
+        kappa A^2; 0: no member buckling term) add stress limits to the same run, as `SizeMembers` takes them: the dict
+        then also holds "utilisation" [nM] (required area / area; <= 1 is feasible), "governing" [nM] (the load case
+        that sets a member's requirement, -1: none) and "stress_history" [maxIters + 1], and status 0 asks the
+        utilisation too for <= 1 + `limitTol`.
         The truss's own members, loads and solved state stay as they are.  Raises ValueError for bad arguments (as
         `batch.solve_min_weight`) and `TrussNotStableError` when the counting test fails."""
         if not self.isStable:
@@ -794,7 +800,8 @@ class Truss:
         result = solve_min_weight(packed, loads, limit_case=[r[0] for r in rows], limit_joint=[r[1] for r in rows],
                                   limit_direction=[r[2] for r in rows], limit_value=[r[3] for r in rows], measure=measure,
                                   move=move, area_min=bound(areaMin), area_max=bound(areaMax), tol=tol, max_iters=maxIters,
-                                  sweeps=sweeps, limit_tol=limitTol, want_sensitivity=returnSensitivity)
+                                  sweeps=sweeps, limit_tol=limitTol, want_sensitivity=returnSensitivity,
+                                  allow_tension=allowTension, allow_compression=allowCompression, euler_kappa=eulerKappa)
         out = {"areas": result.areas[0, :nM].copy(), "measure": float(result.measure[0]),
                "displacement": result.displacement[0].copy(), "ratio": result.ratio[0].copy(),
                "multipliers": result.multipliers[0].copy(), "iterations": int(result.iterations[0]),
@@ -802,6 +809,9 @@ class Truss:
                "worst_history": result.worst_history[0].copy()}
         if returnSensitivity:
             out["sensitivity"] = result.sensitivity[0, :, :nM].copy()
+        if result.utilisation is not None:
+            out.update(utilisation=result.utilisation[0, :nM].copy(), governing=result.governing[0, :nM].copy(),
+                       stress_history=result.stress_history[0].copy())
         return out
 
     def SolveUnilateral(self, kinds, cases=None, slackFactor=0.0, maxIters=20):
